@@ -13,18 +13,26 @@ Workload (BASELINE.json: "inverse images/sec + fwd+logdet ms/img, 3x3 conv @64x6
 init rule (layers/conv.py:63-79).  A step = one pass of the hot path over one batch resident in HBM:
 `unit.reverse(z)`, the module's public call (allocation of the result included; one launch of the MFMA
 wavefront kernel).  The timed region is exactly K such steps between barrier + torch.cuda.synchronize();
-value = images solved by all ranks / max-over-ranks time.  The forward (+logdet, identically 0) is timed the
-same way right after and reported next to it, and so is the inverse on z ~ N(0,1) (the sampling distribution,
-train/losses.py:42-45).
+value = images solved by all ranks / max-over-ranks time, ms_per_step = that time / K.
+
+A plain run does only what `value` needs: set-up, the untimed spin-up and W warmup steps, the K timed steps, the
+outputs (--dump-outputs) and the JSON line (`launch` and `roofline` come from the same K steps' HIP events).  Every other
+leg runs under `--full` only: the forward (+logdet, identically 0) timed the same way and reported next to the inverse, the
+inverse on z ~ N(0,1) (the sampling distribution, train/losses.py:42-45), the training step, `strong_share`, `clock`,
+board power and `cpu_baseline` -- with `--full` the line is the one every earlier round reported.
+
+`--dump-outputs DIR` writes what the timed path returned in its last step (rank 0) as DIR/<name>.npy, float32 (float64 stays
+float64), at most DUMP_BUDGET_BYTES in all: beyond that a fixed, seeded sample of whole images along the batch dimension, the
+line's `outputs` says which.  Inputs and weights are seeded, so two builds run with the same arguments compare output for output.
 
 Images are independent, so ranks shard the batch with no data-path collective; the only RCCL traffic is one broadcast of
 the layer's weights before the timed region.  `--scaling weak` (default: what the driver's 1/2/4/8 run measures) keeps the
 per-GPU batch fixed; `--scaling strong` keeps the GLOBAL batch of the workload fixed and gives every rank B/N images -- the
 split SURVEY 8(e) worries about (c3: 32 images = 128 problems per GPU at N = 8, fewer problems than compute units).  The
-N = 1 line also carries `strong_share`: the time of ONE GPU on the share B/P it would get at P = 2, 4, 8 (a single-GPU
+N = 1 line of --full also carries `strong_share`: the time of ONE GPU on the share B/P it would get at P = 2, 4, 8 (a single-GPU
 measurement of the per-GPU work of a strong split, NOT a multi-GPU measurement).
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (cpu_baseline: --full):
   roofline      dominant kernel (inverse): algorithmic bytes per launch (8*E + 4*C*Cq*KH*KW)
                 / mean launch duration from HIP events on the launch stream, vs 8 TB/s HBM peak; `traffic`
                 = HBM bytes per launch from rocprofv3 PMC passes (profiles/traffic_*.json; a profiler pass, not
@@ -35,7 +43,7 @@ Extra objects on the JSON line:
                 build container, because the compiled reference never travels -- the reference's own rate and the
                 port / reference ratio on one core there.
 
-Self-diagnosis (round 4): every leg carries the board power read from sysfs while it ran (`power_w`), and the `clock` object
+Self-diagnosis (round 4; --full): every leg carries the board power read from sysfs while it ran (`power_w`), and the `clock` object
 re-runs the two inverse legs -- z = forward(x) and z ~ N(0,1) -- in both orders with a one-wave clock probe beside them
 (include/finc.h: finc_debug_clock_probe_*): the shader clock each leg actually ran at.  `config.library` / `config.runtime_switches`
 say which library file ran and that no A/B switch was in effect (a judged line is refused otherwise).
@@ -43,6 +51,7 @@ say which library file ran and that no A/B switch was in effect (a judged line i
 `--workload ref_timing` reproduces the one protocol the reference publishes numbers for (fastflow/timing_comparision.py:10-14,
 fastflow/test_layers.py:1624-1693): `sample(100)` of the FInC stack (num_blocks=2, block_size=16, actnorm, split prior) at seven
 image sizes, 1 warm-up + mean of 10, wall clock, and prints them beside the published seconds (unstated NVIDIA GPU, CUDA 10.2).
+It is a protocol of its own (its step count is the protocol's, not --steps) and runs the same with or without --full.
 
 FINC_BENCH_STUB=1 replaces the step by a host-only stand-in (no GPU, no HIP library): it exists so that the
 launcher / rendezvous / gather logic is covered by a CPU test (tests/test_bench_launcher.py), never for numbers.
@@ -85,6 +94,8 @@ NOT_BASELINE = {"w512": "not a BASELINE config (a bank outside the register-resi
                 "c3_b320": "not a BASELINE config (configs[2]'s layer at 320 images: one round of the wavefront kernel + a remainder launch)"}
 # single-thread CPU sample sizes (images): about 10-20 s of host work per workload
 CPU_SAMPLE_1T = {"c3": 160, "c2": 64, "c5": 3, "c3_share8": 32, "w512": 8, "c3_b320": 160}
+# --dump-outputs: bytes written in all (c3: 32 of the 256 images)
+DUMP_BUDGET_BYTES = 48 << 20
 
 
 def parse(argv=None):
@@ -104,6 +115,11 @@ def parse(argv=None):
     ap.add_argument("--no-share", action="store_true",
                     help="skip the strong_share legs (profile runs: they launch other variants of the inverse kernel)")
     ap.add_argument("--master-port", type=int, default=None, help="rendezvous port when this process starts the ranks")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (forward, sampling, training step, strong_share, clock, power, "
+                         "CPU baseline; c4: hot_path_share); a plain run times the headline step only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step (rank 0) as DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -259,7 +275,8 @@ class Harness:
             # rank drives its own card -- two ranks on one device would halve each rank's throughput and still "scale"
             assert dist.get_world_size() == args.gpus == self.world, (dist.get_world_size(), args.gpus, self.world)
         self.devices = self.gather_devices()
-        self.sensors = None if stub else Sensors(torch, self.dev)
+        self.sensors = None if stub or not args.full else Sensors(torch, self.dev)      # (board power: --full only)
+        self.last_sensors = None
         self.spin_up_s = 0.0 if stub else 0.25
 
     def gather_devices(self):
@@ -300,10 +317,11 @@ class Harness:
                 fn()
             self.sync()
 
-    def timed(self, fn, steps, warmup):
+    def timed(self, fn, steps, warmup, tail=None):
         """W untimed steps, then exactly K steps between barrier+synchronize; per-launch durations from HIP events on
         the launch stream (torch's current stream IS the stream the ABI call launches on).  Returns the max-over-ranks
-        wall time, every rank's wall time and the sorted per-launch milliseconds of this rank."""
+        wall time, every rank's wall time and the sorted per-launch milliseconds of this rank.  `tail` (default `fn`) is
+        what keeps the card busy while the sensors are read behind the region, so that `fn` can keep its last step's result."""
         torch = self.torch
         if self.sensors is not None and not self.stub:
             self.sensors.start()
@@ -338,7 +356,7 @@ class Harness:
                 t1 = time.perf_counter()
                 self.sensors.quiet(False)
                 while time.perf_counter() - t1 < 0.012:
-                    fn()
+                    (tail or fn)()
                     self.sync()
             self.last_sensors = self.sensors.stop(t0 + dt, None) if self.sensors is not None else None
             per = sorted(a.elapsed_time(b) for a, b in evs)
@@ -385,6 +403,37 @@ def launch_stats(per):
     n = len(per)
     pick = lambda f: per[min(n - 1, max(0, int(round(f * (n - 1)))))]
     return {"mean_ms": sum(per) / n, "median_ms": pick(0.5), "p10_ms": pick(0.1), "p90_ms": pick(0.9)}
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array of `arrays` ({name: tensor or ndarray, batch dimension first}) as out_dir/<name>.npy, float64
+    kept, everything else as float32.  An array above its share of DUMP_BUDGET_BYTES keeps a fixed, seeded sample of whole
+    images (rows of the batch dimension, in batch order), taken on the device before the copy to the host.  Returns the line's
+    `outputs` object."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // len(arrays)
+    files = {}
+    for name, a in arrays.items():
+        n = int(a.shape[0])
+        f64 = str(a.dtype).endswith("float64")
+        per = int(np.prod(a.shape[1:], dtype=np.int64)) * (8 if f64 else 4)
+        keep = min(n, share // per)
+        if keep < 1:
+            raise SystemExit(f"--dump-outputs: one image of `{name}` ({per} bytes) exceeds the budget of {share} bytes")
+        idx = None if keep == n else np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        if hasattr(a, "detach"):                               # a torch tensor: sample where it lies, then copy
+            t = a.detach()
+            if idx is not None:
+                import torch
+                t = t.index_select(0, torch.as_tensor(idx, device=t.device))
+            arr = (t.double() if f64 else t.float()).cpu().numpy()
+        else:
+            arr = np.asarray(a if idx is None else a[idx], dtype=np.float64 if f64 else np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        files[name] = {"file": name + ".npy", "shape": list(arr.shape), "dtype": str(arr.dtype), "of_shape": [int(s) for s in a.shape],
+                       "batch_index": "all" if idx is None else [int(i) for i in idx]}
+    return {"dir": out_dir, "what": "the timed path's result in its last timed step", "files": files}
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -508,8 +557,9 @@ def bench_stack(args):
     its own replica of the model (weights broadcast once; sampling needs no collective).  A step = model.sample(n),
     replayed from one HIP graph when capture succeeds.  The reference's published whole-stack numbers
     (timing_comparision.py:10-14) are for a different stack size and batch 100, so vs_baseline stays null.  The step is
-    mostly NOT the hot path: `hot_path_share` says what fraction of the kernel time of one pass the finc_* kernels are
-    (profiles/r02/c4_kernel_stats.csv)."""
+    mostly NOT the hot path: `hot_path_share` (--full: one eager pass of its own) says what fraction of the kernel time of one
+    pass the finc_* kernels are (profiles/r02/c4_kernel_stats.csv).  No --dump-outputs: every sample draws from the prior's
+    generator, whose state at the last step depends on how many launches the time-bounded spin-up made."""
     os.environ.setdefault("MIOPEN_FIND_MODE", "2")   # coupling-net convs: heuristics, not an exhaustive find per shape
     h = Harness(args, stub=False)
     import numpy as np
@@ -547,7 +597,8 @@ def bench_stack(args):
         fn = (lambda: graph.replay()) if graph is not None else (lambda: model.sample(n))
         dt, ranks, per = h.timed(fn, args.steps, args.warmup)
         finite = bool(torch.isfinite(s).all())
-        share = hot_path_share(torch, lambda: model.sample(n), launch_stats(per)["mean_ms"] if graph is not None else None)
+        share = (hot_path_share(torch, lambda: model.sample(n), launch_stats(per)["mean_ms"] if graph is not None else None)
+                 if args.full else None)
     units = sum(isinstance(m, FastFlowUnit) for m in model)
     from fincflow_amd import _lib as _lq
     switches, libinfo = _lq.runtime_switches(), _lq.library_info()
@@ -566,7 +617,7 @@ def bench_stack(args):
                        "parallelism": f"batch-sharded x{world}, no collective on the data path",
                        "world_size_seen": world, "backend": h.backend, "per_rank_ms": [r * 1e3 for r in ranks],
                        "rank_devices": h.devices, "library": libinfo, "runtime_switches": switches,
-                       "hot_path_share": share},
+                       "hot_path_share": share, "full": args.full},
             "launch": launch_stats(per), "power": h.last_sensors, "roofline": None, "cpu_baseline": None}), flush=True)
     h.finish()
 
@@ -607,7 +658,7 @@ def bench_ref_timing(args):
     metric is quoted at -- and `vs_baseline` = value / published seconds (time-like: below 1 is faster).  Context for the
     north star's "reported wall-clock", NOT a same-hardware comparison: the published numbers are from an unnamed NVIDIA GPU.
     Eager, exactly as the protocol runs it (one Python call per layer); the same pass replayed from one HIP graph is reported
-    beside it."""
+    beside it.  --dump-outputs: the last eager sample(100) of the last size (every size starts from torch.manual_seed(0))."""
     os.environ.setdefault("MIOPEN_FIND_MODE", "2")
     h = Harness(args, stub=False)
     if h.world != 1:
@@ -634,6 +685,7 @@ def bench_ref_timing(args):
                 if i:
                     times.append(time.perf_counter() - t0)
             eager = sum(times) / len(times)
+            last_eager = s                                 # (--dump-outputs: the protocol's own last eager sample)
             graph_s = None
             try:
                 g = torch.cuda.CUDAGraph()
@@ -668,6 +720,7 @@ def bench_ref_timing(args):
     switches, libinfo = _lib.runtime_switches(), _lib.library_info()
     refuse_switches(args, switches, libinfo)
     last = rows[-1]
+    outputs = dump_outputs(args.dump_outputs, {"samples": last_eager}) if args.dump_outputs else None
     print(json.dumps({
         "metric": "seconds per sample(100), FInC stack (num_blocks=2, block_size=%d) at 3x64x64 -- the reference's timing protocol" % bs,
         "value": last["seconds_eager"], "unit": "s", "n_gpus": 1, "steps": n_loops, "warmup": 1,
@@ -680,7 +733,7 @@ def bench_ref_timing(args):
                    "comparison": "context for the bar, NOT a same-node comparison: the published seconds are from other, unnamed "
                                  "hardware; vs_baseline = value / published (below 1 = faster)",
                    "library": libinfo, "runtime_switches": switches},
-        "sweep": rows, "roofline": None, "cpu_baseline": None}), flush=True)
+        "sweep": rows, "roofline": None, "cpu_baseline": None, **({"outputs": outputs} if outputs else {})}), flush=True)
     h.finish()
 
 
@@ -693,11 +746,15 @@ def bench_stub(args):
     B = 4 // h.world if args.scaling == "strong" else 4      # (strong: the global batch is fixed, every rank owns B / N)
     a = np.random.default_rng(h.rank).standard_normal((B, 64, 64))
 
+    keep = {}
+
     def fn():
-        np.linalg.norm(a @ a.transpose(0, 2, 1))
+        keep["p"] = a @ a.transpose(0, 2, 1)
+        np.linalg.norm(keep["p"])
 
     dt, ranks, per = h.timed(fn, args.steps, args.warmup)
     if h.rank == 0:
+        outputs = dump_outputs(args.dump_outputs, {"product": keep["p"]}) if args.dump_outputs else None
         print(json.dumps({"metric": "stub steps/s (host-only stand-in: launcher test, not a measurement)",
                           "value": h.world * B * args.steps / dt, "unit": "images/s", "n_gpus": h.world,
                           "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
@@ -706,7 +763,8 @@ def bench_stub(args):
                                                      "global_batch": B * h.world,
                                                      "world_size_seen": h.world, "per_rank_ms": [r * 1e3 for r in ranks],
                                                      "rank_devices": h.devices},
-                          "launch": launch_stats(per), "roofline": None, "cpu_baseline": None}), flush=True)
+                          "launch": launch_stats(per), "roofline": None, "cpu_baseline": None,
+                          **({"outputs": outputs} if outputs else {})}), flush=True)
     h.finish()
 
 
@@ -766,7 +824,7 @@ def bench_unit(args):
         broadcast_weights(unit, src=0)
     gen = torch.Generator(device=dev).manual_seed(1000 + rank)  # each rank owns different images
     x = torch.randn(B, C, H, W, device=dev, generator=gen)
-    zn = torch.randn(B, C, H, W, device=dev, generator=gen)     # the sampling distribution
+    zn = torch.randn(B, C, H, W, device=dev, generator=gen) if args.full else None   # the sampling distribution (--full)
     with torch.no_grad():
         z, logdet = unit(x)
         xr = unit.reverse(z)                      # also builds the packed-fragment cache
@@ -783,62 +841,64 @@ def bench_unit(args):
         keep["xs"] = unit.reverse(zn)
 
     with torch.no_grad():
-        inv_dt, inv_ranks, inv_per = h.timed(step_inverse, args.steps, args.warmup)
+        inv_dt, inv_ranks, inv_per = h.timed(step_inverse, args.steps, args.warmup, tail=lambda: unit.reverse(z))
         inv_sens = h.last_sensors
-        fwd_dt, _, fwd_per = h.timed(lambda: unit(x), args.steps, args.warmup)
-        fwd_sens = h.last_sensors
-        smp_dt, _, smp_per = h.timed(step_sampling, args.steps, args.warmup)
-        smp_sens = h.last_sensors
-        # Clock diagnosis: the two inverse legs launch the SAME kernel; on one driver box they differed by
-        # 27 %.  Both legs again, in both orders, each with the shader clock it really ran at (one-wave probe beside it) and
-        # the board power: a swing that follows the clock is DVFS (data-dependent power), one that does not is stalls.
-        clock = None
-        if world == 1 and not args.no_clock:
-            legs = []
-            k = max(args.steps, 50)                        # (>= 20 ms per leg: the probe samples every 0.1 ms)
-            for order, name, fn in ((1, "round_trip", step_inverse), (1, "sampling", step_sampling),
-                                    (2, "sampling", step_sampling), (2, "round_trip", step_inverse)):
-                ls, probe, sens = h.probed(fn, k, 5)
-                legs.append({"leg": name, "order": order, "launch": ls, "sclk_mhz": probe["mean_mhz"], "sclk": probe,
-                             "power_w": sens["power_w"], "sensors": sens,
-                             "cycles_per_launch": ls["mean_ms"] * 1e-3 * probe["mean_mhz"] * 1e6 if probe["mean_mhz"] else None})
-            by = lambda nm, key: [l[key] for l in legs if l["leg"] == nm and l[key]]
-            mean = lambda v: sum(v) / len(v) if v else None
-            rt_ms, sm_ms = mean([l["launch"]["mean_ms"] for l in legs if l["leg"] == "round_trip"]), mean([l["launch"]["mean_ms"] for l in legs if l["leg"] == "sampling"])
-            rt_clk, sm_clk = mean(by("round_trip", "sclk_mhz")), mean(by("sampling", "sclk_mhz"))
-            rt_cyc, sm_cyc = mean(by("round_trip", "cycles_per_launch")), mean(by("sampling", "cycles_per_launch"))
-            clock = {"what": "the two inverse legs (same kernel) re-run in both orders, each with a one-wave clock probe beside it "
-                             "(d s_memtime / d s_memrealtime x 100 MHz, sampled every 0.1 ms) and the board power from sysfs; "
-                             "diagnostic legs, not `value`",
-                     "legs": legs,
-                     "sampling_over_round_trip": {"time": sm_ms / rt_ms if rt_ms else None,
-                                                  "clock": sm_clk / rt_clk if (rt_clk and sm_clk) else None,
-                                                  "cycles": sm_cyc / rt_cyc if (rt_cyc and sm_cyc) else None},
-                     "reading": "time ratio ~ 1/clock ratio with equal cycles: the swing is the clock (DVFS on data-dependent power); "
-                                "cycles ratio > 1: the kernel itself stalls on that data"}
-        err_after = float((keep["x"] - x).abs().max() / x.abs().max())
-        resid = float((unit(keep["xs"])[0] - zn).abs().max() / zn.abs().max())
+        x_last = keep["x"]                                 # what the timed path returned in its last timed step
+        err_after = float((x_last - x).abs().max() / x.abs().max())
     assert err_after <= 1e-5, err_after
-    assert resid <= 1e-5, resid
-    # SURVEY 8 f1, reported beside the metric (not part of `value`): the layer's training step -- forward, grad-input and
-    # grad-weight (+ the fused corner-tap mask) through autograd, gradients reset every step
-    xg = x.detach().clone().requires_grad_(True)
-    gz = torch.randn_like(z)
+    clock = strong_share = None
+    if args.full:
+        with torch.no_grad():
+            fwd_dt, _, fwd_per = h.timed(lambda: unit(x), args.steps, args.warmup)
+            fwd_sens = h.last_sensors
+            smp_dt, _, smp_per = h.timed(step_sampling, args.steps, args.warmup)
+            smp_sens = h.last_sensors
+            # Clock diagnosis: the two inverse legs launch the SAME kernel; on one driver box they differed by
+            # 27 %.  Both legs again, in both orders, each with the shader clock it really ran at (one-wave probe beside it) and
+            # the board power: a swing that follows the clock is DVFS (data-dependent power), one that does not is stalls.
+            if world == 1 and not args.no_clock:
+                legs = []
+                k = max(args.steps, 50)                        # (>= 20 ms per leg: the probe samples every 0.1 ms)
+                for order, name, fn in ((1, "round_trip", step_inverse), (1, "sampling", step_sampling),
+                                        (2, "sampling", step_sampling), (2, "round_trip", step_inverse)):
+                    ls, probe, sens = h.probed(fn, k, 5)
+                    legs.append({"leg": name, "order": order, "launch": ls, "sclk_mhz": probe["mean_mhz"], "sclk": probe,
+                                 "power_w": sens["power_w"], "sensors": sens,
+                                 "cycles_per_launch": ls["mean_ms"] * 1e-3 * probe["mean_mhz"] * 1e6 if probe["mean_mhz"] else None})
+                by = lambda nm, key: [l[key] for l in legs if l["leg"] == nm and l[key]]
+                mean = lambda v: sum(v) / len(v) if v else None
+                rt_ms, sm_ms = mean([l["launch"]["mean_ms"] for l in legs if l["leg"] == "round_trip"]), mean([l["launch"]["mean_ms"] for l in legs if l["leg"] == "sampling"])
+                rt_clk, sm_clk = mean(by("round_trip", "sclk_mhz")), mean(by("sampling", "sclk_mhz"))
+                rt_cyc, sm_cyc = mean(by("round_trip", "cycles_per_launch")), mean(by("sampling", "cycles_per_launch"))
+                clock = {"what": "the two inverse legs (same kernel) re-run in both orders, each with a one-wave clock probe beside it "
+                                 "(d s_memtime / d s_memrealtime x 100 MHz, sampled every 0.1 ms) and the board power from sysfs; "
+                                 "diagnostic legs, not `value`",
+                         "legs": legs,
+                         "sampling_over_round_trip": {"time": sm_ms / rt_ms if rt_ms else None,
+                                                      "clock": sm_clk / rt_clk if (rt_clk and sm_clk) else None,
+                                                      "cycles": sm_cyc / rt_cyc if (rt_cyc and sm_cyc) else None},
+                         "reading": "time ratio ~ 1/clock ratio with equal cycles: the swing is the clock (DVFS on data-dependent power); "
+                                    "cycles ratio > 1: the kernel itself stalls on that data"}
+            resid = float((unit(keep["xs"])[0] - zn).abs().max() / zn.abs().max())
+        assert resid <= 1e-5, resid
+        # SURVEY 8 f1, reported beside the metric (not part of `value`): the layer's training step -- forward, grad-input and
+        # grad-weight (+ the fused corner-tap mask) through autograd, gradients reset every step
+        xg = x.detach().clone().requires_grad_(True)
+        gz = torch.randn_like(z)
 
-    def step_train():
-        xg.grad = None
-        for p_ in unit.parameters():
-            p_.grad = None
-        zz, _ = unit(xg)
-        zz.backward(gz)
+        def step_train():
+            xg.grad = None
+            for p_ in unit.parameters():
+                p_.grad = None
+            zz, _ = unit(xg)
+            zz.backward(gz)
 
-    tr_steps = min(args.steps, 20)
-    tr_dt, _, tr_per = h.timed(step_train, tr_steps, 3)
-    del xg, gz
+        tr_steps = min(args.steps, 20)
+        tr_dt, _, tr_per = h.timed(step_train, tr_steps, 3)
+        del xg, gz
 
     # the per-GPU work of a STRONG split, measured on this one GPU: the share B/P of the workload's batch for P = 2, 4, 8
-    strong_share = None
-    if world == 1 and args.scaling == "weak" and not args.no_share:
+    if args.full and world == 1 and args.scaling == "weak" and not args.no_share:
         from fincflow_amd import _lib as _l
         strong_share = {"what": "one GPU on the batch share Bw/P it would own in a P-way strong split of the workload's batch "
                                 "(single-GPU measurement of the per-GPU work, NOT a multi-GPU measurement)",
@@ -878,8 +938,8 @@ def bench_unit(args):
         # (5x5: F(2,5) = 6 frequencies x 5 row taps per 2 outputs: 3/5)
         fwd_flops = (alg_flops * 2 // 3 if conv_form == "winograd" else alg_flops // 2 if conv_form in ("winograd4", "winograd4m")
                      else alg_flops * 3 // 5 if conv_form == "winograd25" else alg_flops)
-        inv, fwd, smp = launch_stats(inv_per), launch_stats(fwd_per), launch_stats(smp_per)
-        inv_launch_ms, fwd_launch_ms = inv["mean_ms"], fwd["mean_ms"]
+        inv = launch_stats(inv_per)
+        inv_launch_ms = inv["mean_ms"]
         inv_gbs = alg_bytes / (inv_launch_ms * 1e-3) / 1e9
         traffic = load_traffic(args.workload)
         P = min(16, W)
@@ -909,35 +969,10 @@ def bench_unit(args):
                        "per_gpu_batch": B, "global_batch": B * world, "parallelism": f"batch-sharded x{world}",
                        "world_size_seen": world, "backend": h.backend, "per_rank_ms": [r * 1e3 for r in inv_ranks],
                        "rank_devices": h.devices, "library": libinfo, "runtime_switches": switches,
-                       "round_trip_rel_err": err_after, "spin_up_s": h.spin_up_s, "hlp_timeouts": hlp_timeouts},
+                       "round_trip_rel_err": err_after, "spin_up_s": h.spin_up_s, "hlp_timeouts": hlp_timeouts,
+                       "full": args.full},
             "launch": inv,
             "power": inv_sens,
-            "sampling": {"what": "the same step on z ~ N(0,1) (train/losses.py:42-45)",
-                         "images_per_s": world * B * args.steps / smp_dt, "launch": smp, "power": smp_sens,
-                         "forward_residual_rel_err": resid,
-                         "note": "the conservative figure: the sampling distribution is the real use of the inverse, and on some "
-                                 "boxes this leg runs at a lower clock than the round-trip leg (see `clock`)"},
-            "forward": {"ms_per_img": fwd_dt / args.steps / B * 1e3, "images_per_s": world * B * args.steps / fwd_dt,
-                        "logdet": 0.0, "launch_ms": fwd_launch_ms, "launch": fwd, "power": fwd_sens,
-                        "kernel": conv_form,
-                        "frac_hbm_peak": alg_bytes / (fwd_launch_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                        "executed_flops_per_launch": fwd_flops,
-                        "frac_fp32_peak": fwd_flops / (fwd_launch_ms * 1e-3) / 1e12 / FP32_PEAK_TFLOPS,
-                        "direct_equivalent_frac_fp32_peak": alg_flops / (fwd_launch_ms * 1e-3) / 1e12 / FP32_PEAK_TFLOPS,
-                        "hbm_frac_ceiling_at_fp32": hbm_ceiling * alg_flops / fwd_flops,
-                        "note": f"fp32-compute-bound shape: at 100 % of the fp32 peak the direct sum reaches {hbm_ceiling:.0%} of "
-                                f"HBM peak" + (f"; the Winograd F(2,3) kernel executes 2/3 of the direct multiplies, which lifts "
-                                               f"that ceiling to {hbm_ceiling * 1.5:.0%}" if conv_form == "winograd" else
-                                               f"; the Winograd F(4,3) kernel executes 1/2 of the direct multiplies, which lifts "
-                                               f"that ceiling to {hbm_ceiling * 2:.0%}" if conv_form == "winograd4" else
-                                               f"; the Winograd F(2,5) kernel executes 3/5 of the direct multiplies, which lifts "
-                                               f"that ceiling to {hbm_ceiling / 0.6:.0%}" if conv_form == "winograd25" else "")},
-            "training_step": {"what": "z = unit(x); z.backward(gz): forward + grad-input + grad-weight with the corner-tap mask "
-                                      "(SURVEY 8 f1), HIP kernels under autograd", "ms_per_step": tr_dt / tr_steps * 1e3,
-                              "steps": tr_steps, "launch": launch_stats(tr_per),
-                              "grad_weight_kernel": bvar["gradw"],
-                              "frac_fp32_peak": (gw_flops + 2 * fwd_flops) / (tr_dt / tr_steps) / 1e12 / FP32_PEAK_TFLOPS,
-                              "direct_equivalent_frac_fp32_peak": 3 * alg_flops / (tr_dt / tr_steps) / 1e12 / FP32_PEAK_TFLOPS},
             "roofline": {"kernel": inverse_kernel_name(B, Cq, H, W, K), "bound": "hbm", "achieved": inv_gbs,
                          "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": inv_gbs / HBM_PEAK_GBS,
                          "traffic": (traffic or {}).get("inverse_hbm_bytes_per_launch"),
@@ -960,6 +995,37 @@ def bench_unit(args):
                                      "note": "shapes whose problems do not fill the chip (c2, the c4 units) are bound by "
                                              "dependent_steps x us_per_step, not by bandwidth"}},
         }
+        if args.full:
+            fwd, smp = launch_stats(fwd_per), launch_stats(smp_per)
+            fwd_launch_ms = fwd["mean_ms"]
+            line.update({
+                "sampling": {"what": "the same step on z ~ N(0,1) (train/losses.py:42-45)",
+                             "images_per_s": world * B * args.steps / smp_dt, "launch": smp, "power": smp_sens,
+                             "forward_residual_rel_err": resid,
+                             "note": "the conservative figure: the sampling distribution is the real use of the inverse, and on some "
+                                     "boxes this leg runs at a lower clock than the round-trip leg (see `clock`)"},
+                "forward": {"ms_per_img": fwd_dt / args.steps / B * 1e3, "images_per_s": world * B * args.steps / fwd_dt,
+                            "logdet": 0.0, "launch_ms": fwd_launch_ms, "launch": fwd, "power": fwd_sens,
+                            "kernel": conv_form,
+                            "frac_hbm_peak": alg_bytes / (fwd_launch_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                            "executed_flops_per_launch": fwd_flops,
+                            "frac_fp32_peak": fwd_flops / (fwd_launch_ms * 1e-3) / 1e12 / FP32_PEAK_TFLOPS,
+                            "direct_equivalent_frac_fp32_peak": alg_flops / (fwd_launch_ms * 1e-3) / 1e12 / FP32_PEAK_TFLOPS,
+                            "hbm_frac_ceiling_at_fp32": hbm_ceiling * alg_flops / fwd_flops,
+                            "note": f"fp32-compute-bound shape: at 100 % of the fp32 peak the direct sum reaches {hbm_ceiling:.0%} of "
+                                    f"HBM peak" + (f"; the Winograd F(2,3) kernel executes 2/3 of the direct multiplies, which lifts "
+                                                   f"that ceiling to {hbm_ceiling * 1.5:.0%}" if conv_form == "winograd" else
+                                                   f"; the Winograd F(4,3) kernel executes 1/2 of the direct multiplies, which lifts "
+                                                   f"that ceiling to {hbm_ceiling * 2:.0%}" if conv_form == "winograd4" else
+                                                   f"; the Winograd F(2,5) kernel executes 3/5 of the direct multiplies, which lifts "
+                                                   f"that ceiling to {hbm_ceiling / 0.6:.0%}" if conv_form == "winograd25" else "")},
+                "training_step": {"what": "z = unit(x); z.backward(gz): forward + grad-input + grad-weight with the corner-tap mask "
+                                          "(SURVEY 8 f1), HIP kernels under autograd", "ms_per_step": tr_dt / tr_steps * 1e3,
+                                  "steps": tr_steps, "launch": launch_stats(tr_per),
+                                  "grad_weight_kernel": bvar["gradw"],
+                                  "frac_fp32_peak": (gw_flops + 2 * fwd_flops) / (tr_dt / tr_steps) / 1e12 / FP32_PEAK_TFLOPS,
+                                  "direct_equivalent_frac_fp32_peak": 3 * alg_flops / (tr_dt / tr_steps) / 1e12 / FP32_PEAK_TFLOPS},
+            })
         if strong_share is not None:
             for sh in strong_share["shares"]:
                 sh["speedup_over_full_batch_implied"] = sh["implied_images_per_s_at_P"] / (B / (inv_launch_ms * 1e-3))
@@ -969,10 +1035,12 @@ def bench_unit(args):
         # the CPU baseline is an N = 1 measurement (rank 0 only); at N > 1 the object keeps its shape and says so
         line["cpu_baseline"] = {"value": None, "unit": "images/s", "cores": None, "kind": "port",
                                 "sample": "not measured in this run (the CPU baseline is taken at N = 1 only)" if world > 1
-                                else "skipped (--no-cpu)"}
-        if not args.no_cpu and world == 1:
+                                else "skipped (--no-cpu)" if args.full else "not measured in this run (it runs under --full)"}
+        if args.full and not args.no_cpu and world == 1:
             line["cpu_baseline"] = cpu_baseline(args.workload, B, C, H, W, K, std,
                                                 args.cpu_sample or CPU_SAMPLE_1T[args.workload])
+        if args.dump_outputs:
+            line["outputs"] = dump_outputs(args.dump_outputs, {"x": x_last})
         print(json.dumps(line), flush=True)
     h.finish()
 
@@ -982,6 +1050,9 @@ def main(argv=None):
     args = parse(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.dump_outputs and args.workload == "c4":
+        raise SystemExit("--dump-outputs: --workload c4 samples from the prior's generator, whose state at the last step is not "
+                         "fixed by the arguments (the spin-up is time-bounded); no output to compare")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args, argv)             # nothing above this line touches torch or the GPU
     if os.environ.get("FINC_BENCH_STUB") == "1":

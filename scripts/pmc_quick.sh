@@ -11,7 +11,7 @@ OUT=$ROOT/gpurun_out/pmc_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # PMC_PY=<script> profiles that script (with the arguments after --) instead of a short bench run
-if [ -n "$PMC_PY" ]; then CMD="$ROOT/$PMC_PY"; else CMD="$ROOT/bench.py --steps 5 --warmup 2 --no-cpu --no-share --no-clock"; fi
+if [ -n "$PMC_PY" ]; then CMD="$ROOT/$PMC_PY"; else CMD="$ROOT/bench.py --full --steps 5 --warmup 2 --no-cpu --no-share --no-clock"; fi
 for grp in "${GROUPS_[@]}"; do
   name=$(echo $grp | tr ' ' '_' | cut -c1-40)
   rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $OUT/$name -- python3 $CMD "$@" > $OUT/$name.log 2>&1 || echo "pass $name failed"

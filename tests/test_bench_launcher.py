@@ -72,3 +72,52 @@ def test_parent_does_not_import_torch_before_spawning():
     assert "import torch" not in head
     main_body = src[src.index("def main("):]
     assert main_body.index("launch_ranks(args, argv)") < main_body.index("bench_unit(args)")
+
+
+def test_dump_outputs_writes_the_last_step_and_repeats(tmp_path):
+    """--dump-outputs DIR: the timed path's last result as DIR/<name>.npy (float32 or float64), named in the line; the same
+    arguments give the same inputs, so two runs write the same arrays."""
+    import numpy as np
+    got = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = run_bench(["--gpus", "1", "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr
+        line = json_lines(r.stdout)[0]
+        assert line["steps"] == 5 and line["ms_per_step"] > 0
+        files = line["outputs"]["files"]
+        assert files and all((d / f["file"]).exists() for f in files.values())
+        arrays = {name: np.load(d / f["file"]) for name, f in files.items()}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 * 10**6
+        got.append(arrays)
+    assert got[0].keys() == got[1].keys() and all(np.array_equal(got[0][k], got[1][k]) for k in got[0])
+
+
+def test_dump_outputs_with_two_ranks(tmp_path):
+    r = run_bench(["--gpus", "2", "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json_lines(r.stdout)[0]
+    assert all((tmp_path / f["file"]).exists() for f in line["outputs"]["files"].values())
+
+
+def test_full_is_an_option_and_plain_is_the_default():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    plain = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert not plain.full and plain.dump_outputs is None and plain.steps == 7 and plain.warmup == 3
+    assert bench.parse(["--full"]).full
+    r = run_bench(["--gpus", "1", "--full"])
+    assert r.returncode == 0, r.stderr
+    assert json_lines(r.stdout)[0]["steps"] == 5
+
+
+def test_dump_outputs_refused_where_the_samples_are_not_reproducible(tmp_path):
+    """c4 samples from the prior's generator, whose state after the time-bounded spin-up is not fixed: refused up front."""
+    env = dict(os.environ)
+    env.pop("FINC_BENCH_STUB", None)
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--workload", "c4", "--dump-outputs", str(tmp_path)],
+                       env=env, capture_output=True, text=True, timeout=120, cwd=REPO)
+    assert r.returncode != 0 and "--dump-outputs" in r.stderr

@@ -141,17 +141,21 @@ def test_synthetic_weights_follow_reference_init():
 
 
 def test_against_live_reference_solver_if_built():
-    """When oracle/_ref holds the reference's rebuilt Cython module, compare directly on fresh data."""
+    """The reference's Cython solver on fresh data: its answer as recorded in tests/golden/solver_B2_C7_9x13_k3.npz
+    (tests/golden/make_golden_solver.py), and -- when oracle/_ref holds the rebuilt module -- the live solver as well."""
     from oracle import build_ref
-    solve_parallel = build_ref.load()
-    if solve_parallel is None:
-        pytest.skip("oracle/_ref not built (reference tree absent)")
+    g = golden("solver_B2_C7_9x13_k3")
     rng = np.random.default_rng(5)
     wc = oracle.make_stored_weights(1, 7, 3, 3, orient=0, seed=77)
     z = rng.standard_normal((2, 7, 9, 13)).astype(np.float32)
-    ref = solve_parallel(np.array(z, dtype=np.float64), np.array(wc, dtype=np.float64), (3, 3))
-    assert np.array_equal(oracle.inverse_f64(z, wc, 1), ref)
-    assert np.array_equal(oracle.inverse_via_f64(z, wc, 1, 0), ref.astype(np.float32))
+    assert np.array_equal(z, g["z"]) and np.array_equal(wc, g["wc"])      # the recorded inputs are this test's inputs
+    refs = [g["ref"]]
+    solve_parallel = build_ref.load()
+    if solve_parallel is not None:
+        refs.append(solve_parallel(np.array(z, dtype=np.float64), np.array(wc, dtype=np.float64), (3, 3)))
+    for ref in refs:
+        assert np.array_equal(oracle.inverse_f64(z, wc, 1), ref)
+        assert np.array_equal(oracle.inverse_via_f64(z, wc, 1, 0), ref.astype(np.float32))
 
 
 def test_openmp_threads_do_not_change_results():
