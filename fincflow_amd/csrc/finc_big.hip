@@ -752,12 +752,12 @@ size_t finc_bigfwd_packed_bytes(int G, int Cq, int KH, int KW)
     return i ? ((size_t)G * i->nwv * i->nreg * 64 + (size_t)G * Cq) * sizeof(float) : 0;
 }
 
-bool finc_bigfwd_takes(const float *in, const float *out, const FincShape &s)
+bool finc_bigfwd_takes(const FincShape &s, int align)
 {
     static const bool off = finc_env("FINC_NO_BIGFWD") != nullptr;           // A/B switch: the 8-wave K-split row of the strip kernel
     const BFInst *i = find_bfinst(s.Cq, s.KH, s.KW);
     if (!i || off || s.W % 4 != 0 || s.W < 4 || s.H < 1) return false;       // (16-byte pieces)
-    if (((uintptr_t)in | (uintptr_t)out) & 15u) return false;
+    if (align < 16) return false;
     return (size_t)s.Cq * s.H * s.W * 4 < ((size_t)1 << 30);
 }
 
@@ -779,7 +779,7 @@ int finc_bigfwd_pack(const float *wc, void *packed, int G, int Cq, int KH, int K
 int finc_bigfwd_launch(const float *in, const void *packed, float *out, const FincShape &s, hipStream_t st)
 {
     const BFInst *i = find_bfinst(s.Cq, s.KH, s.KW);
-    if (!i || !finc_bigfwd_takes(in, out, s)) return FINC_ERR_UNSUPPORTED;
+    if (!i || !finc_bigfwd_takes(s, finc_align(in, out))) return FINC_ERR_UNSUPPORTED;
     const int NS = (s.W + 15) / 16;
     const float *sh = (const float *)packed + (size_t)s.G * i->nwv * i->nreg * 64;
     hipLaunchKernelGGL(i->fn, dim3(s.B * s.G * NS), dim3(64 * i->nwv), 0, st, in, (const float *)packed, sh, out, s.G, s.Cq, s.H, s.W,

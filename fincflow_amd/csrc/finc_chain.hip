@@ -644,7 +644,7 @@ bool chain_off()
 extern "C" int finc_debug_chain_stamps(unsigned long long *h) { return (int)hipMemcpyFromSymbol(h, HIP_SYMBOL(finc_chain_stamps), sizeof(finc_chain_stamps)); }
 #endif
 
-// (the caller has established what finc_split_takes establishes: problems, W % 4 == 0, P >= KH - 1, slab < 1 GiB)
+// (the caller has established what finc_split_plan establishes: problems, W % 4 == 0, P >= KH - 1, slab < 1 GiB)
 bool finc_chain_takes(const FincShape &s)
 {
     if (chain_off()) return false;

@@ -111,6 +111,7 @@ bool finc_mfma_zpre_takes(const FincShape &s);
 // can an affine map with a SHIFT be folded into the bank this problem set runs on? (not on finc_big.hip's kernels: the big
 // banks and the wide-map takeover of the 33..64-channel banks carry a scale only)
 bool finc_mfma_affine_takes(const FincShape &s);
+bool finc_mfma_needs_align16(const FincShape &s);   // the kernel this problem set runs moves 16-byte pieces
 // info[0..7] = {Cq padded, waves per problem, problems per workgroup, 32-byte I/O (1) or 16-byte (0), LDS bytes of a
 // workgroup, workgroups, index into the instantiation table, rows of the table}; FINC_ERR_UNSUPPORTED if none applies
 int finc_mfma_variant(int B, int G, int Cq, int H, int W, int KH, int KW, int *info);
@@ -132,21 +133,28 @@ int finc_big_pack(const float *wc, const float *scale, const float *shift, void 
 int finc_big_info(const FincShape &s, int *waves, int *lds_bytes, int *cqp);
 int finc_big_launch(const float *in, const void *packed, float *out, const FincShape &s, hipStream_t st);
 size_t finc_bigfwd_packed_bytes(int G, int Cq, int KH, int KW);         // 0: no big-bank forward for this bank
-bool finc_bigfwd_takes(const float *in, const float *out, const FincShape &s);
+bool finc_bigfwd_takes(const FincShape &s, int align);
 int finc_bigfwd_pack(const float *wc, void *packed, int G, int Cq, int KH, int KW, bool transpose, hipStream_t st, const float *scale,
                      const float *shift);
 int finc_bigfwd_launch(const float *in, const void *packed, float *out, const FincShape &s, hipStream_t st);
 unsigned finc_build_flags_big();
-bool finc_split_takes(const FincShape &s);       // this problem set runs on the role-split kernel
-int finc_split_info(const FincShape &s, int *waves, int *lds_bytes, int *steps, int *nwg = nullptr);   // nwg: workgroups per problem (band split)
+// Which form of the role-split kernel a problem set takes, if any: the one place this is decided (finc_mfma.hip's inverse plan reads it,
+// finc_split_launch runs it; only a band split short of progress words falls back to the chained form at launch)
+struct FincSplitPlan {
+    bool takes = false;            // this problem set runs on the role-split kernel
+    bool chain = false;            // ... in its short-step form (finc_chain.hip)
+    int row = -1;                  // the role-split kernel's instantiation (-1: the short-step form's)
+    int nwg = 1;                   // workgroups per problem (band split)
+    int waves = 0, lds = 0, steps = 0;   // of a workgroup
+};
+FincSplitPlan finc_split_plan(const FincShape &s);
 int finc_split_prepare(hipStream_t st);          // allocates the band split's progress words for the current device (not inside a capture)
 int finc_split_timeouts_count(unsigned *count);  // progress waits of the band split that gave up (must be 0)
 unsigned *finc_fault_device_word();              // device pointer to the current device's (armed) fault word, or nullptr
-int finc_split_launch(const float *in, const void *packed, float *out, const FincShape &s, hipStream_t st);
+int finc_split_launch(const float *in, const void *packed, float *out, const FincShape &s, const FincSplitPlan &p, hipStream_t st);
 // finc_chain.hip: the short-step form of the same idea for the banks of up to 16 channels (output channels, not taps, shared out
-// over the preparing waves); finc_split_launch / finc_split_info hand over to it
-bool finc_chain_takes(const FincShape &s);        // (can run it; finc_split_uses_chain: does run it)
-bool finc_split_uses_chain(const FincShape &s);
+// over the preparing waves); finc_split_plan / finc_split_launch hand over to it
+bool finc_chain_takes(const FincShape &s);        // (can run it; finc_split_plan: does run it)
 int finc_chain_info(const FincShape &s, int *waves, int *lds_bytes, int *steps);
 int finc_chain_launch(const float *in, const void *packed, float *out, const FincShape &s, hipStream_t st);
 unsigned finc_build_flags_chain();
@@ -163,6 +171,12 @@ int finc_stream_launch(const float *in, const void *packed, float *out, const Fi
 unsigned finc_build_flags_stream();
 
 // ---- forward / grad-input, MFMA strip kernel: finc_conv.hip ----
+// bytes that both activations of a call are aligned to (16, 8 or 4): the `align` input of the forward kernels' *_takes
+inline int finc_align(const void *a, const void *b)
+{
+    const uintptr_t x = (uintptr_t)a | (uintptr_t)b;
+    return (x & 15u) == 0 ? 16 : (x & 7u) == 0 ? 8 : 4;
+}
 bool finc_conv_supported(int Cq, int H, int W, int KH, int KW);
 size_t finc_conv_packed_bytes(int G, int Cq, int KH, int KW);
 // scale / shift [G*Cq] or nullptr: z' = scale * conv(x) + shift folded into the bank (the affine layer BEHIND the conv)
@@ -172,7 +186,7 @@ int finc_conv_launch(const float *in, const void *packed, float *out, const Finc
 // ---- 3x3 forward / grad-input with 1.5x fewer multiplies (Winograd F(2,3) along W): finc_wino.hip; its bank sits behind the
 // strip kernels' in the packed buffer
 size_t finc_wino_packed_bytes(int G, int Cq, int KH, int KW);          // 0: no Winograd kernel for this bank
-bool finc_wino_takes(const float *in, const float *out, const FincShape &s);
+bool finc_wino_takes(const FincShape &s, int align);
 int finc_wino_pack(const float *wc, void *packed, int G, int Cq, bool transpose, hipStream_t st, const float *scale, const float *shift);
 int finc_wino_launch(const float *in, const void *packed, float *out, const FincShape &s, hipStream_t st);
 bool finc_wino_disabled();                                          // FINC_NO_WINO / finc_debug_set_forward_form(1)
@@ -180,7 +194,7 @@ int finc_wino_pack_bank(const float *wc, float *packed, int G, int Cq, int MT, i
                         const float *scale, const float *shift);
 // 3x3 banks of 28 .. 64 channels: F(4,3) along W, M-split over the waves of a workgroup (finc_wino4m.hip)
 size_t finc_wino4m_packed_bytes(int G, int Cq, int KH, int KW);        // 0: no such kernel for this bank
-bool finc_wino4m_takes(const float *in, const float *out, const FincShape &s);
+bool finc_wino4m_takes(const FincShape &s, int align);
 int finc_wino4m_pack(const float *wc, void *packed, int G, int Cq, bool transpose, hipStream_t st, const float *scale, const float *shift);
 int finc_wino4m_launch(const float *in, const void *packed, float *out, const FincShape &s, hipStream_t st);
 unsigned finc_build_flags_wino4m();
@@ -189,7 +203,7 @@ int finc_wino_set_form(int form);                                      // 0 libr
 unsigned finc_build_flags_wino();
 // ---- 5x5 forward / grad-input with 0.6 x the multiplies (Winograd F(2,5) along W): finc_wino5.hip; bank behind the strip kernels'
 size_t finc_wino5_packed_bytes(int G, int Cq, int KH, int KW);         // 0: no such kernel for this bank
-bool finc_wino5_takes(const float *in, const float *out, const FincShape &s);
+bool finc_wino5_takes(const FincShape &s, int align);
 int finc_wino5_pack(const float *wc, void *packed, int G, int Cq, bool transpose, hipStream_t st, const float *scale, const float *shift);
 int finc_wino5_launch(const float *in, const void *packed, float *out, const FincShape &s, hipStream_t st);
 unsigned finc_build_flags_wino5();

@@ -662,63 +662,84 @@ int finc_conv_pack(const float *wc, void *packed, int G, int Cq, int KH, int KW,
     return FINC_OK;
 }
 
-int finc_conv_launch(const float *in, const void *packed, float *out, const FincShape &s, hipStream_t st)
+// The launch plan of a forward / grad-input call: which kernel runs and, on the strip kernel, in how many row chunks.  conv_plan() is
+// the one place this is decided; finc_conv_launch and finc_conv_variant read it.  `align`: bytes both activations are aligned to
+// (finc_align; the variant query answers for 16).  `form` is the variant's info[1]: 0 strip kernel, 1 its 16-byte-piece form,
+// 2 Winograd F(2,3), 3 the big banks' M-split, 4 F(4,3), 5 F(2,5), 6 F(4,3) M-split, 7 the streaming bank; -1: none.
+struct ConvPlan {
+    int form = -1;
+    const ConvInst *i = nullptr;
+    int nrc = 1, RC = 0;         // strip kernel: row chunks, rows per chunk
+};
+static ConvPlan conv_plan(const FincShape &s, int align)
 {
-    if (stream_bank(s.Cq, s.KH, s.KW)) return finc_stream_launch(in, packed, out, s, false, st);
-    const ConvInst *i = find_conv(s.Cq, s.KH, s.KW);
-    if (!i || !finc_conv_supported(s.Cq, s.H, s.W, s.KH, s.KW)) return FINC_ERR_UNSUPPORTED;
+    ConvPlan p;
+    if (stream_bank(s.Cq, s.KH, s.KW)) {
+        if (finc_conv_supported(s.Cq, s.H, s.W, s.KH, s.KW)) p.form = 7;
+        return p;
+    }
+    p.i = find_conv(s.Cq, s.KH, s.KW);
+    if (!p.i || !finc_conv_supported(s.Cq, s.H, s.W, s.KH, s.KW)) return p;
+    // (each kernel below has its bank behind the strip kernels' in the packed buffer; at most one of them exists for a bank)
     // 3x3 with fewer multiplies (Winograd F(2,3) along W: finc_wino.hip) where the call allows it
-    if (finc_wino_packed_bytes(s.G, s.Cq, s.KH, s.KW) && finc_wino_takes(in, out, s))
-        return finc_wino_launch(in, (const char *)packed + conv_bank_bytes(i, s.G), out, s, st);
-    if (finc_bigfwd_packed_bytes(s.G, s.Cq, s.KH, s.KW) && finc_bigfwd_takes(in, out, s))
-        return finc_bigfwd_launch(in, (const char *)packed + conv_bank_bytes(i, s.G), out, s, st);
+    if (finc_wino_packed_bytes(s.G, s.Cq, s.KH, s.KW) && finc_wino_takes(s, align)) p.form = finc_wino_form(s) == 4 ? 4 : 2;
+    else if (finc_bigfwd_packed_bytes(s.G, s.Cq, s.KH, s.KW) && finc_bigfwd_takes(s, align)) p.form = 3;
     // 5x5 with 0.6 x the multiplies (Winograd F(2,5) along W: finc_wino5.hip) where the call allows it
-    if (finc_wino5_packed_bytes(s.G, s.Cq, s.KH, s.KW) && finc_wino5_takes(in, out, s))
-        return finc_wino5_launch(in, (const char *)packed + conv_bank_bytes(i, s.G), out, s, st);
+    else if (finc_wino5_packed_bytes(s.G, s.Cq, s.KH, s.KW) && finc_wino5_takes(s, align)) p.form = 5;
     // 3x3 banks of 25 .. 64 channels with half the multiplies (F(4,3), M-split over a workgroup's waves: finc_wino4m.hip)
-    if (finc_wino4m_packed_bytes(s.G, s.Cq, s.KH, s.KW) && finc_wino4m_takes(in, out, s))
-        return finc_wino4m_launch(in, (const char *)packed + conv_bank_bytes(i, s.G), out, s, st);
-    const int NS = (s.W + 15) / 16;
-    // row chunks of at least 4 rows: the count that minimises rounds x (rows per chunk + KH: every chunk recomputes KH-1 rows of operands
-    // and loads the bank once more), two waves per SIMD (finc_common.h finc_row_chunks; profiles/r05/notes/row_chunks.txt)
-    const long long waves = (long long)s.B * s.G * NS * i->nw;
-    int nrc = finc_row_chunks(waves, 1024, s.H, 4, s.KH, 14);
-    static const int force_chunks = finc_env("FINC_CONV_CHUNKS") ? atoi(finc_env("FINC_CONV_CHUNKS")) : 0;   // experiment switch
-    if (force_chunks > 0) nrc = force_chunks;
-    if (nrc > s.H / 4) nrc = s.H / 4 > 0 ? s.H / 4 : 1;
-    const int RC = (s.H + nrc - 1) / nrc;
-    nrc = (s.H + RC - 1) / RC;
-    static const bool no_wide = finc_env("FINC_CONV_NO_WIDE") != nullptr;   // experiment switch: the dword form everywhere
+    else if (finc_wino4m_packed_bytes(s.G, s.Cq, s.KH, s.KW) && finc_wino4m_takes(s, align)) p.form = 6;
+    if (p.form >= 0) return p;
     // the staged form moves 16-byte pieces: activations that are only float-aligned (a view into a larger tensor) take the
     // dword form, as the inverse sends them to its strict kernel
-    const bool aligned16 = (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
-    const conv_fn fn = (i->fn_wide && s.W % 16 == 0 && aligned16 && !no_wide) ? i->fn_wide : i->fn;
-    hipLaunchKernelGGL(fn, dim3(s.B * s.G * NS, nrc), dim3(64 * i->nw), 0, st, in, (const float *)packed, out, s.G, s.Cq,
-                       s.H, s.W, NS, RC, s.orient);
+    static const bool no_wide = finc_env("FINC_CONV_NO_WIDE") != nullptr;   // experiment switch: the dword form everywhere
+    p.form = (p.i->fn_wide && s.W % 16 == 0 && align >= 16 && !no_wide) ? 1 : 0;
+    // row chunks of at least 4 rows: the count that minimises rounds x (rows per chunk + KH: every chunk recomputes KH-1 rows of operands
+    // and loads the bank once more), two waves per SIMD (finc_common.h finc_row_chunks; profiles/r05/notes/row_chunks.txt)
+    const int NS = (s.W + 15) / 16;
+    const long long waves = (long long)s.B * s.G * NS * p.i->nw;
+    p.nrc = finc_row_chunks(waves, 1024, s.H, 4, s.KH, 14);
+    static const int force_chunks = finc_env("FINC_CONV_CHUNKS") ? atoi(finc_env("FINC_CONV_CHUNKS")) : 0;   // experiment switch
+    if (force_chunks > 0) p.nrc = force_chunks;
+    if (p.nrc > s.H / 4) p.nrc = s.H / 4 > 0 ? s.H / 4 : 1;
+    p.RC = (s.H + p.nrc - 1) / p.nrc;
+    p.nrc = (s.H + p.RC - 1) / p.RC;
+    return p;
+}
+
+int finc_conv_launch(const float *in, const void *packed, float *out, const FincShape &s, hipStream_t st)
+{
+    const ConvPlan p = conv_plan(s, finc_align(in, out));
+    const void *behind = p.i ? (const char *)packed + conv_bank_bytes(p.i, s.G) : nullptr;
+    switch (p.form) {
+    case -1: return FINC_ERR_UNSUPPORTED;
+    case 7: return finc_stream_launch(in, packed, out, s, false, st);
+    case 2:
+    case 4: return finc_wino_launch(in, behind, out, s, st);
+    case 3: return finc_bigfwd_launch(in, behind, out, s, st);
+    case 5: return finc_wino5_launch(in, behind, out, s, st);
+    case 6: return finc_wino4m_launch(in, behind, out, s, st);
+    }
+    const int NS = (s.W + 15) / 16;
+    hipLaunchKernelGGL(p.form == 1 ? p.i->fn_wide : p.i->fn, dim3(s.B * s.G * NS, p.nrc), dim3(64 * p.i->nw), 0, st, in,
+                       (const float *)packed, out, s.G, s.Cq, s.H, s.W, NS, p.RC, s.orient);
     FINC_CHECK_LAUNCH();
     return FINC_OK;
 }
 
 int finc_conv_variant(int B, int G, int Cq, int H, int W, int KH, int KW, int *info)
 {
-    if (stream_bank(Cq, KH, KW)) {              // (7: the streaming-bank kernel, one or four waves per problem)
-        if (!finc_conv_supported(Cq, H, W, KH, KW)) return FINC_ERR_UNSUPPORTED;
+    const FincShape s{B, G, Cq, H, W, KH, KW, 0};
+    const ConvPlan p = conv_plan(s, 16);
+    if (p.form < 0) return FINC_ERR_UNSUPPORTED;
+    if (p.form == 7) {                          // (the streaming-bank kernel, one or four waves per problem)
         int waves = 0;
-        (void)finc_stream_info(FincShape{B, G, Cq, H, W, KH, KW, 0}, false, nullptr, nullptr, nullptr, &waves);
+        (void)finc_stream_info(s, false, nullptr, nullptr, nullptr, &waves);
         info[0] = waves; info[1] = 7; info[2] = 1;
         return FINC_OK;
     }
-    const ConvInst *i = find_conv(Cq, KH, KW);
-    if (!i || !finc_conv_supported(Cq, H, W, KH, KW)) return FINC_ERR_UNSUPPORTED;
-    static const bool no_wide = finc_env("FINC_CONV_NO_WIDE") != nullptr;
-    info[0] = i->nw;
-    info[1] = (i->fn_wide && W % 16 == 0 && !no_wide) ? 1 : 0;
+    info[0] = p.i->nw;
+    info[1] = p.form;
     info[2] = (W + 15) / 16;
-    const FincShape s{B, G, Cq, H, W, KH, KW, 0};
-    if (finc_wino_packed_bytes(G, Cq, KH, KW) && finc_wino_takes(nullptr, nullptr, s)) info[1] = finc_wino_form(s) == 4 ? 4 : 2;   // (2: Winograd F(2,3), 4: F(4,3))
-    if (finc_bigfwd_packed_bytes(G, Cq, KH, KW) && finc_bigfwd_takes(nullptr, nullptr, s)) info[1] = 3;   // (3: the big banks' M-split)
-    if (finc_wino5_packed_bytes(G, Cq, KH, KW) && finc_wino5_takes(nullptr, nullptr, s)) info[1] = 5;     // (5: Winograd F(2,5), 5x5)
-    if (finc_wino4m_packed_bytes(G, Cq, KH, KW) && finc_wino4m_takes(nullptr, nullptr, s)) info[1] = 6;   // (6: Winograd F(4,3), M-split)
     return FINC_OK;
 }
 

@@ -1491,10 +1491,8 @@ constexpr Inst make_inst()
                 C::NKZT, C::NKDT, C::NK, C::MT, C::NFRAGT, C::MTB, NW, C::NKZ, C::NKD, NPW, MAXP};
 }
 
-#define FINC_BOTH(cqp, kh, kw) make_inst<cqp, kh, kw>()
-
 #ifdef FINC_ONLY_C3   // experiment builds (scripts/build_variant.sh): only the c3 kernels, compiles in seconds
-const Inst g_insts[] = {make_inst<24, 3, 3, 2, 2, 512>(), FINC_BOTH(24, 3, 3), FINC_BOTH(12, 3, 3)};
+const Inst g_insts[] = {make_inst<24, 3, 3, 2, 2, 512>(), make_inst<24, 3, 3>(), make_inst<12, 3, 3>()};
 #else
 const Inst g_insts[] = {
     // 3x3: every Cq % 4 == 0 up to 32, then K-split (2 / 4 waves per problem) for the banks one wave cannot hold.
@@ -1504,24 +1502,24 @@ const Inst g_insts[] = {
     // (While the problems do not outnumber the CUs -- B*G <= 256 -- the 2x2 and 3x3 banks up to Cq = 32 do not come here at
     // all: they run on the role-split kernel, finc_split.hip.  Its predecessors in this table, three-wave K-splits of
     // <24,3,3> and <12,3,3>, took 245 / 48 us at c3 / c2 where it takes 165 / 2x us: profiles/r03.)
-    FINC_BOTH(4, 3, 3),  FINC_BOTH(8, 3, 3),  FINC_BOTH(12, 3, 3), FINC_BOTH(16, 3, 3),
-    FINC_BOTH(20, 3, 3),
-    make_inst<24, 3, 3, 2, 2, 512>(), FINC_BOTH(24, 3, 3), FINC_BOTH(28, 3, 3),
+    make_inst<4, 3, 3>(),  make_inst<8, 3, 3>(),  make_inst<12, 3, 3>(), make_inst<16, 3, 3>(),
+    make_inst<20, 3, 3>(),
+    make_inst<24, 3, 3, 2, 2, 512>(), make_inst<24, 3, 3>(), make_inst<28, 3, 3>(),
     // Cq = 32: one wave's rings (53 KB at W = 64) let only 2 problems onto a CU; split over 2 waves and packed in pairs
     // the same 2 problems keep all 4 SIMDs busy (1.25 -> 0.89 ms at B = 256, 64x64)
-    make_inst<32, 3, 3, 2, 2>(), FINC_BOTH(32, 3, 3),
+    make_inst<32, 3, 3, 2, 2>(), make_inst<32, 3, 3>(),
     make_inst<40, 3, 3, 2, 2>(), make_inst<40, 3, 3, 2>(), make_inst<48, 3, 3, 4>(), make_inst<64, 3, 3, 4>(),
-    FINC_BOTH(4, 2, 2),  FINC_BOTH(8, 2, 2),  FINC_BOTH(12, 2, 2), FINC_BOTH(16, 2, 2), FINC_BOTH(24, 2, 2),
+    make_inst<4, 2, 2>(),  make_inst<8, 2, 2>(),  make_inst<12, 2, 2>(), make_inst<16, 2, 2>(), make_inst<24, 2, 2>(),
     // (Cq = 32 at 2x2: as at 3x3, one wave's rings let 3 problems onto a CU; 2 waves per problem, packed in pairs: 685 -> 608 us
     // at B = 256, 64x64)
-    make_inst<32, 2, 2, 2, 2>(), FINC_BOTH(32, 2, 2),
-    FINC_BOTH(4, 5, 5),  FINC_BOTH(8, 5, 5),  FINC_BOTH(12, 5, 5), FINC_BOTH(16, 5, 5),
+    make_inst<32, 2, 2, 2, 2>(), make_inst<32, 2, 2>(),
+    make_inst<4, 5, 5>(),  make_inst<8, 5, 5>(),  make_inst<12, 5, 5>(), make_inst<16, 5, 5>(),
     // (Cq = 17 .. 24 at 5x5 -- the 20-channel 5x5 layers of fastflow/test_examples.py:218-222 -- on two waves: the operands
     // of a 5x5 filter do not rotate in place, and their ageing copies beside 450 fragments do not fit one wave)
     make_inst<24, 5, 5, 2>(), make_inst<32, 5, 5, 4>(), make_inst<48, 5, 5, 4>(),
     // non-square filters (PaddedConv2d takes a (K_H, K_W) tuple, layers/conv.py:30-36; the reference's fixtures have 3x5 and 2x3)
-    FINC_BOTH(4, 3, 5),  FINC_BOTH(8, 3, 5),  FINC_BOTH(16, 3, 5),
-    FINC_BOTH(4, 2, 3),  FINC_BOTH(8, 2, 3),  FINC_BOTH(16, 2, 3),
+    make_inst<4, 3, 5>(),  make_inst<8, 3, 5>(),  make_inst<16, 3, 5>(),
+    make_inst<4, 2, 3>(),  make_inst<8, 2, 3>(),  make_inst<16, 2, 3>(),
 };
 #endif
 
@@ -1541,21 +1539,42 @@ bool finc_no_s64()
     return off;
 }
 
-// first variant of the shape (any: they share the packed layout); with a problem count and a width, the first variant
-// that may run them
 // Cq padded to the smallest compiled bank that holds it (0: none).  One-wave kernels mask the last group of four only -- the
 // table has every multiple of 4 up to their largest bank --, the K-split banks any number of padded channels.
 int padded_cq(int Cq, int KH, int KW)
 {
-    int best = 0, nw = 1;
+    int best = 0;
     for (const Inst &i : g_insts)
-        if (i.cqp >= Cq && i.kh == KH && i.kw == KW && (best == 0 || i.cqp < best)) { best = i.cqp; nw = i.nw; }
+        if (i.cqp >= Cq && i.kh == KH && i.kw == KW && (best == 0 || i.cqp < best)) best = i.cqp;
     if (best && best - Cq > 3) {               // needs a K-split bank: every variant of that bank must be one
         for (const Inst &i : g_insts)
             if (i.cqp == best && i.kh == KH && i.kw == KW && i.nw == 1) return 0;
     }
-    (void)nw;
     return best;
+}
+
+// the first row of bank cqp that may run `problems` problems (-1: any number of them) on a map W columns wide -- table order,
+// max_problems, problems per workgroup, the rings in the LDS
+const Inst *find_inst(int cqp, int KH, int KW, long long problems, int W)
+{
+    const int P = W < 16 ? W : 16;
+    for (const Inst &i : g_insts) {
+        if (i.cqp != cqp || i.kh != KH || i.kw != KW) continue;
+        if (i.max_problems > 0 && (problems < 0 || problems > i.max_problems)) continue;
+        if (problems < 0 ? i.npw != 1 : problems % i.npw != 0) continue;
+        if (lds_bytes(i, W, P) > 160 * 1024) continue;
+        return &i;
+    }
+    return nullptr;
+}
+
+// the packed two-wave row of bank cqp (two problems per workgroup) whose rings fit the LDS at this width, or nullptr
+const Inst *pair_inst(int cqp, int KH, int KW, int W)
+{
+    const int P = W < 16 ? W : 16;
+    for (const Inst &i : g_insts)
+        if (i.cqp == cqp && i.kh == KH && i.kw == KW && i.nw == 2 && i.npw == 2 && lds_bytes(i, W, P) <= 160 * 1024) return &i;
+    return nullptr;
 }
 
 // A bank without a two-wave form of its own borrows the next bank's: the 28-channel 3x3 bank (7 k-steps do not split over two
@@ -1579,43 +1598,6 @@ static bool borrowed_form_wins(long long problems, size_t lds_one_wave)
     if (n1 >= 3 && problems > 2 * CUS) return false;
     const long long r1 = (problems + n1 * CUS - 1) / (n1 * CUS), r2 = (problems + 2 * CUS - 1) / (2 * CUS);
     return r2 * 13 < r1 * 16;                                   // (437 / 540 = 0.81 = 13 / 16)
-}
-
-const Inst *find_inst(int Cq, int KH, int KW, long long problems = -1, int W = 0)
-{
-    const int cqp = padded_cq(Cq, KH, KW);
-    if (cqp == 0) return nullptr;
-    for (const Inst &i : g_insts) {
-        if (i.cqp != cqp || i.kh != KH || i.kw != KW) continue;
-        if (problems >= 0) {
-            if (i.max_problems > 0 && problems > i.max_problems) continue;
-            if (problems % i.npw != 0) continue;
-            const int P = W < 16 ? W : 16;
-            if (lds_bytes(i, W, P) > 160 * 1024) continue;
-        }
-        if (problems >= 0 && W > 0 && i.nw == 1 && i.npw == 1 && problems % 2 == 0 && borrowed_cqp(cqp, KH, KW)) {
-            const int P = W < 16 ? W : 16;
-            if (borrowed_form_wins(problems, lds_bytes(i, W, P)))
-                for (const Inst &k : g_insts)
-                    if (k.cqp == borrowed_cqp(cqp, KH, KW) && k.kh == KH && k.kw == KW && k.nw == 2 && k.npw == 2 && lds_bytes(k, W, P) <= 160 * 1024)
-                        return &k;
-        }
-        // Wide maps: the band hand-over FIFO grows with W, and once four one-wave problems no longer fit a CU's LDS (W >= 80
-        // at Cq = 24) the helper-wave form is out and only three SIMDs of a CU have a problem.  The packed two-wave form
-        // -- two problems per workgroup, every SIMD busy -- is then the faster one at ANY problem count (B = 256:
-        // 64x80 1,033 -> 764 us, 64x96 1,225 -> 903, 128x128 3,163 -> 2,302; profiles/r02/notes/ab36), although it loses
-        // at 64x64 where four one-wave problems do fit (521 vs 413 us).
-        if (problems >= 0 && W > 0 && i.nw == 1 && i.npw == 1) {
-            const int P = W < 16 ? W : 16;
-            if (4 * lds_bytes(i, W, P) + 64 > 160 * 1024 && problems % 2 == 0) {
-                for (const Inst &k : g_insts)
-                    if (k.cqp == cqp && k.kh == KH && k.kw == KW && k.nw == 2 && k.npw == 2 && lds_bytes(k, W, P) <= 160 * 1024)
-                        return &k;
-            }
-        }
-        return &i;
-    }
-    return nullptr;
 }
 
 size_t lds_bytes(const Inst &i, int W, int P)
@@ -1654,35 +1636,15 @@ static bool stream_bank(int Cq, int KH, int KW)
     return !finc_big_bank(Cq, KH, KW) && padded_cq(Cq, KH, KW) == 0 && finc_stream_bank_ok(Cq, KH, KW);
 }
 
-bool finc_mfma_supported(int Cq, int H, int W, int KH, int KW)
+// the bank's first row of the table (its variants share the packed layout) and the bytes of the bank's parts in a packed buffer:
+// the bank's own, then the borrowed one (borrowed_cqp), then -- for the banks finc_big.hip takes over on wide maps -- finc_big.hip's
+static const Inst *bank_inst(int Cq, int KH, int KW)
 {
-    if (finc_big_bank(Cq, KH, KW)) return finc_big_supported(Cq, H, W, KH, KW);   // beyond this table: finc_big.hip
-    if (stream_bank(Cq, KH, KW)) return finc_stream_supported(Cq, H, W, KH, KW, true);
-    if (W % 4 != 0 || W < 4 || H < 1) return false;
-    const int P = W < 16 ? W : 16;
-    if (P < KH - 1) return false;
-    // the shape is supported if a variant exists that takes ANY problem count (a huge odd one rules out the packed and
-    // the small-batch variants) and whose rings fit the LDS at this width -- or, on maps too wide for that, finc_big.hip does
-    if (!find_inst(Cq, KH, KW, (1LL << 40) + 1, W)) return finc_big_wide_bank(Cq, KH, KW) && finc_big_supported(Cq, H, W, KH, KW);
-    if ((size_t)Cq * H * W * 4 >= ((size_t)1 << 30)) return false; // buffer-offset range marks (OFF_BAD_CHANNEL)
-    return true;
+    const int cqp = padded_cq(Cq, KH, KW);
+    for (const Inst &i : g_insts)
+        if (cqp && i.cqp == cqp && i.kh == KH && i.kw == KW) return &i;
+    return nullptr;
 }
-
-int finc_mfma_packed_cqp(int Cq, int KH, int KW)
-{
-    if (finc_big_bank(Cq, KH, KW)) { int w, l, c; return finc_big_info(FincShape{1, 1, Cq, 16, 16, KH, KW, 0}, &w, &l, &c) ? 0 : c; }
-    if (stream_bank(Cq, KH, KW)) { int c = 0; return finc_stream_info(FincShape{1, 1, Cq, 16, 16, KH, KW, 0}, true, &c, nullptr, nullptr) ? 0 : c; }
-    const Inst *a = find_inst(Cq, KH, KW);
-    return a ? a->cqp : 0;
-}
-
-// bytes of this table's own bank
-static size_t own_bank_bytes(int G, int Cq, int KH, int KW)
-{
-    const Inst *a = find_inst(Cq, KH, KW);
-    return a ? (size_t)(a->nfrag + 8 * a->mt) * 64 * sizeof(float) * (size_t)G : 0;
-}
-// the borrowed bank's row of the table (nullptr: the bank borrows none) and its bytes
 static const Inst *borrowed_inst(int Cq, int KH, int KW)
 {
     const int b = borrowed_cqp(padded_cq(Cq, KH, KW), KH, KW);
@@ -1691,22 +1653,139 @@ static const Inst *borrowed_inst(int Cq, int KH, int KW)
             if (k.cqp == b && k.kh == KH && k.kw == KW && k.nw == 2 && k.npw == 2) return &k;
     return nullptr;
 }
-static size_t borrowed_bank_bytes(int G, int Cq, int KH, int KW)
-{
-    const Inst *k = borrowed_inst(Cq, KH, KW);
-    return k ? (size_t)(k->nfrag + 8 * k->mt) * 64 * sizeof(float) * (size_t)G : 0;
-}
-// bytes of this table's banks: its own, then the borrowed one (behind them: the bank of finc_big.hip for the banks it takes over on
-// wide maps)
+static size_t bank_bytes(const Inst *i, int G) { return i ? (size_t)(i->nfrag + 8 * i->mt) * 64 * sizeof(float) * (size_t)G : 0; }
 static size_t wave_bank_bytes(int G, int Cq, int KH, int KW)
 {
-    return own_bank_bytes(G, Cq, KH, KW) + borrowed_bank_bytes(G, Cq, KH, KW);
+    return bank_bytes(bank_inst(Cq, KH, KW), G) + bank_bytes(borrowed_inst(Cq, KH, KW), G);
 }
-// (which problem sets of such a bank go to finc_big.hip: those no variant of this table can hold)
-static bool wide_takeover(const FincShape &s)
+
+// -----------------------------------------------------------------------------------------------
+// The launch plan of an inverse call: which kernel runs, in which form, on which part of the packed buffer.  inverse_plan() is the
+// one place this is decided; finc_mfma_launch and every query (supported, variant, premultiplied / affine, remainder) read it.
+// -----------------------------------------------------------------------------------------------
+enum InvForm {
+    INV_NONE,    // no MFMA form: the strict kernel
+    INV_TABLE,   // a row of this table
+    INV_SPLIT,   // the role-split kernel or its short-step form (finc_split.hip)
+    INV_BIG,     // the big banks beyond this table (finc_big.hip)
+    INV_WIDE,    // a bank of this table on a map too wide for every row of it: finc_big.hip's bank, packed behind this table's
+    INV_STREAM,  // banks no register-resident kernel holds (finc_stream.hip)
+};
+
+struct InvPlan {
+    InvForm form = INV_NONE;
+    const Inst *inst = nullptr;   // INV_TABLE: the row that runs (INV_SPLIT: the row the table would run; the variant reports its bank)
+    int io = 0;                   // INV_TABLE: 0 16-byte groups, 1 32-byte pieces, 2 64-byte sector pairing, 3 sector pairing + helper waves
+    wave_fn fn = nullptr;
+    size_t lds = 0;               // INV_TABLE: dynamic LDS bytes of a workgroup
+    int grid = 0, block = 0;
+    size_t bank_offset = 0;       // bytes into the packed buffer where the bank this kernel reads begins
+    int tail_images = 0;          // INV_TABLE: images of the remainder launch (0: one launch)
+    bool zpre = false;            // the premultiplied-input form exists (finc_mfma_zpre_takes)
+    bool affine = false;          // a folded shift can be carried (finc_mfma_affine_takes)
+    bool align16 = true;          // the activations must be 16-byte aligned
+    FincSplitPlan split{};        // INV_SPLIT (and INV_TABLE: how the role-split kernel answered)
+};
+
+// the kernel family of a map: what does not depend on the problem count
+static InvForm inverse_form(int Cq, int H, int W, int KH, int KW)
 {
-    return finc_big_wide_bank(s.Cq, s.KH, s.KW) && !find_inst(s.Cq, s.KH, s.KW, (1LL << 40) + 1, s.W) &&
-           finc_big_supported(s.Cq, s.H, s.W, s.KH, s.KW);
+    if (finc_big_bank(Cq, KH, KW)) return finc_big_supported(Cq, H, W, KH, KW) ? INV_BIG : INV_NONE;   // beyond this table
+    if (stream_bank(Cq, KH, KW)) return finc_stream_supported(Cq, H, W, KH, KW, true) ? INV_STREAM : INV_NONE;   // beyond both
+    if (W % 4 != 0 || W < 4 || H < 1) return INV_NONE;
+    const int P = W < 16 ? W : 16;
+    if (P < KH - 1) return INV_NONE;
+    // a row must take ANY problem count (the packed and the small-batch rows do not) with rings that fit the LDS at this width --
+    // or, on maps too wide for that, finc_big.hip does
+    if (!find_inst(padded_cq(Cq, KH, KW), KH, KW, -1, W))
+        return finc_big_wide_bank(Cq, KH, KW) && finc_big_supported(Cq, H, W, KH, KW) ? INV_WIDE : INV_NONE;
+    if ((size_t)Cq * H * W * 4 >= ((size_t)1 << 30)) return INV_NONE;   // buffer-offset range marks (OFF_BAD_CHANNEL)
+    return INV_TABLE;
+}
+
+static InvPlan inverse_plan(const FincShape &s)
+{
+    InvPlan p;
+    p.form = inverse_form(s.Cq, s.H, s.W, s.KH, s.KW);
+    if (p.form == INV_NONE) return p;
+    // (a folded shift is the one thing finc_big.hip does not carry; the streaming bank takes the scale into the z-term's columns and
+    // Linv * shift as the accumulators' start)
+    p.affine = p.form != INV_BIG && p.form != INV_WIDE;
+    if (p.form == INV_WIDE) p.bank_offset = wave_bank_bytes(s.G, s.Cq, s.KH, s.KW);
+    if (p.form == INV_BIG || p.form == INV_WIDE) return p;
+    // Every form but the role-split kernel moves aligned 16-byte pieces.  (The streaming-bank shapes whose padded bank the role-split
+    // kernel holds -- 2x2, 17 .. 20 and 25 .. 28 channels -- ask it too.)
+    p.split = finc_split_plan(s);
+    p.align16 = !p.split.takes;
+    if (p.form == INV_STREAM) return p;
+
+    const long long problems = (long long)s.B * s.G;
+    const int cqp = padded_cq(s.Cq, s.KH, s.KW), P = s.W < 16 ? s.W : 16;
+    const Inst *i = find_inst(cqp, s.KH, s.KW, problems, s.W);
+    if (!i) return InvPlan{};                  // (not reached: the row that takes any count takes these)
+    if (i->nw == 1 && i->npw == 1 && problems % 2 == 0) {
+        const Inst *k = nullptr;
+        if (borrowed_cqp(cqp, s.KH, s.KW) && borrowed_form_wins(problems, lds_bytes(*i, s.W, P)))
+            k = pair_inst(borrowed_cqp(cqp, s.KH, s.KW), s.KH, s.KW, s.W);
+        // Wide maps: the band hand-over FIFO grows with W, and once four one-wave problems no longer fit a CU's LDS (W >= 80
+        // at Cq = 24) the helper-wave form is out and only three SIMDs of a CU have a problem.  The packed two-wave form
+        // -- two problems per workgroup, every SIMD busy -- is then the faster one at ANY problem count (B = 256:
+        // 64x80 1,033 -> 764 us, 64x96 1,225 -> 903, 128x128 3,163 -> 2,302; profiles/r02/notes/ab36), although it loses
+        // at 64x64 where four one-wave problems do fit (521 vs 413 us).
+        if (!k && 4 * lds_bytes(*i, s.W, P) + 64 > 160 * 1024) k = pair_inst(cqp, s.KH, s.KW, s.W);
+        if (k) i = k;
+    }
+    p.inst = i;
+    if (p.split.takes) {                       // the under-filled chip (finc_split.hip)
+        p.form = INV_SPLIT;
+        return p;
+    }
+    if (i == borrowed_inst(s.Cq, s.KH, s.KW))  // the borrowed two-wave form reads the bank packed behind the bank's own
+        p.bank_offset = bank_bytes(bank_inst(s.Cq, s.KH, s.KW), s.G);
+    const size_t lds = lds_bytes(*i, s.W, P);
+    const bool s64 = s.W % 16 == 0 && i->fn_s64 && !finc_no_s64();
+    // helper waves: 4 problems per 8-wave workgroup; their rings + 3 progress words each must fit one CU's LDS
+    const bool hlp = s64 && i->fn_hlp && problems % 4 == 0 && 4 * lds + 64 <= 160 * 1024 && !finc_no_hlp();
+    p.io = hlp ? 3 : s64 ? 2 : s.W % 8 == 0 ? 1 : 0;
+    p.fn = hlp ? i->fn_hlp : s64 ? i->fn_s64 : s.W % 8 == 0 ? i->fn_sec : i->fn;
+    p.lds = hlp ? 4 * lds + 64 : lds;
+    p.grid = hlp ? s.B * s.G / 4 : s.B * s.G / i->npw;
+    p.block = hlp ? 512 : 64 * i->nw * i->npw;
+
+    // A problem set that is not a whole number of ROUNDS.  One-wave problems run n1 to a compute unit and every problem is the same
+    // chain of steps, so 1,025 problems take as long as 2,048 -- unless the remainder goes to the kernel the library would pick for it
+    // on its own (role-split / short-step kernel up to 256 / 512 problems, the two-wave variants), which is faster than a round of this
+    // one or it would not be picked.  The images are independent: the remainder is a second launch on the images behind the whole
+    // rounds (c3, 64x64: B = 320 = 1,024 + 256 problems 765 -> 591 us, B = 264 761 -> 522; profiles/r05/notes/remainder_launch.txt).
+    // The packed two-wave kernels -- a pair of problems on a unit's four SIMDs -- work in rounds of 512 the same way (32 channels,
+    // B = 160: 865 -> 642 us).
+    static const bool no_remainder = finc_env("FINC_NO_REMAINDER_LAUNCH") != nullptr;   // experiment switch (A/B timing)
+    const bool one_wave = i->nw == 1 && i->npw == 1, packed_pair = i->nw == 2 && i->npw == 2;
+    if (!no_remainder && (one_wave || packed_pair)) {
+        long long n1 = packed_pair ? 2 : hlp ? 4 : (long long)((160 * 1024 - 64) / lds);
+        n1 = n1 > 4 ? 4 : n1 < 1 ? 1 : n1;
+        const long long round = n1 * 256, r = problems % round;
+        if (problems > round && r != 0 && r <= 512 && r % s.G == 0) {
+            FincShape tail = s;
+            tail.B = (int)(r / s.G);
+            const InvPlan t = inverse_plan(tail);
+            if (t.form == INV_SPLIT || t.inst != i) p.tail_images = tail.B;
+        }
+    }
+    // The premultiplied-input form exists for the shapes the helper-wave kernel takes (a full chip: the role-split kernel's small
+    // problem sets and the forms without helper waves keep their z-term) -- in ONE launch: a problem set with a remainder launch keeps
+    // the plain chain, whose remainder runs on kernels without that form (c3, B = 264: 522 us against 0.93 x 761)
+    p.zpre = hlp && i->fn_zpre && p.tail_images == 0;
+    return p;
+}
+
+bool finc_mfma_supported(int Cq, int H, int W, int KH, int KW) { return inverse_form(Cq, H, W, KH, KW) != INV_NONE; }
+
+int finc_mfma_packed_cqp(int Cq, int KH, int KW)
+{
+    if (finc_big_bank(Cq, KH, KW)) { int w, l, c; return finc_big_info(FincShape{1, 1, Cq, 16, 16, KH, KW, 0}, &w, &l, &c) ? 0 : c; }
+    if (stream_bank(Cq, KH, KW)) { int c = 0; return finc_stream_info(FincShape{1, 1, Cq, 16, 16, KH, KW, 0}, true, &c, nullptr, nullptr) ? 0 : c; }
+    return padded_cq(Cq, KH, KW);
 }
 
 // Banks packed WITH a folded shift have no wide-map form (finc_big.hip carries a scale only).  Such a packed buffer is
@@ -1737,12 +1816,12 @@ static bool dead_wide_has(const void *packed)
     return false;
 }
 
-bool finc_mfma_affine_takes(const FincShape &s)
-{
-    if (!finc_mfma_supported(s.Cq, s.H, s.W, s.KH, s.KW)) return false;
-    if (stream_bank(s.Cq, s.KH, s.KW)) return true;       // (scale into the z-term's columns, Linv * shift as the accumulators' start)
-    return !finc_big_bank(s.Cq, s.KH, s.KW) && !wide_takeover(s);
-}
+bool finc_mfma_affine_takes(const FincShape &s) { return inverse_plan(s).affine; }
+bool finc_mfma_zpre_takes(const FincShape &s) { return inverse_plan(s).zpre; }
+bool finc_mfma_needs_align16(const FincShape &s) { return inverse_plan(s).align16; }
+
+// images of the remainder launch of an inverse call (0: the call is one launch) -- the launch's own decision, for tests and bench.py
+int finc_mfma_remainder_images(const FincShape &s) { return inverse_plan(s).tail_images; }
 
 size_t finc_mfma_packed_bytes(int G, int Cq, int KH, int KW)
 {
@@ -1759,13 +1838,13 @@ int finc_mfma_pack(const float *wc, const float *scale, const float *shift, void
     (void)finc_split_prepare(st);              // ... and the band split's progress words (finc_split.hip)
     if (finc_big_bank(Cq, KH, KW)) return finc_big_pack(wc, scale, shift, packed, G, Cq, KH, KW, st);
     if (stream_bank(Cq, KH, KW)) return finc_stream_pack(wc, scale, shift, packed, G, Cq, KH, KW, true, false, st);
-    const Inst *i = find_inst(Cq, KH, KW);
+    const Inst *i = bank_inst(Cq, KH, KW);
     if (!i) return FINC_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(pack_kernel, dim3(G), dim3(256), sizeof(double) * Cq * Cq, st, wc, scale, shift, (float *)packed, Cq,
                        KH, KW, i->mt, i->nkz, i->nkd, i->mtb, i->nfrag);
     FINC_CHECK_LAUNCH();
     if (const Inst *k = borrowed_inst(Cq, KH, KW)) {      // the borrowed two-wave bank, same fold, behind the bank's own
-        float *behind = (float *)((char *)packed + own_bank_bytes(G, Cq, KH, KW));
+        float *behind = (float *)((char *)packed + bank_bytes(i, G));
         hipLaunchKernelGGL(pack_kernel, dim3(G), dim3(256), sizeof(double) * Cq * Cq, st, wc, scale, shift, behind, Cq, KH, KW, k->mt,
                            k->nkz, k->nkd, k->mtb, k->nfrag);
         FINC_CHECK_LAUNCH();
@@ -1783,43 +1862,37 @@ int finc_mfma_pack(const float *wc, const float *scale, const float *shift, void
 
 int finc_mfma_variant(int B, int G, int Cq, int H, int W, int KH, int KW, int *info)
 {
-    if (!finc_mfma_supported(Cq, H, W, KH, KW)) return FINC_ERR_UNSUPPORTED;
-    if (stream_bank(Cq, KH, KW)) {             // form 7: the streaming-bank kernel, one workgroup of info[1] waves per problem
+    const FincShape s{B, G, Cq, H, W, KH, KW, 0};
+    const InvPlan p = inverse_plan(s);
+    const int rows = (int)(sizeof(g_insts) / sizeof(g_insts[0]));
+    switch (p.form) {
+    case INV_NONE: return FINC_ERR_UNSUPPORTED;
+    case INV_STREAM: {                         // form 7: the streaming-bank kernel, one workgroup of info[1] waves per problem
         int cqp = 0, lds = 0, waves = 0, owv = 0;
-        if (int e = finc_stream_info(FincShape{B, G, Cq, H, W, KH, KW, 0}, true, &cqp, &lds, nullptr, &waves, &owv)) return e;
+        if (int e = finc_stream_info(s, true, &cqp, &lds, nullptr, &waves, &owv)) return e;
         info[0] = cqp; info[1] = waves; info[2] = 1; info[3] = 7; info[4] = lds; info[5] = B * G;
-        info[6] = owv ? -4 : -3;               // (-4: one-wave problems in their per-lane 16-byte form) info[7] = (int)(sizeof(g_insts) / sizeof(g_insts[0]));
+        info[6] = owv ? -4 : -3;               // (-4: one-wave problems in their per-lane 16-byte form; info[7] is left as it was)
         return FINC_OK;
     }
-    if (finc_big_bank(Cq, KH, KW) || wide_takeover(FincShape{B, G, Cq, H, W, KH, KW, 0})) {   // form 5: the big-bank kernel, one workgroup of info[1] waves per problem
+    case INV_BIG:
+    case INV_WIDE: {                           // form 5: the big-bank kernel, one workgroup of info[1] waves per problem
         int waves = 0, lds = 0, cqp = 0;
-        if (int e = finc_big_info(FincShape{B, G, Cq, H, W, KH, KW, 0}, &waves, &lds, &cqp)) return e;
+        if (int e = finc_big_info(s, &waves, &lds, &cqp)) return e;
         info[0] = cqp; info[1] = waves; info[2] = 1; info[3] = 5; info[4] = lds; info[5] = B * G;
-        info[6] = -2; info[7] = (int)(sizeof(g_insts) / sizeof(g_insts[0]));
+        info[6] = -2; info[7] = rows;
         return FINC_OK;
     }
-    const Inst *i = find_inst(Cq, KH, KW, (long long)B * G, W);
-    if (!i) return FINC_ERR_UNSUPPORTED;
-    const int P = W < 16 ? W : 16;
-    const FincShape fs{B, G, Cq, H, W, KH, KW, 0};
-    if (finc_split_takes(fs)) {                // form 4: the role-split kernel, info[5] / (B*G) workgroups of info[1] waves per problem
-        int waves = 0, lds = 0, steps = 0, nwg = 1;
-        if (int e = finc_split_info(fs, &waves, &lds, &steps, &nwg)) return e;
-        info[0] = i->cqp; info[1] = waves; info[2] = 1; info[3] = finc_split_uses_chain(fs) ? 6 : 4; info[4] = lds; info[5] = B * G * nwg;   // (6: its short-step form for the small banks, finc_chain.hip)
-        info[6] = -1; info[7] = (int)(sizeof(g_insts) / sizeof(g_insts[0]));
+    case INV_SPLIT:                            // form 4: the role-split kernel, info[5] / (B*G) workgroups of info[1] waves per problem
+        info[0] = p.inst->cqp; info[1] = p.split.waves; info[2] = 1; info[3] = p.split.chain ? 6 : 4;   // (6: its short-step form for the small banks, finc_chain.hip)
+        info[4] = p.split.lds; info[5] = B * G * p.split.nwg;
+        info[6] = -1; info[7] = rows;
+        return FINC_OK;
+    case INV_TABLE:
+        info[0] = p.inst->cqp; info[1] = p.inst->nw; info[2] = p.inst->npw; info[3] = p.io; info[4] = (int)p.lds; info[5] = p.grid;
+        info[6] = (int)(p.inst - g_insts); info[7] = rows;
         return FINC_OK;
     }
-    info[0] = i->cqp;
-    info[1] = i->nw;
-    info[2] = i->npw;
-    const bool s64 = W % 16 == 0 && i->fn_s64 && !finc_no_s64();
-    const bool hlp = s64 && i->fn_hlp && ((long long)B * G) % 4 == 0 && 4 * lds_bytes(*i, W, P) + 64 <= 160 * 1024 && !finc_no_hlp();
-    info[3] = hlp ? 3 : s64 ? 2 : W % 8 == 0 ? 1 : 0;
-    info[4] = hlp ? (int)(4 * lds_bytes(*i, W, P) + 64) : (int)lds_bytes(*i, W, P);
-    info[5] = hlp ? B * G / 4 : B * G / i->npw;
-    info[6] = (int)(i - g_insts);
-    info[7] = (int)(sizeof(g_insts) / sizeof(g_insts[0]));
-    return FINC_OK;
+    return FINC_ERR_UNSUPPORTED;
 }
 
 int finc_mfma_table_row(int row, int *info)
@@ -1831,101 +1904,40 @@ int finc_mfma_table_row(int row, int *info)
     return FINC_OK;
 }
 
-// A problem set that is not a whole number of ROUNDS.  One-wave problems run n1 to a compute unit and every problem is the same chain
-// of steps, so 1,025 problems take as long as 2,048 -- unless the remainder goes to the kernel the library would pick for it on its
-// own (role-split / short-step kernel up to 256 / 512 problems, the two-wave variants), which is faster than a round of this one or
-// it would not be picked.  The images are independent: the remainder is a second launch on the images behind the whole rounds
-// (c3, 64x64: B = 320 = 1,024 + 256 problems 765 -> 591 us, B = 264 761 -> 522; profiles/r05/notes/remainder_launch.txt).
-// The packed two-wave kernels -- a pair of problems on a unit's four SIMDs -- work in rounds of 512 the same way (32 channels,
-// B = 160: 865 -> 642 us).  Returns the number of images of the remainder launch (0: one launch).
-static int remainder_images(const FincShape &s, const Inst *i, bool hlp, size_t lds)
-{
-    static const bool no_remainder = finc_env("FINC_NO_REMAINDER_LAUNCH") != nullptr;   // experiment switch (A/B timing)
-    const bool one_wave = i->nw == 1 && i->npw == 1, packed_pair = i->nw == 2 && i->npw == 2;
-    if (no_remainder || !(one_wave || packed_pair)) return 0;
-    const long long problems = (long long)s.B * s.G;
-    long long n1 = packed_pair ? 2 : hlp ? 4 : (long long)((160 * 1024 - 64) / lds);
-    n1 = n1 > 4 ? 4 : n1 < 1 ? 1 : n1;
-    const long long round = n1 * 256, r = problems % round;
-    if (problems <= round || r == 0 || r > 512 || r % s.G != 0) return 0;
-    FincShape tail = s;
-    tail.B = (int)(r / s.G);
-    return (finc_split_takes(tail) || find_inst(s.Cq, s.KH, s.KW, r, s.W) != i) ? tail.B : 0;
-}
-
-// the premultiplied-input form exists for the shapes the helper-wave kernel takes (a full chip: the role-split kernel's
-// small problem sets and the forms without helper waves keep their z-term) -- in ONE launch: a problem set with a remainder launch
-// (above) keeps the plain chain, whose remainder runs on kernels without that form (c3, B = 264: 522 us against 0.93 x 761)
-bool finc_mfma_zpre_takes(const FincShape &s)
-{
-    if (!finc_mfma_supported(s.Cq, s.H, s.W, s.KH, s.KW) || stream_bank(s.Cq, s.KH, s.KW) || finc_split_takes(s)) return false;
-    const Inst *i = find_inst(s.Cq, s.KH, s.KW, (long long)s.B * s.G, s.W);
-    if (!i || !i->fn_zpre || s.W % 16 != 0 || finc_no_s64() || finc_no_hlp()) return false;
-    const int P = 16;
-    if (!(((long long)s.B * s.G) % 4 == 0 && 4 * lds_bytes(*i, s.W, P) + 64 <= 160 * 1024)) return false;
-    return remainder_images(s, i, true, lds_bytes(*i, s.W, P)) == 0;
-}
-
-// images of the remainder launch of an inverse call (0: the call is one launch) -- the launch's own decision, for tests and bench.py
-int finc_mfma_remainder_images(const FincShape &s)
-{
-    if (!finc_mfma_supported(s.Cq, s.H, s.W, s.KH, s.KW) || finc_big_bank(s.Cq, s.KH, s.KW) || stream_bank(s.Cq, s.KH, s.KW) || wide_takeover(s) ||
-        finc_split_takes(s))
-        return 0;
-    const Inst *i = find_inst(s.Cq, s.KH, s.KW, (long long)s.B * s.G, s.W);
-    if (!i) return 0;
-    const int P = s.W < 16 ? s.W : 16;
-    const size_t lds = lds_bytes(*i, s.W, P);
-    const bool s64 = s.W % 16 == 0 && i->fn_s64 && !finc_no_s64();
-    const bool hlp = s64 && i->fn_hlp && ((long long)s.B * s.G) % 4 == 0 && 4 * lds + 64 <= 160 * 1024 && !finc_no_hlp();
-    return remainder_images(s, i, hlp, lds);
-}
-
 int finc_mfma_launch(const float *in, const void *packed, float *out, const FincShape &s, hipStream_t st, bool zpre)
 {
-    if (!finc_mfma_supported(s.Cq, s.H, s.W, s.KH, s.KW)) return FINC_ERR_UNSUPPORTED;
-    if (zpre && !finc_mfma_zpre_takes(s)) return FINC_ERR_UNSUPPORTED;
+    const InvPlan p = inverse_plan(s);
+    if (p.form == INV_NONE) return FINC_ERR_UNSUPPORTED;
+    if (zpre && !p.zpre) return FINC_ERR_UNSUPPORTED;
     if (int e = finc_fault_gate(false)) return e;          // an earlier launch on this device gave up a protocol wait
-    if (finc_big_bank(s.Cq, s.KH, s.KW)) return finc_big_launch(in, packed, out, s, st);   // beyond this table (finc_big.hip)
-    if (stream_bank(s.Cq, s.KH, s.KW)) return finc_stream_launch(in, packed, out, s, true, st);   // beyond both (finc_stream.hip)
-    if (wide_takeover(s) && dead_wide_has(packed)) return FINC_ERR_UNSUPPORTED;            // packed with a folded shift: no wide-map form
-    if (wide_takeover(s))                                                                  // too wide for this table's forms
-        return finc_big_launch(in, (const char *)packed + wave_bank_bytes(s.G, s.Cq, s.KH, s.KW), out, s, st);
-    if (finc_split_takes(s)) return finc_split_launch(in, packed, out, s, st);   // the under-filled chip (finc_split.hip)
-    const Inst *i = find_inst(s.Cq, s.KH, s.KW, (long long)s.B * s.G, s.W);
-    if (!i) return FINC_ERR_UNSUPPORTED;
+    switch (p.form) {
+    case INV_BIG: return finc_big_launch(in, packed, out, s, st);
+    case INV_STREAM: return finc_stream_launch(in, packed, out, s, true, st);
+    case INV_WIDE:
+        if (dead_wide_has(packed)) return FINC_ERR_UNSUPPORTED;                            // packed with a folded shift: no wide-map form
+        return finc_big_launch(in, (const char *)packed + p.bank_offset, out, s, st);
+    case INV_SPLIT: return finc_split_launch(in, packed, out, s, p.split, st);
+    default: break;
+    }
     if (((uintptr_t)in & 15u) || ((uintptr_t)out & 15u)) return FINC_ERR_ALIGNMENT;
+    if (!zpre && p.tail_images) {                           // whole rounds + a remainder on the remainder's own kernel
+        FincShape head = s, tail = s;
+        tail.B = p.tail_images;
+        head.B = s.B - p.tail_images;
+        const size_t off = (size_t)head.B * s.G * s.Cq * s.H * s.W;
+        if (int e = finc_mfma_launch(in, packed, out, head, st, false)) return e;
+        return finc_mfma_launch(in + off, packed, out + off, tail, st, false);
+    }
+    const wave_fn fn = zpre ? p.inst->fn_zpre : p.fn;
     const int P = s.W < 16 ? s.W : 16;
     const int NB = (s.H + P - 1) / P;
     const int Tend = s.W % 8 == 0 ? (NB * s.W + P - 1 + 7) / 8 * 8 : (NB * s.W + P - 1 + 3) / 4 * 4;  // 32-byte I/O: x8 loop
-    const size_t lds = lds_bytes(*i, s.W, P);
-    const bool s64 = s.W % 16 == 0 && i->fn_s64 && !finc_no_s64();
-    // helper waves: 4 problems per 8-wave workgroup; their rings + 3 progress words each must fit one CU's LDS
-    const size_t lds_hlp = 4 * lds + 64;
-    const bool hlp = s64 && i->fn_hlp && ((long long)s.B * s.G) % 4 == 0 && lds_hlp <= 160 * 1024 && !finc_no_hlp();
-    const wave_fn fn = zpre ? i->fn_zpre : hlp ? i->fn_hlp : s64 ? i->fn_s64 : (s.W % 8 == 0) ? i->fn_sec : i->fn;
-    if (!zpre) {                                            // whole rounds + a remainder on the remainder's own kernel (remainder_images)
-        if (const int tb = remainder_images(s, i, hlp, lds)) {
-            FincShape head = s, tail = s;
-            tail.B = tb;
-            head.B = s.B - tb;
-            const size_t off = (size_t)head.B * s.G * s.Cq * s.H * s.W;
-            if (int e = finc_mfma_launch(in, packed, out, head, st, false)) return e;
-            return finc_mfma_launch(in + off, packed, out + off, tail, st, false);
-        }
-    }
-    if (i == borrowed_inst(s.Cq, s.KH, s.KW))              // the borrowed two-wave form reads the bank packed behind the bank's own
-        packed = (const char *)packed + own_bank_bytes(s.G, s.Cq, s.KH, s.KW);
-    if (int e = finc_ensure_dynamic_lds((const void *)fn, hlp ? lds_hlp : lds)) return e;
-    if (hlp) {
+    if (int e = finc_ensure_dynamic_lds((const void *)fn, p.lds)) return e;
+    if (p.io == 3) {
         if (int e = finc_fault_gate(true, st)) return e;   // (arms the device's fault word if no packing call has: never inside a capture)
     }
-    if (hlp)
-        hipLaunchKernelGGL(fn, dim3(s.B * s.G / 4), dim3(512), lds_hlp, st, in, (const float *)packed, out, s.G, s.Cq, s.H, s.W, P,
-                           Tend, s.orient);
-    else
-        hipLaunchKernelGGL(fn, dim3(s.B * s.G / i->npw), dim3(64 * i->nw * i->npw), lds, st, in, (const float *)packed, out, s.G, s.Cq, s.H, s.W, P,
-                           Tend, s.orient);
+    hipLaunchKernelGGL(fn, dim3(p.grid), dim3(p.block), p.lds, st, in, (const float *)((const char *)packed + p.bank_offset), out,
+                       s.G, s.Cq, s.H, s.W, P, Tend, s.orient);
     FINC_CHECK_LAUNCH();
     return FINC_OK;
 }

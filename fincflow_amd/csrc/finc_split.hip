@@ -1081,68 +1081,53 @@ extern "C" int finc_debug_bsp_trace(unsigned long long *h, int reset)
 extern "C" int finc_debug_split_stamps(unsigned long long *h) { return (int)hipMemcpyFromSymbol(h, HIP_SYMBOL(finc_split_stamps), sizeof(finc_split_stamps)); }
 #endif
 
-// the short-step form (finc_chain.hip) runs the banks of up to 16 channels -- except where this kernel would deal the bands of a
-// 16-channel problem out to two workgroups: there the band split is the faster one (C = 64, 64x64: 85 against 90 us; 128x64: 141
-// against 168; profiles/r05/notes/chain_vs_split.txt), while the 12-channel banks win on one workgroup (64x64: 76 against 80 us)
-bool finc_split_uses_chain(const FincShape &s)
+FincSplitPlan finc_split_plan(const FincShape &s)
 {
-    if (!finc_chain_takes(s)) return false;
-    const SInst *i = find_sinst(s.Cq, s.KH, s.KW);
-    const int P = s.W < 16 ? s.W : 16;
-    if ((long long)s.B * s.G > split_max_problems()) return true;          // (only it takes two problems per compute unit: finc_split_takes)
-    if (i && i->cqp == 16 && fifo_fits(*i, s.W, P) && bsp_nwg(*i, s) > 1) return false;
-    return true;
-}
-
-bool finc_split_takes(const FincShape &s)
-{
+    FincSplitPlan p;
     const long long problems = (long long)s.B * s.G;
+    const SInst *i = find_sinst(s.Cq, s.KH, s.KW);
+    const int P = s.W < 16 ? s.W : 16;
     if (problems > split_max_problems()) {
-        // two problems per compute unit: the short-step form still beats the wavefront kernel's table (its workgroup is 45 KB of LDS
-        // and five waves) -- C = 48, 32x32, B = 128: 40.3 against 57.3 us; the maps of the CIFAR stack at its sampling batch: 16x16
-        // 12.6 against 15.1, 8x8 10.3 against 11.7, 4x4 9.0 against 9.6 (profiles/r05/tiny_maps_kernel_time.txt)
-        return problems <= 2 * split_max_problems() && finc_chain_takes(s);
+        // two problems per compute unit: only the short-step form, which still beats the wavefront kernel's table (its workgroup is
+        // 45 KB of LDS and five waves) -- C = 48, 32x32, B = 128: 40.3 against 57.3 us; the maps of the CIFAR stack at its sampling
+        // batch: 16x16 12.6 against 15.1, 8x8 10.3 against 11.7, 4x4 9.0 against 9.6 (profiles/r05/tiny_maps_kernel_time.txt)
+        p.takes = p.chain = problems <= 2 * split_max_problems() && finc_chain_takes(s);
+    } else {
+        // the short-step form (finc_chain.hip) runs the banks of up to 16 channels -- except where this kernel would deal the bands of
+        // a 16-channel problem out to two workgroups: there the band split is the faster one (C = 64, 64x64: 85 against 90 us; 128x64:
+        // 141 against 168; profiles/r05/notes/chain_vs_split.txt), while the 12-channel banks win on one workgroup (64x64: 76 against
+        // 80 us).  The short-step form has no FIFO-width limit; this kernel's FIFO of a k-step must fit.
+        p.chain = finc_chain_takes(s) && !(i && i->cqp == 16 && fifo_fits(*i, s.W, P) && bsp_nwg(*i, s) > 1);
+        p.takes = p.chain || (i && s.H >= 1 && s.W >= 1 && P >= s.KH - 1 && s.W % 4 == 0 &&   // (16-byte pieces)
+                              (size_t)s.Cq * s.H * s.W * 4 < ((size_t)1 << 30) &&             // buffer-offset range marks (OFF_BAD_CHANNEL)
+                              fifo_fits(*i, s.W, P));
     }
-    if (finc_split_uses_chain(s)) return true;                             // (the small banks' short-step form: no FIFO-width limit)
-    const SInst *i = find_sinst(s.Cq, s.KH, s.KW);
-    if (!i || s.H < 1 || s.W < 1) return false;
-    const int P = s.W < 16 ? s.W : 16;
-    if (P < s.KH - 1) return false;
-    if (s.W % 4 != 0) return false;                                        // 16-byte pieces
-    if ((size_t)s.Cq * s.H * s.W * 4 >= ((size_t)1 << 30)) return false;   // buffer-offset range marks (OFF_BAD_CHANNEL)
-    return fifo_fits(*i, s.W, P);
-}
-
-int finc_split_info(const FincShape &s, int *waves, int *lds, int *steps, int *nwg)
-{
-    if (finc_split_uses_chain(s)) {
-        if (nwg) *nwg = 1;
-        return finc_chain_info(s, waves, lds, steps);
+    if (!p.takes) return p;
+    if (p.chain) {
+        (void)finc_chain_info(s, &p.waves, &p.lds, &p.steps);
+        return p;
     }
-    const SInst *i = find_sinst(s.Cq, s.KH, s.KW);
-    if (!i) return FINC_ERR_UNSUPPORTED;
-    const int P = s.W < 16 ? s.W : 16;
     const int NB = (s.H + P - 1) / P;
-    const int n = bsp_nwg(*i, s);
-    *waves = 1 + i->nbw;
-    *lds = i->lds_bytes;
-    *steps = ((NB + n - 1) / n) * s.W + P - 1;         // steps of one workgroup (BSP: + the hand-over lag between workgroups)
-    if (nwg) *nwg = n;
-    return FINC_OK;
+    p.row = (int)(i - g_sinsts);
+    p.nwg = bsp_nwg(*i, s);
+    p.waves = 1 + i->nbw;
+    p.lds = i->lds_bytes;
+    p.steps = ((NB + p.nwg - 1) / p.nwg) * s.W + P - 1;   // steps of one workgroup (BSP: + the hand-over lag between workgroups)
+    return p;
 }
 
-int finc_split_launch(const float *in, const void *packed, float *out, const FincShape &s, hipStream_t st)
+int finc_split_launch(const float *in, const void *packed, float *out, const FincShape &s, const FincSplitPlan &p, hipStream_t st)
 {
-    if (finc_split_uses_chain(s)) return finc_chain_launch(in, packed, out, s, st);   // the small banks' short-step form (finc_chain.hip)
-    const SInst *i = find_sinst(s.Cq, s.KH, s.KW);
-    if (!i) return FINC_ERR_UNSUPPORTED;
+    if (p.chain) return finc_chain_launch(in, packed, out, s, st);   // the small banks' short-step form (finc_chain.hip)
+    if (p.row < 0) return FINC_ERR_UNSUPPORTED;
+    const SInst *i = &g_sinsts[p.row];
     const int P = s.W < 16 ? s.W : 16;
     const int NB = (s.H + P - 1) / P;
     const size_t lds = (size_t)i->lds_bytes;
-    int nwg = bsp_nwg(*i, s);
+    int nwg = p.nwg;
     unsigned *slot = nullptr;
     int slot_index = -1;
-    if (nwg > 1) {
+    if (nwg > 1) {                                             // (no progress-word slot free: the chained form, a run-time event)
         (void)finc_split_prepare(st);                          // (allocates unless a capture is going on)
         slot = bsp_take_slot(st, &slot_index);
         if (!slot) nwg = 1;

@@ -691,11 +691,11 @@ size_t finc_wino_packed_bytes(int G, int Cq, int KH, int KW)
     return i ? (size_t)G * (i->npack + i->npack4) * 64 * sizeof(float) : 0;
 }
 
-bool finc_wino_takes(const float *in, const float *out, const FincShape &s)
+bool finc_wino_takes(const FincShape &s, int align)
 {
     if (s.KH != 3 || s.KW != 3 || s.W % 4 != 0 || s.W < 4 || finc_no_wino() || !find_winst(s.Cq)) return false;
     if ((size_t)s.Cq * s.H * s.W * 4 >= ((size_t)1 << 30)) return false;
-    return ((((uintptr_t)in) | ((uintptr_t)out)) & 15u) == 0;             // a row arrives as 16-byte windows
+    return align >= 16;                                                    // a row arrives as 16-byte windows
 }
 
 // Which form a call runs: F(4,3) has 1.33x fewer MFMAs but runs one wave per SIMD over strips of 64 columns, so it wants

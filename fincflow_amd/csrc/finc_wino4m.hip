@@ -243,11 +243,11 @@ size_t finc_wino4m_packed_bytes(int G, int Cq, int KH, int KW)
     return i ? (size_t)i->npack * 64 * sizeof(float) * (size_t)G : 0;
 }
 
-bool finc_wino4m_takes(const float *in, const float *out, const FincShape &s)
+bool finc_wino4m_takes(const FincShape &s, int align)
 {
     if (s.KH != 3 || s.KW != 3 || !find_w4m(s.Cq) || finc_wino_disabled()) return false;
     if (s.W % 4 != 0 || s.W < 4) return false;
-    if ((((uintptr_t)in) | ((uintptr_t)out)) & 15u) return false;          // a row arrives as 16-byte windows
+    if (align < 16) return false;                                          // a row arrives as 16-byte windows
     if ((size_t)s.Cq * s.H * s.W * 4 >= ((size_t)1 << 30)) return false;
     // strips of 64 columns: at least three quarters of what they cover is image, and enough workgroups for the chip
     const int NS = (s.W + 63) / 64;

@@ -407,11 +407,11 @@ size_t finc_wino5_packed_bytes(int G, int Cq, int KH, int KW)
     return i ? (size_t)i->npack * 64 * sizeof(float) * (size_t)G : 0;
 }
 
-bool finc_wino5_takes(const float *in, const float *out, const FincShape &s)
+bool finc_wino5_takes(const FincShape &s, int align)
 {
     if (s.KH != 5 || s.KW != 5 || no_wino5() || !find_w5(s.Cq)) return false;
     if (s.W % 2 != 0 || s.W < 2) return false;                             // pairs
-    if ((((uintptr_t)in) | ((uintptr_t)out)) & 7u) return false;           // 8-byte pieces
+    if (align < 8) return false;                                           // 8-byte pieces
     return (size_t)s.Cq * s.H * s.W * 4 < ((size_t)1 << 30);
 }
 

@@ -105,79 +105,22 @@ def report(kind, **fields):
 # ---------------------------------------------------------------------------
 # the MFMA inverse's instantiation table (finc_mfma.hip g_insts), walked by tests
 # ---------------------------------------------------------------------------
-SPLIT_MAX_PROBLEMS = 256      # finc_split.hip split_max_problems()
-SPLIT_BANKS = {(3, 3): (4, 8, 12, 16, 20, 24, 28, 32), (2, 2): (4, 8, 12, 16, 24, 32)}
-
-
-def chain_takes(cqp, kh, kw, problems, H, W):
-    """Mirror of finc_chain.hip finc_chain_takes (inside finc_split_takes): the short-step form of the role-split kernel takes the
-    2x2 / 3x3 banks of up to 16 channels on any map whose width is a multiple of 4 (its hand-over FIFO is 128 bytes per step)."""
-    if problems > 2 * SPLIT_MAX_PROBLEMS or cqp > 16 or cqp not in SPLIT_BANKS.get((kh, kw), ()) or H < 1 or W < 4 or W % 4:
-        return False
-    P = min(16, W)
-    nbw = sum(1 for a in range(kh) for b in range(kw) if a + b == 2)
-    fixed = 8 * (64 + 8 + 1 + 8) * 16 + 2 * nbw * 1024 + (cqp // 4) * 8 * 1024
-    if not (P >= kh - 1 and fixed + 2 * (W - P + 2) * 128 <= 160 * 1024):
-        return False
-    # (finc_split_uses_chain: a 16-channel problem whose bands the role-split kernel would deal out to two workgroups stays there)
-    band_split = 2 * problems <= 256 and H > 16 and W >= 64 and kh > 1 and (W - P + kh + kw - 2) * 4 * (kh - 1) * 4 <= 2048 - 4
-    return not (cqp == 16 and band_split)
-
-
-def split_takes(cqp, kh, kw, problems, H, W):
-    """Mirror of finc_split.hip finc_split_takes: the role-split kernel runs the problem sets that do not outnumber the
-    compute units, for the 2x2 / 3x3 banks one wave holds, on maps whose hand-over FIFO fits its 2 KB per k-step (the banks of
-    up to 16 channels, on the short-step form: any width)."""
-    if chain_takes(cqp, kh, kw, problems, H, W):
-        return True
-    if problems > SPLIT_MAX_PROBLEMS or cqp not in SPLIT_BANKS.get((kh, kw), ()) or H < 1 or W < 4 or W % 4:
-        return False
-    P = min(16, W)
-    return P >= kh - 1 and (W - P + kh + kw - 2) * 4 * (kh - 1) * 4 <= 2048 - 4
-
-
-def pick_row(rows, cqp, kh, kw, problems, H=10, W=32):
-    """Mirror of the library's selection rule: -1 when the role-split kernel takes the problem set, else find_inst's table
-    walk (table order; max_problems; problems % npw) -- LDS fit not modelled, the test shapes are narrow.  The host test
-    checks this mirror against the library's own answer."""
-    if split_takes(cqp, kh, kw, problems, H, W):
-        return -1
-    for r, i in enumerate(rows):
-        if (i["cqp"], i["kh"], i["kw"]) != (cqp, kh, kw):
-            continue
-        if i["max_problems"] > 0 and problems > i["max_problems"]:
-            continue
-        if problems % i["npw"] != 0:
-            continue
-        if (cqp, kh, kw) == (28, 3, 3) and problems % 2 == 0 and borrowed_form_wins(problems, W):
-            return next(k for k, x in enumerate(rows) if (x["cqp"], x["kh"], x["kw"], x["nw"], x["npw"]) == (32, 3, 3, 2, 2))
-        return r
-    return None
-
-
-def borrowed_form_wins(problems, W):
-    """The 28-channel 3x3 bank on the 32-channel bank's packed two-wave kernel (finc_mfma.hip, borrowed_form_wins): the chip takes
-    one-wave problems n1 to a compute unit (as many of their rings as fit 160 KB, at most four), two-wave problems two; a two-wave
-    round takes 13/16 of a one-wave round; beyond 512 problems only where at most two one-wave problems fit a unit."""
-    P = min(W, 16)
-    lds = 4 * (7 * 12 * 64 + 7 * 8 * 64 + (W - P + 1) * 56 + 56 + 64)
-    n1 = max(1, min(4, (160 * 1024 - 64) // lds))
-    if n1 >= 3 and problems > 512:          # (the bank's own kernel has the better rate and hands a remainder to the role-split kernel)
-        return False
-    r1, r2 = -(-problems // (n1 * 256)), -(-problems // 512)
-    return r2 * 13 < r1 * 16
-
-
 def problem_counts_for_row(rows, r):
-    """Problem counts (B*G) that select row r: the smallest, and the ones next to each max_problems edge of the shape (for
-    the banks the role-split kernel serves: counts beyond its 256 problems)."""
+    """Problem counts (B*G) that select row r -- the library's own answer on a 10x32 map, a host-only call: the smallest, and the
+    ones next to each max_problems edge of the shape (for the banks the role-split kernel serves: counts beyond its 256 problems)."""
+    from fincflow_amd import _lib
     i = rows[r]
     shape = (i["cqp"], i["kh"], i["kw"])
     edges = sorted({x["max_problems"] for x in rows if (x["cqp"], x["kh"], x["kw"]) == shape and x["max_problems"] > 0})
     cands = [1, 2, 3, 4, 6, 8, 257, 258, 259, 260, 262, 264, 513, 514, 515, 516, 518, 520]   # (beyond the role-split kernel's 256 and its short-step form's 512)
     for e in edges:
         cands += [e - 2, e - 1, e, e + 1, e + 2, e + 4]
-    hits = [n for n in sorted(set(cands)) if n > 0 and pick_row(rows, *shape, n) == r]
+
+    def row_of(n):
+        B, G, _ = split_problems(n)
+        v = _lib.inverse_variant(B, G, i["cqp"], 10, 32, i["kh"], i["kw"])
+        return v and v["row"]
+    hits = [n for n in sorted(set(cands)) if n > 0 and row_of(n) == r]
     if not hits:
         return []
     out = [hits[0]]

@@ -155,18 +155,19 @@ def test_role_split_kernel_takes_the_under_filled_chip():
     split; the c4 units) run on the role-split kernel -- form 4, one workgroup of four waves per problem; the banks of up to 16
     channels on its short-step form (finc_chain.hip, form 6: the recurrence wave, one wave per tap with a + b == 2, the I/O
     wave); everything else stays with the wavefront kernel's table (host-only calls)."""
-    from helpers import split_takes, chain_takes
-    for (B, G, Cq, H, W, K), want in (((64, 4, 12, 32, 32, 3), True), ((32, 4, 24, 64, 64, 3), True), ((64, 4, 24, 64, 64, 3), True),
-                                      ((65, 4, 24, 64, 64, 3), False), ((128, 4, 3, 16, 16, 3), True), ((128, 4, 6, 8, 8, 3), True), ((129, 4, 3, 16, 16, 3), False),
-                                      ((64, 4, 3, 16, 16, 3), True),
-                                      ((16, 4, 12, 4, 4, 3), True), ((1, 1, 23, 40, 36, 3), True), ((8, 4, 24, 8, 80, 3), False),
-                                      ((8, 4, 16, 30, 44, 2), True), ((8, 4, 16, 32, 32, 5), False), ((8, 4, 40, 32, 32, 3), False),
-                                      ((8, 4, 12, 8, 80, 3), True), ((2, 4, 16, 16, 256, 3), True), ((8, 4, 20, 8, 80, 3), False)):
+    # want: the role-split kernel takes the problem set; chain: on its short-step form (sec == 6)
+    for (B, G, Cq, H, W, K), want, chain in (((64, 4, 12, 32, 32, 3), True, True), ((32, 4, 24, 64, 64, 3), True, False),
+                                             ((64, 4, 24, 64, 64, 3), True, False), ((65, 4, 24, 64, 64, 3), False, False),
+                                             ((128, 4, 3, 16, 16, 3), True, True), ((128, 4, 6, 8, 8, 3), True, True),
+                                             ((129, 4, 3, 16, 16, 3), False, False), ((64, 4, 3, 16, 16, 3), True, True),
+                                             ((16, 4, 12, 4, 4, 3), True, True), ((1, 1, 23, 40, 36, 3), True, False),
+                                             ((8, 4, 24, 8, 80, 3), False, False), ((8, 4, 16, 30, 44, 2), True, True),
+                                             ((8, 4, 16, 32, 32, 5), False, False), ((8, 4, 40, 32, 32, 3), False, False),
+                                             ((8, 4, 12, 8, 80, 3), True, True), ((2, 4, 16, 16, 256, 3), True, True),
+                                             ((8, 4, 20, 8, 80, 3), False, False)):
         v = _lib.inverse_variant(B, G, Cq, H, W, K, K)
         assert v is not None, (B, G, Cq, H, W, K)
         assert (v["sec"] in (4, 6)) == want, (B, G, Cq, H, W, K, v)
-        assert split_takes(v["cqp"], K, K, B * G, H, W) == want
-        chain = chain_takes(v["cqp"], K, K, B * G, H, W)
         assert (v["sec"] == 6) == chain, (B, G, Cq, H, W, K, v)
         if chain:
             assert v["cqp"] <= 16 and v["nw"] == (5 if K == 3 else 3) and v["workgroups"] == B * G and v["row"] == -1, v
@@ -179,7 +180,7 @@ def test_role_split_kernel_takes_the_under_filled_chip():
 
 
 def test_wide_maps_take_the_packed_two_wave_form():
-    """finc_mfma.hip find_inst: once four one-wave problems do not fit a CU's LDS (the band hand-over FIFO grows with W) the
+    """finc_mfma.hip inverse_plan: once four one-wave problems do not fit a CU's LDS (the band hand-over FIFO grows with W) the
     packed two-wave form is chosen at any problem count; at 64x64 and below nothing changes (host-side call, no GPU)."""
     from fincflow_amd import _lib
     v = _lib.inverse_variant(256, 4, 24, 64, 64, 3, 3)
@@ -311,7 +312,7 @@ def test_row_chunks_minimise_rounds_times_rows():
 
 
 def test_premultiplied_form_only_where_the_call_is_one_launch():
-    """finc_mfma.hip remainder_images: a problem set of whole rounds plus a remainder of at most 512 problems is two launches, and the
+    """finc_mfma.hip inverse_plan: a problem set of whole rounds plus a remainder of at most 512 problems is two launches, and the
     remainder's kernels (role-split, short-step, two-wave variants) have no premultiplied-input form -- the query says so, and a flow stack
     then keeps the plain chain (c3, B = 264: 522 us in two launches against 0.93 x 761 in one)."""
     q = _lib.lib().finc_inverse_premultiplied_supported

@@ -405,7 +405,7 @@ def test_remainder_of_a_round_runs_on_the_remainders_own_kernel(case, dev):
 
 def test_a_flow_stack_at_a_batch_with_a_remainder_keeps_the_plain_chain(dev):
     """[unit, ActNorm, Conv1x1] reversed at B = 260 (1,040 problems = a round + 16): the premultiplied-input form is one launch or nothing
-    (finc_mfma.hip remainder_images), so the container runs the plain inverse -- two launches -- and gives what the layer-by-layer
+    (finc_mfma.hip inverse_plan), so the container runs the plain inverse -- two launches -- and gives what the layer-by-layer
     chain gives and what went in; at B = 256 it takes the fused path as before."""
     from fincflow_amd import FastFlowUnit, FlowSequential, glow, _lib
     from fincflow_amd.layers import StandardNormal

@@ -161,7 +161,7 @@ def test_role_split_kernel_with_the_affine_fold(dev):
 
 
 def test_wide_map_at_a_full_problem_count(dev):
-    """A map wider than 64 columns with more problems than the small-batch rows take: the packed two-wave form (find_inst's
+    """A map wider than 64 columns with more problems than the small-batch rows take: the packed two-wave form (inverse_plan's
     LDS rule), against the oracle."""
     e_max, _ = run_inverse_case(dev, 130, 4, ORIENT_FASTFLOW, 24, 5, 80, 3, 3, seed=4242, tag="wide_map")
     from fincflow_amd import _lib
