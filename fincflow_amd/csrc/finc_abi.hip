@@ -600,11 +600,18 @@ int finc_debug_inverse_table_row(int row, int *info)
     return finc_mfma_table_row(row, info);
 }
 
+// the backward's workspace: the grad-input bank (finc_conv_pack), then the grad-weight partials from the next 256-byte boundary
+struct BackwardWorkspace { size_t bank, partials; };
+static BackwardWorkspace backward_workspace(const FincShape &s)
+{
+    return {align256(finc_conv_packed_bytes(s.G, s.Cq, s.KH, s.KW)), finc_gradw_workspace_bytes(s)};
+}
+
 size_t finc_backward_workspace_bytes(int B, int G, int Cq, int H, int W, int KH, int KW)
 {
     if (B <= 0 || G <= 0 || Cq <= 0 || H <= 0 || W <= 0 || KH <= 0 || KW <= 0) return 256;
-    FincShape s{B, G, Cq, H, W, KH, KW, 0};
-    const size_t n = align256(finc_conv_packed_bytes(G, Cq, KH, KW)) + finc_gradw_workspace_bytes(s);
+    const BackwardWorkspace ws = backward_workspace(FincShape{B, G, Cq, H, W, KH, KW, 0});
+    const size_t n = ws.bank + ws.partials;
     return n < 256 ? 256 : n;
 }
 
@@ -620,21 +627,22 @@ int finc_backward_f32(const float *grad_z, const float *x, const float *w_canon,
     if (int e = finc_fault_gate(false)) return e;
     FincShape s{B, G, Cq, H, W, KH, KW, orient};
     hipStream_t st = (hipStream_t)stream;
-    const size_t pk = align256(finc_conv_packed_bytes(G, Cq, KH, KW));
+    const BackwardWorkspace ws = backward_workspace(s);
     // grad_x: the same conv on the H- and W-flipped image with in/out channels transposed (finc_conv.hip)
-    if (grad_x && workspace && finc_conv_supported(Cq, H, W, KH, KW) && pk > 0 && workspace_bytes >= pk) {
+    if (grad_x && workspace && finc_conv_supported(Cq, H, W, KH, KW) && ws.bank > 0 && workspace_bytes >= ws.bank) {
         if (int e = finc_conv_pack(w_canon, workspace, G, Cq, KH, KW, true, st)) return e;
         FincShape sb = s;
         sb.orient = orient ^ ((G >= 16) ? 0xFFFFFFFFu : ((1u << (2 * G)) - 1u));
         if (int e = finc_conv_launch(grad_z, workspace, grad_x, sb, st)) return e;
         grad_x = nullptr;
     }
-    // grad_w: MFMA strip kernel with the pixels on K + reduce (+ corner-tap mask)
-    const size_t gwb = finc_gradw_workspace_bytes(s);
-    if (grad_w_canon && workspace && gwb > 0 && workspace_bytes >= pk + gwb) {
-        const int e = finc_gradw_launch(grad_z, x, grad_w_canon, (char *)workspace + pk, s, st);
-        if (e == FINC_OK) grad_w_canon = nullptr;
-        else if (e != FINC_ERR_UNSUPPORTED) return e;       // (unsupported for THIS call, e.g. float-aligned views: the direct kernel below)
+    // grad_w: an MFMA kernel with the pixels on K + reduce (+ corner-tap mask), where the plan for these activations has one
+    if (grad_w_canon && workspace && workspace_bytes >= ws.bank + ws.partials) {
+        const FincGradwPlan p = finc_gradw_plan(s, finc_align(grad_z, x));
+        if (p.form) {
+            if (int e = finc_gradw_launch(grad_z, x, grad_w_canon, (char *)workspace + ws.bank, s, p, st)) return e;
+            grad_w_canon = nullptr;
+        }
     }
     if (!grad_x && !grad_w_canon) return FINC_OK;
     return finc_launch_backward_generic(grad_z, x, w_canon, grad_x, grad_w_canon, s, st);

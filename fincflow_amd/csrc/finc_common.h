@@ -207,11 +207,35 @@ bool finc_wino5_takes(const FincShape &s, int align);
 int finc_wino5_pack(const float *wc, void *packed, int G, int Cq, bool transpose, hipStream_t st, const float *scale, const float *shift);
 int finc_wino5_launch(const float *in, const void *packed, float *out, const FincShape &s, hipStream_t st);
 unsigned finc_build_flags_wino5();
-size_t finc_gradw_workspace_bytes(const FincShape &s); // 0: no MFMA grad-weight kernel for this shape
-int finc_gradw_launch(const float *gz, const float *x, float *gw, void *workspace, const FincShape &s, hipStream_t st);
-int finc_gradw_variant(const FincShape &s);   // 0 direct, 1 dword MFMA, 2 staged, 3 tiled, 4 Winograd, 5 Winograd tiled
 // info[0..2] = {waves per strip (K-split), staged form (1) or dword form (0), strips per slab}; FINC_ERR_UNSUPPORTED: direct kernel
 int finc_conv_variant(int B, int G, int Cq, int H, int W, int KH, int KW, int *info);
+
+// ---- weight gradient, MFMA kernels + a reduce: finc_gradw.hip ----
+// Which kernel a call runs and on which grid: finc_gradw_plan is the one place this is decided (the run-time switches are read there);
+// finc_gradw_launch runs the plan, finc_gradw_variant and finc_gradw_workspace_bytes read it.  `align`: bytes gz and x are both
+// aligned to (finc_align).
+typedef void (*finc_gradw_fn)(const float *, const float *, float *, int, int, int, int, int, int, int, unsigned);
+typedef void (*finc_gradw_pair_fn)(const float *, const float *, float *, int, int, int, int, int, int, int, unsigned, int);
+typedef void (*finc_gradw_pair_reduce_fn)(const float *, float *, int, int, int, int);
+struct FincGradwPlan {
+    int form = 0;         // 0 none (the direct kernel, finc_generic.hip), 1 dword MFMA, 2 staged, 3 tiled, 4 Winograd, 5 Winograd tile-pair
+    finc_gradw_fn fn = nullptr;             // main kernel of forms 1, 2, 4 ...
+    finc_gradw_pair_fn fn_pair = nullptr;   // ... of forms 3, 5: one (o, i) tile pair per workgroup (takes mtt)
+    dim3 grid, block = dim3(64);
+    int wpg = 0;                            // workgroups per group: the partials the reduce sums
+    int strip = 16, ns = 0;                 // strip width in columns, strips per row
+    int mtt = 0;                            // 16-channel tiles on each side of the bank
+    int cqp = 0, fs = 1;                    // form 4: the bank, waves per workgroup (frequency split)
+    // the reduce: form 4 gradw_wino_reduce_kernel, form 5 this one (gradw_winot_reduce_kernel<KW>), forms 1..3 gradw_reduce_kernel
+    finc_gradw_pair_reduce_fn reduce_pair = nullptr;
+    dim3 rgrid;                             // the reduce's grid (blocks of 256 threads)
+    size_t bytes = 0;                       // partial sums in the workspace
+};
+FincGradwPlan finc_gradw_plan(const FincShape &s, int align);
+int finc_gradw_launch(const float *gz, const float *x, float *gw, void *workspace, const FincShape &s, const FincGradwPlan &p,
+                      hipStream_t st);
+int finc_gradw_variant(const FincShape &s);             // finc_gradw_plan(s, 16).form
+size_t finc_gradw_workspace_bytes(const FincShape &s);  // room for the plans of 16-byte and of float-aligned activations (0: none)
 
 // ---- double precision on the matrix cores: finc_f64.hip (the c2 / c3 class of banks: Cq <= 24 at 3x3, <= 32 at 2x2) ----
 bool finc_f64_supported(const FincShape &s);

@@ -1282,17 +1282,15 @@ __global__ __launch_bounds__(256) void gradw_winot_reduce_kernel(const float *__
     for (int t = 0; t < KW; ++t) o[t] = k[t];
 }
 
-typedef void (*gradw_fn)(const float *, const float *, float *, int, int, int, int, int, int, int, unsigned);
-typedef void (*gradw_tiled_fn)(const float *, const float *, float *, int, int, int, int, int, int, int, unsigned, int);
 struct GradwInst {
     int cqp, kh, kw;
-    int mtg;            // ceil(Cq/16) tiles in both dimensions of the partial layout
-    gradw_fn gw;        // dword loads, any W (nullptr: NTAP*MT*MT accumulators would not fit)
-    gradw_fn gw_staged; // W % 4 == 0, 16-byte aligned activations (nullptr: none)
-    gradw_tiled_fn gw_tiled;   // one (o, i) tile pair per workgroup, same conditions: for the banks gw cannot hold (nullptr: KW > 5)
+    int mtg;                      // ceil(Cq/16) tiles in both dimensions of the partial layout
+    finc_gradw_fn gw;             // dword loads, any W (nullptr: NTAP*MT*MT accumulators would not fit)
+    finc_gradw_fn gw_staged;      // W % 4 == 0, 16-byte aligned activations (nullptr: none)
+    finc_gradw_pair_fn gw_tiled;  // one (o, i) tile pair per workgroup, same conditions: for the banks gw cannot hold (nullptr: KW > 5)
 };
 template <int CQP, int KH, int KW>
-constexpr gradw_fn gradw_staged_fn()
+constexpr finc_gradw_fn gradw_staged_fn()
 {
     constexpr int MTG = (CQP + 15) / 16, NTAP = KH * KW;
     // 4-row blocks for the channels behind the last full 16 where their accumulators fit beside the operand slots
@@ -1326,32 +1324,22 @@ const GradwInst g_gradw[] = {
 // the Winograd form: 3x3 banks of 16 (one wave holds all six frequencies), 24 and 32 channels (two waves, three each)
 struct GradwWinoInst {
     int cqp, kh, fs;
-    gradw_fn fn, fn32;      // strips of 16 columns / of 32 (maps at least 32 wide: 128-byte rows per request, half the steps)
+    finc_gradw_fn fn, fn32; // strips of 16 columns / of 32 (maps at least 32 wide: 128-byte rows per request, half the steps)
 };
 const GradwWinoInst g_gradw_wino[] = {
     {16, 3, 1, finc_gradw_wino_kernel<16, 3, 1, 1>, finc_gradw_wino_kernel<16, 3, 1, 2>},
     {24, 3, 2, finc_gradw_wino_kernel<24, 3, 2, 1>, finc_gradw_wino_kernel<24, 3, 2, 2>},
     {32, 3, 2, finc_gradw_wino_kernel<32, 3, 2, 1>, finc_gradw_wino_kernel<32, 3, 2, 2>},
 };
-static int gradw_wino_strip(const FincShape &s)
+const GradwWinoInst *find_gradw_wino(int Cq, int KH)
 {
-    static const char *force = finc_env("FINC_GRADW_WINO_STRIP");             // experiment switch: 16 / 32
-    if (force) return atoi(force) == 32 ? 32 : 16;
-    return s.W >= 32 ? 32 : 16;
-}
-const GradwWinoInst *find_gradw_wino(const FincShape &s)
-{
-    static const bool off = finc_env("FINC_GRADW_NO_WINO") != nullptr;      // experiment switch
-    static const char *pmax = finc_env("FINC_GRADW_WINO_PAIR_MAX");         // experiment switch: larger banks go to the tile-pair form
-    if (off || s.KW != 3 || s.W % 4 != 0 || s.Cq <= 12 || (pmax && s.Cq > atoi(pmax))) return nullptr;
     const GradwWinoInst *best = nullptr;
     for (const GradwWinoInst &i : g_gradw_wino)
-        if (i.cqp >= s.Cq && i.kh == s.KH && (!best || i.cqp < best->cqp)) best = &i;
+        if (i.cqp >= Cq && i.kh == KH && (!best || i.cqp < best->cqp)) best = &i;
     return best;
 }
-// the smallest compiled bank that holds Cq channels (every kernel here tests `channel < CQ` per lane: any padding is fine)
 // the tile-pair kernels take any tile count: the filter shapes they are compiled for
-gradw_tiled_fn tiled_for(int KH, int KW)
+finc_gradw_pair_fn tiled_for(int KH, int KW)
 {
     switch (KH * 8 + KW) {
     case 2 * 8 + 2: return finc_gradw_tiled_kernel<2, 2>;
@@ -1366,166 +1354,139 @@ gradw_tiled_fn tiled_for(int KH, int KW)
     return nullptr;
 }
 
-const GradwInst *find_gradw(int Cq, int KH, int KW)
+// the smallest compiled bank that holds Cq channels (every kernel here tests `channel < CQ` per lane: any padding is fine);
+// cqp == 0: none
+GradwInst find_gradw(int Cq, int KH, int KW)
 {
     const GradwInst *best = nullptr;
     for (const GradwInst &i : g_gradw)
         if (i.cqp >= Cq && i.kh == KH && i.kw == KW && (!best || i.cqp < best->cqp)) best = &i;
-    if (best) return best;
+    if (best) return *best;
     // banks beyond the table (the forward / grad-input of these run on the streaming-bank kernel, finc_stream.hip): one
     // (o, i) tile pair per workgroup, whatever the number of tiles
-    const gradw_tiled_fn t = tiled_for(KH, KW);
-    if (!t || Cq < 1 || Cq > FINC_MAX_CQ) return nullptr;
-    static thread_local GradwInst gen;
+    const finc_gradw_pair_fn t = tiled_for(KH, KW);
+    if (!t || Cq < 1 || Cq > FINC_MAX_CQ) return GradwInst{};
     const int cqp = (Cq + 15) / 16 * 16;
-    gen = GradwInst{cqp, KH, KW, cqp / 16, nullptr, nullptr, t};
-    return &gen;
+    return GradwInst{cqp, KH, KW, cqp / 16, nullptr, nullptr, t};
 }
 
 } // namespace
 
-static int gradw_wpg(const FincShape &s)
+// workgroups per group: one per strip of `strip` columns of an image, but no more than the chip's 1,024 SIMDs hold `per_simd` waves
+// deep when a strip takes `waves` waves of each group (the Winograd pair's frequency split, the tile pairs), and no more than `cap`
+static int gradw_wpg(const FincShape &s, int strip, int waves, int per_simd, int cap)
 {
-    const int units = s.B * ((s.W + 15) / 16);
-    int w = 1024 / s.G;                                   // one wave per SIMD over all groups (G = 4: 256 per group)
-    if (w < 1) w = 1;
+    const int units = s.B * ((s.W + strip - 1) / strip);
+    int w = 1024 * per_simd / (s.G * waves);
+    w = w < 1 ? 1 : w > cap ? cap : w;
     return units < w ? units : w;
 }
-// tiled form: G * MTT^2 * WPG workgroups of one wave; about two per SIMD
-static int gradw_wpg_tiled(const FincShape &s, int mtt)
-{
-    const int units = s.B * ((s.W + 15) / 16);
-    int w = 2048 / (s.G * mtt * mtt);
-    if (w < 1) w = 1;
-    if (w > 256) w = 256;
-    return units < w ? units : w;
-}
-// Winograd form: G * FS * WPG workgroups of one wave, one per SIMD
-static int gradw_wpg_wino(const FincShape &s, int fs)
-{
-    const int sw = gradw_wino_strip(s);
-    const int units = s.B * ((s.W + sw - 1) / sw);
-    int w = 1024 / (s.G * fs);                            // one wave per SIMD over all groups (G = 4, two waves per strip: 128)
-    if (w < 1) w = 1;
-    return units < w ? units : w;
-}
-static size_t gradw_wino_bytes(const FincShape &s, const GradwWinoInst *w)
-{
-    return (size_t)s.G * w->fs * gradw_wpg_wino(s, w->fs) * (6 / w->fs) * s.KH * w->cqp * w->cqp * sizeof(float);
-}
-static bool gradw_use_tiled(const GradwInst *i, const FincShape &s) { return i && !i->gw && i->gw_tiled && s.W % 4 == 0; }
-// ... and its Winograd form: 3x3 (strips of 32 columns) and 5x5 (strips of 16)
+
+// the Winograd form on one tile pair per wave: 3x3 (F(4,3), strips of 32 columns) and 5x5 (F(2,5), strips of 16) ...
 static int gradw_winot_strip(const FincShape &s) { return s.KW == 3 ? 32 : 16; }
-static bool gradw_use_winot(const GradwInst *i, const FincShape &s)
+// ... for a shape the pair kernel does not take
+static bool gradw_winot_takes(const FincShape &s, const GradwInst &i)
 {
-    static const bool off = finc_env("FINC_GRADW_NO_WINO") != nullptr;
-    if (off || !i || s.W % 4 != 0 || s.W < gradw_winot_strip(s)) return false;
-    if (s.KH == 5 && s.KW == 5 && s.Cq > 12 && s.Cq <= 16) return true;   // one full tile: beats the staged direct kernel too
-    if (s.KH == 3 && s.KW == 3 && s.Cq > 12 && !find_gradw_wino(s)) return true;   // (only with FINC_GRADW_WINO_PAIR_MAX)
+    const bool k3 = s.KH == 3 && s.KW == 3, k5 = s.KH == 5 && s.KW == 5;
+    if (s.W < gradw_winot_strip(s)) return false;
+    if (k5 && s.Cq > 12 && s.Cq <= 16) return true;       // one full tile: beats the staged direct kernel too
+    if (k3 && s.Cq > 12) return true;                     // beyond the pair kernel's banks (or above FINC_GRADW_WINO_PAIR_MAX)
     // 9 .. 12 channels on one (3/4 full) tile pair: from a chip's worth of strips on (C = 48, 64x64, B = 256: 193 -> 125 us; c2's 64
     // images stay on the staged direct kernel: 26 against 30 us)
-    if (s.KH == 3 && s.KW == 3 && s.Cq > 8 && s.Cq <= 12 && (long long)s.B * ((s.W + 31) / 32) >= 256) return true;
-    return gradw_use_tiled(i, s) && ((s.KH == 3 && s.KW == 3) || (s.KH == 5 && s.KW == 5));
-}
-static int gradw_wpg_winot(const FincShape &s, int mtt)
-{
-    const int sw = gradw_winot_strip(s);
-    const int units = s.B * ((s.W + sw - 1) / sw);
-    int w = 2048 / (s.G * mtt * mtt);
-    if (w < 1) w = 1;
-    if (w > 256) w = 256;
-    return units < w ? units : w;
+    if (k3 && s.Cq > 8 && s.Cq <= 12 && (long long)s.B * ((s.W + 31) / 32) >= 256) return true;
+    return (k3 || k5) && !i.gw && i.gw_tiled;             // (the banks of the tiled kernel)
 }
 
-size_t finc_gradw_workspace_bytes(const FincShape &s)
+// The launch plan of a grad-weight call (finc_common.h).  The Winograd forms, the tiled kernel and the staged form move 16-byte pieces
+// of rows a multiple of 4 wide: activations that are only float-aligned (a view into a larger tensor) take the dword form, or the
+// direct kernel where the bank has none.
+FincGradwPlan finc_gradw_plan(const FincShape &s, int align)
 {
-    const GradwInst *i = find_gradw(s.Cq, s.KH, s.KW);
-    if (!i || !finc_conv_supported(s.Cq, s.H, s.W, s.KH, s.KW)) return 0;
-    // room for the form the launch picks AND the one it falls back to on unaligned activations
-    size_t need = 0;
-    auto grow = [&](size_t n) { need = n > need ? n : need; };
-    if (const GradwWinoInst *w = find_gradw_wino(s)) grow(gradw_wino_bytes(s, w));
-    if (gradw_use_winot(i, s)) grow((size_t)s.G * gradw_wpg_winot(s, i->mtg) * 6 * s.KH * i->mtg * i->mtg * 256 * sizeof(float));
-    if (gradw_use_tiled(i, s)) grow((size_t)s.G * gradw_wpg_tiled(s, i->mtg) * s.KH * s.KW * i->mtg * i->mtg * 256 * sizeof(float));
-    else if (i->gw) grow((size_t)s.G * gradw_wpg(s) * s.KH * s.KW * i->mtg * i->mtg * 256 * sizeof(float));
-    return need;
-}
-
-// FINC_ERR_UNSUPPORTED: no MFMA grad-weight kernel for this call (the caller falls back to the direct kernel)
-int finc_gradw_launch(const float *gz, const float *x, float *gw, void *workspace, const FincShape &s, hipStream_t st)
-{
-    const GradwInst *i = find_gradw(s.Cq, s.KH, s.KW);
-    if (!i) return FINC_ERR_UNSUPPORTED;
-    const int NS = (s.W + 15) / 16;
-    const bool aligned16 = (((uintptr_t)gz | (uintptr_t)x) & 15) == 0;
-    int WPG;
-    if (const GradwWinoInst *w = aligned16 ? find_gradw_wino(s) : nullptr) {
-        WPG = gradw_wpg_wino(s, w->fs);
-        const int sw = gradw_wino_strip(s);
-        hipLaunchKernelGGL(sw == 32 ? w->fn32 : w->fn, dim3(s.G * WPG), dim3(64 * w->fs), 0, st, gz, x, (float *)workspace, s.G,
-                           s.Cq, s.H, s.W, (s.W + sw - 1) / sw, s.B, WPG, s.orient);
-        FINC_CHECK_LAUNCH();
-        hipLaunchKernelGGL(gradw_wino_reduce_kernel, dim3(s.KH * w->cqp * w->cqp / 32, s.G), dim3(256), 0, st,
-                           (const float *)workspace, gw, s.Cq, w->cqp, s.KH, w->fs, WPG);
-        FINC_CHECK_LAUNCH();
-        return FINC_OK;
-    }
-    if (aligned16 && gradw_use_winot(i, s)) {
-        WPG = gradw_wpg_winot(s, i->mtg);
-        const int sw = gradw_winot_strip(s);
-        const dim3 grid(s.G * i->mtg * i->mtg * WPG);
-        const int entries = i->mtg * i->mtg * s.KH * 256;
+    // experiment switches
+    static const bool no_wino = finc_env("FINC_GRADW_NO_WINO") != nullptr;       // no Winograd form for any bank
+    static const char *pair_max = finc_env("FINC_GRADW_WINO_PAIR_MAX");         // 3x3 banks above n channels: the tile-pair form
+    static const bool no_staged = finc_env("FINC_GRADW_NO_STAGED") != nullptr;   // the dword form for every width
+    static const char *wino_strip = finc_env("FINC_GRADW_WINO_STRIP");           // the pair kernel's strips: 16 / 32 columns
+    FincGradwPlan p;
+    const GradwInst i = find_gradw(s.Cq, s.KH, s.KW);
+    if (!i.cqp || !finc_conv_supported(s.Cq, s.H, s.W, s.KH, s.KW)) return p;
+    const bool wide = align >= 16 && s.W % 4 == 0, wino = wide && !no_wino;
+    const GradwWinoInst *w =
+        (wino && s.KW == 3 && s.Cq > 12 && !(pair_max && s.Cq > atoi(pair_max))) ? find_gradw_wino(s.Cq, s.KH) : nullptr;
+    int per = 0, entries = 0;       // partial sums a workgroup writes; entries the reduce sums them into per group
+    p.mtt = i.mtg;
+    if (w) {
+        p.form = 4;
+        p.strip = wino_strip ? (atoi(wino_strip) == 32 ? 32 : 16) : s.W >= 32 ? 32 : 16;
+        p.fn = p.strip == 32 ? w->fn32 : w->fn;
+        p.cqp = w->cqp;
+        p.fs = w->fs;
+        p.wpg = gradw_wpg(s, p.strip, w->fs, 1, 1024);   // one wave per SIMD over all groups (G = 4, two waves per strip: 128)
+        p.grid = dim3(s.G * p.wpg);
+        p.block = dim3(64 * w->fs);
+        per = 6 * s.KH * w->cqp * w->cqp;
+        entries = s.KH * w->cqp * w->cqp;
+    } else if (wino && gradw_winot_takes(s, i)) {
+        p.form = 5;
+        p.strip = gradw_winot_strip(s);
         if (s.KW == 3) {
-            hipLaunchKernelGGL((finc_gradw_winot_kernel<3, 3>), grid, dim3(64), 0, st, gz, x, (float *)workspace, s.G, s.Cq, s.H, s.W,
-                               (s.W + sw - 1) / sw, s.B, WPG, s.orient, i->mtg);
-            FINC_CHECK_LAUNCH();
-            hipLaunchKernelGGL(gradw_winot_reduce_kernel<3>, dim3(entries / 32, s.G), dim3(256), 0, st, (const float *)workspace, gw, s.Cq,
-                               s.KH, i->mtg, WPG);
+            p.fn_pair = finc_gradw_winot_kernel<3, 3>;
+            p.reduce_pair = gradw_winot_reduce_kernel<3>;
         } else {
-            hipLaunchKernelGGL((finc_gradw_winot_kernel<5, 5>), grid, dim3(64), 0, st, gz, x, (float *)workspace, s.G, s.Cq, s.H, s.W,
-                               (s.W + sw - 1) / sw, s.B, WPG, s.orient, i->mtg);
-            FINC_CHECK_LAUNCH();
-            hipLaunchKernelGGL(gradw_winot_reduce_kernel<5>, dim3(entries / 32, s.G), dim3(256), 0, st, (const float *)workspace, gw, s.Cq,
-                               s.KH, i->mtg, WPG);
+            p.fn_pair = finc_gradw_winot_kernel<5, 5>;
+            p.reduce_pair = gradw_winot_reduce_kernel<5>;
         }
-        FINC_CHECK_LAUNCH();
-        return FINC_OK;
-    }
-    if (gradw_use_tiled(i, s)) {
-        if (!aligned16) return FINC_ERR_UNSUPPORTED;
-        WPG = gradw_wpg_tiled(s, i->mtg);
-        hipLaunchKernelGGL(i->gw_tiled, dim3(s.G * i->mtg * i->mtg * WPG), dim3(64), 0, st, gz, x, (float *)workspace, s.G, s.Cq,
-                           s.H, s.W, NS, s.B, WPG, s.orient, i->mtg);
-    } else {
-        if (!i->gw) return FINC_ERR_UNSUPPORTED;
-        WPG = gradw_wpg(s);
-        static const bool no_staged = finc_env("FINC_GRADW_NO_STAGED") != nullptr;   // experiment switch
-        const gradw_fn fn = (i->gw_staged && s.W % 4 == 0 && aligned16 && !no_staged) ? i->gw_staged : i->gw;
-        hipLaunchKernelGGL(fn, dim3(s.G * WPG), dim3(64), 0, st, gz, x, (float *)workspace, s.G, s.Cq, s.H, s.W, NS, s.B,
-                           WPG, s.orient);
-    }
+        p.wpg = gradw_wpg(s, p.strip, i.mtg * i.mtg, 2, 256);   // G * MTT^2 * WPG workgroups of one wave, about two per SIMD
+        p.grid = dim3(s.G * i.mtg * i.mtg * p.wpg);
+        per = 6 * s.KH * 256;
+        entries = i.mtg * i.mtg * s.KH * 256;
+    } else if (wide && !i.gw && i.gw_tiled) {
+        p.form = 3;
+        p.fn_pair = i.gw_tiled;
+        p.wpg = gradw_wpg(s, 16, i.mtg * i.mtg, 2, 256);
+        p.grid = dim3(s.G * i.mtg * i.mtg * p.wpg);
+        per = s.KH * s.KW * 256;
+        entries = s.KH * s.KW * i.mtg * i.mtg * 256;
+    } else if (i.gw) {
+        p.form = (wide && i.gw_staged && !no_staged) ? 2 : 1;
+        p.fn = p.form == 2 ? i.gw_staged : i.gw;
+        p.wpg = gradw_wpg(s, 16, 1, 1, 1024);              // one wave per SIMD over all groups (G = 4: 256 per group)
+        p.grid = dim3(s.G * p.wpg);
+        per = s.KH * s.KW * i.mtg * i.mtg * 256;
+        entries = per;
+    } else return p;
+    p.ns = (s.W + p.strip - 1) / p.strip;
+    p.rgrid = dim3(entries / 32, s.G);
+    p.bytes = (size_t)p.grid.x * per * sizeof(float);
+    return p;
+}
+
+// the main kernel, then the reduce that sums its WPG partials per entry in a fixed order and applies the corner tap's mask
+int finc_gradw_launch(const float *gz, const float *x, float *gw, void *workspace, const FincShape &s, const FincGradwPlan &p,
+                      hipStream_t st)
+{
+    if (!p.form) return FINC_ERR_UNSUPPORTED;
+    float *part = (float *)workspace;
+    if (p.fn) hipLaunchKernelGGL(p.fn, p.grid, p.block, 0, st, gz, x, part, s.G, s.Cq, s.H, s.W, p.ns, s.B, p.wpg, s.orient);
+    else hipLaunchKernelGGL(p.fn_pair, p.grid, p.block, 0, st, gz, x, part, s.G, s.Cq, s.H, s.W, p.ns, s.B, p.wpg, s.orient, p.mtt);
     FINC_CHECK_LAUNCH();
-    const int per = s.KH * s.KW * i->mtg * i->mtg * 256;
-    const int blocks = per / 32;
-    hipLaunchKernelGGL(gradw_reduce_kernel, dim3(blocks, s.G), dim3(256), 0, st, (const float *)workspace, gw, s.Cq, s.KH,
-                       s.KW, i->mtg, WPG);
+    const float *sums = part;
+    switch (p.form) {
+    case 4: hipLaunchKernelGGL(gradw_wino_reduce_kernel, p.rgrid, dim3(256), 0, st, sums, gw, s.Cq, p.cqp, s.KH, p.fs, p.wpg); break;
+    case 5: hipLaunchKernelGGL(p.reduce_pair, p.rgrid, dim3(256), 0, st, sums, gw, s.Cq, s.KH, p.mtt, p.wpg); break;
+    default: hipLaunchKernelGGL(gradw_reduce_kernel, p.rgrid, dim3(256), 0, st, sums, gw, s.Cq, s.KH, s.KW, p.mtt, p.wpg);
+    }
     FINC_CHECK_LAUNCH();
     return FINC_OK;
 }
 
-// which grad-weight kernel finc_backward_f32 runs for this shape, given 16-byte aligned activations and a full workspace:
-// 0 direct (no MFMA instantiation), 1 dword MFMA kernel, 2 staged (16-byte pieces through LDS), 3 tiled (one tile pair per workgroup),
-// 4 Winograd (transposed F(4,3): half the multiplies), 5 Winograd on one tile pair per wave (3x3: F(4,3), 5x5: F(2,5))
-int finc_gradw_variant(const FincShape &s)
+int finc_gradw_variant(const FincShape &s) { return finc_gradw_plan(s, 16).form; }
+
+// room for the partials of either plan a call can take: 16-byte aligned activations or not
+size_t finc_gradw_workspace_bytes(const FincShape &s)
 {
-    const GradwInst *i = find_gradw(s.Cq, s.KH, s.KW);
-    if (!i || finc_gradw_workspace_bytes(s) == 0) return 0;
-    if (find_gradw_wino(s)) return 4;
-    if (gradw_use_winot(i, s)) return 5;
-    if (gradw_use_tiled(i, s)) return 3;
-    if (!i->gw) return 0;
-    static const bool no_staged = finc_env("FINC_GRADW_NO_STAGED") != nullptr;
-    return (i->gw_staged && s.W % 4 == 0 && !no_staged) ? 2 : 1;
+    const size_t a = finc_gradw_plan(s, 16).bytes, u = finc_gradw_plan(s, 4).bytes;
+    return a > u ? a : u;
 }
 
 unsigned finc_build_flags_gradw() { return FINC_BUILD_FLAGS; }

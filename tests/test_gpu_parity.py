@@ -936,6 +936,48 @@ def test_unaligned_activations_fall_back(dev):
             assert rel_err(xbuf[1:n + 1].cpu().numpy().reshape(z.shape), oracle.inverse_via_f64(z, wco)) <= 1e-5
 
 
+# (B, C, H, W, K, grad-weight form for 16-byte aligned activations): one shape per form that moves 16-byte pieces.  Float-aligned
+# activations take the dword form instead, or the direct kernel where the bank has none (the tiled kernel's banks).
+FLOAT_ALIGNED_BACKWARD_CASES = [
+    (3, 96, 12, 32, 3, "winograd"),          # c3's bank -> dword
+    (2, 192, 8, 32, 3, "winograd_tiled"),    # Cq = 48 3x3 -> direct
+    (2, 64, 7, 32, 5, "winograd_tiled"),     # Cq = 16 5x5 -> dword
+    (2, 192, 10, 16, 3, "tiled"),            # Cq = 48 3x3 -> direct
+    (2, 48, 9, 32, 3, "staged"),             # c2's bank -> dword
+]
+
+
+@pytest.mark.parametrize("case", FLOAT_ALIGNED_BACKWARD_CASES, ids=lambda c: "B%d_C%d_%dx%d_k%d_%s" % c)
+def test_backward_on_float_aligned_views(case, dev):
+    """grad_z and x whose data start 4 bytes into the allocation (as in test_unaligned_activations_fall_back): finc_backward_f32
+    runs the grad-weight plan for such activations.  grad_x and grad_w agree with the same call on aligned tensors, and the
+    masked entries of grad_w are exact zeros."""
+    from fincflow_amd import _lib, ops
+    B, C, H, W, K, form = case
+    Cq = C // 4
+    assert _lib.backward_variant(B, 4, Cq, H, W, K, K)["gradw"] == form
+    torch.manual_seed(sum(case[:5]))
+    wc = canon(oracle.make_stored_weights(4, Cq, K, K), 4, ORIENT_FASTFLOW, dev)
+    x = torch.randn(B, C, H, W, device=dev)
+    gz = torch.randn(B, C, H, W, device=dev)
+
+    def float_aligned(a):
+        v = torch.zeros(a.numel() + 8, device=dev)[1:a.numel() + 1].view(a.shape)
+        v.copy_(a)
+        return v
+
+    xu, gzu = float_aligned(x), float_aligned(gz)
+    assert xu.data_ptr() % 16 == 4 and gzu.data_ptr() % 16 == 4
+    gx, gw = ops.finc_backward(gz, x, wc, 4, ORIENT_FASTFLOW)
+    gxu, gwu = ops.finc_backward(gzu, xu, wc, 4, ORIENT_FASTFLOW)
+    assert rel_err(gxu.cpu().numpy(), gx.cpu().numpy()) <= TOL
+    assert rel_err(gwu.cpu().numpy(), gw.cpu().numpy()) <= TOL
+    mask = torch.ones_like(wc)
+    for c in range(Cq):
+        mask.view(4, Cq, Cq, K, K)[:, c, c:, -1, -1] = 0
+    assert torch.all(gwu[mask == 0] == 0)
+
+
 # (B, C, H, W): every bank of the Winograd kernels (Cq = 4 .. 24, padded channel counts among them), widths that fill one,
 # two and three strips of 64 columns and leave a partial last strip, maps shorter than the two-row prologue, row chunks
 FORWARD_FORM_CASES = [(2, 96, 20, 64), (3, 80, 9, 60), (2, 64, 12, 128), (2, 48, 64, 64), (5, 32, 7, 68), (2, 16, 16, 136),
