@@ -31,7 +31,11 @@ SYMBOLS = [
     "finc_debug_row_chunks", "finc_debug_inverse_remainder_images",
     "finc_inverse_affine_supported", "finc_fault_pending", "finc_runtime_switches",
     "finc_debug_clock_probe_begin", "finc_debug_clock_probe_end",
+    "finc_mix_backward_workspace_bytes", "finc_mix_backward_f32",
 ]
+
+#: the ABI version this binding is written against (include/finc.h: finc_version)
+ABI_VERSION = 103
 
 _lib = None
 
@@ -50,7 +54,15 @@ def lib():
             "(or `make -C fincflow_amd/csrc`).  fincflow_amd has no CPU / PyTorch fallback.")
     L = ctypes.CDLL(LIB_PATH)
     vp, i, u, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_size_t
-    L.finc_version.restype = i
+    # the version first: an older build (FINCFLOW_LIB) lacks symbols bound below, and an AttributeError from ctypes would not say why
+    try:
+        L.finc_version.restype = i
+        have = int(L.finc_version())
+    except AttributeError:
+        raise FincError(f"{LIB_PATH} does not export finc_version: not a build of libfinc_hip.so") from None
+    if have < ABI_VERSION:
+        raise FincError(f"{LIB_PATH} reports finc_version() = {have}, this package needs at least {ABI_VERSION}: rebuild it "
+                        "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
     L.finc_build_flags.restype = u
     L.finc_clear_fault.restype = i
     L.finc_status_string.restype = ctypes.c_char_p
@@ -102,6 +114,9 @@ def lib():
     L.finc_debug_set_forward_form.argtypes = [i]
     L.finc_mix_supported_f32.argtypes = [i]
     L.finc_mix_f32.argtypes = [vp, vp, vp, vp, i, i, i, vp]
+    L.finc_mix_backward_workspace_bytes.restype = sz
+    L.finc_mix_backward_workspace_bytes.argtypes = [i, i, i]
+    L.finc_mix_backward_f32.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp]
     for name in SYMBOLS:
         getattr(L, name)  # AttributeError here = header and library out of sync
     _lib = L

@@ -174,7 +174,7 @@ static int canonicalize(const T *w_stored, T *w_canon, int G, int Cq, int KH, in
 
 extern "C" {
 
-int finc_version(void) { return 102; }
+int finc_version(void) { return 103; }
 
 unsigned finc_build_flags(void)
 {
@@ -555,6 +555,38 @@ int finc_mix_f32(const float *in, const float *mat, const float *bias, float *ou
     if ((size_t)B * C * HW >= ((size_t)1 << 40)) return FINC_ERR_BAD_DIMS;
     if (int e = finc_fault_gate(false)) return e;
     return finc_mix_launch(in, mat, bias, out, B, C, HW, (hipStream_t)stream);
+}
+
+size_t finc_mix_backward_workspace_bytes(int B, int C, int HW)
+{
+    if (B <= 0 || C <= 0 || HW <= 0) return 256;
+    const size_t n = align256(finc_mix_gradw_workspace_bytes(B, C, HW));
+    return n < 256 ? 256 : n;
+}
+
+int finc_mix_backward_f32(const float *grad_out, const float *in, const float *mat, float *grad_in, float *grad_mat, float *grad_bias,
+                          int B, int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    if (!grad_out || !mat || (!grad_in && !grad_mat && !grad_bias) || (grad_mat && !in)) return FINC_ERR_NULL_POINTER;
+    if (B <= 0 || C <= 0 || HW <= 0 || C > FINC_MAX_CQ * FINC_MAX_GROUPS) return FINC_ERR_BAD_DIMS;
+    if ((size_t)B * C * HW >= ((size_t)1 << 40)) return FINC_ERR_BAD_DIMS;
+    if (grad_in && (grad_in == grad_out || grad_in == in)) return FINC_ERR_BAD_DIMS;
+    if (misaligned(grad_out) || misaligned(mat) || (in && misaligned(in)) || (grad_in && misaligned(grad_in)) ||
+        (grad_mat && misaligned(grad_mat)) || (grad_bias && misaligned(grad_bias)))
+        return FINC_ERR_ALIGNMENT;
+    if (!finc_mix_supported(C)) return FINC_ERR_UNSUPPORTED;
+    if ((grad_mat || grad_bias) && (!workspace || misaligned(workspace) || workspace_bytes < finc_mix_backward_workspace_bytes(B, C, HW)))
+        return FINC_ERR_WORKSPACE;
+    if (int e = finc_fault_gate(false)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    // grad_in = mat^T * grad_out: the forward kernel, its fragments read transposed from the same matrix
+    if (grad_in)
+        if (int e = finc_mix_launch(grad_out, mat, nullptr, grad_in, B, C, HW, st, true)) return e;
+    // grad_mat, grad_bias: pixels on the MFMA K dimension, partial tiles in the workspace, then a fixed-order reduce (finc_gradw.hip)
+    if (grad_mat || grad_bias)
+        return finc_mix_gradw_launch(grad_out, in, grad_mat, grad_bias, workspace, B, C, HW, finc_align(grad_out, grad_mat ? in : grad_out),
+                                     st);
+    return FINC_OK;
 }
 
 int finc_debug_backward_variant(int B, int G, int Cq, int H, int W, int KH, int KW, int *info)

@@ -246,4 +246,11 @@ unsigned finc_build_flags_f64();
 
 // ---- per-pixel channel mixing (1x1 conv + folded affine): finc_mix.hip ----
 bool finc_mix_supported(int C);
-int finc_mix_launch(const float *in, const float *mat, const float *bias, float *out, int B, int C, int HW, hipStream_t st);
+// transposed: out = mat^T * in (+ bias), `mat` still the row-major forward matrix (the mix's grad-input)
+int finc_mix_launch(const float *in, const float *mat, const float *bias, float *out, int B, int C, int HW, hipStream_t st,
+                    bool transposed = false);
+// weight and bias gradient of the mix, pixels on the MFMA K dimension + a fixed-order reduce: finc_gradw.hip.  `align`: bytes
+// grad_out and in are both aligned to (finc_align); gm or gb may be nullptr (in may be nullptr with gm)
+size_t finc_mix_gradw_workspace_bytes(int B, int C, int HW);     // 0: no instantiation for C
+int finc_mix_gradw_launch(const float *grad_out, const float *in, float *gm, float *gb, void *workspace, int B, int C, int HW,
+                          int align, hipStream_t st);

@@ -1489,4 +1489,260 @@ size_t finc_gradw_workspace_bytes(const FincShape &s)
     return a > u ? a : u;
 }
 
+// -----------------------------------------------------------------------------------------------
+// Weight and bias gradient of the per-pixel channel mix (finc_mix.hip; autograd through F.conv2d, layers/conv1x1.py:29-31):
+//     gm[o][i] = sum_{b,p} go[b,o,p] * x[b,i,p],     gb[o] = sum_{b,p} go[b,o,p]          (fp32, NCHW, HW = H*W)
+// The PIXELS are the MFMA K dimension, as in the kernels above: A = go, B = x, both with lane (q,m) = channel 16t+m, pixel slot q,
+// D = a 16x16 (o, i) tile kept in an accumulator for the whole kernel.  Both operands have the same lane layout, so the pixels of
+// a chunk may be handed to the k-slots in any order as long as both sides use the same one: a chunk is 16 consecutive pixels of one
+// image, lane (q,m) loads pixels 4q .. 4q+3 of its channel as ONE 16-byte piece (the four lane rows of a channel ask for 64
+// contiguous bytes), and register k of the piece is the operand of k-step k.  V = 1 is the same walk on dword loads, for pixel counts
+// that are not a multiple of 4 and activations that are only float-aligned.
+// The MT x MT tile grid (MT = ceil(C/16); C = 192: 144 tiles) is split over the WO x WI waves of a workgroup: wave (wo, wi) owns TO x TI
+// tiles and loads only their TO + TI channel tiles; the waves share nothing but the chunk walk (and so the L1 lines).  A workgroup walks
+// a run of consecutive chunks of the B * ceil(HW/16) chunks, the operands of the next chunk in flight during the MFMAs of this one (two register
+// sets, the loop unrolled by two), and writes its partial tiles: part[s * per + (mo * MT + mi) * 256 + r * 64 + lane], D layout.
+// The bias sum needs no MFMA: a lane adds up the go values it loaded anyway (VALU, beside the MFMAs), the four lane rows of a channel meet
+// once at the end, part[s * per + MT*MT*256 + channel].  mix_gradw_reduce_kernel sums the NS partials per entry in a fixed order.
+// -----------------------------------------------------------------------------------------------
+namespace {
+
+template <int C, int TO, int TI, int WO, int WI, int V>
+__global__ __launch_bounds__((64 * WO * WI)) void finc_mix_gradw_kernel(const float *__restrict__ go, const float *__restrict__ x,
+                                                                      float *__restrict__ part, int HW, int chunks_per_image,
+                                                                      int total_chunks, int chunks_per_stream, int per, int do_mat)
+{
+    constexpr int MT = (C + 15) / 16;
+    static_assert(TO * WO == MT && TI * WI == MT, "the waves' tiles cover the tile grid");
+    static_assert(WO * WI == 1 || C % 16 == 0, "a partial tile is only tested for where the tile index is a constant");
+    static_assert(V == 1 || V == 4, "dwords or 16-byte pieces");
+    typedef unsigned v4u __attribute__((ext_vector_type(4)));
+    const int lane = threadIdx.x & 63;
+    const int q = lane >> 4, m = lane & 15;
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int wo = wv / WI, wi = wv % WI;
+    const int to0 = wo * TO, ti0 = wi * TI;                        // first tile of this wave on either side
+    const unsigned img_bytes = (unsigned)C * (unsigned)HW * 4u;
+    const unsigned rowpart = (unsigned)m * (unsigned)HW * 4u;      // lane part of an offset: channel m of a tile
+    const int tile_step = 16 * HW * 4;                             // bytes between two channel tiles
+
+    v4f acc[TO][TI];
+    float bs[TO];
+#pragma unroll
+    for (int a = 0; a < TO; ++a) {
+        bs[a] = 0.f;
+#pragma unroll
+        for (int b = 0; b < TI; ++b) acc[a][b] = (v4f){0.f, 0.f, 0.f, 0.f};
+    }
+    // a workgroup's chunks are CONSECUTIVE: the 64-byte pieces of a channel row that two chunks in a row ask for share a 128-byte line,
+    // which the same compute unit then asks for twice (dealt out as s, s + NS, ... the halves went to different workgroups: c3 372 us,
+    // consecutive 285 us)
+    const int end = min((blockIdx.x + 1) * chunks_per_stream, total_chunks);
+    // channels >= C exist only in the last tile: their lanes point beyond the image and read zeros
+    auto chan_ok = [&](int t) { return C % 16 == 0 || t < MT - 1 || 16 * t + m < C; };
+
+    auto load = [&](v4f (&A)[TO], v4f (&Bx)[TI], int chunk) {
+        const bool live = chunk < end;                             // (past the end: every lane invalid, the MFMAs add zeros)
+        const int cc = live ? chunk : 0;
+        const int b = __builtin_amdgcn_readfirstlane(cc / chunks_per_image), ci = cc - b * chunks_per_image;
+        const __amdgpu_buffer_rsrc_t rg =
+            __builtin_amdgcn_make_buffer_rsrc((void *)(go + (size_t)b * C * HW), 0, (int)img_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rx =
+            __builtin_amdgcn_make_buffer_rsrc((void *)(x + (size_t)b * C * HW), 0, (int)img_bytes, 0x00020000);
+        const int pix = ci * 16 + 4 * q;
+        if constexpr (V == 4) {
+            const bool ok = live && pix < HW;                      // (HW % 4 == 0: a piece is inside the row or outside)
+            const unsigned vo = ok ? (unsigned)pix * 4u + rowpart : OFF_INVALID;
+#pragma unroll
+            for (int a = 0; a < TO; ++a) {
+                const v4u v = __builtin_amdgcn_raw_buffer_load_b128(rg, chan_ok(to0 + a) ? vo : OFF_INVALID, (to0 + a) * tile_step, 0);
+                A[a] = __builtin_bit_cast(v4f, v);
+            }
+            if (do_mat) {
+#pragma unroll
+                for (int c = 0; c < TI; ++c) {
+                    const v4u v = __builtin_amdgcn_raw_buffer_load_b128(rx, chan_ok(ti0 + c) ? vo : OFF_INVALID, (ti0 + c) * tile_step, 0);
+                    Bx[c] = __builtin_bit_cast(v4f, v);
+                }
+            }
+        } else {
+            unsigned vo[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) vo[k] = (live && pix + k < HW) ? (unsigned)(pix + k) * 4u + rowpart : OFF_INVALID;
+#pragma unroll
+            for (int a = 0; a < TO; ++a) {
+                float e[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    e[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rg, chan_ok(to0 + a) ? vo[k] : OFF_INVALID,
+                                                                                          (to0 + a) * tile_step, 0));
+                A[a] = (v4f){e[0], e[1], e[2], e[3]};
+            }
+            if (do_mat) {
+#pragma unroll
+                for (int c = 0; c < TI; ++c) {
+                    float e[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        e[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, chan_ok(ti0 + c) ? vo[k] : OFF_INVALID,
+                                                                                              (ti0 + c) * tile_step, 0));
+                    Bx[c] = (v4f){e[0], e[1], e[2], e[3]};
+                }
+            }
+        }
+    };
+    auto mma = [&](const v4f (&A)[TO], const v4f (&Bx)[TI]) {
+#pragma unroll
+        for (int a = 0; a < TO; ++a) bs[a] += (A[a].x + A[a].y) + (A[a].z + A[a].w);
+        if (do_mat) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+#pragma unroll
+                for (int a = 0; a < TO; ++a)
+#pragma unroll
+                    for (int c = 0; c < TI; ++c) acc[a][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[a][k], Bx[c][k], acc[a][c], 0, 0, 0);
+        }
+    };
+
+    v4f A0[TO], B0[TI], A1[TO], B1[TI];
+#pragma unroll
+    for (int c = 0; c < TI; ++c) { B0[c] = (v4f){0.f, 0.f, 0.f, 0.f}; B1[c] = (v4f){0.f, 0.f, 0.f, 0.f}; }
+    int chunk = blockIdx.x * chunks_per_stream;
+    load(A0, B0, chunk);
+    for (; chunk < end; chunk += 2) {
+        load(A1, B1, chunk + 1);
+        __builtin_amdgcn_sched_barrier(0);
+        mma(A0, B0);
+        __builtin_amdgcn_sched_barrier(0);
+        load(A0, B0, chunk + 2);
+        __builtin_amdgcn_sched_barrier(0);
+        mma(A1, B1);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+
+    float *dst = part + (size_t)blockIdx.x * per;
+    if (do_mat) {
+#pragma unroll
+        for (int a = 0; a < TO; ++a)
+#pragma unroll
+            for (int c = 0; c < TI; ++c) {
+                const v4f v = acc[a][c];
+                const float v0 = v.x, v1 = v.y, v2 = v.z, v3 = v.w;
+                float *d = dst + ((to0 + a) * MT + (ti0 + c)) * 256 + lane;
+                d[0] = v0; d[64] = v1; d[128] = v2; d[192] = v3;
+            }
+    }
+    if (wi == 0) {                                                 // the four lane rows of a channel, in a fixed order
+#pragma unroll
+        for (int a = 0; a < TO; ++a) {
+            float v = bs[a];
+            v += __shfl_xor(v, 16, 64);
+            v += __shfl_xor(v, 32, 64);
+            if (q == 0) dst[MT * MT * 256 + 16 * (to0 + a) + m] = v;
+        }
+    }
+}
+
+// gm[o][i] / gb[o] = sum over the NS partials; D layout: lane (q,n), reg r -> o = 16mo+4q+r, i = 16mi+n, the bias sums behind the
+// tiles.  As gradw_reduce_kernel: a block of 256 threads owns 32 consecutive entries, its 8 thread groups sum 8 interleaved slices
+// of the partials and the slices meet in LDS in a FIXED order -- the same bits on every run.  An output that is not wanted (nullptr) is
+// neither read nor written.
+__global__ __launch_bounds__(256) void mix_gradw_reduce_kernel(const float *__restrict__ part, float *__restrict__ gm,
+                                                               float *__restrict__ gb, int C, int MT, int NS, int per)
+{
+    __shared__ float slice[8][32];
+    const int el = threadIdx.x & 31, j = threadIdx.x >> 5;
+    const int e = blockIdx.x * 32 + el;                    // per is a multiple of 256: every block is full, and on one side of the tiles' end
+    const bool tiles = e < MT * MT * 256;
+    if (tiles ? gm == nullptr : gb == nullptr) return;     // (uniform per block)
+    float s;
+    const float *p = part + e;
+    {
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+        int w = j;
+        for (; w + 24 < NS; w += 32) {
+            s0 += p[(size_t)w * per]; s1 += p[(size_t)(w + 8) * per]; s2 += p[(size_t)(w + 16) * per]; s3 += p[(size_t)(w + 24) * per];
+        }
+        for (; w < NS; w += 8) s0 += p[(size_t)w * per];
+        s = (s0 + s1) + (s2 + s3);
+    }
+    slice[j][el] = s;
+    __syncthreads();
+    if (j != 0) return;
+    s = ((slice[0][el] + slice[1][el]) + (slice[2][el] + slice[3][el])) + ((slice[4][el] + slice[5][el]) + (slice[6][el] + slice[7][el]));
+    if (tiles) {
+        const int lane = e & 63, r = (e >> 6) & 3, tile = e >> 8;
+        const int mi = tile % MT, mo = tile / MT;
+        const int oc = 16 * mo + 4 * (lane >> 4) + r, ic = 16 * mi + (lane & 15);
+        if (oc < C && ic < C) gm[(size_t)oc * C + ic] = s;
+    } else {
+        const int c = e - MT * MT * 256;
+        if (c < C) gb[c] = s;
+    }
+}
+
+typedef void (*mix_gradw_fn)(const float *, const float *, float *, int, int, int, int, int, int);
+struct MixGradwInst {
+    int C, waves;          // channels; waves of a workgroup (the split of the tile grid)
+    int wgs_per_cu;        // workgroups a compute unit holds (registers): the persistent grid's cap
+    mix_gradw_fn fn[2];    // [dwords / 16-byte pieces]
+};
+template <int C, int TO, int TI, int WO, int WI>
+constexpr MixGradwInst make_mix_gradw(int wgs_per_cu)
+{
+    return MixGradwInst{C, WO * WI, wgs_per_cu, {finc_mix_gradw_kernel<C, TO, TI, WO, WI, 1>, finc_mix_gradw_kernel<C, TO, TI, WO, WI, 4>}};
+}
+// the channel counts of finc_mix.hip's table.  Up to 64 channels one wave holds the whole tile grid (<= 16 tiles); 96 and 128: 2 x 2
+// waves of 3 x 3 / 4 x 4 tiles; 192: 2 x 4 waves of 6 x 3 tiles (72 accumulator registers, two waves per SIMD)
+const MixGradwInst g_mix_gradw[] = {
+    make_mix_gradw<4, 1, 1, 1, 1>(8),   make_mix_gradw<8, 1, 1, 1, 1>(8),   make_mix_gradw<12, 1, 1, 1, 1>(8),  make_mix_gradw<16, 1, 1, 1, 1>(8),
+    make_mix_gradw<24, 2, 2, 1, 1>(8),  make_mix_gradw<32, 2, 2, 1, 1>(8),  make_mix_gradw<48, 3, 3, 1, 1>(8),  make_mix_gradw<64, 4, 4, 1, 1>(8),
+    make_mix_gradw<96, 3, 3, 2, 2>(4),  make_mix_gradw<128, 4, 4, 2, 2>(3), make_mix_gradw<192, 6, 3, 2, 4>(1),
+};
+const MixGradwInst *find_mix_gradw(int C)
+{
+    for (const MixGradwInst &i : g_mix_gradw)
+        if (i.C == C) return &i;
+    return nullptr;
+}
+int mix_gradw_per(int C) { const int mt = (C + 15) / 16; return mt * mt * 256 + 256; }   // floats of one partial: the tiles, then the bias sums
+
+} // namespace
+
+// Workgroups (= partials) of a call: one per 16 chunks or more, at most what the chip holds at once.  The workspace is sized by the pixel count
+// alone -- a call never has more chunks than pixels -- so it never shrinks when B * HW grows.
+size_t finc_mix_gradw_workspace_bytes(int B, int C, int HW)
+{
+    const MixGradwInst *i = find_mix_gradw(C);
+    if (!i || B < 1 || HW < 1) return 0;
+    const long long pixels = (long long)B * HW, cap = 256LL * i->wgs_per_cu;
+    const long long ns = pixels < cap ? pixels : cap;
+    return (size_t)ns * mix_gradw_per(C) * sizeof(float);
+}
+
+int finc_mix_gradw_launch(const float *grad_out, const float *in, float *gm, float *gb, void *workspace, int B, int C, int HW,
+                          int align, hipStream_t st)
+{
+    const MixGradwInst *i = find_mix_gradw(C);
+    if (!i) return FINC_ERR_UNSUPPORTED;
+    if (!gm && !gb) return FINC_OK;
+    const int cpi = (HW + 15) / 16;
+    const long long total = (long long)B * cpi;
+    if ((size_t)C * HW * 4 >= ((size_t)1 << 31) || total >= (1LL << 31) - 8192) return FINC_ERR_BAD_DIMS;
+    long long ns = total / 16;
+    const long long cap = 256LL * i->wgs_per_cu;
+    ns = ns < 1 ? 1 : ns > cap ? cap : ns;
+    const long long cps = (total + ns - 1) / ns;                   // consecutive chunks per workgroup ...
+    ns = (total + cps - 1) / cps;                                  // ... and no workgroup without one
+    const int per = mix_gradw_per(C);
+    float *part = (float *)workspace;
+    const mix_gradw_fn fn = i->fn[(align >= 16 && HW % 4 == 0) ? 1 : 0];
+    hipLaunchKernelGGL(fn, dim3((unsigned)ns), dim3(64 * i->waves), 0, st, grad_out, gm ? in : grad_out, part, HW, cpi, (int)total, (int)cps, per,
+                       gm ? 1 : 0);
+    FINC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(mix_gradw_reduce_kernel, dim3(per / 32), dim3(256), 0, st, (const float *)part, gm, gb, C, (C + 15) / 16, (int)ns, per);
+    FINC_CHECK_LAUNCH();
+    return FINC_OK;
+}
+
 unsigned finc_build_flags_gradw() { return FINC_BUILD_FLAGS; }

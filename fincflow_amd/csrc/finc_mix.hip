@@ -91,19 +91,20 @@ struct PixVec<4> {
 template <int MTN, int NK, int PX, int WGW>
 __global__ __launch_bounds__((64 * WGW)) void finc_mix_kernel(const float *__restrict__ in, const float *__restrict__ mat,
                                                            const float *__restrict__ bias, float *out, int C, int HW,
-                                                           int chunks_per_image, int total_chunks)
+                                                           int chunks_per_image, int total_chunks, int transposed)
 {
     extern __shared__ __attribute__((aligned(16))) float afrag[];   // [(mt*(NK+1) + j)*64 + lane]
     const int lane = threadIdx.x & 63;
     const int q = lane >> 4, p = lane & 15;
     // ---- M (and the bias column) -> LDS, fragment order: lane (q,i) of fragment (mt, j) = M[16mt+i][4j+q]
+    // (`transposed`: the fragments of M^T, read from the same row-major M -- the grad-input of the mix, finc_mix_backward_f32)
     for (int e = threadIdx.x; e < MTN * (NK + 1) * 64; e += (int)blockDim.x) {
         const int l = e & 63, f = e >> 6;
         const int j = f % (NK + 1), mt = f / (NK + 1);
         const int row = 16 * mt + (l & 15), col = 4 * j + (l >> 4);
         float v = 0.f;
         if (row < C) {
-            if (j < NK) v = col < C ? mat[(size_t)row * C + col] : 0.f;
+            if (j < NK) v = col < C ? mat[transposed ? (size_t)col * C + row : (size_t)row * C + col] : 0.f;
             else v = ((l >> 4) == 0 && bias) ? bias[row] : 0.f;      // bias rides on k-slot 0 of the extra k-step
         }
         afrag[e] = v;
@@ -180,7 +181,7 @@ __global__ __launch_bounds__((64 * WGW)) void finc_mix_kernel(const float *__res
     }
 }
 
-typedef void (*mix_fn)(const float *, const float *, const float *, float *, int, int, int, int);
+typedef void (*mix_fn)(const float *, const float *, const float *, float *, int, int, int, int, int);
 struct MixInst {
     int C;
     mix_fn fn[3][2];   // [1, 2 or 4 pixels per lane][4- or 16-wave workgroup]; nullptr = not instantiated
@@ -216,7 +217,7 @@ const MixInst *find_mix(int C)
 
 bool finc_mix_supported(int C) { return find_mix(C) != nullptr; }
 
-int finc_mix_launch(const float *in, const float *mat, const float *bias, float *out, int B, int C, int HW, hipStream_t st)
+int finc_mix_launch(const float *in, const float *mat, const float *bias, float *out, int B, int C, int HW, hipStream_t st, bool transposed)
 {
     const MixInst *m = find_mix(C);
     if (!m) return FINC_ERR_UNSUPPORTED;
@@ -250,7 +251,7 @@ int finc_mix_launch(const float *in, const float *mat, const float *bias, float 
     if (wgs_per_cu < 1) wgs_per_cu = 1;
     long long wgs = (total + wgw - 1) / wgw;
     if (wgs > 256LL * wgs_per_cu) wgs = 256LL * wgs_per_cu;
-    hipLaunchKernelGGL(fn, dim3((unsigned)wgs), dim3(64 * wgw), lds, st, in, mat, bias, out, C, HW, cpi, (int)total);
+    hipLaunchKernelGGL(fn, dim3((unsigned)wgs), dim3(64 * wgw), lds, st, in, mat, bias, out, C, HW, cpi, (int)total, transposed ? 1 : 0);
     FINC_CHECK_LAUNCH();
     return FINC_OK;
 }

@@ -107,8 +107,10 @@ class ActNorm(FlowLayer):
 
 
 class Conv1x1(FlowLayer):
-    """layers/conv1x1.py:8-49.  Inference / sampling (no autograd graph, device tensors, a channel count the library
-    instantiates) runs on the HIP mixing kernel (`ops.finc_mix`, one streaming launch); training keeps F.conv2d."""
+    """layers/conv1x1.py:8-49.  Device tensors in fp32 with a channel count the library instantiates run on the HIP mixing
+    kernel: inference / sampling (no autograd graph) as one streaming launch (`ops.finc_mix`), `forward` under autograd through
+    `ops.mix_forward` (backward: finc_mix_backward_f32).  Everything else -- CPU tensors, fp64, other channel counts, `reverse`
+    under autograd -- keeps F.conv2d."""
 
     def __init__(self, n_channels):
         super().__init__()
@@ -116,10 +118,12 @@ class Conv1x1(FlowLayer):
         q = np.linalg.qr(np.random.randn(n_channels, n_channels))[0]
         self.W = nn.Parameter(torch.from_numpy(q.astype('float32')))
 
-    def _hip(self, x):
+    def _hip_device(self, x):
         from . import ops
-        return (not (torch.is_grad_enabled() and (self.W.requires_grad or x.requires_grad)) and x.is_cuda
-                and x.dtype == torch.float32 and x.dim() == 4 and ops.mix_supported(self.n_channels))
+        return x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and ops.mix_supported(self.n_channels)
+
+    def _hip(self, x):
+        return not (torch.is_grad_enabled() and (self.W.requires_grad or x.requires_grad)) and self._hip_device(x)
 
     def forward(self, x, context=None):
         h, w = x.shape[2:]
@@ -127,6 +131,9 @@ class Conv1x1(FlowLayer):
         if self._hip(x):
             from . import ops
             return ops.finc_mix(x.contiguous(), self.W.detach().contiguous()), ldj
+        if torch.is_grad_enabled() and self._hip_device(x):      # training: the same kernel under autograd
+            from . import ops
+            return ops.mix_forward(x, self.W), ldj
         return F.conv2d(x, self.W.view(self.n_channels, self.n_channels, 1, 1)), ldj
 
     def _inverse_matrix(self):

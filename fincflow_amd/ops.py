@@ -196,6 +196,67 @@ def finc_mix(x, mat, bias=None, out=None):
     return out
 
 
+def finc_mix_backward(grad_out, x, mat, need_gx=True, need_gm=True, need_gb=False):
+    """Gradients of `finc_mix` (autograd through F.conv2d, layers/conv1x1.py:29-31): grad_x = mat^T @ grad_out per pixel,
+    grad_mat[o][i] = sum grad_out[:, o] * x[:, i], grad_bias[o] = sum grad_out[:, o]; each is computed only if asked for (None
+    otherwise).  grad_out, x [B,C,H,W] fp32 contiguous on the device (`x` may be None without grad_mat), mat [C,C] the forward
+    matrix.  The sums run in a fixed order: the same inputs give the same bits."""
+    _require_device(grad_out, "grad_output")
+    _require_device(mat, "matrix")
+    if grad_out.dim() != 4 or mat.shape != (grad_out.shape[1], grad_out.shape[1]) or mat.device != grad_out.device:
+        raise ValueError("expected a gradient [B,C,H,W] and a [C,C] matrix on the same device")
+    if need_gm:
+        if x is None:
+            raise ValueError("grad_mat needs the forward's input")
+        _require_device(x, "input")
+        if x.shape != grad_out.shape or x.device != grad_out.device:
+            raise ValueError("input must match grad_output in shape and device")
+    B, C, H, W = grad_out.shape
+    gx = torch.empty_like(grad_out) if need_gx else None
+    gm = torch.empty_like(mat) if need_gm else None
+    gb = torch.empty(C, dtype=torch.float32, device=grad_out.device) if need_gb else None
+    if not (need_gx or need_gm or need_gb):
+        return gx, gm, gb
+    if grad_out.numel() == 0:
+        for t in (gm, gb):
+            if t is not None:
+                t.zero_()
+        return gx, gm, gb
+    L = _lib.lib()
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with torch.cuda.device(grad_out.device):
+        ws = _workspace(grad_out.device, L.finc_mix_backward_workspace_bytes(B, C, H * W)) if (need_gm or need_gb) else None
+        st = L.finc_mix_backward_f32(grad_out.data_ptr(), ptr(x) if need_gm else None, mat.data_ptr(), ptr(gx), ptr(gm), ptr(gb),
+                                     B, C, H * W, ptr(ws), ws.numel() if ws is not None else 0, _stream_ptr(grad_out))
+    _lib.check(st, "finc_mix_backward_f32")
+    return gx, gm, gb
+
+
+class _FincMixFunction(torch.autograd.Function):
+    """`finc_mix` under autograd: both directions on the HIP kernels (finc_mix_f32 / finc_mix_backward_f32)."""
+
+    @staticmethod
+    def forward(ctx, x, mat, bias):
+        x = x.contiguous()
+        mat = mat.contiguous()
+        out = finc_mix(x, mat, None if bias is None else bias.contiguous())
+        ctx.save_for_backward(x if ctx.needs_input_grad[1] else None, mat)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, mat = ctx.saved_tensors
+        gx, gm, gb = finc_mix_backward(grad_out.contiguous(), x, mat, need_gx=ctx.needs_input_grad[0],
+                                       need_gm=ctx.needs_input_grad[1], need_gb=ctx.needs_input_grad[2])
+        return gx, gm, gb
+
+
+def mix_forward(x, mat, bias=None):
+    """`finc_mix(x, mat, bias)` under autograd: gradients for `x`, `mat` and `bias`, each computed only where needed."""
+    return _FincMixFunction.apply(x, mat, bias)
+
+
 def inverse(input, kernel, output):
     """Drop-in for the reference extension's `inverse` (cinc_cuda_level2.cpp:19-32).
 

@@ -236,6 +236,23 @@ int finc_mix_f32(const float *in, const float *mat, const float *bias, float *ou
                  finc_stream_t stream);
 
 /*
+ * Backward of finc_mix_f32 (replaces autograd through F.conv2d, layers/conv1x1.py:29-31), for out = mat * in + bias:
+ *   grad_in[b, :, p]  = transpose(mat) * grad_out[b, :, p]
+ *   grad_mat[o][i]    = sum_{b,p} grad_out[b,o,p] * in[b,i,p]
+ *   grad_bias[o]      = sum_{b,p} grad_out[b,o,p]
+ * Same layout as the forward: activations fp32 NCHW with HW = H*W, `mat` the FORWARD matrix, [C][C] row-major (the call
+ * transposes it on the device).  Every output is OVERWRITTEN (not accumulated); any of the three may be NULL to skip it, not
+ * all of them.  `in` is read for grad_mat only and may be NULL without it.  grad_in may alias neither grad_out nor in
+ * (FINC_ERR_BAD_DIMS).  grad_mat and grad_bias need a `workspace` of finc_mix_backward_workspace_bytes() bytes for their partial
+ * sums (FINC_ERR_WORKSPACE when it is NULL or smaller; its content on entry is irrelevant); the partials are summed in a fixed
+ * order, without atomics: the same inputs give the same bits.  Channel counts: those of finc_mix_supported_f32.
+ */
+size_t finc_mix_backward_workspace_bytes(int B, int C, int HW);
+int finc_mix_backward_f32(const float *grad_out, const float *in, const float *mat, float *grad_in, float *grad_mat,
+                          float *grad_bias, int B, int C, int HW, void *workspace, size_t workspace_bytes,
+                          finc_stream_t stream);
+
+/*
  * Introspection (tests, diagnostics; no reference counterpart).
  * finc_inverse_kernel_variant: which MFMA inverse kernel FINC_ALGO_AUTO / finc_inverse_packed_f32 launches for this
  *   problem.  info[8] = {Cq padded to 4, waves per problem (K-split), problems per workgroup, 3 = sector pairing with
