@@ -32,10 +32,12 @@ SYMBOLS = [
     "finc_inverse_affine_supported", "finc_fault_pending", "finc_runtime_switches",
     "finc_debug_clock_probe_begin", "finc_debug_clock_probe_end",
     "finc_mix_backward_workspace_bytes", "finc_mix_backward_f32",
+    "finc_coupling_supported_f32", "finc_coupling_workspace_bytes", "finc_coupling_f32", "finc_coupling_backward_f32",
+    "finc_bias_relu_f32",
 ]
 
 #: the ABI version this binding is written against (include/finc.h: finc_version)
-ABI_VERSION = 103
+ABI_VERSION = 104
 
 _lib = None
 
@@ -117,6 +119,12 @@ def lib():
     L.finc_mix_backward_workspace_bytes.restype = sz
     L.finc_mix_backward_workspace_bytes.argtypes = [i, i, i]
     L.finc_mix_backward_f32.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp]
+    L.finc_coupling_supported_f32.argtypes = [i]
+    L.finc_coupling_workspace_bytes.restype = sz
+    L.finc_coupling_workspace_bytes.argtypes = [i, i, i]
+    L.finc_coupling_f32.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, vp, sz, vp]
+    L.finc_coupling_backward_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp]
+    L.finc_bias_relu_f32.argtypes = [vp, vp, vp, i, i, i, vp]
     for name in SYMBOLS:
         getattr(L, name)  # AttributeError here = header and library out of sync
     _lib = L

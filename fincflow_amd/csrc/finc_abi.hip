@@ -174,7 +174,7 @@ static int canonicalize(const T *w_stored, T *w_canon, int G, int Cq, int KH, in
 
 extern "C" {
 
-int finc_version(void) { return 103; }
+int finc_version(void) { return 104; }
 
 unsigned finc_build_flags(void)
 {
@@ -587,6 +587,68 @@ int finc_mix_backward_f32(const float *grad_out, const float *in, const float *m
         return finc_mix_gradw_launch(grad_out, in, grad_mat, grad_bias, workspace, B, C, HW, finc_align(grad_out, grad_mat ? in : grad_out),
                                      st);
     return FINC_OK;
+}
+
+int finc_coupling_supported_f32(int C) { return (C >= 2 && C % 2 == 0 && C <= FINC_MAX_CQ * FINC_MAX_GROUPS) ? 1 : 0; }
+
+size_t finc_coupling_workspace_bytes(int B, int C, int HW)
+{
+    if (B <= 0 || C < 2 || HW <= 0) return 256;
+    const size_t n = align256(finc_coupling_workspace_floats(B, C, HW) * sizeof(float));
+    return n < 256 ? 256 : n;
+}
+
+// NULL, then the dims, then the alignment, then the channel count, then the workspace: the order of finc_mix_backward_f32
+static int coupling_dims(int B, int C, int HW)
+{
+    if (B <= 0 || C <= 0 || HW <= 0 || C > FINC_MAX_CQ * FINC_MAX_GROUPS) return FINC_ERR_BAD_DIMS;
+    if ((size_t)B * C * HW >= ((size_t)1 << 40)) return FINC_ERR_BAD_DIMS;
+    return FINC_OK;
+}
+
+int finc_coupling_f32(const float *x, const float *raw, const float *a, const float *b, float *y, float *logdet, int B, int C, int HW,
+                      int direction, void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    if (!x || !raw || !a || !b || !y) return FINC_ERR_NULL_POINTER;
+    if (int e = coupling_dims(B, C, HW)) return e;
+    if (direction != 1 && direction != -1) return FINC_ERR_BAD_DIMS;
+    if (y == raw) return FINC_ERR_BAD_DIMS;
+    if (misaligned(x) || misaligned(raw) || misaligned(a) || misaligned(b) || misaligned(y) || (logdet && misaligned(logdet)))
+        return FINC_ERR_ALIGNMENT;
+    if (!finc_coupling_supported_f32(C)) return FINC_ERR_UNSUPPORTED;
+    const bool sums = direction > 0 && logdet;
+    if (sums && (!workspace || misaligned(workspace) || workspace_bytes < finc_coupling_workspace_bytes(B, C, HW))) return FINC_ERR_WORKSPACE;
+    if (int e = finc_fault_gate(false)) return e;
+    return finc_coupling_launch(x, raw, a, b, y, sums ? logdet : nullptr, B, C, HW, direction, (float *)workspace, (hipStream_t)stream);
+}
+
+int finc_coupling_backward_f32(const float *grad_y, const float *grad_logdet, const float *x, const float *raw, const float *a,
+                               const float *b, float *grad_x, float *grad_raw, float *grad_a, float *grad_b, int B, int C, int HW,
+                               void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    if (!grad_y || !x || !raw || !a || !b || (!grad_x && !grad_raw && !grad_a && !grad_b)) return FINC_ERR_NULL_POINTER;
+    if (int e = coupling_dims(B, C, HW)) return e;
+    if (grad_x && (grad_x == grad_y || grad_x == x || grad_x == raw)) return FINC_ERR_BAD_DIMS;
+    if (grad_raw && (grad_raw == grad_y || grad_raw == x || grad_raw == raw || grad_raw == grad_x)) return FINC_ERR_BAD_DIMS;
+    if (misaligned(grad_y) || (grad_logdet && misaligned(grad_logdet)) || misaligned(x) || misaligned(raw) || misaligned(a) || misaligned(b) ||
+        (grad_x && misaligned(grad_x)) || (grad_raw && misaligned(grad_raw)) || (grad_a && misaligned(grad_a)) || (grad_b && misaligned(grad_b)))
+        return FINC_ERR_ALIGNMENT;
+    if (!finc_coupling_supported_f32(C)) return FINC_ERR_UNSUPPORTED;
+    if ((grad_a || grad_b) && (!workspace || misaligned(workspace) || workspace_bytes < finc_coupling_workspace_bytes(B, C, HW)))
+        return FINC_ERR_WORKSPACE;
+    if (int e = finc_fault_gate(false)) return e;
+    return finc_coupling_backward_launch(grad_y, grad_logdet, x, raw, a, b, grad_x, grad_raw, grad_a, grad_b, B, C, HW, (float *)workspace,
+                                         (hipStream_t)stream);
+}
+
+int finc_bias_relu_f32(const float *in, const float *bias, float *out, int B, int C, int HW, finc_stream_t stream)
+{
+    if (!in || !bias || !out) return FINC_ERR_NULL_POINTER;
+    if (B <= 0 || C <= 0 || HW <= 0) return FINC_ERR_BAD_DIMS;
+    if ((size_t)B * C * HW >= ((size_t)1 << 40)) return FINC_ERR_BAD_DIMS;
+    if (misaligned(in) || misaligned(bias) || misaligned(out)) return FINC_ERR_ALIGNMENT;
+    if (int e = finc_fault_gate(false)) return e;
+    return finc_bias_relu_launch(in, bias, out, B, C, HW, (hipStream_t)stream);
 }
 
 int finc_debug_backward_variant(int B, int G, int Cq, int H, int W, int KH, int KW, int *info)

@@ -254,3 +254,12 @@ int finc_mix_launch(const float *in, const float *mat, const float *bias, float 
 size_t finc_mix_gradw_workspace_bytes(int B, int C, int HW);     // 0: no instantiation for C
 int finc_mix_gradw_launch(const float *grad_out, const float *in, float *gm, float *gb, void *workspace, int B, int C, int HW,
                           int align, hipStream_t st);
+
+// ---- the affine coupling's glue (transform + log-det, its backward, bias + ReLU): finc_coupling.h, compiled into finc_mix.o ----
+// C even; `ws` holds finc_coupling_workspace_floats floats (needed with logdet / ga / gb only); direction +1 forward, -1 reverse
+size_t finc_coupling_workspace_floats(int B, int C, int HW);
+int finc_coupling_launch(const float *x, const float *raw, const float *a, const float *b, float *y, float *logdet, int B, int C, int HW,
+                         int direction, float *ws, hipStream_t st);
+int finc_coupling_backward_launch(const float *gy, const float *gld, const float *x, const float *raw, const float *a, const float *b,
+                                  float *gx, float *graw, float *ga, float *gb, int B, int C, int HW, float *ws, hipStream_t st);
+int finc_bias_relu_launch(const float *in, const float *bias, float *out, int B, int C, int HW, hipStream_t st);

@@ -1,0 +1,294 @@
+// The affine coupling's glue for gfx950 (included by finc_mix.hip: same object file, the per-pixel streaming neighbours of the unit).
+//
+// Reference: layers/coupling.py:44-105 (Coupling) around layers/coupling.py:9-41 (Conv2dZero).  Behind the coupling net's last
+// convolution the reference runs twelve elementwise launches -- bias add, logs * 3, exp, broadcast multiply, / 2, tanh, * 2, neg, exp,
+// sub, mul, cat -- and two more (bias add, ReLU) behind each of the first two convolutions.  Here:
+//   * finc_coupling_kernel      one pass: h = a * raw + b per channel, s = 2 tanh(u / 2), y2 = x2 * exp(s) + t  (forward, + log-det)
+//                               or y2 = (x2 - t) * exp(-s) (reverse); the untouched half is copied by the same threads.
+//   * finc_coupling_bwd_kernel  one pass: every gradient of the forward direction; s and exp(s) are recomputed from raw (two
+//                               transcendentals per element) instead of being saved: saving them would add two tensor writes to the
+//                               forward and two reads here, and this kernel is bound by its memory traffic, not by the VALU.
+//   * finc_bias_relu_kernel     out = max(in + bias[c], 0), in place or not.
+// Layout: x, y [B][C][HW] fp32, raw [B][C][HW] with channel 2j = u_j (pre-activation of the log-scale) and 2j+1 = t_j (translation).
+// A thread owns V consecutive pixels of one channel pair j: V = 4 (16-byte pieces) when HW % 4 == 0 and every pointer is 16-byte
+// aligned, else V = 1 (dwords).  Every index is checked against the element count: nothing is read or written beyond a tensor.
+// Sums (log-det per image; grad_a, grad_b per channel) never use atomics: each workgroup reduces its share in a fixed order (wave
+// butterflies, then the four waves in LDS) and writes ONE partial to the workspace; finc_coupling_reduce_kernel adds the partials of
+// an output in a fixed order.  The same inputs give the same bits.
+#ifndef FINC_COUPLING_H
+#define FINC_COUPLING_H
+
+namespace {
+
+typedef float cpl_v4f __attribute__((ext_vector_type(4)));
+constexpr int CPL_THREADS = 256;
+
+template <int V>
+__device__ inline void cpl_load(float (&d)[V], const float *p)
+{
+    if constexpr (V == 4) {
+        const cpl_v4f v = *reinterpret_cast<const cpl_v4f *>(p);
+        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+    } else {
+        d[0] = *p;
+    }
+}
+template <int V>
+__device__ inline void cpl_store(float *p, const float (&d)[V])
+{
+    if constexpr (V == 4) {
+        cpl_v4f v;
+        v.x = d[0]; v.y = d[1]; v.z = d[2]; v.w = d[3];
+        *reinterpret_cast<cpl_v4f *>(p) = v;
+    } else {
+        *p = d[0];
+    }
+}
+
+// Sum of N values per thread over the 256 threads of a workgroup, in a fixed order; every thread returns with the totals in v[].
+template <int N>
+__device__ inline void cpl_block_sum(float (&v)[N], float (*sm)[4])
+{
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) sm[k][threadIdx.x >> 6] = v[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = (sm[k][0] + sm[k][1]) + (sm[k][2] + sm[k][3]);
+}
+
+// Workgroup = (image, part): P parts per image share its half * HW / V thread items.  DIR +1 forward, -1 reverse.
+// y == x is allowed (a thread reads its pieces before it writes them, and nobody else touches them).
+template <int V, int DIR, bool LOGDET>
+__global__ __launch_bounds__(CPL_THREADS) void finc_coupling_kernel(const float *x, const float *__restrict__ raw,
+                                                                    const float *__restrict__ a, const float *__restrict__ b, float *y,
+                                                                    float *__restrict__ part, int half, int HW, int nv, int items, int P)
+{
+    const int img = (int)blockIdx.x / P, pi = (int)blockIdx.x - img * P;
+    const size_t ibase = (size_t)img * (size_t)(2 * half) * (size_t)HW;
+    float ls[1] = {0.f};
+    for (int idx = pi * CPL_THREADS + (int)threadIdx.x; idx < items; idx += P * CPL_THREADS) {
+        const int j = idx / nv, p = (idx - j * nv) * V;
+        const size_t o1 = ibase + (size_t)j * HW + p, o2 = o1 + (size_t)half * HW;
+        const size_t ou = ibase + (size_t)(2 * j) * HW + p, ot = ou + HW;
+        float x1[V], x2[V], u[V], t[V], y2[V];
+        cpl_load<V>(x1, x + o1);
+        cpl_load<V>(x2, x + o2);
+        cpl_load<V>(u, raw + ou);
+        cpl_load<V>(t, raw + ot);
+        const float au = a[2 * j], bu = b[2 * j], at = a[2 * j + 1], bt = b[2 * j + 1];
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            const float s = 2.f * tanhf(0.5f * fmaf(au, u[e], bu));
+            const float tr = fmaf(at, t[e], bt);
+            if constexpr (DIR > 0) {
+                y2[e] = fmaf(x2[e], expf(s), tr);
+                if constexpr (LOGDET) ls[0] += s;
+            } else {
+                y2[e] = (x2[e] - tr) * expf(-s);
+            }
+        }
+        cpl_store<V>(y + o1, x1);
+        cpl_store<V>(y + o2, y2);
+    }
+    if constexpr (LOGDET) {
+        __shared__ float sm[1][4];
+        cpl_block_sum<1>(ls, sm);
+        if (threadIdx.x == 0) part[blockIdx.x] = ls[0];
+    }
+}
+
+// Workgroup = (channel pair j, part): Q parts per pair share its B * HW / V thread items, so the four per-channel sums of a
+// workgroup belong to ONE pair.  Partials: part[(4j + k) * Q + q], k = 0 grad_a[2j], 1 grad_b[2j], 2 grad_a[2j+1], 3 grad_b[2j+1].
+// gld (grad of the log-det, per image), gx, graw may be nullptr; `sums` = 0 skips the partials.
+template <int V>
+__global__ __launch_bounds__(CPL_THREADS) void finc_coupling_bwd_kernel(const float *__restrict__ gy, const float *__restrict__ gld,
+                                                                        const float *__restrict__ x, const float *__restrict__ raw,
+                                                                        const float *__restrict__ a, const float *__restrict__ b,
+                                                                        float *__restrict__ gx, float *__restrict__ graw,
+                                                                        float *__restrict__ part, int half, int HW, int nv, int items, int Q,
+                                                                        int sums)
+{
+    const int j = (int)blockIdx.x / Q, qi = (int)blockIdx.x - j * Q;
+    const float au = a[2 * j], bu = b[2 * j], at = a[2 * j + 1];
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int idx = qi * CPL_THREADS + (int)threadIdx.x; idx < items; idx += Q * CPL_THREADS) {
+        const int img = idx / nv, p = (idx - img * nv) * V;
+        const size_t ibase = (size_t)img * (size_t)(2 * half) * (size_t)HW;
+        const size_t o1 = ibase + (size_t)j * HW + p, o2 = o1 + (size_t)half * HW;
+        const size_t ou = ibase + (size_t)(2 * j) * HW + p, ot = ou + HW;
+        float g1[V], g2[V], x2[V], u[V], t[V], gx2[V], gu[V], gt[V];
+        if (gx) cpl_load<V>(g1, gy + o1);
+        cpl_load<V>(g2, gy + o2);
+        cpl_load<V>(x2, x + o2);
+        cpl_load<V>(u, raw + ou);
+        if (sums) cpl_load<V>(t, raw + ot);
+        const float gl = gld ? gld[img] : 0.f;
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            const float th = tanhf(0.5f * fmaf(au, u[e], bu));     // s = 2 th, 1 - s*s/4 = 1 - th*th
+            gx2[e] = g2[e] * expf(2.f * th);
+            const float gh = fmaf(gx2[e], x2[e], gl) * fmaf(-th, th, 1.f);
+            gu[e] = au * gh;
+            gt[e] = at * g2[e];
+            if (sums) {
+                acc[0] = fmaf(gh, u[e], acc[0]);
+                acc[1] += gh;
+                acc[2] = fmaf(g2[e], t[e], acc[2]);
+                acc[3] += g2[e];
+            }
+        }
+        if (gx) {
+            cpl_store<V>(gx + o1, g1);
+            cpl_store<V>(gx + o2, gx2);
+        }
+        if (graw) {
+            cpl_store<V>(graw + ou, gu);
+            cpl_store<V>(graw + ot, gt);
+        }
+    }
+    if (sums) {
+        __shared__ float sm[4][4];
+        cpl_block_sum<4>(acc, sm);
+        if (threadIdx.x < 4) part[((size_t)(4 * j) + threadIdx.x) * Q + qi] = acc[threadIdx.x];
+    }
+}
+
+// One wave per output: out = sum of its n consecutive partials, lane l takes l, l + 64, ... and the lanes meet in a butterfly.
+// pairs == 0: out_a[o] (the log-det of image o).  pairs == 1: output o = 4j + k goes to out_a / out_b as listed above; a nullptr
+// destination is neither summed nor written.
+__global__ __launch_bounds__(64) void finc_coupling_reduce_kernel(const float *__restrict__ part, int n, float *__restrict__ out_a,
+                                                                  float *__restrict__ out_b, int pairs)
+{
+    const int o = (int)blockIdx.x;
+    float *dst = out_a + o;
+    if (pairs) {
+        float *base = (o & 1) ? out_b : out_a;
+        if (!base) return;
+        dst = base + (2 * (o >> 2) + ((o >> 1) & 1));
+    }
+    const float *p = part + (size_t)o * n;
+    float s = 0.f;
+    for (int i = (int)threadIdx.x; i < n; i += 64) s += p[i];
+#pragma unroll
+    for (int k = 32; k > 0; k >>= 1) s += __shfl_xor(s, k, 64);
+    if (threadIdx.x == 0) *dst = s;
+}
+
+// Thread item = V consecutive pixels of one (image, channel) row.  relu as torch.relu has it: a NaN stays a NaN.
+template <int V>
+__global__ __launch_bounds__(CPL_THREADS) void finc_bias_relu_kernel(const float *in, const float *__restrict__ bias, float *out, int C,
+                                                                     int HW, int nv, unsigned items)
+{
+    for (unsigned idx = blockIdx.x * CPL_THREADS + threadIdx.x; idx < items; idx += gridDim.x * CPL_THREADS) {
+        const unsigned row = idx / (unsigned)nv, p = (idx - row * (unsigned)nv) * V;
+        const float bv = bias[row % (unsigned)C];
+        const size_t o = (size_t)row * HW + p;
+        float v[V];
+        cpl_load<V>(v, in + o);
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            const float w = v[e] + bv;
+            v[e] = w != w ? w : fmaxf(w, 0.f);
+        }
+        cpl_store<V>(out + o, v);
+    }
+}
+
+// workgroups that fill the chip at eight of these per compute unit
+constexpr long long CPL_CHIP_WGS = 256 * 8;
+
+inline int cpl_parts(long long items, long long outer)
+{
+    long long p = (items + CPL_THREADS - 1) / CPL_THREADS;             // one pass of the loop each ...
+    const long long cap = (CPL_CHIP_WGS + outer - 1) / outer;          // ... unless the chip is full already
+    if (p > cap) p = cap;
+    return p < 1 ? 1 : (int)p;
+}
+inline bool cpl_wide(int HW, uintptr_t ptrs) { return HW % 4 == 0 && (ptrs & 15u) == 0; }
+
+} // namespace
+
+// floats: forward log-det partials (B images x P parts) and backward partials (4 sums x C/2 pairs x Q parts).  outer * cpl_parts(items,
+// outer) is at most outer * ceil(items / 256) and below CPL_CHIP_WGS + outer; the smaller of these two bounds, for the dword form's
+// item count, is what is reserved: it never shrinks when B or HW grows.
+size_t finc_coupling_workspace_floats(int B, int C, int HW)
+{
+    const long long half = C / 2;
+    auto bound = [](long long items, long long outer) {
+        const long long all = outer * ((items + CPL_THREADS - 1) / CPL_THREADS), cap = CPL_CHIP_WGS + outer;
+        return all < cap ? all : cap;
+    };
+    const long long fwd = bound(half * HW, B), bwd = 4 * bound((long long)B * HW, half);
+    return (size_t)(fwd > bwd ? fwd : bwd);
+}
+
+int finc_coupling_launch(const float *x, const float *raw, const float *a, const float *b, float *y, float *logdet, int B, int C, int HW,
+                         int direction, float *ws, hipStream_t st)
+{
+    const int half = C / 2;
+    if ((size_t)C * HW * 4 >= ((size_t)1 << 31)) return FINC_ERR_BAD_DIMS;
+    const bool wide = cpl_wide(HW, (uintptr_t)x | (uintptr_t)raw | (uintptr_t)y);
+    const int V = wide ? 4 : 1, nv = HW / V, items = half * nv;
+    const int P = cpl_parts(items, B);
+    if ((long long)B * P >= (1LL << 31)) return FINC_ERR_BAD_DIMS;
+    const dim3 grid((unsigned)((long long)B * P)), block(CPL_THREADS);
+    const bool ld = direction > 0 && logdet;
+#define FINC_CPL_GO(V_, D_, L_) hipLaunchKernelGGL((finc_coupling_kernel<V_, D_, L_>), grid, block, 0, st, x, raw, a, b, y, ws, half, HW, nv, items, P)
+    if (direction > 0) {
+        if (ld) { if (wide) FINC_CPL_GO(4, 1, true); else FINC_CPL_GO(1, 1, true); }
+        else { if (wide) FINC_CPL_GO(4, 1, false); else FINC_CPL_GO(1, 1, false); }
+    } else {
+        if (wide) FINC_CPL_GO(4, -1, false); else FINC_CPL_GO(1, -1, false);
+    }
+#undef FINC_CPL_GO
+    FINC_CHECK_LAUNCH();
+    if (ld) {
+        hipLaunchKernelGGL(finc_coupling_reduce_kernel, dim3((unsigned)B), dim3(64), 0, st, (const float *)ws, P, logdet, (float *)nullptr, 0);
+        FINC_CHECK_LAUNCH();
+    }
+    return FINC_OK;
+}
+
+int finc_coupling_backward_launch(const float *gy, const float *gld, const float *x, const float *raw, const float *a, const float *b,
+                                  float *gx, float *graw, float *ga, float *gb, int B, int C, int HW, float *ws, hipStream_t st)
+{
+    const int half = C / 2;
+    if ((size_t)C * HW * 4 >= ((size_t)1 << 31) || (long long)B * HW >= (1LL << 31) - (CPL_CHIP_WGS + 1) * CPL_THREADS)
+        return FINC_ERR_BAD_DIMS;
+    const bool wide = cpl_wide(HW, (uintptr_t)gy | (uintptr_t)x | (uintptr_t)raw | (uintptr_t)gx | (uintptr_t)graw);
+    const int V = wide ? 4 : 1, nv = HW / V, items = B * nv;
+    const int Q = cpl_parts(items, half);
+    const int sums = (ga || gb) ? 1 : 0;
+    const dim3 grid((unsigned)((long long)half * Q)), block(CPL_THREADS);
+    if (wide) hipLaunchKernelGGL(finc_coupling_bwd_kernel<4>, grid, block, 0, st, gy, gld, x, raw, a, b, gx, graw, ws, half, HW, nv, items, Q, sums);
+    else hipLaunchKernelGGL(finc_coupling_bwd_kernel<1>, grid, block, 0, st, gy, gld, x, raw, a, b, gx, graw, ws, half, HW, nv, items, Q, sums);
+    FINC_CHECK_LAUNCH();
+    if (sums) {
+        hipLaunchKernelGGL(finc_coupling_reduce_kernel, dim3((unsigned)(4 * half)), dim3(64), 0, st, (const float *)ws, Q, ga, gb, 1);
+        FINC_CHECK_LAUNCH();
+    }
+    return FINC_OK;
+}
+
+int finc_bias_relu_launch(const float *in, const float *bias, float *out, int B, int C, int HW, hipStream_t st)
+{
+    const bool wide = cpl_wide(HW, (uintptr_t)in | (uintptr_t)out);
+    const int V = wide ? 4 : 1, nv = HW / V;
+    const long long items = (long long)B * C * nv;
+    if (items >= (1LL << 32) - 4 * CPL_CHIP_WGS * CPL_THREADS) return FINC_ERR_BAD_DIMS;
+    long long wgs = (items + CPL_THREADS - 1) / CPL_THREADS;
+    if (wgs > 4 * CPL_CHIP_WGS) wgs = 4 * CPL_CHIP_WGS;
+    if (wide) hipLaunchKernelGGL(finc_bias_relu_kernel<4>, dim3((unsigned)wgs), dim3(CPL_THREADS), 0, st, in, bias, out, C, HW, nv, (unsigned)items);
+    else hipLaunchKernelGGL(finc_bias_relu_kernel<1>, dim3((unsigned)wgs), dim3(CPL_THREADS), 0, st, in, bias, out, C, HW, nv, (unsigned)items);
+    FINC_CHECK_LAUNCH();
+    return FINC_OK;
+}
+
+#endif /* FINC_COUPLING_H */

@@ -256,4 +256,6 @@ int finc_mix_launch(const float *in, const float *mat, const float *bias, float 
     return FINC_OK;
 }
 
+#include "finc_coupling.h"
+
 unsigned finc_build_flags_mix() { return FINC_BUILD_FLAGS; }

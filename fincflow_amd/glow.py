@@ -9,7 +9,8 @@ Reference semantics followed:
   Squeeze        layers/squeeze.py:5-41          space-to-depth, channel order (c, dy, dx)
   ActNorm        layers/actnorm.py:5-66          data-dependent init on first forward; out = (x - t) * exp(-log_scale)
   Conv1x1        layers/conv1x1.py:8-49          orthogonal init, ldj = H*W*log|det W|
-  Coupling       layers/coupling.py:46-113       affine, net = conv3x3-ReLU-conv1x1-ReLU-Conv2dZero, log_s = 2*tanh(h/2)
+  Coupling       layers/coupling.py:46-113       affine, net = conv3x3-ReLU-conv1x1-ReLU-Conv2dZero, log_s = 2*tanh(h/2);
+                 on the device the part behind the net is one HIP launch (ops.finc_coupling)
   SplitPrior     layers/splitprior.py:7-41       Coupling + factor out the second half under a standard normal
   Normalization, LogitTransform, Dequantization  layers/normalize.py, transforms.py:6-19, dequantize.py
   GaussianPrior  train/losses.py:17-45           standard-normal base (log_prob per sample, sample(n))
@@ -219,6 +220,13 @@ class Conv2dZero(nn.Module):
 
 
 class Coupling(FlowLayer):
+    """layers/coupling.py:44-105.  Device tensors in fp32 with an even channel count run everything behind the net's last convolution
+    on the HIP coupling kernel (`ops.finc_coupling`: affine transform, log-det and the copy of the untouched half in one launch).
+    Without an autograd graph (inference, sampling) the net's `Conv2d(bias) + ReLU` pairs are `F.conv2d(bias=None)` +
+    `ops.finc_bias_relu` in place as well; under autograd `forward` goes through `ops.coupling_forward` (backward:
+    finc_coupling_backward_f32) and the net stays PyTorch.  Everything else -- CPU tensors, fp64, odd channel counts, `reverse` under
+    autograd -- keeps the PyTorch formula below."""
+
     def __init__(self, input_size, width=512, n_context=None):
         super().__init__()
         self.n_channels = input_size[0]
@@ -230,6 +238,57 @@ class Coupling(FlowLayer):
                                  nn.Conv2d(width, width, (1, 1)), nn.ReLU(),
                                  Conv2dZero(width, self.n_channels))
 
+    def _hip_device(self, x):
+        from . import ops
+        return x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and ops.coupling_supported(self.n_channels)
+
+    def _records_graph(self, x, context):
+        return torch.is_grad_enabled() and (x.requires_grad or (context is not None and context.requires_grad)
+                                            or any(p.requires_grad for p in self.net.parameters()))
+
+    def _hip(self, x, context=None):
+        """The inference path: HIP transform and HIP bias + ReLU, nothing recorded for autograd."""
+        return not self._records_graph(x, context) and self._hip_device(x)
+
+    def _hip_train(self, x, context=None):
+        """`forward` under autograd: PyTorch net, HIP transform with its own backward."""
+        return self._records_graph(x, context) and self._hip_device(x)
+
+    def _scale_shift(self):
+        # h = a * raw + b with raw the last convolution WITHOUT its bias: Conv2dZero is (conv + bias) * exp(logs * factor)
+        last = self.net[4]
+        a = torch.exp(last.logs * last.logscale_factor)
+        return a, last.bias * a
+
+    def _scale_shift_cached(self):
+        # once per parameter version: a sampling pass has no [C]-sized launches in it.  (During a stream capture nothing is cached:
+        # a tensor made there is only filled when the graph replays.)
+        last = self.net[4]
+        key = (last.logs.data_ptr(), last.logs._version, last.bias.data_ptr(), last.bias._version, last.logs.device)
+        if getattr(self, "_ab_key", None) == key:
+            return self._ab
+        with torch.no_grad():
+            a, b = self._scale_shift()
+            ab = (a.contiguous(), b.contiguous())
+        if not torch.cuda.is_current_stream_capturing():
+            self._ab, self._ab_key = ab, key
+        return ab
+
+    def _net_input(self, x, context):
+        assert (context is not None) == self.uses_context
+        x1 = x[:, :self.half_channels]
+        return x1 if context is None else torch.cat([x1, context], dim=1)
+
+    def _raw_inference(self, x, context):
+        from . import ops
+        n = self.net
+        with torch.no_grad():
+            h = F.conv2d(self._net_input(x, context), n[0].weight, None, padding=1).contiguous()
+            ops.finc_bias_relu(h, n[0].bias.detach(), out=h)
+            h = F.conv2d(h, n[2].weight, None).contiguous()
+            ops.finc_bias_relu(h, n[2].bias.detach(), out=h)
+            return F.conv2d(h, n[4].weight, None, padding=1).contiguous()
+
     def _params(self, x, context):
         assert (context is not None) == self.uses_context
         x1, x2 = x[:, :self.half_channels], x[:, self.half_channels:]
@@ -238,10 +297,26 @@ class Coupling(FlowLayer):
         return x1, x2, log_s, h[:, 1::2]
 
     def forward(self, input, context=None):
+        if self._hip(input, context):
+            from . import ops
+            x = input.contiguous()
+            a, b = self._scale_shift_cached()
+            return ops.finc_coupling(x, self._raw_inference(x, context), a, b, 1, True)
+        if self._hip_train(input, context):
+            from . import ops
+            n = self.net
+            raw = F.conv2d(n[:4](self._net_input(input, context)), n[4].weight, None, padding=1)
+            a, b = self._scale_shift()
+            return ops.coupling_forward(input, raw, a, b)
         x1, x2, log_s, t = self._params(input, context)
         return torch.cat([x1, x2 * torch.exp(log_s) + t], dim=1), log_s.flatten(start_dim=1).sum(-1)
 
     def reverse(self, input, context=None):
+        if self._hip(input, context):
+            from . import ops
+            x = input.contiguous()
+            a, b = self._scale_shift_cached()
+            return ops.finc_coupling(x, self._raw_inference(x, context), a, b, -1, False)[0]
         x1, x2, log_s, t = self._params(input, context)
         return torch.cat([x1, (x2 - t) * torch.exp(-log_s)], dim=1)
 

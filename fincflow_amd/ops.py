@@ -257,6 +257,138 @@ def mix_forward(x, mat, bias=None):
     return _FincMixFunction.apply(x, mat, bias)
 
 
+def coupling_supported(C):
+    return bool(_lib.lib().finc_coupling_supported_f32(int(C)))
+
+
+def _coupling_args(x, raw, a, b, what="input"):
+    _require_device(x, what)
+    _require_device(raw, "raw")
+    _require_device(a, "scale")
+    _require_device(b, "shift")
+    if x.dim() != 4 or raw.shape != x.shape or raw.device != x.device:
+        raise ValueError(f"expected {what} [B,C,H,W] and the coupling net's output of the same shape on the same device")
+    C = x.shape[1]
+    if a.numel() != C or b.numel() != C or a.device != x.device or b.device != x.device:
+        raise ValueError("scale and shift must have one entry per channel, on the activations' device")
+    if not coupling_supported(C):
+        raise _lib.FincError(f"finc_coupling: no kernel for {C} channels (the coupling splits an even channel count)")
+
+
+def finc_coupling(x, raw, a, b, direction=1, want_logdet=False, out=None):
+    """The affine coupling behind its net (layers/coupling.py:79-101) as one streaming HIP launch: with h = a * raw + b per channel,
+    s = 2 tanh(h[:, ::2] / 2), t = h[:, 1::2]:  y = cat(x1, x2 * exp(s) + t) (direction +1) or cat(x1, (x2 - t) * exp(-s)) (-1).
+    x, raw [B,C,H,W] fp32 contiguous on the device, C even; a, b [C].  Returns (y, logdet): logdet [B] = s summed per image when
+    `want_logdet` (forward direction; one more small launch, fixed-order sums), else None.  `out` may be `x`."""
+    _coupling_args(x, raw, a, b)
+    if direction not in (1, -1):
+        raise ValueError("direction must be +1 (forward) or -1 (reverse)")
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _require_device(out, "output")
+        if out.shape != x.shape or out.device != x.device:
+            raise ValueError("output must match input in shape and device")
+    B, C, H, W = x.shape
+    want_logdet = bool(want_logdet) and direction == 1
+    if x.numel() == 0:
+        return out, (torch.zeros(B, dtype=torch.float32, device=x.device) if want_logdet else None)
+    logdet = torch.empty(B, dtype=torch.float32, device=x.device) if want_logdet else None
+    L = _lib.lib()
+    with torch.cuda.device(x.device):
+        ws = _workspace(x.device, L.finc_coupling_workspace_bytes(B, C, H * W)) if want_logdet else None
+        st = L.finc_coupling_f32(x.data_ptr(), raw.data_ptr(), a.data_ptr(), b.data_ptr(), out.data_ptr(),
+                                 logdet.data_ptr() if want_logdet else None, B, C, H * W, direction,
+                                 ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, _stream_ptr(x))
+    _lib.check(st, "finc_coupling_f32")
+    return out, logdet
+
+
+def finc_coupling_backward(grad_y, grad_logdet, x, raw, a, b, need_gx=True, need_graw=True, need_ga=True, need_gb=True):
+    """Gradients of `finc_coupling(..., direction=1, want_logdet=True)` (include/finc.h: finc_coupling_backward_f32), given grad_y
+    [B,C,H,W] and grad_logdet [B] or None (zeros): (grad_x, grad_raw, grad_a, grad_b), each computed only if asked for (None
+    otherwise).  grad_x[:, :C/2] is grad_y[:, :C/2]: what reaches that half through the net is the caller's (autograd's).  s and exp(s)
+    are recomputed from `raw`; the per-channel sums run in a fixed order: the same inputs give the same bits."""
+    _coupling_args(x, raw, a, b)
+    _require_device(grad_y, "grad_output")
+    if grad_y.shape != x.shape or grad_y.device != x.device:
+        raise ValueError("grad_output must match input in shape and device")
+    B, C, H, W = x.shape
+    if grad_logdet is not None:
+        _require_device(grad_logdet, "grad_logdet")
+        if grad_logdet.numel() != B or grad_logdet.device != x.device:
+            raise ValueError("grad_logdet must have one entry per image, on the activations' device")
+    gx = torch.empty_like(x) if need_gx else None
+    graw = torch.empty_like(raw) if need_graw else None
+    ga = torch.empty(C, dtype=torch.float32, device=x.device) if need_ga else None
+    gb = torch.empty(C, dtype=torch.float32, device=x.device) if need_gb else None
+    if not (need_gx or need_graw or need_ga or need_gb):
+        return gx, graw, ga, gb
+    if x.numel() == 0:
+        for t in (ga, gb):
+            if t is not None:
+                t.zero_()
+        return gx, graw, ga, gb
+    L = _lib.lib()
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with torch.cuda.device(x.device):
+        ws = _workspace(x.device, L.finc_coupling_workspace_bytes(B, C, H * W)) if (need_ga or need_gb) else None
+        st = L.finc_coupling_backward_f32(grad_y.data_ptr(), ptr(grad_logdet), x.data_ptr(), raw.data_ptr(), a.data_ptr(), b.data_ptr(),
+                                          ptr(gx), ptr(graw), ptr(ga), ptr(gb), B, C, H * W, ptr(ws),
+                                          ws.numel() if ws is not None else 0, _stream_ptr(x))
+    _lib.check(st, "finc_coupling_backward_f32")
+    return gx, graw, ga, gb
+
+
+class _FincCouplingFunction(torch.autograd.Function):
+    """`finc_coupling` in the forward direction under autograd: (y, logdet) and their backward on the HIP kernels."""
+
+    @staticmethod
+    def forward(ctx, x, raw, a, b):
+        x, raw, a, b = x.contiguous(), raw.contiguous(), a.contiguous(), b.contiguous()
+        y, logdet = finc_coupling(x, raw, a, b, 1, True)
+        ctx.save_for_backward(x, raw, a, b)
+        return y, logdet
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y, grad_logdet):
+        x, raw, a, b = ctx.saved_tensors
+        if grad_y is None:
+            grad_y = torch.zeros_like(x)
+        need = ctx.needs_input_grad
+        return finc_coupling_backward(grad_y.contiguous(), None if grad_logdet is None else grad_logdet.contiguous(), x, raw, a, b,
+                                      need_gx=need[0], need_graw=need[1], need_ga=need[2], need_gb=need[3])
+
+
+def coupling_forward(x, raw, a, b):
+    """`finc_coupling(x, raw, a, b, +1, want_logdet=True)` under autograd: returns (y, logdet), gradients for `x`, `raw`, `a` and
+    `b`, each computed only where needed."""
+    return _FincCouplingFunction.apply(x, raw, a, b)
+
+
+def finc_bias_relu(x, bias, out=None):
+    """max(x + bias[c], 0) in one pass: the bias and the ReLU behind a convolution of the coupling net (layers/coupling.py:58-63).
+    x [B,C,H,W] fp32 contiguous on the device, bias [C]; `out` may be `x`.  Inference only: no autograd graph is recorded."""
+    _require_device(x, "input")
+    _require_device(bias, "bias")
+    if x.dim() != 4 or bias.numel() != x.shape[1] or bias.device != x.device:
+        raise ValueError("expected activations [B,C,H,W] and one bias entry per channel on the same device")
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _require_device(out, "output")
+        if out.shape != x.shape or out.device != x.device:
+            raise ValueError("output must match input in shape and device")
+    if x.numel() == 0:
+        return out
+    B, C, H, W = x.shape
+    with torch.cuda.device(x.device):
+        st = _lib.lib().finc_bias_relu_f32(x.data_ptr(), bias.data_ptr(), out.data_ptr(), B, C, H * W, _stream_ptr(x))
+    _lib.check(st, "finc_bias_relu_f32")
+    return out
+
+
 def inverse(input, kernel, output):
     """Drop-in for the reference extension's `inverse` (cinc_cuda_level2.cpp:19-32).
 

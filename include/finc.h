@@ -253,6 +253,41 @@ int finc_mix_backward_f32(const float *grad_out, const float *in, const float *m
                           finc_stream_t stream);
 
 /*
+ * The affine coupling behind its net (layers/coupling.py:44-105; the net's last layer is Conv2dZero, layers/coupling.py:9-41):
+ * everything after the last convolution in ONE launch, instead of the reference's twelve elementwise ones.
+ *   x, y [B][C][HW] fp32 NCHW, C even, half = C/2;  raw [B][C][HW] = the last convolution's output WITHOUT its bias;
+ *   a, b [C]: h = a[c] * raw[:, c] + b[c]   (Conv2dZero: a = exp(3 * logs), b = bias * a);
+ *   u_j = h[:, 2j], t_j = h[:, 2j+1], s_j = 2 * tanh(u_j / 2)   (layers/coupling.py:79-82).
+ * finc_coupling_f32:   y[:, :half] = x[:, :half];
+ *   direction +1 (Coupling.forward, :86-92):  y[:, half+j] = x[:, half+j] * exp(s_j) + t_j,  logdet[b] = sum_{j,p} s_j[b,p]
+ *   direction -1 (Coupling.reverse, :95-101): y[:, half+j] = (x[:, half+j] - t_j) * exp(-s_j).
+ *   `logdet` [B] may be NULL (and is ignored in the reverse direction); with it the call needs a `workspace` of
+ *   finc_coupling_workspace_bytes() bytes for the workgroups' partial sums, added in a fixed order by a second small launch: no
+ *   atomics, the same inputs give the same bits.  y == x is allowed; y == raw is not (FINC_ERR_BAD_DIMS).
+ * finc_coupling_backward_f32: the gradients of direction +1 (replaces autograd through :79-92 and :38-40), given grad_y and
+ *   grad_logdet [B] (NULL = zeros); s and exp(s) are recomputed from raw, nothing else was saved:
+ *     grad_x[:, :half] = grad_y[:, :half]  (what reaches x[:, :half] THROUGH THE NET is the caller's: it owns the net's backward)
+ *     grad_x[:, half+j] = grad_y2 * exp(s_j)                    with grad_y2 = grad_y[:, half+j]
+ *     grad_h[:, 2j+1] = grad_y2,   grad_h[:, 2j] = (grad_y2 * x[:, half+j] * exp(s_j) + grad_logdet[b]) * (1 - s_j^2 / 4)
+ *     grad_raw[:, c] = a[c] * grad_h[:, c],   grad_a[c] = sum_{b,p} grad_h[b,c,p] * raw[b,c,p],   grad_b[c] = sum_{b,p} grad_h[b,c,p]
+ *   Every output is OVERWRITTEN; any may be NULL to skip it, not all of them.  grad_a / grad_b need the workspace (same size, same
+ *   fixed-order sums).  The outputs may alias no input and not each other (FINC_ERR_BAD_DIMS).
+ * finc_bias_relu_f32: out = max(in + bias[c], 0) -- the Conv2d bias and the nn.ReLU behind the net's first two convolutions
+ *   (layers/coupling.py:58-63) in one pass; in == out allowed.  Inference only (no backward).
+ * Rows of HW floats move as 16-byte pieces when HW % 4 == 0 and every activation pointer is 16-byte aligned, as dwords otherwise.
+ * Status: a NULL required pointer FINC_ERR_NULL_POINTER, non-positive dims FINC_ERR_BAD_DIMS, odd C FINC_ERR_UNSUPPORTED
+ * (finc_coupling_supported_f32(C) == 0), a missing / short workspace where one is needed FINC_ERR_WORKSPACE.
+ */
+int finc_coupling_supported_f32(int C);
+size_t finc_coupling_workspace_bytes(int B, int C, int HW);
+int finc_coupling_f32(const float *x, const float *raw, const float *a, const float *b, float *y, float *logdet, int B, int C,
+                      int HW, int direction, void *workspace, size_t workspace_bytes, finc_stream_t stream);
+int finc_coupling_backward_f32(const float *grad_y, const float *grad_logdet, const float *x, const float *raw, const float *a,
+                               const float *b, float *grad_x, float *grad_raw, float *grad_a, float *grad_b, int B, int C, int HW,
+                               void *workspace, size_t workspace_bytes, finc_stream_t stream);
+int finc_bias_relu_f32(const float *in, const float *bias, float *out, int B, int C, int HW, finc_stream_t stream);
+
+/*
  * Introspection (tests, diagnostics; no reference counterpart).
  * finc_inverse_kernel_variant: which MFMA inverse kernel FINC_ALGO_AUTO / finc_inverse_packed_f32 launches for this
  *   problem.  info[8] = {Cq padded to 4, waves per problem (K-split), problems per workgroup, 3 = sector pairing with
