@@ -34,10 +34,14 @@ SYMBOLS = [
     "finc_mix_backward_workspace_bytes", "finc_mix_backward_f32",
     "finc_coupling_supported_f32", "finc_coupling_workspace_bytes", "finc_coupling_f32", "finc_coupling_backward_f32",
     "finc_bias_relu_f32",
+    "finc_actnorm_workspace_bytes", "finc_actnorm_f32", "finc_actnorm_backward_f32", "finc_actnorm_init_f32",
 ]
 
 #: the ABI version this binding is written against (include/finc.h: finc_version)
 ABI_VERSION = 104
+#: the version that added the ActNorm entry points (finc_actnorm_f32, finc_actnorm_backward_f32, finc_actnorm_init_f32); a second,
+#: named floor behind the first so that each refusal says what the library lacks
+ACTNORM_ABI_VERSION = 105
 
 _lib = None
 
@@ -64,6 +68,10 @@ def lib():
         raise FincError(f"{LIB_PATH} does not export finc_version: not a build of libfinc_hip.so") from None
     if have < ABI_VERSION:
         raise FincError(f"{LIB_PATH} reports finc_version() = {have}, this package needs at least {ABI_VERSION}: rebuild it "
+                        "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
+    if have < ACTNORM_ABI_VERSION:
+        raise FincError(f"{LIB_PATH} reports finc_version() = {have}, the ActNorm entry points (finc_actnorm_f32, "
+                        f"finc_actnorm_backward_f32, finc_actnorm_init_f32) came with {ACTNORM_ABI_VERSION}: rebuild it "
                         "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
     L.finc_build_flags.restype = u
     L.finc_clear_fault.restype = i
@@ -125,6 +133,11 @@ def lib():
     L.finc_coupling_f32.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, vp, sz, vp]
     L.finc_coupling_backward_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp]
     L.finc_bias_relu_f32.argtypes = [vp, vp, vp, i, i, i, vp]
+    L.finc_actnorm_workspace_bytes.restype = sz
+    L.finc_actnorm_workspace_bytes.argtypes = [i, i, i]
+    L.finc_actnorm_f32.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, vp]
+    L.finc_actnorm_backward_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp]
+    L.finc_actnorm_init_f32.argtypes = [vp, vp, vp, i, i, i, vp, sz, vp]
     for name in SYMBOLS:
         getattr(L, name)  # AttributeError here = header and library out of sync
     _lib = L

@@ -174,7 +174,7 @@ static int canonicalize(const T *w_stored, T *w_canon, int G, int Cq, int KH, in
 
 extern "C" {
 
-int finc_version(void) { return 104; }
+int finc_version(void) { return 105; }
 
 unsigned finc_build_flags(void)
 {
@@ -649,6 +649,57 @@ int finc_bias_relu_f32(const float *in, const float *bias, float *out, int B, in
     if (misaligned(in) || misaligned(bias) || misaligned(out)) return FINC_ERR_ALIGNMENT;
     if (int e = finc_fault_gate(false)) return e;
     return finc_bias_relu_launch(in, bias, out, B, C, HW, (hipStream_t)stream);
+}
+
+size_t finc_actnorm_workspace_bytes(int B, int C, int HW)
+{
+    if (B <= 0 || C <= 0 || HW <= 0) return 256;
+    const size_t n = align256(finc_actnorm_workspace_floats(B, C, HW) * sizeof(float));
+    return n < 256 ? 256 : n;
+}
+
+// NULL, then the dims / direction / aliasing, then the alignment, then the workspace: the order of the coupling's entry points
+int finc_actnorm_f32(const float *x, const float *log_scale, const float *translation, float *y, float *logdet, int B, int C, int HW,
+                     int direction, finc_stream_t stream)
+{
+    if (!x || !log_scale || !translation || !y) return FINC_ERR_NULL_POINTER;
+    if (int e = coupling_dims(B, C, HW)) return e;
+    if (direction != 1 && direction != -1) return FINC_ERR_BAD_DIMS;
+    if (misaligned(x) || misaligned(log_scale) || misaligned(translation) || misaligned(y) || (logdet && misaligned(logdet)))
+        return FINC_ERR_ALIGNMENT;
+    if (int e = finc_fault_gate(false)) return e;
+    return finc_actnorm_launch(x, log_scale, translation, y, direction > 0 ? logdet : nullptr, B, C, HW, direction, (hipStream_t)stream);
+}
+
+int finc_actnorm_backward_f32(const float *grad_y, const float *grad_logdet, const float *y, const float *log_scale, float *grad_x,
+                              float *grad_log_scale, float *grad_translation, int B, int C, int HW, void *workspace,
+                              size_t workspace_bytes, finc_stream_t stream)
+{
+    if (!grad_y || !y || !log_scale || (!grad_x && !grad_log_scale && !grad_translation)) return FINC_ERR_NULL_POINTER;
+    if (int e = coupling_dims(B, C, HW)) return e;
+    if (grad_x && grad_x == y) return FINC_ERR_BAD_DIMS;
+    if (misaligned(grad_y) || (grad_logdet && misaligned(grad_logdet)) || misaligned(y) || misaligned(log_scale) ||
+        (grad_x && misaligned(grad_x)) || (grad_log_scale && misaligned(grad_log_scale)) || (grad_translation && misaligned(grad_translation)))
+        return FINC_ERR_ALIGNMENT;
+    if ((grad_log_scale || grad_translation) &&
+        (!workspace || misaligned(workspace) || workspace_bytes < finc_actnorm_workspace_bytes(B, C, HW)))
+        return FINC_ERR_WORKSPACE;
+    if (int e = finc_fault_gate(false)) return e;
+    return finc_actnorm_backward_launch(grad_y, grad_logdet, y, log_scale, grad_x, grad_log_scale, grad_translation, B, C, HW,
+                                        (float *)workspace, (hipStream_t)stream);
+}
+
+int finc_actnorm_init_f32(const float *x, float *log_scale, float *translation, int B, int C, int HW, void *workspace,
+                          size_t workspace_bytes, finc_stream_t stream)
+{
+    if (!x || !log_scale || !translation) return FINC_ERR_NULL_POINTER;
+    if (int e = coupling_dims(B, C, HW)) return e;
+    if ((long long)B * HW < 2) return FINC_ERR_BAD_DIMS;             // the unbiased deviation of one value (torch.std: NaN)
+    if (log_scale == translation) return FINC_ERR_BAD_DIMS;
+    if (misaligned(x) || misaligned(log_scale) || misaligned(translation)) return FINC_ERR_ALIGNMENT;
+    if (!workspace || misaligned(workspace) || workspace_bytes < finc_actnorm_workspace_bytes(B, C, HW)) return FINC_ERR_WORKSPACE;
+    if (int e = finc_fault_gate(false)) return e;
+    return finc_actnorm_init_launch(x, log_scale, translation, B, C, HW, (float *)workspace, (hipStream_t)stream);
 }
 
 int finc_debug_backward_variant(int B, int G, int Cq, int H, int W, int KH, int KW, int *info)

@@ -263,3 +263,11 @@ int finc_coupling_launch(const float *x, const float *raw, const float *a, const
 int finc_coupling_backward_launch(const float *gy, const float *gld, const float *x, const float *raw, const float *a, const float *b,
                                   float *gx, float *graw, float *ga, float *gb, int B, int C, int HW, float *ws, hipStream_t st);
 int finc_bias_relu_launch(const float *in, const float *bias, float *out, int B, int C, int HW, hipStream_t st);
+// ---- ActNorm (transform + log-det, its backward from the forward's OUTPUT, the data-dependent initialisation): finc_actnorm.h, same object ----
+// `ws` holds finc_actnorm_workspace_floats floats (backward with gls / gt, and the initialisation)
+size_t finc_actnorm_workspace_floats(int B, int C, int HW);
+int finc_actnorm_launch(const float *x, const float *ls, const float *tr, float *y, float *logdet, int B, int C, int HW, int direction,
+                        hipStream_t st);
+int finc_actnorm_backward_launch(const float *gy, const float *gld, const float *y, const float *ls, float *gx, float *gls, float *gt,
+                                 int B, int C, int HW, float *ws, hipStream_t st);
+int finc_actnorm_init_launch(const float *x, float *ls, float *tr, int B, int C, int HW, float *ws, hipStream_t st);

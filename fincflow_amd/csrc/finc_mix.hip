@@ -257,5 +257,6 @@ int finc_mix_launch(const float *in, const float *mat, const float *bias, float 
 }
 
 #include "finc_coupling.h"
+#include "finc_actnorm.h"
 
 unsigned finc_build_flags_mix() { return FINC_BUILD_FLAGS; }

@@ -1,13 +1,16 @@
 """The layers either side of the hot path in the reference's CIFAR Glow stack (BASELINE
 configs[3]): thin PyTorch modules with the reference's constructor arguments, parameter names and
 forward -> (out, logdet[B]) / reverse -> out protocol, so that `create_model` below builds the topology of
-fastflow/fastflow_cifar.py:35-63 around fincflow_amd.FastFlowUnit.  None of this is a HIP kernel: these are
-per-pixel / 1x1 / small-conv ops that PyTorch-ROCm already runs; the point of this file is that a whole
-sampling pass (96 units at 16x16 / 8x8 / 4x4) can run and be captured in one HIP graph.
+fastflow/fastflow_cifar.py:35-63 around fincflow_amd.FastFlowUnit.  ActNorm, Conv1x1 and the coupling's transform run on HIP
+kernels of their own (ops.finc_actnorm, ops.finc_mix, ops.finc_coupling), in inference and under autograd; the coupling net's
+convolutions, Squeeze and the preprocessing layers are ops that PyTorch-ROCm already runs.  The point of this file is that a
+whole sampling pass (96 units at 16x16 / 8x8 / 4x4) can run and be captured in one HIP graph.
 
 Reference semantics followed:
   Squeeze        layers/squeeze.py:5-41          space-to-depth, channel order (c, dy, dx)
-  ActNorm        layers/actnorm.py:5-66          data-dependent init on first forward; out = (x - t) * exp(-log_scale)
+  ActNorm        layers/actnorm.py:5-66          data-dependent init on first forward; out = (x - t) * exp(-log_scale);
+                 on the device one HIP launch each way (ops.finc_actnorm), init and backward included (ops.finc_actnorm_init,
+                 ops.actnorm_forward)
   Conv1x1        layers/conv1x1.py:8-49          orthogonal init, ldj = H*W*log|det W|
   Coupling       layers/coupling.py:46-113       affine, net = conv3x3-ReLU-conv1x1-ReLU-Conv2dZero, log_s = 2*tanh(h/2);
                  on the device the part behind the net is one HIP launch (ops.finc_coupling)
@@ -41,6 +44,12 @@ class Squeeze(FlowLayer):
 
 
 class ActNorm(FlowLayer):
+    """layers/actnorm.py:5-66.  Device tensors in fp32, 4-D, with fp32 parameters on the same device run on the HIP ActNorm kernels:
+    `forward` without an autograd graph as one launch (`ops.finc_actnorm`, the log-det included), `forward` under autograd through
+    `ops.actnorm_forward` (backward: finc_actnorm_backward_f32, from the saved OUTPUT), `reverse` without a graph as one launch, and
+    the data-dependent initialisation of the first forward as `ops.finc_actnorm_init` (at least two values per channel).  Everything
+    else -- CPU tensors, fp64, 2-D inputs, `reverse` under autograd, one value per channel -- keeps the PyTorch lines below."""
+
     def __init__(self, n_dims):
         super().__init__()
         self.n_dims = n_dims
@@ -75,18 +84,40 @@ class ActNorm(FlowLayer):
         shape = (1, -1) + (1,) * (input.dim() - 2)
         return self.translation.view(shape), self.log_scale.view(shape)
 
+    def _hip_device(self, x):
+        from . import ops
+        p = (self.translation, self.log_scale)
+        return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == self.n_dims
+                and all(q.dtype == torch.float32 and q.device == x.device for q in p) and ops.actnorm_supported())
+
+    def _records_graph(self, x):
+        return torch.is_grad_enabled() and (x.requires_grad or self.log_scale.requires_grad or self.translation.requires_grad)
+
     def forward(self, input, context=None):
+        hip = self._hip_device(input)
         if not self._is_initialized():
             with torch.no_grad():
-                dims = [d for d in range(input.dim()) if d != 1]
-                self.translation.copy_(input.mean(dim=dims))
-                self.log_scale.copy_(torch.log(input.std(dim=dims) + 1e-8))
+                if hip and input.numel() // self.n_dims >= 2:
+                    from . import ops
+                    ops.finc_actnorm_init(input.detach().contiguous(), self.log_scale.detach(), self.translation.detach())
+                else:
+                    dims = [d for d in range(input.dim()) if d != 1]
+                    self.translation.copy_(input.mean(dim=dims))
+                    self.log_scale.copy_(torch.log(input.std(dim=dims) + 1e-8))
                 self.initialized.fill_(1)
                 self._init_known = True
+        if hip:
+            from . import ops
+            if self._records_graph(input):
+                return ops.actnorm_forward(input, self.log_scale, self.translation)
+            return ops.finc_actnorm(input.contiguous(), self.log_scale.detach(), self.translation.detach(), 1, True)
         t, ls = self._shaped(input)
         return (input - t) * torch.exp(-ls), self.logdet(input, context)
 
     def reverse(self, input, context=None):
+        if self._hip_device(input) and not self._records_graph(input):
+            from . import ops
+            return ops.finc_actnorm(input.contiguous(), self.log_scale.detach(), self.translation.detach(), -1)[0]
         t, ls = self._shaped(input)
         return input * torch.exp(ls) + t
 

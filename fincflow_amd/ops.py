@@ -389,6 +389,140 @@ def finc_bias_relu(x, bias, out=None):
     return out
 
 
+_actnorm_ok = None
+
+
+def actnorm_supported():
+    """ActNorm's kernels take any channel count, and a library without them does not load (fincflow_amd._lib: ACTNORM_ABI_VERSION):
+    True once the library is loaded, no call into it per layer and pass."""
+    global _actnorm_ok
+    if _actnorm_ok is None:
+        _lib.lib()
+        _actnorm_ok = True
+    return _actnorm_ok
+
+
+def _actnorm_args(x, log_scale, translation, what="input"):
+    _require_device(x, what)
+    _require_device(log_scale, "log_scale")
+    if x.dim() != 4:
+        raise ValueError(f"expected {what} [B,C,H,W]")
+    C = x.shape[1]
+    if log_scale.numel() != C or log_scale.device != x.device:
+        raise ValueError("log_scale must have one entry per channel, on the activations' device")
+    if translation is not None:
+        _require_device(translation, "translation")
+        if translation.numel() != C or translation.device != x.device:
+            raise ValueError("translation must have one entry per channel, on the activations' device")
+
+
+def finc_actnorm(x, log_scale, translation, direction=1, want_logdet=False, out=None):
+    """ActNorm (layers/actnorm.py:34, :51) as one streaming HIP launch: y = (x - translation) * exp(-log_scale) per channel
+    (direction +1) or y = x * exp(log_scale) + translation (-1).  x [B,C,H,W] fp32 contiguous on the device; log_scale, translation
+    [C].  Returns (y, logdet): logdet [B] = -sum(log_scale) * H * W when `want_logdet` (forward direction; written by the same
+    launch), else None.  `out` may be `x`.  Nothing is recorded for autograd (`actnorm_forward` does that)."""
+    _actnorm_args(x, log_scale, translation)
+    if direction not in (1, -1):
+        raise ValueError("direction must be +1 (forward) or -1 (reverse)")
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _require_device(out, "output")
+        if out.shape != x.shape or out.device != x.device:
+            raise ValueError("output must match input in shape and device")
+    B, C, H, W = x.shape
+    want_logdet = bool(want_logdet) and direction == 1
+    if x.numel() == 0:
+        return out, (torch.zeros(B, dtype=torch.float32, device=x.device) if want_logdet else None)
+    logdet = torch.empty(B, dtype=torch.float32, device=x.device) if want_logdet else None
+    with torch.cuda.device(x.device):
+        st = _lib.lib().finc_actnorm_f32(x.data_ptr(), log_scale.data_ptr(), translation.data_ptr(), out.data_ptr(),
+                                         logdet.data_ptr() if want_logdet else None, B, C, H * W, direction, _stream_ptr(x))
+    _lib.check(st, "finc_actnorm_f32")
+    return out, logdet
+
+
+def finc_actnorm_backward(grad_y, grad_logdet, y, log_scale, need_gx=True, need_gls=True, need_gt=True):
+    """Gradients of `finc_actnorm(..., direction=1, want_logdet=True)` (include/finc.h: finc_actnorm_backward_f32), given grad_y
+    [B,C,H,W], grad_logdet [B] or None (zeros), the forward's OUTPUT `y` and log_scale: (grad_x, grad_log_scale, grad_translation),
+    each computed only if asked for (None otherwise).  The per-channel sums run in a fixed order: the same inputs give the same bits."""
+    _actnorm_args(y, log_scale, None, "output")
+    _require_device(grad_y, "grad_output")
+    if grad_y.shape != y.shape or grad_y.device != y.device:
+        raise ValueError("grad_output must match the forward's output in shape and device")
+    B, C, H, W = y.shape
+    if grad_logdet is not None:
+        _require_device(grad_logdet, "grad_logdet")
+        if grad_logdet.numel() != B or grad_logdet.device != y.device:
+            raise ValueError("grad_logdet must have one entry per image, on the activations' device")
+    gx = torch.empty_like(y) if need_gx else None
+    gls = torch.empty(C, dtype=torch.float32, device=y.device) if need_gls else None
+    gt = torch.empty(C, dtype=torch.float32, device=y.device) if need_gt else None
+    if not (need_gx or need_gls or need_gt):
+        return gx, gls, gt
+    if y.numel() == 0:
+        for t in (gls, gt):
+            if t is not None:
+                t.zero_()
+        return gx, gls, gt
+    L = _lib.lib()
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with torch.cuda.device(y.device):
+        ws = _workspace(y.device, L.finc_actnorm_workspace_bytes(B, C, H * W)) if (need_gls or need_gt) else None
+        st = L.finc_actnorm_backward_f32(grad_y.data_ptr(), ptr(grad_logdet), y.data_ptr(), log_scale.data_ptr(), ptr(gx), ptr(gls),
+                                         ptr(gt), B, C, H * W, ptr(ws), ws.numel() if ws is not None else 0, _stream_ptr(y))
+    _lib.check(st, "finc_actnorm_backward_f32")
+    return gx, gls, gt
+
+
+def finc_actnorm_init(x, log_scale, translation):
+    """ActNorm's data-dependent initialisation (layers/actnorm.py:17-23) on the device, written IN PLACE into the two parameters:
+    translation = per-channel mean of x, log_scale = log(unbiased std + 1e-8).  x [B,C,H,W] fp32 contiguous with B * H * W >= 2.
+    No host round trip, capturable; fixed-order merges: the same input gives the same bits."""
+    _actnorm_args(x, log_scale, translation)
+    B, C, H, W = x.shape
+    if B * H * W < 2:
+        raise ValueError("the unbiased standard deviation needs at least two values per channel")
+    L = _lib.lib()
+    with torch.cuda.device(x.device):
+        ws = _workspace(x.device, L.finc_actnorm_workspace_bytes(B, C, H * W))
+        st = L.finc_actnorm_init_f32(x.data_ptr(), log_scale.data_ptr(), translation.data_ptr(), B, C, H * W, ws.data_ptr(), ws.numel(),
+                                     _stream_ptr(x))
+    _lib.check(st, "finc_actnorm_init_f32")
+    # the kernel wrote behind PyTorch's back: the caches keyed on (address, version) of the parameters (FlowSequential's folds) must see it
+    torch.autograd.graph.increment_version(log_scale)
+    torch.autograd.graph.increment_version(translation)
+    return log_scale, translation
+
+
+class _FincActNormFunction(torch.autograd.Function):
+    """`finc_actnorm` in the forward direction under autograd: (y, logdet) and their backward on the HIP kernels.  What is saved is
+    the OUTPUT y -- the tensor the next layer keeps as its input anyway -- and log_scale; the input is not kept."""
+
+    @staticmethod
+    def forward(ctx, x, log_scale, translation):
+        x, log_scale, translation = x.contiguous(), log_scale.contiguous(), translation.contiguous()
+        y, logdet = finc_actnorm(x, log_scale, translation, 1, True)
+        ctx.save_for_backward(y, log_scale)
+        return y, logdet
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y, grad_logdet):
+        y, log_scale = ctx.saved_tensors
+        if grad_y is None:
+            grad_y = torch.zeros_like(y)
+        need = ctx.needs_input_grad
+        return finc_actnorm_backward(grad_y.contiguous(), None if grad_logdet is None else grad_logdet.contiguous(), y, log_scale,
+                                     need_gx=need[0], need_gls=need[1], need_gt=need[2])
+
+
+def actnorm_forward(x, log_scale, translation):
+    """`finc_actnorm(x, log_scale, translation, +1, want_logdet=True)` under autograd: returns (y, logdet), gradients for `x`,
+    `log_scale` and `translation`, each computed only where needed."""
+    return _FincActNormFunction.apply(x, log_scale, translation)
+
+
 def inverse(input, kernel, output):
     """Drop-in for the reference extension's `inverse` (cinc_cuda_level2.cpp:19-32).
 

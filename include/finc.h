@@ -288,6 +288,41 @@ int finc_coupling_backward_f32(const float *grad_y, const float *grad_logdet, co
 int finc_bias_relu_f32(const float *in, const float *bias, float *out, int B, int C, int HW, finc_stream_t stream);
 
 /*
+ * ActNorm (layers/actnorm.py:5-66) on its own kernels: activations [B][C][HW] fp32, log_scale and translation [C], any C >= 1
+ * (up to FINC_MAX_CQ * FINC_MAX_GROUPS), HW >= 1.
+ * finc_actnorm_f32: direction +1: y = (x - translation[c]) * exp(-log_scale[c]) (layers/actnorm.py:34); direction -1:
+ *   y = x * exp(log_scale[c]) + translation[c] (:51).  y == x allowed.  A non-NULL `logdet` (forward direction; ignored in the
+ *   reverse) is filled by the SAME launch: logdet[b] = -(sum_c log_scale[c]) * HW for every image (:57-65), the sum over C in a
+ *   fixed order by one wave.  No workspace.
+ * finc_actnorm_backward_f32: gradients of the forward direction from grad_y, grad_logdet ([B], NULL = zeros), log_scale and `y`,
+ *   the forward's OUTPUT (x - translation = y * exp(log_scale): nothing but what the next layer keeps anyway is needed):
+ *     grad_x[b,c,p]       = grad_y[b,c,p] * exp(-log_scale[c])
+ *     grad_translation[c] = -exp(-log_scale[c]) * sum_{b,p} grad_y[b,c,p]
+ *     grad_log_scale[c]   = -sum_{b,p} grad_y[b,c,p] * y[b,c,p]  -  HW * sum_b grad_logdet[b]
+ *   Every output is OVERWRITTEN; any may be NULL to skip it, not all of them.  grad_x == grad_y allowed, grad_x == y is not
+ *   (FINC_ERR_BAD_DIMS).  The two per-channel outputs need the workspace; their sums run in a fixed order (no atomics).
+ * finc_actnorm_init_f32: the data-dependent initialisation (:17-23) written straight into the parameters, no host round trip:
+ *   translation[c] = mean over (b, p), log_scale[c] = log(std + 1e-8) with the UNBIASED standard deviation (divisor n - 1,
+ *   n = B * HW; torch.std's default), one pass over x on (n, mean, M2) triples merged pairwise in a fixed order.  n < 2 is
+ *   FINC_ERR_BAD_DIMS (the reference's result there is NaN).  Needs the workspace.
+ * finc_actnorm_workspace_bytes: one bound for the backward and the initialisation; > 0 for any arguments, never shrinks when B or
+ *   HW grows.
+ * Rows of HW floats move as 16-byte pieces when HW % 4 == 0 and every activation pointer is 16-byte aligned, as dwords otherwise.
+ * Status: a NULL required pointer FINC_ERR_NULL_POINTER; non-positive / overflowing dims, a direction other than +1 / -1 or
+ * forbidden aliasing FINC_ERR_BAD_DIMS; a pointer not 4-byte aligned FINC_ERR_ALIGNMENT; a missing / short workspace where one is
+ * needed FINC_ERR_WORKSPACE -- checked in that order, before any HIP call.  The three launching calls take part in the
+ * sticky-fault rule below like every other.
+ */
+size_t finc_actnorm_workspace_bytes(int B, int C, int HW);
+int finc_actnorm_f32(const float *x, const float *log_scale, const float *translation, float *y, float *logdet, int B, int C, int HW,
+                     int direction, finc_stream_t stream);
+int finc_actnorm_backward_f32(const float *grad_y, const float *grad_logdet, const float *y, const float *log_scale, float *grad_x,
+                              float *grad_log_scale, float *grad_translation, int B, int C, int HW, void *workspace,
+                              size_t workspace_bytes, finc_stream_t stream);
+int finc_actnorm_init_f32(const float *x, float *log_scale, float *translation, int B, int C, int HW, void *workspace,
+                          size_t workspace_bytes, finc_stream_t stream);
+
+/*
  * Introspection (tests, diagnostics; no reference counterpart).
  * finc_inverse_kernel_variant: which MFMA inverse kernel FINC_ALGO_AUTO / finc_inverse_packed_f32 launches for this
  *   problem.  info[8] = {Cq padded to 4, waves per problem (K-split), problems per workgroup, 3 = sector pairing with
@@ -343,7 +378,7 @@ int finc_debug_attr_table_insert(int device, size_t kernel_token);
 int finc_debug_hlp_timeouts(unsigned *h_count);
 /* A wait that gives up leaves garbage in that launch's output.  It does not pass silently: the kernel also sets a word in
  * mapped host memory, and every later launching call on that device -- finc_inverse_*, finc_forward_*, finc_mix_f32,
- * finc_backward_f32, finc_check_invariant_f32 -- returns FINC_ERR_LAUNCH (finc_last_hip_error() names the cause) until
+ * finc_backward_f32, finc_check_invariant_f32, the coupling's and ActNorm's calls -- returns FINC_ERR_LAUNCH (finc_last_hip_error() names the cause) until
  * finc_clear_fault(); no synchronisation is added to the launch path.  The word is armed by the packing calls (and by the
  * first helper-wave launch outside a stream capture).  The launch that faulted has itself returned FINC_OK (it is
  * asynchronous): callers check finc_fault_pending() at their own synchronisation points -- the Python layer does at the
