@@ -74,7 +74,9 @@ int check_shape(int B, int G, int Cq, int H, int W, int KH, int KW)
     return FINC_OK;
 }
 
-inline bool misaligned(const void *p) { return ((uintptr_t)p & 3u) != 0; }
+// any of the pointers off a 4-byte boundary?  (nullptr, an output nobody asked for, is aligned)
+template <typename... P>
+inline bool misaligned(const P *...p) { return ((... | (uintptr_t)p) & 3u) != 0; }
 
 } // namespace
 
@@ -545,37 +547,50 @@ int finc_inverse_kernel_variant(int B, int G, int Cq, int H, int W, int KH, int 
     return finc_mfma_variant(B, G, Cq, H, W, KH, KW, info);
 }
 
+// ---- the per-pixel neighbours of the unit (finc_mix.hip, finc_coupling.h, finc_actnorm.h) ----
+// Every entry point refuses in one order, which tests/test_*_host.py pin with fake pointers: NULL, then the dims (with the direction
+// and the aliasing rules), then the alignment, then a channel count without a kernel, then the workspace, then the fault gate.
+
+// counts below one; with `cap_channels`, more channels than the unit's widest layer (finc_bias_relu_f32 runs on the coupling net's
+// width, which has no such cap)
+static bool pixel_counts_bad(int B, int C, int HW, bool cap_channels)
+{
+    return B <= 0 || C <= 0 || HW <= 0 || (cap_channels && C > FINC_MAX_CQ * FINC_MAX_GROUPS);
+}
+static bool pixel_total_bad(int B, int C, int HW) { return (size_t)B * C * HW >= ((size_t)1 << 40); }
+static int pixel_dims(int B, int C, int HW, bool cap_channels)
+{
+    return (pixel_counts_bad(B, C, HW, cap_channels) || pixel_total_bad(B, C, HW)) ? FINC_ERR_BAD_DIMS : FINC_OK;
+}
+static bool workspace_short(const void *workspace, size_t bytes, size_t need) { return !workspace || misaligned(workspace) || bytes < need; }
+static size_t padded_ws_bytes(size_t n) { return n < 256 ? 256 : align256(n); }
+
 int finc_mix_supported_f32(int C) { return (C > 0 && finc_mix_supported(C)) ? 1 : 0; }
 
 int finc_mix_f32(const float *in, const float *mat, const float *bias, float *out, int B, int C, int HW, finc_stream_t stream)
 {
     if (!in || !mat || !out) return FINC_ERR_NULL_POINTER;
-    if (B <= 0 || C <= 0 || HW <= 0 || C > FINC_MAX_CQ * FINC_MAX_GROUPS) return FINC_ERR_BAD_DIMS;
-    if (misaligned(in) || misaligned(mat) || misaligned(out) || (bias && misaligned(bias))) return FINC_ERR_ALIGNMENT;
-    if ((size_t)B * C * HW >= ((size_t)1 << 40)) return FINC_ERR_BAD_DIMS;
+    if (pixel_counts_bad(B, C, HW, true)) return FINC_ERR_BAD_DIMS;
+    if (misaligned(in, mat, out, bias)) return FINC_ERR_ALIGNMENT;
+    if (pixel_total_bad(B, C, HW)) return FINC_ERR_BAD_DIMS;         // (this entry point alone judges the total behind the alignment)
     if (int e = finc_fault_gate(false)) return e;
     return finc_mix_launch(in, mat, bias, out, B, C, HW, (hipStream_t)stream);
 }
 
 size_t finc_mix_backward_workspace_bytes(int B, int C, int HW)
 {
-    if (B <= 0 || C <= 0 || HW <= 0) return 256;
-    const size_t n = align256(finc_mix_gradw_workspace_bytes(B, C, HW));
-    return n < 256 ? 256 : n;
+    return pixel_counts_bad(B, C, HW, false) ? 256 : padded_ws_bytes(finc_mix_gradw_workspace_bytes(B, C, HW));
 }
 
 int finc_mix_backward_f32(const float *grad_out, const float *in, const float *mat, float *grad_in, float *grad_mat, float *grad_bias,
                           int B, int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream)
 {
     if (!grad_out || !mat || (!grad_in && !grad_mat && !grad_bias) || (grad_mat && !in)) return FINC_ERR_NULL_POINTER;
-    if (B <= 0 || C <= 0 || HW <= 0 || C > FINC_MAX_CQ * FINC_MAX_GROUPS) return FINC_ERR_BAD_DIMS;
-    if ((size_t)B * C * HW >= ((size_t)1 << 40)) return FINC_ERR_BAD_DIMS;
+    if (int e = pixel_dims(B, C, HW, true)) return e;
     if (grad_in && (grad_in == grad_out || grad_in == in)) return FINC_ERR_BAD_DIMS;
-    if (misaligned(grad_out) || misaligned(mat) || (in && misaligned(in)) || (grad_in && misaligned(grad_in)) ||
-        (grad_mat && misaligned(grad_mat)) || (grad_bias && misaligned(grad_bias)))
-        return FINC_ERR_ALIGNMENT;
+    if (misaligned(grad_out, mat, in, grad_in, grad_mat, grad_bias)) return FINC_ERR_ALIGNMENT;
     if (!finc_mix_supported(C)) return FINC_ERR_UNSUPPORTED;
-    if ((grad_mat || grad_bias) && (!workspace || misaligned(workspace) || workspace_bytes < finc_mix_backward_workspace_bytes(B, C, HW)))
+    if ((grad_mat || grad_bias) && workspace_short(workspace, workspace_bytes, finc_mix_backward_workspace_bytes(B, C, HW)))
         return FINC_ERR_WORKSPACE;
     if (int e = finc_fault_gate(false)) return e;
     hipStream_t st = (hipStream_t)stream;
@@ -594,30 +609,20 @@ int finc_coupling_supported_f32(int C) { return (C >= 2 && C % 2 == 0 && C <= FI
 size_t finc_coupling_workspace_bytes(int B, int C, int HW)
 {
     if (B <= 0 || C < 2 || HW <= 0) return 256;
-    const size_t n = align256(finc_coupling_workspace_floats(B, C, HW) * sizeof(float));
-    return n < 256 ? 256 : n;
-}
-
-// NULL, then the dims, then the alignment, then the channel count, then the workspace: the order of finc_mix_backward_f32
-static int coupling_dims(int B, int C, int HW)
-{
-    if (B <= 0 || C <= 0 || HW <= 0 || C > FINC_MAX_CQ * FINC_MAX_GROUPS) return FINC_ERR_BAD_DIMS;
-    if ((size_t)B * C * HW >= ((size_t)1 << 40)) return FINC_ERR_BAD_DIMS;
-    return FINC_OK;
+    return padded_ws_bytes(finc_coupling_workspace_floats(B, C, HW) * sizeof(float));
 }
 
 int finc_coupling_f32(const float *x, const float *raw, const float *a, const float *b, float *y, float *logdet, int B, int C, int HW,
                       int direction, void *workspace, size_t workspace_bytes, finc_stream_t stream)
 {
     if (!x || !raw || !a || !b || !y) return FINC_ERR_NULL_POINTER;
-    if (int e = coupling_dims(B, C, HW)) return e;
+    if (int e = pixel_dims(B, C, HW, true)) return e;
     if (direction != 1 && direction != -1) return FINC_ERR_BAD_DIMS;
     if (y == raw) return FINC_ERR_BAD_DIMS;
-    if (misaligned(x) || misaligned(raw) || misaligned(a) || misaligned(b) || misaligned(y) || (logdet && misaligned(logdet)))
-        return FINC_ERR_ALIGNMENT;
+    if (misaligned(x, raw, a, b, y, logdet)) return FINC_ERR_ALIGNMENT;
     if (!finc_coupling_supported_f32(C)) return FINC_ERR_UNSUPPORTED;
     const bool sums = direction > 0 && logdet;
-    if (sums && (!workspace || misaligned(workspace) || workspace_bytes < finc_coupling_workspace_bytes(B, C, HW))) return FINC_ERR_WORKSPACE;
+    if (sums && workspace_short(workspace, workspace_bytes, finc_coupling_workspace_bytes(B, C, HW))) return FINC_ERR_WORKSPACE;
     if (int e = finc_fault_gate(false)) return e;
     return finc_coupling_launch(x, raw, a, b, y, sums ? logdet : nullptr, B, C, HW, direction, (float *)workspace, (hipStream_t)stream);
 }
@@ -627,14 +632,12 @@ int finc_coupling_backward_f32(const float *grad_y, const float *grad_logdet, co
                                void *workspace, size_t workspace_bytes, finc_stream_t stream)
 {
     if (!grad_y || !x || !raw || !a || !b || (!grad_x && !grad_raw && !grad_a && !grad_b)) return FINC_ERR_NULL_POINTER;
-    if (int e = coupling_dims(B, C, HW)) return e;
+    if (int e = pixel_dims(B, C, HW, true)) return e;
     if (grad_x && (grad_x == grad_y || grad_x == x || grad_x == raw)) return FINC_ERR_BAD_DIMS;
     if (grad_raw && (grad_raw == grad_y || grad_raw == x || grad_raw == raw || grad_raw == grad_x)) return FINC_ERR_BAD_DIMS;
-    if (misaligned(grad_y) || (grad_logdet && misaligned(grad_logdet)) || misaligned(x) || misaligned(raw) || misaligned(a) || misaligned(b) ||
-        (grad_x && misaligned(grad_x)) || (grad_raw && misaligned(grad_raw)) || (grad_a && misaligned(grad_a)) || (grad_b && misaligned(grad_b)))
-        return FINC_ERR_ALIGNMENT;
+    if (misaligned(grad_y, grad_logdet, x, raw, a, b, grad_x, grad_raw, grad_a, grad_b)) return FINC_ERR_ALIGNMENT;
     if (!finc_coupling_supported_f32(C)) return FINC_ERR_UNSUPPORTED;
-    if ((grad_a || grad_b) && (!workspace || misaligned(workspace) || workspace_bytes < finc_coupling_workspace_bytes(B, C, HW)))
+    if ((grad_a || grad_b) && workspace_short(workspace, workspace_bytes, finc_coupling_workspace_bytes(B, C, HW)))
         return FINC_ERR_WORKSPACE;
     if (int e = finc_fault_gate(false)) return e;
     return finc_coupling_backward_launch(grad_y, grad_logdet, x, raw, a, b, grad_x, grad_raw, grad_a, grad_b, B, C, HW, (float *)workspace,
@@ -644,29 +647,24 @@ int finc_coupling_backward_f32(const float *grad_y, const float *grad_logdet, co
 int finc_bias_relu_f32(const float *in, const float *bias, float *out, int B, int C, int HW, finc_stream_t stream)
 {
     if (!in || !bias || !out) return FINC_ERR_NULL_POINTER;
-    if (B <= 0 || C <= 0 || HW <= 0) return FINC_ERR_BAD_DIMS;
-    if ((size_t)B * C * HW >= ((size_t)1 << 40)) return FINC_ERR_BAD_DIMS;
-    if (misaligned(in) || misaligned(bias) || misaligned(out)) return FINC_ERR_ALIGNMENT;
+    if (int e = pixel_dims(B, C, HW, false)) return e;
+    if (misaligned(in, bias, out)) return FINC_ERR_ALIGNMENT;
     if (int e = finc_fault_gate(false)) return e;
     return finc_bias_relu_launch(in, bias, out, B, C, HW, (hipStream_t)stream);
 }
 
 size_t finc_actnorm_workspace_bytes(int B, int C, int HW)
 {
-    if (B <= 0 || C <= 0 || HW <= 0) return 256;
-    const size_t n = align256(finc_actnorm_workspace_floats(B, C, HW) * sizeof(float));
-    return n < 256 ? 256 : n;
+    return pixel_counts_bad(B, C, HW, false) ? 256 : padded_ws_bytes(finc_actnorm_workspace_floats(B, C, HW) * sizeof(float));
 }
 
-// NULL, then the dims / direction / aliasing, then the alignment, then the workspace: the order of the coupling's entry points
 int finc_actnorm_f32(const float *x, const float *log_scale, const float *translation, float *y, float *logdet, int B, int C, int HW,
                      int direction, finc_stream_t stream)
 {
     if (!x || !log_scale || !translation || !y) return FINC_ERR_NULL_POINTER;
-    if (int e = coupling_dims(B, C, HW)) return e;
+    if (int e = pixel_dims(B, C, HW, true)) return e;
     if (direction != 1 && direction != -1) return FINC_ERR_BAD_DIMS;
-    if (misaligned(x) || misaligned(log_scale) || misaligned(translation) || misaligned(y) || (logdet && misaligned(logdet)))
-        return FINC_ERR_ALIGNMENT;
+    if (misaligned(x, log_scale, translation, y, logdet)) return FINC_ERR_ALIGNMENT;
     if (int e = finc_fault_gate(false)) return e;
     return finc_actnorm_launch(x, log_scale, translation, y, direction > 0 ? logdet : nullptr, B, C, HW, direction, (hipStream_t)stream);
 }
@@ -676,13 +674,10 @@ int finc_actnorm_backward_f32(const float *grad_y, const float *grad_logdet, con
                               size_t workspace_bytes, finc_stream_t stream)
 {
     if (!grad_y || !y || !log_scale || (!grad_x && !grad_log_scale && !grad_translation)) return FINC_ERR_NULL_POINTER;
-    if (int e = coupling_dims(B, C, HW)) return e;
+    if (int e = pixel_dims(B, C, HW, true)) return e;
     if (grad_x && grad_x == y) return FINC_ERR_BAD_DIMS;
-    if (misaligned(grad_y) || (grad_logdet && misaligned(grad_logdet)) || misaligned(y) || misaligned(log_scale) ||
-        (grad_x && misaligned(grad_x)) || (grad_log_scale && misaligned(grad_log_scale)) || (grad_translation && misaligned(grad_translation)))
-        return FINC_ERR_ALIGNMENT;
-    if ((grad_log_scale || grad_translation) &&
-        (!workspace || misaligned(workspace) || workspace_bytes < finc_actnorm_workspace_bytes(B, C, HW)))
+    if (misaligned(grad_y, grad_logdet, y, log_scale, grad_x, grad_log_scale, grad_translation)) return FINC_ERR_ALIGNMENT;
+    if ((grad_log_scale || grad_translation) && workspace_short(workspace, workspace_bytes, finc_actnorm_workspace_bytes(B, C, HW)))
         return FINC_ERR_WORKSPACE;
     if (int e = finc_fault_gate(false)) return e;
     return finc_actnorm_backward_launch(grad_y, grad_logdet, y, log_scale, grad_x, grad_log_scale, grad_translation, B, C, HW,
@@ -693,11 +688,11 @@ int finc_actnorm_init_f32(const float *x, float *log_scale, float *translation, 
                           size_t workspace_bytes, finc_stream_t stream)
 {
     if (!x || !log_scale || !translation) return FINC_ERR_NULL_POINTER;
-    if (int e = coupling_dims(B, C, HW)) return e;
+    if (int e = pixel_dims(B, C, HW, true)) return e;
     if ((long long)B * HW < 2) return FINC_ERR_BAD_DIMS;             // the unbiased deviation of one value (torch.std: NaN)
     if (log_scale == translation) return FINC_ERR_BAD_DIMS;
-    if (misaligned(x) || misaligned(log_scale) || misaligned(translation)) return FINC_ERR_ALIGNMENT;
-    if (!workspace || misaligned(workspace) || workspace_bytes < finc_actnorm_workspace_bytes(B, C, HW)) return FINC_ERR_WORKSPACE;
+    if (misaligned(x, log_scale, translation)) return FINC_ERR_ALIGNMENT;
+    if (workspace_short(workspace, workspace_bytes, finc_actnorm_workspace_bytes(B, C, HW))) return FINC_ERR_WORKSPACE;
     if (int e = finc_fault_gate(false)) return e;
     return finc_actnorm_init_launch(x, log_scale, translation, B, C, HW, (float *)workspace, (hipStream_t)stream);
 }

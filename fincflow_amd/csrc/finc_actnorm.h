@@ -184,38 +184,26 @@ __global__ __launch_bounds__(64) void finc_actnorm_stats_final_kernel(const floa
     }
 }
 
-// the channel's items must index as int with a full grid's stride beyond them
-inline bool an_rows_fit(int B, int C, int HW)
-{
-    return (size_t)C * HW * 4 < ((size_t)1 << 31) && (long long)B * HW < (1LL << 31) - (CPL_CHIP_WGS + 1) * CPL_THREADS;
-}
-
 } // namespace
 
-// floats: backward partials (2 outputs x C channels x (Q + 1)) or the stats' triples (3 x C x Q).  C * Q is at most
-// C * ceil(B * HW / 256) and below CPL_CHIP_WGS + C (cpl_parts); the smaller of the two, for the dword form's item count, is what is
-// reserved three times over, plus the 2 C extra slots of the backward: it never shrinks when B or HW grows.
+// floats: backward partials (2 outputs x C channels x (Q + 1)) or the stats' triples (3 x C x Q).  C * Q at its bound
+// (cpl_partials_bound) for the dword form's item count is reserved three times over, plus the 2 C extra slots of the backward.
 size_t finc_actnorm_workspace_floats(int B, int C, int HW)
 {
-    const long long items = (long long)B * HW;
-    const long long all = (long long)C * ((items + CPL_THREADS - 1) / CPL_THREADS), cap = CPL_CHIP_WGS + C;
-    return (size_t)(3 * (all < cap ? all : cap) + 2LL * C);
+    return (size_t)(3 * cpl_partials_bound((long long)B * HW, C) + 2LL * C);
 }
 
 int finc_actnorm_launch(const float *x, const float *ls, const float *tr, float *y, float *logdet, int B, int C, int HW, int direction,
                         hipStream_t st)
 {
     const bool wide = cpl_wide(HW, (uintptr_t)x | (uintptr_t)y);
-    const int V = wide ? 4 : 1, nv = HW / V;
+    const int nv = HW / (wide ? 4 : 1);
     const long long items = (long long)B * C * nv;
-    if (items >= (1LL << 32) - 4 * CPL_CHIP_WGS * CPL_THREADS) return FINC_ERR_BAD_DIMS;
-    long long wgs = (items + CPL_THREADS - 1) / CPL_THREADS;
-    if (wgs > 4 * CPL_CHIP_WGS) wgs = 4 * CPL_CHIP_WGS;
-    const dim3 grid((unsigned)wgs), block(CPL_THREADS);
-#define FINC_AN_GO(V_, D_) hipLaunchKernelGGL((finc_actnorm_kernel<V_, D_>), grid, block, 0, st, x, ls, tr, y, logdet, B, C, HW, nv, (unsigned)items)
-    if (direction > 0) { if (wide) FINC_AN_GO(4, 1); else FINC_AN_GO(1, 1); }
-    else { if (wide) FINC_AN_GO(4, -1); else FINC_AN_GO(1, -1); }
-#undef FINC_AN_GO
+    const unsigned wgs = cpl_row_grid(items);
+    if (!wgs) return FINC_ERR_BAD_DIMS;
+    const auto kernel = direction > 0 ? (wide ? finc_actnorm_kernel<4, 1> : finc_actnorm_kernel<1, 1>)
+                                      : (wide ? finc_actnorm_kernel<4, -1> : finc_actnorm_kernel<1, -1>);
+    hipLaunchKernelGGL(kernel, dim3(wgs), dim3(CPL_THREADS), 0, st, x, ls, tr, y, logdet, B, C, HW, nv, (unsigned)items);
     FINC_CHECK_LAUNCH();
     return FINC_OK;
 }
@@ -223,15 +211,13 @@ int finc_actnorm_launch(const float *x, const float *ls, const float *tr, float 
 int finc_actnorm_backward_launch(const float *gy, const float *gld, const float *y, const float *ls, float *gx, float *gls, float *gt,
                                  int B, int C, int HW, float *ws, hipStream_t st)
 {
-    if (!an_rows_fit(B, C, HW)) return FINC_ERR_BAD_DIMS;
+    if (!cpl_rows_fit(B, C, HW)) return FINC_ERR_BAD_DIMS;
     if (!gls) y = nullptr;                                           // only grad_ls reads y
     const bool wide = cpl_wide(HW, (uintptr_t)gy | (uintptr_t)y | (uintptr_t)gx);
-    const int V = wide ? 4 : 1, nv = HW / V, items = B * nv;
-    const int Q = cpl_parts(items, C);
-    const int sums = (gls || gt) ? 1 : 0;
+    const int nv = HW / (wide ? 4 : 1), items = B * nv, Q = cpl_parts(items, C), sums = (gls || gt) ? 1 : 0;
     const dim3 grid((unsigned)((long long)C * Q)), block(CPL_THREADS);
-    if (wide) hipLaunchKernelGGL(finc_actnorm_bwd_kernel<4>, grid, block, 0, st, gy, gld, y, ls, gx, ws, B, C, HW, nv, items, Q, sums);
-    else hipLaunchKernelGGL(finc_actnorm_bwd_kernel<1>, grid, block, 0, st, gy, gld, y, ls, gx, ws, B, C, HW, nv, items, Q, sums);
+    hipLaunchKernelGGL(wide ? finc_actnorm_bwd_kernel<4> : finc_actnorm_bwd_kernel<1>, grid, block, 0, st, gy, gld, y, ls, gx, ws, B, C, HW,
+                       nv, items, Q, sums);
     FINC_CHECK_LAUNCH();
     if (sums) {
         hipLaunchKernelGGL(finc_coupling_reduce_kernel, dim3((unsigned)(2 * C)), dim3(64), 0, st, (const float *)ws, Q + 1, gt, gls, 1);
@@ -242,13 +228,11 @@ int finc_actnorm_backward_launch(const float *gy, const float *gld, const float 
 
 int finc_actnorm_init_launch(const float *x, float *ls, float *tr, int B, int C, int HW, float *ws, hipStream_t st)
 {
-    if (!an_rows_fit(B, C, HW)) return FINC_ERR_BAD_DIMS;
+    if (!cpl_rows_fit(B, C, HW)) return FINC_ERR_BAD_DIMS;
     const bool wide = cpl_wide(HW, (uintptr_t)x);
-    const int V = wide ? 4 : 1, nv = HW / V, items = B * nv;
-    const int Q = cpl_parts(items, C);
+    const int nv = HW / (wide ? 4 : 1), items = B * nv, Q = cpl_parts(items, C);
     const dim3 grid((unsigned)((long long)C * Q)), block(CPL_THREADS);
-    if (wide) hipLaunchKernelGGL(finc_actnorm_stats_kernel<4>, grid, block, 0, st, x, ws, C, HW, nv, items, Q);
-    else hipLaunchKernelGGL(finc_actnorm_stats_kernel<1>, grid, block, 0, st, x, ws, C, HW, nv, items, Q);
+    hipLaunchKernelGGL(wide ? finc_actnorm_stats_kernel<4> : finc_actnorm_stats_kernel<1>, grid, block, 0, st, x, ws, C, HW, nv, items, Q);
     FINC_CHECK_LAUNCH();
     hipLaunchKernelGGL(finc_actnorm_stats_final_kernel, dim3((unsigned)C), dim3(64), 0, st, (const float *)ws, Q, ls, tr,
                        (float)((long long)B * HW - 1));

@@ -211,21 +211,30 @@ inline int cpl_parts(long long items, long long outer)
     if (p > cap) p = cap;
     return p < 1 ? 1 : (int)p;
 }
+// outer * cpl_parts(items, outer) is at most outer * ceil(items / 256) and below CPL_CHIP_WGS + outer: the smaller of these two bounds,
+// for the dword form's item count, is what a workspace reserves per sum.  It never shrinks when B or HW grows.
+inline long long cpl_partials_bound(long long items, long long outer)
+{
+    const long long all = outer * ((items + CPL_THREADS - 1) / CPL_THREADS), cap = CPL_CHIP_WGS + outer;
+    return all < cap ? all : cap;
+}
 inline bool cpl_wide(int HW, uintptr_t ptrs) { return HW % 4 == 0 && (ptrs & 15u) == 0; }
+inline bool cpl_rows_fit(int B, int C, int HW)          // a channel's B * HW / V items index as int with a full grid's stride beyond them
+{
+    return (size_t)C * HW * 4 < ((size_t)1 << 31) && (long long)B * HW < (1LL << 31) - (CPL_CHIP_WGS + 1) * CPL_THREADS;
+}
+inline unsigned cpl_row_grid(long long items)           // grid-stride over rows, up to four chips' worth; 0: they do not index as unsigned
+{
+    const long long wgs = (items + CPL_THREADS - 1) / CPL_THREADS, most = 4 * CPL_CHIP_WGS;
+    return items >= (1LL << 32) - most * CPL_THREADS ? 0u : (unsigned)(wgs > most ? most : wgs);
+}
 
 } // namespace
 
-// floats: forward log-det partials (B images x P parts) and backward partials (4 sums x C/2 pairs x Q parts).  outer * cpl_parts(items,
-// outer) is at most outer * ceil(items / 256) and below CPL_CHIP_WGS + outer; the smaller of these two bounds, for the dword form's
-// item count, is what is reserved: it never shrinks when B or HW grows.
+// floats: forward log-det partials (B images x P parts) and backward partials (4 sums x C/2 pairs x Q parts)
 size_t finc_coupling_workspace_floats(int B, int C, int HW)
 {
-    const long long half = C / 2;
-    auto bound = [](long long items, long long outer) {
-        const long long all = outer * ((items + CPL_THREADS - 1) / CPL_THREADS), cap = CPL_CHIP_WGS + outer;
-        return all < cap ? all : cap;
-    };
-    const long long fwd = bound(half * HW, B), bwd = 4 * bound((long long)B * HW, half);
+    const long long half = C / 2, fwd = cpl_partials_bound(half * HW, B), bwd = 4 * cpl_partials_bound((long long)B * HW, half);
     return (size_t)(fwd > bwd ? fwd : bwd);
 }
 
@@ -235,19 +244,14 @@ int finc_coupling_launch(const float *x, const float *raw, const float *a, const
     const int half = C / 2;
     if ((size_t)C * HW * 4 >= ((size_t)1 << 31)) return FINC_ERR_BAD_DIMS;
     const bool wide = cpl_wide(HW, (uintptr_t)x | (uintptr_t)raw | (uintptr_t)y);
-    const int V = wide ? 4 : 1, nv = HW / V, items = half * nv;
-    const int P = cpl_parts(items, B);
+    const int nv = HW / (wide ? 4 : 1), items = half * nv, P = cpl_parts(items, B);
     if ((long long)B * P >= (1LL << 31)) return FINC_ERR_BAD_DIMS;
     const dim3 grid((unsigned)((long long)B * P)), block(CPL_THREADS);
     const bool ld = direction > 0 && logdet;
-#define FINC_CPL_GO(V_, D_, L_) hipLaunchKernelGGL((finc_coupling_kernel<V_, D_, L_>), grid, block, 0, st, x, raw, a, b, y, ws, half, HW, nv, items, P)
-    if (direction > 0) {
-        if (ld) { if (wide) FINC_CPL_GO(4, 1, true); else FINC_CPL_GO(1, 1, true); }
-        else { if (wide) FINC_CPL_GO(4, 1, false); else FINC_CPL_GO(1, 1, false); }
-    } else {
-        if (wide) FINC_CPL_GO(4, -1, false); else FINC_CPL_GO(1, -1, false);
-    }
-#undef FINC_CPL_GO
+    const auto kernel = direction < 0 ? (wide ? finc_coupling_kernel<4, -1, false> : finc_coupling_kernel<1, -1, false>)
+                        : ld          ? (wide ? finc_coupling_kernel<4, 1, true> : finc_coupling_kernel<1, 1, true>)
+                                      : (wide ? finc_coupling_kernel<4, 1, false> : finc_coupling_kernel<1, 1, false>);
+    hipLaunchKernelGGL(kernel, grid, block, 0, st, x, raw, a, b, y, ws, half, HW, nv, items, P);
     FINC_CHECK_LAUNCH();
     if (ld) {
         hipLaunchKernelGGL(finc_coupling_reduce_kernel, dim3((unsigned)B), dim3(64), 0, st, (const float *)ws, P, logdet, (float *)nullptr, 0);
@@ -259,16 +263,13 @@ int finc_coupling_launch(const float *x, const float *raw, const float *a, const
 int finc_coupling_backward_launch(const float *gy, const float *gld, const float *x, const float *raw, const float *a, const float *b,
                                   float *gx, float *graw, float *ga, float *gb, int B, int C, int HW, float *ws, hipStream_t st)
 {
-    const int half = C / 2;
-    if ((size_t)C * HW * 4 >= ((size_t)1 << 31) || (long long)B * HW >= (1LL << 31) - (CPL_CHIP_WGS + 1) * CPL_THREADS)
-        return FINC_ERR_BAD_DIMS;
+    const int half = C / 2, sums = (ga || gb) ? 1 : 0;
+    if (!cpl_rows_fit(B, C, HW)) return FINC_ERR_BAD_DIMS;
     const bool wide = cpl_wide(HW, (uintptr_t)gy | (uintptr_t)x | (uintptr_t)raw | (uintptr_t)gx | (uintptr_t)graw);
-    const int V = wide ? 4 : 1, nv = HW / V, items = B * nv;
-    const int Q = cpl_parts(items, half);
-    const int sums = (ga || gb) ? 1 : 0;
+    const int nv = HW / (wide ? 4 : 1), items = B * nv, Q = cpl_parts(items, half);
     const dim3 grid((unsigned)((long long)half * Q)), block(CPL_THREADS);
-    if (wide) hipLaunchKernelGGL(finc_coupling_bwd_kernel<4>, grid, block, 0, st, gy, gld, x, raw, a, b, gx, graw, ws, half, HW, nv, items, Q, sums);
-    else hipLaunchKernelGGL(finc_coupling_bwd_kernel<1>, grid, block, 0, st, gy, gld, x, raw, a, b, gx, graw, ws, half, HW, nv, items, Q, sums);
+    hipLaunchKernelGGL(wide ? finc_coupling_bwd_kernel<4> : finc_coupling_bwd_kernel<1>, grid, block, 0, st, gy, gld, x, raw, a, b, gx, graw,
+                       ws, half, HW, nv, items, Q, sums);
     FINC_CHECK_LAUNCH();
     if (sums) {
         hipLaunchKernelGGL(finc_coupling_reduce_kernel, dim3((unsigned)(4 * half)), dim3(64), 0, st, (const float *)ws, Q, ga, gb, 1);
@@ -280,13 +281,12 @@ int finc_coupling_backward_launch(const float *gy, const float *gld, const float
 int finc_bias_relu_launch(const float *in, const float *bias, float *out, int B, int C, int HW, hipStream_t st)
 {
     const bool wide = cpl_wide(HW, (uintptr_t)in | (uintptr_t)out);
-    const int V = wide ? 4 : 1, nv = HW / V;
+    const int nv = HW / (wide ? 4 : 1);
     const long long items = (long long)B * C * nv;
-    if (items >= (1LL << 32) - 4 * CPL_CHIP_WGS * CPL_THREADS) return FINC_ERR_BAD_DIMS;
-    long long wgs = (items + CPL_THREADS - 1) / CPL_THREADS;
-    if (wgs > 4 * CPL_CHIP_WGS) wgs = 4 * CPL_CHIP_WGS;
-    if (wide) hipLaunchKernelGGL(finc_bias_relu_kernel<4>, dim3((unsigned)wgs), dim3(CPL_THREADS), 0, st, in, bias, out, C, HW, nv, (unsigned)items);
-    else hipLaunchKernelGGL(finc_bias_relu_kernel<1>, dim3((unsigned)wgs), dim3(CPL_THREADS), 0, st, in, bias, out, C, HW, nv, (unsigned)items);
+    const unsigned wgs = cpl_row_grid(items);
+    if (!wgs) return FINC_ERR_BAD_DIMS;
+    hipLaunchKernelGGL(wide ? finc_bias_relu_kernel<4> : finc_bias_relu_kernel<1>, dim3(wgs), dim3(CPL_THREADS), 0, st, in, bias, out, C, HW,
+                       nv, (unsigned)items);
     FINC_CHECK_LAUNCH();
     return FINC_OK;
 }

@@ -25,7 +25,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .layers import FastFlowUnit, FlowLayer, FlowSequential
+from . import ops
+from .layers import FastFlowUnit, FlowLayer, FlowSequential, _hip_tensor, _records_graph
 
 
 class Squeeze(FlowLayer):
@@ -85,21 +86,19 @@ class ActNorm(FlowLayer):
         return self.translation.view(shape), self.log_scale.view(shape)
 
     def _hip_device(self, x):
-        from . import ops
         p = (self.translation, self.log_scale)
-        return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == self.n_dims
+        return (_hip_tensor(x) and x.shape[1] == self.n_dims
                 and all(q.dtype == torch.float32 and q.device == x.device for q in p) and ops.actnorm_supported())
 
     def _records_graph(self, x):
-        return torch.is_grad_enabled() and (x.requires_grad or self.log_scale.requires_grad or self.translation.requires_grad)
+        return _records_graph(x, self.log_scale, self.translation)
 
     def forward(self, input, context=None):
         hip = self._hip_device(input)
         if not self._is_initialized():
             with torch.no_grad():
                 if hip and input.numel() // self.n_dims >= 2:
-                    from . import ops
-                    ops.finc_actnorm_init(input.detach().contiguous(), self.log_scale.detach(), self.translation.detach())
+                            ops.finc_actnorm_init(input.detach().contiguous(), self.log_scale.detach(), self.translation.detach())
                 else:
                     dims = [d for d in range(input.dim()) if d != 1]
                     self.translation.copy_(input.mean(dim=dims))
@@ -107,7 +106,6 @@ class ActNorm(FlowLayer):
                 self.initialized.fill_(1)
                 self._init_known = True
         if hip:
-            from . import ops
             if self._records_graph(input):
                 return ops.actnorm_forward(input, self.log_scale, self.translation)
             return ops.finc_actnorm(input.contiguous(), self.log_scale.detach(), self.translation.detach(), 1, True)
@@ -116,7 +114,6 @@ class ActNorm(FlowLayer):
 
     def reverse(self, input, context=None):
         if self._hip_device(input) and not self._records_graph(input):
-            from . import ops
             return ops.finc_actnorm(input.contiguous(), self.log_scale.detach(), self.translation.detach(), -1)[0]
         t, ls = self._shaped(input)
         return input * torch.exp(ls) + t
@@ -151,27 +148,24 @@ class Conv1x1(FlowLayer):
         self.W = nn.Parameter(torch.from_numpy(q.astype('float32')))
 
     def _hip_device(self, x):
-        from . import ops
-        return x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and ops.mix_supported(self.n_channels)
+        return _hip_tensor(x) and ops.mix_supported(self.n_channels)
 
     def _hip(self, x):
-        return not (torch.is_grad_enabled() and (self.W.requires_grad or x.requires_grad)) and self._hip_device(x)
+        return not _records_graph(x, self.W) and self._hip_device(x)
 
     def forward(self, x, context=None):
         h, w = x.shape[2:]
         ldj = h * w * torch.slogdet(self.W)[1]
         if self._hip(x):
-            from . import ops
             return ops.finc_mix(x.contiguous(), self.W.detach().contiguous()), ldj
         if torch.is_grad_enabled() and self._hip_device(x):      # training: the same kernel under autograd
-            from . import ops
             return ops.mix_forward(x, self.W), ldj
         return F.conv2d(x, self.W.view(self.n_channels, self.n_channels, 1, 1)), ldj
 
     def _inverse_matrix(self):
         # the reference inverts W on every call (layers/conv1x1.py:37-39); cache it per weight version so that a
         # sampling pass has no LU factorisation (and no host sync) in it and can be captured in a HIP graph
-        key = (self.W.data_ptr(), self.W._version, self.W.device)
+        key = ops.version_key(self.W) + (self.W.device,)
         if getattr(self, "_inv_key", None) != key:
             with torch.no_grad():
                 self._w_inv = torch.inverse(self.W.detach()).contiguous()
@@ -181,7 +175,6 @@ class Conv1x1(FlowLayer):
 
     def reverse(self, z, context=None):
         if self._hip(z):
-            from . import ops
             return ops.finc_mix(z.contiguous(), self._inverse_matrix())
         if torch.is_grad_enabled() and self.W.requires_grad:
             w_inv = torch.inverse(self.W)
@@ -195,9 +188,8 @@ class Conv1x1(FlowLayer):
         mix is a row scaling of the matrix plus a bias.  None when this call cannot take the HIP path."""
         if not self._hip(z):
             return None
-        from . import ops
         w_inv = self._inverse_matrix()
-        key = (log_scale.data_ptr(), log_scale._version, translation.data_ptr(), translation._version)
+        key = ops.version_key(log_scale, translation)
         if getattr(self, "_aff_key", None) != key:
             with torch.no_grad():
                 self._m_aff = (torch.exp(log_scale.detach().float()).view(-1, 1) * w_inv).contiguous()
@@ -212,11 +204,10 @@ class Conv1x1(FlowLayer):
         once per weight version.  None when this call cannot take the HIP path."""
         if not self._hip(z):
             return None
-        from . import ops
         w_inv = self._inverse_matrix()
         # (`lead` and `w_inv` are compared by identity and kept alive here: both are cache entries that are REPLACED when their
         # weights change, and the address of a freed tensor is the first one the allocator hands out again)
-        key = () if log_scale is None else (log_scale.data_ptr(), log_scale._version, translation.data_ptr(), translation._version)
+        key = () if log_scale is None else ops.version_key(log_scale, translation)
         if (getattr(self, "_lead_key", None) != key or getattr(self, "_lead_inv", None) is not w_inv
                 or getattr(self, "_lead_obj", None) is not lead):
             with torch.no_grad():
@@ -270,12 +261,11 @@ class Coupling(FlowLayer):
                                  Conv2dZero(width, self.n_channels))
 
     def _hip_device(self, x):
-        from . import ops
-        return x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and ops.coupling_supported(self.n_channels)
+        return _hip_tensor(x) and ops.coupling_supported(self.n_channels)
 
     def _records_graph(self, x, context):
-        return torch.is_grad_enabled() and (x.requires_grad or (context is not None and context.requires_grad)
-                                            or any(p.requires_grad for p in self.net.parameters()))
+        # (the net's parameters are walked only where a graph can be recorded at all: not per layer of a sampling pass)
+        return torch.is_grad_enabled() and _records_graph(x, context, *self.net.parameters())
 
     def _hip(self, x, context=None):
         """The inference path: HIP transform and HIP bias + ReLU, nothing recorded for autograd."""
@@ -295,7 +285,7 @@ class Coupling(FlowLayer):
         # once per parameter version: a sampling pass has no [C]-sized launches in it.  (During a stream capture nothing is cached:
         # a tensor made there is only filled when the graph replays.)
         last = self.net[4]
-        key = (last.logs.data_ptr(), last.logs._version, last.bias.data_ptr(), last.bias._version, last.logs.device)
+        key = ops.version_key(last.logs, last.bias) + (last.logs.device,)
         if getattr(self, "_ab_key", None) == key:
             return self._ab
         with torch.no_grad():
@@ -311,7 +301,6 @@ class Coupling(FlowLayer):
         return x1 if context is None else torch.cat([x1, context], dim=1)
 
     def _raw_inference(self, x, context):
-        from . import ops
         n = self.net
         with torch.no_grad():
             h = F.conv2d(self._net_input(x, context), n[0].weight, None, padding=1).contiguous()
@@ -329,12 +318,10 @@ class Coupling(FlowLayer):
 
     def forward(self, input, context=None):
         if self._hip(input, context):
-            from . import ops
             x = input.contiguous()
             a, b = self._scale_shift_cached()
             return ops.finc_coupling(x, self._raw_inference(x, context), a, b, 1, True)
         if self._hip_train(input, context):
-            from . import ops
             n = self.net
             raw = F.conv2d(n[:4](self._net_input(input, context)), n[4].weight, None, padding=1)
             a, b = self._scale_shift()
@@ -344,7 +331,6 @@ class Coupling(FlowLayer):
 
     def reverse(self, input, context=None):
         if self._hip(input, context):
-            from . import ops
             x = input.contiguous()
             a, b = self._scale_shift_cached()
             return ops.finc_coupling(x, self._raw_inference(x, context), a, b, -1, False)[0]

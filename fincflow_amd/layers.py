@@ -19,6 +19,16 @@ import torch.nn as nn
 from . import _lib, ops
 
 
+def _hip_tensor(x):
+    """The activations every HIP path of the model takes: fp32, [B,C,H,W], on the device."""
+    return x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+
+
+def _records_graph(x, *params):
+    """Does a call on `x` with these parameters (None: absent) record an autograd graph?"""
+    return torch.is_grad_enabled() and (x.requires_grad or any(p is not None and p.requires_grad for p in params))
+
+
 class FlowLayer(nn.Module, metaclass=ABCMeta):
     """layers/flowlayer.py:8-30."""
 
@@ -108,7 +118,7 @@ class PaddedConv2d(FlowLayer):
             self.conv.weight.grad = self.conv.weight.grad * self.mask.to(self.conv.weight.grad.device)
 
     def forward(self, x, context=None, compute_expensive=None):
-        if torch.is_grad_enabled() and (x.requires_grad or self.conv.weight.requires_grad):
+        if _records_graph(x, self.conv.weight):
             out = ops.conv_forward(x, [self.conv.weight], 1, self._orient, self._cache)
         else:  # density evaluation / sampling checks: cached fragments, one launch
             out = self._cache.forward(x.contiguous(), [self.conv.weight], 1, self._orient)
@@ -150,7 +160,7 @@ class FastFlowUnit(nn.Module):
                 self.conv_br.conv.weight]
 
     def forward(self, x, context=None):
-        if torch.is_grad_enabled() and (x.requires_grad or any(w.requires_grad for w in self._weights())):
+        if _records_graph(x, *self._weights()):
             out = ops.conv_forward(x, self._weights(), 4, ops.ORIENT_FASTFLOW, self._cache)
         else:  # density evaluation / sampling checks: cached fragments, one launch
             out = self._cache.forward(x.contiguous(), self._weights(), 4, ops.ORIENT_FASTFLOW)
@@ -178,9 +188,7 @@ class FastFlowUnit(nn.Module):
         bias) also applies blockdiag(Linv_g) of this unit -- the same dense C x C product per pixel -- and the inverse
         runs without its z-term.  `mix` exposes `reverse_premultiplied(u, lead, log_scale, translation)`.  None when this
         call cannot take that path (shape without the kernel, autograd on, CPU tensors)."""
-        if torch.is_grad_enabled() and (u.requires_grad or any(w.requires_grad for w in self._weights())):
-            return None
-        if not u.is_cuda or u.dtype != torch.float32 or u.dim() != 4:
+        if _records_graph(u, *self._weights()) or not _hip_tensor(u):
             return None
         with torch.no_grad():
             if not self._cache.premultiplied_supported(tuple(u.shape), self._weights(), 4, ops.ORIENT_FASTFLOW):
@@ -194,7 +202,7 @@ class FastFlowUnit(nn.Module):
     def forward_affine(self, x, log_scale, translation):
         """(forward(x) - translation) * exp(-log_scale): the ActNorm behind the unit rides in the forward bank (SURVEY 8
         f3, forward direction).  Inference only; None if this call cannot take the fused path."""
-        if torch.is_grad_enabled() and (x.requires_grad or any(w.requires_grad for w in self._weights())):
+        if _records_graph(x, *self._weights()):
             return None
         with torch.no_grad():
             return self._cache.forward_affine(x.contiguous(), self._weights(), 4, ops.ORIENT_FASTFLOW, log_scale,

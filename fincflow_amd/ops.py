@@ -40,6 +40,59 @@ def _float_dtype(t, name):
     return t.dtype
 
 
+def _out_like(x, out, dtype=torch.float32):
+    if out is None:
+        return torch.empty_like(x)
+    _require_device(out, "output", dtype)
+    if out.shape != x.shape or out.device != x.device:
+        raise ValueError("output must match input in shape and device")
+    return out
+
+
+def _per_channel(x, label, *tensors):
+    if any(t.numel() != x.shape[1] or t.device != x.device for t in tensors):
+        raise ValueError(f"{label} must have one entry per channel, on the activations' device")
+
+
+def _per_image(t, name, x):
+    if t is not None:
+        _require_device(t, name)
+        if t.numel() != x.shape[0] or t.device != x.device:
+            raise ValueError(f"{name} must have one entry per image, on the activations' device")
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def version_key(*tensors):
+    """(address, version counter) of every tensor, flat: what the caches of values derived from parameters are keyed on."""
+    return tuple(v for t in tensors for v in (t.data_ptr(), t._version))
+
+
+def _nothing_to_launch(x, grads, sums):
+    """An empty batch (the sums over it are zero) or no gradient asked for: `grads` is the result as it stands."""
+    if x.numel() == 0:
+        for t in sums:
+            if t is not None:
+                t.zero_()
+        return True
+    return all(g is None for g in grads)
+
+
+def _call(name, device, *args, may_refuse=False):
+    """One entry point of the library under the device guard, its status checked under the same name.  `may_refuse`: hand
+    FINC_ERR_UNSUPPORTED (3) back to a caller that has another path; every other failure raises here all the same.
+    (The symbol is looked up on `_lib.lib()` per call, as every call site did: ctypes keeps a bound symbol in the library object's
+    own dict, and bench.py swaps that object for one pass to bracket the launches.)"""
+    fn = getattr(_lib.lib(), name)
+    with torch.cuda.device(device):
+        st = fn(*args)
+    if st and not (may_refuse and st == 3):
+        _lib.check(st, name)
+    return st
+
+
 def release_workspaces():
     """Drop every cached per-(device, stream) scratch buffer (they are re-created on demand).  For long-lived
     processes that cycle through many streams; call it at a synchronisation point."""
@@ -53,6 +106,14 @@ def _workspace(device, nbytes):
         ws = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
         _workspaces[key] = ws
     return ws
+
+
+def _ws_args(device, nbytes):
+    """(pointer, size) of the stream's scratch buffer grown to `nbytes`; (None, 0) for a call that needs none (`nbytes` None)."""
+    if nbytes is None:
+        return None, 0
+    ws = _workspace(device, nbytes)
+    return ws.data_ptr(), ws.numel()
 
 
 def _dims(act, w, G):
@@ -77,20 +138,16 @@ def canonicalize(w_stored, G, orient):
     out = torch.empty_like(w_stored)
     Cq = w_stored.shape[0] // G
     fn = "finc_canonicalize_weights_f32" if dt == torch.float32 else "finc_canonicalize_weights_f64"
-    with torch.cuda.device(w_stored.device):
-        st = getattr(_lib.lib(), fn)(w_stored.data_ptr(), out.data_ptr(), G, Cq, w_stored.shape[2],
-                                     w_stored.shape[3], orient, _stream_ptr(w_stored))
-    _lib.check(st, fn)
+    _call(fn, w_stored.device, w_stored.data_ptr(), out.data_ptr(), G, Cq, w_stored.shape[2], w_stored.shape[3], orient,
+          _stream_ptr(w_stored))
     return out
 
 
 def check_invariant(w_canon, G):
     """Raises if the corner tap is not unit lower triangular (layers/conv.py:63-70).  Synchronises."""
     _require_device(w_canon, "weights")
-    with torch.cuda.device(w_canon.device):
-        st = _lib.lib().finc_check_invariant_f32(w_canon.data_ptr(), G, w_canon.shape[0] // G, w_canon.shape[2],
-                                                 w_canon.shape[3], _stream_ptr(w_canon))
-    _lib.check(st, "finc_check_invariant_f32")
+    _call("finc_check_invariant_f32", w_canon.device, w_canon.data_ptr(), G, w_canon.shape[0] // G, w_canon.shape[2],
+          w_canon.shape[3], _stream_ptr(w_canon))
 
 
 def _run(fn_name, act, w_canon, G, orient, algo, out):
@@ -98,39 +155,26 @@ def _run(fn_name, act, w_canon, G, orient, algo, out):
     _require_device(act, "input", dt)
     _require_device(w_canon, "kernel", dt)
     B, Cq, H, W, KH, KW = _dims(act, w_canon, G)
-    if out is None:
-        out = torch.empty_like(act)
-    else:
-        _require_device(out, "output", dt)
-        if out.shape != act.shape or out.device != act.device:
-            raise ValueError("output must match input in shape and device")
+    out = _out_like(act, out, dt)
     if act.numel() == 0:
         return out
     L = _lib.lib()
+    run = (act.data_ptr(), w_canon.data_ptr(), out.data_ptr(), B, G, Cq, H, W, KH, KW, orient)
     if dt == torch.float64:
         # strict: the reference-order fp64 kernels (bit-exact with the reference's Cython solver; no packed form, no workspace);
         # auto / mfma: the matrix-core form where the bank has one (finc_f64.hip: Cq <= 24 at 3x3, <= 32 at 2x2), else strict
         fn64 = fn_name.replace("_f32", "_f64")
-        with torch.cuda.device(act.device):
-            if algo == "strict":
-                st = getattr(L, fn64)(act.data_ptr(), w_canon.data_ptr(), out.data_ptr(), B, G, Cq, H, W, KH, KW, orient,
-                                      _stream_ptr(act))
-            else:
-                ws = _workspace(act.device, L.finc_f64_workspace_bytes(G, Cq, KH, KW))
-                fn64 += "_algo"
-                st = getattr(L, fn64)(act.data_ptr(), w_canon.data_ptr(), out.data_ptr(), B, G, Cq, H, W, KH, KW, orient,
-                                      _lib.ALGO[algo], ws.data_ptr(), ws.numel(), _stream_ptr(act))
-        _lib.check(st, fn64)
+        if algo == "strict":
+            _call(fn64, act.device, *run, _stream_ptr(act))
+        else:
+            _call(fn64 + "_algo", act.device, *run, _lib.ALGO[algo], *_ws_args(act.device, L.finc_f64_workspace_bytes(G, Cq, KH, KW)),
+                  _stream_ptr(act))
         return out
     if fn_name == "finc_inverse_f32":      # room for the zero-padded copy an odd width is solved on
         nbytes = L.finc_inverse_workspace_bytes(B, G, Cq, H, W, KH, KW)
     else:
         nbytes = L.finc_workspace_bytes(G, Cq, KH, KW)
-    with torch.cuda.device(act.device):
-        ws = _workspace(act.device, nbytes)
-        st = getattr(L, fn_name)(act.data_ptr(), w_canon.data_ptr(), out.data_ptr(), B, G, Cq, H, W, KH, KW, orient,
-                                 _lib.ALGO[algo], ws.data_ptr(), ws.numel(), _stream_ptr(act))
-    _lib.check(st, fn_name)
+    _call(fn_name, act.device, *run, _lib.ALGO[algo], *_ws_args(act.device, nbytes), _stream_ptr(act))
     return out
 
 
@@ -153,14 +197,8 @@ def finc_backward(grad_z, x, w_canon, G, orient, need_gx=True, need_gw=True):
         if gw is not None:
             gw.zero_()
         return gx, gw
-    L = _lib.lib()
-    with torch.cuda.device(grad_z.device):
-        ws = _workspace(grad_z.device, L.finc_backward_workspace_bytes(B, G, Cq, H, W, KH, KW))
-        st = L.finc_backward_f32(grad_z.data_ptr(), x.data_ptr() if x is not None else None,
-                                 w_canon.data_ptr(), gx.data_ptr() if gx is not None else None,
-                                 gw.data_ptr() if gw is not None else None, B, G, Cq, H, W, KH, KW, orient,
-                                 ws.data_ptr(), ws.numel(), _stream_ptr(grad_z))
-    _lib.check(st, "finc_backward_f32")
+    _call("finc_backward_f32", grad_z.device, grad_z.data_ptr(), _ptr(x), w_canon.data_ptr(), _ptr(gx), _ptr(gw), B, G, Cq, H, W, KH, KW,
+          orient, *_ws_args(grad_z.device, _lib.lib().finc_backward_workspace_bytes(B, G, Cq, H, W, KH, KW)), _stream_ptr(grad_z))
     return gx, gw
 
 
@@ -180,19 +218,11 @@ def finc_mix(x, mat, bias=None, out=None):
         _require_device(bias, "bias")
         if bias.numel() != x.shape[1]:
             raise ValueError("bias must have one entry per channel")
-    if out is None:
-        out = torch.empty_like(x)
-    else:
-        _require_device(out, "output")
-        if out.shape != x.shape or out.device != x.device:
-            raise ValueError("output must match input in shape and device")
+    out = _out_like(x, out)
     if x.numel() == 0:
         return out
     B, C, H, W = x.shape
-    with torch.cuda.device(x.device):
-        st = _lib.lib().finc_mix_f32(x.data_ptr(), mat.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                     out.data_ptr(), B, C, H * W, _stream_ptr(x))
-    _lib.check(st, "finc_mix_f32")
+    _call("finc_mix_f32", x.device, x.data_ptr(), mat.data_ptr(), _ptr(bias), out.data_ptr(), B, C, H * W, _stream_ptr(x))
     return out
 
 
@@ -215,20 +245,11 @@ def finc_mix_backward(grad_out, x, mat, need_gx=True, need_gm=True, need_gb=Fals
     gx = torch.empty_like(grad_out) if need_gx else None
     gm = torch.empty_like(mat) if need_gm else None
     gb = torch.empty(C, dtype=torch.float32, device=grad_out.device) if need_gb else None
-    if not (need_gx or need_gm or need_gb):
+    if _nothing_to_launch(grad_out, (gx, gm, gb), (gm, gb)):
         return gx, gm, gb
-    if grad_out.numel() == 0:
-        for t in (gm, gb):
-            if t is not None:
-                t.zero_()
-        return gx, gm, gb
-    L = _lib.lib()
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    with torch.cuda.device(grad_out.device):
-        ws = _workspace(grad_out.device, L.finc_mix_backward_workspace_bytes(B, C, H * W)) if (need_gm or need_gb) else None
-        st = L.finc_mix_backward_f32(grad_out.data_ptr(), ptr(x) if need_gm else None, mat.data_ptr(), ptr(gx), ptr(gm), ptr(gb),
-                                     B, C, H * W, ptr(ws), ws.numel() if ws is not None else 0, _stream_ptr(grad_out))
-    _lib.check(st, "finc_mix_backward_f32")
+    nbytes = _lib.lib().finc_mix_backward_workspace_bytes(B, C, H * W) if (need_gm or need_gb) else None
+    _call("finc_mix_backward_f32", grad_out.device, grad_out.data_ptr(), _ptr(x) if need_gm else None, mat.data_ptr(), _ptr(gx), _ptr(gm),
+          _ptr(gb), B, C, H * W, *_ws_args(grad_out.device, nbytes), _stream_ptr(grad_out))
     return gx, gm, gb
 
 
@@ -269,8 +290,7 @@ def _coupling_args(x, raw, a, b, what="input"):
     if x.dim() != 4 or raw.shape != x.shape or raw.device != x.device:
         raise ValueError(f"expected {what} [B,C,H,W] and the coupling net's output of the same shape on the same device")
     C = x.shape[1]
-    if a.numel() != C or b.numel() != C or a.device != x.device or b.device != x.device:
-        raise ValueError("scale and shift must have one entry per channel, on the activations' device")
+    _per_channel(x, "scale and shift", a, b)
     if not coupling_supported(C):
         raise _lib.FincError(f"finc_coupling: no kernel for {C} channels (the coupling splits an even channel count)")
 
@@ -283,24 +303,15 @@ def finc_coupling(x, raw, a, b, direction=1, want_logdet=False, out=None):
     _coupling_args(x, raw, a, b)
     if direction not in (1, -1):
         raise ValueError("direction must be +1 (forward) or -1 (reverse)")
-    if out is None:
-        out = torch.empty_like(x)
-    else:
-        _require_device(out, "output")
-        if out.shape != x.shape or out.device != x.device:
-            raise ValueError("output must match input in shape and device")
+    out = _out_like(x, out)
     B, C, H, W = x.shape
     want_logdet = bool(want_logdet) and direction == 1
     if x.numel() == 0:
         return out, (torch.zeros(B, dtype=torch.float32, device=x.device) if want_logdet else None)
     logdet = torch.empty(B, dtype=torch.float32, device=x.device) if want_logdet else None
-    L = _lib.lib()
-    with torch.cuda.device(x.device):
-        ws = _workspace(x.device, L.finc_coupling_workspace_bytes(B, C, H * W)) if want_logdet else None
-        st = L.finc_coupling_f32(x.data_ptr(), raw.data_ptr(), a.data_ptr(), b.data_ptr(), out.data_ptr(),
-                                 logdet.data_ptr() if want_logdet else None, B, C, H * W, direction,
-                                 ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, _stream_ptr(x))
-    _lib.check(st, "finc_coupling_f32")
+    nbytes = _lib.lib().finc_coupling_workspace_bytes(B, C, H * W) if want_logdet else None
+    _call("finc_coupling_f32", x.device, x.data_ptr(), raw.data_ptr(), a.data_ptr(), b.data_ptr(), out.data_ptr(), _ptr(logdet), B, C,
+          H * W, direction, *_ws_args(x.device, nbytes), _stream_ptr(x))
     return out, logdet
 
 
@@ -314,30 +325,23 @@ def finc_coupling_backward(grad_y, grad_logdet, x, raw, a, b, need_gx=True, need
     if grad_y.shape != x.shape or grad_y.device != x.device:
         raise ValueError("grad_output must match input in shape and device")
     B, C, H, W = x.shape
-    if grad_logdet is not None:
-        _require_device(grad_logdet, "grad_logdet")
-        if grad_logdet.numel() != B or grad_logdet.device != x.device:
-            raise ValueError("grad_logdet must have one entry per image, on the activations' device")
+    _per_image(grad_logdet, "grad_logdet", x)
     gx = torch.empty_like(x) if need_gx else None
     graw = torch.empty_like(raw) if need_graw else None
     ga = torch.empty(C, dtype=torch.float32, device=x.device) if need_ga else None
     gb = torch.empty(C, dtype=torch.float32, device=x.device) if need_gb else None
-    if not (need_gx or need_graw or need_ga or need_gb):
+    if _nothing_to_launch(x, (gx, graw, ga, gb), (ga, gb)):
         return gx, graw, ga, gb
-    if x.numel() == 0:
-        for t in (ga, gb):
-            if t is not None:
-                t.zero_()
-        return gx, graw, ga, gb
-    L = _lib.lib()
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    with torch.cuda.device(x.device):
-        ws = _workspace(x.device, L.finc_coupling_workspace_bytes(B, C, H * W)) if (need_ga or need_gb) else None
-        st = L.finc_coupling_backward_f32(grad_y.data_ptr(), ptr(grad_logdet), x.data_ptr(), raw.data_ptr(), a.data_ptr(), b.data_ptr(),
-                                          ptr(gx), ptr(graw), ptr(ga), ptr(gb), B, C, H * W, ptr(ws),
-                                          ws.numel() if ws is not None else 0, _stream_ptr(x))
-    _lib.check(st, "finc_coupling_backward_f32")
+    nbytes = _lib.lib().finc_coupling_workspace_bytes(B, C, H * W) if (need_ga or need_gb) else None
+    _call("finc_coupling_backward_f32", x.device, grad_y.data_ptr(), _ptr(grad_logdet), x.data_ptr(), raw.data_ptr(), a.data_ptr(),
+          b.data_ptr(), _ptr(gx), _ptr(graw), _ptr(ga), _ptr(gb), B, C, H * W, *_ws_args(x.device, nbytes), _stream_ptr(x))
     return gx, graw, ga, gb
+
+
+def _incoming_grads(like, grad_y, grad_logdet):
+    """What a (y, logdet) Function's backward is handed, as the kernels take it: contiguous, zeros for a `y` nobody used (None)."""
+    grad_y = torch.zeros_like(like) if grad_y is None else grad_y
+    return grad_y.contiguous(), None if grad_logdet is None else grad_logdet.contiguous()
 
 
 class _FincCouplingFunction(torch.autograd.Function):
@@ -354,10 +358,8 @@ class _FincCouplingFunction(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_y, grad_logdet):
         x, raw, a, b = ctx.saved_tensors
-        if grad_y is None:
-            grad_y = torch.zeros_like(x)
         need = ctx.needs_input_grad
-        return finc_coupling_backward(grad_y.contiguous(), None if grad_logdet is None else grad_logdet.contiguous(), x, raw, a, b,
+        return finc_coupling_backward(*_incoming_grads(x, grad_y, grad_logdet), x, raw, a, b,
                                       need_gx=need[0], need_graw=need[1], need_ga=need[2], need_gb=need[3])
 
 
@@ -374,32 +376,19 @@ def finc_bias_relu(x, bias, out=None):
     _require_device(bias, "bias")
     if x.dim() != 4 or bias.numel() != x.shape[1] or bias.device != x.device:
         raise ValueError("expected activations [B,C,H,W] and one bias entry per channel on the same device")
-    if out is None:
-        out = torch.empty_like(x)
-    else:
-        _require_device(out, "output")
-        if out.shape != x.shape or out.device != x.device:
-            raise ValueError("output must match input in shape and device")
+    out = _out_like(x, out)
     if x.numel() == 0:
         return out
     B, C, H, W = x.shape
-    with torch.cuda.device(x.device):
-        st = _lib.lib().finc_bias_relu_f32(x.data_ptr(), bias.data_ptr(), out.data_ptr(), B, C, H * W, _stream_ptr(x))
-    _lib.check(st, "finc_bias_relu_f32")
+    _call("finc_bias_relu_f32", x.device, x.data_ptr(), bias.data_ptr(), out.data_ptr(), B, C, H * W, _stream_ptr(x))
     return out
-
-
-_actnorm_ok = None
 
 
 def actnorm_supported():
     """ActNorm's kernels take any channel count, and a library without them does not load (fincflow_amd._lib: ACTNORM_ABI_VERSION):
     True once the library is loaded, no call into it per layer and pass."""
-    global _actnorm_ok
-    if _actnorm_ok is None:
-        _lib.lib()
-        _actnorm_ok = True
-    return _actnorm_ok
+    _lib.lib()
+    return True
 
 
 def _actnorm_args(x, log_scale, translation, what="input"):
@@ -407,13 +396,10 @@ def _actnorm_args(x, log_scale, translation, what="input"):
     _require_device(log_scale, "log_scale")
     if x.dim() != 4:
         raise ValueError(f"expected {what} [B,C,H,W]")
-    C = x.shape[1]
-    if log_scale.numel() != C or log_scale.device != x.device:
-        raise ValueError("log_scale must have one entry per channel, on the activations' device")
+    _per_channel(x, "log_scale", log_scale)
     if translation is not None:
         _require_device(translation, "translation")
-        if translation.numel() != C or translation.device != x.device:
-            raise ValueError("translation must have one entry per channel, on the activations' device")
+        _per_channel(x, "translation", translation)
 
 
 def finc_actnorm(x, log_scale, translation, direction=1, want_logdet=False, out=None):
@@ -424,21 +410,14 @@ def finc_actnorm(x, log_scale, translation, direction=1, want_logdet=False, out=
     _actnorm_args(x, log_scale, translation)
     if direction not in (1, -1):
         raise ValueError("direction must be +1 (forward) or -1 (reverse)")
-    if out is None:
-        out = torch.empty_like(x)
-    else:
-        _require_device(out, "output")
-        if out.shape != x.shape or out.device != x.device:
-            raise ValueError("output must match input in shape and device")
+    out = _out_like(x, out)
     B, C, H, W = x.shape
     want_logdet = bool(want_logdet) and direction == 1
     if x.numel() == 0:
         return out, (torch.zeros(B, dtype=torch.float32, device=x.device) if want_logdet else None)
     logdet = torch.empty(B, dtype=torch.float32, device=x.device) if want_logdet else None
-    with torch.cuda.device(x.device):
-        st = _lib.lib().finc_actnorm_f32(x.data_ptr(), log_scale.data_ptr(), translation.data_ptr(), out.data_ptr(),
-                                         logdet.data_ptr() if want_logdet else None, B, C, H * W, direction, _stream_ptr(x))
-    _lib.check(st, "finc_actnorm_f32")
+    _call("finc_actnorm_f32", x.device, x.data_ptr(), log_scale.data_ptr(), translation.data_ptr(), out.data_ptr(), _ptr(logdet), B, C,
+          H * W, direction, _stream_ptr(x))
     return out, logdet
 
 
@@ -451,27 +430,15 @@ def finc_actnorm_backward(grad_y, grad_logdet, y, log_scale, need_gx=True, need_
     if grad_y.shape != y.shape or grad_y.device != y.device:
         raise ValueError("grad_output must match the forward's output in shape and device")
     B, C, H, W = y.shape
-    if grad_logdet is not None:
-        _require_device(grad_logdet, "grad_logdet")
-        if grad_logdet.numel() != B or grad_logdet.device != y.device:
-            raise ValueError("grad_logdet must have one entry per image, on the activations' device")
+    _per_image(grad_logdet, "grad_logdet", y)
     gx = torch.empty_like(y) if need_gx else None
     gls = torch.empty(C, dtype=torch.float32, device=y.device) if need_gls else None
     gt = torch.empty(C, dtype=torch.float32, device=y.device) if need_gt else None
-    if not (need_gx or need_gls or need_gt):
+    if _nothing_to_launch(y, (gx, gls, gt), (gls, gt)):
         return gx, gls, gt
-    if y.numel() == 0:
-        for t in (gls, gt):
-            if t is not None:
-                t.zero_()
-        return gx, gls, gt
-    L = _lib.lib()
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    with torch.cuda.device(y.device):
-        ws = _workspace(y.device, L.finc_actnorm_workspace_bytes(B, C, H * W)) if (need_gls or need_gt) else None
-        st = L.finc_actnorm_backward_f32(grad_y.data_ptr(), ptr(grad_logdet), y.data_ptr(), log_scale.data_ptr(), ptr(gx), ptr(gls),
-                                         ptr(gt), B, C, H * W, ptr(ws), ws.numel() if ws is not None else 0, _stream_ptr(y))
-    _lib.check(st, "finc_actnorm_backward_f32")
+    nbytes = _lib.lib().finc_actnorm_workspace_bytes(B, C, H * W) if (need_gls or need_gt) else None
+    _call("finc_actnorm_backward_f32", y.device, grad_y.data_ptr(), _ptr(grad_logdet), y.data_ptr(), log_scale.data_ptr(), _ptr(gx),
+          _ptr(gls), _ptr(gt), B, C, H * W, *_ws_args(y.device, nbytes), _stream_ptr(y))
     return gx, gls, gt
 
 
@@ -483,12 +450,8 @@ def finc_actnorm_init(x, log_scale, translation):
     B, C, H, W = x.shape
     if B * H * W < 2:
         raise ValueError("the unbiased standard deviation needs at least two values per channel")
-    L = _lib.lib()
-    with torch.cuda.device(x.device):
-        ws = _workspace(x.device, L.finc_actnorm_workspace_bytes(B, C, H * W))
-        st = L.finc_actnorm_init_f32(x.data_ptr(), log_scale.data_ptr(), translation.data_ptr(), B, C, H * W, ws.data_ptr(), ws.numel(),
-                                     _stream_ptr(x))
-    _lib.check(st, "finc_actnorm_init_f32")
+    _call("finc_actnorm_init_f32", x.device, x.data_ptr(), log_scale.data_ptr(), translation.data_ptr(), B, C, H * W,
+          *_ws_args(x.device, _lib.lib().finc_actnorm_workspace_bytes(B, C, H * W)), _stream_ptr(x))
     # the kernel wrote behind PyTorch's back: the caches keyed on (address, version) of the parameters (FlowSequential's folds) must see it
     torch.autograd.graph.increment_version(log_scale)
     torch.autograd.graph.increment_version(translation)
@@ -510,10 +473,8 @@ class _FincActNormFunction(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_y, grad_logdet):
         y, log_scale = ctx.saved_tensors
-        if grad_y is None:
-            grad_y = torch.zeros_like(y)
         need = ctx.needs_input_grad
-        return finc_actnorm_backward(grad_y.contiguous(), None if grad_logdet is None else grad_logdet.contiguous(), y, log_scale,
+        return finc_actnorm_backward(*_incoming_grads(y, grad_y, grad_logdet), y, log_scale,
                                      need_gx=need[0], need_gls=need[1], need_gt=need[2])
 
 
@@ -599,7 +560,7 @@ class PackedWeights:
         # The entry is keyed on (address, version counter) of every source tensor AND holds their storages alive: a weight
         # rebound through `.data` to a fresh tensor keeps its version counter, and the address of a freed tensor is the first
         # one the allocator hands out again -- with the old storage still referenced here the new one cannot land on it.
-        key = tuple((w.data_ptr(), w._version) for w in weights) + (orient,)
+        key = version_key(*weights) + (orient,)
         if key != bank.key:
             ws = torch.cat([w.detach() for w in weights], dim=0).contiguous() if len(weights) > 1 else weights[0].detach().contiguous()
             bank.w_canon = canonicalize(ws, G, orient)
@@ -630,15 +591,13 @@ class PackedWeights:
         L = _lib.lib()
         if x.numel() == 0 or L.finc_forward_algo_for(Cq, H, W, KH, KW) != _lib.ALGO["mfma"]:
             return finc_forward(x, w_canon, G, orient, out=out)
-        with torch.cuda.device(x.device):
-            if bank.packed_fwd is None:
-                bank.packed_fwd = torch.empty(L.finc_workspace_bytes(G, Cq, KH, KW), dtype=torch.uint8, device=x.device)
-                _lib.check(L.finc_pack_forward_weights_f32(w_canon.data_ptr(), bank.packed_fwd.data_ptr(), G, Cq, KH, KW,
-                                                           _stream_ptr(x)), "finc_pack_forward_weights_f32")
-            if out is None:
-                out = torch.empty_like(x)
-            _lib.check(L.finc_forward_packed_f32(x.data_ptr(), bank.packed_fwd.data_ptr(), out.data_ptr(), B, G, Cq, H, W,
-                                                 KH, KW, orient, _stream_ptr(x)), "finc_forward_packed_f32")
+        if bank.packed_fwd is None:
+            bank.packed_fwd = torch.empty(L.finc_workspace_bytes(G, Cq, KH, KW), dtype=torch.uint8, device=x.device)
+            _call("finc_pack_forward_weights_f32", x.device, w_canon.data_ptr(), bank.packed_fwd.data_ptr(), G, Cq, KH, KW, _stream_ptr(x))
+        if out is None:
+            out = torch.empty_like(x)
+        _call("finc_forward_packed_f32", x.device, x.data_ptr(), bank.packed_fwd.data_ptr(), out.data_ptr(), B, G, Cq, H, W, KH, KW,
+              orient, _stream_ptr(x))
         return out
 
     def forward_affine(self, x, weights, G, orient, log_scale, translation, out=None):
@@ -652,22 +611,20 @@ class PackedWeights:
         L = _lib.lib()
         if x.numel() == 0 or L.finc_forward_algo_for(Cq, H, W, KH, KW) != _lib.ALGO["mfma"]:
             return None
-        key = (log_scale.data_ptr(), log_scale._version, translation.data_ptr(), translation._version)
-        with torch.cuda.device(x.device):
-            if bank.packed_faff is None or bank.faff_key != key:
-                scale = torch.exp(-log_scale.detach().float()).contiguous()
-                shift = (-translation.detach().float() * scale).contiguous()
-                if scale.numel() != G * Cq:
-                    raise ValueError("affine parameters must have one entry per channel")
-                bank.packed_faff = torch.empty(L.finc_workspace_bytes(G, Cq, KH, KW), dtype=torch.uint8, device=x.device)
-                _lib.check(L.finc_pack_forward_weights_affine_f32(w_canon.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                                                                  bank.packed_faff.data_ptr(), G, Cq, KH, KW, _stream_ptr(x)),
-                           "finc_pack_forward_weights_affine_f32")
-                bank.faff_key = key
-            if out is None:
-                out = torch.empty_like(x)
-            _lib.check(L.finc_forward_packed_f32(x.data_ptr(), bank.packed_faff.data_ptr(), out.data_ptr(), B, G, Cq, H, W,
-                                                 KH, KW, orient, _stream_ptr(x)), "finc_forward_packed_f32")
+        key = version_key(log_scale, translation)
+        if bank.packed_faff is None or bank.faff_key != key:
+            scale = torch.exp(-log_scale.detach().float()).contiguous()
+            shift = (-translation.detach().float() * scale).contiguous()
+            if scale.numel() != G * Cq:
+                raise ValueError("affine parameters must have one entry per channel")
+            bank.packed_faff = torch.empty(L.finc_workspace_bytes(G, Cq, KH, KW), dtype=torch.uint8, device=x.device)
+            _call("finc_pack_forward_weights_affine_f32", x.device, w_canon.data_ptr(), scale.data_ptr(), shift.data_ptr(),
+                  bank.packed_faff.data_ptr(), G, Cq, KH, KW, _stream_ptr(x))
+            bank.faff_key = key
+        if out is None:
+            out = torch.empty_like(x)
+        _call("finc_forward_packed_f32", x.device, x.data_ptr(), bank.packed_faff.data_ptr(), out.data_ptr(), B, G, Cq, H, W, KH, KW,
+              orient, _stream_ptr(x))
         return out
 
     @staticmethod
@@ -679,6 +636,15 @@ class PackedWeights:
         ptrs = t.data_ptr() | (out.data_ptr() if out is not None else 0)
         return (ptrs & 15) == 0
 
+    @staticmethod
+    def _packed_inverse(bank, t, G, Cq, KH, KW):
+        """The bank's packed inverse fragments, packed on `t`'s stream the first time a weight version asks for them."""
+        if bank.packed_inv is None:
+            bank.packed_inv = torch.empty(_lib.lib().finc_workspace_bytes(G, Cq, KH, KW), dtype=torch.uint8, device=t.device)
+            _call("finc_pack_inverse_weights_f32", t.device, bank.w_canon.data_ptr(), bank.packed_inv.data_ptr(), G, Cq, KH, KW,
+                  _stream_ptr(t))
+        return bank.packed_inv
+
     def inverse(self, z, weights, G, orient, out=None):
         bank = self._get(weights, G, orient)
         w_canon = bank.w_canon
@@ -689,13 +655,9 @@ class PackedWeights:
             out = torch.empty_like(z)
         if not self._packed_path_ok(L, z, out, Cq, H, W, KH, KW):
             return finc_inverse(z, w_canon, G, orient, out=out)
-        with torch.cuda.device(z.device):
-            if bank.packed_inv is None:
-                bank.packed_inv = torch.empty(L.finc_workspace_bytes(G, Cq, KH, KW), dtype=torch.uint8, device=z.device)
-                _lib.check(L.finc_pack_inverse_weights_f32(w_canon.data_ptr(), bank.packed_inv.data_ptr(), G, Cq, KH, KW,
-                                                           _stream_ptr(z)), "finc_pack_inverse_weights_f32")
-            _lib.check(L.finc_inverse_packed_f32(z.data_ptr(), bank.packed_inv.data_ptr(), out.data_ptr(), B, G, Cq, H, W,
-                                                 KH, KW, orient, _stream_ptr(z)), "finc_inverse_packed_f32")
+        packed = self._packed_inverse(bank, z, G, Cq, KH, KW)
+        _call("finc_inverse_packed_f32", z.device, z.data_ptr(), packed.data_ptr(), out.data_ptr(), B, G, Cq, H, W, KH, KW, orient,
+              _stream_ptr(z))
         return out
 
     def lead_inverse(self, weights, G, orient):
@@ -734,14 +696,9 @@ class PackedWeights:
             out = torch.empty_like(zp)
         if (zp.data_ptr() | out.data_ptr()) & 15:
             return None
-        with torch.cuda.device(zp.device):
-            if bank.packed_inv is None:
-                bank.packed_inv = torch.empty(L.finc_workspace_bytes(G, Cq, KH, KW), dtype=torch.uint8, device=zp.device)
-                _lib.check(L.finc_pack_inverse_weights_f32(w_canon.data_ptr(), bank.packed_inv.data_ptr(), G, Cq, KH, KW,
-                                                           _stream_ptr(zp)), "finc_pack_inverse_weights_f32")
-            _lib.check(L.finc_inverse_packed_premultiplied_f32(zp.data_ptr(), bank.packed_inv.data_ptr(), out.data_ptr(), B, G,
-                                                               Cq, H, W, KH, KW, orient, _stream_ptr(zp)),
-                       "finc_inverse_packed_premultiplied_f32")
+        packed = self._packed_inverse(bank, zp, G, Cq, KH, KW)
+        _call("finc_inverse_packed_premultiplied_f32", zp.device, zp.data_ptr(), packed.data_ptr(), out.data_ptr(), B, G, Cq, H, W, KH,
+              KW, orient, _stream_ptr(zp))
         return out
 
     def inverse_affine(self, y, weights, G, orient, log_scale, translation, out=None):
@@ -762,26 +719,23 @@ class PackedWeights:
         # over from the 33..64-channel banks (Cq = 50 at 256 columns) carry a scale and nothing else -> two launches there
         if not L.finc_inverse_affine_supported(B, G, Cq, H, W, KH, KW):
             return None
-        key = (log_scale.data_ptr(), log_scale._version, translation.data_ptr(), translation._version)
-        with torch.cuda.device(y.device):
-            if bank.packed_aff is None or bank.aff_key != key:
-                scale = torch.exp(log_scale.detach().float()).contiguous()
-                shift = translation.detach().float().contiguous()
-                if scale.numel() != G * Cq or shift.numel() != G * Cq:
-                    raise ValueError("affine parameters must have one entry per channel")
-                packed = torch.empty(L.finc_workspace_bytes(G, Cq, KH, KW), dtype=torch.uint8, device=y.device)
-                st = L.finc_pack_inverse_weights_affine_f32(w_canon.data_ptr(), scale.data_ptr(), shift.data_ptr(), packed.data_ptr(),
-                                                            G, Cq, KH, KW, _stream_ptr(y))
-                if st == 3:        # FINC_ERR_UNSUPPORTED: a bank whose kernel cannot carry the shift (the big banks, finc_big.hip)
-                    return None
-                _lib.check(st, "finc_pack_inverse_weights_affine_f32")
-                bank.packed_aff = packed
-                bank.aff_key = key
-            st = L.finc_inverse_packed_f32(y.data_ptr(), bank.packed_aff.data_ptr(), out.data_ptr(), B, G, Cq, H, W, KH, KW, orient,
-                                           _stream_ptr(y))
-            if st == 3:            # (the launch itself refuses a shift-carrying bank on a map it cannot serve)
+        key = version_key(log_scale, translation)
+        if bank.packed_aff is None or bank.aff_key != key:
+            scale = torch.exp(log_scale.detach().float()).contiguous()
+            shift = translation.detach().float().contiguous()
+            if scale.numel() != G * Cq or shift.numel() != G * Cq:
+                raise ValueError("affine parameters must have one entry per channel")
+            packed = torch.empty(L.finc_workspace_bytes(G, Cq, KH, KW), dtype=torch.uint8, device=y.device)
+            # FINC_ERR_UNSUPPORTED: a bank whose kernel cannot carry the shift (the big banks, finc_big.hip)
+            if _call("finc_pack_inverse_weights_affine_f32", y.device, w_canon.data_ptr(), scale.data_ptr(), shift.data_ptr(),
+                     packed.data_ptr(), G, Cq, KH, KW, _stream_ptr(y), may_refuse=True):
                 return None
-            _lib.check(st, "finc_inverse_packed_f32")
+            bank.packed_aff = packed
+            bank.aff_key = key
+        # (the launch itself refuses a shift-carrying bank on a map it cannot serve)
+        if _call("finc_inverse_packed_f32", y.device, y.data_ptr(), bank.packed_aff.data_ptr(), out.data_ptr(), B, G, Cq, H, W, KH, KW,
+                 orient, _stream_ptr(y), may_refuse=True):
+            return None
         return out
 
 

@@ -1,6 +1,10 @@
-"""Shared helpers for the parity tests (numpy only)."""
+"""Shared helpers for the parity tests (numpy only; torch is imported where a helper needs it)."""
+import ctypes
 import glob
 import os
+import shutil
+import subprocess
+import sys
 
 import numpy as np
 
@@ -29,6 +33,53 @@ def rel_err(a, b):
     a = np.asarray(a, dtype=np.float64)
     b = np.asarray(b, dtype=np.float64)
     return float(np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-30))
+
+
+# ---------------------------------------------------------------------------
+# the per-pixel layers' host and GPU tests (mix backward, coupling, ActNorm)
+# ---------------------------------------------------------------------------
+def fake_ptr(v):
+    """An address for a status-code test: the entry points refuse before anything reads it."""
+    return ctypes.c_void_p(v)
+
+
+def offset_view(t, dev):
+    """A contiguous device copy of `t` that starts one float into its allocation: 4-byte aligned, not 16."""
+    import torch
+    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=dev)
+    v = buf[1:].view(t.shape)
+    v.copy_(t)
+    assert v.is_contiguous() and v.data_ptr() % 16 == 4
+    return v
+
+
+def load_stub_library(tmp_path, version, mask_path=True):
+    """What `fincflow_amd._lib.lib()` says, in a fresh process, to a library that exports finc_version() = `version` and nothing
+    else: the text of its FincError (any other outcome fails the calling test).  `mask_path`: the library's path reads `<lib>` in
+    that text, for callers that search it for version numbers."""
+    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
+    assert cc, "no C compiler to build the stub library with"
+    d = tmp_path / ("stub" + "abcdef"[version % 6])         # (a directory name without digits, one per version)
+    d.mkdir()
+    src = d / "old.c"
+    src.write_text("int finc_version(void) { return %d; }\n" % version)
+    so = d / "libold.so"
+    subprocess.check_call([cc, "-shared", "-fPIC", "-o", str(so), str(src)])
+    code = ("import sys\n"
+            "from fincflow_amd import _lib\n"
+            "try:\n"
+            "    _lib.lib()\n"
+            "except _lib.FincError as e:\n"
+            "    print('FincError:', e)\n"
+            "    sys.exit(0)\n"
+            "except BaseException as e:\n"
+            "    print(type(e).__name__, e)\n"
+            "    sys.exit(3)\n"
+            "sys.exit(4)\n")
+    env = dict(os.environ, FINCFLOW_LIB=str(so), PYTHONPATH=REPO + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, cwd=REPO, timeout=300)
+    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr[-500:])
+    return r.stdout.replace(str(so), "<lib>") if mask_path else r.stdout
 
 
 # ---------------------------------------------------------------------------

@@ -2,11 +2,7 @@
 exported symbols and the second ABI version gate, argument refusals before any HIP call, the workspace size, the kernels' register
 allocation, and the unchanged PyTorch path of glow.ActNorm on CPU tensors against the reference-made fixtures
 (tests/golden/make_golden_actnorm.py) -- no GPU needed, the library built."""
-import ctypes
 import os
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -14,7 +10,7 @@ import torch
 
 from actnorm_cases import BIG, BIG_IMAGES, CASES, inputs
 from fincflow_amd import _lib
-from helpers import golden, rel_err
+from helpers import fake_ptr as _p, golden, load_stub_library, rel_err
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("finc_actnorm_workspace_bytes", "finc_actnorm_f32", "finc_actnorm_backward_f32", "finc_actnorm_init_f32")
@@ -33,43 +29,13 @@ def test_new_symbols_are_exported_declared_and_bound():
     assert ops.actnorm_supported()
 
 
-def _load_stub(tmp_path, version):
-    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
-    assert cc, "no C compiler to build the stub library with"
-    d = tmp_path / ("stub" + "abcdef"[version % 6])         # (a directory name without digits: the message is searched for version numbers)
-    d.mkdir()
-    src = d / "old.c"
-    src.write_text("int finc_version(void) { return %d; }\n" % version)
-    so = d / "libold.so"
-    subprocess.check_call([cc, "-shared", "-fPIC", "-o", str(so), str(src)])
-    code = ("import sys\n"
-            "from fincflow_amd import _lib\n"
-            "try:\n"
-            "    _lib.lib()\n"
-            "except _lib.FincError as e:\n"
-            "    print('FincError:', str(e).replace(sys.argv[1], '<lib>'))\n"
-            "    sys.exit(0)\n"
-            "except BaseException as e:\n"
-            "    print(type(e).__name__, e)\n"
-            "    sys.exit(3)\n"
-            "sys.exit(4)\n")
-    env = dict(os.environ, FINCFLOW_LIB=str(so), PYTHONPATH=REPO + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    r = subprocess.run([sys.executable, "-c", code, str(so)], env=env, capture_output=True, text=True, cwd=REPO, timeout=300)
-    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr[-500:])
-    return r.stdout
-
-
 def test_version_is_105_and_older_libraries_are_refused_by_name(tmp_path):
     assert _lib.lib().finc_version() >= 105
     assert _lib.ABI_VERSION == 104 and _lib.ACTNORM_ABI_VERSION == 105
-    out = _load_stub(tmp_path, 104)
+    out = load_stub_library(tmp_path, 104)
     assert "= 104" in out and "105" in out and "finc_actnorm_f32" in out, out
-    out = _load_stub(tmp_path, 103)
+    out = load_stub_library(tmp_path, 103)
     assert "= 103" in out and "at least 104" in out, out
-
-
-def _p(v):
-    return ctypes.c_void_p(v)
 
 
 def test_actnorm_status_codes_without_touching_the_gpu():

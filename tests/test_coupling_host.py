@@ -1,17 +1,14 @@
 """Host side of the coupling kernels (finc_coupling_f32, finc_coupling_backward_f32, finc_bias_relu_f32; include/finc.h): the
 exported symbols and the ABI version gate, argument refusals before any HIP call, the workspace size, the kernels' register
 allocation, and the unchanged PyTorch path of glow.Coupling / SplitPrior on CPU tensors -- no GPU needed, the library built."""
-import ctypes
 import os
-import shutil
-import subprocess
-import sys
 
 import pytest
 import torch
 import torch.nn.functional as F
 
 from fincflow_amd import _lib
+from helpers import fake_ptr as _p, load_stub_library
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("finc_coupling_supported_f32", "finc_coupling_workspace_bytes", "finc_coupling_f32", "finc_coupling_backward_f32",
@@ -34,33 +31,8 @@ def test_new_symbols_are_exported_declared_and_bound():
 def test_version_is_104_and_a_103_library_is_refused_by_name(tmp_path):
     assert _lib.lib().finc_version() >= 104
     assert _lib.ABI_VERSION >= 104
-    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
-    assert cc, "no C compiler to build the stub library with"
-    d = tmp_path / "stub"                       # (a directory name without digits: the message is searched for version numbers)
-    d.mkdir()
-    src = d / "old.c"
-    src.write_text("int finc_version(void) { return 103; }\n")
-    so = d / "libold.so"
-    subprocess.check_call([cc, "-shared", "-fPIC", "-o", str(so), str(src)])
-    code = ("import sys\n"
-            "from fincflow_amd import _lib\n"
-            "try:\n"
-            "    _lib.lib()\n"
-            "except _lib.FincError as e:\n"
-            "    print('FincError:', str(e).replace(sys.argv[1], '<lib>'))\n"
-            "    sys.exit(0)\n"
-            "except BaseException as e:\n"
-            "    print(type(e).__name__, e)\n"
-            "    sys.exit(3)\n"
-            "sys.exit(4)\n")
-    env = dict(os.environ, FINCFLOW_LIB=str(so), PYTHONPATH=REPO + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    r = subprocess.run([sys.executable, "-c", code, str(so)], env=env, capture_output=True, text=True, cwd=REPO, timeout=300)
-    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr[-500:])
-    assert "= 103" in r.stdout and "at least 104" in r.stdout, r.stdout
-
-
-def _p(v):
-    return ctypes.c_void_p(v)
+    out = load_stub_library(tmp_path, 103)
+    assert "= 103" in out and "at least 104" in out, out
 
 
 def test_coupling_status_codes_without_touching_the_gpu():

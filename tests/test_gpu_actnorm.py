@@ -16,7 +16,7 @@ import pytest
 import torch
 
 from actnorm_cases import BIG, BIG_IMAGES, CASES, inputs
-from helpers import STACK_INPUT, fill_stack_parameters, golden, rel_err, report
+from helpers import STACK_INPUT, fill_stack_parameters, golden, offset_view, rel_err, report
 
 pytestmark = pytest.mark.gpu
 
@@ -62,15 +62,6 @@ def ref_gradients(x, ls, t, gy, gl):
         loss = loss + (ld * gl.double()).sum()
     loss.backward()
     return [v.grad.numpy() for v in leaves]
-
-
-def offset_view(t, dev):
-    """A contiguous device copy of `t` that starts one float into its allocation: 4-byte aligned, not 16."""
-    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=dev)
-    v = buf[1:].view(t.shape)
-    v.copy_(t)
-    assert v.is_contiguous() and v.data_ptr() % 16 == 4
-    return v
 
 
 def fixture_case(name):

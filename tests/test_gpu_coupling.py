@@ -12,7 +12,7 @@ import itertools
 import pytest
 import torch
 
-from helpers import rel_err, report
+from helpers import offset_view, rel_err, report
 
 pytestmark = pytest.mark.gpu
 
@@ -66,15 +66,6 @@ def ref_gradients(x, raw, a, b, gy, gl):
         loss = loss + (ld * gl.double()).sum()
     loss.backward()
     return [t.grad.numpy() for t in leaves]
-
-
-def offset_view(t, dev):
-    """A contiguous device copy of `t` that starts one float into its allocation: 4-byte aligned, not 16."""
-    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=dev)
-    v = buf[1:].view(t.shape)
-    v.copy_(t)
-    assert v.is_contiguous() and v.data_ptr() % 16 == 4
-    return v
 
 
 def check_transform(shape, dev, move, kind):

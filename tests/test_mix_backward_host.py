@@ -1,16 +1,13 @@
 """Host side of the mix's backward (finc_mix_backward_f32, include/finc.h): argument validation before any HIP call, the
 workspace size, the ABI version gate of the ctypes binding, the unchanged CPU path of glow.Conv1x1, and the register
 allocation of the new weight-gradient kernel -- no GPU needed, the library built."""
-import ctypes
 import os
-import shutil
-import subprocess
-import sys
 
 import pytest
 import torch
 
 from fincflow_amd import _lib
+from helpers import fake_ptr as p, load_stub_library
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MIX_CHANNELS = (4, 8, 12, 16, 24, 32, 48, 64, 96, 128, 192)
@@ -20,7 +17,6 @@ def test_status_codes_without_touching_the_gpu():
     """NULL -> 1, bad dims / aliasing -> 2, alignment below 4 bytes -> 7, unsupported C -> 3, workspace -> 4, in that order of
     precedence, with fake pointers: nothing is launched."""
     L = _lib.lib()
-    p = lambda v: ctypes.c_void_p(v)
     go, x, m, gi, gm, gb, ws = p(0x1000), p(0x2000), p(0x3000), p(0x4000), p(0x5000), p(0x6000), p(0x10000)
     big = 1 << 40
     f = L.finc_mix_backward_f32
@@ -71,27 +67,8 @@ def test_workspace_size_is_positive_and_monotone_in_the_pixel_count():
 def test_version_is_103_and_an_older_library_is_refused_by_name(tmp_path):
     assert _lib.lib().finc_version() >= 103
     assert _lib.ABI_VERSION >= 103
-    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
-    assert cc, "no C compiler to build the stub library with"
-    src = tmp_path / "old.c"
-    src.write_text("int finc_version(void) { return 102; }\n")
-    so = tmp_path / "libold.so"
-    subprocess.check_call([cc, "-shared", "-fPIC", "-o", str(so), str(src)])
-    code = ("import sys\n"
-            "from fincflow_amd import _lib\n"
-            "try:\n"
-            "    _lib.lib()\n"
-            "except _lib.FincError as e:\n"
-            "    print('FincError:', e)\n"
-            "    sys.exit(0)\n"
-            "except BaseException as e:\n"
-            "    print(type(e).__name__, e)\n"
-            "    sys.exit(3)\n"
-            "sys.exit(4)\n")
-    env = dict(os.environ, FINCFLOW_LIB=str(so), PYTHONPATH=REPO + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, cwd=REPO, timeout=300)
-    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr[-500:])
-    assert "102" in r.stdout and "103" in r.stdout, r.stdout
+    out = load_stub_library(tmp_path, 102, mask_path=False)
+    assert "102" in out and "103" in out, out
 
 
 def test_conv1x1_on_cpu_tensors_is_plain_conv2d_autograd():
