@@ -74,9 +74,22 @@ int check_shape(int B, int G, int Cq, int H, int W, int KH, int KW)
     return FINC_OK;
 }
 
-// any of the pointers off a 4-byte boundary?  (nullptr, an output nobody asked for, is aligned)
+// any of the pointers off a boundary of `mask` + 1 bytes?  (nullptr, an output nobody asked for, is aligned)
 template <typename... P>
-inline bool misaligned(const P *...p) { return ((... | (uintptr_t)p) & 3u) != 0; }
+inline bool off_boundary(uintptr_t mask, const P *...p) { return ((... | (uintptr_t)p) & mask) != 0; }
+template <typename... P>
+inline bool misaligned(const P *...p) { return off_boundary(3u, p...); }
+
+// What the unit's entry points refuse first, in the order tests/test_abi.py pins: NULL, the dims, a pointer off its element size
+// (`mask`: 3 for fp32, 7 for fp64; `bank` is held to it as a weight tensor, packed fragments have no rule), then in == out.
+int unit_prelude(const void *in, const void *bank, const void *out, int B, int G, int Cq, int H, int W, int KH, int KW, uintptr_t mask,
+                 bool bank_is_tensor)
+{
+    if (!in || !bank || !out) return FINC_ERR_NULL_POINTER;
+    if (int e = check_shape(B, G, Cq, H, W, KH, KW)) return e;
+    if (off_boundary(mask, in, out, bank_is_tensor ? bank : nullptr)) return FINC_ERR_ALIGNMENT;
+    return in == out ? FINC_ERR_BAD_DIMS : FINC_OK;
+}
 
 } // namespace
 
@@ -328,10 +341,7 @@ static int run(const float *in, const float *w_canon, float *out, int B, int G, 
                int KW, unsigned orient, int algo, void *workspace, size_t workspace_bytes, finc_stream_t stream,
                bool forward)
 {
-    if (!in || !w_canon || !out) return FINC_ERR_NULL_POINTER;
-    if (int e = check_shape(B, G, Cq, H, W, KH, KW)) return e;
-    if (misaligned(in) || misaligned(w_canon) || misaligned(out)) return FINC_ERR_ALIGNMENT;
-    if (in == out) return FINC_ERR_BAD_DIMS;
+    if (int e = unit_prelude(in, w_canon, out, B, G, Cq, H, W, KH, KW, 3, true)) return e;
     if (int e = finc_fault_gate(false)) return e;          // an earlier launch on this device gave up a protocol wait
     FincShape s{B, G, Cq, H, W, KH, KW, orient};
     hipStream_t st = (hipStream_t)stream;
@@ -384,55 +394,48 @@ int finc_forward_f32(const float *x, const float *w_canon, float *z, int B, int 
     return run(x, w_canon, z, B, G, Cq, H, W, KH, KW, orient, algo, workspace, workspace_bytes, stream, true);
 }
 
-static int pack(const float *w_canon, void *packed, int G, int Cq, int KH, int KW, finc_stream_t stream, bool forward)
+// `scale`, `shift`: the per-channel affine neighbour folded into the fragments, or nullptr (the plain banks)
+static int pack(const float *w_canon, const float *scale, const float *shift, void *packed, int G, int Cq, int KH, int KW,
+                finc_stream_t stream, bool forward)
 {
     if (!w_canon || !packed) return FINC_ERR_NULL_POINTER;
     if (int e = check_shape(1, G, Cq, 1, 1, KH, KW)) return e;
     if (forward) {
         if (finc_conv_packed_bytes(G, Cq, KH, KW) == 0) return FINC_ERR_UNSUPPORTED;
-        return finc_conv_pack(w_canon, packed, G, Cq, KH, KW, false, (hipStream_t)stream);
+        return finc_conv_pack(w_canon, packed, G, Cq, KH, KW, false, (hipStream_t)stream, scale, shift);
     }
     if (finc_mfma_packed_bytes(G, Cq, KH, KW) == 0) return FINC_ERR_UNSUPPORTED;
-    return finc_mfma_pack(w_canon, nullptr, nullptr, packed, G, Cq, KH, KW, (hipStream_t)stream);
+    return finc_mfma_pack(w_canon, scale, shift, packed, G, Cq, KH, KW, (hipStream_t)stream);
 }
 
 int finc_pack_inverse_weights_f32(const float *w_canon, void *packed, int G, int Cq, int KH, int KW,
                                   finc_stream_t stream)
 {
-    return pack(w_canon, packed, G, Cq, KH, KW, stream, false);
+    return pack(w_canon, nullptr, nullptr, packed, G, Cq, KH, KW, stream, false);
 }
 
 int finc_pack_inverse_weights_affine_f32(const float *w_canon, const float *scale, const float *shift, void *packed,
                                          int G, int Cq, int KH, int KW, finc_stream_t stream)
 {
-    if (!w_canon || !packed) return FINC_ERR_NULL_POINTER;
-    if (int e = check_shape(1, G, Cq, 1, 1, KH, KW)) return e;
-    if (finc_mfma_packed_bytes(G, Cq, KH, KW) == 0) return FINC_ERR_UNSUPPORTED;
-    return finc_mfma_pack(w_canon, scale, shift, packed, G, Cq, KH, KW, (hipStream_t)stream);
+    return pack(w_canon, scale, shift, packed, G, Cq, KH, KW, stream, false);
 }
 
 int finc_pack_forward_weights_f32(const float *w_canon, void *packed, int G, int Cq, int KH, int KW,
                                   finc_stream_t stream)
 {
-    return pack(w_canon, packed, G, Cq, KH, KW, stream, true);
+    return pack(w_canon, nullptr, nullptr, packed, G, Cq, KH, KW, stream, true);
 }
 
 int finc_pack_forward_weights_affine_f32(const float *w_canon, const float *scale, const float *shift, void *packed,
                                          int G, int Cq, int KH, int KW, finc_stream_t stream)
 {
-    if (!w_canon || !packed) return FINC_ERR_NULL_POINTER;
-    if (int e = check_shape(1, G, Cq, 1, 1, KH, KW)) return e;
-    if (finc_conv_packed_bytes(G, Cq, KH, KW) == 0) return FINC_ERR_UNSUPPORTED;
-    return finc_conv_pack(w_canon, packed, G, Cq, KH, KW, false, (hipStream_t)stream, scale, shift);
+    return pack(w_canon, scale, shift, packed, G, Cq, KH, KW, stream, true);
 }
 
 static int run_packed(const float *in, const void *packed, float *out, int B, int G, int Cq, int H, int W, int KH,
                       int KW, unsigned orient, finc_stream_t stream, bool forward)
 {
-    if (!in || !packed || !out) return FINC_ERR_NULL_POINTER;
-    if (int e = check_shape(B, G, Cq, H, W, KH, KW)) return e;
-    if (misaligned(in) || misaligned(out)) return FINC_ERR_ALIGNMENT;
-    if (in == out) return FINC_ERR_BAD_DIMS;
+    if (int e = unit_prelude(in, packed, out, B, G, Cq, H, W, KH, KW, 3, false)) return e;
     if (int e = finc_fault_gate(false)) return e;
     FincShape s{B, G, Cq, H, W, KH, KW, orient};
     if (forward) {
@@ -470,36 +473,10 @@ int finc_inverse_premultiplied_supported(int B, int G, int Cq, int H, int W, int
 int finc_inverse_packed_premultiplied_f32(const float *zp, const void *packed, float *x, int B, int G, int Cq, int H, int W,
                                           int KH, int KW, unsigned orient, finc_stream_t stream)
 {
-    if (!zp || !packed || !x) return FINC_ERR_NULL_POINTER;
-    if (int e = check_shape(B, G, Cq, H, W, KH, KW)) return e;
-    if (misaligned(zp) || misaligned(x)) return FINC_ERR_ALIGNMENT;
-    if (zp == x) return FINC_ERR_BAD_DIMS;
+    if (int e = unit_prelude(zp, packed, x, B, G, Cq, H, W, KH, KW, 3, false)) return e;
+    // (unlike run_packed: neither the fault gate nor finc_mfma_supported is consulted here -- a known difference)
     FincShape s{B, G, Cq, H, W, KH, KW, orient};
     return finc_mfma_launch(zp, packed, x, s, (hipStream_t)stream, true);
-}
-
-static int run_f64(const double *in, const double *w_canon, double *out, int B, int G, int Cq, int H, int W, int KH,
-                   int KW, unsigned orient, finc_stream_t stream, bool forward)
-{
-    if (!in || !w_canon || !out) return FINC_ERR_NULL_POINTER;
-    if (int e = check_shape(B, G, Cq, H, W, KH, KW)) return e;
-    if (((uintptr_t)in | (uintptr_t)w_canon | (uintptr_t)out) & 7u) return FINC_ERR_ALIGNMENT;
-    if (in == out) return FINC_ERR_BAD_DIMS;
-    FincShape s{B, G, Cq, H, W, KH, KW, orient};
-    return forward ? finc_launch_forward_generic_f64(in, w_canon, out, s, (hipStream_t)stream)
-                   : finc_launch_inverse_strict_f64(in, w_canon, out, s, (hipStream_t)stream);
-}
-
-int finc_inverse_f64(const double *z, const double *w_canon, double *x, int B, int G, int Cq, int H, int W, int KH,
-                     int KW, unsigned orient, finc_stream_t stream)
-{
-    return run_f64(z, w_canon, x, B, G, Cq, H, W, KH, KW, orient, stream, false);
-}
-
-int finc_forward_f64(const double *x, const double *w_canon, double *z, int B, int G, int Cq, int H, int W, int KH,
-                     int KW, unsigned orient, finc_stream_t stream)
-{
-    return run_f64(x, w_canon, z, B, G, Cq, H, W, KH, KW, orient, stream, true);
 }
 
 size_t finc_f64_workspace_bytes(int G, int Cq, int KH, int KW)
@@ -511,10 +488,7 @@ size_t finc_f64_workspace_bytes(int G, int Cq, int KH, int KW)
 static int run_f64_algo(const double *in, const double *w_canon, double *out, int B, int G, int Cq, int H, int W, int KH, int KW,
                         unsigned orient, int algo, void *workspace, size_t workspace_bytes, finc_stream_t stream, bool forward)
 {
-    if (!in || !w_canon || !out) return FINC_ERR_NULL_POINTER;
-    if (int e = check_shape(B, G, Cq, H, W, KH, KW)) return e;
-    if (((uintptr_t)in | (uintptr_t)w_canon | (uintptr_t)out) & 7u) return FINC_ERR_ALIGNMENT;
-    if (in == out) return FINC_ERR_BAD_DIMS;
+    if (int e = unit_prelude(in, w_canon, out, B, G, Cq, H, W, KH, KW, 7, true)) return e;
     if (algo != FINC_ALGO_AUTO && algo != FINC_ALGO_STRICT && algo != FINC_ALGO_MFMA) return FINC_ERR_BAD_DIMS;
     FincShape s{B, G, Cq, H, W, KH, KW, orient};
     const bool can = algo != FINC_ALGO_STRICT && finc_f64_supported(s) && workspace && ((uintptr_t)workspace & 7u) == 0 &&
@@ -526,6 +500,19 @@ static int run_f64_algo(const double *in, const double *w_canon, double *out, in
     }
     if (int e = finc_fault_gate(false)) return e;
     return finc_f64_launch(in, w_canon, out, workspace, s, forward, (hipStream_t)stream);
+}
+
+// the reference-order kernels: the strict path, which needs no workspace
+int finc_inverse_f64(const double *z, const double *w_canon, double *x, int B, int G, int Cq, int H, int W, int KH,
+                     int KW, unsigned orient, finc_stream_t stream)
+{
+    return run_f64_algo(z, w_canon, x, B, G, Cq, H, W, KH, KW, orient, FINC_ALGO_STRICT, nullptr, 0, stream, false);
+}
+
+int finc_forward_f64(const double *x, const double *w_canon, double *z, int B, int G, int Cq, int H, int W, int KH,
+                     int KW, unsigned orient, finc_stream_t stream)
+{
+    return run_f64_algo(x, w_canon, z, B, G, Cq, H, W, KH, KW, orient, FINC_ALGO_STRICT, nullptr, 0, stream, true);
 }
 
 int finc_inverse_f64_algo(const double *z, const double *w_canon, double *x, int B, int G, int Cq, int H, int W, int KH, int KW,
@@ -759,6 +746,7 @@ int finc_backward_f32(const float *grad_z, const float *x, const float *w_canon,
                       int B, int G, int Cq, int H, int W, int KH, int KW, unsigned orient, void *workspace,
                       size_t workspace_bytes, finc_stream_t stream)
 {
+    // (its own prelude: every output is optional, what must be there depends on which is asked for, and no pointer has an alignment rule)
     if (!grad_z) return FINC_ERR_NULL_POINTER;
     if (grad_x && !w_canon) return FINC_ERR_NULL_POINTER;
     if (grad_w_canon && !x) return FINC_ERR_NULL_POINTER;

@@ -117,11 +117,14 @@ class PaddedConv2d(FlowLayer):
         if self.conv.weight.grad is not None:
             self.conv.weight.grad = self.conv.weight.grad * self.mask.to(self.conv.weight.grad.device)
 
+    def _cache_args(self):   # (weights, G, orient): what the cache's methods take after the activations
+        return [self.conv.weight], 1, self._orient
+
     def forward(self, x, context=None, compute_expensive=None):
         if _records_graph(x, self.conv.weight):
-            out = ops.conv_forward(x, [self.conv.weight], 1, self._orient, self._cache)
+            out = ops.conv_forward(x, *self._cache_args(), self._cache)
         else:  # density evaluation / sampling checks: cached fragments, one launch
-            out = self._cache.forward(x.contiguous(), [self.conv.weight], 1, self._orient)
+            out = self._cache.forward(x.contiguous(), *self._cache_args())
         b = self.bias if self.bias is not None else self.conv.bias          # (conv.bias: set by hand, the reference's dead branch)
         if b is not None:
             out = out + b.view(1, -1, 1, 1)
@@ -132,7 +135,7 @@ class PaddedConv2d(FlowLayer):
             b = self.bias if self.bias is not None else self.conv.bias
             if b is not None:
                 x = x - b.reshape(-1, x.shape[1], 1, 1)
-            y = self._cache.inverse(x.contiguous(), [self.conv.weight], 1, self._orient)
+            y = self._cache.inverse(x.contiguous(), *self._cache_args())
         return y, 0
 
     def logdet(self, x=None, context=None):
@@ -159,11 +162,14 @@ class FastFlowUnit(nn.Module):
         return [self.conv_tl.conv.weight, self.conv_tr.conv.weight, self.conv_bl.conv.weight,
                 self.conv_br.conv.weight]
 
+    def _cache_args(self):   # (weights, G, orient): what the cache's methods take after the activations
+        return self._weights(), 4, ops.ORIENT_FASTFLOW
+
     def forward(self, x, context=None):
         if _records_graph(x, *self._weights()):
-            out = ops.conv_forward(x, self._weights(), 4, ops.ORIENT_FASTFLOW, self._cache)
+            out = ops.conv_forward(x, *self._cache_args(), self._cache)
         else:  # density evaluation / sampling checks: cached fragments, one launch
-            out = self._cache.forward(x.contiguous(), self._weights(), 4, ops.ORIENT_FASTFLOW)
+            out = self._cache.forward(x.contiguous(), *self._cache_args())
         return out, 0.0
 
     def reverse(self, x, context=None):
@@ -172,15 +178,14 @@ class FastFlowUnit(nn.Module):
     def reverse_level2(self, x):
         """fastflow.py:78-100 without the 6 flip/cat/zeros copies: the kernel indexes the flipped pixel."""
         with torch.no_grad():
-            return self._cache.inverse(x.contiguous(), self._weights(), 4, ops.ORIENT_FASTFLOW)
+            return self._cache.inverse(x.contiguous(), *self._cache_args())
 
     def reverse_affine(self, y, log_scale, translation):
         """reverse(exp(log_scale) * y + translation): the ActNorm that follows the unit in the model precedes it in the
         reverse chain, and its affine map rides in the inverse's filter bank at no cost per step.
         Returns None if this shape cannot take the fused path."""
         with torch.no_grad():
-            return self._cache.inverse_affine(y.contiguous(), self._weights(), 4, ops.ORIENT_FASTFLOW, log_scale,
-                                              translation)
+            return self._cache.inverse_affine(y.contiguous(), *self._cache_args(), log_scale, translation)
 
     def reverse_after_mix(self, u, mix, affine=None):
         """reverse(affine(mix.reverse(u))) in TWO launches that cost less than the plain two: the channel mix
@@ -191,13 +196,13 @@ class FastFlowUnit(nn.Module):
         if _records_graph(u, *self._weights()) or not _hip_tensor(u):
             return None
         with torch.no_grad():
-            if not self._cache.premultiplied_supported(tuple(u.shape), self._weights(), 4, ops.ORIENT_FASTFLOW):
+            if not self._cache.premultiplied_supported(tuple(u.shape), *self._cache_args()):
                 return None
-            lead = self._cache.lead_inverse(self._weights(), 4, ops.ORIENT_FASTFLOW)
+            lead = self._cache.lead_inverse(*self._cache_args())
             zp = mix.reverse_premultiplied(u, lead, *(affine if affine is not None else (None, None)))
             if zp is None:
                 return None
-            return self._cache.inverse_premultiplied(zp, self._weights(), 4, ops.ORIENT_FASTFLOW)
+            return self._cache.inverse_premultiplied(zp, *self._cache_args())
 
     def forward_affine(self, x, log_scale, translation):
         """(forward(x) - translation) * exp(-log_scale): the ActNorm behind the unit rides in the forward bank (SURVEY 8
@@ -205,8 +210,7 @@ class FastFlowUnit(nn.Module):
         if _records_graph(x, *self._weights()):
             return None
         with torch.no_grad():
-            return self._cache.forward_affine(x.contiguous(), self._weights(), 4, ops.ORIENT_FASTFLOW, log_scale,
-                                              translation)
+            return self._cache.forward_affine(x.contiguous(), *self._cache_args(), log_scale, translation)
 
     def reverse_level1(self, x):
         """fastflow.py:57-76: one solve per group."""

@@ -500,22 +500,67 @@ def inverse(input, kernel, output):
 
 
 class _DeviceBank:
-    """What PackedWeights holds for ONE device."""
-    __slots__ = ("key", "keep", "validated", "w_canon", "packed_inv", "packed_fwd", "packed_aff", "aff_key", "packed_faff",
-                 "faff_key", "linv")
+    """What PackedWeights holds for ONE device and ONE weight version: a new version starts from a fresh object."""
+    __slots__ = ("key", "keep", "validated", "w_canon", "linv", "packed")
 
-    def __init__(self):
-        self.key = None
-        self.keep = None          # the source tensors' storages, kept alive while the entry is (see PackedWeights._get)
+    def __init__(self, key=None, keep=None, w_canon=None):
+        self.key = key
+        self.keep = keep          # the source tensors' storages, kept alive while the entry is (see PackedWeights._get)
         self.validated = False    # check_invariant has run on THIS weight version
-        self.w_canon = None
-        self.packed_inv = None
-        self.packed_fwd = None
-        self.packed_aff = None
-        self.aff_key = None
-        self.packed_faff = None
-        self.faff_key = None
+        self.w_canon = w_canon
         self.linv = None
+        self.packed = {}          # bank kind -> (key of the folded affine parameters or None, packed fragments)
+
+
+def _fold_forward(log_scale, translation):
+    """(y - translation) * exp(-log_scale) behind the forward, as the (scale, shift) its bank carries."""
+    scale = torch.exp(-log_scale.detach().float()).contiguous()
+    return scale, (-translation.detach().float() * scale).contiguous()
+
+
+def _fold_inverse(log_scale, translation):
+    """exp(log_scale) * y + translation in front of the inverse, as the (scale, shift) its bank carries."""
+    return torch.exp(log_scale.detach().float()).contiguous(), translation.detach().float().contiguous()
+
+
+def _packed(bank, kind, pack, t, G, dims, fold=None, params=(), may_refuse=False):
+    """The bank's packed fragments of one kind, allocated and packed by the entry point `pack` on `t`'s stream the first time a
+    weight version asks for them -- and, for a kind that carries `fold(*params)` = (scale, shift), again when (address, version) of
+    the parameters change.  `may_refuse`: None, and nothing cached, when the pack answers FINC_ERR_UNSUPPORTED."""
+    key = version_key(*params) if fold is not None else None
+    hit = bank.packed.get(kind)
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    B, Cq, H, W, KH, KW = dims
+    affine = ()
+    if fold is not None:
+        scale, shift = fold(*params)
+        if scale.numel() != G * Cq or shift.numel() != G * Cq:
+            raise ValueError("affine parameters must have one entry per channel")
+        affine = (scale.data_ptr(), shift.data_ptr())
+    packed = torch.empty(_lib.lib().finc_workspace_bytes(G, Cq, KH, KW), dtype=torch.uint8, device=t.device)
+    if _call(pack, t.device, bank.w_canon.data_ptr(), *affine, packed.data_ptr(), G, Cq, KH, KW, _stream_ptr(t), may_refuse=may_refuse):
+        return None
+    bank.packed[kind] = (key, packed)
+    return packed
+
+
+def _launch_packed(name, t, packed, out, G, dims, orient, may_refuse=False):
+    """One launch on packed fragments: finc_forward_packed_f32, finc_inverse_packed_f32 or finc_inverse_packed_premultiplied_f32."""
+    B, Cq, H, W, KH, KW = dims
+    return _call(name, t.device, t.data_ptr(), packed.data_ptr(), out.data_ptr(), B, G, Cq, H, W, KH, KW, orient, _stream_ptr(t),
+                 may_refuse=may_refuse)
+
+
+def _has_mfma(query, t, dims):
+    """Does `query` (finc_forward_algo_for / finc_inverse_algo_for) name an MFMA instantiation for these (non-empty) activations?"""
+    return t.numel() != 0 and getattr(_lib.lib(), query)(*dims[1:]) == _lib.ALGO["mfma"]
+
+
+def _aligned16(t, out):
+    """The packed inverse streams 16-byte pieces (a view into a larger allocation may be only 4-byte aligned; INTEGRATION.md: such
+    calls fall back)."""
+    return not (t.data_ptr() | (out.data_ptr() if out is not None else 0)) & 15
 
 
 class PackedWeights:
@@ -556,22 +601,16 @@ class PackedWeights:
     def _get(self, weights, G, orient, validate=True):
         """`validate=False`: the training path -- the gradient mask keeps the corner tap unit triangular (layers/conv.py:98-99,
         applied inside the HIP backward), and the check is a device->host synchronisation per layer and step."""
-        bank = self._bank(weights[0].device)
+        device = weights[0].device
+        bank = self._bank(device)
         # The entry is keyed on (address, version counter) of every source tensor AND holds their storages alive: a weight
         # rebound through `.data` to a fresh tensor keeps its version counter, and the address of a freed tensor is the first
         # one the allocator hands out again -- with the old storage still referenced here the new one cannot land on it.
         key = version_key(*weights) + (orient,)
         if key != bank.key:
             ws = torch.cat([w.detach() for w in weights], dim=0).contiguous() if len(weights) > 1 else weights[0].detach().contiguous()
-            bank.w_canon = canonicalize(ws, G, orient)
-            bank.validated = False
-            bank.packed_inv = None
-            bank.packed_fwd = None
-            bank.packed_aff = None
-            bank.packed_faff = None
-            bank.linv = None
-            bank.key = key
-            bank.keep = tuple(w.untyped_storage() for w in weights)
+            # (a fresh entry: not validated, no packed fragments of any kind, no Linv)
+            bank = self._banks[device] = _DeviceBank(key, tuple(w.untyped_storage() for w in weights), canonicalize(ws, G, orient))
         # An entry the training path created (validate=False) is NOT validated: the first inference call on the same weight
         # version runs the check, so an optimiser effect outside the in-kernel gradient mask (weight decay on the diagonal,
         # a manual edit followed by a forward under grad) cannot reach the inverse unnoticed.
@@ -580,85 +619,51 @@ class PackedWeights:
             bank.validated = True
         return bank
 
+    def _enter(self, t, weights, G, orient, validate=True):
+        """What every launch starts with: the device's entry for this weight version, and (B, Cq, H, W, KH, KW) of activations `t`."""
+        bank = self._get(weights, G, orient, validate)
+        _require_device(t, "input")
+        return bank, _dims(t, bank.w_canon, G)
+
     def forward(self, x, weights, G, orient, out=None, validate=True):
         """Forward on the cached canonical bank + cached strip-kernel fragments (also the forward of the autograd path: a
         weight version that has not changed since the last call -- evaluation under grad, several micro-batches per
         optimiser step -- costs no cat / canonicalise / pack launch)."""
-        bank = self._get(weights, G, orient, validate)
-        w_canon = bank.w_canon
-        _require_device(x, "input")
-        B, Cq, H, W, KH, KW = _dims(x, w_canon, G)
-        L = _lib.lib()
-        if x.numel() == 0 or L.finc_forward_algo_for(Cq, H, W, KH, KW) != _lib.ALGO["mfma"]:
-            return finc_forward(x, w_canon, G, orient, out=out)
-        if bank.packed_fwd is None:
-            bank.packed_fwd = torch.empty(L.finc_workspace_bytes(G, Cq, KH, KW), dtype=torch.uint8, device=x.device)
-            _call("finc_pack_forward_weights_f32", x.device, w_canon.data_ptr(), bank.packed_fwd.data_ptr(), G, Cq, KH, KW, _stream_ptr(x))
+        bank, dims = self._enter(x, weights, G, orient, validate)
+        if not _has_mfma("finc_forward_algo_for", x, dims):
+            return finc_forward(x, bank.w_canon, G, orient, out=out)
+        packed = _packed(bank, "fwd", "finc_pack_forward_weights_f32", x, G, dims)
         if out is None:
             out = torch.empty_like(x)
-        _call("finc_forward_packed_f32", x.device, x.data_ptr(), bank.packed_fwd.data_ptr(), out.data_ptr(), B, G, Cq, H, W, KH, KW,
-              orient, _stream_ptr(x))
+        _launch_packed("finc_forward_packed_f32", x, packed, out, G, dims, orient)
         return out
 
     def forward_affine(self, x, weights, G, orient, log_scale, translation, out=None):
         """(forward(x) - translation) * exp(-log_scale) in ONE launch: the per-channel affine layer BEHIND the unit in the
         model (ActNorm.forward, layers/actnorm.py:39-46) folded into the forward bank -- filter rows scaled, accumulators
         started from the shift.  Returns None when the shape has no MFMA strip kernel (the caller runs the two layers)."""
-        bank = self._get(weights, G, orient)
-        w_canon = bank.w_canon
-        _require_device(x, "input")
-        B, Cq, H, W, KH, KW = _dims(x, w_canon, G)
-        L = _lib.lib()
-        if x.numel() == 0 or L.finc_forward_algo_for(Cq, H, W, KH, KW) != _lib.ALGO["mfma"]:
+        bank, dims = self._enter(x, weights, G, orient)
+        if not _has_mfma("finc_forward_algo_for", x, dims):
             return None
-        key = version_key(log_scale, translation)
-        if bank.packed_faff is None or bank.faff_key != key:
-            scale = torch.exp(-log_scale.detach().float()).contiguous()
-            shift = (-translation.detach().float() * scale).contiguous()
-            if scale.numel() != G * Cq:
-                raise ValueError("affine parameters must have one entry per channel")
-            bank.packed_faff = torch.empty(L.finc_workspace_bytes(G, Cq, KH, KW), dtype=torch.uint8, device=x.device)
-            _call("finc_pack_forward_weights_affine_f32", x.device, w_canon.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                  bank.packed_faff.data_ptr(), G, Cq, KH, KW, _stream_ptr(x))
-            bank.faff_key = key
+        packed = _packed(bank, "fwd_affine", "finc_pack_forward_weights_affine_f32", x, G, dims, _fold_forward, (log_scale, translation))
         if out is None:
             out = torch.empty_like(x)
-        _call("finc_forward_packed_f32", x.device, x.data_ptr(), bank.packed_faff.data_ptr(), out.data_ptr(), B, G, Cq, H, W, KH, KW,
-              orient, _stream_ptr(x))
+        _launch_packed("finc_forward_packed_f32", x, packed, out, G, dims, orient)
         return out
 
-    @staticmethod
-    def _packed_path_ok(L, t, out, Cq, H, W, KH, KW):
-        """The packed launch streams 16-byte pieces: it needs an MFMA instantiation AND 16-byte aligned activations
-        (a view into a larger allocation may be only 4-byte aligned; INTEGRATION.md: such calls fall back)."""
-        if t.numel() == 0 or L.finc_inverse_algo_for(Cq, H, W, KH, KW) != _lib.ALGO["mfma"]:
-            return False
-        ptrs = t.data_ptr() | (out.data_ptr() if out is not None else 0)
-        return (ptrs & 15) == 0
-
-    @staticmethod
-    def _packed_inverse(bank, t, G, Cq, KH, KW):
-        """The bank's packed inverse fragments, packed on `t`'s stream the first time a weight version asks for them."""
-        if bank.packed_inv is None:
-            bank.packed_inv = torch.empty(_lib.lib().finc_workspace_bytes(G, Cq, KH, KW), dtype=torch.uint8, device=t.device)
-            _call("finc_pack_inverse_weights_f32", t.device, bank.w_canon.data_ptr(), bank.packed_inv.data_ptr(), G, Cq, KH, KW,
-                  _stream_ptr(t))
-        return bank.packed_inv
+    def _inverse_packed(self, name, t, bank, out, G, dims, orient):
+        """`name` (a packed inverse launch) on the plain inverse fragments."""
+        _launch_packed(name, t, _packed(bank, "inv", "finc_pack_inverse_weights_f32", t, G, dims), out, G, dims, orient)
+        return out
 
     def inverse(self, z, weights, G, orient, out=None):
-        bank = self._get(weights, G, orient)
-        w_canon = bank.w_canon
-        _require_device(z, "input")
-        B, Cq, H, W, KH, KW = _dims(z, w_canon, G)
-        L = _lib.lib()
+        bank, dims = self._enter(z, weights, G, orient)
         if out is None and z.numel():
             out = torch.empty_like(z)
-        if not self._packed_path_ok(L, z, out, Cq, H, W, KH, KW):
-            return finc_inverse(z, w_canon, G, orient, out=out)
-        packed = self._packed_inverse(bank, z, G, Cq, KH, KW)
-        _call("finc_inverse_packed_f32", z.device, z.data_ptr(), packed.data_ptr(), out.data_ptr(), B, G, Cq, H, W, KH, KW, orient,
-              _stream_ptr(z))
-        return out
+        # the packed launch needs an MFMA instantiation AND 16-byte aligned activations
+        if not (_has_mfma("finc_inverse_algo_for", z, dims) and _aligned16(z, out)):
+            return finc_inverse(z, bank.w_canon, G, orient, out=out)
+        return self._inverse_packed("finc_inverse_packed_f32", z, bank, out, G, dims, orient)
 
     def lead_inverse(self, weights, G, orient):
         """Linv_g = inverse of the unit lower triangular tap of the pixel itself (canonical tap [KH-1, KW-1],
@@ -685,56 +690,34 @@ class PackedWeights:
         """inverse(z) given zp = blockdiag(Linv) z (the channel mix in front of the unit applied Linv for free),
         ONE launch without the z-term's MFMAs.  None when the shape has no such kernel or the activations are not 16-byte
         aligned (the caller runs the plain chain)."""
-        bank = self._get(weights, G, orient)
-        w_canon = bank.w_canon
-        _require_device(zp, "input")
-        B, Cq, H, W, KH, KW = _dims(zp, w_canon, G)
-        L = _lib.lib()
-        if zp.numel() == 0 or not L.finc_inverse_premultiplied_supported(B, G, Cq, H, W, KH, KW):
+        bank, dims = self._enter(zp, weights, G, orient)
+        if zp.numel() == 0 or not _lib.lib().finc_inverse_premultiplied_supported(dims[0], G, *dims[1:]):
             return None
         if out is None:
             out = torch.empty_like(zp)
-        if (zp.data_ptr() | out.data_ptr()) & 15:
+        if not _aligned16(zp, out):
             return None
-        packed = self._packed_inverse(bank, zp, G, Cq, KH, KW)
-        _call("finc_inverse_packed_premultiplied_f32", zp.device, zp.data_ptr(), packed.data_ptr(), out.data_ptr(), B, G, Cq, H, W, KH,
-              KW, orient, _stream_ptr(zp))
-        return out
+        return self._inverse_packed("finc_inverse_packed_premultiplied_f32", zp, bank, out, G, dims, orient)
 
     def inverse_affine(self, y, weights, G, orient, log_scale, translation, out=None):
         """inverse(exp(log_scale) * y + translation) in ONE launch: the per-channel affine layer in front
         of the unit in the reverse chain (ActNorm.reverse, layers/actnorm.py:39-52) is folded into the packed bank.
         Returns None when the shape has no MFMA instantiation or the activations are not 16-byte aligned (the caller
         then runs the two layers one after the other)."""
-        bank = self._get(weights, G, orient)
-        w_canon = bank.w_canon
-        _require_device(y, "input")
-        B, Cq, H, W, KH, KW = _dims(y, w_canon, G)
-        L = _lib.lib()
+        bank, dims = self._enter(y, weights, G, orient)
         if out is None and y.numel():
             out = torch.empty_like(y)
-        if not self._packed_path_ok(L, y, out, Cq, H, W, KH, KW):
+        if not (_has_mfma("finc_inverse_algo_for", y, dims) and _aligned16(y, out)):
             return None
         # the shift rides on the wavefront / role-split kernels only: the big banks and the wide maps that finc_big.hip takes
         # over from the 33..64-channel banks (Cq = 50 at 256 columns) carry a scale and nothing else -> two launches there
-        if not L.finc_inverse_affine_supported(B, G, Cq, H, W, KH, KW):
+        if not _lib.lib().finc_inverse_affine_supported(dims[0], G, *dims[1:]):
             return None
-        key = version_key(log_scale, translation)
-        if bank.packed_aff is None or bank.aff_key != key:
-            scale = torch.exp(log_scale.detach().float()).contiguous()
-            shift = translation.detach().float().contiguous()
-            if scale.numel() != G * Cq or shift.numel() != G * Cq:
-                raise ValueError("affine parameters must have one entry per channel")
-            packed = torch.empty(L.finc_workspace_bytes(G, Cq, KH, KW), dtype=torch.uint8, device=y.device)
-            # FINC_ERR_UNSUPPORTED: a bank whose kernel cannot carry the shift (the big banks, finc_big.hip)
-            if _call("finc_pack_inverse_weights_affine_f32", y.device, w_canon.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                     packed.data_ptr(), G, Cq, KH, KW, _stream_ptr(y), may_refuse=True):
-                return None
-            bank.packed_aff = packed
-            bank.aff_key = key
+        # FINC_ERR_UNSUPPORTED from the pack: a bank whose kernel cannot carry the shift (the big banks, finc_big.hip)
+        packed = _packed(bank, "inv_affine", "finc_pack_inverse_weights_affine_f32", y, G, dims, _fold_inverse, (log_scale, translation),
+                         may_refuse=True)
         # (the launch itself refuses a shift-carrying bank on a map it cannot serve)
-        if _call("finc_inverse_packed_f32", y.device, y.data_ptr(), bank.packed_aff.data_ptr(), out.data_ptr(), B, G, Cq, H, W, KH, KW,
-                 orient, _stream_ptr(y), may_refuse=True):
+        if packed is None or _launch_packed("finc_inverse_packed_f32", y, packed, out, G, dims, orient, may_refuse=True):
             return None
         return out
 
