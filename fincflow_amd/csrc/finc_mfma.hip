@@ -87,6 +87,11 @@ struct Cfg {
     // exchange needs no LDS of its own: 2 x (2 waves x 20.4 KB) = 81.7 KB lets TWO 4-wave workgroups share a CU.
     // More waves: a buffer [dst][src][reg][lane].
     static constexpr bool XALIAS = NW == 2;
+    // Paired remainder tile (3x3, one wave per problem, 8 channels beside the 16-row tiles): the 4-row blocks of two taps that
+    // share a B operand -- (0,1)|(0,2) on the solved pixel, (1,0)|(1,1) on its row_shr:1 -- are stacked into ONE 16-row
+    // fragment per k-step (finc_pair_row, finc_tile.h).  NPAIR such fragments per group lie behind the bank of all groups.
+    static constexpr bool PAIR = finc_pair_bank(CQP, KH, KW) && NW == 1;
+    static constexpr int NPAIR = 2 * NKDT;
     static constexpr int XCH = (NW > 1 && !XALIAS) ? NW * NW * NKD * 64 : 0;
 };
 
@@ -363,6 +368,15 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
     constexpr int NSMALL = (NFRAG / MT) * C::NSM, NSR = (NSMALL + 3) / 4;
     float af[NFRAG];
     float afs[NSR > 0 ? NSR : 1];
+    float afp[C::PAIR ? C::NPAIR : 1];        // paired fragments: [0, NK) = (0,1)|(0,2), [NK, 2NK) = (1,0)|(1,1)
+    // block fragment s belongs to a tap whose blocks ride on a paired tile: taps 1..4 = (0,1) (0,2) (1,0) (1,1)
+    // (small_paired is asked about a register's FIRST block fragment only: the z-term's and every tap's must fill whole registers)
+    static_assert(!C::PAIR || ((NKZ * C::NSM) % 4 == 0 && (NK * C::NSM) % 4 == 0),
+                  "a packed block register must not straddle a paired and an unpaired tap");
+    auto small_paired = [](int sfr) {
+        const int tapi = sfr < NKZ * C::NSM ? 0 : 1 + (sfr - NKZ * C::NSM) / (NK * (C::NSM > 0 ? C::NSM : 1));
+        return C::PAIR && tapi >= 1 && tapi <= 4;
+    };
     if (!helper) {
         // packed index: z-term (j*MT + mt), then taps ((tap-1)*NKDT + j)*MT + mt, j global; this wave's j = wv*N + jl
         const float *pk = packed + (size_t)g * C::NPACK * 64 + lane;
@@ -381,6 +395,7 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
         const int quad = (lane & 15) >> 2;
 #pragma unroll
         for (int r = 0; r < NSR; ++r) {
+            if (small_paired(4 * r)) { afs[r] = 0.f; continue; }   // never read
             int gi = 0;
 #pragma unroll
             for (int a = 3; a >= 0; --a) {
@@ -403,7 +418,17 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
             asm volatile("" : "+a"(af[f]));
         }
 #pragma unroll
-        for (int r = 0; r < NSR; ++r) asm volatile("" : "+a"(afs[r]));
+        for (int r = 0; r < NSR; ++r) {
+            if (small_paired(4 * r)) continue;
+            asm volatile("" : "+a"(afs[r]));
+        }
+        if constexpr (C::PAIR) {
+            const float *pp = packed + finc_pair_offset(G, C::NPACK, C::NPAIR, g, 0) + lane;
+#pragma unroll
+            for (int f = 0; f < C::NPAIR; ++f) afp[f] = pp[f * 64];
+#pragma unroll
+            for (int f = 0; f < C::NPAIR; ++f) asm volatile("" : "+a"(afp[f]));
+        }
     }
     // one accumulator update with fragment f (tile mt = f % MT)
     auto mma = [&](v4f &acc_, int f, float b) {
@@ -1023,18 +1048,28 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
         float zqc[C::NSM > 0 ? C::NSM : 1], zqn[C::NSM > 0 ? C::NSM : 1];
 #pragma unroll
         for (int sb = 0; sb < (C::NSM > 0 ? C::NSM : 1); ++sb) zqc[sb] = zqn[sb] = 0.f;
+        // PAIR: the paired tile.  Registers 0,1 = channels 16*MTB + 4r + q of the pixel being solved, in operand layout as they
+        // are; registers 2,3 = what the partner taps (0,2), (1,1) add to the NEXT pixel of the lane (the carry).
+        v4f accp = (v4f){0.f, 0.f, 0.f, 0.f};
 
         auto phase_a = [&](auto pha_c, int j0, int j1) {
             constexpr int PHA = decltype(pha_c)::value;
 #pragma unroll
             for (int j = j0; j < j1; ++j)
 #pragma unroll
-                for (int mt = 0; mt < MT; ++mt) {
+                for (int mt = 0; mt < (C::PAIR ? C::MTB : MT); ++mt) {
                     if constexpr (KW > 1)
                         mma(acc[mt], FT + ((0 * KW + 1 - 1) * NK + j) * MT + mt, ROT ? Q[0][(PHA + 3) & 3][j] : R[0][1][j]);
                     if constexpr (KH > 1)
                         mma(acc[mt], FT + ((1 * KW + 0 - 1) * NK + j) * MT + mt, ROT ? Q[1][(PHA + 3) & 3][j] : R[1][0][j]);
                 }
+            if constexpr (C::PAIR) {           // the 8 remainder channels of (0,1), (1,0) and, a step ahead, of (0,2), (1,1)
+#pragma unroll
+                for (int j = j0; j < j1; ++j) {
+                    accp = __builtin_amdgcn_mfma_f32_16x16x4f32(afp[j], Q[0][(PHA + 3) & 3][j], accp, 0, 0, 0);
+                    accp = __builtin_amdgcn_mfma_f32_16x16x4f32(afp[NK + j], Q[1][(PHA + 3) & 3][j], accp, 0, 0, 0);
+                }
+            }
         };
 
 #ifdef FINC_STAMP
@@ -1059,6 +1094,18 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
                 if (__builtin_expect(__builtin_amdgcn_readfirstlane(peek_b) < win, 0)) { FINC_COLD(); FINC_HLP_LATE(0); flag_wait(IC<1>{}, win); }
             }
             if constexpr (HLP && PH == 1) flag_peek(IC<2>{}, peek_b2);     // (for the check before this step's x-ring write)
+            if constexpr (C::PAIR) {
+                // The paired tile starts from the terms that are not on it -- z, (1,2) and row 2, summed on the 4-row blocks during
+                // the previous step and reduced here, off the MFMA stream's dependences -- plus the carry; the carry restarts at 0.
+                float rs[C::NSM];
+#pragma unroll
+                for (int sb = 0; sb < C::NSM; ++sb) {
+                    rs[sb] = finc_block_reduce(acc[C::MTB + sb]);
+                    if constexpr (ZPRE) rs[sb] += zqc[sb];
+                }
+                const float c0 = accp.z, c1 = accp.w;
+                accp = (v4f){c0 + rs[0], c1 + rs[1], 0.f, 0.f};
+            }
 
             // ---- RA1: z of the next position is requested; operands that do not depend on this step age
 #pragma unroll
@@ -1196,7 +1243,26 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
                     for (int j = 0; j < NKD; ++j) asm volatile("" ::"v"(xpk[j]));
                     return;
                 }
-                if constexpr (NW == 1) {
+                if constexpr (C::PAIR) {
+#pragma unroll
+                    for (int mt = 0; mt < C::MTB; ++mt) {
+                        xpk[4 * mt + 0] = acc[mt].x;
+                        xpk[4 * mt + 1] = acc[mt].y;
+                        xpk[4 * mt + 2] = acc[mt].z;
+                        xpk[4 * mt + 3] = acc[mt].w;
+                    }
+                    xpk[4 * C::MTB + 0] = accp.x;
+                    xpk[4 * C::MTB + 1] = accp.y;
+                    // a lane whose next position starts a row carries nothing into it (its (0,2) and (1,1) neighbours lie left
+                    // of the image)
+                    if (__builtin_expect(any_wrap, 0)) {
+                        FINC_COLD();
+                        const bool wrapn = p == tm;
+                        const float c0 = accp.z, c1 = accp.w;
+                        accp.z = wrapn ? 0.f : c0;
+                        accp.w = wrapn ? 0.f : c1;
+                    }
+                } else if constexpr (NW == 1) {
                     pack_d<C>(acc, xpk);
                     if constexpr (ZPRE) {
 #pragma unroll
@@ -1241,7 +1307,7 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
 #pragma unroll
                 for (int j = 0; j < NK; ++j)
 #pragma unroll
-                    for (int mt = 0; mt < MT; ++mt)
+                    for (int mt = 0; mt < ((C::PAIR && a + b == 2 && a < 2) ? C::MTB : MT); ++mt)   // ((0,2), (1,1): blocks on the paired tile)
                         mma(accn[mt], FT + ((a * KW + b - 1) * NK + j) * MT + mt, ROT ? Q[a][(PH + 9 - a - b) & 3][j] : R[a][b][j]);
                 if constexpr (CI == 0) {
                     if constexpr (HLP && PH == 1) {    // the helper must have read what this write replaces (peeked in step 0)
@@ -1384,7 +1450,7 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
 // -----------------------------------------------------------------------------------------------
 __global__ void pack_kernel(const float *__restrict__ wc, const float *__restrict__ scale,
                             const float *__restrict__ shift, float *__restrict__ packed, int Cq, int KH, int KW, int MT,
-                            int NKZ, int NKD, int MTB, int nfrag)
+                            int NKZ, int NKD, int MTB, int nfrag, int npair)
 {
     extern __shared__ __attribute__((aligned(16))) double sm[]; // Linv [Cq][Cq]
     const int g = blockIdx.x;
@@ -1427,6 +1493,19 @@ __global__ void pack_kernel(const float *__restrict__ wc, const float *__restric
             }
         }
         packed[((size_t)g * npack + f) * 64 + lane] = (float)v;
+    }
+    // paired remainder fragments (finc_pair_row), behind the bank of all groups: pair 0 = taps (0,1)|(0,2), pair 1 = (1,0)|(1,1)
+    for (int e = threadIdx.x; e < npair * 64; e += blockDim.x) {
+        const int lane = e & 63, f = e >> 6;
+        int row, j, q, a, b;
+        finc_pair_elem(MTB, NKD, f, lane, &row, &j, &q, &a, &b);
+        const int col = chan_d(MTB, j, q);
+        double v = 0.0;
+        if (row < Cq && col < Cq) {
+            const int widx = (KH - 1 - a) * KW + (KW - 1 - b);
+            for (int k = 0; k <= row; ++k) v -= Linv[row * Cq + k] * (double)wg[((size_t)k * Cq + col) * KK + widx];
+        }
+        packed[finc_pair_offset(gridDim.x, npack, npair, g, f) + lane] = (float)v;
     }
     for (int e = threadIdx.x; e < 8 * MT * 64; e += blockDim.x) {
         const int lane = e & 63, f = e >> 6;           // f < 4*MT: bias register r of tile mt; then the zero block
@@ -1472,6 +1551,10 @@ constexpr Inst make_inst()
     // AGPR budget next to the pinned fragments: loads paired park 16 registers per k-step of z
     constexpr bool one = NW == 1 && NPW == 1;
     constexpr int pinned = (C::NFRAG / C::MT) * C::MTB - zskip + ((C::NFRAG / C::MT) * C::NSM + 3) / 4;
+    // (counts the block fragments of ALL taps four to a register.  With the paired tile the four paired taps' packed registers,
+    // 4 * NK * NSM / 4 of them, are never loaded and NPAIR paired fragments are pinned instead: the same number, or `pinned`,
+    // `mode` and `hlp_fits` below would have to count them apart)
+    static_assert(!C::PAIR || C::NPAIR == C::NK * C::NSM, "paired fragments must replace as many packed block registers");
     constexpr int mode = !one ? 0 : (pinned + 8 * C::NKZ + 8 * C::NKD <= 256) ? 3 : (pinned + 8 * C::NKD <= 256) ? 1 : 0;
     wave_fn f64 = nullptr, fhl = nullptr, fzp = nullptr;
     if constexpr (mode != 0) f64 = finc_wave_kernel<CQP, KH, KW, true, NW, NPW, mode>;
@@ -1653,7 +1736,16 @@ static const Inst *borrowed_inst(int Cq, int KH, int KW)
             if (k.cqp == b && k.kh == KH && k.kw == KW && k.nw == 2 && k.npw == 2) return &k;
     return nullptr;
 }
-static size_t bank_bytes(const Inst *i, int G) { return i ? (size_t)(i->nfrag + 8 * i->mt) * 64 * sizeof(float) * (size_t)G : 0; }
+// paired fragments per group behind a bank (Cfg::NPAIR): only where a one-wave row reads them (Cfg::PAIR), so a bank with
+// K-split rows alone -- <40,3,3> -- keeps the layout and the size it had
+static int pair_frags(const Inst *i)
+{
+    if (!finc_pair_bank(i->cqp, i->kh, i->kw)) return 0;
+    for (const Inst &k : g_insts)
+        if (k.cqp == i->cqp && k.kh == i->kh && k.kw == i->kw && k.nw == 1) return 2 * i->nkd;
+    return 0;
+}
+static size_t bank_bytes(const Inst *i, int G) { return i ? (size_t)(i->nfrag + 8 * i->mt + pair_frags(i)) * 64 * sizeof(float) * (size_t)G : 0; }
 static size_t wave_bank_bytes(int G, int Cq, int KH, int KW)
 {
     return bank_bytes(bank_inst(Cq, KH, KW), G) + bank_bytes(borrowed_inst(Cq, KH, KW), G);
@@ -1841,12 +1933,12 @@ int finc_mfma_pack(const float *wc, const float *scale, const float *shift, void
     const Inst *i = bank_inst(Cq, KH, KW);
     if (!i) return FINC_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(pack_kernel, dim3(G), dim3(256), sizeof(double) * Cq * Cq, st, wc, scale, shift, (float *)packed, Cq,
-                       KH, KW, i->mt, i->nkz, i->nkd, i->mtb, i->nfrag);
+                       KH, KW, i->mt, i->nkz, i->nkd, i->mtb, i->nfrag, pair_frags(i));
     FINC_CHECK_LAUNCH();
     if (const Inst *k = borrowed_inst(Cq, KH, KW)) {      // the borrowed two-wave bank, same fold, behind the bank's own
         float *behind = (float *)((char *)packed + bank_bytes(i, G));
         hipLaunchKernelGGL(pack_kernel, dim3(G), dim3(256), sizeof(double) * Cq * Cq, st, wc, scale, shift, behind, Cq, KH, KW, k->mt,
-                           k->nkz, k->nkd, k->mtb, k->nfrag);
+                           k->nkz, k->nkd, k->mtb, k->nfrag, pair_frags(k));
         FINC_CHECK_LAUNCH();
     }
     // (a folded shift is the one thing finc_big.hip does not carry: such a bank has no wide-map form -- the launch refuses

@@ -6,6 +6,7 @@
 // pixel p), so the rest of a group (Cq = 24: 8 channels) costs 2 x 2 passes per k-step instead of 8 for a second,
 // half-empty 16-row tile; neither M nor K carries padding.  Layouts pinned on hardware by scripts/micro/mfma4x4.hip.
 #pragma once
+#include <stddef.h>
 
 typedef float finc_v4f __attribute__((ext_vector_type(4)));
 typedef unsigned finc_v2u __attribute__((ext_vector_type(2)));
@@ -68,4 +69,35 @@ __host__ __device__ constexpr bool finc_zterm_is_zero(int MTB, int j, int mt)
 __host__ __device__ inline int finc_tile_row(int MTB, int mt, int i)
 {
     return mt < MTB ? 16 * mt + i : 16 * MTB + 4 * (mt - MTB) + (i & 3);
+}
+
+// Paired remainder tile (the inverse's one-wave 3x3 kernels, finc_mfma.hip).  A bank with 8 channels beside its 16-row tiles
+// stacks the 4-row blocks of two taps that read the SAME operand into one 16-row fragment: row i = 4*qq + r of the fragment is
+//   r = 0, 1: channel 16*MTB + 4r + qq of the pair's first tap ((0,1) resp. (1,0)) -- the pixel being solved;
+//   r = 2, 3: channel 16*MTB + 4(r-2) + qq of its partner ((0,2) resp. (1,1)) -- the lane's next pixel.
+// So D register r < 2 of lane row qq is channel 16*MTB + 4r + qq: what chan_d gives k-slot qq of operand register 4*MTB + r.
+__host__ __device__ constexpr bool finc_pair_bank(int cqp, int KH, int KW) { return KH == 3 && KW == 3 && cqp > 16 && cqp % 16 == 8; }
+__host__ __device__ inline int finc_pair_row(int MTB, int i, int *partner)
+{
+    const int qq = i >> 2, r = i & 3;
+    *partner = r >> 1;
+    return 16 * MTB + 4 * (r & 1) + qq;
+}
+// Element `lane` of paired fragment f (0 .. 2*NKD-1) of a group, as the packer writes it and the kernel reads it: pair f / NKD
+// (0: taps (0,1)|(0,2), 1: (1,0)|(1,1)), k-step j = f % NKD and k-slot q = lane / 16 of the column (its channel is chan_d(MTB, j, q)),
+// row channel and tap (a, b) by finc_pair_row.  The one statement of the map: pack_kernel calls it, and so does the host test.
+__host__ __device__ inline void finc_pair_elem(int MTB, int NKD, int f, int lane, int *row, int *j, int *q, int *a, int *b)
+{
+    int partner;
+    const int pr = f / NKD;
+    *row = finc_pair_row(MTB, lane & 15, &partner);
+    *j = f % NKD;
+    *q = lane >> 4;
+    *a = pr == 0 ? 0 : 1;
+    *b = (pr == 0 ? 1 : 0) + partner;
+}
+// float offset of that fragment in the packed buffer: the paired fragments of all groups lie behind the G banks of npack fragments
+__host__ __device__ inline size_t finc_pair_offset(int G, int npack, int npair, int g, int f)
+{
+    return ((size_t)G * npack + (size_t)g * npair + f) * 64;
 }
