@@ -214,3 +214,109 @@ def fuzz_case(rng, case):
     orient = ORIENT_FASTFLOW if G == 4 else int(rng.integers(0, 4))
     std = (0.05 if K < 5 else 0.02) * min(1.0, (24.0 / Cq) ** 0.5)   # keep the operator norm of the bank roughly constant
     return dict(case=case, B=B, G=G, Cq=Cq, H=H, W=W, K=K, orient=orient, std=std)
+
+
+# ---------------------------------------------------------------------------
+# guard bands and problem isolation (tests/test_gpu_bounds.py on the GPU, tests/test_bounds_host.py for the helpers themselves)
+# ---------------------------------------------------------------------------
+GUARD_BITS = {4: 0x7FC0BEEF, 8: 0x7FF80000_00C0BEEF}      # one quiet NaN per element size, recognisable in a dump
+
+
+def _as_ints(t):
+    import torch
+    assert t.dtype in (torch.float32, torch.float64), t.dtype
+    return t.view(torch.int32 if t.element_size() == 4 else torch.int64)
+
+
+def guard_elements(t):
+    """Elements of ONE guard of `t`: a 16-channel padded tile of the map for activations (the largest over-reach by one tile), 4096
+    for everything else; a multiple of 128 elements (512 bytes), so the payload keeps the alignment class of a fresh allocation."""
+    n = max(4096, 16 * t.shape[2] * t.shape[3]) if t.dim() == 4 else 4096
+    return (n + 127) // 128 * 128
+
+
+def nan_filled(shape, dtype, dev):
+    """A fresh tensor whose every element is the guards' NaN pattern (outputs and workspaces: whatever is left of it was not written)."""
+    import torch
+    out = torch.empty(shape, dtype=dtype, device=dev)
+    _as_ints(out).fill_(GUARD_BITS[out.element_size()])
+    return out
+
+
+def guarded(t, dev, lead_floats=0):
+    """(view, buffer): a contiguous view holding `t`'s values inside one larger buffer laid out [front guard | payload | back guard],
+    both guards filled with GUARD_BITS.  `lead_floats` = 1 shifts the payload by one element (4-byte aligned, not 16: the dword
+    forms, to be compared with the plain call on `offset_view`)."""
+    g, n = guard_elements(t), t.numel()
+    buf = nan_filled((2 * g + n + lead_floats,), t.dtype, dev)
+    view = buf[g + lead_floats:g + lead_floats + n].view(t.shape)
+    view.copy_(t)
+    assert view.is_contiguous() and (view.data_ptr() - buf.data_ptr()) % 512 == lead_floats * t.element_size()
+    return view, buf
+
+
+def _guard_spans(buffer, view):
+    off = (view.data_ptr() - buffer.data_ptr()) // buffer.element_size()
+    assert 0 <= off and off + view.numel() <= buffer.numel() and buffer.dtype == view.dtype
+    ints = _as_ints(buffer)
+    return ints[:off], ints[off + view.numel():]
+
+
+def guards_intact(buffer, view):
+    """Do both guards around `view` still hold the fill pattern, bit for bit?"""
+    bits = GUARD_BITS[buffer.element_size()]
+    return all(bool((span == bits).all()) for span in _guard_spans(buffer, view))
+
+
+def broken_guards(buffer, view):
+    """Which guards of `buffer` were written: a list out of "front", "back" (what a failing test prints)."""
+    bits = GUARD_BITS[buffer.element_size()]
+    return [name for name, span in zip(("front", "back"), _guard_spans(buffer, view)) if not bool((span == bits).all())]
+
+
+def poison(t, index, value=float("nan")):
+    """A clone of `t` with t[index] set to NaN."""
+    c = t.clone()
+    c[index] = value
+    return c
+
+
+def poison_inf(t, index):
+    return poison(t, index, float("inf"))
+
+
+def same_bits(a, b):
+    import torch
+    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(_as_ints(a.contiguous()), _as_ints(b.contiguous()))
+
+
+def isolation_check(clean, dirty, reach):
+    """The isolation comparison: `reach` is a boolean mask of the output elements the poison can reach by the operation's
+    definition.  Returns (leaked, reached): the number of elements OUTSIDE the mask whose bits differ from the clean run, and whether
+    the part inside holds a non-finite value at all (the poison was read: the comparison is not vacuous)."""
+    import torch
+    reach = reach.expand_as(clean) if reach.shape != clean.shape else reach
+    leaked = int(((_as_ints(clean.contiguous()) != _as_ints(dirty.contiguous())) & ~reach).sum())
+    reached = bool((~torch.isfinite(dirty[reach])).any())
+    return leaked, reached
+
+
+# float64 formulas of the per-pixel layers (layers/coupling.py:79-101, layers/actnorm.py:34, :51, :57-65): the references of
+# tests/test_gpu_bounds.py, and what tests/test_bounds_host.py shows to be isolated themselves
+def coupling_ref(x, raw, a, b, direction):
+    """(y, logdet) of the forward direction, (y, None) of the reverse."""
+    import torch
+    half = x.shape[1] // 2
+    h = a.view(1, -1, 1, 1) * raw + b.view(1, -1, 1, 1)
+    s = 2.0 * torch.tanh(h[:, ::2] / 2.0)
+    sh = h[:, 1::2]
+    if direction > 0:
+        return torch.cat([x[:, :half], x[:, half:] * torch.exp(s) + sh], 1), s.flatten(1).sum(-1)
+    return torch.cat([x[:, :half], (x[:, half:] - sh) * torch.exp(-s)], 1), None
+
+
+def actnorm_ref(x, ls, tr, direction):
+    import torch
+    if direction > 0:
+        return (x - tr.view(1, -1, 1, 1)) * torch.exp(-ls.view(1, -1, 1, 1)), (-ls.sum() * x.shape[2] * x.shape[3]).expand(x.shape[0])
+    return x * torch.exp(ls.view(1, -1, 1, 1)) + tr.view(1, -1, 1, 1), None
