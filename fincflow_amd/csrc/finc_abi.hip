@@ -189,7 +189,7 @@ static int canonicalize(const T *w_stored, T *w_canon, int G, int Cq, int KH, in
 
 extern "C" {
 
-int finc_version(void) { return 105; }
+int finc_version(void) { return 106; }
 
 unsigned finc_build_flags(void)
 {

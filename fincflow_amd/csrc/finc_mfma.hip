@@ -91,7 +91,10 @@ struct Cfg {
     // share a B operand -- (0,1)|(0,2) on the solved pixel, (1,0)|(1,1) on its row_shr:1 -- are stacked into ONE 16-row
     // fragment per k-step (finc_pair_row, finc_tile.h).  NPAIR such fragments per group lie behind the bank of all groups.
     static constexpr bool PAIR = finc_pair_bank(CQP, KH, KW) && NW == 1;
-    static constexpr int NPAIR = 2 * NKDT;
+    static constexpr int NPAIR = 3 * NKDT;
+    // Stage 2: a third pair, (2,0)|(2,1) on row_shr:2 of the solved pixel, OPENS the next step's paired tile during phase B.  The
+    // bank always carries its NKDT fragments (behind the other two pairs'); a form reads them only where its registers allow it.
+    static constexpr int NPAIR1 = 2 * NKDT;
     static constexpr int XCH = (NW > 1 && !XALIAS) ? NW * NW * NKD * 64 : 0;
 };
 
@@ -103,6 +106,15 @@ __host__ __device__ inline int chan_d(int MTB, int j, int q)
     if (j < 4 * MTB) return 16 * (j >> 2) + 4 * q + (j & 3);
     return 16 * MTB + 4 * (j - 4 * MTB) + q;
 }
+
+// Stage 2 of the paired tile keeps a second tile alive beside the first (+4 VGPRs in the compute role) and runs in the helper-wave
+// forms only.  Their compute role is held to 128 architectural VGPRs beside the helper, and how many it needs is the compiler's
+// answer, not a quantity this file can compute: hlp_fits (make_inst) budgets the helper role and the pinned fragments only.  So the
+// register budget of stage 2 rests on the build's metadata -- 116 VGPRs + 120 AGPRs, no spill, no scratch on the 24-channel bank
+// (scripts/kernel_regs.py) -- and tests/test_code_objects.py and tests/test_wave_kernel_registers.py hold every build to it: no finc_wave_kernel may spill or use
+// scratch, and a helper-wave form may not exceed 128 VGPRs or 128 AGPRs (a spill there is a wrong result, not a slow one: hlp_fits).
+template <class C>
+__host__ __device__ constexpr bool finc_pair2_form(bool hlp) { return C::PAIR && hlp; }
 
 template <int N>
 __device__ inline float row_shr(float old, float src)
@@ -368,14 +380,16 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
     constexpr int NSMALL = (NFRAG / MT) * C::NSM, NSR = (NSMALL + 3) / 4;
     float af[NFRAG];
     float afs[NSR > 0 ? NSR : 1];
-    float afp[C::PAIR ? C::NPAIR : 1];        // paired fragments: [0, NK) = (0,1)|(0,2), [NK, 2NK) = (1,0)|(1,1)
-    // block fragment s belongs to a tap whose blocks ride on a paired tile: taps 1..4 = (0,1) (0,2) (1,0) (1,1)
+    constexpr bool PAIR2 = finc_pair2_form<C>(HLP);   // stage 2 of the paired tile runs in this form
+    constexpr int NPAIRF = PAIR2 ? C::NPAIR : C::NPAIR1;
+    float afp[C::PAIR ? NPAIRF : 1];          // paired fragments: [0, NK) = (0,1)|(0,2), [NK, 2NK) = (1,0)|(1,1), [2NK, 3NK) = (2,0)|(2,1)
+    // block fragment s belongs to a tap whose blocks ride on a paired tile: taps 1..4 = (0,1) (0,2) (1,0) (1,1); stage 2: 6, 7 = (2,0) (2,1)
     // (small_paired is asked about a register's FIRST block fragment only: the z-term's and every tap's must fill whole registers)
     static_assert(!C::PAIR || ((NKZ * C::NSM) % 4 == 0 && (NK * C::NSM) % 4 == 0),
                   "a packed block register must not straddle a paired and an unpaired tap");
     auto small_paired = [](int sfr) {
         const int tapi = sfr < NKZ * C::NSM ? 0 : 1 + (sfr - NKZ * C::NSM) / (NK * (C::NSM > 0 ? C::NSM : 1));
-        return C::PAIR && tapi >= 1 && tapi <= 4;
+        return C::PAIR && ((tapi >= 1 && tapi <= 4) || (PAIR2 && (tapi == 6 || tapi == 7)));
     };
     if (!helper) {
         // packed index: z-term (j*MT + mt), then taps ((tap-1)*NKDT + j)*MT + mt, j global; this wave's j = wv*N + jl
@@ -425,9 +439,9 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
         if constexpr (C::PAIR) {
             const float *pp = packed + finc_pair_offset(G, C::NPACK, C::NPAIR, g, 0) + lane;
 #pragma unroll
-            for (int f = 0; f < C::NPAIR; ++f) afp[f] = pp[f * 64];
+            for (int f = 0; f < NPAIRF; ++f) afp[f] = pp[f * 64];
 #pragma unroll
-            for (int f = 0; f < C::NPAIR; ++f) asm volatile("" : "+a"(afp[f]));
+            for (int f = 0; f < NPAIRF; ++f) asm volatile("" : "+a"(afp[f]));
         }
     }
     // one accumulator update with fragment f (tile mt = f % MT)
@@ -1051,6 +1065,10 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
         // PAIR: the paired tile.  Registers 0,1 = channels 16*MTB + 4r + q of the pixel being solved, in operand layout as they
         // are; registers 2,3 = what the partner taps (0,2), (1,1) add to the NEXT pixel of the lane (the carry).
         v4f accp = (v4f){0.f, 0.f, 0.f, 0.f};
+        // PAIR2: the tile of the NEXT step, opened in phase B by (2,0)|(2,1) -- registers 0,1 = what (2,0) adds to the next pixel,
+        // registers 2,3 = what (2,1) adds to the one after it -- and the carry of the current one (registers 2,3 behind phase A)
+        v4f accq = (v4f){0.f, 0.f, 0.f, 0.f};
+        float cy[2] = {0.f, 0.f};
 
         auto phase_a = [&](auto pha_c, int j0, int j1) {
             constexpr int PHA = decltype(pha_c)::value;
@@ -1084,7 +1102,19 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
             FINC_STAMP_AT(9);                           // segment 9: loop latch (between two steps)
             // the masks cost VALU issue that f32 MFMAs do not hide: apply them only on the steps where a lane
             // wraps (P of every W steps) / has not started yet (the first P steps); both tests are scalar
-            const bool any_wrap = tm >= 0 && tm < P;
+            // PAIR: the wrap test stays a scalar integer (bit 31 = "0 <= tm < P") that every use tests for itself -- as a bool it
+            // crosses basic blocks through a VGPR (v_cndmask 0,1 + v_cmp_ne per step)
+            std::conditional_t<C::PAIR, int, bool> wrap_state;   // PAIR: an integer, the sign bit answers; otherwise the bool
+            if constexpr (C::PAIR) wrap_state = (tm - P) & ~tm;
+            else wrap_state = tm >= 0 && tm < P;
+            auto any_wrap = [&]() -> bool {
+                if constexpr (C::PAIR) {
+                    asm volatile("" : "+s"(wrap_state));
+                    return wrap_state < 0;
+                } else {
+                    return wrap_state;
+                }
+            };
             const bool any_idle = tp1 < P - 1;
             float zraw[NKZ], zv[NKZ], xpk[NKD];
             float xown[NKD];                          // K-split: this wave's own share of the registers it finalises
@@ -1103,8 +1133,14 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
                     rs[sb] = finc_block_reduce(acc[C::MTB + sb]);
                     if constexpr (ZPRE) rs[sb] += zqc[sb];
                 }
-                const float c0 = accp.z, c1 = accp.w;
-                accp = (v4f){c0 + rs[0], c1 + rs[1], 0.f, 0.f};
+                if constexpr (PAIR2) {
+                    accp = accq;
+                    accp.x += cy[0] + rs[0];
+                    accp.y += cy[1] + rs[1];
+                } else {
+                    const float c0 = accp.z, c1 = accp.w;
+                    accp = (v4f){c0 + rs[0], c1 + rs[1], 0.f, 0.f};
+                }
             }
 
             // ---- RA1: z of the next position is requested; operands that do not depend on this step age
@@ -1125,7 +1161,7 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
                         for (int j = 0; j < NK; ++j) R[a][0][j] = DL[a][a - 2][j];
                     }
                 }
-                if (__builtin_expect(any_wrap, 0)) {
+                if (__builtin_expect(any_wrap(), 0)) {
                     FINC_COLD();
                     const bool wrapn = p == tm;
 #pragma unroll
@@ -1158,7 +1194,7 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
             if constexpr (ROT) {
                 // the operands phase A just read unmasked (b = 0 / 1 of this step) become b >= 1 taps of a step that
                 // starts a row: zero them, for the wrapping lanes only, after phase A has issued and before phase B
-                if (__builtin_expect(any_wrap, 0)) {
+                if (__builtin_expect(any_wrap(), 0)) {
                     FINC_COLD();
                     const bool wrapn = p == tm;
 #pragma unroll
@@ -1255,12 +1291,21 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
                     xpk[4 * C::MTB + 1] = accp.y;
                     // a lane whose next position starts a row carries nothing into it (its (0,2) and (1,1) neighbours lie left
                     // of the image)
-                    if (__builtin_expect(any_wrap, 0)) {
+                    if constexpr (PAIR2) {
+                        cy[0] = accp.z;
+                        cy[1] = accp.w;
+                    }
+                    if (__builtin_expect(any_wrap(), 0)) {
                         FINC_COLD();
                         const bool wrapn = p == tm;
                         const float c0 = accp.z, c1 = accp.w;
-                        accp.z = wrapn ? 0.f : c0;
-                        accp.w = wrapn ? 0.f : c1;
+                        if constexpr (PAIR2) {
+                            cy[0] = wrapn ? 0.f : c0;
+                            cy[1] = wrapn ? 0.f : c1;
+                        } else {
+                            accp.z = wrapn ? 0.f : c0;
+                            accp.w = wrapn ? 0.f : c1;
+                        }
                     }
                 } else if constexpr (NW == 1) {
                     pack_d<C>(acc, xpk);
@@ -1286,8 +1331,11 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
                     fifo_push(xpk);
                     fifo_pop_all();
                 }
-                if constexpr (KW > 1) {                // S_0(t): tap (0,1) of the next step
-                    if (__builtin_expect(any_wrap, 0)) {
+                if constexpr (C::PAIR) {               // S_0(t) IS the accumulator set; its wrap zeroing follows the shifts (post2)
+#pragma unroll
+                    for (int j = 0; j < NK; ++j) Q[0][PH][j] = xpk[j];
+                } else if constexpr (KW > 1) {         // S_0(t): tap (0,1) of the next step
+                    if (__builtin_expect(any_wrap(), 0)) {
                         FINC_COLD();
                         const bool wrapn = p == tm;
 #pragma unroll
@@ -1298,7 +1346,19 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
                     }
                 }
             };
-            auto post2 = [&]() { if constexpr (FINC_ABLATE < 2) shift_all(xpk, ph_c); };
+            auto post2 = [&]() {
+                if constexpr (FINC_ABLATE < 2) shift_all(xpk, ph_c);
+                if constexpr (C::PAIR && FINC_ABLATE < 2) {
+                    // the x-ring write, the FIFO push and the shifts have read the pixel: now a lane whose next position starts a
+                    // row loses it as tap (0,1) -- in place, so the hot path needs no copy of the accumulators
+                    if (__builtin_expect(any_wrap(), 0)) {
+                        FINC_COLD();
+                        const bool wrapn = p == tm;
+#pragma unroll
+                        for (int j = 0; j < NK; ++j) Q[0][PH][j] = wrapn ? 0.f : Q[0][PH][j];
+                    }
+                }
+            };
 
             // ---- RB1..: one region per remaining tap, side work attached to the first three
             auto chunk = [&](auto ci_c) {
@@ -1307,8 +1367,14 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
 #pragma unroll
                 for (int j = 0; j < NK; ++j)
 #pragma unroll
-                    for (int mt = 0; mt < ((C::PAIR && a + b == 2 && a < 2) ? C::MTB : MT); ++mt)   // ((0,2), (1,1): blocks on the paired tile)
+                    for (int mt = 0; mt < ((C::PAIR && ((a + b == 2 && a < 2) || (PAIR2 && a == 2 && b < 2))) ? C::MTB : MT); ++mt)   // ((0,2), (1,1), stage 2: (2,0), (2,1): blocks on the paired tile)
                         mma(accn[mt], FT + ((a * KW + b - 1) * NK + j) * MT + mt, ROT ? Q[a][(PH + 9 - a - b) & 3][j] : R[a][b][j]);
+                if constexpr (PAIR2 && a == 2 && b == 0) {
+                    // S_2 of the previous step: (2,0) of the next pixel and (2,1) of the one after it.  C = 0 opens the tile.
+#pragma unroll
+                    for (int j = 0; j < NK; ++j)
+                        accq = __builtin_amdgcn_mfma_f32_16x16x4f32(afp[2 * NK + j], Q[2][(PH + 7) & 3][j], j == 0 ? (v4f){0.f, 0.f, 0.f, 0.f} : accq, 0, 0, 0);
+                }
                 if constexpr (CI == 0) {
                     if constexpr (HLP && PH == 1) {    // the helper must have read what this write replaces (peeked in step 0)
                         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1494,7 +1560,7 @@ __global__ void pack_kernel(const float *__restrict__ wc, const float *__restric
         }
         packed[((size_t)g * npack + f) * 64 + lane] = (float)v;
     }
-    // paired remainder fragments (finc_pair_row), behind the bank of all groups: pair 0 = taps (0,1)|(0,2), pair 1 = (1,0)|(1,1)
+    // paired remainder fragments (finc_pair_row), behind the bank of all groups: pair 0 = taps (0,1)|(0,2), pair 1 = (1,0)|(1,1), pair 2 = (2,0)|(2,1)
     for (int e = threadIdx.x; e < npair * 64; e += blockDim.x) {
         const int lane = e & 63, f = e >> 6;
         int row, j, q, a, b;
@@ -1554,7 +1620,8 @@ constexpr Inst make_inst()
     // (counts the block fragments of ALL taps four to a register.  With the paired tile the four paired taps' packed registers,
     // 4 * NK * NSM / 4 of them, are never loaded and NPAIR paired fragments are pinned instead: the same number, or `pinned`,
     // `mode` and `hlp_fits` below would have to count them apart)
-    static_assert(!C::PAIR || C::NPAIR == C::NK * C::NSM, "paired fragments must replace as many packed block registers");
+    static_assert(!C::PAIR || (C::NPAIR1 == 4 * C::NK * C::NSM / 4 && C::NPAIR == 6 * C::NK * C::NSM / 4),
+                  "paired fragments must replace as many packed block registers (stage 1: four taps, stage 2: six)");
     constexpr int mode = !one ? 0 : (pinned + 8 * C::NKZ + 8 * C::NKD <= 256) ? 3 : (pinned + 8 * C::NKD <= 256) ? 1 : 0;
     wave_fn f64 = nullptr, fhl = nullptr, fzp = nullptr;
     if constexpr (mode != 0) f64 = finc_wave_kernel<CQP, KH, KW, true, NW, NPW, mode>;
@@ -1742,7 +1809,7 @@ static int pair_frags(const Inst *i)
 {
     if (!finc_pair_bank(i->cqp, i->kh, i->kw)) return 0;
     for (const Inst &k : g_insts)
-        if (k.cqp == i->cqp && k.kh == i->kh && k.kw == i->kw && k.nw == 1) return 2 * i->nkd;
+        if (k.cqp == i->cqp && k.kh == i->kh && k.kw == i->kw && k.nw == 1) return 3 * i->nkd;
     return 0;
 }
 static size_t bank_bytes(const Inst *i, int G) { return i ? (size_t)(i->nfrag + 8 * i->mt + pair_frags(i)) * 64 * sizeof(float) * (size_t)G : 0; }

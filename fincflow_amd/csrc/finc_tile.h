@@ -93,7 +93,7 @@ __host__ __device__ inline void finc_pair_elem(int MTB, int NKD, int f, int lane
     *row = finc_pair_row(MTB, lane & 15, &partner);
     *j = f % NKD;
     *q = lane >> 4;
-    *a = pr == 0 ? 0 : 1;
+    *a = pr;                                  // pair 2 (stage 2): taps (2,0)|(2,1)
     *b = (pr == 0 ? 1 : 0) + partner;
 }
 // float offset of that fragment in the packed buffer: the paired fragments of all groups lie behind the G banks of npack fragments
