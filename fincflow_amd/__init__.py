@@ -8,7 +8,7 @@ library is missing or a tensor is not on a ROCm device.
 from . import ops  # noqa: F401
 from .layers import (CINCFlowUnit, FastFlowUnit, FlowLayer, FlowSequential, PaddedConv2d,  # noqa: F401
                      load_reference_checkpoint)
-from .ops import finc_forward, finc_inverse, inverse  # noqa: F401
+from .ops import finc_forward, finc_inverse, inverse, reverse_grad  # noqa: F401
 
 __all__ = ["FastFlowUnit", "CINCFlowUnit", "load_reference_checkpoint", "PaddedConv2d", "FlowLayer", "FlowSequential", "finc_forward", "finc_inverse", "inverse",
-           "ops"]
+           "reverse_grad", "ops"]

@@ -35,6 +35,8 @@ SYMBOLS = [
     "finc_coupling_supported_f32", "finc_coupling_workspace_bytes", "finc_coupling_f32", "finc_coupling_backward_f32",
     "finc_bias_relu_f32",
     "finc_actnorm_workspace_bytes", "finc_actnorm_f32", "finc_actnorm_backward_f32", "finc_actnorm_init_f32",
+    "finc_adjoint_weights_f32", "finc_lead_product_f32", "finc_negate_f32", "finc_inverse_backward_workspace_bytes",
+    "finc_inverse_backward_f32",
 ]
 
 #: the ABI version this binding is written against (include/finc.h: finc_version)
@@ -42,6 +44,9 @@ ABI_VERSION = 104
 #: the version that added the ActNorm entry points (finc_actnorm_f32, finc_actnorm_backward_f32, finc_actnorm_init_f32); a second,
 #: named floor behind the first so that each refusal says what the library lacks
 ACTNORM_ABI_VERSION = 105
+#: the version that added the backward through the inverse (finc_adjoint_weights_f32, finc_lead_product_f32, finc_negate_f32,
+#: finc_inverse_backward_f32)
+INVERSE_BACKWARD_ABI_VERSION = 107
 
 _lib = None
 
@@ -72,6 +77,10 @@ def lib():
     if have < ACTNORM_ABI_VERSION:
         raise FincError(f"{LIB_PATH} reports finc_version() = {have}, the ActNorm entry points (finc_actnorm_f32, "
                         f"finc_actnorm_backward_f32, finc_actnorm_init_f32) came with {ACTNORM_ABI_VERSION}: rebuild it "
+                        "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
+    if have < INVERSE_BACKWARD_ABI_VERSION:
+        raise FincError(f"{LIB_PATH} reports finc_version() = {have}, the backward through the inverse (finc_adjoint_weights_f32, "
+                        f"finc_inverse_backward_f32) came with {INVERSE_BACKWARD_ABI_VERSION}: rebuild it "
                         "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
     L.finc_build_flags.restype = u
     L.finc_clear_fault.restype = i
@@ -138,6 +147,12 @@ def lib():
     L.finc_actnorm_f32.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, vp]
     L.finc_actnorm_backward_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp]
     L.finc_actnorm_init_f32.argtypes = [vp, vp, vp, i, i, i, vp, sz, vp]
+    L.finc_adjoint_weights_f32.argtypes = [vp, vp, vp, i, i, i, i, vp]
+    L.finc_lead_product_f32.argtypes = [vp, vp, i, i, i, i, vp]
+    L.finc_negate_f32.argtypes = [vp, sz, vp]
+    L.finc_inverse_backward_workspace_bytes.restype = sz
+    L.finc_inverse_backward_workspace_bytes.argtypes = [i, i, i, i, i, i, i]
+    L.finc_inverse_backward_f32.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, u, vp, sz, vp]
     for name in SYMBOLS:
         getattr(L, name)  # AttributeError here = header and library out of sync
     _lib = L

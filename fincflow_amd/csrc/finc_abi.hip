@@ -189,7 +189,7 @@ static int canonicalize(const T *w_stored, T *w_canon, int G, int Cq, int KH, in
 
 extern "C" {
 
-int finc_version(void) { return 106; }
+int finc_version(void) { return 107; }
 
 unsigned finc_build_flags(void)
 {
@@ -774,6 +774,95 @@ int finc_backward_f32(const float *grad_z, const float *x, const float *w_canon,
     }
     if (!grad_x && !grad_w_canon) return FINC_OK;
     return finc_launch_backward_generic(grad_z, x, w_canon, grad_x, grad_w_canon, s, st);
+}
+
+// ---- backward through the inverse (finc_adjoint.h) ----
+int finc_adjoint_weights_f32(const float *w_canon, float *w_adj, float *lead_t, int G, int Cq, int KH, int KW, finc_stream_t stream)
+{
+    if (!w_canon || !w_adj || !lead_t) return FINC_ERR_NULL_POINTER;
+    if (int e = check_shape(1, G, Cq, 1, 1, KH, KW)) return e;
+    if (misaligned(w_canon, w_adj, lead_t)) return FINC_ERR_ALIGNMENT;
+    if (w_adj == w_canon || lead_t == w_canon || (const float *)lead_t == w_adj) return FINC_ERR_BAD_DIMS;
+    if (int e = finc_fault_gate(false)) return e;
+    return finc_adjoint_weights_launch(w_canon, w_adj, lead_t, G, Cq, KH, KW, (hipStream_t)stream);
+}
+
+int finc_lead_product_f32(float *v, const float *lead_t, int B, int G, int Cq, int HW, finc_stream_t stream)
+{
+    if (!v || !lead_t) return FINC_ERR_NULL_POINTER;
+    if (G <= 0 || Cq <= 0 || G > FINC_MAX_GROUPS || Cq > FINC_MAX_CQ) return FINC_ERR_BAD_DIMS;
+    if (int e = pixel_dims(B, G * Cq, HW, true)) return e;
+    if ((size_t)G * Cq * HW >= ((size_t)1 << 29)) return FINC_ERR_BAD_DIMS;      // an image's bytes index as int (finc_mix_launch)
+    if (misaligned(v, lead_t)) return FINC_ERR_ALIGNMENT;
+    if ((const float *)v == lead_t) return FINC_ERR_BAD_DIMS;
+    if (int e = finc_fault_gate(false)) return e;
+    return finc_lead_launch(v, lead_t, B, G, Cq, HW, (hipStream_t)stream);
+}
+
+int finc_negate_f32(float *p, size_t n, finc_stream_t stream)
+{
+    if (!p) return FINC_ERR_NULL_POINTER;
+    if (n == 0 || n >= ((size_t)1 << 31)) return FINC_ERR_BAD_DIMS;
+    if (misaligned(p)) return FINC_ERR_ALIGNMENT;
+    if (int e = finc_fault_gate(false)) return e;
+    return finc_negate_launch(p, n, (hipStream_t)stream);
+}
+
+// the one-call form's workspace: the adjoint bank, lead_t, one activation-sized buffer (y, when the caller skips grad_z), then what the
+// solve (finc_inverse_f32, AUTO) and the grad-weight (finc_backward_f32) take, one after the other on the same bytes.  The activation
+// parts are sized for rows padded to 8 floats whatever the width, so that the bound never shrinks when B, H or W grows.
+struct InverseBackwardWorkspace { size_t w_adj, lead_t, y, calls, total; };
+static InverseBackwardWorkspace inverse_backward_workspace(int B, int G, int Cq, int H, int W, int KH, int KW)
+{
+    InverseBackwardWorkspace ws;
+    const size_t act = align256((size_t)B * G * Cq * H * ((W + 7) / 8 * 8) * sizeof(float));
+    ws.w_adj = 0;
+    ws.lead_t = align256((size_t)G * Cq * Cq * KH * KW * sizeof(float));
+    ws.y = ws.lead_t + align256((size_t)G * Cq * G * Cq * sizeof(float));
+    ws.calls = ws.y + act;
+    const size_t inv = align256(finc_workspace_bytes(G, Cq, KH, KW)) + 2 * act;
+    // (the grad-weight plan's own bytes change form with the width: its bound over all maps of no more strips does not)
+    const size_t bwd = align256(finc_conv_packed_bytes(G, Cq, KH, KW)) + finc_gradw_workspace_bound(G, Cq, KH, KW, (long long)B * ((W + 15) / 16));
+    ws.total = ws.calls + align256(inv > bwd ? inv : bwd);
+    return ws;
+}
+
+size_t finc_inverse_backward_workspace_bytes(int B, int G, int Cq, int H, int W, int KH, int KW)
+{
+    if (B <= 0 || G <= 0 || Cq <= 0 || H <= 0 || W <= 0 || KH <= 0 || KW <= 0) return 256;
+    return inverse_backward_workspace(B, G, Cq, H, W, KH, KW).total;
+}
+
+int finc_inverse_backward_f32(const float *grad_x, const float *x, const float *w_canon, float *grad_z, float *grad_w_canon, int B, int G,
+                              int Cq, int H, int W, int KH, int KW, unsigned orient, void *workspace, size_t workspace_bytes,
+                              finc_stream_t stream)
+{
+    if (!grad_x || !w_canon || (!grad_z && !grad_w_canon) || (grad_w_canon && !x)) return FINC_ERR_NULL_POINTER;
+    if (int e = check_shape(B, G, Cq, H, W, KH, KW)) return e;
+    if ((size_t)G * Cq * H * W >= ((size_t)1 << 29)) return FINC_ERR_BAD_DIMS;   // an image's bytes index as int in the lead product
+    if (misaligned(grad_x, x, w_canon, grad_z, grad_w_canon)) return FINC_ERR_ALIGNMENT;
+    if (grad_z && (grad_z == grad_x || grad_z == x)) return FINC_ERR_BAD_DIMS;
+    const InverseBackwardWorkspace ws = inverse_backward_workspace(B, G, Cq, H, W, KH, KW);
+    // (the parts start on 256-byte boundaries of a 16-byte aligned buffer: the packed launch and the 16-byte forms stay available)
+    if (!workspace || off_boundary(15u, workspace) || workspace_bytes < ws.total) return FINC_ERR_WORKSPACE;
+    float *y = grad_z ? grad_z : (float *)((char *)workspace + ws.y);
+    // the forward's weight gradient has no kernel for this filter (finc_backward_f32 says the same): refuse before anything is launched
+    if (grad_w_canon && !finc_backward_generic_has_gradw(KH, KW) && !finc_gradw_plan(FincShape{B, G, Cq, H, W, KH, KW, orient}, finc_align(y, x)).form)
+        return FINC_ERR_UNSUPPORTED;
+    if (int e = finc_fault_gate(false)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    char *base = (char *)workspace;
+    float *w_adj = (float *)(base + ws.w_adj), *lead_t = (float *)(base + ws.lead_t);
+    void *calls = base + ws.calls;
+    const size_t calls_bytes = ws.total - ws.calls;
+    if (int e = finc_adjoint_weights_launch(w_canon, w_adj, lead_t, G, Cq, KH, KW, st)) return e;
+    // M^T reads the opposite corner: every group's orientation bits complemented
+    const unsigned adj_orient = orient ^ ((G >= 16) ? 0xFFFFFFFFu : ((1u << (2 * G)) - 1u));
+    if (int e = run(grad_x, w_adj, y, B, G, Cq, H, W, KH, KW, adj_orient, FINC_ALGO_AUTO, calls, calls_bytes, stream, false)) return e;
+    if (int e = finc_lead_launch(y, lead_t, B, G, Cq, H * W, st)) return e;
+    if (!grad_w_canon) return FINC_OK;
+    if (int e = finc_backward_f32(y, x, w_canon, nullptr, grad_w_canon, B, G, Cq, H, W, KH, KW, orient, calls, calls_bytes, stream)) return e;
+    return finc_negate_launch(grad_w_canon, (size_t)G * Cq * Cq * KH * KW, st);
 }
 
 } // extern "C"

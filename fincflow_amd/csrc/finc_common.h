@@ -95,6 +95,7 @@ int finc_launch_inverse_strict_f64(const double *z, const double *wc, double *x,
 int finc_launch_forward_generic_f64(const double *x, const double *wc, double *z, const FincShape &s, hipStream_t st);
 int finc_launch_backward_generic(const float *gz, const float *x, const float *wc, float *gx, float *gw,
                                  const FincShape &s, hipStream_t st);
+bool finc_backward_generic_has_gradw(int KH, int KW);   // false: finc_launch_backward_generic answers a grad-weight with FINC_ERR_UNSUPPORTED
 
 // ---- inverse, MFMA wavefront kernel: finc_mfma.hip ----
 // rows x Win floats -> rows x Wout floats (Wout > Win: zero fill on the right; Wout < Win: crop)
@@ -236,6 +237,8 @@ int finc_gradw_launch(const float *gz, const float *x, float *gw, void *workspac
                       hipStream_t st);
 int finc_gradw_variant(const FincShape &s);             // finc_gradw_plan(s, 16).form
 size_t finc_gradw_workspace_bytes(const FincShape &s);  // room for the plans of 16-byte and of float-aligned activations (0: none)
+// >= finc_gradw_workspace_bytes of every call on this bank with at most `units` = B * ceil(W / 16) strips; never shrinks when units grows
+size_t finc_gradw_workspace_bound(int G, int Cq, int KH, int KW, long long units);
 
 // ---- double precision on the matrix cores: finc_f64.hip (the c2 / c3 class of banks: Cq <= 24 at 3x3, <= 32 at 2x2) ----
 bool finc_f64_supported(const FincShape &s);
@@ -271,3 +274,10 @@ int finc_actnorm_launch(const float *x, const float *ls, const float *tr, float 
 int finc_actnorm_backward_launch(const float *gy, const float *gld, const float *y, const float *ls, float *gx, float *gls, float *gt,
                                  int B, int C, int HW, float *ws, hipStream_t st);
 int finc_actnorm_init_launch(const float *x, float *ls, float *tr, int B, int C, int HW, float *ws, hipStream_t st);
+// ---- backward through the unit's inverse (adjoint bank, lead product, the weight gradient's sign): finc_adjoint.h, same object ----
+// w_adj [G*Cq][Cq][KH][KW]: the canonical bank whose inverse (orientation complemented) is the adjoint solve up to the lead product;
+// lead_t [C][C]: blockdiag(Linv_g^T), row = output channel
+int finc_adjoint_weights_launch(const float *wc, float *w_adj, float *lead_t, int G, int Cq, int KH, int KW, hipStream_t st);
+// v <- blockdiag(L^-T) v in place: finc_mix_launch where the channel count has an instantiation, the grouped kernel otherwise
+int finc_lead_launch(float *v, const float *lead_t, int B, int G, int Cq, int HW, hipStream_t st);
+int finc_negate_launch(float *p, size_t n, hipStream_t st);

@@ -235,6 +235,9 @@ int finc_launch_forward_generic_f64(const double *x, const double *wc, double *z
     return launch_forward_generic<double>(x, wc, z, s, st);
 }
 
+// the direct grad-weight kernel keeps one accumulator per tap: filters beyond BW_MAX_TAPS taps have no grad-weight at all
+bool finc_backward_generic_has_gradw(int KH, int KW) { return KH * KW <= BW_MAX_TAPS; }
+
 int finc_launch_backward_generic(const float *gz, const float *x, const float *wc, float *gx, float *gw,
                                  const FincShape &s, hipStream_t st)
 {

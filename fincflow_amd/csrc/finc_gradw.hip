@@ -1489,6 +1489,27 @@ size_t finc_gradw_workspace_bytes(const FincShape &s)
     return a > u ? a : u;
 }
 
+// An upper bound of finc_gradw_workspace_bytes over every call of this bank with at most `units` = B * ceil(W / 16) strips, whichever
+// form the plan picks (the largest grid each form of finc_gradw_plan can launch times what its workgroups write): it never shrinks when
+// `units` grows, which the bytes of the plans themselves do (a wider map changes form).  For workspace bounds that promise as much.
+size_t finc_gradw_workspace_bound(int G, int Cq, int KH, int KW, long long units)
+{
+    const GradwInst i = find_gradw(Cq, KH, KW);
+    if (!i.cqp || units < 1) return 0;
+    const auto grid = [&](int waves, int per_simd, int cap) {      // G * waves * wpg at gradw_wpg's largest
+        int w = 1024 * per_simd / (G * waves);
+        w = w < 1 ? 1 : w > cap ? cap : w;
+        return (size_t)G * waves * (size_t)(units < w ? units : w);
+    };
+    size_t most = 0;
+    const auto take = [&](size_t floats) { most = floats > most ? floats : most; };
+    if (const GradwWinoInst *w = KW == 3 ? find_gradw_wino(Cq, KH) : nullptr) take(grid(w->fs, 1, 1024) / w->fs * 6 * KH * w->cqp * w->cqp);
+    if ((KH == 3 && KW == 3) || (KH == 5 && KW == 5)) take(grid(i.mtg * i.mtg, 2, 256) * 6 * KH * 256);
+    if (i.gw_tiled) take(grid(i.mtg * i.mtg, 2, 256) * KH * KW * 256);
+    if (i.gw) take(grid(1, 1, 1024) * KH * KW * i.mtg * i.mtg * 256);
+    return most * sizeof(float);
+}
+
 // -----------------------------------------------------------------------------------------------
 // Weight and bias gradient of the per-pixel channel mix (finc_mix.hip; autograd through F.conv2d, layers/conv1x1.py:29-31):
 //     gm[o][i] = sum_{b,p} go[b,o,p] * x[b,i,p],     gb[o] = sum_{b,p} go[b,o,p]          (fp32, NCHW, HW = H*W)

@@ -258,5 +258,6 @@ int finc_mix_launch(const float *in, const float *mat, const float *bias, float 
 
 #include "finc_coupling.h"
 #include "finc_actnorm.h"
+#include "finc_adjoint.h"
 
 unsigned finc_build_flags_mix() { return FINC_BUILD_FLAGS; }

@@ -49,7 +49,8 @@ class ActNorm(FlowLayer):
     `forward` without an autograd graph as one launch (`ops.finc_actnorm`, the log-det included), `forward` under autograd through
     `ops.actnorm_forward` (backward: finc_actnorm_backward_f32, from the saved OUTPUT), `reverse` without a graph as one launch, and
     the data-dependent initialisation of the first forward as `ops.finc_actnorm_init` (at least two values per channel).  Everything
-    else -- CPU tensors, fp64, 2-D inputs, `reverse` under autograd, one value per channel -- keeps the PyTorch lines below."""
+    else -- CPU tensors, fp64, 2-D inputs, `reverse` under autograd (what `FlowSequential.rsample` and `reverse_grad()` record: these
+    lines ARE the differentiable reverse of this layer), one value per channel -- keeps the PyTorch lines below."""
 
     def __init__(self, n_dims):
         super().__init__()
@@ -139,7 +140,7 @@ class Conv1x1(FlowLayer):
     """layers/conv1x1.py:8-49.  Device tensors in fp32 with a channel count the library instantiates run on the HIP mixing
     kernel: inference / sampling (no autograd graph) as one streaming launch (`ops.finc_mix`), `forward` under autograd through
     `ops.mix_forward` (backward: finc_mix_backward_f32).  Everything else -- CPU tensors, fp64, other channel counts, `reverse`
-    under autograd -- keeps F.conv2d."""
+    under autograd (the differentiable reverse that `FlowSequential.rsample` records, through `torch.inverse(W)`) -- keeps F.conv2d."""
 
     def __init__(self, n_channels):
         super().__init__()
@@ -247,7 +248,7 @@ class Coupling(FlowLayer):
     Without an autograd graph (inference, sampling) the net's `Conv2d(bias) + ReLU` pairs are `F.conv2d(bias=None)` +
     `ops.finc_bias_relu` in place as well; under autograd `forward` goes through `ops.coupling_forward` (backward:
     finc_coupling_backward_f32) and the net stays PyTorch.  Everything else -- CPU tensors, fp64, odd channel counts, `reverse` under
-    autograd -- keeps the PyTorch formula below."""
+    autograd (the differentiable reverse that `FlowSequential.rsample` records) -- keeps the PyTorch formula below."""
 
     def __init__(self, input_size, width=512, n_context=None):
         super().__init__()

@@ -131,8 +131,15 @@ class PaddedConv2d(FlowLayer):
         return out, 0.0
 
     def reverse(self, x, context=None, compute_expensive=None):
+        """The inverse, DETACHED from autograd (the reference's `reverse` solves outside the graph too, layers/conv.py:109-163) -- unless
+        the call sits inside `fincflow_amd.reverse_grad()` and autograd is recording: then the result is attached, with the HIP backward
+        of `ops.inverse_reverse` behind it (the bias subtraction stays a differentiable PyTorch line)."""
+        b = self.bias if self.bias is not None else self.conv.bias
+        if ops.reverse_grad_enabled() and _records_graph(x, self.conv.weight, b):
+            if b is not None:
+                x = x - b.reshape(-1, x.shape[1], 1, 1)
+            return ops.inverse_reverse(x, *self._cache_args(), self._cache), 0
         with torch.no_grad():
-            b = self.bias if self.bias is not None else self.conv.bias
             if b is not None:
                 x = x - b.reshape(-1, x.shape[1], 1, 1)
             y = self._cache.inverse(x.contiguous(), *self._cache_args())
@@ -144,7 +151,9 @@ class PaddedConv2d(FlowLayer):
 
 class FastFlowUnit(nn.Module):
     """Four PaddedConv2d (TL, TR, BL, BR), one per channel quarter (fastflow.py:13-100), evaluated as ONE
-    grouped launch in each direction."""
+    grouped launch in each direction.  `forward` records an autograd graph whenever one is being recorded; `reverse` returns a
+    DETACHED tensor, as it always has, except inside `fincflow_amd.reverse_grad()`, where it is differentiable with respect to its
+    input and the four stored banks (`ops.inverse_reverse`: the backward runs the inverse kernels on the adjoint bank)."""
 
     def __init__(self, in_channels, out_channels, kernel_size):
         super().__init__()
@@ -177,6 +186,8 @@ class FastFlowUnit(nn.Module):
 
     def reverse_level2(self, x):
         """fastflow.py:78-100 without the 6 flip/cat/zeros copies: the kernel indexes the flipped pixel."""
+        if ops.reverse_grad_enabled() and _records_graph(x, *self._weights()):
+            return ops.inverse_reverse(x, *self._cache_args(), self._cache)
         with torch.no_grad():
             return self._cache.inverse(x.contiguous(), *self._cache_args())
 
@@ -222,7 +233,8 @@ class FastFlowUnit(nn.Module):
 
 class CINCFlowUnit(nn.Module):
     """The groups=1 (CInC) unit of cinc_flow.py:9-80: ONE top-left PaddedConv2d over all channels
-    (`out_channels` is overridden with `in_channels`, cinc_flow.py:17), state-dict key `conv_tl.conv.weight`."""
+    (`out_channels` is overridden with `in_channels`, cinc_flow.py:17), state-dict key `conv_tl.conv.weight`.  `reverse` is
+    PaddedConv2d's: detached, differentiable inside `fincflow_amd.reverse_grad()`."""
 
     def __init__(self, in_channels, out_channels, kernel_size):
         super().__init__()
@@ -412,6 +424,18 @@ class FlowSequential(nn.Module):
         if x.is_cuda:
             _lib.raise_if_faulted("FlowSequential.sample")
         return x, x_true
+
+    def rsample(self, n_samples, context=None):
+        """A reparameterised sample: x = reverse(z), z drawn from the base, with the reverse chain RECORDED for autograd (grad enabled,
+        inside `reverse_grad()`: the fused folds step aside, the units' inverses are differentiable), so that a loss on x reaches
+        every parameter -- reverse-KL training, adversarial fine-tuning of the sampler.  Returns x alone, attached to the graph; the
+        fault word is checked as in `sample`."""
+        z, _ = self.base_distribution.sample(n_samples, context)
+        with torch.enable_grad(), ops.reverse_grad():
+            x = self._reverse_chain(z, context)
+        if x.is_cuda:
+            _lib.raise_if_faulted("FlowSequential.rsample")
+        return x
 
     def reconstruct(self, input, context=None, compute_expensive=False):
         z = self.forward(input, context)[0]

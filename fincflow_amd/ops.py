@@ -7,6 +7,7 @@ RuntimeError for non-device / non-contiguous tensors.  `finc_inverse` /
 `finc_forward` are the orientation-aware calls FastFlowUnit uses (no flips, no
 chunk/cat copies: fastflow.py:78-100 collapses into one launch).
 """
+import contextlib
 import threading
 
 import torch
@@ -17,6 +18,26 @@ ORDER_BITS = {"TL": 0, "TR": 1, "BL": 2, "BR": 3}
 ORIENT_FASTFLOW = 0xE4  # TL,TR,BL,BR (fastflow.py:24-27)
 
 _workspaces = {}
+_reverse_grad = threading.local()
+
+
+@contextlib.contextmanager
+def reverse_grad():
+    """Inside this context the `reverse` of FastFlowUnit, PaddedConv2d and CINCFlowUnit is differentiable: whenever autograd is
+    recording (grad enabled, the input or a weight requires grad) it goes through `inverse_reverse` -- the same cached launch, with a
+    backward on the HIP kernels (finc_adjoint_weights_f32, the inverse itself on the adjoint bank, finc_lead_product_f32,
+    finc_backward_f32) -- and returns a tensor attached to the graph.  Outside it `reverse` is what it always was: detached.  The flag
+    is per thread and nests."""
+    depth = getattr(_reverse_grad, "depth", 0)
+    _reverse_grad.depth = depth + 1
+    try:
+        yield
+    finally:
+        _reverse_grad.depth = depth
+
+
+def reverse_grad_enabled():
+    return getattr(_reverse_grad, "depth", 0) > 0
 
 
 def _stream_ptr(t):
@@ -501,7 +522,7 @@ def inverse(input, kernel, output):
 
 class _DeviceBank:
     """What PackedWeights holds for ONE device and ONE weight version: a new version starts from a fresh object."""
-    __slots__ = ("key", "keep", "validated", "w_canon", "linv", "packed")
+    __slots__ = ("key", "keep", "validated", "w_canon", "linv", "packed", "adjoint")
 
     def __init__(self, key=None, keep=None, w_canon=None):
         self.key = key
@@ -510,6 +531,7 @@ class _DeviceBank:
         self.w_canon = w_canon
         self.linv = None
         self.packed = {}          # bank kind -> (key of the folded affine parameters or None, packed fragments)
+        self.adjoint = None       # (w_adj, lead_t) of the backward through the inverse (finc_adjoint_weights_f32), built by the first one
 
 
 def _fold_forward(log_scale, translation):
@@ -523,10 +545,11 @@ def _fold_inverse(log_scale, translation):
     return torch.exp(log_scale.detach().float()).contiguous(), translation.detach().float().contiguous()
 
 
-def _packed(bank, kind, pack, t, G, dims, fold=None, params=(), may_refuse=False):
+def _packed(bank, kind, pack, t, G, dims, fold=None, params=(), may_refuse=False, src=None):
     """The bank's packed fragments of one kind, allocated and packed by the entry point `pack` on `t`'s stream the first time a
     weight version asks for them -- and, for a kind that carries `fold(*params)` = (scale, shift), again when (address, version) of
-    the parameters change.  `may_refuse`: None, and nothing cached, when the pack answers FINC_ERR_UNSUPPORTED."""
+    the parameters change.  `may_refuse`: None, and nothing cached, when the pack answers FINC_ERR_UNSUPPORTED.  `src`: the canonical
+    bank to pack when it is not the entry's own (the adjoint bank)."""
     key = version_key(*params) if fold is not None else None
     hit = bank.packed.get(kind)
     if hit is not None and hit[0] == key:
@@ -539,7 +562,8 @@ def _packed(bank, kind, pack, t, G, dims, fold=None, params=(), may_refuse=False
             raise ValueError("affine parameters must have one entry per channel")
         affine = (scale.data_ptr(), shift.data_ptr())
     packed = torch.empty(_lib.lib().finc_workspace_bytes(G, Cq, KH, KW), dtype=torch.uint8, device=t.device)
-    if _call(pack, t.device, bank.w_canon.data_ptr(), *affine, packed.data_ptr(), G, Cq, KH, KW, _stream_ptr(t), may_refuse=may_refuse):
+    if _call(pack, t.device, (bank.w_canon if src is None else src).data_ptr(), *affine, packed.data_ptr(), G, Cq, KH, KW, _stream_ptr(t),
+             may_refuse=may_refuse):
         return None
     bank.packed[kind] = (key, packed)
     return packed
@@ -665,6 +689,44 @@ class PackedWeights:
             return finc_inverse(z, bank.w_canon, G, orient, out=out)
         return self._inverse_packed("finc_inverse_packed_f32", z, bank, out, G, dims, orient)
 
+    @staticmethod
+    def inverse_backward(bank, grad_x, x, G, orient, need_gz=True, need_gw=True):
+        """Gradients of x = inverse(z) on the entry `bank` of the weight version the forward ran on, given grad_x and the
+        inverse's OUTPUT x: (grad_z, grad_w_canon), each computed only if asked for.  grad_z = blockdiag(L^-T) inverse(grad_x) on the
+        adjoint bank with every group's orientation complemented; grad_w_canon = -(the forward's weight gradient at (x, grad_z)), masked
+        in-kernel.  The adjoint bank (w_adj, lead_t) and its packed fragments are a bank kind of the entry: built by the first backward
+        of a weight version, dropped with it.  The solve takes `inverse`'s route: the packed launch when there is an MFMA instantiation
+        and the activations are 16-byte aligned, otherwise finc_inverse."""
+        _require_device(grad_x, "grad_output")
+        w_canon = bank.w_canon
+        dims = _dims(grad_x, w_canon, G)
+        B, Cq, H, W, KH, KW = dims
+        gw = torch.empty_like(w_canon) if need_gw else None
+        if grad_x.numel() == 0:
+            if gw is not None:
+                gw.zero_()
+            return (torch.empty_like(grad_x) if need_gz else None), gw
+        if bank.adjoint is None:
+            w_adj = torch.empty_like(w_canon)
+            lead_t = torch.empty(G * Cq, G * Cq, dtype=torch.float32, device=w_canon.device)
+            _call("finc_adjoint_weights_f32", w_canon.device, w_canon.data_ptr(), w_adj.data_ptr(), lead_t.data_ptr(), G, Cq, KH, KW,
+                  _stream_ptr(grad_x))
+            bank.adjoint = (w_adj, lead_t)
+        w_adj, lead_t = bank.adjoint
+        adj_orient = orient ^ ((1 << (2 * G)) - 1)            # the transposed operator reads the opposite corner
+        y = torch.empty_like(grad_x)
+        if _has_mfma("finc_inverse_algo_for", grad_x, dims) and _aligned16(grad_x, y):
+            packed = _packed(bank, "inv_adjoint", "finc_pack_inverse_weights_f32", grad_x, G, dims, src=w_adj)
+            _launch_packed("finc_inverse_packed_f32", grad_x, packed, y, G, dims, adj_orient)
+        else:
+            finc_inverse(grad_x, w_adj, G, adj_orient, out=y)
+        _call("finc_lead_product_f32", y.device, y.data_ptr(), lead_t.data_ptr(), B, G, Cq, H * W, _stream_ptr(y))
+        if need_gw:
+            _call("finc_backward_f32", y.device, y.data_ptr(), x.data_ptr(), w_canon.data_ptr(), None, gw.data_ptr(), B, G, Cq, H, W, KH, KW,
+                  orient, *_ws_args(y.device, _lib.lib().finc_backward_workspace_bytes(B, G, Cq, H, W, KH, KW)), _stream_ptr(y))
+            _call("finc_negate_f32", gw.device, gw.data_ptr(), gw.numel(), _stream_ptr(y))
+        return (y if need_gz else None), gw
+
     def lead_inverse(self, weights, G, orient):
         """Linv_g = inverse of the unit lower triangular tap of the pixel itself (canonical tap [KH-1, KW-1],
         layers/conv.py:63-70), [G, Cq, Cq] fp32 (solved in fp64), cached per weight version: what a channel mix in front of
@@ -753,3 +815,41 @@ def conv_forward(x, weights, G, orient, cache):
     """z = forward(x) under autograd.  `weights`: the stored (state-dict form) banks of the G groups, one tensor per group or
     one tensor for all; `cache`: the layer's PackedWeights."""
     return _FincConvFunction.apply(x, cache, G, orient, *weights)
+
+
+class _FincInverseFunction(torch.autograd.Function):
+    """The autograd.Function underneath the units' `reverse` inside `reverse_grad()`.  Forward: the cached launch of
+    `PackedWeights.inverse`, invariant check included.  Saved: the OUTPUT and the canonical bank (with the cache entry of this weight
+    version, which holds the adjoint bank).  Backward: `PackedWeights.inverse_backward`, then canonical -> stored per group as
+    `_FincConvFunction.backward` does; only what `needs_input_grad` asks for is computed."""
+
+    @staticmethod
+    def forward(ctx, z, cache, G, orient, *weights):
+        z = z.contiguous()
+        out = cache.inverse(z, list(weights), G, orient)
+        bank = cache._get(list(weights), G, orient)             # (same entry: canonical and checked already)
+        ctx.save_for_backward(out, bank.w_canon)
+        ctx.bank, ctx.G, ctx.orient, ctx.nw = bank, G, orient, len(weights)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_x):
+        x, _ = ctx.saved_tensors
+        need_gw = any(ctx.needs_input_grad[4:])
+        gz, gw = PackedWeights.inverse_backward(ctx.bank, grad_x.contiguous(), x, ctx.G, ctx.orient,
+                                                need_gz=ctx.needs_input_grad[0], need_gw=need_gw)
+        gws = (None,) * ctx.nw
+        if gw is not None:
+            gw = canonicalize(gw, ctx.G, ctx.orient)  # canonical -> stored orientation
+            gws = tuple(gw.chunk(ctx.nw, dim=0)) if ctx.nw > 1 else (gw,)
+        return (gz, None, None, None) + gws
+
+
+def inverse_reverse(z, weights, G, orient, cache):
+    """x = inverse(z) under autograd (see `reverse_grad`): gradients for `z` and for every stored bank in `weights`.  fp32 tensors on
+    the device only: anything else raises instead of returning a detached result."""
+    if not z.is_cuda or z.dtype != torch.float32 or z.dim() != 4:
+        raise _lib.FincError("reverse_grad(): the differentiable inverse takes fp32 [B,C,H,W] tensors on the device, got "
+                             f"{z.dtype} on {z.device} with {z.dim()} dimensions (there is no fp64 and no CPU backward)")
+    return _FincInverseFunction.apply(z, cache, G, orient, *weights)

@@ -194,6 +194,49 @@ int finc_backward_f32(const float *grad_z, const float *x, const float *w_canon,
                       size_t workspace_bytes, finc_stream_t stream);
 
 /*
+ * Backward through the unit's INVERSE (differentiable sampling: reverse-KL training, latent optimisation; the reference has no
+ * counterpart -- its `inverse` op, cinc_cuda_level2.cpp:19-32, records nothing for autograd).  With x = inverse(z), i.e. M x = z for
+ * M = L_blk + N (L: the unit lower triangular tap of the pixel itself, w_canon[g][:, :, KH-1, KW-1]; N: every other tap), and an
+ * upstream gradient grad_x:
+ *     grad_z       = y = transpose(inverse(M)) * grad_x
+ *     grad_w_canon = -(finc_backward_f32's grad_w at input x and grad_z := y), the same in-kernel corner mask (masked entries 0)
+ * transpose(M) is the same convolution read from the opposite corner (every group's orientation bits complemented) with transposed
+ * channel matrices; its corner tap, transpose(L), is UPPER triangular, which no inverse kernel takes, so it is factored out on the
+ * right:  transpose(M) = (I + sum_t S_t T_t) * transpose(L_blk),  T_t = transpose(W_t) * transpose(inverse(L)),  and
+ *     v = inverse(grad_x; bank w_adj, orientation complemented),      y = blockdiag(transpose(inverse(L_g))) * v   per pixel.
+ * finc_adjoint_weights_f32: w_canon -> w_adj [G*Cq][Cq][KH][KW] and lead_t [C][C] (C = G*Cq), all math in fp64, rounded once:
+ *     w_adj[g][i][o][kh][kw] = sum_k w_canon[g][k][i][kh][kw] * Linv_g[o][k]  for every tap but the corner, whose tap is the identity
+ *     lead_t[g*Cq + a][g*Cq + b] = Linv_g[b][a], zero outside the diagonal blocks (row = output channel: a finc_mix_f32 matrix)
+ *   w_adj is a canonical bank like any other (finc_check_invariant_f32 passes): finc_inverse_f32 / finc_pack_inverse_weights_f32 +
+ *   finc_inverse_packed_f32 solve it with every kernel and launch rule they have.  Any Cq <= FINC_MAX_CQ, G <= 16, any filter.  The
+ *   outputs may alias neither the input nor each other (FINC_ERR_BAD_DIMS).
+ * finc_lead_product_f32: v <- blockdiag(transpose(inverse(L_g))) * v IN PLACE, v [B][C][HW]: finc_mix_f32's kernel with lead_t where
+ *   finc_mix_supported_f32(C), else a plain grouped kernel on the unit upper triangular block of each group (any C; 16-byte pieces when
+ *   HW % 4 == 0 and v is 16-byte aligned, dwords otherwise).
+ * finc_negate_f32: p[i] <- -p[i] for n floats (0 stays +0): the sign of grad_w, on the [C][Cq][KH][KW] result -- never a pass over
+ *   activations.
+ * finc_inverse_backward_f32: the one-call form -- adjoint bank, pack, the inverse's FINC_ALGO_AUTO dispatch on w_adj with the
+ *   complemented orientation, the lead product, the grad-weight and its sign, all on `stream`, asynchronously.  `x` is the inverse's
+ *   OUTPUT.  Either output may be NULL to skip it, not both; grad_w_canon is OVERWRITTEN; `x` is read for grad_w_canon only and may be
+ *   NULL without it; grad_z may alias neither grad_x nor x.  `workspace`: finc_inverse_backward_workspace_bytes() bytes, 16-byte
+ *   aligned (it holds w_adj, lead_t, y when grad_z is skipped, and what the solve and the grad-weight take: packed fragments, the
+ *   padded copies of a width that is no multiple of 4, partial sums); the bound is > 0 for any arguments and never shrinks when B, H
+ *   or W grows.  An image of 2 GiB or more (G*Cq*H*W >= 2^29) is FINC_ERR_BAD_DIMS.  Callers that run many backwards on one weight
+ *   version keep w_adj, lead_t and the packed fragments and call the pieces (the Python layer does).
+ * Status, checked in this order before any HIP call: a NULL required pointer FINC_ERR_NULL_POINTER; the dims FINC_ERR_BAD_DIMS; a
+ * pointer not 4-byte aligned FINC_ERR_ALIGNMENT; forbidden aliasing FINC_ERR_BAD_DIMS; a missing, misaligned or short workspace
+ * FINC_ERR_WORKSPACE; grad_w_canon for a filter finc_backward_f32 has no grad-weight kernel for (more than 49 taps: 8x8 and up)
+ * FINC_ERR_UNSUPPORTED -- grad_z alone is available for every filter.  The four launching calls take part in the sticky-fault rule below like every other.
+ */
+int finc_adjoint_weights_f32(const float *w_canon, float *w_adj, float *lead_t, int G, int Cq, int KH, int KW, finc_stream_t stream);
+int finc_lead_product_f32(float *v, const float *lead_t, int B, int G, int Cq, int HW, finc_stream_t stream);
+int finc_negate_f32(float *p, size_t n, finc_stream_t stream);
+size_t finc_inverse_backward_workspace_bytes(int B, int G, int Cq, int H, int W, int KH, int KW);
+int finc_inverse_backward_f32(const float *grad_x, const float *x, const float *w_canon, float *grad_z, float *grad_w_canon, int B,
+                              int G, int Cq, int H, int W, int KH, int KW, unsigned orient, void *workspace, size_t workspace_bytes,
+                              finc_stream_t stream);
+
+/*
  * Double precision: the reference op dispatches over float AND double (AT_DISPATCH_FLOATING_TYPES,
  * cinc_cuda_kernel_level2.cu:117), and its CPU solver computes in fp64 (solve_parallel_mc.pyx:77-126, called from
  * layers/conv.py:113-163).  These entry points run the reference visitation and term order in fp64 (separately
@@ -378,7 +421,7 @@ int finc_debug_attr_table_insert(int device, size_t kernel_token);
 int finc_debug_hlp_timeouts(unsigned *h_count);
 /* A wait that gives up leaves garbage in that launch's output.  It does not pass silently: the kernel also sets a word in
  * mapped host memory, and every later launching call on that device -- finc_inverse_*, finc_forward_*, finc_mix_f32,
- * finc_backward_f32, finc_check_invariant_f32, the coupling's and ActNorm's calls -- returns FINC_ERR_LAUNCH (finc_last_hip_error() names the cause) until
+ * finc_backward_f32, finc_check_invariant_f32, the coupling's and ActNorm's calls, the inverse's backward -- returns FINC_ERR_LAUNCH (finc_last_hip_error() names the cause) until
  * finc_clear_fault(); no synchronisation is added to the launch path.  The word is armed by the packing calls (and by the
  * first helper-wave launch outside a stream capture).  The launch that faulted has itself returned FINC_OK (it is
  * asynchronous): callers check finc_fault_pending() at their own synchronisation points -- the Python layer does at the
