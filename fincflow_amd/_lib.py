@@ -37,6 +37,7 @@ SYMBOLS = [
     "finc_actnorm_workspace_bytes", "finc_actnorm_f32", "finc_actnorm_backward_f32", "finc_actnorm_init_f32",
     "finc_adjoint_weights_f32", "finc_lead_product_f32", "finc_negate_f32", "finc_inverse_backward_workspace_bytes",
     "finc_inverse_backward_f32",
+    "finc_coupling_reverse_backward_f32", "finc_actnorm_reverse_backward_f32",
 ]
 
 #: the ABI version this binding is written against (include/finc.h: finc_version)
@@ -47,6 +48,9 @@ ACTNORM_ABI_VERSION = 105
 #: the version that added the backward through the inverse (finc_adjoint_weights_f32, finc_lead_product_f32, finc_negate_f32,
 #: finc_inverse_backward_f32)
 INVERSE_BACKWARD_ABI_VERSION = 107
+#: the version that added the backwards of the per-pixel layers' reverse direction (finc_coupling_reverse_backward_f32,
+#: finc_actnorm_reverse_backward_f32)
+REVERSE_BACKWARD_ABI_VERSION = 108
 
 _lib = None
 
@@ -81,6 +85,11 @@ def lib():
     if have < INVERSE_BACKWARD_ABI_VERSION:
         raise FincError(f"{LIB_PATH} reports finc_version() = {have}, the backward through the inverse (finc_adjoint_weights_f32, "
                         f"finc_inverse_backward_f32) came with {INVERSE_BACKWARD_ABI_VERSION}: rebuild it "
+                        "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
+    if have < REVERSE_BACKWARD_ABI_VERSION:
+        raise FincError(f"{LIB_PATH} reports finc_version() = {have}, the backwards of the reverse direction "
+                        f"(finc_coupling_reverse_backward_f32, finc_actnorm_reverse_backward_f32) came with "
+                        f"{REVERSE_BACKWARD_ABI_VERSION}: rebuild it "
                         "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
     L.finc_build_flags.restype = u
     L.finc_clear_fault.restype = i
@@ -153,6 +162,8 @@ def lib():
     L.finc_inverse_backward_workspace_bytes.restype = sz
     L.finc_inverse_backward_workspace_bytes.argtypes = [i, i, i, i, i, i, i]
     L.finc_inverse_backward_f32.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, u, vp, sz, vp]
+    L.finc_coupling_reverse_backward_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp]
+    L.finc_actnorm_reverse_backward_f32.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp]
     for name in SYMBOLS:
         getattr(L, name)  # AttributeError here = header and library out of sync
     _lib = L

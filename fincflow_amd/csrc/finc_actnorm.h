@@ -8,6 +8,8 @@
 //   * finc_actnorm_bwd_kernel    one pass over grad_y and y (the forward's OUTPUT: x - t = y * exp(ls), so
 //                                d loss / d ls[c] = -sum grad_y * y needs nothing the forward's caller does not keep anyway):
 //                                grad_x = grad_y * exp(-ls[c]) and the two per-channel sums, then finc_coupling_reduce_kernel.
+//   * finc_actnorm_rev_bwd_kernel  the same for the reverse direction, from the reverse's INPUT (what `reverse` under autograd
+//                                records inside ops.reverse_grad()).
 //   * finc_actnorm_stats_kernel  the data-dependent initialisation (:17-23): per-channel mean and unbiased standard deviation in ONE
 //                                pass over x.  Every thread folds its pieces into a running (n, mean, M2) triple (Chan et al.'s pairwise
 //                                update: the squares are taken of differences from a running mean, never of x itself -- the
@@ -97,6 +99,44 @@ __global__ __launch_bounds__(CPL_THREADS) void finc_actnorm_bwd_kernel(const flo
                 p0[Q] = 0.f;
                 p1[Q] = -(float)HW * l;
             }
+        }
+    }
+}
+
+// The backward of the REVERSE direction, y = x * exp(ls[c]) + t[c] (layers/actnorm.py:47-52), from grad_y and the reverse's INPUT x:
+// grad_x = grad_y * exp(ls[c]), grad_ls[c] = exp(ls[c]) * sum grad_y * x, grad_t[c] = sum grad_y.  (The output would do in real
+// arithmetic -- x * exp(ls) = y - t -- but on a channel with |t| >> |y - t| that difference has lost its digits.)
+// Workgroups and partials as in finc_actnorm_bwd_kernel, Q per output: part[(2c) * Q + q] = sum gy, part[(2c+1) * Q + q] =
+// exp(ls[c]) * sum gy * x.  x (without grad_ls), gx may be nullptr; `sums` = 0 skips the partials.  gx == gy is allowed.
+template <int V>
+__global__ __launch_bounds__(CPL_THREADS) void finc_actnorm_rev_bwd_kernel(const float *gy, const float *__restrict__ x,
+                                                                           const float *__restrict__ ls, float *gx,
+                                                                           float *__restrict__ part, int C, int HW, int nv, int items, int Q,
+                                                                           int sums)
+{
+    const int c = (int)blockIdx.x / Q, qi = (int)blockIdx.x - c * Q;
+    const float s = expf(ls[c]);
+    float acc[2] = {0.f, 0.f};
+    for (int idx = qi * CPL_THREADS + (int)threadIdx.x; idx < items; idx += Q * CPL_THREADS) {
+        const int img = idx / nv, p = (idx - img * nv) * V;
+        const size_t o = ((size_t)img * C + c) * (size_t)HW + p;
+        float g[V], xv[V], d[V];
+        cpl_load<V>(g, gy + o);
+        if (x) cpl_load<V>(xv, x + o);
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            d[e] = g[e] * s;
+            acc[0] += g[e];
+            if (x) acc[1] = fmaf(g[e], xv[e], acc[1]);
+        }
+        if (gx) cpl_store<V>(gx + o, d);
+    }
+    if (sums) {
+        __shared__ float sm[2][4];
+        cpl_block_sum<2>(acc, sm);
+        if (threadIdx.x == 0) {
+            part[(size_t)(2 * c) * Q + qi] = acc[0];
+            part[(size_t)(2 * c + 1) * Q + qi] = s * acc[1];
         }
     }
 }
@@ -221,6 +261,24 @@ int finc_actnorm_backward_launch(const float *gy, const float *gld, const float 
     FINC_CHECK_LAUNCH();
     if (sums) {
         hipLaunchKernelGGL(finc_coupling_reduce_kernel, dim3((unsigned)(2 * C)), dim3(64), 0, st, (const float *)ws, Q + 1, gt, gls, 1);
+        FINC_CHECK_LAUNCH();
+    }
+    return FINC_OK;
+}
+
+int finc_actnorm_reverse_backward_launch(const float *gy, const float *x, const float *ls, float *gx, float *gls, float *gt, int B, int C,
+                                         int HW, float *ws, hipStream_t st)
+{
+    if (!cpl_rows_fit(B, C, HW)) return FINC_ERR_BAD_DIMS;
+    if (!gls) x = nullptr;                                           // only grad_ls reads x
+    const bool wide = cpl_wide(HW, (uintptr_t)gy | (uintptr_t)x | (uintptr_t)gx);
+    const int nv = HW / (wide ? 4 : 1), items = B * nv, Q = cpl_parts(items, C), sums = (gls || gt) ? 1 : 0;
+    const dim3 grid((unsigned)((long long)C * Q)), block(CPL_THREADS);
+    hipLaunchKernelGGL(wide ? finc_actnorm_rev_bwd_kernel<4> : finc_actnorm_rev_bwd_kernel<1>, grid, block, 0, st, gy, x, ls, gx, ws, C, HW,
+                       nv, items, Q, sums);
+    FINC_CHECK_LAUNCH();
+    if (sums) {
+        hipLaunchKernelGGL(finc_coupling_reduce_kernel, dim3((unsigned)(2 * C)), dim3(64), 0, st, (const float *)ws, Q, gt, gls, 1);
         FINC_CHECK_LAUNCH();
     }
     return FINC_OK;

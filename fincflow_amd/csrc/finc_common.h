@@ -265,6 +265,9 @@ int finc_coupling_launch(const float *x, const float *raw, const float *a, const
                          int direction, float *ws, hipStream_t st);
 int finc_coupling_backward_launch(const float *gy, const float *gld, const float *x, const float *raw, const float *a, const float *b,
                                   float *gx, float *graw, float *ga, float *gb, int B, int C, int HW, float *ws, hipStream_t st);
+// the backward of direction -1, from the reverse's OUTPUT y
+int finc_coupling_reverse_backward_launch(const float *gy, const float *y, const float *raw, const float *a, const float *b, float *gx,
+                                          float *graw, float *ga, float *gb, int B, int C, int HW, float *ws, hipStream_t st);
 int finc_bias_relu_launch(const float *in, const float *bias, float *out, int B, int C, int HW, hipStream_t st);
 // ---- ActNorm (transform + log-det, its backward from the forward's OUTPUT, the data-dependent initialisation): finc_actnorm.h, same object ----
 // `ws` holds finc_actnorm_workspace_floats floats (backward with gls / gt, and the initialisation)
@@ -273,6 +276,9 @@ int finc_actnorm_launch(const float *x, const float *ls, const float *tr, float 
                         hipStream_t st);
 int finc_actnorm_backward_launch(const float *gy, const float *gld, const float *y, const float *ls, float *gx, float *gls, float *gt,
                                  int B, int C, int HW, float *ws, hipStream_t st);
+// the backward of direction -1, from the reverse's INPUT x
+int finc_actnorm_reverse_backward_launch(const float *gy, const float *x, const float *ls, float *gx, float *gls, float *gt, int B, int C,
+                                         int HW, float *ws, hipStream_t st);
 int finc_actnorm_init_launch(const float *x, float *ls, float *tr, int B, int C, int HW, float *ws, hipStream_t st);
 // ---- backward through the unit's inverse (adjoint bank, lead product, the weight gradient's sign): finc_adjoint.h, same object ----
 // w_adj [G*Cq][Cq][KH][KW]: the canonical bank whose inverse (orientation complemented) is the adjoint solve up to the lead product;

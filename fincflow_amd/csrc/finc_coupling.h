@@ -8,6 +8,8 @@
 //   * finc_coupling_bwd_kernel  one pass: every gradient of the forward direction; s and exp(s) are recomputed from raw (two
 //                               transcendentals per element) instead of being saved: saving them would add two tensor writes to the
 //                               forward and two reads here, and this kernel is bound by its memory traffic, not by the VALU.
+//   * finc_coupling_rev_bwd_kernel  the same for the reverse direction, from the reverse's OUTPUT (what `reverse` under autograd
+//                               records inside ops.reverse_grad()).
 //   * finc_bias_relu_kernel     out = max(in + bias[c], 0), in place or not.
 // Layout: x, y [B][C][HW] fp32, raw [B][C][HW] with channel 2j = u_j (pre-activation of the log-scale) and 2j+1 = t_j (translation).
 // A thread owns V consecutive pixels of one channel pair j: V = 4 (16-byte pieces) when HW % 4 == 0 and every pointer is 16-byte
@@ -160,6 +162,60 @@ __global__ __launch_bounds__(CPL_THREADS) void finc_coupling_bwd_kernel(const fl
     }
 }
 
+// The backward of the REVERSE direction, y2 = (x2 - t) * exp(-s) (layers/coupling.py:95-101), from grad_y and the reverse's OUTPUT y:
+// d y2 / d x2 = E = exp(-s), d y2 / d t = -E, d y2 / d s = -y2, so the input is not needed (in a recorded reverse chain y is the tensor
+// the next layer keeps anyway).  Workgroups, partials and the nullptr rules as in finc_coupling_bwd_kernel; no log-det in this direction.
+template <int V>
+__global__ __launch_bounds__(CPL_THREADS) void finc_coupling_rev_bwd_kernel(const float *__restrict__ gy, const float *__restrict__ y,
+                                                                            const float *__restrict__ raw, const float *__restrict__ a,
+                                                                            const float *__restrict__ b, float *__restrict__ gx,
+                                                                            float *__restrict__ graw, float *__restrict__ part, int half,
+                                                                            int HW, int nv, int items, int Q, int sums)
+{
+    const int j = (int)blockIdx.x / Q, qi = (int)blockIdx.x - j * Q;
+    const float au = a[2 * j], bu = b[2 * j], at = a[2 * j + 1];
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int idx = qi * CPL_THREADS + (int)threadIdx.x; idx < items; idx += Q * CPL_THREADS) {
+        const int img = idx / nv, p = (idx - img * nv) * V;
+        const size_t ibase = (size_t)img * (size_t)(2 * half) * (size_t)HW;
+        const size_t o1 = ibase + (size_t)j * HW + p, o2 = o1 + (size_t)half * HW;
+        const size_t ou = ibase + (size_t)(2 * j) * HW + p, ot = ou + HW;
+        float g1[V], g2[V], y2[V], u[V], t[V], gx2[V], gu[V], gt[V];
+        if (gx) cpl_load<V>(g1, gy + o1);
+        cpl_load<V>(g2, gy + o2);
+        cpl_load<V>(y2, y + o2);
+        cpl_load<V>(u, raw + ou);
+        if (sums) cpl_load<V>(t, raw + ot);
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            const float th = tanhf(0.5f * fmaf(au, u[e], bu));     // s = 2 th, d s / d h = 1 - th*th
+            gx2[e] = g2[e] * expf(-2.f * th);
+            const float ghu = -(g2[e] * y2[e]) * fmaf(-th, th, 1.f), ght = -gx2[e];
+            gu[e] = au * ghu;
+            gt[e] = at * ght;
+            if (sums) {
+                acc[0] = fmaf(ghu, u[e], acc[0]);
+                acc[1] += ghu;
+                acc[2] = fmaf(ght, t[e], acc[2]);
+                acc[3] += ght;
+            }
+        }
+        if (gx) {
+            cpl_store<V>(gx + o1, g1);
+            cpl_store<V>(gx + o2, gx2);
+        }
+        if (graw) {
+            cpl_store<V>(graw + ou, gu);
+            cpl_store<V>(graw + ot, gt);
+        }
+    }
+    if (sums) {
+        __shared__ float sm[4][4];
+        cpl_block_sum<4>(acc, sm);
+        if (threadIdx.x < 4) part[((size_t)(4 * j) + threadIdx.x) * Q + qi] = acc[threadIdx.x];
+    }
+}
+
 // One wave per output: out = sum of its n consecutive partials, lane l takes l, l + 64, ... and the lanes meet in a butterfly.
 // pairs == 0: out_a[o] (the log-det of image o).  pairs == 1: output o = 4j + k goes to out_a / out_b as listed above; a nullptr
 // destination is neither summed nor written.
@@ -270,6 +326,24 @@ int finc_coupling_backward_launch(const float *gy, const float *gld, const float
     const dim3 grid((unsigned)((long long)half * Q)), block(CPL_THREADS);
     hipLaunchKernelGGL(wide ? finc_coupling_bwd_kernel<4> : finc_coupling_bwd_kernel<1>, grid, block, 0, st, gy, gld, x, raw, a, b, gx, graw,
                        ws, half, HW, nv, items, Q, sums);
+    FINC_CHECK_LAUNCH();
+    if (sums) {
+        hipLaunchKernelGGL(finc_coupling_reduce_kernel, dim3((unsigned)(4 * half)), dim3(64), 0, st, (const float *)ws, Q, ga, gb, 1);
+        FINC_CHECK_LAUNCH();
+    }
+    return FINC_OK;
+}
+
+int finc_coupling_reverse_backward_launch(const float *gy, const float *y, const float *raw, const float *a, const float *b, float *gx,
+                                          float *graw, float *ga, float *gb, int B, int C, int HW, float *ws, hipStream_t st)
+{
+    const int half = C / 2, sums = (ga || gb) ? 1 : 0;
+    if (!cpl_rows_fit(B, C, HW)) return FINC_ERR_BAD_DIMS;
+    const bool wide = cpl_wide(HW, (uintptr_t)gy | (uintptr_t)y | (uintptr_t)raw | (uintptr_t)gx | (uintptr_t)graw);
+    const int nv = HW / (wide ? 4 : 1), items = B * nv, Q = cpl_parts(items, half);
+    const dim3 grid((unsigned)((long long)half * Q)), block(CPL_THREADS);
+    hipLaunchKernelGGL(wide ? finc_coupling_rev_bwd_kernel<4> : finc_coupling_rev_bwd_kernel<1>, grid, block, 0, st, gy, y, raw, a, b, gx,
+                       graw, ws, half, HW, nv, items, Q, sums);
     FINC_CHECK_LAUNCH();
     if (sums) {
         hipLaunchKernelGGL(finc_coupling_reduce_kernel, dim3((unsigned)(4 * half)), dim3(64), 0, st, (const float *)ws, Q, ga, gb, 1);

@@ -2,7 +2,9 @@
 configs[3]): thin PyTorch modules with the reference's constructor arguments, parameter names and
 forward -> (out, logdet[B]) / reverse -> out protocol, so that `create_model` below builds the topology of
 fastflow/fastflow_cifar.py:35-63 around fincflow_amd.FastFlowUnit.  ActNorm, Conv1x1 and the coupling's transform run on HIP
-kernels of their own (ops.finc_actnorm, ops.finc_mix, ops.finc_coupling), in inference and under autograd; the coupling net's
+kernels of their own (ops.finc_actnorm, ops.finc_mix, ops.finc_coupling), in inference and under autograd -- `forward` always,
+`reverse` inside `ops.reverse_grad()` (what `FlowSequential.rsample` records: ops.actnorm_reverse, ops.mix_forward on W^-1,
+ops.coupling_reverse); `reverse` under autograd outside that context keeps its PyTorch lines.  The coupling net's
 convolutions, Squeeze and the preprocessing layers are ops that PyTorch-ROCm already runs.  The point of this file is that a
 whole sampling pass (96 units at 16x16 / 8x8 / 4x4) can run and be captured in one HIP graph.
 
@@ -10,7 +12,7 @@ Reference semantics followed:
   Squeeze        layers/squeeze.py:5-41          space-to-depth, channel order (c, dy, dx)
   ActNorm        layers/actnorm.py:5-66          data-dependent init on first forward; out = (x - t) * exp(-log_scale);
                  on the device one HIP launch each way (ops.finc_actnorm), init and backward included (ops.finc_actnorm_init,
-                 ops.actnorm_forward)
+                 ops.actnorm_forward, ops.actnorm_reverse)
   Conv1x1        layers/conv1x1.py:8-49          orthogonal init, ldj = H*W*log|det W|
   Coupling       layers/coupling.py:46-113       affine, net = conv3x3-ReLU-conv1x1-ReLU-Conv2dZero, log_s = 2*tanh(h/2);
                  on the device the part behind the net is one HIP launch (ops.finc_coupling)
@@ -48,9 +50,10 @@ class ActNorm(FlowLayer):
     """layers/actnorm.py:5-66.  Device tensors in fp32, 4-D, with fp32 parameters on the same device run on the HIP ActNorm kernels:
     `forward` without an autograd graph as one launch (`ops.finc_actnorm`, the log-det included), `forward` under autograd through
     `ops.actnorm_forward` (backward: finc_actnorm_backward_f32, from the saved OUTPUT), `reverse` without a graph as one launch, and
-    the data-dependent initialisation of the first forward as `ops.finc_actnorm_init` (at least two values per channel).  Everything
-    else -- CPU tensors, fp64, 2-D inputs, `reverse` under autograd (what `FlowSequential.rsample` and `reverse_grad()` record: these
-    lines ARE the differentiable reverse of this layer), one value per channel -- keeps the PyTorch lines below."""
+    the data-dependent initialisation of the first forward as `ops.finc_actnorm_init` (at least two values per channel).  `reverse`
+    under autograd inside `ops.reverse_grad()` (what `FlowSequential.rsample` records) goes through `ops.actnorm_reverse` (backward:
+    finc_actnorm_reverse_backward_f32, from the saved INPUT).  Everything else -- CPU tensors, fp64, 2-D inputs, `reverse` under
+    autograd outside that context, one value per channel -- keeps the PyTorch lines below, which are differentiable as they are."""
 
     def __init__(self, n_dims):
         super().__init__()
@@ -113,7 +116,13 @@ class ActNorm(FlowLayer):
         t, ls = self._shaped(input)
         return (input - t) * torch.exp(-ls), self.logdet(input, context)
 
+    def _hip_reverse_grad(self, x):
+        """`reverse` while autograd records inside `ops.reverse_grad()`: the HIP launch with a backward of its own."""
+        return ops.reverse_grad_enabled() and self._records_graph(x) and self._hip_device(x)
+
     def reverse(self, input, context=None):
+        if self._hip_reverse_grad(input):
+            return ops.actnorm_reverse(input, self.log_scale, self.translation)
         if self._hip_device(input) and not self._records_graph(input):
             return ops.finc_actnorm(input.contiguous(), self.log_scale.detach(), self.translation.detach(), -1)[0]
         t, ls = self._shaped(input)
@@ -139,8 +148,9 @@ class ActNorm(FlowLayer):
 class Conv1x1(FlowLayer):
     """layers/conv1x1.py:8-49.  Device tensors in fp32 with a channel count the library instantiates run on the HIP mixing
     kernel: inference / sampling (no autograd graph) as one streaming launch (`ops.finc_mix`), `forward` under autograd through
-    `ops.mix_forward` (backward: finc_mix_backward_f32).  Everything else -- CPU tensors, fp64, other channel counts, `reverse`
-    under autograd (the differentiable reverse that `FlowSequential.rsample` records, through `torch.inverse(W)`) -- keeps F.conv2d."""
+    `ops.mix_forward` (backward: finc_mix_backward_f32), and so does `reverse` under autograd inside `ops.reverse_grad()` (what
+    `FlowSequential.rsample` records), on `torch.inverse(W)` -- a recorded [C, C] op -- or, with W frozen, on the cached inverse.
+    Everything else -- CPU tensors, fp64, other channel counts, `reverse` under autograd outside that context -- keeps F.conv2d."""
 
     def __init__(self, n_channels):
         super().__init__()
@@ -174,6 +184,10 @@ class Conv1x1(FlowLayer):
             self._aff_key = None
         return self._w_inv
 
+    def _hip_reverse_grad(self, z):
+        """`reverse` while autograd records inside `ops.reverse_grad()`: the mix kernel under autograd."""
+        return ops.reverse_grad_enabled() and _records_graph(z, self.W) and self._hip_device(z)
+
     def reverse(self, z, context=None):
         if self._hip(z):
             return ops.finc_mix(z.contiguous(), self._inverse_matrix())
@@ -181,6 +195,8 @@ class Conv1x1(FlowLayer):
             w_inv = torch.inverse(self.W)
         else:
             w_inv = self._inverse_matrix()
+        if self._hip_reverse_grad(z):
+            return ops.mix_forward(z, w_inv)
         return F.conv2d(z, w_inv.view(self.n_channels, self.n_channels, 1, 1))
 
     def reverse_then_affine(self, z, log_scale, translation):
@@ -247,8 +263,10 @@ class Coupling(FlowLayer):
     on the HIP coupling kernel (`ops.finc_coupling`: affine transform, log-det and the copy of the untouched half in one launch).
     Without an autograd graph (inference, sampling) the net's `Conv2d(bias) + ReLU` pairs are `F.conv2d(bias=None)` +
     `ops.finc_bias_relu` in place as well; under autograd `forward` goes through `ops.coupling_forward` (backward:
-    finc_coupling_backward_f32) and the net stays PyTorch.  Everything else -- CPU tensors, fp64, odd channel counts, `reverse` under
-    autograd (the differentiable reverse that `FlowSequential.rsample` records) -- keeps the PyTorch formula below."""
+    finc_coupling_backward_f32) and the net stays PyTorch; so does `reverse` under autograd inside `ops.reverse_grad()` (what
+    `FlowSequential.rsample` records), through `ops.coupling_reverse` (backward: finc_coupling_reverse_backward_f32, from the saved
+    OUTPUT).  Everything else -- CPU tensors, fp64, odd channel counts, `reverse` under autograd outside that context -- keeps the
+    PyTorch formula below."""
 
     def __init__(self, input_size, width=512, n_context=None):
         super().__init__()
@@ -275,6 +293,14 @@ class Coupling(FlowLayer):
     def _hip_train(self, x, context=None):
         """`forward` under autograd: PyTorch net, HIP transform with its own backward."""
         return self._records_graph(x, context) and self._hip_device(x)
+
+    def _hip_reverse_grad(self, x, context=None):
+        """`reverse` while autograd records inside `ops.reverse_grad()`: PyTorch net, HIP transform with its own backward."""
+        return ops.reverse_grad_enabled() and self._hip_train(x, context)
+
+    def _raw_train(self, x, context):
+        n = self.net
+        return F.conv2d(n[:4](self._net_input(x, context)), n[4].weight, None, padding=1)
 
     def _scale_shift(self):
         # h = a * raw + b with raw the last convolution WITHOUT its bias: Conv2dZero is (conv + bias) * exp(logs * factor)
@@ -323,10 +349,8 @@ class Coupling(FlowLayer):
             a, b = self._scale_shift_cached()
             return ops.finc_coupling(x, self._raw_inference(x, context), a, b, 1, True)
         if self._hip_train(input, context):
-            n = self.net
-            raw = F.conv2d(n[:4](self._net_input(input, context)), n[4].weight, None, padding=1)
             a, b = self._scale_shift()
-            return ops.coupling_forward(input, raw, a, b)
+            return ops.coupling_forward(input, self._raw_train(input, context), a, b)
         x1, x2, log_s, t = self._params(input, context)
         return torch.cat([x1, x2 * torch.exp(log_s) + t], dim=1), log_s.flatten(start_dim=1).sum(-1)
 
@@ -335,6 +359,9 @@ class Coupling(FlowLayer):
             x = input.contiguous()
             a, b = self._scale_shift_cached()
             return ops.finc_coupling(x, self._raw_inference(x, context), a, b, -1, False)[0]
+        if self._hip_reverse_grad(input, context):
+            a, b = self._scale_shift()
+            return ops.coupling_reverse(input, self._raw_train(input, context), a, b)
         x1, x2, log_s, t = self._params(input, context)
         return torch.cat([x1, (x2 - t) * torch.exp(-log_s)], dim=1)
 

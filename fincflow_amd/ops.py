@@ -359,6 +359,28 @@ def finc_coupling_backward(grad_y, grad_logdet, x, raw, a, b, need_gx=True, need
     return gx, graw, ga, gb
 
 
+def finc_coupling_reverse_backward(grad_y, y, raw, a, b, need_gx=True, need_graw=True, need_ga=True, need_gb=True):
+    """Gradients of `finc_coupling(..., direction=-1)` (include/finc.h: finc_coupling_reverse_backward_f32), given grad_y [B,C,H,W]
+    and the reverse's OUTPUT `y`: (grad_x, grad_raw, grad_a, grad_b), each computed only if asked for (None otherwise).
+    grad_x[:, :C/2] is grad_y[:, :C/2]: what reaches that half through the net is the caller's (autograd's).  tanh and exp(-s) are
+    recomputed from `raw`; the per-channel sums run in a fixed order: the same inputs give the same bits."""
+    _coupling_args(y, raw, a, b, "output")
+    _require_device(grad_y, "grad_output")
+    if grad_y.shape != y.shape or grad_y.device != y.device:
+        raise ValueError("grad_output must match the reverse's output in shape and device")
+    B, C, H, W = y.shape
+    gx = torch.empty_like(y) if need_gx else None
+    graw = torch.empty_like(raw) if need_graw else None
+    ga = torch.empty(C, dtype=torch.float32, device=y.device) if need_ga else None
+    gb = torch.empty(C, dtype=torch.float32, device=y.device) if need_gb else None
+    if _nothing_to_launch(y, (gx, graw, ga, gb), (ga, gb)):
+        return gx, graw, ga, gb
+    nbytes = _lib.lib().finc_coupling_workspace_bytes(B, C, H * W) if (need_ga or need_gb) else None
+    _call("finc_coupling_reverse_backward_f32", y.device, grad_y.data_ptr(), y.data_ptr(), raw.data_ptr(), a.data_ptr(), b.data_ptr(),
+          _ptr(gx), _ptr(graw), _ptr(ga), _ptr(gb), B, C, H * W, *_ws_args(y.device, nbytes), _stream_ptr(y))
+    return gx, graw, ga, gb
+
+
 def _incoming_grads(like, grad_y, grad_logdet):
     """What a (y, logdet) Function's backward is handed, as the kernels take it: contiguous, zeros for a `y` nobody used (None)."""
     grad_y = torch.zeros_like(like) if grad_y is None else grad_y
@@ -388,6 +410,31 @@ def coupling_forward(x, raw, a, b):
     """`finc_coupling(x, raw, a, b, +1, want_logdet=True)` under autograd: returns (y, logdet), gradients for `x`, `raw`, `a` and
     `b`, each computed only where needed."""
     return _FincCouplingFunction.apply(x, raw, a, b)
+
+
+class _FincCouplingReverseFunction(torch.autograd.Function):
+    """`finc_coupling` in the reverse direction under autograd (inside `reverse_grad()`): y and its backward on the HIP kernels.  What
+    is saved is the OUTPUT y -- the tensor the next layer of a reverse chain keeps as its input anyway -- with raw, a and b."""
+
+    @staticmethod
+    def forward(ctx, x, raw, a, b):
+        x, raw, a, b = x.contiguous(), raw.contiguous(), a.contiguous(), b.contiguous()
+        y = finc_coupling(x, raw, a, b, -1, False)[0]
+        ctx.save_for_backward(y, raw, a, b)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        y, raw, a, b = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        return finc_coupling_reverse_backward(grad_y.contiguous(), y, raw, a, b,
+                                              need_gx=need[0], need_graw=need[1], need_ga=need[2], need_gb=need[3])
+
+
+def coupling_reverse(x, raw, a, b):
+    """`finc_coupling(x, raw, a, b, -1)[0]` under autograd: gradients for `x`, `raw`, `a` and `b`, each computed only where needed."""
+    return _FincCouplingReverseFunction.apply(x, raw, a, b)
 
 
 def finc_bias_relu(x, bias, out=None):
@@ -463,6 +510,26 @@ def finc_actnorm_backward(grad_y, grad_logdet, y, log_scale, need_gx=True, need_
     return gx, gls, gt
 
 
+def finc_actnorm_reverse_backward(grad_y, x, log_scale, need_gx=True, need_gls=True, need_gt=True):
+    """Gradients of `finc_actnorm(..., direction=-1)` (include/finc.h: finc_actnorm_reverse_backward_f32), given grad_y [B,C,H,W],
+    the reverse's INPUT `x` and log_scale: (grad_x, grad_log_scale, grad_translation), each computed only if asked for (None
+    otherwise).  The per-channel sums run in a fixed order: the same inputs give the same bits."""
+    _actnorm_args(x, log_scale, None)
+    _require_device(grad_y, "grad_output")
+    if grad_y.shape != x.shape or grad_y.device != x.device:
+        raise ValueError("grad_output must match the reverse's input in shape and device")
+    B, C, H, W = x.shape
+    gx = torch.empty_like(x) if need_gx else None
+    gls = torch.empty(C, dtype=torch.float32, device=x.device) if need_gls else None
+    gt = torch.empty(C, dtype=torch.float32, device=x.device) if need_gt else None
+    if _nothing_to_launch(x, (gx, gls, gt), (gls, gt)):
+        return gx, gls, gt
+    nbytes = _lib.lib().finc_actnorm_workspace_bytes(B, C, H * W) if (need_gls or need_gt) else None
+    _call("finc_actnorm_reverse_backward_f32", x.device, grad_y.data_ptr(), x.data_ptr(), log_scale.data_ptr(), _ptr(gx), _ptr(gls),
+          _ptr(gt), B, C, H * W, *_ws_args(x.device, nbytes), _stream_ptr(x))
+    return gx, gls, gt
+
+
 def finc_actnorm_init(x, log_scale, translation):
     """ActNorm's data-dependent initialisation (layers/actnorm.py:17-23) on the device, written IN PLACE into the two parameters:
     translation = per-channel mean of x, log_scale = log(unbiased std + 1e-8).  x [B,C,H,W] fp32 contiguous with B * H * W >= 2.
@@ -503,6 +570,32 @@ def actnorm_forward(x, log_scale, translation):
     """`finc_actnorm(x, log_scale, translation, +1, want_logdet=True)` under autograd: returns (y, logdet), gradients for `x`,
     `log_scale` and `translation`, each computed only where needed."""
     return _FincActNormFunction.apply(x, log_scale, translation)
+
+
+class _FincActNormReverseFunction(torch.autograd.Function):
+    """`finc_actnorm` in the reverse direction under autograd (inside `reverse_grad()`): y and its backward on the HIP kernels.  What
+    is saved is the INPUT x and log_scale: grad_log_scale from the output would be a sum over grad_y * (y - translation), which
+    cancels on a channel whose translation dwarfs its spread."""
+
+    @staticmethod
+    def forward(ctx, x, log_scale, translation):
+        x, log_scale, translation = x.contiguous(), log_scale.contiguous(), translation.contiguous()
+        y = finc_actnorm(x, log_scale, translation, -1)[0]
+        ctx.save_for_backward(x, log_scale)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        x, log_scale = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        return finc_actnorm_reverse_backward(grad_y.contiguous(), x, log_scale, need_gx=need[0], need_gls=need[1], need_gt=need[2])
+
+
+def actnorm_reverse(x, log_scale, translation):
+    """`finc_actnorm(x, log_scale, translation, -1)[0]` under autograd: gradients for `x`, `log_scale` and `translation`, each
+    computed only where needed."""
+    return _FincActNormReverseFunction.apply(x, log_scale, translation)
 
 
 def inverse(input, kernel, output):

@@ -315,6 +315,14 @@ int finc_mix_backward_f32(const float *grad_out, const float *in, const float *m
  *     grad_raw[:, c] = a[c] * grad_h[:, c],   grad_a[c] = sum_{b,p} grad_h[b,c,p] * raw[b,c,p],   grad_b[c] = sum_{b,p} grad_h[b,c,p]
  *   Every output is OVERWRITTEN; any may be NULL to skip it, not all of them.  grad_a / grad_b need the workspace (same size, same
  *   fixed-order sums).  The outputs may alias no input and not each other (FINC_ERR_BAD_DIMS).
+ * finc_coupling_reverse_backward_f32: the gradients of direction -1 (replaces autograd through layers/coupling.py:95-101 and :38-40),
+ *   given grad_y and `y`, the reverse's OUTPUT (y2 = (x2 - t) * E with E = exp(-s): d y2 / d s = -y2, so the input is not needed, and
+ *   in a recorded reverse chain y is what the next layer keeps anyway); th = tanh(u / 2) and E are recomputed from raw:
+ *     grad_x[:, :half] = grad_y[:, :half]  (what reaches x[:, :half] through the net is the caller's, as in the forward direction)
+ *     grad_x[:, half+j] = grad_y2 * E_j                         with grad_y2 = grad_y[:, half+j]
+ *     grad_h[:, 2j+1] = -grad_y2 * E_j,   grad_h[:, 2j] = -(grad_y2 * y[:, half+j]) * (1 - th_j^2)
+ *     grad_raw[:, c] = a[c] * grad_h[:, c],   grad_a[c] = sum_{b,p} grad_h[b,c,p] * raw[b,c,p],   grad_b[c] = sum_{b,p} grad_h[b,c,p]
+ *   There is no log-det in this direction.  Outputs, workspace, aliasing and status as for finc_coupling_backward_f32.
  * finc_bias_relu_f32: out = max(in + bias[c], 0) -- the Conv2d bias and the nn.ReLU behind the net's first two convolutions
  *   (layers/coupling.py:58-63) in one pass; in == out allowed.  Inference only (no backward).
  * Rows of HW floats move as 16-byte pieces when HW % 4 == 0 and every activation pointer is 16-byte aligned, as dwords otherwise.
@@ -328,6 +336,9 @@ int finc_coupling_f32(const float *x, const float *raw, const float *a, const fl
 int finc_coupling_backward_f32(const float *grad_y, const float *grad_logdet, const float *x, const float *raw, const float *a,
                                const float *b, float *grad_x, float *grad_raw, float *grad_a, float *grad_b, int B, int C, int HW,
                                void *workspace, size_t workspace_bytes, finc_stream_t stream);
+int finc_coupling_reverse_backward_f32(const float *grad_y, const float *y, const float *raw, const float *a, const float *b,
+                                       float *grad_x, float *grad_raw, float *grad_a, float *grad_b, int B, int C, int HW,
+                                       void *workspace, size_t workspace_bytes, finc_stream_t stream);
 int finc_bias_relu_f32(const float *in, const float *bias, float *out, int B, int C, int HW, finc_stream_t stream);
 
 /*
@@ -344,6 +355,13 @@ int finc_bias_relu_f32(const float *in, const float *bias, float *out, int B, in
  *     grad_log_scale[c]   = -sum_{b,p} grad_y[b,c,p] * y[b,c,p]  -  HW * sum_b grad_logdet[b]
  *   Every output is OVERWRITTEN; any may be NULL to skip it, not all of them.  grad_x == grad_y allowed, grad_x == y is not
  *   (FINC_ERR_BAD_DIMS).  The two per-channel outputs need the workspace; their sums run in a fixed order (no atomics).
+ * finc_actnorm_reverse_backward_f32: gradients of the reverse direction (replaces autograd through layers/actnorm.py:47-52) from
+ *   grad_y, log_scale and `x`, the reverse's INPUT (the output would do in real arithmetic, x * exp(log_scale) = y - translation, but
+ *   that difference cancels on a channel whose translation dwarfs its spread):
+ *     grad_x[b,c,p]       = grad_y[b,c,p] * exp(log_scale[c])
+ *     grad_log_scale[c]   = exp(log_scale[c]) * sum_{b,p} grad_y[b,c,p] * x[b,c,p]
+ *     grad_translation[c] = sum_{b,p} grad_y[b,c,p]
+ *   Outputs, workspace and status as for finc_actnorm_backward_f32; grad_x == grad_y allowed, grad_x == x is not.
  * finc_actnorm_init_f32: the data-dependent initialisation (:17-23) written straight into the parameters, no host round trip:
  *   translation[c] = mean over (b, p), log_scale[c] = log(std + 1e-8) with the UNBIASED standard deviation (divisor n - 1,
  *   n = B * HW; torch.std's default), one pass over x on (n, mean, M2) triples merged pairwise in a fixed order.  n < 2 is
@@ -353,7 +371,7 @@ int finc_bias_relu_f32(const float *in, const float *bias, float *out, int B, in
  * Rows of HW floats move as 16-byte pieces when HW % 4 == 0 and every activation pointer is 16-byte aligned, as dwords otherwise.
  * Status: a NULL required pointer FINC_ERR_NULL_POINTER; non-positive / overflowing dims, a direction other than +1 / -1 or
  * forbidden aliasing FINC_ERR_BAD_DIMS; a pointer not 4-byte aligned FINC_ERR_ALIGNMENT; a missing / short workspace where one is
- * needed FINC_ERR_WORKSPACE -- checked in that order, before any HIP call.  The three launching calls take part in the
+ * needed FINC_ERR_WORKSPACE -- checked in that order, before any HIP call.  The four launching calls take part in the
  * sticky-fault rule below like every other.
  */
 size_t finc_actnorm_workspace_bytes(int B, int C, int HW);
@@ -362,6 +380,9 @@ int finc_actnorm_f32(const float *x, const float *log_scale, const float *transl
 int finc_actnorm_backward_f32(const float *grad_y, const float *grad_logdet, const float *y, const float *log_scale, float *grad_x,
                               float *grad_log_scale, float *grad_translation, int B, int C, int HW, void *workspace,
                               size_t workspace_bytes, finc_stream_t stream);
+int finc_actnorm_reverse_backward_f32(const float *grad_y, const float *x, const float *log_scale, float *grad_x, float *grad_log_scale,
+                                      float *grad_translation, int B, int C, int HW, void *workspace, size_t workspace_bytes,
+                                      finc_stream_t stream);
 int finc_actnorm_init_f32(const float *x, float *log_scale, float *translation, int B, int C, int HW, void *workspace,
                           size_t workspace_bytes, finc_stream_t stream);
 
