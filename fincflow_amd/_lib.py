@@ -38,6 +38,7 @@ SYMBOLS = [
     "finc_adjoint_weights_f32", "finc_lead_product_f32", "finc_negate_f32", "finc_inverse_backward_workspace_bytes",
     "finc_inverse_backward_f32",
     "finc_coupling_reverse_backward_f32", "finc_actnorm_reverse_backward_f32",
+    "finc_coupling_reverse_logdet_f32", "finc_coupling_reverse_logdet_backward_f32",
 ]
 
 #: the ABI version this binding is written against (include/finc.h: finc_version)
@@ -51,6 +52,9 @@ INVERSE_BACKWARD_ABI_VERSION = 107
 #: the version that added the backwards of the per-pixel layers' reverse direction (finc_coupling_reverse_backward_f32,
 #: finc_actnorm_reverse_backward_f32)
 REVERSE_BACKWARD_ABI_VERSION = 108
+#: the version that added the coupling's reverse with its log-det and the backward of that (finc_coupling_reverse_logdet_f32,
+#: finc_coupling_reverse_logdet_backward_f32): what sample_with_log_prob / rsample_with_log_prob launch
+SAMPLE_LOGDET_ABI_VERSION = 109
 
 _lib = None
 
@@ -90,6 +94,11 @@ def lib():
         raise FincError(f"{LIB_PATH} reports finc_version() = {have}, the backwards of the reverse direction "
                         f"(finc_coupling_reverse_backward_f32, finc_actnorm_reverse_backward_f32) came with "
                         f"{REVERSE_BACKWARD_ABI_VERSION}: rebuild it "
+                        "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
+    if have < SAMPLE_LOGDET_ABI_VERSION:
+        raise FincError(f"{LIB_PATH} reports finc_version() = {have}, the coupling's reverse with its log-det "
+                        f"(finc_coupling_reverse_logdet_f32, finc_coupling_reverse_logdet_backward_f32) came with "
+                        f"{SAMPLE_LOGDET_ABI_VERSION}: rebuild it "
                         "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
     L.finc_build_flags.restype = u
     L.finc_clear_fault.restype = i
@@ -164,6 +173,8 @@ def lib():
     L.finc_inverse_backward_f32.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, u, vp, sz, vp]
     L.finc_coupling_reverse_backward_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp]
     L.finc_actnorm_reverse_backward_f32.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp]
+    L.finc_coupling_reverse_logdet_f32.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp]
+    L.finc_coupling_reverse_logdet_backward_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp]
     for name in SYMBOLS:
         getattr(L, name)  # AttributeError here = header and library out of sync
     _lib = L

@@ -189,7 +189,7 @@ static int canonicalize(const T *w_stored, T *w_canon, int G, int Cq, int KH, in
 
 extern "C" {
 
-int finc_version(void) { return 108; }
+int finc_version(void) { return 109; }
 
 unsigned finc_build_flags(void)
 {
@@ -644,8 +644,39 @@ int finc_coupling_reverse_backward_f32(const float *grad_y, const float *y, cons
     if ((grad_a || grad_b) && workspace_short(workspace, workspace_bytes, finc_coupling_workspace_bytes(B, C, HW)))
         return FINC_ERR_WORKSPACE;
     if (int e = finc_fault_gate(false)) return e;
-    return finc_coupling_reverse_backward_launch(grad_y, y, raw, a, b, grad_x, grad_raw, grad_a, grad_b, B, C, HW, (float *)workspace,
-                                                 (hipStream_t)stream);
+    return finc_coupling_reverse_backward_launch(grad_y, nullptr, y, raw, a, b, grad_x, grad_raw, grad_a, grad_b, B, C, HW,
+                                                 (float *)workspace, (hipStream_t)stream);
+}
+
+int finc_coupling_reverse_logdet_f32(const float *x, const float *raw, const float *a, const float *b, float *y, float *logdet, int B,
+                                     int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    if (!x || !raw || !a || !b || !y || !logdet) return FINC_ERR_NULL_POINTER;
+    if (int e = pixel_dims(B, C, HW, true)) return e;
+    if (y == raw) return FINC_ERR_BAD_DIMS;
+    if (misaligned(x, raw, a, b, y, logdet)) return FINC_ERR_ALIGNMENT;
+    if (!finc_coupling_supported_f32(C)) return FINC_ERR_UNSUPPORTED;
+    if (workspace_short(workspace, workspace_bytes, finc_coupling_workspace_bytes(B, C, HW))) return FINC_ERR_WORKSPACE;
+    if (int e = finc_fault_gate(false)) return e;
+    return finc_coupling_reverse_logdet_launch(x, raw, a, b, y, logdet, B, C, HW, (float *)workspace, (hipStream_t)stream);
+}
+
+int finc_coupling_reverse_logdet_backward_f32(const float *grad_y, const float *grad_logdet, const float *y, const float *raw,
+                                              const float *a, const float *b, float *grad_x, float *grad_raw, float *grad_a,
+                                              float *grad_b, int B, int C, int HW, void *workspace, size_t workspace_bytes,
+                                              finc_stream_t stream)
+{
+    if (!grad_y || !y || !raw || !a || !b || (!grad_x && !grad_raw && !grad_a && !grad_b)) return FINC_ERR_NULL_POINTER;
+    if (int e = pixel_dims(B, C, HW, true)) return e;
+    if (grad_x && (grad_x == grad_y || grad_x == y || grad_x == raw)) return FINC_ERR_BAD_DIMS;
+    if (grad_raw && (grad_raw == grad_y || grad_raw == y || grad_raw == raw || grad_raw == grad_x)) return FINC_ERR_BAD_DIMS;
+    if (misaligned(grad_y, grad_logdet, y, raw, a, b, grad_x, grad_raw, grad_a, grad_b)) return FINC_ERR_ALIGNMENT;
+    if (!finc_coupling_supported_f32(C)) return FINC_ERR_UNSUPPORTED;
+    if ((grad_a || grad_b) && workspace_short(workspace, workspace_bytes, finc_coupling_workspace_bytes(B, C, HW)))
+        return FINC_ERR_WORKSPACE;
+    if (int e = finc_fault_gate(false)) return e;
+    return finc_coupling_reverse_backward_launch(grad_y, grad_logdet, y, raw, a, b, grad_x, grad_raw, grad_a, grad_b, B, C, HW,
+                                                 (float *)workspace, (hipStream_t)stream);
 }
 
 int finc_bias_relu_f32(const float *in, const float *bias, float *out, int B, int C, int HW, finc_stream_t stream)

@@ -265,9 +265,13 @@ int finc_coupling_launch(const float *x, const float *raw, const float *a, const
                          int direction, float *ws, hipStream_t st);
 int finc_coupling_backward_launch(const float *gy, const float *gld, const float *x, const float *raw, const float *a, const float *b,
                                   float *gx, float *graw, float *ga, float *gb, int B, int C, int HW, float *ws, hipStream_t st);
-// the backward of direction -1, from the reverse's OUTPUT y
-int finc_coupling_reverse_backward_launch(const float *gy, const float *y, const float *raw, const float *a, const float *b, float *gx,
-                                          float *graw, float *ga, float *gb, int B, int C, int HW, float *ws, hipStream_t st);
+// direction -1 with logdet[b] = sum s, the FORWARD map's log-det at the recovered input (always summed: `ws` and `logdet` required)
+int finc_coupling_reverse_logdet_launch(const float *x, const float *raw, const float *a, const float *b, float *y, float *logdet, int B,
+                                        int C, int HW, float *ws, hipStream_t st);
+// the backward of direction -1, from the reverse's OUTPUT y; gld: the gradient of that log-det per image, or nullptr
+int finc_coupling_reverse_backward_launch(const float *gy, const float *gld, const float *y, const float *raw, const float *a,
+                                          const float *b, float *gx, float *graw, float *ga, float *gb, int B, int C, int HW, float *ws,
+                                          hipStream_t st);
 int finc_bias_relu_launch(const float *in, const float *bias, float *out, int B, int C, int HW, hipStream_t st);
 // ---- ActNorm (transform + log-det, its backward from the forward's OUTPUT, the data-dependent initialisation): finc_actnorm.h, same object ----
 // `ws` holds finc_actnorm_workspace_floats floats (backward with gls / gt, and the initialisation)

@@ -10,6 +10,8 @@
 //                               forward and two reads here, and this kernel is bound by its memory traffic, not by the VALU.
 //   * finc_coupling_rev_bwd_kernel  the same for the reverse direction, from the reverse's OUTPUT (what `reverse` under autograd
 //                               records inside ops.reverse_grad()).
+//   * finc_coupling_rev_logdet_kernel  the reverse pass that also sums s per image: the sample and the forward log-det at the
+//                               sample in one pass (FlowSequential.sample_with_log_prob / rsample_with_log_prob).
 //   * finc_bias_relu_kernel     out = max(in + bias[c], 0), in place or not.
 // Layout: x, y [B][C][HW] fp32, raw [B][C][HW] with channel 2j = u_j (pre-activation of the log-scale) and 2j+1 = t_j (translation).
 // A thread owns V consecutive pixels of one channel pair j: V = 4 (16-byte pieces) when HW % 4 == 0 and every pointer is 16-byte
@@ -67,10 +69,13 @@ __device__ inline void cpl_block_sum(float (&v)[N], float (*sm)[4])
 
 // Workgroup = (image, part): P parts per image share its half * HW / V thread items.  DIR +1 forward, -1 reverse.
 // y == x is allowed (a thread reads its pieces before it writes them, and nobody else touches them).
+// LOGDET: the workgroup's partial of sum s goes to part[blockIdx.x], in EITHER direction: what is summed is the FORWARD map's log-det,
+// sum_{j,p} s_j -- in the reverse direction that is the log-det of Coupling.forward at the recovered input y (s depends on the
+// untouched half only, which both directions share); the reverse map's own Jacobian is its negative.
 template <int V, int DIR, bool LOGDET>
-__global__ __launch_bounds__(CPL_THREADS) void finc_coupling_kernel(const float *x, const float *__restrict__ raw,
-                                                                    const float *__restrict__ a, const float *__restrict__ b, float *y,
-                                                                    float *__restrict__ part, int half, int HW, int nv, int items, int P)
+__device__ __forceinline__ void cpl_transform(const float *x, const float *__restrict__ raw, const float *__restrict__ a,
+                                              const float *__restrict__ b, float *y, float *__restrict__ part, int half, int HW, int nv,
+                                              int items, int P)
 {
     const int img = (int)blockIdx.x / P, pi = (int)blockIdx.x - img * P;
     const size_t ibase = (size_t)img * (size_t)(2 * half) * (size_t)HW;
@@ -94,6 +99,7 @@ __global__ __launch_bounds__(CPL_THREADS) void finc_coupling_kernel(const float 
                 if constexpr (LOGDET) ls[0] += s;
             } else {
                 y2[e] = (x2[e] - tr) * expf(-s);
+                if constexpr (LOGDET) ls[0] += s;
             }
         }
         cpl_store<V>(y + o1, x1);
@@ -104,6 +110,25 @@ __global__ __launch_bounds__(CPL_THREADS) void finc_coupling_kernel(const float 
         cpl_block_sum<1>(ls, sm);
         if (threadIdx.x == 0) part[blockIdx.x] = ls[0];
     }
+}
+
+template <int V, int DIR, bool LOGDET>
+__global__ __launch_bounds__(CPL_THREADS) void finc_coupling_kernel(const float *x, const float *__restrict__ raw,
+                                                                    const float *__restrict__ a, const float *__restrict__ b, float *y,
+                                                                    float *__restrict__ part, int half, int HW, int nv, int items, int P)
+{
+    cpl_transform<V, DIR, LOGDET>(x, raw, a, b, y, part, half, HW, nv, items, P);
+}
+
+// The reverse direction WITH the log-det partials (sampling with its log-density): cpl_transform<V, -1, true> under a name of its
+// own, so that the six instantiations of finc_coupling_kernel stay the six they were.
+template <int V>
+__global__ __launch_bounds__(CPL_THREADS) void finc_coupling_rev_logdet_kernel(const float *x, const float *__restrict__ raw,
+                                                                               const float *__restrict__ a, const float *__restrict__ b,
+                                                                               float *y, float *__restrict__ part, int half, int HW, int nv,
+                                                                               int items, int P)
+{
+    cpl_transform<V, -1, true>(x, raw, a, b, y, part, half, HW, nv, items, P);
 }
 
 // Workgroup = (channel pair j, part): Q parts per pair share its B * HW / V thread items, so the four per-channel sums of a
@@ -164,13 +189,16 @@ __global__ __launch_bounds__(CPL_THREADS) void finc_coupling_bwd_kernel(const fl
 
 // The backward of the REVERSE direction, y2 = (x2 - t) * exp(-s) (layers/coupling.py:95-101), from grad_y and the reverse's OUTPUT y:
 // d y2 / d x2 = E = exp(-s), d y2 / d t = -E, d y2 / d s = -y2, so the input is not needed (in a recorded reverse chain y is the tensor
-// the next layer keeps anyway).  Workgroups, partials and the nullptr rules as in finc_coupling_bwd_kernel; no log-det in this direction.
+// the next layer keeps anyway).  Workgroups, partials and the nullptr rules as in finc_coupling_bwd_kernel.  gld: the gradient of the
+// log-det finc_coupling_rev_logdet_kernel reports (sum s, per image), d / d s = gld[img]; nullptr = none, and then every result has the
+// bits it had before this argument existed (the neutral element below is -0: v + -0 is v for every v, -0 included).
 template <int V>
-__global__ __launch_bounds__(CPL_THREADS) void finc_coupling_rev_bwd_kernel(const float *__restrict__ gy, const float *__restrict__ y,
-                                                                            const float *__restrict__ raw, const float *__restrict__ a,
-                                                                            const float *__restrict__ b, float *__restrict__ gx,
-                                                                            float *__restrict__ graw, float *__restrict__ part, int half,
-                                                                            int HW, int nv, int items, int Q, int sums)
+__global__ __launch_bounds__(CPL_THREADS) void finc_coupling_rev_bwd_kernel(const float *__restrict__ gy, const float *__restrict__ gld,
+                                                                            const float *__restrict__ y, const float *__restrict__ raw,
+                                                                            const float *__restrict__ a, const float *__restrict__ b,
+                                                                            float *__restrict__ gx, float *__restrict__ graw,
+                                                                            float *__restrict__ part, int half, int HW, int nv, int items,
+                                                                            int Q, int sums)
 {
     const int j = (int)blockIdx.x / Q, qi = (int)blockIdx.x - j * Q;
     const float au = a[2 * j], bu = b[2 * j], at = a[2 * j + 1];
@@ -186,11 +214,12 @@ __global__ __launch_bounds__(CPL_THREADS) void finc_coupling_rev_bwd_kernel(cons
         cpl_load<V>(y2, y + o2);
         cpl_load<V>(u, raw + ou);
         if (sums) cpl_load<V>(t, raw + ot);
+        const float gl = gld ? gld[img] : -0.f;
 #pragma unroll
         for (int e = 0; e < V; ++e) {
             const float th = tanhf(0.5f * fmaf(au, u[e], bu));     // s = 2 th, d s / d h = 1 - th*th
             gx2[e] = g2[e] * expf(-2.f * th);
-            const float ghu = -(g2[e] * y2[e]) * fmaf(-th, th, 1.f), ght = -gx2[e];
+            const float ghu = (-(g2[e] * y2[e]) + gl) * fmaf(-th, th, 1.f), ght = -gx2[e];
             gu[e] = au * ghu;
             gt[e] = at * ght;
             if (sums) {
@@ -316,6 +345,25 @@ int finc_coupling_launch(const float *x, const float *raw, const float *a, const
     return FINC_OK;
 }
 
+// The reverse direction with the forward map's log-det of the recovered input: the grid, the parts and the reduce of the forward
+// direction with its log-det (B x P partials: the forward bound of finc_coupling_workspace_floats covers them).
+int finc_coupling_reverse_logdet_launch(const float *x, const float *raw, const float *a, const float *b, float *y, float *logdet, int B,
+                                        int C, int HW, float *ws, hipStream_t st)
+{
+    const int half = C / 2;
+    if ((size_t)C * HW * 4 >= ((size_t)1 << 31)) return FINC_ERR_BAD_DIMS;
+    const bool wide = cpl_wide(HW, (uintptr_t)x | (uintptr_t)raw | (uintptr_t)y);
+    const int nv = HW / (wide ? 4 : 1), items = half * nv, P = cpl_parts(items, B);
+    if ((long long)B * P >= (1LL << 31)) return FINC_ERR_BAD_DIMS;
+    const dim3 grid((unsigned)((long long)B * P)), block(CPL_THREADS);
+    hipLaunchKernelGGL(wide ? finc_coupling_rev_logdet_kernel<4> : finc_coupling_rev_logdet_kernel<1>, grid, block, 0, st, x, raw, a, b, y,
+                       ws, half, HW, nv, items, P);
+    FINC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(finc_coupling_reduce_kernel, dim3((unsigned)B), dim3(64), 0, st, (const float *)ws, P, logdet, (float *)nullptr, 0);
+    FINC_CHECK_LAUNCH();
+    return FINC_OK;
+}
+
 int finc_coupling_backward_launch(const float *gy, const float *gld, const float *x, const float *raw, const float *a, const float *b,
                                   float *gx, float *graw, float *ga, float *gb, int B, int C, int HW, float *ws, hipStream_t st)
 {
@@ -334,16 +382,18 @@ int finc_coupling_backward_launch(const float *gy, const float *gld, const float
     return FINC_OK;
 }
 
-int finc_coupling_reverse_backward_launch(const float *gy, const float *y, const float *raw, const float *a, const float *b, float *gx,
-                                          float *graw, float *ga, float *gb, int B, int C, int HW, float *ws, hipStream_t st)
+// gld: the gradient of the reverse's log-det output (finc_coupling_reverse_logdet_launch), or nullptr (the plain reverse)
+int finc_coupling_reverse_backward_launch(const float *gy, const float *gld, const float *y, const float *raw, const float *a,
+                                          const float *b, float *gx, float *graw, float *ga, float *gb, int B, int C, int HW, float *ws,
+                                          hipStream_t st)
 {
     const int half = C / 2, sums = (ga || gb) ? 1 : 0;
     if (!cpl_rows_fit(B, C, HW)) return FINC_ERR_BAD_DIMS;
     const bool wide = cpl_wide(HW, (uintptr_t)gy | (uintptr_t)y | (uintptr_t)raw | (uintptr_t)gx | (uintptr_t)graw);
     const int nv = HW / (wide ? 4 : 1), items = B * nv, Q = cpl_parts(items, half);
     const dim3 grid((unsigned)((long long)half * Q)), block(CPL_THREADS);
-    hipLaunchKernelGGL(wide ? finc_coupling_rev_bwd_kernel<4> : finc_coupling_rev_bwd_kernel<1>, grid, block, 0, st, gy, y, raw, a, b, gx,
-                       graw, ws, half, HW, nv, items, Q, sums);
+    hipLaunchKernelGGL(wide ? finc_coupling_rev_bwd_kernel<4> : finc_coupling_rev_bwd_kernel<1>, grid, block, 0, st, gy, gld, y, raw, a, b,
+                       gx, graw, ws, half, HW, nv, items, Q, sums);
     FINC_CHECK_LAUNCH();
     if (sums) {
         hipLaunchKernelGGL(finc_coupling_reduce_kernel, dim3((unsigned)(4 * half)), dim3(64), 0, st, (const float *)ws, Q, ga, gb, 1);

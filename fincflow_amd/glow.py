@@ -4,7 +4,9 @@ forward -> (out, logdet[B]) / reverse -> out protocol, so that `create_model` be
 fastflow/fastflow_cifar.py:35-63 around fincflow_amd.FastFlowUnit.  ActNorm, Conv1x1 and the coupling's transform run on HIP
 kernels of their own (ops.finc_actnorm, ops.finc_mix, ops.finc_coupling), in inference and under autograd -- `forward` always,
 `reverse` inside `ops.reverse_grad()` (what `FlowSequential.rsample` records: ops.actnorm_reverse, ops.mix_forward on W^-1,
-ops.coupling_reverse); `reverse` under autograd outside that context keeps its PyTorch lines.  The coupling net's
+ops.coupling_reverse); `reverse` under autograd outside that context keeps its PyTorch lines.  `reverse_with_logdet` is `reverse`
+plus the forward log-det at its result from the same pass (ops.finc_coupling_reverse_logdet, ops.coupling_reverse_logdet; parameters
+only for ActNorm and Conv1x1): what `FlowSequential.sample_with_log_prob` / `rsample_with_log_prob` add up.  The coupling net's
 convolutions, Squeeze and the preprocessing layers are ops that PyTorch-ROCm already runs.  The point of this file is that a
 whole sampling pass (96 units at 16x16 / 8x8 / 4x4) can run and be captured in one HIP graph.
 
@@ -41,6 +43,9 @@ class Squeeze(FlowLayer):
         b, c, h, w = input.shape
         x = input.reshape(b, c // 4, 2, 2, h, w).permute(0, 1, 4, 2, 5, 3)
         return x.reshape(b, c // 4, h * 2, w * 2)
+
+    def reverse_with_logdet(self, input, context=None):
+        return self.reverse(input, context), input.new_zeros(len(input))
 
     def logdet(self, input, context=None):
         return input.new_zeros(len(input))
@@ -128,6 +133,12 @@ class ActNorm(FlowLayer):
         t, ls = self._shaped(input)
         return input * torch.exp(ls) + t
 
+    def reverse_with_logdet(self, input, context=None):
+        """`reverse` and the forward log-det at its result: parameters only (`logdet`: a few [C]-sized ops, recorded when a graph is),
+        no kernel of its own."""
+        out = self.reverse(input, context)
+        return out, self.logdet(out, context)
+
     def forward_affine_params(self):
         """forward(x) = (x - translation) * exp(-log_scale): what FlowSequential folds into the FastFlowUnit in front of
         this layer (only once the data-dependent initialisation has happened)."""
@@ -198,6 +209,27 @@ class Conv1x1(FlowLayer):
         if self._hip_reverse_grad(z):
             return ops.mix_forward(z, w_inv)
         return F.conv2d(z, w_inv.view(self.n_channels, self.n_channels, 1, 1))
+
+    def _log_abs_det(self):
+        """log|det W|, 0-dim: recorded (`torch.slogdet`) while autograd records through W; otherwise cached per weight version, as
+        `_inverse_matrix` is, so that a no-grad sampling pass has no LU factorisation (and no host sync) in it."""
+        if torch.is_grad_enabled() and self.W.requires_grad:
+            return torch.slogdet(self.W)[1]
+        key = ops.version_key(self.W) + (self.W.device,)
+        if getattr(self, "_ld_key", None) != key:
+            with torch.no_grad():
+                self._ld = torch.slogdet(self.W.detach())[1]
+            self._ld_key = key
+        return self._ld
+
+    def mix_logdet(self, x):
+        """The layer's forward log-det for activations shaped like `x`, [B]: h * w * log|det W| (the same in and out of the layer)."""
+        h, w = x.shape[2:]
+        return (h * w * self._log_abs_det()).expand(len(x))
+
+    def reverse_with_logdet(self, z, context=None):
+        out = self.reverse(z, context)
+        return out, self.mix_logdet(out)
 
     def reverse_then_affine(self, z, log_scale, translation):
         """exp(log_scale) * reverse(z) + translation in ONE launch: the ActNorm that precedes this layer in
@@ -365,6 +397,20 @@ class Coupling(FlowLayer):
         x1, x2, log_s, t = self._params(input, context)
         return torch.cat([x1, (x2 - t) * torch.exp(-log_s)], dim=1)
 
+    def reverse_with_logdet(self, input, context=None):
+        """`reverse` with the forward log-det at its result, sum s per image, from the same pass (s depends on the untouched half
+        only): the three branches of `reverse`, on `ops.finc_coupling_reverse_logdet` / `ops.coupling_reverse_logdet` (backward:
+        finc_coupling_reverse_logdet_backward_f32) where that one launches the HIP kernel."""
+        if self._hip(input, context):
+            x = input.contiguous()
+            a, b = self._scale_shift_cached()
+            return ops.finc_coupling_reverse_logdet(x, self._raw_inference(x, context), a, b)
+        if self._hip_reverse_grad(input, context):
+            a, b = self._scale_shift()
+            return ops.coupling_reverse_logdet(input, self._raw_train(input, context), a, b)
+        x1, x2, log_s, t = self._params(input, context)
+        return torch.cat([x1, (x2 - t) * torch.exp(-log_s)], dim=1), log_s.flatten(start_dim=1).sum(-1)
+
     def logdet(self, input, context=None):
         return self.forward(input, context)[1]
 
@@ -407,6 +453,12 @@ class SplitPrior(FlowLayer):
         x2, _ = self.base.sample(input.shape[0], context)
         return self.transform.reverse(torch.cat([input, x2], dim=1), context)
 
+    def reverse_with_logdet(self, input, context=None):
+        """Mirrors `forward`: the drawn half's density under the base plus the coupling's log-det."""
+        x2, _ = self.base.sample(input.shape[0], context)
+        out, ldj = self.transform.reverse_with_logdet(torch.cat([input, x2], dim=1), context)
+        return out, self.base.log_prob(x2) + ldj
+
     def logdet(self, input, context=None):
         return self.forward(input, context)[1]
 
@@ -427,6 +479,10 @@ class Normalization(FlowLayer):
     def reverse(self, input, context=None):
         return input * self.scale + self.translation
 
+    def reverse_with_logdet(self, input, context=None):
+        out = self.reverse(input, context)
+        return out, self.logdet(out, context)
+
     def logdet(self, input, context=None):
         n, c, h, w = input.shape
         return (-c * h * w * torch.log(self.scale)).expand(n)
@@ -438,6 +494,10 @@ class LogitTransform(FlowLayer):
 
     def reverse(self, input, context=None):
         return torch.sigmoid(input)
+
+    def reverse_with_logdet(self, input, context=None):
+        out = self.reverse(input, context)
+        return out, self.logdet(out, context)
 
     def logdet(self, input, context=None):
         return (-torch.log(input) - torch.log(1 - input)).flatten(start_dim=1).sum(-1)
@@ -455,6 +515,11 @@ class Dequantization(FlowLayer):
 
     def reverse(self, input, context=None):
         return input.floor()
+
+    def reverse_with_logdet(self, input, context=None):
+        """`floor` and zeros, as `forward` reports zero: the density a sampler carries through this layer is the CONTINUOUS one of
+        the variable in front of the floor, not a probability mass of the integer result."""
+        return input.floor(), input.new_zeros(len(input), dtype=torch.float32)
 
     def logdet(self, input, context=None):
         raise NotImplementedError

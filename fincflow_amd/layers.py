@@ -29,6 +29,13 @@ def _records_graph(x, *params):
     return torch.is_grad_enabled() and (x.requires_grad or any(p is not None and p.requires_grad for p in params))
 
 
+def _per_image_logdet(logdet, out):
+    """A layer's log-det as a [B] tensor beside `out`: a Python number or a 0-dim tensor (the same for every image) is broadcast."""
+    if not torch.is_tensor(logdet):
+        return out.new_full((len(out),), float(logdet))
+    return logdet.expand(len(out)) if logdet.dim() == 0 else logdet
+
+
 class FlowLayer(nn.Module, metaclass=ABCMeta):
     """layers/flowlayer.py:8-30."""
 
@@ -43,6 +50,15 @@ class FlowLayer(nn.Module, metaclass=ABCMeta):
     @abstractmethod
     def logdet(self, input, context=None):
         pass
+
+    def reverse_with_logdet(self, input, context=None):
+        """`(out, logdet[B])`: `out` is what `reverse(input, context)` returns on the same path, `logdet` what
+        `forward(out, context)[1]` returns -- the FORWARD map's log-det at the recovered input, so that a sampler adds it to the base
+        density: log q(x) = log p(z) + sum over the layers.  Every layer of this package overrides it with a form that costs no second
+        pass; this default is for a layer from elsewhere (one `forward` more)."""
+        out = self.reverse(input, context)
+        out = out[0] if isinstance(out, tuple) else out
+        return out, _per_image_logdet(self.forward(out, context)[1], out)
 
     def reconstruct_forward(self, input, context=None):
         return self.forward(input)
@@ -145,6 +161,11 @@ class PaddedConv2d(FlowLayer):
             y = self._cache.inverse(x.contiguous(), *self._cache_args())
         return y, 0
 
+    def reverse_with_logdet(self, x, context=None):
+        """`reverse(x)[0]` and the layer's log-det per image: zeros (unit-triangular)."""
+        out = self.reverse(x, context)[0]
+        return out, out.new_zeros(len(out))
+
     def logdet(self, x=None, context=None):
         return 0.0
 
@@ -183,6 +204,11 @@ class FastFlowUnit(nn.Module):
 
     def reverse(self, x, context=None):
         return self.reverse_level2(x)
+
+    def reverse_with_logdet(self, x, context=None):
+        """`reverse(x)` and the unit's log-det per image: zeros (four unit-triangular banks)."""
+        out = self.reverse(x, context)
+        return out, out.new_zeros(len(out))
 
     def reverse_level2(self, x):
         """fastflow.py:78-100 without the 6 flip/cat/zeros copies: the kernel indexes the flipped pixel."""
@@ -249,6 +275,10 @@ class CINCFlowUnit(nn.Module):
 
     def reverse(self, x, context=None):
         return self.reverse_level1(x)
+
+    def reverse_with_logdet(self, x, context=None):
+        out = self.reverse(x, context)
+        return out, out.new_zeros(len(out))
 
     def reverse_level1(self, x):
         return self.conv_tl.reverse(x)[0]
@@ -366,9 +396,14 @@ class FlowSequential(nn.Module):
     #: let the channel mix in front of a FastFlowUnit (reverse chain) apply the unit's blockdiag(Linv) as well
     fuse_lead = True
 
-    def _reverse_chain(self, input, context, fuse=None):
+    def _reverse_chain(self, input, context, fuse=None, with_logdet=False):
+        """The layers' reverses, last layer first.  `with_logdet`: returns `(x, logdet[B])`, the sum of the layers' FORWARD log-dets
+        at their recovered inputs (`reverse_with_logdet`), in the same pass: every fold below stays, and a folded per-channel affine
+        layer or channel mix adds its term -- parameters only, a few [C]-sized ops or a cached number -- beside the fused launch (the
+        unit's own is zero)."""
         fuse = self.fuse_affine if fuse is None else fuse
         mods = list(reversed(self.sequence_modules))
+        logdet = input.new_zeros(len(input)) if with_logdet else None
         i = 0
         while i < len(mods):
             m = mods[i]
@@ -376,6 +411,8 @@ class FlowSequential(nn.Module):
                     and isinstance(mods[i + 1], FastFlowUnit) and not torch.is_grad_enabled()):
                 fused = mods[i + 1].reverse_affine(input, *m.reverse_affine_params())
                 if fused is not None:
+                    if with_logdet:
+                        logdet = logdet + m.logdet(input, context)
                     input = fused
                     i += 2
                     continue
@@ -389,6 +426,10 @@ class FlowSequential(nn.Module):
                 if j < len(mods) and isinstance(mods[j], FastFlowUnit) and (j == i + 1 or affine is not None):
                     fused = mods[j].reverse_after_mix(input, m, affine)
                     if fused is not None:
+                        if with_logdet:
+                            logdet = logdet + m.mix_logdet(input)
+                            if affine is not None:
+                                logdet = logdet + mods[i + 1].logdet(input, context)
                         input = fused
                         i = j + 1
                         continue
@@ -397,13 +438,19 @@ class FlowSequential(nn.Module):
                     and not (i + 2 < len(mods) and isinstance(mods[i + 2], FastFlowUnit)) and not torch.is_grad_enabled()):
                 fused = m.reverse_then_affine(input, *mods[i + 1].reverse_affine_params())
                 if fused is not None:
+                    if with_logdet:
+                        logdet = logdet + m.mix_logdet(input) + mods[i + 1].logdet(input, context)
                     input = fused
                     i += 2
                     continue
-            output = m.reverse(input, context)
-            input = output[0] if isinstance(output, tuple) else output
+            if with_logdet:
+                input, layer_logdet = m.reverse_with_logdet(input, context)
+                logdet = logdet + layer_logdet
+            else:
+                output = m.reverse(input, context)
+                input = output[0] if isinstance(output, tuple) else output
             i += 1
-        return input
+        return (input, logdet) if with_logdet else input
 
     def sample(self, n_samples, context=None, compute_expensive=False, also_true_inverse=False):
         """layers/flowsequential.py:89-115: returns `(input, input_true)` -- the runner unpacks two values
@@ -436,6 +483,32 @@ class FlowSequential(nn.Module):
         if x.is_cuda:
             _lib.raise_if_faulted("FlowSequential.rsample")
         return x
+
+    def sample_with_log_prob(self, n_samples, context=None):
+        """A sample and its log-density under the model, from ONE reverse pass: `(x, log_q)` with x = reverse(z), z drawn from the
+        base, and log_q[B] = base.log_prob(z) + the layers' forward log-dets at their recovered inputs -- what `log_prob(x)` would
+        compute with a second, forward pass over the stack.  Runs under `torch.no_grad()` (the pass of `sample` under no_grad, folds
+        included: the same x from the same seed); nothing is recorded.  The fault word is checked as in `sample`.  With a
+        Dequantization layer in the stack, log_q is the density of the CONTINUOUS variable in front of its floor."""
+        with torch.no_grad():
+            z, _ = self.base_distribution.sample(n_samples, context)
+            x, logdet = self._reverse_chain(z, context, with_logdet=True)
+            log_q = self.base_distribution.log_prob(z) + logdet
+        if x.is_cuda:
+            _lib.raise_if_faulted("FlowSequential.sample_with_log_prob")
+        return x, log_q
+
+    def rsample_with_log_prob(self, n_samples, context=None):
+        """`rsample` with the sample's log-density: `(x, log_q)`, both attached to every parameter (the reverse chain is recorded
+        inside `reverse_grad()`, the coupling's log-det comes out of its reverse launch and has a backward of its own), so that
+        reverse-KL training -- E_q[log q(x) - log p*(x)] -- needs no second pass through `log_prob`."""
+        z, _ = self.base_distribution.sample(n_samples, context)
+        with torch.enable_grad(), ops.reverse_grad():
+            x, logdet = self._reverse_chain(z, context, with_logdet=True)
+            log_q = self.base_distribution.log_prob(z) + logdet
+        if x.is_cuda:
+            _lib.raise_if_faulted("FlowSequential.rsample_with_log_prob")
+        return x, log_q
 
     def reconstruct(self, input, context=None, compute_expensive=False):
         z = self.forward(input, context)[0]

@@ -381,6 +381,45 @@ def finc_coupling_reverse_backward(grad_y, y, raw, a, b, need_gx=True, need_graw
     return gx, graw, ga, gb
 
 
+def finc_coupling_reverse_logdet(x, raw, a, b, out=None):
+    """`finc_coupling(x, raw, a, b, -1)` -- the same y, bit for bit -- with, from the same pass, logdet [B] = s summed per image: the
+    log-det of the FORWARD map at the recovered input, what `finc_coupling(y, raw, a, b, 1, True)[1]` would report (include/finc.h:
+    finc_coupling_reverse_logdet_f32; the reverse map's own log-Jacobian is its negative).  Returns (y, logdet); `out` may be `x`.
+    One more small launch for the fixed-order sums: the same inputs give the same bits."""
+    _coupling_args(x, raw, a, b)
+    out = _out_like(x, out)
+    B, C, H, W = x.shape
+    if x.numel() == 0:
+        return out, torch.zeros(B, dtype=torch.float32, device=x.device)
+    logdet = torch.empty(B, dtype=torch.float32, device=x.device)
+    nbytes = _lib.lib().finc_coupling_workspace_bytes(B, C, H * W)
+    _call("finc_coupling_reverse_logdet_f32", x.device, x.data_ptr(), raw.data_ptr(), a.data_ptr(), b.data_ptr(), out.data_ptr(),
+          logdet.data_ptr(), B, C, H * W, *_ws_args(x.device, nbytes), _stream_ptr(x))
+    return out, logdet
+
+
+def finc_coupling_reverse_logdet_backward(grad_y, grad_logdet, y, raw, a, b, need_gx=True, need_graw=True, need_ga=True, need_gb=True):
+    """Gradients of `finc_coupling_reverse_logdet` (include/finc.h: finc_coupling_reverse_logdet_backward_f32), given grad_y
+    [B,C,H,W], grad_logdet [B] or None (zeros) and the reverse's OUTPUT `y`: (grad_x, grad_raw, grad_a, grad_b), each computed only
+    if asked for (None otherwise).  With grad_logdet None every result has the bits of `finc_coupling_reverse_backward`."""
+    _coupling_args(y, raw, a, b, "output")
+    _require_device(grad_y, "grad_output")
+    if grad_y.shape != y.shape or grad_y.device != y.device:
+        raise ValueError("grad_output must match the reverse's output in shape and device")
+    B, C, H, W = y.shape
+    _per_image(grad_logdet, "grad_logdet", y)
+    gx = torch.empty_like(y) if need_gx else None
+    graw = torch.empty_like(raw) if need_graw else None
+    ga = torch.empty(C, dtype=torch.float32, device=y.device) if need_ga else None
+    gb = torch.empty(C, dtype=torch.float32, device=y.device) if need_gb else None
+    if _nothing_to_launch(y, (gx, graw, ga, gb), (ga, gb)):
+        return gx, graw, ga, gb
+    nbytes = _lib.lib().finc_coupling_workspace_bytes(B, C, H * W) if (need_ga or need_gb) else None
+    _call("finc_coupling_reverse_logdet_backward_f32", y.device, grad_y.data_ptr(), _ptr(grad_logdet), y.data_ptr(), raw.data_ptr(),
+          a.data_ptr(), b.data_ptr(), _ptr(gx), _ptr(graw), _ptr(ga), _ptr(gb), B, C, H * W, *_ws_args(y.device, nbytes), _stream_ptr(y))
+    return gx, graw, ga, gb
+
+
 def _incoming_grads(like, grad_y, grad_logdet):
     """What a (y, logdet) Function's backward is handed, as the kernels take it: contiguous, zeros for a `y` nobody used (None)."""
     grad_y = torch.zeros_like(like) if grad_y is None else grad_y
@@ -435,6 +474,32 @@ class _FincCouplingReverseFunction(torch.autograd.Function):
 def coupling_reverse(x, raw, a, b):
     """`finc_coupling(x, raw, a, b, -1)[0]` under autograd: gradients for `x`, `raw`, `a` and `b`, each computed only where needed."""
     return _FincCouplingReverseFunction.apply(x, raw, a, b)
+
+
+class _FincCouplingReverseLogdetFunction(torch.autograd.Function):
+    """`finc_coupling_reverse_logdet` under autograd (inside `reverse_grad()`): (y, logdet) and their backward on the HIP kernels.
+    Saved, as by its sibling without the log-det: the OUTPUT y, raw, a and b."""
+
+    @staticmethod
+    def forward(ctx, x, raw, a, b):
+        x, raw, a, b = x.contiguous(), raw.contiguous(), a.contiguous(), b.contiguous()
+        y, logdet = finc_coupling_reverse_logdet(x, raw, a, b)
+        ctx.save_for_backward(y, raw, a, b)
+        return y, logdet
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y, grad_logdet):
+        y, raw, a, b = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        return finc_coupling_reverse_logdet_backward(*_incoming_grads(y, grad_y, grad_logdet), y, raw, a, b,
+                                                     need_gx=need[0], need_graw=need[1], need_ga=need[2], need_gb=need[3])
+
+
+def coupling_reverse_logdet(x, raw, a, b):
+    """`finc_coupling_reverse_logdet(x, raw, a, b)` under autograd: returns (y, logdet), gradients for `x`, `raw`, `a` and `b`, each
+    computed only where needed."""
+    return _FincCouplingReverseLogdetFunction.apply(x, raw, a, b)
 
 
 def finc_bias_relu(x, bias, out=None):

@@ -323,6 +323,19 @@ int finc_mix_backward_f32(const float *grad_out, const float *in, const float *m
  *     grad_h[:, 2j+1] = -grad_y2 * E_j,   grad_h[:, 2j] = -(grad_y2 * y[:, half+j]) * (1 - th_j^2)
  *     grad_raw[:, c] = a[c] * grad_h[:, c],   grad_a[c] = sum_{b,p} grad_h[b,c,p] * raw[b,c,p],   grad_b[c] = sum_{b,p} grad_h[b,c,p]
  *   There is no log-det in this direction.  Outputs, workspace, aliasing and status as for finc_coupling_backward_f32.
+ * finc_coupling_reverse_logdet_f32: direction -1 of finc_coupling_f32 -- the same y, bit for bit -- and, from the same pass,
+ *     logdet[b] = sum_{j,p} s_j[b,p]:
+ *   the log-det of the FORWARD map, i.e. what direction +1 reports at the recovered input y (s depends on the untouched half only,
+ *   which x and y share).  The reverse map's own log-Jacobian is its negative.  It is what a sampler adds to the base density:
+ *   log q(y) = log p(x) + (the layers in front) + logdet.  `logdet` [B] is required (FINC_ERR_NULL_POINTER), and so is a `workspace`
+ *   of finc_coupling_workspace_bytes() bytes: the partials are those of direction +1 (one per workgroup, the same grid), which that
+ *   size already covers, summed by the same second launch in a fixed order -- no atomics, the same inputs give the same bits.
+ *   y == x is allowed; y == raw is not (FINC_ERR_BAD_DIMS).
+ * finc_coupling_reverse_logdet_backward_f32: the gradients of finc_coupling_reverse_logdet_f32, given grad_y, grad_logdet [B]
+ *   (NULL = zeros) and the reverse's OUTPUT y: finc_coupling_reverse_backward_f32 with one more term,
+ *     grad_h[:, 2j] = (-(grad_y2 * y[:, half+j]) + grad_logdet[b]) * (1 - th_j^2)
+ *   and everything else as there.  With grad_logdet NULL every output has the bits finc_coupling_reverse_backward_f32 gives.
+ *   Outputs, workspace, aliasing and status as for finc_coupling_reverse_backward_f32.
  * finc_bias_relu_f32: out = max(in + bias[c], 0) -- the Conv2d bias and the nn.ReLU behind the net's first two convolutions
  *   (layers/coupling.py:58-63) in one pass; in == out allowed.  Inference only (no backward).
  * Rows of HW floats move as 16-byte pieces when HW % 4 == 0 and every activation pointer is 16-byte aligned, as dwords otherwise.
@@ -339,6 +352,12 @@ int finc_coupling_backward_f32(const float *grad_y, const float *grad_logdet, co
 int finc_coupling_reverse_backward_f32(const float *grad_y, const float *y, const float *raw, const float *a, const float *b,
                                        float *grad_x, float *grad_raw, float *grad_a, float *grad_b, int B, int C, int HW,
                                        void *workspace, size_t workspace_bytes, finc_stream_t stream);
+int finc_coupling_reverse_logdet_f32(const float *x, const float *raw, const float *a, const float *b, float *y, float *logdet,
+                                     int B, int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream);
+int finc_coupling_reverse_logdet_backward_f32(const float *grad_y, const float *grad_logdet, const float *y, const float *raw,
+                                              const float *a, const float *b, float *grad_x, float *grad_raw, float *grad_a,
+                                              float *grad_b, int B, int C, int HW, void *workspace, size_t workspace_bytes,
+                                              finc_stream_t stream);
 int finc_bias_relu_f32(const float *in, const float *bias, float *out, int B, int C, int HW, finc_stream_t stream);
 
 /*
