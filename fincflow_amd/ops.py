@@ -11,6 +11,7 @@ import contextlib
 import threading
 
 import torch
+from torch.optim.optimizer import register_optimizer_step_post_hook
 
 from . import _lib
 
@@ -86,9 +87,26 @@ def _ptr(t):
     return t.data_ptr() if t is not None else None
 
 
+_steps = [0]
+
+
+def _after_optimizer_step(optimizer, args, kwargs):
+    _steps[0] += 1
+
+
+# PyTorch's fused optimisers (Adam / AdamW / SGD with fused=True) update the parameters in one kernel that does NOT advance
+# Tensor._version: keyed on (address, version counter) alone, every value derived from a parameter would outlive such a step and a
+# sample would come from last step's weights.  So the key also carries the number of optimiser steps this process has taken, any
+# torch.optim optimiser's: after a step every derived value is rebuilt on its next use -- as it is after a step that does bump the
+# counters -- and a process that only samples never takes one.
+register_optimizer_step_post_hook(_after_optimizer_step)
+
+
 def version_key(*tensors):
-    """(address, version counter) of every tensor, flat: what the caches of values derived from parameters are keyed on."""
-    return tuple(v for t in tensors for v in (t.data_ptr(), t._version))
+    """(optimiser steps taken so far, then address and version counter of every tensor), flat: what the caches of values derived from
+    parameters are keyed on.  Writes that neither bump `Tensor._version` nor are a torch.optim step (collectives, `.data`) still need
+    `PackedWeights.invalidate()`."""
+    return (_steps[0],) + tuple(v for t in tensors for v in (t.data_ptr(), t._version))
 
 
 def _nothing_to_launch(x, grads, sums):
@@ -757,6 +775,18 @@ class PackedWeights:
     def __init__(self):
         self._banks = {}
         self._lock = threading.Lock()
+
+    # A copy of the owning module (copy.deepcopy for an EMA model, pickle, torch.save of the module) starts from an empty cache with a
+    # lock of its own: the banks are derived from the weights -- the copy's first call rebuilds them from ITS weights -- and a lock
+    # cannot be pickled.
+    def __deepcopy__(self, memo):
+        return type(self)()
+
+    def __getstate__(self):
+        return {}
+
+    def __setstate__(self, state):
+        self.__init__()
 
     def _bank(self, device):
         b = self._banks.get(device)
