@@ -39,6 +39,7 @@ SYMBOLS = [
     "finc_inverse_backward_f32",
     "finc_coupling_reverse_backward_f32", "finc_actnorm_reverse_backward_f32",
     "finc_coupling_reverse_logdet_f32", "finc_coupling_reverse_logdet_backward_f32",
+    "finc_actnorm_backward_reconstruct_f32", "finc_coupling_backward_reconstruct_f32",
 ]
 
 #: the ABI version this binding is written against (include/finc.h: finc_version)
@@ -55,6 +56,9 @@ REVERSE_BACKWARD_ABI_VERSION = 108
 #: the version that added the coupling's reverse with its log-det and the backward of that (finc_coupling_reverse_logdet_f32,
 #: finc_coupling_reverse_logdet_backward_f32): what sample_with_log_prob / rsample_with_log_prob launch
 SAMPLE_LOGDET_ABI_VERSION = 109
+#: the version that added the forward-direction backwards that rebuild the layer's input from its output
+#: (finc_actnorm_backward_reconstruct_f32, finc_coupling_backward_reconstruct_f32): what FlowSequential.invertible_backward launches
+INVERTIBLE_BACKWARD_ABI_VERSION = 110
 
 _lib = None
 
@@ -99,6 +103,11 @@ def lib():
         raise FincError(f"{LIB_PATH} reports finc_version() = {have}, the coupling's reverse with its log-det "
                         f"(finc_coupling_reverse_logdet_f32, finc_coupling_reverse_logdet_backward_f32) came with "
                         f"{SAMPLE_LOGDET_ABI_VERSION}: rebuild it "
+                        "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
+    if have < INVERTIBLE_BACKWARD_ABI_VERSION:
+        raise FincError(f"{LIB_PATH} reports finc_version() = {have}, the backwards that rebuild a layer's input from its output "
+                        f"(finc_actnorm_backward_reconstruct_f32, finc_coupling_backward_reconstruct_f32) came with "
+                        f"{INVERTIBLE_BACKWARD_ABI_VERSION}: rebuild it "
                         "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
     L.finc_build_flags.restype = u
     L.finc_clear_fault.restype = i
@@ -175,6 +184,8 @@ def lib():
     L.finc_actnorm_reverse_backward_f32.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp]
     L.finc_coupling_reverse_logdet_f32.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp]
     L.finc_coupling_reverse_logdet_backward_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp]
+    L.finc_actnorm_backward_reconstruct_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp]
+    L.finc_coupling_backward_reconstruct_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp]
     for name in SYMBOLS:
         getattr(L, name)  # AttributeError here = header and library out of sync
     _lib = L

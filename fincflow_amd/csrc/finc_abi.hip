@@ -189,7 +189,7 @@ static int canonicalize(const T *w_stored, T *w_canon, int G, int Cq, int KH, in
 
 extern "C" {
 
-int finc_version(void) { return 109; }
+int finc_version(void) { return 110; }
 
 unsigned finc_build_flags(void)
 {
@@ -679,6 +679,25 @@ int finc_coupling_reverse_logdet_backward_f32(const float *grad_y, const float *
                                                  (float *)workspace, (hipStream_t)stream);
 }
 
+int finc_coupling_backward_reconstruct_f32(const float *grad_y, const float *grad_logdet, const float *y, const float *raw, const float *a,
+                                           const float *b, float *x_out, float *grad_x, float *grad_raw, float *grad_a, float *grad_b,
+                                           int B, int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    if (!grad_y || !y || !raw || !a || !b || (!x_out && !grad_x && !grad_raw && !grad_a && !grad_b)) return FINC_ERR_NULL_POINTER;
+    if (int e = pixel_dims(B, C, HW, true)) return e;
+    // x_out == y and grad_x == grad_y are the two allowed overlaps
+    if (x_out && (x_out == grad_y || x_out == raw || x_out == grad_x || x_out == grad_raw)) return FINC_ERR_BAD_DIMS;
+    if (grad_x && (grad_x == y || grad_x == raw || grad_x == grad_raw)) return FINC_ERR_BAD_DIMS;
+    if (grad_raw && (grad_raw == grad_y || grad_raw == y || grad_raw == raw)) return FINC_ERR_BAD_DIMS;
+    if (misaligned(grad_y, grad_logdet, y, raw, a, b, x_out, grad_x, grad_raw, grad_a, grad_b)) return FINC_ERR_ALIGNMENT;
+    if (!finc_coupling_supported_f32(C)) return FINC_ERR_UNSUPPORTED;
+    if ((grad_a || grad_b) && workspace_short(workspace, workspace_bytes, finc_coupling_workspace_bytes(B, C, HW)))
+        return FINC_ERR_WORKSPACE;
+    if (int e = finc_fault_gate(false)) return e;
+    return finc_coupling_backward_reconstruct_launch(grad_y, grad_logdet, y, raw, a, b, x_out, grad_x, grad_raw, grad_a, grad_b, B, C, HW,
+                                                     (float *)workspace, (hipStream_t)stream);
+}
+
 int finc_bias_relu_f32(const float *in, const float *bias, float *out, int B, int C, int HW, finc_stream_t stream)
 {
     if (!in || !bias || !out) return FINC_ERR_NULL_POINTER;
@@ -717,6 +736,25 @@ int finc_actnorm_backward_f32(const float *grad_y, const float *grad_logdet, con
     if (int e = finc_fault_gate(false)) return e;
     return finc_actnorm_backward_launch(grad_y, grad_logdet, y, log_scale, grad_x, grad_log_scale, grad_translation, B, C, HW,
                                         (float *)workspace, (hipStream_t)stream);
+}
+
+int finc_actnorm_backward_reconstruct_f32(const float *grad_y, const float *grad_logdet, const float *y, const float *log_scale,
+                                          const float *translation, float *x_out, float *grad_x, float *grad_log_scale,
+                                          float *grad_translation, int B, int C, int HW, void *workspace, size_t workspace_bytes,
+                                          finc_stream_t stream)
+{
+    if (!grad_y || !y || !log_scale || (x_out && !translation) || (!x_out && !grad_x && !grad_log_scale && !grad_translation))
+        return FINC_ERR_NULL_POINTER;
+    if (int e = pixel_dims(B, C, HW, true)) return e;
+    // x_out == y and grad_x == grad_y are the two allowed overlaps
+    if (x_out && (x_out == grad_y || x_out == grad_x)) return FINC_ERR_BAD_DIMS;
+    if (grad_x && grad_x == y) return FINC_ERR_BAD_DIMS;
+    if (misaligned(grad_y, grad_logdet, y, log_scale, translation, x_out, grad_x, grad_log_scale, grad_translation)) return FINC_ERR_ALIGNMENT;
+    if ((grad_log_scale || grad_translation) && workspace_short(workspace, workspace_bytes, finc_actnorm_workspace_bytes(B, C, HW)))
+        return FINC_ERR_WORKSPACE;
+    if (int e = finc_fault_gate(false)) return e;
+    return finc_actnorm_backward_reconstruct_launch(grad_y, grad_logdet, y, log_scale, translation, x_out, grad_x, grad_log_scale,
+                                                    grad_translation, B, C, HW, (float *)workspace, (hipStream_t)stream);
 }
 
 int finc_actnorm_reverse_backward_f32(const float *grad_y, const float *x, const float *log_scale, float *grad_x, float *grad_log_scale,

@@ -8,6 +8,8 @@
 //   * finc_actnorm_bwd_kernel    one pass over grad_y and y (the forward's OUTPUT: x - t = y * exp(ls), so
 //                                d loss / d ls[c] = -sum grad_y * y needs nothing the forward's caller does not keep anyway):
 //                                grad_x = grad_y * exp(-ls[c]) and the two per-channel sums, then finc_coupling_reduce_kernel.
+//   * finc_actnorm_recon_kernel  that backward, and from the same read of y the forward's INPUT x = y * exp(ls[c]) + t[c]: the step of a
+//                                training backward that stores no activations (FlowSequential.invertible_backward).
 //   * finc_actnorm_rev_bwd_kernel  the same for the reverse direction, from the reverse's INPUT (what `reverse` under autograd
 //                                records inside ops.reverse_grad()).
 //   * finc_actnorm_stats_kernel  the data-dependent initialisation (:17-23): per-channel mean and unbiased standard deviation in ONE
@@ -98,6 +100,60 @@ __global__ __launch_bounds__(CPL_THREADS) void finc_actnorm_bwd_kernel(const flo
             if (threadIdx.x == 0) {
                 p0[Q] = 0.f;
                 p1[Q] = -(float)HW * l;
+            }
+        }
+    }
+}
+
+// finc_actnorm_bwd_kernel that also REBUILDS the forward's input from the same read of y: xo = y * exp(ls[c]) + t[c] (the arithmetic of
+// finc_actnorm_kernel's reverse direction, so the same bits).  What a training step without stored activations runs per ActNorm: one
+// launch instead of a reverse launch plus a backward launch, y read once.  Workgroups, partials and slot Q as in
+// finc_actnorm_bwd_kernel.  gld, xo (then tr is not read), gx may be nullptr; `sums` = 0 skips the partials; `need_y` = 0 (neither xo
+// nor grad_ls) skips the read of y.  xo == y and gx == gy are allowed (an item is read before it is written, by the same thread).
+template <int V>
+__global__ __launch_bounds__(CPL_THREADS) void finc_actnorm_recon_kernel(const float *gy, const float *__restrict__ gld, const float *y,
+                                                                         const float *__restrict__ ls, const float *__restrict__ tr,
+                                                                         float *xo, float *gx, float *__restrict__ part, int B, int C, int HW,
+                                                                         int nv, int items, int Q, int sums, int need_y)
+{
+    const int c = (int)blockIdx.x / Q, qi = (int)blockIdx.x - c * Q;
+    const float l = ls[c], s = expf(-l), si = expf(l), t = xo ? tr[c] : 0.f;
+    float acc[2] = {0.f, 0.f};
+    for (int idx = qi * CPL_THREADS + (int)threadIdx.x; idx < items; idx += Q * CPL_THREADS) {
+        const int img = idx / nv, p = (idx - img * nv) * V;
+        const size_t o = ((size_t)img * C + c) * (size_t)HW + p;
+        float g[V], yv[V], d[V], xv[V];
+        cpl_load<V>(g, gy + o);
+        if (need_y) cpl_load<V>(yv, y + o);
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            d[e] = g[e] * s;
+            acc[0] += g[e];
+            if (need_y) {
+                acc[1] = fmaf(g[e], yv[e], acc[1]);
+                xv[e] = fmaf(yv[e], si, t);
+            }
+        }
+        if (xo) cpl_store<V>(xo + o, xv);
+        if (gx) cpl_store<V>(gx + o, d);
+    }
+    if (sums) {
+        __shared__ float sm[2][4];
+        cpl_block_sum<2>(acc, sm);
+        float *p0 = part + (size_t)(2 * c) * (Q + 1), *p1 = p0 + (Q + 1);
+        if (threadIdx.x == 0) {
+            p0[qi] = -s * acc[0];
+            p1[qi] = -acc[1];
+        }
+        if (qi == 0 && threadIdx.x < 64) {
+            float gl = 0.f;
+            if (gld)
+                for (int b = (int)threadIdx.x; b < B; b += 64) gl += gld[b];
+#pragma unroll
+            for (int k = 32; k > 0; k >>= 1) gl += __shfl_xor(gl, k, 64);
+            if (threadIdx.x == 0) {
+                p0[Q] = 0.f;
+                p1[Q] = -(float)HW * gl;
             }
         }
     }
@@ -258,6 +314,25 @@ int finc_actnorm_backward_launch(const float *gy, const float *gld, const float 
     const dim3 grid((unsigned)((long long)C * Q)), block(CPL_THREADS);
     hipLaunchKernelGGL(wide ? finc_actnorm_bwd_kernel<4> : finc_actnorm_bwd_kernel<1>, grid, block, 0, st, gy, gld, y, ls, gx, ws, B, C, HW,
                        nv, items, Q, sums);
+    FINC_CHECK_LAUNCH();
+    if (sums) {
+        hipLaunchKernelGGL(finc_coupling_reduce_kernel, dim3((unsigned)(2 * C)), dim3(64), 0, st, (const float *)ws, Q + 1, gt, gls, 1);
+        FINC_CHECK_LAUNCH();
+    }
+    return FINC_OK;
+}
+
+int finc_actnorm_backward_reconstruct_launch(const float *gy, const float *gld, const float *y, const float *ls, const float *tr, float *xo,
+                                             float *gx, float *gls, float *gt, int B, int C, int HW, float *ws, hipStream_t st)
+{
+    if (!cpl_rows_fit(B, C, HW)) return FINC_ERR_BAD_DIMS;
+    const int need_y = (xo || gls) ? 1 : 0;                          // grad_ls and the rebuilt input read y
+    if (!need_y) y = nullptr;
+    const bool wide = cpl_wide(HW, (uintptr_t)gy | (uintptr_t)y | (uintptr_t)xo | (uintptr_t)gx);
+    const int nv = HW / (wide ? 4 : 1), items = B * nv, Q = cpl_parts(items, C), sums = (gls || gt) ? 1 : 0;
+    const dim3 grid((unsigned)((long long)C * Q)), block(CPL_THREADS);
+    hipLaunchKernelGGL(wide ? finc_actnorm_recon_kernel<4> : finc_actnorm_recon_kernel<1>, grid, block, 0, st, gy, gld, y, ls, tr, xo, gx, ws,
+                       B, C, HW, nv, items, Q, sums, need_y);
     FINC_CHECK_LAUNCH();
     if (sums) {
         hipLaunchKernelGGL(finc_coupling_reduce_kernel, dim3((unsigned)(2 * C)), dim3(64), 0, st, (const float *)ws, Q + 1, gt, gls, 1);

@@ -272,6 +272,10 @@ int finc_coupling_reverse_logdet_launch(const float *x, const float *raw, const 
 int finc_coupling_reverse_backward_launch(const float *gy, const float *gld, const float *y, const float *raw, const float *a,
                                           const float *b, float *gx, float *graw, float *ga, float *gb, int B, int C, int HW, float *ws,
                                           hipStream_t st);
+// the backward of direction +1 from its OUTPUT y, which also writes the rebuilt input xo; gld, xo, gx, graw, ga, gb may be nullptr
+int finc_coupling_backward_reconstruct_launch(const float *gy, const float *gld, const float *y, const float *raw, const float *a,
+                                              const float *b, float *xo, float *gx, float *graw, float *ga, float *gb, int B, int C, int HW,
+                                              float *ws, hipStream_t st);
 int finc_bias_relu_launch(const float *in, const float *bias, float *out, int B, int C, int HW, hipStream_t st);
 // ---- ActNorm (transform + log-det, its backward from the forward's OUTPUT, the data-dependent initialisation): finc_actnorm.h, same object ----
 // `ws` holds finc_actnorm_workspace_floats floats (backward with gls / gt, and the initialisation)
@@ -280,6 +284,9 @@ int finc_actnorm_launch(const float *x, const float *ls, const float *tr, float 
                         hipStream_t st);
 int finc_actnorm_backward_launch(const float *gy, const float *gld, const float *y, const float *ls, float *gx, float *gls, float *gt,
                                  int B, int C, int HW, float *ws, hipStream_t st);
+// finc_actnorm_backward_launch that also writes the rebuilt input xo = y * exp(ls) + tr; gld, xo (then tr too), gx, gls, gt may be nullptr
+int finc_actnorm_backward_reconstruct_launch(const float *gy, const float *gld, const float *y, const float *ls, const float *tr, float *xo,
+                                             float *gx, float *gls, float *gt, int B, int C, int HW, float *ws, hipStream_t st);
 // the backward of direction -1, from the reverse's INPUT x
 int finc_actnorm_reverse_backward_launch(const float *gy, const float *x, const float *ls, float *gx, float *gls, float *gt, int B, int C,
                                          int HW, float *ws, hipStream_t st);

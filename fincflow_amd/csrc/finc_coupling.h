@@ -10,6 +10,8 @@
 //                               forward and two reads here, and this kernel is bound by its memory traffic, not by the VALU.
 //   * finc_coupling_rev_bwd_kernel  the same for the reverse direction, from the reverse's OUTPUT (what `reverse` under autograd
 //                               records inside ops.reverse_grad()).
+//   * finc_coupling_recon_kernel  the backward of the forward direction from the forward's OUTPUT, which also writes the rebuilt
+//                               input: the step of a training backward that stores no activations.
 //   * finc_coupling_rev_logdet_kernel  the reverse pass that also sums s per image: the sample and the forward log-det at the
 //                               sample in one pass (FlowSequential.sample_with_log_prob / rsample_with_log_prob).
 //   * finc_bias_relu_kernel     out = max(in + bias[c], 0), in place or not.
@@ -245,6 +247,71 @@ __global__ __launch_bounds__(CPL_THREADS) void finc_coupling_rev_bwd_kernel(cons
     }
 }
 
+// The backward of the FORWARD direction from the forward's OUTPUT y, which also rebuilds the forward's input (layers/coupling.py:79-101):
+// with d = y2 - t, x2 = d * exp(-s) (the arithmetic of finc_coupling_kernel's reverse direction, so the same bits), and
+// x2 * exp(s) = d: grad_x2 = grad_y2 * exp(s), grad_h[2j+1] = grad_y2, grad_h[2j] = (grad_y2 * d + gld[img]) * (1 - th^2).  What a
+// training step without stored activations runs per coupling: one launch instead of a reverse launch plus a backward launch; y and
+// raw are read once.  Workgroups and partials as in finc_coupling_bwd_kernel.  gld, xo, gx, graw may be nullptr; `sums` = 0 skips the
+// partials.  xo == y and gx == gy are allowed (a thread reads its pieces before it writes them, and nobody else touches them).
+template <int V>
+__global__ __launch_bounds__(CPL_THREADS) void finc_coupling_recon_kernel(const float *gy, const float *__restrict__ gld, const float *y,
+                                                                          const float *__restrict__ raw, const float *__restrict__ a,
+                                                                          const float *__restrict__ b, float *xo, float *gx,
+                                                                          float *__restrict__ graw, float *__restrict__ part, int half, int HW,
+                                                                          int nv, int items, int Q, int sums)
+{
+    const int j = (int)blockIdx.x / Q, qi = (int)blockIdx.x - j * Q;
+    const float au = a[2 * j], bu = b[2 * j], at = a[2 * j + 1], bt = b[2 * j + 1];
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int idx = qi * CPL_THREADS + (int)threadIdx.x; idx < items; idx += Q * CPL_THREADS) {
+        const int img = idx / nv, p = (idx - img * nv) * V;
+        const size_t ibase = (size_t)img * (size_t)(2 * half) * (size_t)HW;
+        const size_t o1 = ibase + (size_t)j * HW + p, o2 = o1 + (size_t)half * HW;
+        const size_t ou = ibase + (size_t)(2 * j) * HW + p, ot = ou + HW;
+        float g1[V], g2[V], y1[V], y2[V], u[V], t[V], x2[V], gx2[V], gu[V], gt[V];
+        if (gx) cpl_load<V>(g1, gy + o1);
+        cpl_load<V>(g2, gy + o2);
+        if (xo) cpl_load<V>(y1, y + o1);
+        cpl_load<V>(y2, y + o2);
+        cpl_load<V>(u, raw + ou);
+        cpl_load<V>(t, raw + ot);
+        const float gl = gld ? gld[img] : 0.f;
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            const float th = tanhf(0.5f * fmaf(au, u[e], bu));     // s = 2 th, d s / d h = 1 - th*th
+            const float s = 2.f * th, d = y2[e] - fmaf(at, t[e], bt);
+            x2[e] = d * expf(-s);
+            gx2[e] = g2[e] * expf(s);
+            const float gh = fmaf(g2[e], d, gl) * fmaf(-th, th, 1.f);
+            gu[e] = au * gh;
+            gt[e] = at * g2[e];
+            if (sums) {
+                acc[0] = fmaf(gh, u[e], acc[0]);
+                acc[1] += gh;
+                acc[2] = fmaf(g2[e], t[e], acc[2]);
+                acc[3] += g2[e];
+            }
+        }
+        if (xo) {
+            cpl_store<V>(xo + o1, y1);
+            cpl_store<V>(xo + o2, x2);
+        }
+        if (gx) {
+            cpl_store<V>(gx + o1, g1);
+            cpl_store<V>(gx + o2, gx2);
+        }
+        if (graw) {
+            cpl_store<V>(graw + ou, gu);
+            cpl_store<V>(graw + ot, gt);
+        }
+    }
+    if (sums) {
+        __shared__ float sm[4][4];
+        cpl_block_sum<4>(acc, sm);
+        if (threadIdx.x < 4) part[((size_t)(4 * j) + threadIdx.x) * Q + qi] = acc[threadIdx.x];
+    }
+}
+
 // One wave per output: out = sum of its n consecutive partials, lane l takes l, l + 64, ... and the lanes meet in a butterfly.
 // pairs == 0: out_a[o] (the log-det of image o).  pairs == 1: output o = 4j + k goes to out_a / out_b as listed above; a nullptr
 // destination is neither summed nor written.
@@ -374,6 +441,26 @@ int finc_coupling_backward_launch(const float *gy, const float *gld, const float
     const dim3 grid((unsigned)((long long)half * Q)), block(CPL_THREADS);
     hipLaunchKernelGGL(wide ? finc_coupling_bwd_kernel<4> : finc_coupling_bwd_kernel<1>, grid, block, 0, st, gy, gld, x, raw, a, b, gx, graw,
                        ws, half, HW, nv, items, Q, sums);
+    FINC_CHECK_LAUNCH();
+    if (sums) {
+        hipLaunchKernelGGL(finc_coupling_reduce_kernel, dim3((unsigned)(4 * half)), dim3(64), 0, st, (const float *)ws, Q, ga, gb, 1);
+        FINC_CHECK_LAUNCH();
+    }
+    return FINC_OK;
+}
+
+// the backward of direction +1 from its OUTPUT y, with the rebuilt input in xo: partials and reduce of finc_coupling_backward_launch
+int finc_coupling_backward_reconstruct_launch(const float *gy, const float *gld, const float *y, const float *raw, const float *a,
+                                              const float *b, float *xo, float *gx, float *graw, float *ga, float *gb, int B, int C, int HW,
+                                              float *ws, hipStream_t st)
+{
+    const int half = C / 2, sums = (ga || gb) ? 1 : 0;
+    if (!cpl_rows_fit(B, C, HW)) return FINC_ERR_BAD_DIMS;
+    const bool wide = cpl_wide(HW, (uintptr_t)gy | (uintptr_t)y | (uintptr_t)raw | (uintptr_t)xo | (uintptr_t)gx | (uintptr_t)graw);
+    const int nv = HW / (wide ? 4 : 1), items = B * nv, Q = cpl_parts(items, half);
+    const dim3 grid((unsigned)((long long)half * Q)), block(CPL_THREADS);
+    hipLaunchKernelGGL(wide ? finc_coupling_recon_kernel<4> : finc_coupling_recon_kernel<1>, grid, block, 0, st, gy, gld, y, raw, a, b, xo, gx,
+                       graw, ws, half, HW, nv, items, Q, sums);
     FINC_CHECK_LAUNCH();
     if (sums) {
         hipLaunchKernelGGL(finc_coupling_reduce_kernel, dim3((unsigned)(4 * half)), dim3(64), 0, st, (const float *)ws, Q, ga, gb, 1);

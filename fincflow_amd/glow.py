@@ -6,7 +6,9 @@ kernels of their own (ops.finc_actnorm, ops.finc_mix, ops.finc_coupling), in inf
 `reverse` inside `ops.reverse_grad()` (what `FlowSequential.rsample` records: ops.actnorm_reverse, ops.mix_forward on W^-1,
 ops.coupling_reverse); `reverse` under autograd outside that context keeps its PyTorch lines.  `reverse_with_logdet` is `reverse`
 plus the forward log-det at its result from the same pass (ops.finc_coupling_reverse_logdet, ops.coupling_reverse_logdet; parameters
-only for ActNorm and Conv1x1): what `FlowSequential.sample_with_log_prob` / `rsample_with_log_prob` add up.  The coupling net's
+only for ActNorm and Conv1x1): what `FlowSequential.sample_with_log_prob` / `rsample_with_log_prob` add up.  `backward_from_output`
+differentiates a layer from its OUTPUT and rebuilds its input in the same pass (ops.finc_actnorm_backward_reconstruct,
+ops.finc_coupling_backward_reconstruct, the mix on W^-1): the steps of `FlowSequential.invertible_backward`.  The coupling net's
 convolutions, Squeeze and the preprocessing layers are ops that PyTorch-ROCm already runs.  The point of this file is that a
 whole sampling pass (96 units at 16x16 / 8x8 / 4x4) can run and be captured in one HIP graph.
 
@@ -30,7 +32,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .layers import FastFlowUnit, FlowLayer, FlowSequential, _hip_tensor, _records_graph
+from .layers import FastFlowUnit, FlowLayer, FlowSequential, _hip_tensor, _param_needs, _params_on_device, _records_graph
 
 
 class Squeeze(FlowLayer):
@@ -46,6 +48,18 @@ class Squeeze(FlowLayer):
 
     def reverse_with_logdet(self, input, context=None):
         return self.reverse(input, context), input.new_zeros(len(input))
+
+    def invertible_backward_supported(self, input, context=None):
+        return _hip_tensor(input) and input.shape[2] % 2 == 0 and input.shape[3] % 2 == 0
+
+    def invertible_output_shape(self, shape):
+        b, c, h, w = shape
+        return b, c * 4, h // 2, w // 2
+
+    def backward_from_output(self, output, grad_output, grad_logdet, context, needs):
+        """The permutation's inverse applied to the output and to its gradient."""
+        x = self.reverse(output) if needs.input else None
+        return x, (self.reverse(grad_output) if needs.grad_input else None), None, []
 
     def logdet(self, input, context=None):
         return input.new_zeros(len(input))
@@ -139,6 +153,20 @@ class ActNorm(FlowLayer):
         out = self.reverse(input, context)
         return out, self.logdet(out, context)
 
+    def invertible_backward_supported(self, input, context=None):
+        """Once initialised.  The call that still has to initialise runs the stored path, as it always has."""
+        return self._is_initialized() and self._hip_device(input)
+
+    def backward_from_output(self, output, grad_output, grad_logdet, context, needs):
+        """ONE launch (`ops.finc_actnorm_backward_reconstruct`): the gradients of `forward` and its input from one read of the output."""
+        params, asked = _param_needs(self, needs)
+        want = {id(p): a for p, a in zip(params, asked)}
+        x, gx, gls, gt = ops.finc_actnorm_backward_reconstruct(
+            grad_output.contiguous(), grad_logdet, output.contiguous(), self.log_scale.detach(), self.translation.detach(),
+            need_x=needs.input, need_gx=needs.grad_input, need_gls=want[id(self.log_scale)], need_gt=want[id(self.translation)])
+        grads = {id(self.log_scale): gls, id(self.translation): gt}
+        return x, gx, None, [grads[id(p)] for p in params]
+
     def forward_affine_params(self):
         """forward(x) = (x - translation) * exp(-log_scale): what FlowSequential folds into the FastFlowUnit in front of
         this layer (only once the data-dependent initialisation has happened)."""
@@ -209,6 +237,22 @@ class Conv1x1(FlowLayer):
         if self._hip_reverse_grad(z):
             return ops.mix_forward(z, w_inv)
         return F.conv2d(z, w_inv.view(self.n_channels, self.n_channels, 1, 1))
+
+    def invertible_backward_supported(self, x, context=None):
+        return self._hip_device(x) and x.shape[1] == self.n_channels and _params_on_device(x, self.W)
+
+    def backward_from_output(self, output, grad_output, grad_logdet, context, needs):
+        """Two existing launches: x = finc_mix(output, W^-1) on the cached inverse, then finc_mix_backward at (grad_output, x); the
+        log-det's share, H * W * (sum_b grad_logdet[b]) * W^-T, is a [C, C] op."""
+        need_gw = _param_needs(self, needs)[1][0]
+        w_inv = self._inverse_matrix()
+        x = ops.finc_mix(output.contiguous(), w_inv) if (needs.input or need_gw) else None
+        gx, gw, _ = ops.finc_mix_backward(grad_output.contiguous(), x, self.W.detach().contiguous(), need_gx=needs.grad_input,
+                                          need_gm=need_gw)
+        if need_gw and grad_logdet is not None:
+            h, w = output.shape[2:]
+            gw = gw + (h * w) * grad_logdet.sum() * w_inv.t()
+        return x, gx, None, [gw]
 
     def _log_abs_det(self):
         """log|det W|, 0-dim: recorded (`torch.slogdet`) while autograd records through W; otherwise cached per weight version, as
@@ -410,6 +454,40 @@ class Coupling(FlowLayer):
             return ops.coupling_reverse_logdet(input, self._raw_train(input, context), a, b)
         x1, x2, log_s, t = self._params(input, context)
         return torch.cat([x1, (x2 - t) * torch.exp(-log_s)], dim=1), log_s.flatten(start_dim=1).sum(-1)
+
+    def invertible_backward_supported(self, input, context=None):
+        if (context is not None) != self.uses_context or not self._hip_device(input) or input.shape[1] != self.n_channels:
+            return False
+        acts = (input,) if context is None else (input, context)
+        return all(_hip_tensor(t) for t in acts) and _params_on_device(input, *acts[1:], *self.net.parameters())
+
+    def backward_from_output(self, output, grad_output, grad_logdet, context, needs):
+        """The net sees the untouched half only, and that half of the input IS that half of the output, bit for bit: the net is run
+        again on it under autograd (`_raw_train` on a detached leaf), ONE launch (`ops.finc_coupling_backward_reconstruct`) gives the
+        input, the direct grad_input and the gradients of raw, a and b, and one `torch.autograd.grad` pushes those three through the net
+        and `_scale_shift()` to the net's parameters, the untouched half and the context."""
+        params, asked = _param_needs(self, needs)
+        y, half = output.contiguous(), self.half_channels
+        with torch.enable_grad():
+            y1 = y[:, :half].detach().requires_grad_(needs.grad_input)
+            ctx = None if context is None else context.detach().requires_grad_(needs.grad_context)
+            raw = self._raw_train(y1, ctx)
+            a, b = self._scale_shift()
+        wanted = [t for t, w in [(y1, needs.grad_input), (ctx, needs.grad_context)] + list(zip(params, asked)) if w]
+        through = bool(wanted)                                  # does anything behind raw, a and b want a gradient?
+        x, gx, graw, ga, gb = ops.finc_coupling_backward_reconstruct(
+            grad_output.contiguous(), grad_logdet, y, raw.detach().contiguous(), a.detach().contiguous(), b.detach().contiguous(),
+            need_x=needs.input, need_gx=needs.grad_input, need_graw=through and raw.requires_grad,
+            need_ga=through and a.requires_grad, need_gb=through and b.requires_grad)
+        heads = [(t, g) for t, g in ((raw, graw), (a, ga), (b, gb)) if g is not None]
+        got = iter(torch.autograd.grad([t for t, _ in heads], wanted, [g for _, g in heads], allow_unused=True)
+                   if heads else [None] * len(wanted))
+        if needs.grad_input:
+            g1 = next(got)
+            if g1 is not None:
+                gx[:, :half] += g1
+        gctx = next(got) if needs.grad_context else None
+        return x, gx, gctx, [next(got) if w else None for w in asked]
 
     def logdet(self, input, context=None):
         return self.forward(input, context)[1]

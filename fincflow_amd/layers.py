@@ -12,6 +12,7 @@ so a reference `FlowSequential` (layers/flowsequential.py:21-44,89-115) or
 The arithmetic runs in libfinc_hip.so; there is no CPU path.
 """
 from abc import ABCMeta, abstractmethod
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -34,6 +35,45 @@ def _per_image_logdet(logdet, out):
     if not torch.is_tensor(logdet):
         return out.new_full((len(out),), float(logdet))
     return logdet.expand(len(out)) if logdet.dim() == 0 else logdet
+
+
+class BackwardNeeds(NamedTuple):
+    """What a `backward_from_output` call has to produce (everything else comes back as None and costs no launch)."""
+    input: bool = True           # the rebuilt input: what the layer in front is handed as ITS output
+    grad_input: bool = True
+    grad_context: bool = False
+    params: object = True        # one bool for all of `list(layer.parameters())`, or one per parameter
+
+
+def _param_needs(layer, needs):
+    """`needs.params` per parameter of `layer`, False for a frozen one."""
+    params = list(layer.parameters())
+    asked = [bool(needs.params)] * len(params) if isinstance(needs.params, bool) else list(needs.params)
+    if len(asked) != len(params):
+        raise ValueError("needs.params must hold one entry per parameter of the layer")
+    return params, [a and p.requires_grad for a, p in zip(asked, params)]
+
+
+def _params_on_device(x, *params):
+    return all(p.dtype == torch.float32 and p.device == x.device for p in params)
+
+
+def _unit_backward_from_output(cache, cache_args, y, grad_y, need_x, need_gx, need_gw):
+    """The invertible backward of a unit on the cache `cache`: x = inverse(y) without the invariant check (the training path: the
+    in-kernel gradient mask keeps the corner tap unit triangular, and a check per unit and step is a host synchronisation), then
+    `ops.finc_backward` at (grad_y, x) and canonical -> stored as `ops._FincConvFunction.backward` does.  There is no re-forward.
+    Returns (x, grad_x, [grad of each stored bank] or None)."""
+    weights, G, orient = cache_args
+    x = gx = gws = None
+    if need_x or need_gw:
+        x = cache.inverse(y.contiguous(), weights, G, orient, validate=False)
+    if need_gx or need_gw:
+        w_canon = cache._get(weights, G, orient, validate=False).w_canon         # (same entry: no check, no synchronisation)
+        gx, gw = ops.finc_backward(grad_y.contiguous(), x, w_canon, G, orient, need_gx=need_gx, need_gw=need_gw)
+        if gw is not None:
+            gw = ops.canonicalize(gw, G, orient)  # canonical -> stored orientation
+            gws = list(gw.chunk(len(weights), dim=0)) if len(weights) > 1 else [gw]
+    return x, gx, gws
 
 
 class FlowLayer(nn.Module, metaclass=ABCMeta):
@@ -59,6 +99,19 @@ class FlowLayer(nn.Module, metaclass=ABCMeta):
         out = self.reverse(input, context)
         out = out[0] if isinstance(out, tuple) else out
         return out, _per_image_logdet(self.forward(out, context)[1], out)
+
+    # The protocol of `FlowSequential.invertible_backward`: a layer that can differentiate from its OUTPUT.
+    def invertible_backward_supported(self, input, context=None):
+        """Can `backward_from_output` serve a `forward(input, context)` call?  Reads the tensors' shape, dtype and device only (the
+        container asks before the activations exist).  A layer from elsewhere inherits this False and keeps its stored activations."""
+        return False
+
+    def backward_from_output(self, output, grad_output, grad_logdet, context, needs):
+        """Given `forward`'s output, the gradient that reaches it, the gradient of the log-det ([B] or None) and a `BackwardNeeds`:
+        `(input, grad_input, grad_context, param_grads)` -- the input REBUILT from the output and the gradients taken there, in the
+        same pass.  `param_grads` is aligned with `list(self.parameters())`; whatever `needs` does not ask for, and the gradient of
+        a frozen parameter, is None."""
+        raise NotImplementedError
 
     def reconstruct_forward(self, input, context=None):
         return self.forward(input)
@@ -166,6 +219,22 @@ class PaddedConv2d(FlowLayer):
         out = self.reverse(x, context)[0]
         return out, out.new_zeros(len(out))
 
+    def invertible_backward_supported(self, x, context=None):
+        # (a `conv.bias` set by hand, the reference's dead branch, keeps the stored path)
+        return _hip_tensor(x) and self.conv.bias is None and _params_on_device(x, *self.parameters())
+
+    def backward_from_output(self, output, grad_output, grad_logdet, context, needs):
+        """x = inverse(output - bias), then the HIP backward at (grad_output, x); the bias gradient is grad_output summed per channel."""
+        params, asked = _param_needs(self, needs)
+        want = {id(p): a for p, a in zip(params, asked)}
+        y = output if self.bias is None else output - self.bias.detach().view(1, -1, 1, 1)
+        x, gx, gws = _unit_backward_from_output(self._cache, self._cache_args(), y, grad_output, needs.input, needs.grad_input,
+                                                want[id(self.conv.weight)])
+        grads = {id(self.conv.weight): gws[0] if gws is not None else None}
+        if self.bias is not None and want[id(self.bias)]:
+            grads[id(self.bias)] = grad_output.sum(dim=(0, 2, 3))
+        return x, gx, None, [grads.get(id(p)) for p in params]
+
     def logdet(self, x=None, context=None):
         return 0.0
 
@@ -209,6 +278,18 @@ class FastFlowUnit(nn.Module):
         """`reverse(x)` and the unit's log-det per image: zeros (four unit-triangular banks)."""
         out = self.reverse(x, context)
         return out, out.new_zeros(len(out))
+
+    def invertible_backward_supported(self, x, context=None):
+        return _hip_tensor(x) and _params_on_device(x, *self.parameters())
+
+    def backward_from_output(self, output, grad_output, grad_logdet, context, needs):
+        """x = inverse(output) on the cached bank, then the HIP backward at (grad_output, x): the log-det is 0, `grad_logdet` does not
+        enter.  Weight gradients are zero under the corner-tap mask, as on the stored path."""
+        params, asked = _param_needs(self, needs)
+        x, gx, gws = _unit_backward_from_output(self._cache, self._cache_args(), output, grad_output, needs.input, needs.grad_input,
+                                                any(asked))
+        grads = {id(w): g for w, g in zip(self._weights(), gws)} if gws is not None else {}
+        return x, gx, None, [grads.get(id(p)) if a else None for p, a in zip(params, asked)]
 
     def reverse_level2(self, x):
         """fastflow.py:78-100 without the 6 flip/cat/zeros copies: the kernel indexes the flipped pixel."""
@@ -283,6 +364,12 @@ class CINCFlowUnit(nn.Module):
     def reverse_level1(self, x):
         return self.conv_tl.reverse(x)[0]
 
+    def invertible_backward_supported(self, x, context=None):
+        return self.conv_tl.invertible_backward_supported(x, context)
+
+    def backward_from_output(self, output, grad_output, grad_logdet, context, needs):
+        return self.conv_tl.backward_from_output(output, grad_output, grad_logdet, context, needs)
+
 
 def load_reference_checkpoint(model, checkpoint, strict=True, validate=True, trust_pickle=False):
     """Load a reference training checkpoint (train/experiment.py:400-427: a dict holding 'model_state_dict',
@@ -350,6 +437,45 @@ class StandardNormal(nn.Module):
         return torch.randn(n_samples, *self.size, device=self._anchor.device), None
 
 
+class _InvertibleRunFunction(torch.autograd.Function):
+    """A run of layers that support `backward_from_output`, as one autograd node (FlowSequential.invertible_backward).
+    Inputs: the activation, the context, every parameter of the run.  Outputs: the run's output and its summed log-det [B].
+    Forward: the no-grad pass of `FlowSequential.forward` over the run, folds included.  Saved: the run's OUTPUT and the context --
+    nothing per layer.  Backward: the layers last to first, each rebuilding its input from its output and differentiating there; a
+    rebuilt activation lives until the layer in front has consumed it.  The saved output is never written, so the backward can run
+    again under `retain_graph=True`."""
+
+    @staticmethod
+    def forward(ctx, seq, run, x, context, *params):
+        out, logdet = seq._forward_layers(list(run), x, context, x.new_zeros(len(x)))
+        ctx.run = run
+        ctx.counts = [len(list(m.parameters())) for m in run]
+        ctx.save_for_backward(out, context)
+        return out, logdet
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out, grad_logdet):
+        out, context = ctx.saved_tensors
+        need_x, need_ctx, need_p = ctx.needs_input_grad[2], ctx.needs_input_grad[3], ctx.needs_input_grad[4:]
+        grad, gld = ops._incoming_grads(out, grad_out, grad_logdet)
+        starts = [sum(ctx.counts[:k]) for k in range(len(ctx.run))]
+        pgrads, gctx, y = [None] * len(need_p), None, out
+        for k in reversed(range(len(ctx.run))):
+            upstream = need_x or need_ctx or any(need_p[:starts[k]])     # does anything in front of this layer want a gradient?
+            needs = BackwardNeeds(input=k > 0 and upstream, grad_input=upstream, grad_context=need_ctx,
+                                  params=tuple(need_p[starts[k]:starts[k] + ctx.counts[k]]))
+            y, grad, gc, pg = ctx.run[k].backward_from_output(y, grad, gld, context, needs)
+            pgrads[starts[k]:starts[k] + ctx.counts[k]] = pg
+            if gc is not None:
+                gctx = gc if gctx is None else gctx + gc
+            if not upstream:
+                break
+        if out.is_cuda:
+            _lib.raise_if_faulted("FlowSequential.invertible_backward")
+        return (None, None, grad if need_x else None, gctx) + tuple(pgrads)
+
+
 class FlowSequential(nn.Module):
     """Protocol-compatible stand-in for layers/flowsequential.py:9-115 (the reference file cannot travel to
     the GPU box and hard-imports wandb + a cuDNN-only extension).  Only what the hot path's callers use."""
@@ -365,8 +491,16 @@ class FlowSequential(nn.Module):
         yield from self.sequence_modules
 
     def forward(self, input, context=None, compute_expensive=False):
-        logdet = 0
         mods = list(self.sequence_modules)
+        if self.invertible_backward and torch.is_grad_enabled():
+            output, logdet = self._forward_invertible(mods, input, context)
+        else:
+            output, logdet = self._forward_layers(mods, input, context)
+        logprob = self.base_distribution.log_prob(output)
+        return output, logprob + logdet
+
+    def _forward_layers(self, mods, input, context, logdet=0):
+        """`mods` in order on `input`: (output, `logdet` plus the sum of their log-dets)."""
         i = 0
         while i < len(mods):
             module = mods[i]
@@ -384,8 +518,49 @@ class FlowSequential(nn.Module):
             logdet += layer_logdet
             input = output
             i += 1
-        logprob = self.base_distribution.log_prob(input)
-        return output, logprob + logdet
+        return input, logdet
+
+    #: train without stored activations: while `forward` records an autograd graph, every maximal run of two or more
+    #: layers that can differentiate from their output (`invertible_backward_supported`) is ONE autograd node that keeps the run's
+    #: output and nothing else; its backward walks the run from the back, each layer rebuilding its input (`backward_from_output`).
+    #: Off by default; set per instance.  Costs an inverse per layer and step.
+    invertible_backward = False
+
+    def _invertible_run_end(self, mods, i, input, context):
+        """The end j of the maximal run mods[i:j] of layers that support `backward_from_output` for this call.  The layers judge a
+        tensor's shape, dtype and device only, so the activations between them need not exist yet: a layer that changes the shape
+        (`invertible_output_shape`) hands on a stand-in of one element expanded to the new shape."""
+        probe, j = input, i
+        while j < len(mods):
+            supported = getattr(mods[j], "invertible_backward_supported", None)
+            if supported is None or not supported(probe, context):
+                break
+            shape = getattr(mods[j], "invertible_output_shape", None)
+            if shape is not None:
+                probe = probe.new_empty((1,)).expand(shape(tuple(probe.shape)))
+            j += 1
+        return j
+
+    def _forward_invertible(self, mods, input, context):
+        """`_forward_layers` with every run of two or more supporting layers that has something to differentiate behind one
+        `_InvertibleRunFunction`; every other layer runs as it always has, with its stored activations."""
+        logdet = 0
+        i = 0
+        while i < len(mods):
+            j = self._invertible_run_end(mods, i, input, context)
+            if j - i >= 2:
+                run = tuple(mods[i:j])
+                params = [p for m in run for p in m.parameters()]
+                if (input.requires_grad or (context is not None and context.requires_grad) or any(p.requires_grad for p in params)):
+                    input, run_logdet = _InvertibleRunFunction.apply(self, run, input, context, *params)
+                    logdet = logdet + run_logdet
+                    i = j
+                    continue
+            output, layer_logdet = mods[i](input, context)
+            logdet = logdet + layer_logdet
+            input = output
+            i += 1
+        return input, logdet
 
     def log_prob(self, input, context=None, compute_expensive=True):
         return self.forward(input, context, compute_expensive)[1]

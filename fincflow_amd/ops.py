@@ -438,6 +438,32 @@ def finc_coupling_reverse_logdet_backward(grad_y, grad_logdet, y, raw, a, b, nee
     return gx, graw, ga, gb
 
 
+def finc_coupling_backward_reconstruct(grad_y, grad_logdet, y, raw, a, b, need_x=True, need_gx=True, need_graw=True, need_ga=True,
+                                       need_gb=True):
+    """Gradients of `finc_coupling(..., direction=1, want_logdet=True)` from the forward's OUTPUT `y`, and the forward's input rebuilt
+    in the same launch (include/finc.h: finc_coupling_backward_reconstruct_f32): (x, grad_x, grad_raw, grad_a, grad_b), each computed
+    only if asked for (None otherwise).  `x` has the bits of `finc_coupling(y, raw, a, b, -1)`; grad_x[:, :C/2] is grad_y[:, :C/2] (the
+    net's share is the caller's).  grad_logdet [B] or None (zeros).  Fixed-order sums: the same inputs give the same bits."""
+    _coupling_args(y, raw, a, b, "output")
+    _require_device(grad_y, "grad_output")
+    if grad_y.shape != y.shape or grad_y.device != y.device:
+        raise ValueError("grad_output must match the forward's output in shape and device")
+    B, C, H, W = y.shape
+    _per_image(grad_logdet, "grad_logdet", y)
+    x = torch.empty_like(y) if need_x else None
+    gx = torch.empty_like(y) if need_gx else None
+    graw = torch.empty_like(raw) if need_graw else None
+    ga = torch.empty(C, dtype=torch.float32, device=y.device) if need_ga else None
+    gb = torch.empty(C, dtype=torch.float32, device=y.device) if need_gb else None
+    if _nothing_to_launch(y, (x, gx, graw, ga, gb), (ga, gb)):
+        return x, gx, graw, ga, gb
+    nbytes = _lib.lib().finc_coupling_workspace_bytes(B, C, H * W) if (need_ga or need_gb) else None
+    _call("finc_coupling_backward_reconstruct_f32", y.device, grad_y.data_ptr(), _ptr(grad_logdet), y.data_ptr(), raw.data_ptr(),
+          a.data_ptr(), b.data_ptr(), _ptr(x), _ptr(gx), _ptr(graw), _ptr(ga), _ptr(gb), B, C, H * W, *_ws_args(y.device, nbytes),
+          _stream_ptr(y))
+    return x, gx, graw, ga, gb
+
+
 def _incoming_grads(like, grad_y, grad_logdet):
     """What a (y, logdet) Function's backward is handed, as the kernels take it: contiguous, zeros for a `y` nobody used (None)."""
     grad_y = torch.zeros_like(like) if grad_y is None else grad_y
@@ -591,6 +617,30 @@ def finc_actnorm_backward(grad_y, grad_logdet, y, log_scale, need_gx=True, need_
     _call("finc_actnorm_backward_f32", y.device, grad_y.data_ptr(), _ptr(grad_logdet), y.data_ptr(), log_scale.data_ptr(), _ptr(gx),
           _ptr(gls), _ptr(gt), B, C, H * W, *_ws_args(y.device, nbytes), _stream_ptr(y))
     return gx, gls, gt
+
+
+def finc_actnorm_backward_reconstruct(grad_y, grad_logdet, y, log_scale, translation, need_x=True, need_gx=True, need_gls=True,
+                                      need_gt=True):
+    """`finc_actnorm_backward` that rebuilds the forward's input from the same read of `y` (include/finc.h:
+    finc_actnorm_backward_reconstruct_f32): (x, grad_x, grad_log_scale, grad_translation), each computed only if asked for (None
+    otherwise).  `x` has the bits of `finc_actnorm(y, log_scale, translation, -1)`.  One launch (plus the small fixed-order reduce
+    with a per-channel gradient): the same inputs give the same bits."""
+    _actnorm_args(y, log_scale, translation, "output")
+    _require_device(grad_y, "grad_output")
+    if grad_y.shape != y.shape or grad_y.device != y.device:
+        raise ValueError("grad_output must match the forward's output in shape and device")
+    B, C, H, W = y.shape
+    _per_image(grad_logdet, "grad_logdet", y)
+    x = torch.empty_like(y) if need_x else None
+    gx = torch.empty_like(y) if need_gx else None
+    gls = torch.empty(C, dtype=torch.float32, device=y.device) if need_gls else None
+    gt = torch.empty(C, dtype=torch.float32, device=y.device) if need_gt else None
+    if _nothing_to_launch(y, (x, gx, gls, gt), (gls, gt)):
+        return x, gx, gls, gt
+    nbytes = _lib.lib().finc_actnorm_workspace_bytes(B, C, H * W) if (need_gls or need_gt) else None
+    _call("finc_actnorm_backward_reconstruct_f32", y.device, grad_y.data_ptr(), _ptr(grad_logdet), y.data_ptr(), log_scale.data_ptr(),
+          translation.data_ptr(), _ptr(x), _ptr(gx), _ptr(gls), _ptr(gt), B, C, H * W, *_ws_args(y.device, nbytes), _stream_ptr(y))
+    return x, gx, gls, gt
 
 
 def finc_actnorm_reverse_backward(grad_y, x, log_scale, need_gx=True, need_gls=True, need_gt=True):
@@ -868,8 +918,9 @@ class PackedWeights:
         _launch_packed(name, t, _packed(bank, "inv", "finc_pack_inverse_weights_f32", t, G, dims), out, G, dims, orient)
         return out
 
-    def inverse(self, z, weights, G, orient, out=None):
-        bank, dims = self._enter(z, weights, G, orient)
+    def inverse(self, z, weights, G, orient, out=None, validate=True):
+        """`validate=False`: the training path's inverse (the backward that rebuilds a unit's input from its output), as in `_get`."""
+        bank, dims = self._enter(z, weights, G, orient, validate)
         if out is None and z.numel():
             out = torch.empty_like(z)
         # the packed launch needs an MFMA instantiation AND 16-byte aligned activations

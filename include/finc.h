@@ -336,6 +336,19 @@ int finc_mix_backward_f32(const float *grad_out, const float *in, const float *m
  *     grad_h[:, 2j] = (-(grad_y2 * y[:, half+j]) + grad_logdet[b]) * (1 - th_j^2)
  *   and everything else as there.  With grad_logdet NULL every output has the bits finc_coupling_reverse_backward_f32 gives.
  *   Outputs, workspace, aliasing and status as for finc_coupling_reverse_backward_f32.
+ * finc_coupling_backward_reconstruct_f32: the gradients of direction +1 (layers/coupling.py:79-92) given grad_y, grad_logdet [B]
+ *   (NULL = zeros) and `y`, the forward's OUTPUT, with the forward's input rebuilt in the same pass (:95-101) -- what a training
+ *   backward that stores no activations runs per coupling, instead of finc_coupling_f32(direction -1) + finc_coupling_backward_f32.
+ *   With th_j = tanh(u_j / 2), s_j = 2 th_j, E_j = exp(s_j) recomputed from raw:
+ *     x_out[:, :half] = y[:, :half],   x_out[:, half+j] = (y[:, half+j] - t_j) / E_j    (the bits of finc_coupling_f32, direction -1)
+ *     grad_x[:, :half] = grad_y[:, :half]  (what reaches x[:, :half] through the net is the caller's, as above)
+ *     grad_x[:, half+j] = grad_y2 * E_j                         with grad_y2 = grad_y[:, half+j]
+ *     grad_h[:, 2j+1] = grad_y2,   grad_h[:, 2j] = (grad_y2 * (y[:, half+j] - t_j) + grad_logdet[b]) * (1 - th_j^2)
+ *     grad_raw[:, c] = a[c] * grad_h[:, c],   grad_a[c] = sum_{b,p} grad_h[b,c,p] * raw[b,c,p],   grad_b[c] = sum_{b,p} grad_h[b,c,p]
+ *   Every output is OVERWRITTEN; x_out and each gradient may be NULL to skip it, not all of them.  Aliasing: x_out == y and
+ *   grad_x == grad_y are allowed (in place); any other output on grad_y, y, raw or on another output is FINC_ERR_BAD_DIMS.
+ *   Workspace (grad_a / grad_b only) and status as for finc_coupling_backward_f32.  A channel with |t| >> |y - t| loses digits
+ *   in y - t: x_out and grad_h[:, 2j] carry that cancellation, which the stored-input form does not have.
  * finc_bias_relu_f32: out = max(in + bias[c], 0) -- the Conv2d bias and the nn.ReLU behind the net's first two convolutions
  *   (layers/coupling.py:58-63) in one pass; in == out allowed.  Inference only (no backward).
  * Rows of HW floats move as 16-byte pieces when HW % 4 == 0 and every activation pointer is 16-byte aligned, as dwords otherwise.
@@ -358,6 +371,10 @@ int finc_coupling_reverse_logdet_backward_f32(const float *grad_y, const float *
                                               const float *a, const float *b, float *grad_x, float *grad_raw, float *grad_a,
                                               float *grad_b, int B, int C, int HW, void *workspace, size_t workspace_bytes,
                                               finc_stream_t stream);
+int finc_coupling_backward_reconstruct_f32(const float *grad_y, const float *grad_logdet, const float *y, const float *raw,
+                                           const float *a, const float *b, float *x_out, float *grad_x, float *grad_raw,
+                                           float *grad_a, float *grad_b, int B, int C, int HW, void *workspace,
+                                           size_t workspace_bytes, finc_stream_t stream);
 int finc_bias_relu_f32(const float *in, const float *bias, float *out, int B, int C, int HW, finc_stream_t stream);
 
 /*
@@ -374,6 +391,13 @@ int finc_bias_relu_f32(const float *in, const float *bias, float *out, int B, in
  *     grad_log_scale[c]   = -sum_{b,p} grad_y[b,c,p] * y[b,c,p]  -  HW * sum_b grad_logdet[b]
  *   Every output is OVERWRITTEN; any may be NULL to skip it, not all of them.  grad_x == grad_y allowed, grad_x == y is not
  *   (FINC_ERR_BAD_DIMS).  The two per-channel outputs need the workspace; their sums run in a fixed order (no atomics).
+ * finc_actnorm_backward_reconstruct_f32: finc_actnorm_backward_f32 -- the same three formulas, the same fixed-order sums -- that
+ *   from the same read of `y` also rebuilds the forward's input (layers/actnorm.py:51):
+ *     x_out[b,c,p] = y[b,c,p] * exp(log_scale[c]) + translation[c]        (the bits of finc_actnorm_f32, direction -1)
+ *   What a training backward that stores no activations runs per ActNorm, instead of finc_actnorm_f32(direction -1) +
+ *   finc_actnorm_backward_f32.  grad_logdet, x_out and each gradient may be NULL, not every output; `translation` is read for
+ *   x_out only (NULL without it).  Aliasing: x_out == y and grad_x == grad_y are allowed (in place); x_out on grad_y or grad_x,
+ *   and grad_x on y, are FINC_ERR_BAD_DIMS.  Workspace and status as for finc_actnorm_backward_f32.
  * finc_actnorm_reverse_backward_f32: gradients of the reverse direction (replaces autograd through layers/actnorm.py:47-52) from
  *   grad_y, log_scale and `x`, the reverse's INPUT (the output would do in real arithmetic, x * exp(log_scale) = y - translation, but
  *   that difference cancels on a channel whose translation dwarfs its spread):
@@ -399,6 +423,10 @@ int finc_actnorm_f32(const float *x, const float *log_scale, const float *transl
 int finc_actnorm_backward_f32(const float *grad_y, const float *grad_logdet, const float *y, const float *log_scale, float *grad_x,
                               float *grad_log_scale, float *grad_translation, int B, int C, int HW, void *workspace,
                               size_t workspace_bytes, finc_stream_t stream);
+int finc_actnorm_backward_reconstruct_f32(const float *grad_y, const float *grad_logdet, const float *y, const float *log_scale,
+                                          const float *translation, float *x_out, float *grad_x, float *grad_log_scale,
+                                          float *grad_translation, int B, int C, int HW, void *workspace, size_t workspace_bytes,
+                                          finc_stream_t stream);
 int finc_actnorm_reverse_backward_f32(const float *grad_y, const float *x, const float *log_scale, float *grad_x, float *grad_log_scale,
                                       float *grad_translation, int B, int C, int HW, void *workspace, size_t workspace_bytes,
                                       finc_stream_t stream);
