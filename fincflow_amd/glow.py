@@ -35,6 +35,17 @@ from . import ops
 from .layers import FastFlowUnit, FlowLayer, FlowSequential, _hip_tensor, _param_needs, _params_on_device, _records_graph
 
 
+class _DerivedValues:
+    """A layer that keeps values derived from its parameters per parameter version (`ops.version_key`), each with its `ops.Ready`
+    token: the stream it was built on and the event behind its fill, asked in front of every use.  A copy of the layer
+    (copy.deepcopy for an EMA model, pickle, torch.save of the module) starts without any of them, as a copy of `ops.PackedWeights`
+    does: its first call rebuilds them from ITS parameters, and an event belongs to the process and stream that recorded it."""
+    _derived = ()
+
+    def __getstate__(self):
+        return {k: v for k, v in self.__dict__.items() if k not in self._derived}
+
+
 class Squeeze(FlowLayer):
     def forward(self, input, context=None):
         b, c, h, w = input.shape
@@ -184,12 +195,15 @@ class ActNorm(FlowLayer):
         return -self.log_scale.sum().expand(input.size(0)) * pixels
 
 
-class Conv1x1(FlowLayer):
+class Conv1x1(_DerivedValues, FlowLayer):
     """layers/conv1x1.py:8-49.  Device tensors in fp32 with a channel count the library instantiates run on the HIP mixing
     kernel: inference / sampling (no autograd graph) as one streaming launch (`ops.finc_mix`), `forward` under autograd through
     `ops.mix_forward` (backward: finc_mix_backward_f32), and so does `reverse` under autograd inside `ops.reverse_grad()` (what
     `FlowSequential.rsample` records), on `torch.inverse(W)` -- a recorded [C, C] op -- or, with W frozen, on the cached inverse.
     Everything else -- CPU tensors, fp64, other channel counts, `reverse` under autograd outside that context -- keeps F.conv2d."""
+
+    _derived = ("_w_inv", "_inv_key", "_inv_ready", "_ld", "_ld_key", "_ld_ready", "_m_aff", "_b_aff", "_aff_key", "_aff_ready",
+                "_m_lead", "_b_lead", "_lead_key", "_lead_inv", "_lead_obj", "_lead_ready")
 
     def __init__(self, n_channels):
         super().__init__()
@@ -219,8 +233,10 @@ class Conv1x1(FlowLayer):
         if getattr(self, "_inv_key", None) != key:
             with torch.no_grad():
                 self._w_inv = torch.inverse(self.W.detach()).contiguous()
-            self._inv_key = key
+            self._inv_key, self._inv_ready = key, ops.Ready(self.W.device)
             self._aff_key = None
+        else:
+            self._inv_ready.wait(self._w_inv)
         return self._w_inv
 
     def _hip_reverse_grad(self, z):
@@ -263,7 +279,9 @@ class Conv1x1(FlowLayer):
         if getattr(self, "_ld_key", None) != key:
             with torch.no_grad():
                 self._ld = torch.slogdet(self.W.detach())[1]
-            self._ld_key = key
+            self._ld_key, self._ld_ready = key, ops.Ready(self.W.device)
+        else:
+            self._ld_ready.wait(self._ld)
         return self._ld
 
     def mix_logdet(self, x):
@@ -287,7 +305,9 @@ class Conv1x1(FlowLayer):
             with torch.no_grad():
                 self._m_aff = (torch.exp(log_scale.detach().float()).view(-1, 1) * w_inv).contiguous()
                 self._b_aff = translation.detach().float().contiguous()
-            self._aff_key = key
+            self._aff_key, self._aff_ready = key, ops.Ready(z.device)
+        else:
+            self._aff_ready.wait(self._m_aff, self._b_aff)
         return ops.finc_mix(z.contiguous(), self._m_aff, self._b_aff)
 
     def reverse_premultiplied(self, z, lead, log_scale=None, translation=None):
@@ -312,7 +332,9 @@ class Conv1x1(FlowLayer):
                 blk = torch.block_diag(*lead.double().unbind(0))
                 self._m_lead = (blk @ m).float().contiguous()
                 self._b_lead = None if b is None else (blk @ b).float().contiguous()
-            self._lead_key, self._lead_inv, self._lead_obj = key, w_inv, lead
+            self._lead_key, self._lead_inv, self._lead_obj, self._lead_ready = key, w_inv, lead, ops.Ready(z.device)
+        else:
+            self._lead_ready.wait(self._m_lead, self._b_lead)
         return ops.finc_mix(z.contiguous(), self._m_lead, self._b_lead)
 
     def logdet(self, input, context=None):
@@ -334,7 +356,7 @@ class Conv2dZero(nn.Module):
         return out * torch.exp(self.logs * self.logscale_factor).view(1, -1, 1, 1)
 
 
-class Coupling(FlowLayer):
+class Coupling(_DerivedValues, FlowLayer):
     """layers/coupling.py:44-105.  Device tensors in fp32 with an even channel count run everything behind the net's last convolution
     on the HIP coupling kernel (`ops.finc_coupling`: affine transform, log-det and the copy of the untouched half in one launch).
     Without an autograd graph (inference, sampling) the net's `Conv2d(bias) + ReLU` pairs are `F.conv2d(bias=None)` +
@@ -343,6 +365,8 @@ class Coupling(FlowLayer):
     `FlowSequential.rsample` records), through `ops.coupling_reverse` (backward: finc_coupling_reverse_backward_f32, from the saved
     OUTPUT).  Everything else -- CPU tensors, fp64, odd channel counts, `reverse` under autograd outside that context -- keeps the
     PyTorch formula below."""
+
+    _derived = ("_ab", "_ab_key", "_ab_ready")
 
     def __init__(self, input_size, width=512, n_context=None):
         super().__init__()
@@ -390,12 +414,13 @@ class Coupling(FlowLayer):
         last = self.net[4]
         key = ops.version_key(last.logs, last.bias) + (last.logs.device,)
         if getattr(self, "_ab_key", None) == key:
+            self._ab_ready.wait(*self._ab)
             return self._ab
         with torch.no_grad():
             a, b = self._scale_shift()
             ab = (a.contiguous(), b.contiguous())
-        if not torch.cuda.is_current_stream_capturing():
-            self._ab, self._ab_key = ab, key
+        if not (last.logs.is_cuda and ops._capturing()):
+            self._ab, self._ab_key, self._ab_ready = ab, key, ops.Ready(last.logs.device)
         return ab
 
     def _net_input(self, x, context):

@@ -109,6 +109,74 @@ def version_key(*tensors):
     return (_steps[0],) + tuple(v for t in tensors for v in (t.data_ptr(), t._version))
 
 
+def _current_stream(device):
+    return torch.cuda.current_stream(device)
+
+
+_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+
+
+def _current_handle(device):
+    """The current stream's handle on `device`: what a token compares on every use until it is done.  torch's raw getter where the
+    build has it (a thread-local read: no Stream object is made for the comparison), else the public one."""
+    if _raw_stream is not None and device.index is not None:
+        return _raw_stream(device.index)
+    return _current_stream(device).cuda_stream
+
+
+def _capturing():
+    return torch.cuda.is_current_stream_capturing()
+
+
+CAPTURE_IN_FLIGHT = ("a value derived from the parameters is still being built on another stream: synchronise (or let the capturing stream "
+                     "wait for the stream that first used the module) before capturing")
+
+
+class Ready:
+    """The readiness token of ONE cache entry of values derived from parameters (the banks of PackedWeights, the folded matrices of
+    glow.Conv1x1, glow.Coupling's scale and shift): made where the entry is built, right behind its last fill launch, it keeps the
+    building stream's handle, an event recorded there and a `done` flag.  `wait(*tensors)` in front of every use of the entry:
+
+      * `done`, or the current stream is the building stream: nothing (stream order covers it);
+      * the event has completed: `done` for good -- the event is never asked again;
+      * otherwise the current stream waits for the event, and the entry's tensors are marked as used on it (`record_stream`: their
+        memory is not handed out again while this stream may still read it).  Inside a stream capture that raises instead: an event
+        from outside must not enter the graph.
+
+    An entry on the host is born `done`.  An entry built INSIDE a capture has no event (it is filled when the graph replays, in the
+    graph's own order); another stream that asks for it is refused."""
+    __slots__ = ("stream", "event", "done")
+
+    def __init__(self, device):
+        self.stream = self.event = None
+        self.done = device.type != "cuda"
+        if not self.done:
+            stream = _current_stream(device)
+            self.stream = stream.cuda_stream
+            if not _capturing():
+                self.event = stream.record_event()
+
+    def wait(self, *tensors):
+        if self.done:
+            return
+        device = tensors[0].device
+        if _current_handle(device) == self.stream:
+            return
+        stream = _current_stream(device)
+        if self.event is None:
+            raise RuntimeError("a value derived from the parameters was built inside a stream capture and is asked for on another "
+                               "stream: call the module once outside the capture first")
+        if self.event.query():
+            self.done = True
+            return
+        if _capturing():
+            raise RuntimeError(CAPTURE_IN_FLIGHT)
+        stream.wait_event(self.event)
+        for t in tensors:
+            if t is not None:
+                t.record_stream(stream)
+
+
 def _nothing_to_launch(x, grads, sums):
     """An empty batch (the sums over it are zero) or no gradient asked for: `grads` is the result as it stands."""
     if x.numel() == 0:
@@ -748,16 +816,19 @@ def inverse(input, kernel, output):
 
 class _DeviceBank:
     """What PackedWeights holds for ONE device and ONE weight version: a new version starts from a fresh object."""
-    __slots__ = ("key", "keep", "validated", "w_canon", "linv", "packed", "adjoint")
+    __slots__ = ("key", "keep", "validated", "w_canon", "ready", "linv", "linv_ready", "packed", "adjoint", "adjoint_ready")
 
     def __init__(self, key=None, keep=None, w_canon=None):
         self.key = key
         self.keep = keep          # the source tensors' storages, kept alive while the entry is (see PackedWeights._get)
         self.validated = False    # check_invariant has run on THIS weight version
         self.w_canon = w_canon
-        self.linv = None
-        self.packed = {}          # bank kind -> (key of the folded affine parameters or None, packed fragments)
+        # (every derived tensor below has its `Ready` token: the stream it was built on, and the event behind its fill)
+        self.ready = Ready(w_canon.device) if w_canon is not None else None
+        self.linv = self.linv_ready = None
+        self.packed = {}          # bank kind -> (key of the folded affine parameters or None, packed fragments, their token)
         self.adjoint = None       # (w_adj, lead_t) of the backward through the inverse (finc_adjoint_weights_f32), built by the first one
+        self.adjoint_ready = None
 
 
 def _fold_forward(log_scale, translation):
@@ -779,6 +850,7 @@ def _packed(bank, kind, pack, t, G, dims, fold=None, params=(), may_refuse=False
     key = version_key(*params) if fold is not None else None
     hit = bank.packed.get(kind)
     if hit is not None and hit[0] == key:
+        hit[2].wait(hit[1])
         return hit[1]
     B, Cq, H, W, KH, KW = dims
     affine = ()
@@ -791,7 +863,7 @@ def _packed(bank, kind, pack, t, G, dims, fold=None, params=(), may_refuse=False
     if _call(pack, t.device, (bank.w_canon if src is None else src).data_ptr(), *affine, packed.data_ptr(), G, Cq, KH, KW, _stream_ptr(t),
              may_refuse=may_refuse):
         return None
-    bank.packed[kind] = (key, packed)
+    bank.packed[kind] = (key, packed, Ready(t.device))
     return packed
 
 
@@ -873,6 +945,8 @@ class PackedWeights:
             ws = torch.cat([w.detach() for w in weights], dim=0).contiguous() if len(weights) > 1 else weights[0].detach().contiguous()
             # (a fresh entry: not validated, no packed fragments of any kind, no Linv)
             bank = self._banks[device] = _DeviceBank(key, tuple(w.untyped_storage() for w in weights), canonicalize(ws, G, orient))
+        else:
+            bank.ready.wait(bank.w_canon)
         # An entry the training path created (validate=False) is NOT validated: the first inference call on the same weight
         # version runs the check, so an optimiser effect outside the in-kernel gradient mask (weight decay on the diagonal,
         # a manual edit followed by a forward under grad) cannot reach the inverse unnoticed.
@@ -950,7 +1024,9 @@ class PackedWeights:
             lead_t = torch.empty(G * Cq, G * Cq, dtype=torch.float32, device=w_canon.device)
             _call("finc_adjoint_weights_f32", w_canon.device, w_canon.data_ptr(), w_adj.data_ptr(), lead_t.data_ptr(), G, Cq, KH, KW,
                   _stream_ptr(grad_x))
-            bank.adjoint = (w_adj, lead_t)
+            bank.adjoint, bank.adjoint_ready = (w_adj, lead_t), Ready(w_canon.device)
+        else:
+            bank.adjoint_ready.wait(*bank.adjoint)
         w_adj, lead_t = bank.adjoint
         adj_orient = orient ^ ((1 << (2 * G)) - 1)            # the transposed operator reads the opposite corner
         y = torch.empty_like(grad_x)
@@ -977,6 +1053,9 @@ class PackedWeights:
             lead = wc.view(G, Cq, Cq, wc.shape[2], wc.shape[3])[:, :, :, -1, -1].double()
             eye = torch.eye(Cq, dtype=torch.float64, device=wc.device).expand(G, Cq, Cq)
             bank.linv = torch.linalg.solve_triangular(lead, eye, upper=False, unitriangular=True).float().contiguous()
+            bank.linv_ready = Ready(wc.device)
+        else:
+            bank.linv_ready.wait(bank.linv)
         return bank.linv
 
     def premultiplied_supported(self, shape, weights, G, orient):
