@@ -28,7 +28,7 @@ SYMBOLS = [
     "finc_inverse_kernel_variant", "finc_debug_attr_table_insert", "finc_debug_inverse_table_row",
     "finc_mix_supported_f32", "finc_mix_f32", "finc_pack_forward_weights_affine_f32", "finc_debug_hlp_timeouts",
     "finc_build_flags", "finc_inverse_packed_premultiplied_f32", "finc_inverse_premultiplied_supported", "finc_clear_fault", "finc_debug_backward_variant", "finc_debug_set_forward_form",
-    "finc_debug_row_chunks", "finc_debug_inverse_remainder_images",
+    "finc_debug_row_chunks", "finc_debug_inverse_remainder_images", "finc_debug_gradw_plan", "finc_debug_conv_plan",
     "finc_inverse_affine_supported", "finc_fault_pending", "finc_runtime_switches",
     "finc_debug_clock_probe_begin", "finc_debug_clock_probe_end",
     "finc_mix_backward_workspace_bytes", "finc_mix_backward_f32",
@@ -158,6 +158,8 @@ def lib():
     L.finc_debug_inverse_remainder_images.argtypes = [i, i, i, i, i, i, i]
     L.finc_debug_row_chunks.argtypes = [ctypes.c_longlong, ctypes.c_longlong, i, i, i, i]
     L.finc_debug_set_forward_form.argtypes = [i]
+    L.finc_debug_gradw_plan.argtypes = [i, i, i, i, i, i, i, i, ctypes.POINTER(ctypes.c_longlong)]
+    L.finc_debug_conv_plan.argtypes = [i, i, i, i, i, i, i, i, ctypes.POINTER(ctypes.c_int)]
     L.finc_mix_supported_f32.argtypes = [i]
     L.finc_mix_f32.argtypes = [vp, vp, vp, vp, i, i, i, vp]
     L.finc_mix_backward_workspace_bytes.restype = sz
@@ -230,6 +232,36 @@ def backward_variant(B, G, Cq, H, W, KH, KW):
     form = "scalar" if info[1] == 0 else ("strip", "strip16", "winograd", "msplit", "winograd4", "winograd25", "winograd4m", "stream")[info[2]]
     return {"gradw": ("direct", "dword", "staged", "tiled", "winograd", "winograd_tiled")[info[0]], "gradx_waves": info[1],
             "conv_form": form}
+
+
+GRADW_FORMS = ("direct", "dword", "staged", "tiled", "winograd", "winograd_tiled")
+CONV_FORMS = ("strip", "strip16", "winograd", "msplit", "winograd4", "winograd25", "winograd4m", "stream")
+
+
+def gradw_plan(B, G, Cq, H, W, KH, KW, align=16):
+    """The grad-weight launch plan finc_backward_f32 runs for this shape when grad_z and x are `align` bytes aligned (host-only; the
+    launch's own plan object): `form` (backward_variant's names), `strip` columns per strip, `ns` strips per row, `units` = B * ns that
+    the `wpg` workgroups of a group walk (units > wpg: a second trip through a workgroup's unit loop), `grid` and `block` (x),
+    `mtt` 16-channel tiles per side, `fs` waves per workgroup of the winograd form, `bytes` of partial sums in the workspace."""
+    info = (ctypes.c_longlong * 10)()
+    check(lib().finc_debug_gradw_plan(B, G, Cq, H, W, KH, KW, int(align), info), "finc_debug_gradw_plan")
+    d = dict(zip(("form", "strip", "ns", "units", "wpg", "grid", "block", "mtt", "fs", "bytes"), (int(v) for v in info)))
+    d["form"] = GRADW_FORMS[d["form"]]
+    return d
+
+
+def conv_plan(B, G, Cq, H, W, KH, KW, align=16):
+    """The forward / grad-input launch plan for this shape and alignment, a form pinned by set_forward_form honoured (host-only):
+    `form` (backward_variant's conv_form names), `strip` columns per strip, `ns` strips per row, `waves` per workgroup, `nrc` row
+    chunks of `RC` rows (the last one ragged).  None: the direct kernel."""
+    info = (ctypes.c_int * 6)()
+    st = lib().finc_debug_conv_plan(B, G, Cq, H, W, KH, KW, int(align), info)
+    if st == 3:
+        return None
+    check(st, "finc_debug_conv_plan")
+    d = dict(zip(("form", "strip", "ns", "waves", "nrc", "RC"), (int(v) for v in info)))
+    d["form"] = CONV_FORMS[d["form"]]
+    return d
 
 
 def set_forward_form(form):

@@ -798,6 +798,27 @@ int finc_debug_backward_variant(int B, int G, int Cq, int H, int W, int KH, int 
     return FINC_OK;
 }
 
+// (both plan queries answer from the object the launch runs: finc_gradw_plan, conv_plan and the kernels' FincRowPlan functions)
+int finc_debug_gradw_plan(int B, int G, int Cq, int H, int W, int KH, int KW, int align, long long *info)
+{
+    if (!info) return FINC_ERR_NULL_POINTER;
+    if (int e = check_shape(B, G, Cq, H, W, KH, KW)) return e;
+    if (align != 4 && align != 8 && align != 16) return FINC_ERR_BAD_DIMS;
+    const FincGradwPlan p = finc_gradw_plan(FincShape{B, G, Cq, H, W, KH, KW, 0}, align);
+    const long long v[10] = {p.form, p.strip, p.ns, (long long)B * p.ns, p.wpg, (long long)p.grid.x, (long long)p.block.x, p.mtt, p.fs,
+                             (long long)p.bytes};
+    for (int k = 0; k < 10; ++k) info[k] = p.form ? v[k] : 0;
+    return FINC_OK;
+}
+
+int finc_debug_conv_plan(int B, int G, int Cq, int H, int W, int KH, int KW, int align, int *info)
+{
+    if (!info) return FINC_ERR_NULL_POINTER;
+    if (int e = check_shape(B, G, Cq, H, W, KH, KW)) return e;
+    if (align != 4 && align != 8 && align != 16) return FINC_ERR_BAD_DIMS;
+    return finc_conv_plan_info(FincShape{B, G, Cq, H, W, KH, KW, 0}, align, info);
+}
+
 int finc_debug_set_forward_form(int form) { return finc_wino_set_form(form); }
 
 int finc_debug_inverse_remainder_images(int B, int G, int Cq, int H, int W, int KH, int KW)

@@ -788,4 +788,10 @@ int finc_bigfwd_launch(const float *in, const void *packed, float *out, const Fi
     return FINC_OK;
 }
 
+int finc_bigfwd_waves(const FincShape &s)
+{
+    const BFInst *i = find_bfinst(s.Cq, s.KH, s.KW);
+    return i ? i->nwv : 0;
+}
+
 unsigned finc_build_flags_big() { return FINC_BUILD_FLAGS; }

@@ -210,6 +210,20 @@ int finc_wino5_launch(const float *in, const void *packed, float *out, const Fin
 unsigned finc_build_flags_wino5();
 // info[0..2] = {waves per strip (K-split), staged form (1) or dword form (0), strips per slab}; FINC_ERR_UNSUPPORTED: direct kernel
 int finc_conv_variant(int B, int G, int Cq, int H, int W, int KH, int KW, int *info);
+// The row chunks a forward / grad-input kernel launches with: strips of `strip` columns (`ns` per row), `waves` per workgroup, `nrc`
+// chunks of `RC` rows on grid.y (the last one ragged).  One function per kernel decides them -- conv_plan for the strip kernel,
+// finc_wino_rows (F(2,3) and F(4,3)), finc_wino4m_rows, finc_wino5_rows -- and both its launch and finc_conv_plan_info read that one.
+struct FincRowPlan {
+    int strip = 16, ns = 0, waves = 1;
+    int nrc = 1, RC = 0;
+};
+FincRowPlan finc_wino_rows(const FincShape &s);
+FincRowPlan finc_wino4m_rows(const FincShape &s);
+FincRowPlan finc_wino5_rows(const FincShape &s);
+int finc_bigfwd_waves(const FincShape &s);                             // waves of a workgroup of the big banks' M-split (0: no such bank)
+// info[0..5] = {form (finc_conv_variant's info[1]; a pinned forward form is honoured), strip, ns, waves, nrc, RC} of a call whose
+// activations are `align` bytes aligned; FINC_ERR_UNSUPPORTED: direct kernel
+int finc_conv_plan_info(const FincShape &s, int align, int *info);
 
 // ---- weight gradient, MFMA kernels + a reduce: finc_gradw.hip ----
 // Which kernel a call runs and on which grid: finc_gradw_plan is the one place this is decided (the run-time switches are read there);

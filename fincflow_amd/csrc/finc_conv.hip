@@ -743,4 +743,27 @@ int finc_conv_variant(int B, int G, int Cq, int H, int W, int KH, int KW, int *i
     return FINC_OK;
 }
 
+// the plan of a call, kernel by kernel from the function its launch reads (finc_common.h FincRowPlan)
+int finc_conv_plan_info(const FincShape &s, int align, int *info)
+{
+    const ConvPlan p = conv_plan(s, align);
+    FincRowPlan r;
+    switch (p.form) {
+    case -1: return FINC_ERR_UNSUPPORTED;
+    case 0:
+    case 1: r.ns = (s.W + 15) / 16; r.waves = p.i->nw; r.nrc = p.nrc; r.RC = p.RC; break;
+    case 2:
+    case 4: r = finc_wino_rows(s); break;
+    case 3: r.ns = (s.W + 15) / 16; r.waves = finc_bigfwd_waves(s); r.RC = s.H; break;       // (no row chunks: a workgroup walks the map)
+    case 5: r = finc_wino5_rows(s); break;
+    case 6: r = finc_wino4m_rows(s); break;
+    case 7:                                                                                 // (one workgroup per problem, whole rows)
+        r.strip = s.W; r.ns = 1; r.RC = s.H;
+        (void)finc_stream_info(s, false, nullptr, nullptr, nullptr, &r.waves);
+        break;
+    }
+    info[0] = p.form; info[1] = r.strip; info[2] = r.ns; info[3] = r.waves; info[4] = r.nrc; info[5] = r.RC;
+    return FINC_OK;
+}
+
 unsigned finc_build_flags_conv() { return FINC_BUILD_FLAGS; }

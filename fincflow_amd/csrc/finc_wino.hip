@@ -726,13 +726,16 @@ int finc_wino_pack(const float *wc, void *packed, int G, int Cq, bool transpose,
     return FINC_OK;
 }
 
-int finc_wino_launch(const float *in, const void *packed, float *out, const FincShape &s, hipStream_t st)
+// the strips and row chunks of a launch (finc_common.h FincRowPlan): finc_wino_launch runs them, finc_conv_plan_info reports them
+FincRowPlan finc_wino_rows(const FincShape &s)
 {
+    FincRowPlan r;
     const WInst *i = find_winst(s.Cq);
-    if (!i) return FINC_ERR_UNSUPPORTED;
+    if (!i) return r;
     const bool f4 = finc_wino_form(s) == 4;
-    const int NS = f4 ? (s.W + 63) / 64 : (s.W + 31) / 32;
-    const long long waves = (long long)s.B * s.G * NS;
+    r.strip = f4 ? 64 : 32;
+    r.ns = (s.W + r.strip - 1) / r.strip;
+    const long long waves = (long long)s.B * s.G * r.ns;
     // F(2,3): two waves per SIMD, row chunks up to about one; F(4,3): one wave per SIMD, row chunks (of 8 rows or more: a
     // chunk recomputes two rows of operands) up to that
     static const int force_chunks = finc_env("FINC_WINO_CHUNKS") ? atoi(finc_env("FINC_WINO_CHUNKS")) : 0;   // experiment switch
@@ -745,8 +748,18 @@ int finc_wino_launch(const float *in, const void *packed, float *out, const Finc
     }
     if (force_chunks > 0) nrc = force_chunks;
     if (nrc > s.H / 4) nrc = s.H / 4 > 0 ? s.H / 4 : 1;
-    const int RC = (s.H + nrc - 1) / nrc;
-    nrc = (s.H + RC - 1) / RC;
+    r.RC = (s.H + nrc - 1) / nrc;
+    r.nrc = (s.H + r.RC - 1) / r.RC;
+    return r;
+}
+
+int finc_wino_launch(const float *in, const void *packed, float *out, const FincShape &s, hipStream_t st)
+{
+    const WInst *i = find_winst(s.Cq);
+    if (!i) return FINC_ERR_UNSUPPORTED;
+    const bool f4 = finc_wino_form(s) == 4;
+    const FincRowPlan r = finc_wino_rows(s);
+    const int NS = r.ns, nrc = r.nrc, RC = r.RC;
     static const int skew_mask = finc_env("FINC_WINO_SKEW") ? atoi(finc_env("FINC_WINO_SKEW")) : 0;          // (experiment switches)
     static const int skew_sleep = finc_env("FINC_WINO_SLEEP") ? atoi(finc_env("FINC_WINO_SLEEP")) : 2;
     const float *bank = (const float *)packed + (f4 ? (size_t)s.G * i->npack * 64 : 0);

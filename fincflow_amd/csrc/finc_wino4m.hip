@@ -261,17 +261,30 @@ int finc_wino4m_pack(const float *wc, void *packed, int G, int Cq, bool transpos
     return finc_wino_pack_bank(wc, (float *)packed, G, Cq, i->nw, i->nw, i->nk, 6, transpose, st, scale, shift);
 }
 
+// the strips and row chunks of a launch (finc_common.h FincRowPlan): finc_wino4m_launch runs them, finc_conv_plan_info reports them
+FincRowPlan finc_wino4m_rows(const FincShape &s)
+{
+    FincRowPlan r;
+    const W4mInst *i = find_w4m(s.Cq);
+    if (!i) return r;
+    r.strip = 64;
+    r.ns = (s.W + 63) / 64;
+    r.waves = i->nw;
+    const long long wgs = (long long)s.B * s.G * r.ns;
+    const long long fill = 256 * (4 / i->nw);                              // workgroups of one wave per SIMD that a chip holds at once (every
+                                                                           // chunk recomputes two rows of operands)
+    const int nrc = finc_row_chunks(wgs, fill, s.H, 8, 2);                 // (rounds x rows per chunk: finc_common.h)
+    r.RC = (s.H + nrc - 1) / nrc;
+    r.nrc = (s.H + r.RC - 1) / r.RC;
+    return r;
+}
+
 int finc_wino4m_launch(const float *in, const void *packed, float *out, const FincShape &s, hipStream_t st)
 {
     const W4mInst *i = find_w4m(s.Cq);
     if (!i) return FINC_ERR_UNSUPPORTED;
-    const int NS = (s.W + 63) / 64;
-    const long long wgs = (long long)s.B * s.G * NS;
-    const long long fill = 256 * (4 / i->nw);                              // workgroups of one wave per SIMD that a chip holds at once (every
-                                                                           // chunk recomputes two rows of operands)
-    int nrc = finc_row_chunks(wgs, fill, s.H, 8, 2);                       // (rounds x rows per chunk: finc_common.h)
-    const int RC = (s.H + nrc - 1) / nrc;
-    nrc = (s.H + RC - 1) / RC;
+    const FincRowPlan r = finc_wino4m_rows(s);
+    const int NS = r.ns, nrc = r.nrc, RC = r.RC;
     if (int e = finc_ensure_dynamic_lds((const void *)i->fn, i->lds)) return e;
     hipLaunchKernelGGL(i->fn, dim3(s.B * s.G * NS, nrc), dim3(64 * i->nw), i->lds, st, in, (const float *)packed, out, s.G, s.Cq, s.H, s.W, NS,
                        RC, s.orient);

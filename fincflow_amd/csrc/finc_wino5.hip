@@ -428,17 +428,30 @@ int finc_wino5_pack(const float *wc, void *packed, int G, int Cq, bool transpose
     return FINC_OK;
 }
 
+// the strips and row chunks of a launch (finc_common.h FincRowPlan): finc_wino5_launch runs them, finc_conv_plan_info reports them
+FincRowPlan finc_wino5_rows(const FincShape &s)
+{
+    FincRowPlan r;
+    const W5Inst *i = find_w5(s.Cq);
+    if (!i) return r;
+    r.strip = 32;
+    r.ns = (s.W + 31) / 32;
+    r.waves = i->nw;
+    // one workgroup per CU at a time (its waves hold 1/NW of the bank each: one wave per SIMD); row chunks when the strips
+    // alone do not fill the chip (every chunk recomputes 4 rows of operands)
+    const long long wgs = (long long)s.B * s.G * r.ns;
+    const int nrc = finc_row_chunks(wgs, 256, s.H, 8, 4);                  // (rounds x rows per chunk: finc_common.h)
+    r.RC = (s.H + nrc - 1) / nrc;
+    r.nrc = (s.H + r.RC - 1) / r.RC;
+    return r;
+}
+
 int finc_wino5_launch(const float *in, const void *packed, float *out, const FincShape &s, hipStream_t st)
 {
     const W5Inst *i = find_w5(s.Cq);
     if (!i) return FINC_ERR_UNSUPPORTED;
-    const int NS = (s.W + 31) / 32;
-    // one workgroup per CU at a time (its waves hold 1/NW of the bank each: one wave per SIMD); row chunks when the strips
-    // alone do not fill the chip (every chunk recomputes 4 rows of operands)
-    const long long wgs = (long long)s.B * s.G * NS;
-    int nrc = finc_row_chunks(wgs, 256, s.H, 8, 4);                        // (rounds x rows per chunk: finc_common.h)
-    const int RC = (s.H + nrc - 1) / nrc;
-    nrc = (s.H + RC - 1) / RC;
+    const FincRowPlan r = finc_wino5_rows(s);
+    const int NS = r.ns, nrc = r.nrc, RC = r.RC;
     if (int e = finc_ensure_dynamic_lds((const void *)i->fn, i->lds)) return e;
     hipLaunchKernelGGL(i->fn, dim3(s.B * s.G * NS, nrc), dim3(64 * i->nw), i->lds, st, in, (const float *)packed, out, s.G, s.Cq, s.H, s.W, NS,
                        RC, s.orient);

@@ -481,6 +481,20 @@ int finc_debug_inverse_remainder_images(int B, int G, int Cq, int H, int W, int 
  * Host-only; 0 for arguments out of range.  (No reference counterpart: the reference's forward is one cuDNN call,
  * layers/conv.py:98-107.) */
 int finc_debug_row_chunks(long long units, long long slots, int H, int min_rows, int extra, int second_tenant);
+/* The grad-weight launch plan of finc_backward_f32 for this shape when grad_z and x are both aligned to `align` bytes (4, 8 or 16):
+ * the plan object the launch itself runs, not a restatement of its rule.  info[10] = {form (finc_debug_backward_variant's
+ * numbering; 0 = direct kernel, everything else 0 too), strip width in columns, strips per row ns, units = B * ns (what the
+ * workgroups of a group walk: `for (u = slot; u < units; u += wpg)`), wpg = workgroups per group, grid.x, block.x, 16-channel tiles
+ * per side of the bank, waves per workgroup of form 4 (frequency split), bytes of partial sums in the workspace}.  units > wpg: some
+ * workgroup takes a second trip through its unit loop.  Host-only.  (No reference counterpart: the reference's weight gradient is
+ * autograd through F.conv2d, layers/conv.py:98-107.) */
+int finc_debug_gradw_plan(int B, int G, int Cq, int H, int W, int KH, int KW, int align, long long *info);
+/* The forward / grad-input launch plan for this shape at that alignment, a form pinned by finc_debug_set_forward_form honoured:
+ * info[6] = {form (finc_debug_backward_variant's info[2]), strip width in columns, strips per row, waves per workgroup, row chunks
+ * nrc (grid.y), rows per chunk RC}: chunk c owns rows [c * RC, min(H, (c + 1) * RC)) and recomputes the operand rows above them.
+ * Forms 3 and 7 have no row chunks and report nrc = 1, RC = H.  Each kernel's chunk arithmetic lives in one host function that its
+ * launch and this query both call.  FINC_ERR_UNSUPPORTED: the direct kernel.  Host-only. */
+int finc_debug_conv_plan(int B, int G, int Cq, int H, int W, int KH, int KW, int align, int *info);
 int finc_debug_inverse_table_row(int row, int *info);
 int finc_debug_attr_table_insert(int device, size_t kernel_token);
 /* SYNCHRONOUS.  The helper-wave form of the inverse (form 3 of finc_inverse_kernel_variant) pairs each compute wave with a

@@ -23,6 +23,7 @@ import torch
 from oracle import oracle
 from helpers import (ORIENT_FASTFLOW, actnorm_ref, broken_guards, coupling_ref, guarded, guards_intact, isolation_check, nan_filled, offset_view, poison,
                      problem_counts_for_row, rel_err, report, same_bits, split_problems)
+from plan_cases import GRADW_WALK_CASES, ROW_CHUNK_CASES
 
 pytestmark = pytest.mark.gpu
 
@@ -463,6 +464,10 @@ CONV_CASES = {
     "stream_odd_width": ((3, 4, 100, 17, 33, 3, 3), 0, "stream", "direct", 4),
     "stream_wino_tiled_gradw": ((3, 4, 104, 8, 32, 3, 3), 0, "stream", "winograd_tiled", 4),
 }
+# the launch regimes of tests/plan_cases.py: a grad-weight workgroup's second trip through its unit loop (all five forms), and the
+# chunk seams of the one-wave-per-SIMD forward kernels (H >= 16); conv_family asserts each case's plan numbers before it runs
+CONV_CASES.update({n: (c["dims"], 0, c["conv_form"], c["plan"]["form"], c["gradx_waves"]) for n, c in GRADW_WALK_CASES.items()})
+CONV_CASES.update({n: (c["dims"], c["pin"], c["conv_form"], c["gradw"], c["gradx_waves"]) for n, c in ROW_CHUNK_CASES.items()})
 AFFINE_FORWARD = ("strip_staged", "f23", "f43_msplit", "stream")      # the affine fold behind the forward, on four kernel families
 
 
@@ -502,6 +507,23 @@ def group_rows(u, g):
     return slice(g * Cq, (g + 1) * Cq)
 
 
+def assert_regime(name, dims, u):
+    """A case of tests/plan_cases.py really is in its regime (the launch's own plan, under the pinned forward form): its plan numbers
+    are the table's; a walk case has more units than workgroups per group, and the batch's last image -- the image of the last
+    problem, one of the slabs the isolation runs poison -- consists of units a workgroup reaches on its second trip or later."""
+    from fincflow_amd import _lib
+    if name in GRADW_WALK_CASES:
+        p, want = _lib.gradw_plan(*dims, align=16), GRADW_WALK_CASES[name]["plan"]
+        assert p == want, (name, p, want)
+        assert p["units"] > p["wpg"], (name, p)
+        last = u.slab(dims[0] * dims[1] - 1)
+        assert last in u.slabs() and last[0] * p["ns"] >= p["wpg"], (name, last, p)     # (unit = image * ns + strip)
+    if name in ROW_CHUNK_CASES:
+        c, want = _lib.conv_plan(*dims, align=16), ROW_CHUNK_CASES[name]["plan"]
+        assert c == want, (name, c, want)
+        assert c["nrc"] >= 2 and dims[3] >= 16 and dims[3] % c["RC"] != 0, (name, c)
+
+
 def conv_family(dev, name, dims, pin, form, gradw, waves, direct=False):
     from fincflow_amd import _lib
     try:
@@ -512,6 +534,7 @@ def conv_family(dev, name, dims, pin, form, gradw, waves, direct=False):
         if direct:
             bv = dict(gradw="direct", gradx="direct", workspace=None)        # NULL workspace selects the direct kernels (include/finc.h)
         u = Unit(dev, dims, seed=sum(dims) + pin)
+        assert_regime(name, dims, u)
         z, gx, gw = conv_reference(u)
         x, gz = t(u.x, dev), t(u.gz, dev)
         slabs = u.slabs()
@@ -551,6 +574,26 @@ def test_forward_and_backward_family(name, dev):
 def test_backward_direct_kernels(name, dev):
     """finc_backward_f32 without a workspace: the direct grad-input and grad-weight kernels (backward_variant's "direct")."""
     conv_family(dev, name + "_direct", *CONV_CASES[name], direct=True)
+
+
+def test_grad_weight_walk_on_float_aligned_activations(dev):
+    """walk_staged's shape with grad_z and x one float into their allocations (4-byte aligned, not 16): the plan for these
+    activations is the dword form, 258 units on 256 workgroups per group, so the second trip of THAT kernel runs -- between guards,
+    on the exact-size NaN workspace, bit-stable, grad_w and grad_x against the float64 reference of the aligned case at TOL."""
+    from fincflow_amd import _lib
+    dims = GRADW_WALK_CASES["walk_staged"]["dims"]
+    p = _lib.gradw_plan(*dims, align=4)
+    assert p["form"] == "dword" and p["units"] > p["wpg"], p
+    u = Unit(dev, dims, seed=sum(dims))
+    _, gx, gw = conv_reference(u)
+    x, gz = t(u.x, dev), t(u.gz, dev)
+    ws = _lib.lib().finc_backward_workspace_bytes(*dims)
+    assert p["bytes"] <= ws
+    call = lambda guard: run(dev, "finc_backward_f32", lambda q, w, n: (q["gz"], q["x"], q["w"], q["gx"], q["gw"], *dims, u.orient, w, n, None),
+                             dict(gz=gz, x=x, w=u.wc), dict(gx=(u.shape, F32), gw=(tuple(u.wc.shape), F32)), ws, guard, lead=("gz", "x"))
+    check_bounds("walk_staged_float_aligned", call, dict(gradw=p["form"], units=p["units"], wpg=p["wpg"]),
+                 judge_outputs(dict(gx=gx, gw=gw)), entry="backward", dims=list(dims))
+    assert not _lib.fault_pending()
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -359,6 +359,12 @@ def test_ksplit_forward_and_grad_input(shape, dev):
     assert abs(lhs - rhs) <= 1e-5 * scale, (lhs, rhs, scale)
 
 
+# more (image, strip) units than workgroups per group: a workgroup walks several units in a row (asserted through the launch's own
+# plan, _lib.gradw_plan) -- the pair kernel on strips of 32 columns, the staged form, the tile-pair form (57 units on 56 workgroups),
+# the tiled kernel (the same)
+GRADW_WALK_SHAPES = [(130, 96, 2, 32, 3), (140, 48, 3, 24, 3), (57, 192, 3, 32, 3), (57, 192, 3, 16, 3)]
+
+
 @pytest.mark.parametrize("shape", [(3, 96, 20, 40, 3), (2, 64, 9, 17, 5), (2, 16, 12, 12, 2), (64, 96, 64, 64, 3),
                                    # W % 16 == 0: the staged form (16-byte pieces through LDS; 4-row blocks behind the last full 16)
                                    (3, 96, 10, 16, 3), (2, 48, 9, 32, 3), (2, 64, 7, 48, 3), (2, 80, 6, 32, 3), (2, 16, 9, 16, 3),
@@ -366,9 +372,7 @@ def test_ksplit_forward_and_grad_input(shape, dev):
                                    (5, 96, 1, 16, 3), (1, 96, 2, 64, 3),
                                    # banks whose accumulator tiles do not fit one wave: one (o, i) tile pair per workgroup
                                    (2, 192, 6, 32, 3), (1, 192, 5, 16, 5), (2, 128, 6, 32, 5), (2, 160, 5, 32, 3), (1, 256, 4, 16, 3),
-                                   (3, 188, 4, 48, 3),
-                                   # more (image, strip) units than waves per group: a wave walks several units in a row
-                                   (130, 96, 2, 32, 3), (30, 192, 3, 32, 3), (140, 48, 3, 24, 3)])
+                                   (3, 188, 4, 48, 3), (30, 192, 3, 32, 3)] + GRADW_WALK_SHAPES)
 def test_grad_weight_mfma(shape, dev):
     """grad_w on the MFMA strip kernel (pixels on K) + reduce + corner-tap mask.  Pinned by linearity in the weights:
     <grad_w, dW> == <gz, forward(x; dW)> for any bank dW whose masked entries are zero, and against the direct
@@ -378,6 +382,9 @@ def test_grad_weight_mfma(shape, dev):
     L = _lib.lib()
     Cq = C // 4
     assert _lib.backward_variant(B, 4, Cq, H, W, K, K)["gradw"] != "direct"      # an MFMA grad_w kernel exists for this shape
+    plan = _lib.gradw_plan(B, 4, Cq, H, W, K, K)
+    if shape in GRADW_WALK_SHAPES:
+        assert plan["units"] > plan["wpg"], (shape, plan)
     torch.manual_seed(sum(shape))
     wc = canon(oracle.make_stored_weights(4, Cq, K, K), 4, ORIENT_FASTFLOW, dev)
     x = torch.randn(B, C, H, W, device=dev)
@@ -393,13 +400,19 @@ def test_grad_weight_mfma(shape, dev):
     # both sides are sums of many terms of either sign: the yardstick is the sum of their magnitudes, not the (cancelled)
     # total -- 2e-7 of it is fp32 rounding of a few hundred accumulations per entry, whatever order they ran in
     scale = float((gw.double() * dW.double()).abs().sum())
-    assert abs(lhs - rhs) <= 2e-7 * scale + 1e-6, (lhs, rhs, scale)
-    if B * C * H * W <= 1 << 20:
-        gw_direct = torch.empty_like(wc)
-        st = L.finc_backward_f32(gz.data_ptr(), x.data_ptr(), wc.data_ptr(), None, gw_direct.data_ptr(), B, 4, Cq, H, W, K, K,
-                                 ORIENT_FASTFLOW, None, 0, torch.cuda.current_stream().cuda_stream)
-        assert st == 0
-        assert rel_err(gw.cpu().numpy(), gw_direct.cpu().numpy()) <= 1e-4
+    e_direct = None
+    try:
+        assert abs(lhs - rhs) <= 2e-7 * scale + 1e-6, (lhs, rhs, scale)
+        if B * C * H * W <= 1 << 20:
+            gw_direct = torch.empty_like(wc)
+            st = L.finc_backward_f32(gz.data_ptr(), x.data_ptr(), wc.data_ptr(), None, gw_direct.data_ptr(), B, 4, Cq, H, W, K, K,
+                                     ORIENT_FASTFLOW, None, 0, torch.cuda.current_stream().cuda_stream)
+            assert st == 0
+            e_direct = rel_err(gw.cpu().numpy(), gw_direct.cpu().numpy())
+            assert e_direct <= 1e-4
+    finally:
+        report("grad_weight_mfma", shape=list(shape), gradw=plan["form"], units=plan["units"], wpg=plan["wpg"],
+               inner_product_gap=abs(lhs - rhs) / max(scale, 1e-30), vs_direct=e_direct)
 
 
 def test_empty_batch(dev):
