@@ -614,38 +614,40 @@ int finc_coupling_f32(const float *x, const float *raw, const float *a, const fl
     return finc_coupling_launch(x, raw, a, b, y, sums ? logdet : nullptr, B, C, HW, direction, (float *)workspace, (hipStream_t)stream);
 }
 
-int finc_coupling_backward_f32(const float *grad_y, const float *grad_logdet, const float *x, const float *raw, const float *a,
-                               const float *b, float *grad_x, float *grad_raw, float *grad_a, float *grad_b, int B, int C, int HW,
-                               void *workspace, size_t workspace_bytes, finc_stream_t stream)
+// Every backward of the coupling: `v` is the activation the mode reads (FincGradMode), x_out the rebuilt input of FINC_GRAD_REBUILD
+// alone, which also allows grad_x == grad_y (and x_out == v); no other output may be an input or another output.
+static int coupling_grad(FincGradMode mode, const float *grad_y, const float *grad_logdet, const float *v, const float *raw, const float *a,
+                         const float *b, float *x_out, float *grad_x, float *grad_raw, float *grad_a, float *grad_b, int B, int C, int HW,
+                         void *workspace, size_t workspace_bytes, finc_stream_t stream)
 {
-    if (!grad_y || !x || !raw || !a || !b || (!grad_x && !grad_raw && !grad_a && !grad_b)) return FINC_ERR_NULL_POINTER;
+    if (!grad_y || !v || !raw || !a || !b || (!x_out && !grad_x && !grad_raw && !grad_a && !grad_b)) return FINC_ERR_NULL_POINTER;
     if (int e = pixel_dims(B, C, HW, true)) return e;
-    if (grad_x && (grad_x == grad_y || grad_x == x || grad_x == raw)) return FINC_ERR_BAD_DIMS;
-    if (grad_raw && (grad_raw == grad_y || grad_raw == x || grad_raw == raw || grad_raw == grad_x)) return FINC_ERR_BAD_DIMS;
-    if (misaligned(grad_y, grad_logdet, x, raw, a, b, grad_x, grad_raw, grad_a, grad_b)) return FINC_ERR_ALIGNMENT;
+    if (x_out && (x_out == grad_y || x_out == raw || x_out == grad_x || x_out == grad_raw)) return FINC_ERR_BAD_DIMS;
+    if (grad_x && ((grad_x == grad_y && mode != FINC_GRAD_REBUILD) || grad_x == v || grad_x == raw)) return FINC_ERR_BAD_DIMS;
+    if (grad_raw && (grad_raw == grad_y || grad_raw == v || grad_raw == raw || grad_raw == grad_x)) return FINC_ERR_BAD_DIMS;
+    if (misaligned(grad_y, grad_logdet, v, raw, a, b, x_out, grad_x, grad_raw, grad_a, grad_b)) return FINC_ERR_ALIGNMENT;
     if (!finc_coupling_supported_f32(C)) return FINC_ERR_UNSUPPORTED;
     if ((grad_a || grad_b) && workspace_short(workspace, workspace_bytes, finc_coupling_workspace_bytes(B, C, HW)))
         return FINC_ERR_WORKSPACE;
     if (int e = finc_fault_gate(false)) return e;
-    return finc_coupling_backward_launch(grad_y, grad_logdet, x, raw, a, b, grad_x, grad_raw, grad_a, grad_b, B, C, HW, (float *)workspace,
-                                         (hipStream_t)stream);
+    return finc_coupling_grad_launch(mode, grad_y, grad_logdet, v, raw, a, b, x_out, grad_x, grad_raw, grad_a, grad_b, B, C, HW,
+                                     (float *)workspace, (hipStream_t)stream);
+}
+
+int finc_coupling_backward_f32(const float *grad_y, const float *grad_logdet, const float *x, const float *raw, const float *a,
+                               const float *b, float *grad_x, float *grad_raw, float *grad_a, float *grad_b, int B, int C, int HW,
+                               void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    return coupling_grad(FINC_GRAD_FWD, grad_y, grad_logdet, x, raw, a, b, nullptr, grad_x, grad_raw, grad_a, grad_b, B, C, HW, workspace,
+                         workspace_bytes, stream);
 }
 
 int finc_coupling_reverse_backward_f32(const float *grad_y, const float *y, const float *raw, const float *a, const float *b,
                                        float *grad_x, float *grad_raw, float *grad_a, float *grad_b, int B, int C, int HW,
                                        void *workspace, size_t workspace_bytes, finc_stream_t stream)
 {
-    if (!grad_y || !y || !raw || !a || !b || (!grad_x && !grad_raw && !grad_a && !grad_b)) return FINC_ERR_NULL_POINTER;
-    if (int e = pixel_dims(B, C, HW, true)) return e;
-    if (grad_x && (grad_x == grad_y || grad_x == y || grad_x == raw)) return FINC_ERR_BAD_DIMS;
-    if (grad_raw && (grad_raw == grad_y || grad_raw == y || grad_raw == raw || grad_raw == grad_x)) return FINC_ERR_BAD_DIMS;
-    if (misaligned(grad_y, y, raw, a, b, grad_x, grad_raw, grad_a, grad_b)) return FINC_ERR_ALIGNMENT;
-    if (!finc_coupling_supported_f32(C)) return FINC_ERR_UNSUPPORTED;
-    if ((grad_a || grad_b) && workspace_short(workspace, workspace_bytes, finc_coupling_workspace_bytes(B, C, HW)))
-        return FINC_ERR_WORKSPACE;
-    if (int e = finc_fault_gate(false)) return e;
-    return finc_coupling_reverse_backward_launch(grad_y, nullptr, y, raw, a, b, grad_x, grad_raw, grad_a, grad_b, B, C, HW,
-                                                 (float *)workspace, (hipStream_t)stream);
+    return finc_coupling_reverse_logdet_backward_f32(grad_y, nullptr, y, raw, a, b, grad_x, grad_raw, grad_a, grad_b, B, C, HW, workspace,
+                                                     workspace_bytes, stream);
 }
 
 int finc_coupling_reverse_logdet_f32(const float *x, const float *raw, const float *a, const float *b, float *y, float *logdet, int B,
@@ -658,7 +660,7 @@ int finc_coupling_reverse_logdet_f32(const float *x, const float *raw, const flo
     if (!finc_coupling_supported_f32(C)) return FINC_ERR_UNSUPPORTED;
     if (workspace_short(workspace, workspace_bytes, finc_coupling_workspace_bytes(B, C, HW))) return FINC_ERR_WORKSPACE;
     if (int e = finc_fault_gate(false)) return e;
-    return finc_coupling_reverse_logdet_launch(x, raw, a, b, y, logdet, B, C, HW, (float *)workspace, (hipStream_t)stream);
+    return finc_coupling_launch(x, raw, a, b, y, logdet, B, C, HW, -1, (float *)workspace, (hipStream_t)stream);
 }
 
 int finc_coupling_reverse_logdet_backward_f32(const float *grad_y, const float *grad_logdet, const float *y, const float *raw,
@@ -666,36 +668,16 @@ int finc_coupling_reverse_logdet_backward_f32(const float *grad_y, const float *
                                               float *grad_b, int B, int C, int HW, void *workspace, size_t workspace_bytes,
                                               finc_stream_t stream)
 {
-    if (!grad_y || !y || !raw || !a || !b || (!grad_x && !grad_raw && !grad_a && !grad_b)) return FINC_ERR_NULL_POINTER;
-    if (int e = pixel_dims(B, C, HW, true)) return e;
-    if (grad_x && (grad_x == grad_y || grad_x == y || grad_x == raw)) return FINC_ERR_BAD_DIMS;
-    if (grad_raw && (grad_raw == grad_y || grad_raw == y || grad_raw == raw || grad_raw == grad_x)) return FINC_ERR_BAD_DIMS;
-    if (misaligned(grad_y, grad_logdet, y, raw, a, b, grad_x, grad_raw, grad_a, grad_b)) return FINC_ERR_ALIGNMENT;
-    if (!finc_coupling_supported_f32(C)) return FINC_ERR_UNSUPPORTED;
-    if ((grad_a || grad_b) && workspace_short(workspace, workspace_bytes, finc_coupling_workspace_bytes(B, C, HW)))
-        return FINC_ERR_WORKSPACE;
-    if (int e = finc_fault_gate(false)) return e;
-    return finc_coupling_reverse_backward_launch(grad_y, grad_logdet, y, raw, a, b, grad_x, grad_raw, grad_a, grad_b, B, C, HW,
-                                                 (float *)workspace, (hipStream_t)stream);
+    return coupling_grad(FINC_GRAD_REV, grad_y, grad_logdet, y, raw, a, b, nullptr, grad_x, grad_raw, grad_a, grad_b, B, C, HW, workspace,
+                         workspace_bytes, stream);
 }
 
 int finc_coupling_backward_reconstruct_f32(const float *grad_y, const float *grad_logdet, const float *y, const float *raw, const float *a,
                                            const float *b, float *x_out, float *grad_x, float *grad_raw, float *grad_a, float *grad_b,
                                            int B, int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream)
 {
-    if (!grad_y || !y || !raw || !a || !b || (!x_out && !grad_x && !grad_raw && !grad_a && !grad_b)) return FINC_ERR_NULL_POINTER;
-    if (int e = pixel_dims(B, C, HW, true)) return e;
-    // x_out == y and grad_x == grad_y are the two allowed overlaps
-    if (x_out && (x_out == grad_y || x_out == raw || x_out == grad_x || x_out == grad_raw)) return FINC_ERR_BAD_DIMS;
-    if (grad_x && (grad_x == y || grad_x == raw || grad_x == grad_raw)) return FINC_ERR_BAD_DIMS;
-    if (grad_raw && (grad_raw == grad_y || grad_raw == y || grad_raw == raw)) return FINC_ERR_BAD_DIMS;
-    if (misaligned(grad_y, grad_logdet, y, raw, a, b, x_out, grad_x, grad_raw, grad_a, grad_b)) return FINC_ERR_ALIGNMENT;
-    if (!finc_coupling_supported_f32(C)) return FINC_ERR_UNSUPPORTED;
-    if ((grad_a || grad_b) && workspace_short(workspace, workspace_bytes, finc_coupling_workspace_bytes(B, C, HW)))
-        return FINC_ERR_WORKSPACE;
-    if (int e = finc_fault_gate(false)) return e;
-    return finc_coupling_backward_reconstruct_launch(grad_y, grad_logdet, y, raw, a, b, x_out, grad_x, grad_raw, grad_a, grad_b, B, C, HW,
-                                                     (float *)workspace, (hipStream_t)stream);
+    return coupling_grad(FINC_GRAD_REBUILD, grad_y, grad_logdet, y, raw, a, b, x_out, grad_x, grad_raw, grad_a, grad_b, B, C, HW, workspace,
+                         workspace_bytes, stream);
 }
 
 int finc_bias_relu_f32(const float *in, const float *bias, float *out, int B, int C, int HW, finc_stream_t stream)
@@ -723,19 +705,31 @@ int finc_actnorm_f32(const float *x, const float *log_scale, const float *transl
     return finc_actnorm_launch(x, log_scale, translation, y, direction > 0 ? logdet : nullptr, B, C, HW, direction, (hipStream_t)stream);
 }
 
+// Every backward of ActNorm: `v` is the activation the mode reads (FincGradMode), translation and x_out belong to FINC_GRAD_REBUILD
+// alone.  grad_x == grad_y and x_out == v are the two allowed overlaps.
+static int actnorm_grad(FincGradMode mode, const float *grad_y, const float *grad_logdet, const float *v, const float *log_scale,
+                        const float *translation, float *x_out, float *grad_x, float *grad_log_scale, float *grad_translation, int B, int C,
+                        int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    if (!grad_y || !v || !log_scale || (x_out && !translation) || (!x_out && !grad_x && !grad_log_scale && !grad_translation))
+        return FINC_ERR_NULL_POINTER;
+    if (int e = pixel_dims(B, C, HW, true)) return e;
+    if (x_out && (x_out == grad_y || x_out == grad_x)) return FINC_ERR_BAD_DIMS;
+    if (grad_x && grad_x == v) return FINC_ERR_BAD_DIMS;
+    if (misaligned(grad_y, grad_logdet, v, log_scale, translation, x_out, grad_x, grad_log_scale, grad_translation)) return FINC_ERR_ALIGNMENT;
+    if ((grad_log_scale || grad_translation) && workspace_short(workspace, workspace_bytes, finc_actnorm_workspace_bytes(B, C, HW)))
+        return FINC_ERR_WORKSPACE;
+    if (int e = finc_fault_gate(false)) return e;
+    return finc_actnorm_grad_launch(mode, grad_y, grad_logdet, v, log_scale, translation, x_out, grad_x, grad_log_scale, grad_translation, B,
+                                    C, HW, (float *)workspace, (hipStream_t)stream);
+}
+
 int finc_actnorm_backward_f32(const float *grad_y, const float *grad_logdet, const float *y, const float *log_scale, float *grad_x,
                               float *grad_log_scale, float *grad_translation, int B, int C, int HW, void *workspace,
                               size_t workspace_bytes, finc_stream_t stream)
 {
-    if (!grad_y || !y || !log_scale || (!grad_x && !grad_log_scale && !grad_translation)) return FINC_ERR_NULL_POINTER;
-    if (int e = pixel_dims(B, C, HW, true)) return e;
-    if (grad_x && grad_x == y) return FINC_ERR_BAD_DIMS;
-    if (misaligned(grad_y, grad_logdet, y, log_scale, grad_x, grad_log_scale, grad_translation)) return FINC_ERR_ALIGNMENT;
-    if ((grad_log_scale || grad_translation) && workspace_short(workspace, workspace_bytes, finc_actnorm_workspace_bytes(B, C, HW)))
-        return FINC_ERR_WORKSPACE;
-    if (int e = finc_fault_gate(false)) return e;
-    return finc_actnorm_backward_launch(grad_y, grad_logdet, y, log_scale, grad_x, grad_log_scale, grad_translation, B, C, HW,
-                                        (float *)workspace, (hipStream_t)stream);
+    return actnorm_grad(FINC_GRAD_FWD, grad_y, grad_logdet, y, log_scale, nullptr, nullptr, grad_x, grad_log_scale, grad_translation, B, C, HW,
+                        workspace, workspace_bytes, stream);
 }
 
 int finc_actnorm_backward_reconstruct_f32(const float *grad_y, const float *grad_logdet, const float *y, const float *log_scale,
@@ -743,33 +737,16 @@ int finc_actnorm_backward_reconstruct_f32(const float *grad_y, const float *grad
                                           float *grad_translation, int B, int C, int HW, void *workspace, size_t workspace_bytes,
                                           finc_stream_t stream)
 {
-    if (!grad_y || !y || !log_scale || (x_out && !translation) || (!x_out && !grad_x && !grad_log_scale && !grad_translation))
-        return FINC_ERR_NULL_POINTER;
-    if (int e = pixel_dims(B, C, HW, true)) return e;
-    // x_out == y and grad_x == grad_y are the two allowed overlaps
-    if (x_out && (x_out == grad_y || x_out == grad_x)) return FINC_ERR_BAD_DIMS;
-    if (grad_x && grad_x == y) return FINC_ERR_BAD_DIMS;
-    if (misaligned(grad_y, grad_logdet, y, log_scale, translation, x_out, grad_x, grad_log_scale, grad_translation)) return FINC_ERR_ALIGNMENT;
-    if ((grad_log_scale || grad_translation) && workspace_short(workspace, workspace_bytes, finc_actnorm_workspace_bytes(B, C, HW)))
-        return FINC_ERR_WORKSPACE;
-    if (int e = finc_fault_gate(false)) return e;
-    return finc_actnorm_backward_reconstruct_launch(grad_y, grad_logdet, y, log_scale, translation, x_out, grad_x, grad_log_scale,
-                                                    grad_translation, B, C, HW, (float *)workspace, (hipStream_t)stream);
+    return actnorm_grad(FINC_GRAD_REBUILD, grad_y, grad_logdet, y, log_scale, translation, x_out, grad_x, grad_log_scale, grad_translation, B,
+                        C, HW, workspace, workspace_bytes, stream);
 }
 
 int finc_actnorm_reverse_backward_f32(const float *grad_y, const float *x, const float *log_scale, float *grad_x, float *grad_log_scale,
                                       float *grad_translation, int B, int C, int HW, void *workspace, size_t workspace_bytes,
                                       finc_stream_t stream)
 {
-    if (!grad_y || !x || !log_scale || (!grad_x && !grad_log_scale && !grad_translation)) return FINC_ERR_NULL_POINTER;
-    if (int e = pixel_dims(B, C, HW, true)) return e;
-    if (grad_x && grad_x == x) return FINC_ERR_BAD_DIMS;
-    if (misaligned(grad_y, x, log_scale, grad_x, grad_log_scale, grad_translation)) return FINC_ERR_ALIGNMENT;
-    if ((grad_log_scale || grad_translation) && workspace_short(workspace, workspace_bytes, finc_actnorm_workspace_bytes(B, C, HW)))
-        return FINC_ERR_WORKSPACE;
-    if (int e = finc_fault_gate(false)) return e;
-    return finc_actnorm_reverse_backward_launch(grad_y, x, log_scale, grad_x, grad_log_scale, grad_translation, B, C, HW,
-                                                (float *)workspace, (hipStream_t)stream);
+    return actnorm_grad(FINC_GRAD_REV, grad_y, nullptr, x, log_scale, nullptr, nullptr, grad_x, grad_log_scale, grad_translation, B, C, HW,
+                        workspace, workspace_bytes, stream);
 }
 
 int finc_actnorm_init_f32(const float *x, float *log_scale, float *translation, int B, int C, int HW, void *workspace,

@@ -5,13 +5,14 @@
 //   * finc_actnorm_kernel        one pass: y = (x - t[c]) * exp(-ls[c]) (forward, layers/actnorm.py:34) or y = x * exp(ls[c]) + t[c]
 //                                (reverse, :51); with a log-det pointer the first wave of the launch also writes
 //                                logdet[b] = -(sum_c ls[c]) * HW for every image (:57-65): a training forward is ONE launch.
-//   * finc_actnorm_bwd_kernel    one pass over grad_y and y (the forward's OUTPUT: x - t = y * exp(ls), so
+//   * an_grad<V, MODE>           one pass over grad_y and y (the forward's OUTPUT: x - t = y * exp(ls), so
 //                                d loss / d ls[c] = -sum grad_y * y needs nothing the forward's caller does not keep anyway):
-//                                grad_x = grad_y * exp(-ls[c]) and the two per-channel sums, then finc_coupling_reduce_kernel.
-//   * finc_actnorm_recon_kernel  that backward, and from the same read of y the forward's INPUT x = y * exp(ls[c]) + t[c]: the step of a
-//                                training backward that stores no activations (FlowSequential.invertible_backward).
-//   * finc_actnorm_rev_bwd_kernel  the same for the reverse direction, from the reverse's INPUT (what `reverse` under autograd
-//                                records inside ops.reverse_grad()).
+//                                grad_x = grad_y * exp(-ls[c]) and the two per-channel sums, then finc_coupling_reduce_kernel.  Its
+//                                modes are the kernels finc_actnorm_bwd_kernel (that), finc_actnorm_recon_kernel (that, and the
+//                                forward's INPUT rebuilt from the same read of y: the step of a training backward that stores no
+//                                activations, FlowSequential.invertible_backward) and finc_actnorm_rev_bwd_kernel (the reverse
+//                                direction, from the reverse's INPUT: what `reverse` under autograd records inside
+//                                ops.reverse_grad()).
 //   * finc_actnorm_stats_kernel  the data-dependent initialisation (:17-23): per-channel mean and unbiased standard deviation in ONE
 //                                pass over x.  Every thread folds its pieces into a running (n, mean, M2) triple (Chan et al.'s pairwise
 //                                update: the squares are taken of differences from a running mean, never of x itself -- the
@@ -55,146 +56,101 @@ __global__ __launch_bounds__(CPL_THREADS) void finc_actnorm_kernel(const float *
     }
 }
 
+// Every backward of ActNorm is ONE body, an_grad<V, MODE>; a mode (FincGradMode) is what it reads, its scale and its partials:
+//   FINC_GRAD_FWD      of y = (x - t[c]) * exp(-ls[c]), from `v` = the forward's OUTPUT y: grad_x = grad_y * exp(-ls[c]).
+//   FINC_GRAD_REBUILD  that backward, and from the same read of y the forward's input: xo = y * exp(ls[c]) + t[c] (the arithmetic of
+//                      finc_actnorm_kernel's reverse direction, so the same bits).  What a training step without stored activations
+//                      runs per ActNorm: one launch instead of a reverse launch plus a backward launch, y read once.  xo (then tr is
+//                      not read) may be nullptr; xo == v is allowed.
+//   FINC_GRAD_REV      of y = x * exp(ls[c]) + t[c] (layers/actnorm.py:47-52), from `v` = the reverse's INPUT x: grad_x = grad_y *
+//                      exp(ls[c]), grad_ls[c] = exp(ls[c]) * sum grad_y * x, grad_t[c] = sum grad_y.  (The output would do in real
+//                      arithmetic -- x * exp(ls) = y - t -- but on a channel with |t| >> |y - t| that difference has lost its digits.)
 // Workgroup = (channel c, part q): Q parts share the channel's B * HW / V items, so a workgroup's sums belong to ONE channel.
-// Partials, Q + 1 per output, output 2c = grad_t[c], 2c + 1 = grad_ls[c] (the layout finc_coupling_reduce_kernel's pair mode sends to
-// out_a[c] / out_b[c]):  part[(2c) * (Q+1) + q] = -exp(-ls[c]) * sum gy,  part[(2c+1) * (Q+1) + q] = -sum gy * y;  slot Q of grad_ls
-// is -HW * sum_b gld[b] (added by the channel's part 0, one wave in a fixed order), slot Q of grad_t is zero.
-// gld, y (without grad_ls), gx may be nullptr; `sums` = 0 skips the partials.  gx == gy is allowed.
+// Partials, n per output, output 2c = grad_t[c], 2c + 1 = grad_ls[c] (the layout finc_coupling_reduce_kernel's pair mode sends to
+// out_a[c] / out_b[c]).  The two forward modes, n = Q + 1:  part[(2c) * n + q] = -exp(-ls[c]) * sum gy,  part[(2c+1) * n + q] =
+// -sum gy * y;  slot Q of grad_ls is -HW * sum_b gld[b] (added by the channel's part 0, one wave in a fixed order), slot Q of grad_t is
+// zero.  The reverse mode, n = Q:  part[(2c) * Q + q] = sum gy,  part[(2c+1) * Q + q] = exp(ls[c]) * sum gy * x.
+// gld, gx may be nullptr; `sums` = 0 skips the partials; `need_v` = 0 (neither xo nor grad_ls) skips the read of v.  gx == gy is allowed
+// (an item is read before it is written, by the same thread).
+template <int V, int MODE>
+__device__ __forceinline__ void an_grad(const float *gy, const float *__restrict__ gld, const float *v, const float *__restrict__ ls,
+                                        const float *__restrict__ tr, float *xo, float *gx, float *__restrict__ part, int B, int C, int HW,
+                                        int nv, int items, int Q, int sums, int need_v)
+{
+    constexpr bool REBUILD = MODE == FINC_GRAD_REBUILD, REV = MODE == FINC_GRAD_REV;
+    const int c = (int)blockIdx.x / Q, qi = (int)blockIdx.x - c * Q;
+    const float l = ls[c], s = expf(REV ? l : -l), si = REBUILD ? expf(l) : 0.f, t = REBUILD && xo ? tr[c] : 0.f;
+    float acc[2] = {0.f, 0.f};
+    for (int idx = qi * CPL_THREADS + (int)threadIdx.x; idx < items; idx += Q * CPL_THREADS) {
+        const int img = idx / nv, p = (idx - img * nv) * V;
+        const size_t o = ((size_t)img * C + c) * (size_t)HW + p;
+        float g[V], vv[V], d[V], xv[V];
+        cpl_load<V>(g, gy + o);
+        if (need_v) cpl_load<V>(vv, v + o);
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            d[e] = g[e] * s;
+            acc[0] += g[e];
+            if (need_v) {
+                acc[1] = fmaf(g[e], vv[e], acc[1]);
+                if constexpr (REBUILD) xv[e] = fmaf(vv[e], si, t);
+            }
+        }
+        if constexpr (REBUILD)
+            if (xo) cpl_store<V>(xo + o, xv);
+        if (gx) cpl_store<V>(gx + o, d);
+    }
+    if (sums) {
+        __shared__ float sm[2][4];
+        cpl_block_sum<2>(acc, sm);
+        const int n = REV ? Q : Q + 1;
+        float *p0 = part + (size_t)(2 * c) * n, *p1 = p0 + n;
+        if (threadIdx.x == 0) {
+            p0[qi] = REV ? acc[0] : -s * acc[0];
+            p1[qi] = REV ? s * acc[1] : -acc[1];
+        }
+        if constexpr (!REV) {
+            if (qi == 0 && threadIdx.x < 64) {
+                float gl = 0.f;
+                if (gld)
+                    for (int b = (int)threadIdx.x; b < B; b += 64) gl += gld[b];
+#pragma unroll
+                for (int k = 32; k > 0; k >>= 1) gl += __shfl_xor(gl, k, 64);
+                if (threadIdx.x == 0) {
+                    p0[Q] = 0.f;
+                    p1[Q] = -(float)HW * gl;
+                }
+            }
+        }
+    }
+}
+
+// The three modes under the names and parameter lists they have always had.  y / x nullptr (the launcher's, without grad_ls): not read.
 template <int V>
 __global__ __launch_bounds__(CPL_THREADS) void finc_actnorm_bwd_kernel(const float *gy, const float *__restrict__ gld,
                                                                        const float *__restrict__ y, const float *__restrict__ ls, float *gx,
                                                                        float *__restrict__ part, int B, int C, int HW, int nv, int items, int Q,
                                                                        int sums)
 {
-    const int c = (int)blockIdx.x / Q, qi = (int)blockIdx.x - c * Q;
-    const float s = expf(-ls[c]);
-    float acc[2] = {0.f, 0.f};
-    for (int idx = qi * CPL_THREADS + (int)threadIdx.x; idx < items; idx += Q * CPL_THREADS) {
-        const int img = idx / nv, p = (idx - img * nv) * V;
-        const size_t o = ((size_t)img * C + c) * (size_t)HW + p;
-        float g[V], yv[V], d[V];
-        cpl_load<V>(g, gy + o);
-        if (y) cpl_load<V>(yv, y + o);
-#pragma unroll
-        for (int e = 0; e < V; ++e) {
-            d[e] = g[e] * s;
-            acc[0] += g[e];
-            if (y) acc[1] = fmaf(g[e], yv[e], acc[1]);
-        }
-        if (gx) cpl_store<V>(gx + o, d);
-    }
-    if (sums) {
-        __shared__ float sm[2][4];
-        cpl_block_sum<2>(acc, sm);
-        float *p0 = part + (size_t)(2 * c) * (Q + 1), *p1 = p0 + (Q + 1);
-        if (threadIdx.x == 0) {
-            p0[qi] = -s * acc[0];
-            p1[qi] = -acc[1];
-        }
-        if (qi == 0 && threadIdx.x < 64) {
-            float l = 0.f;
-            if (gld)
-                for (int b = (int)threadIdx.x; b < B; b += 64) l += gld[b];
-#pragma unroll
-            for (int k = 32; k > 0; k >>= 1) l += __shfl_xor(l, k, 64);
-            if (threadIdx.x == 0) {
-                p0[Q] = 0.f;
-                p1[Q] = -(float)HW * l;
-            }
-        }
-    }
+    an_grad<V, FINC_GRAD_FWD>(gy, gld, y, ls, nullptr, nullptr, gx, part, B, C, HW, nv, items, Q, sums, y != nullptr);
 }
 
-// finc_actnorm_bwd_kernel that also REBUILDS the forward's input from the same read of y: xo = y * exp(ls[c]) + t[c] (the arithmetic of
-// finc_actnorm_kernel's reverse direction, so the same bits).  What a training step without stored activations runs per ActNorm: one
-// launch instead of a reverse launch plus a backward launch, y read once.  Workgroups, partials and slot Q as in
-// finc_actnorm_bwd_kernel.  gld, xo (then tr is not read), gx may be nullptr; `sums` = 0 skips the partials; `need_y` = 0 (neither xo
-// nor grad_ls) skips the read of y.  xo == y and gx == gy are allowed (an item is read before it is written, by the same thread).
 template <int V>
 __global__ __launch_bounds__(CPL_THREADS) void finc_actnorm_recon_kernel(const float *gy, const float *__restrict__ gld, const float *y,
                                                                          const float *__restrict__ ls, const float *__restrict__ tr,
                                                                          float *xo, float *gx, float *__restrict__ part, int B, int C, int HW,
                                                                          int nv, int items, int Q, int sums, int need_y)
 {
-    const int c = (int)blockIdx.x / Q, qi = (int)blockIdx.x - c * Q;
-    const float l = ls[c], s = expf(-l), si = expf(l), t = xo ? tr[c] : 0.f;
-    float acc[2] = {0.f, 0.f};
-    for (int idx = qi * CPL_THREADS + (int)threadIdx.x; idx < items; idx += Q * CPL_THREADS) {
-        const int img = idx / nv, p = (idx - img * nv) * V;
-        const size_t o = ((size_t)img * C + c) * (size_t)HW + p;
-        float g[V], yv[V], d[V], xv[V];
-        cpl_load<V>(g, gy + o);
-        if (need_y) cpl_load<V>(yv, y + o);
-#pragma unroll
-        for (int e = 0; e < V; ++e) {
-            d[e] = g[e] * s;
-            acc[0] += g[e];
-            if (need_y) {
-                acc[1] = fmaf(g[e], yv[e], acc[1]);
-                xv[e] = fmaf(yv[e], si, t);
-            }
-        }
-        if (xo) cpl_store<V>(xo + o, xv);
-        if (gx) cpl_store<V>(gx + o, d);
-    }
-    if (sums) {
-        __shared__ float sm[2][4];
-        cpl_block_sum<2>(acc, sm);
-        float *p0 = part + (size_t)(2 * c) * (Q + 1), *p1 = p0 + (Q + 1);
-        if (threadIdx.x == 0) {
-            p0[qi] = -s * acc[0];
-            p1[qi] = -acc[1];
-        }
-        if (qi == 0 && threadIdx.x < 64) {
-            float gl = 0.f;
-            if (gld)
-                for (int b = (int)threadIdx.x; b < B; b += 64) gl += gld[b];
-#pragma unroll
-            for (int k = 32; k > 0; k >>= 1) gl += __shfl_xor(gl, k, 64);
-            if (threadIdx.x == 0) {
-                p0[Q] = 0.f;
-                p1[Q] = -(float)HW * gl;
-            }
-        }
-    }
+    an_grad<V, FINC_GRAD_REBUILD>(gy, gld, y, ls, tr, xo, gx, part, B, C, HW, nv, items, Q, sums, need_y);
 }
 
-// The backward of the REVERSE direction, y = x * exp(ls[c]) + t[c] (layers/actnorm.py:47-52), from grad_y and the reverse's INPUT x:
-// grad_x = grad_y * exp(ls[c]), grad_ls[c] = exp(ls[c]) * sum grad_y * x, grad_t[c] = sum grad_y.  (The output would do in real
-// arithmetic -- x * exp(ls) = y - t -- but on a channel with |t| >> |y - t| that difference has lost its digits.)
-// Workgroups and partials as in finc_actnorm_bwd_kernel, Q per output: part[(2c) * Q + q] = sum gy, part[(2c+1) * Q + q] =
-// exp(ls[c]) * sum gy * x.  x (without grad_ls), gx may be nullptr; `sums` = 0 skips the partials.  gx == gy is allowed.
 template <int V>
 __global__ __launch_bounds__(CPL_THREADS) void finc_actnorm_rev_bwd_kernel(const float *gy, const float *__restrict__ x,
                                                                            const float *__restrict__ ls, float *gx,
                                                                            float *__restrict__ part, int C, int HW, int nv, int items, int Q,
                                                                            int sums)
 {
-    const int c = (int)blockIdx.x / Q, qi = (int)blockIdx.x - c * Q;
-    const float s = expf(ls[c]);
-    float acc[2] = {0.f, 0.f};
-    for (int idx = qi * CPL_THREADS + (int)threadIdx.x; idx < items; idx += Q * CPL_THREADS) {
-        const int img = idx / nv, p = (idx - img * nv) * V;
-        const size_t o = ((size_t)img * C + c) * (size_t)HW + p;
-        float g[V], xv[V], d[V];
-        cpl_load<V>(g, gy + o);
-        if (x) cpl_load<V>(xv, x + o);
-#pragma unroll
-        for (int e = 0; e < V; ++e) {
-            d[e] = g[e] * s;
-            acc[0] += g[e];
-            if (x) acc[1] = fmaf(g[e], xv[e], acc[1]);
-        }
-        if (gx) cpl_store<V>(gx + o, d);
-    }
-    if (sums) {
-        __shared__ float sm[2][4];
-        cpl_block_sum<2>(acc, sm);
-        if (threadIdx.x == 0) {
-            part[(size_t)(2 * c) * Q + qi] = acc[0];
-            part[(size_t)(2 * c + 1) * Q + qi] = s * acc[1];
-        }
-    }
+    an_grad<V, FINC_GRAD_REV>(gy, nullptr, x, ls, nullptr, nullptr, gx, part, 0, C, HW, nv, items, Q, sums, x != nullptr);
 }
 
 // (count, mean, sum of squared differences from the mean) of a set of values; two disjoint sets merge exactly in real arithmetic
@@ -304,70 +260,37 @@ int finc_actnorm_launch(const float *x, const float *ls, const float *tr, float 
     return FINC_OK;
 }
 
-int finc_actnorm_backward_launch(const float *gy, const float *gld, const float *y, const float *ls, float *gx, float *gls, float *gt,
-                                 int B, int C, int HW, float *ws, hipStream_t st)
+// v: the forward's OUTPUT (FINC_GRAD_FWD, FINC_GRAD_REBUILD) or the reverse's INPUT (FINC_GRAD_REV, which takes no gld); tr and xo
+// with FINC_GRAD_REBUILD only
+int finc_actnorm_grad_launch(FincGradMode mode, const float *gy, const float *gld, const float *v, const float *ls, const float *tr,
+                             float *xo, float *gx, float *gls, float *gt, int B, int C, int HW, float *ws, hipStream_t st)
 {
-    if (!cpl_rows_fit(B, C, HW)) return FINC_ERR_BAD_DIMS;
-    if (!gls) y = nullptr;                                           // only grad_ls reads y
-    const bool wide = cpl_wide(HW, (uintptr_t)gy | (uintptr_t)y | (uintptr_t)gx);
-    const int nv = HW / (wide ? 4 : 1), items = B * nv, Q = cpl_parts(items, C), sums = (gls || gt) ? 1 : 0;
-    const dim3 grid((unsigned)((long long)C * Q)), block(CPL_THREADS);
-    hipLaunchKernelGGL(wide ? finc_actnorm_bwd_kernel<4> : finc_actnorm_bwd_kernel<1>, grid, block, 0, st, gy, gld, y, ls, gx, ws, B, C, HW,
-                       nv, items, Q, sums);
+    const int need_v = (xo || gls) ? 1 : 0, sums = (gls || gt) ? 1 : 0;      // grad_ls and the rebuilt input read v
+    if (!need_v) v = nullptr;
+    const CplGradPlan p = cpl_grad_plan(B, C, HW, C, cpl_bits(gy, v, xo, gx));
+    if (!p.Q) return FINC_ERR_BAD_DIMS;
+    const dim3 block(CPL_THREADS);
+    if (mode == FINC_GRAD_REBUILD)
+        hipLaunchKernelGGL(p.wide ? finc_actnorm_recon_kernel<4> : finc_actnorm_recon_kernel<1>, p.grid, block, 0, st, gy, gld, v, ls, tr, xo,
+                           gx, ws, B, C, HW, p.nv, p.items, p.Q, sums, need_v);
+    else if (mode == FINC_GRAD_REV)
+        hipLaunchKernelGGL(p.wide ? finc_actnorm_rev_bwd_kernel<4> : finc_actnorm_rev_bwd_kernel<1>, p.grid, block, 0, st, gy, v, ls, gx, ws, C,
+                           HW, p.nv, p.items, p.Q, sums);
+    else
+        hipLaunchKernelGGL(p.wide ? finc_actnorm_bwd_kernel<4> : finc_actnorm_bwd_kernel<1>, p.grid, block, 0, st, gy, gld, v, ls, gx, ws, B, C,
+                           HW, p.nv, p.items, p.Q, sums);
     FINC_CHECK_LAUNCH();
-    if (sums) {
-        hipLaunchKernelGGL(finc_coupling_reduce_kernel, dim3((unsigned)(2 * C)), dim3(64), 0, st, (const float *)ws, Q + 1, gt, gls, 1);
-        FINC_CHECK_LAUNCH();
-    }
-    return FINC_OK;
-}
-
-int finc_actnorm_backward_reconstruct_launch(const float *gy, const float *gld, const float *y, const float *ls, const float *tr, float *xo,
-                                             float *gx, float *gls, float *gt, int B, int C, int HW, float *ws, hipStream_t st)
-{
-    if (!cpl_rows_fit(B, C, HW)) return FINC_ERR_BAD_DIMS;
-    const int need_y = (xo || gls) ? 1 : 0;                          // grad_ls and the rebuilt input read y
-    if (!need_y) y = nullptr;
-    const bool wide = cpl_wide(HW, (uintptr_t)gy | (uintptr_t)y | (uintptr_t)xo | (uintptr_t)gx);
-    const int nv = HW / (wide ? 4 : 1), items = B * nv, Q = cpl_parts(items, C), sums = (gls || gt) ? 1 : 0;
-    const dim3 grid((unsigned)((long long)C * Q)), block(CPL_THREADS);
-    hipLaunchKernelGGL(wide ? finc_actnorm_recon_kernel<4> : finc_actnorm_recon_kernel<1>, grid, block, 0, st, gy, gld, y, ls, tr, xo, gx, ws,
-                       B, C, HW, nv, items, Q, sums, need_y);
-    FINC_CHECK_LAUNCH();
-    if (sums) {
-        hipLaunchKernelGGL(finc_coupling_reduce_kernel, dim3((unsigned)(2 * C)), dim3(64), 0, st, (const float *)ws, Q + 1, gt, gls, 1);
-        FINC_CHECK_LAUNCH();
-    }
-    return FINC_OK;
-}
-
-int finc_actnorm_reverse_backward_launch(const float *gy, const float *x, const float *ls, float *gx, float *gls, float *gt, int B, int C,
-                                         int HW, float *ws, hipStream_t st)
-{
-    if (!cpl_rows_fit(B, C, HW)) return FINC_ERR_BAD_DIMS;
-    if (!gls) x = nullptr;                                           // only grad_ls reads x
-    const bool wide = cpl_wide(HW, (uintptr_t)gy | (uintptr_t)x | (uintptr_t)gx);
-    const int nv = HW / (wide ? 4 : 1), items = B * nv, Q = cpl_parts(items, C), sums = (gls || gt) ? 1 : 0;
-    const dim3 grid((unsigned)((long long)C * Q)), block(CPL_THREADS);
-    hipLaunchKernelGGL(wide ? finc_actnorm_rev_bwd_kernel<4> : finc_actnorm_rev_bwd_kernel<1>, grid, block, 0, st, gy, x, ls, gx, ws, C, HW,
-                       nv, items, Q, sums);
-    FINC_CHECK_LAUNCH();
-    if (sums) {
-        hipLaunchKernelGGL(finc_coupling_reduce_kernel, dim3((unsigned)(2 * C)), dim3(64), 0, st, (const float *)ws, Q, gt, gls, 1);
-        FINC_CHECK_LAUNCH();
-    }
-    return FINC_OK;
+    return cpl_reduce_pairs(sums, ws, 2 * C, mode == FINC_GRAD_REV ? p.Q : p.Q + 1, gt, gls, st);
 }
 
 int finc_actnorm_init_launch(const float *x, float *ls, float *tr, int B, int C, int HW, float *ws, hipStream_t st)
 {
-    if (!cpl_rows_fit(B, C, HW)) return FINC_ERR_BAD_DIMS;
-    const bool wide = cpl_wide(HW, (uintptr_t)x);
-    const int nv = HW / (wide ? 4 : 1), items = B * nv, Q = cpl_parts(items, C);
-    const dim3 grid((unsigned)((long long)C * Q)), block(CPL_THREADS);
-    hipLaunchKernelGGL(wide ? finc_actnorm_stats_kernel<4> : finc_actnorm_stats_kernel<1>, grid, block, 0, st, x, ws, C, HW, nv, items, Q);
+    const CplGradPlan p = cpl_grad_plan(B, C, HW, C, cpl_bits(x));
+    if (!p.Q) return FINC_ERR_BAD_DIMS;
+    hipLaunchKernelGGL(p.wide ? finc_actnorm_stats_kernel<4> : finc_actnorm_stats_kernel<1>, p.grid, dim3(CPL_THREADS), 0, st, x, ws, C, HW,
+                       p.nv, p.items, p.Q);
     FINC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(finc_actnorm_stats_final_kernel, dim3((unsigned)C), dim3(64), 0, st, (const float *)ws, Q, ls, tr,
+    hipLaunchKernelGGL(finc_actnorm_stats_final_kernel, dim3((unsigned)C), dim3(64), 0, st, (const float *)ws, p.Q, ls, tr,
                        (float)((long long)B * HW - 1));
     FINC_CHECK_LAUNCH();
     return FINC_OK;

@@ -273,37 +273,29 @@ int finc_mix_gradw_launch(const float *grad_out, const float *in, float *gm, flo
                           int align, hipStream_t st);
 
 // ---- the affine coupling's glue (transform + log-det, its backward, bias + ReLU): finc_coupling.h, compiled into finc_mix.o ----
-// C even; `ws` holds finc_coupling_workspace_floats floats (needed with logdet / ga / gb only); direction +1 forward, -1 reverse
+// Which backward of a per-pixel layer (a mode of the family's one kernel body and one launcher): of direction +1, of direction -1,
+// or of direction +1 from its OUTPUT with the direction's input rebuilt in the same pass (training without stored activations).
+enum FincGradMode { FINC_GRAD_FWD = 0, FINC_GRAD_REV = 1, FINC_GRAD_REBUILD = 2 };
+// C even; `ws` holds finc_coupling_workspace_floats floats (needed with logdet / ga / gb only); direction +1 forward, -1 reverse.
+// logdet[b] = sum s in EITHER direction: the FORWARD map's log-det, at the recovered input when direction is -1; nullptr: none
 size_t finc_coupling_workspace_floats(int B, int C, int HW);
 int finc_coupling_launch(const float *x, const float *raw, const float *a, const float *b, float *y, float *logdet, int B, int C, int HW,
                          int direction, float *ws, hipStream_t st);
-int finc_coupling_backward_launch(const float *gy, const float *gld, const float *x, const float *raw, const float *a, const float *b,
-                                  float *gx, float *graw, float *ga, float *gb, int B, int C, int HW, float *ws, hipStream_t st);
-// direction -1 with logdet[b] = sum s, the FORWARD map's log-det at the recovered input (always summed: `ws` and `logdet` required)
-int finc_coupling_reverse_logdet_launch(const float *x, const float *raw, const float *a, const float *b, float *y, float *logdet, int B,
-                                        int C, int HW, float *ws, hipStream_t st);
-// the backward of direction -1, from the reverse's OUTPUT y; gld: the gradient of that log-det per image, or nullptr
-int finc_coupling_reverse_backward_launch(const float *gy, const float *gld, const float *y, const float *raw, const float *a,
-                                          const float *b, float *gx, float *graw, float *ga, float *gb, int B, int C, int HW, float *ws,
-                                          hipStream_t st);
-// the backward of direction +1 from its OUTPUT y, which also writes the rebuilt input xo; gld, xo, gx, graw, ga, gb may be nullptr
-int finc_coupling_backward_reconstruct_launch(const float *gy, const float *gld, const float *y, const float *raw, const float *a,
-                                              const float *b, float *xo, float *gx, float *graw, float *ga, float *gb, int B, int C, int HW,
-                                              float *ws, hipStream_t st);
+// v: the forward's input (FINC_GRAD_FWD), the reverse's OUTPUT (FINC_GRAD_REV) or the forward's OUTPUT (FINC_GRAD_REBUILD, which also
+// writes the rebuilt input xo); gld: the gradient of the log-det per image; gld, xo, gx, graw, ga, gb may be nullptr
+int finc_coupling_grad_launch(FincGradMode mode, const float *gy, const float *gld, const float *v, const float *raw, const float *a,
+                              const float *b, float *xo, float *gx, float *graw, float *ga, float *gb, int B, int C, int HW, float *ws,
+                              hipStream_t st);
 int finc_bias_relu_launch(const float *in, const float *bias, float *out, int B, int C, int HW, hipStream_t st);
 // ---- ActNorm (transform + log-det, its backward from the forward's OUTPUT, the data-dependent initialisation): finc_actnorm.h, same object ----
 // `ws` holds finc_actnorm_workspace_floats floats (backward with gls / gt, and the initialisation)
 size_t finc_actnorm_workspace_floats(int B, int C, int HW);
 int finc_actnorm_launch(const float *x, const float *ls, const float *tr, float *y, float *logdet, int B, int C, int HW, int direction,
                         hipStream_t st);
-int finc_actnorm_backward_launch(const float *gy, const float *gld, const float *y, const float *ls, float *gx, float *gls, float *gt,
-                                 int B, int C, int HW, float *ws, hipStream_t st);
-// finc_actnorm_backward_launch that also writes the rebuilt input xo = y * exp(ls) + tr; gld, xo (then tr too), gx, gls, gt may be nullptr
-int finc_actnorm_backward_reconstruct_launch(const float *gy, const float *gld, const float *y, const float *ls, const float *tr, float *xo,
-                                             float *gx, float *gls, float *gt, int B, int C, int HW, float *ws, hipStream_t st);
-// the backward of direction -1, from the reverse's INPUT x
-int finc_actnorm_reverse_backward_launch(const float *gy, const float *x, const float *ls, float *gx, float *gls, float *gt, int B, int C,
-                                         int HW, float *ws, hipStream_t st);
+// v: the forward's OUTPUT (FINC_GRAD_FWD; FINC_GRAD_REBUILD, which also writes the rebuilt input xo = v * exp(ls) + tr) or the
+// reverse's INPUT (FINC_GRAD_REV: no gld); gld, tr and xo, gx, gls, gt may be nullptr
+int finc_actnorm_grad_launch(FincGradMode mode, const float *gy, const float *gld, const float *v, const float *ls, const float *tr,
+                             float *xo, float *gx, float *gls, float *gt, int B, int C, int HW, float *ws, hipStream_t st);
 int finc_actnorm_init_launch(const float *x, float *ls, float *tr, int B, int C, int HW, float *ws, hipStream_t st);
 // ---- backward through the unit's inverse (adjoint bank, lead product, the weight gradient's sign): finc_adjoint.h, same object ----
 // w_adj [G*Cq][Cq][KH][KW]: the canonical bank whose inverse (orientation complemented) is the adjoint solve up to the lead product;

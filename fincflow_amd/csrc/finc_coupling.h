@@ -5,13 +5,13 @@
 // sub, mul, cat -- and two more (bias add, ReLU) behind each of the first two convolutions.  Here:
 //   * finc_coupling_kernel      one pass: h = a * raw + b per channel, s = 2 tanh(u / 2), y2 = x2 * exp(s) + t  (forward, + log-det)
 //                               or y2 = (x2 - t) * exp(-s) (reverse); the untouched half is copied by the same threads.
-//   * finc_coupling_bwd_kernel  one pass: every gradient of the forward direction; s and exp(s) are recomputed from raw (two
+//   * cpl_grad<V, MODE>         one pass: every gradient of one direction; s and exp(s) are recomputed from raw (two
 //                               transcendentals per element) instead of being saved: saving them would add two tensor writes to the
-//                               forward and two reads here, and this kernel is bound by its memory traffic, not by the VALU.
-//   * finc_coupling_rev_bwd_kernel  the same for the reverse direction, from the reverse's OUTPUT (what `reverse` under autograd
-//                               records inside ops.reverse_grad()).
-//   * finc_coupling_recon_kernel  the backward of the forward direction from the forward's OUTPUT, which also writes the rebuilt
-//                               input: the step of a training backward that stores no activations.
+//                               forward and two reads here, and this body is bound by its memory traffic, not by the VALU.  Its modes
+//                               are the kernels finc_coupling_bwd_kernel (forward direction, from its input),
+//                               finc_coupling_rev_bwd_kernel (reverse direction, from its OUTPUT: what `reverse` under autograd
+//                               records inside ops.reverse_grad()) and finc_coupling_recon_kernel (forward direction from its OUTPUT,
+//                               which also writes the rebuilt input: the step of a training backward that stores no activations).
 //   * finc_coupling_rev_logdet_kernel  the reverse pass that also sums s per image: the sample and the forward log-det at the
 //                               sample in one pass (FlowSequential.sample_with_log_prob / rsample_with_log_prob).
 //   * finc_bias_relu_kernel     out = max(in + bias[c], 0), in place or not.
@@ -133,95 +133,67 @@ __global__ __launch_bounds__(CPL_THREADS) void finc_coupling_rev_logdet_kernel(c
     cpl_transform<V, -1, true>(x, raw, a, b, y, part, half, HW, nv, items, P);
 }
 
+// Every backward of the coupling is ONE body, cpl_grad<V, MODE>; a mode (FincGradMode) is what it reads and the few lines of
+// arithmetic behind `if constexpr`:
+//   FINC_GRAD_FWD      of y2 = x2 * exp(s) + t, from `v` = the forward's INPUT x (layers/coupling.py:79-93).
+//   FINC_GRAD_REV      of y2 = (x2 - t) * exp(-s) (layers/coupling.py:95-101), from `v` = the reverse's OUTPUT y: d y2 / d x2 = E =
+//                      exp(-s), d y2 / d t = -E, d y2 / d s = -y2, so the input is not needed (in a recorded reverse chain y is the
+//                      tensor the next layer keeps anyway).  gld: the gradient of the log-det finc_coupling_rev_logdet_kernel reports
+//                      (sum s, per image), d / d s = gld[img]; nullptr = none, and then every result has the bits of a backward
+//                      without that argument: the neutral element is -0 in THIS mode (v + -0 is v for every v, -0 included).
+//   FINC_GRAD_REBUILD  of the forward direction from `v` = the forward's OUTPUT y, which also rebuilds the forward's input into xo:
+//                      with d = y2 - t, x2 = d * exp(-s) (the arithmetic of finc_coupling_kernel's reverse direction, so the same
+//                      bits), and x2 * exp(s) = d: grad_x2 = grad_y2 * exp(s), grad_h[2j+1] = grad_y2, grad_h[2j] = (grad_y2 * d +
+//                      gld[img]) * (1 - th^2).  What a training step without stored activations runs per coupling: one launch instead
+//                      of a reverse launch plus a backward launch; y and raw are read once.  xo == v and gx == gy are allowed here (a
+//                      thread reads its pieces before it writes them, and nobody else touches them).
+// s and exp(s) are recomputed from raw (two transcendentals per element), not saved by the forward.
 // Workgroup = (channel pair j, part): Q parts per pair share its B * HW / V thread items, so the four per-channel sums of a
 // workgroup belong to ONE pair.  Partials: part[(4j + k) * Q + q], k = 0 grad_a[2j], 1 grad_b[2j], 2 grad_a[2j+1], 3 grad_b[2j+1].
-// gld (grad of the log-det, per image), gx, graw may be nullptr; `sums` = 0 skips the partials.
-template <int V>
-__global__ __launch_bounds__(CPL_THREADS) void finc_coupling_bwd_kernel(const float *__restrict__ gy, const float *__restrict__ gld,
-                                                                        const float *__restrict__ x, const float *__restrict__ raw,
-                                                                        const float *__restrict__ a, const float *__restrict__ b,
-                                                                        float *__restrict__ gx, float *__restrict__ graw,
-                                                                        float *__restrict__ part, int half, int HW, int nv, int items, int Q,
-                                                                        int sums)
+// gld (grad of the log-det, per image), xo, gx, graw may be nullptr; `sums` = 0 skips the partials.
+template <int V, int MODE>
+__device__ __forceinline__ void cpl_grad(const float *gy, const float *__restrict__ gld, const float *v, const float *__restrict__ raw,
+                                         const float *__restrict__ a, const float *__restrict__ b, float *xo, float *gx,
+                                         float *__restrict__ graw, float *__restrict__ part, int half, int HW, int nv, int items, int Q,
+                                         int sums)
 {
+    constexpr bool REBUILD = MODE == FINC_GRAD_REBUILD;
     const int j = (int)blockIdx.x / Q, qi = (int)blockIdx.x - j * Q;
-    const float au = a[2 * j], bu = b[2 * j], at = a[2 * j + 1];
+    const float au = a[2 * j], bu = b[2 * j], at = a[2 * j + 1], bt = REBUILD ? b[2 * j + 1] : 0.f;
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     for (int idx = qi * CPL_THREADS + (int)threadIdx.x; idx < items; idx += Q * CPL_THREADS) {
         const int img = idx / nv, p = (idx - img * nv) * V;
         const size_t ibase = (size_t)img * (size_t)(2 * half) * (size_t)HW;
         const size_t o1 = ibase + (size_t)j * HW + p, o2 = o1 + (size_t)half * HW;
         const size_t ou = ibase + (size_t)(2 * j) * HW + p, ot = ou + HW;
-        float g1[V], g2[V], x2[V], u[V], t[V], gx2[V], gu[V], gt[V];
+        float g1[V], g2[V], v1[V], v2[V], u[V], t[V], x2[V], gx2[V], gu[V], gt[V];
         if (gx) cpl_load<V>(g1, gy + o1);
         cpl_load<V>(g2, gy + o2);
-        cpl_load<V>(x2, x + o2);
+        if constexpr (REBUILD)
+            if (xo) cpl_load<V>(v1, v + o1);
+        cpl_load<V>(v2, v + o2);
         cpl_load<V>(u, raw + ou);
-        if (sums) cpl_load<V>(t, raw + ot);
-        const float gl = gld ? gld[img] : 0.f;
+        if (REBUILD || sums) cpl_load<V>(t, raw + ot);
+        const float gl = gld ? gld[img] : (MODE == FINC_GRAD_REV ? -0.f : 0.f);
 #pragma unroll
         for (int e = 0; e < V; ++e) {
-            const float th = tanhf(0.5f * fmaf(au, u[e], bu));     // s = 2 th, 1 - s*s/4 = 1 - th*th
-            gx2[e] = g2[e] * expf(2.f * th);
-            const float gh = fmaf(gx2[e], x2[e], gl) * fmaf(-th, th, 1.f);
-            gu[e] = au * gh;
-            gt[e] = at * g2[e];
-            if (sums) {
-                acc[0] = fmaf(gh, u[e], acc[0]);
-                acc[1] += gh;
-                acc[2] = fmaf(g2[e], t[e], acc[2]);
-                acc[3] += g2[e];
+            const float th = tanhf(0.5f * fmaf(au, u[e], bu));     // s = 2 th, d s / d h = 1 - s*s/4 = 1 - th*th
+            float ghu, ght;                                        // the gradients of h[2j] and h[2j+1]
+            if constexpr (MODE == FINC_GRAD_FWD) {
+                gx2[e] = g2[e] * expf(2.f * th);
+                ghu = fmaf(gx2[e], v2[e], gl) * fmaf(-th, th, 1.f);
+                ght = g2[e];
+            } else if constexpr (MODE == FINC_GRAD_REV) {
+                gx2[e] = g2[e] * expf(-2.f * th);
+                ghu = (-(g2[e] * v2[e]) + gl) * fmaf(-th, th, 1.f);
+                ght = -gx2[e];
+            } else {
+                const float s = 2.f * th, d = v2[e] - fmaf(at, t[e], bt);
+                x2[e] = d * expf(-s);
+                gx2[e] = g2[e] * expf(s);
+                ghu = fmaf(g2[e], d, gl) * fmaf(-th, th, 1.f);
+                ght = g2[e];
             }
-        }
-        if (gx) {
-            cpl_store<V>(gx + o1, g1);
-            cpl_store<V>(gx + o2, gx2);
-        }
-        if (graw) {
-            cpl_store<V>(graw + ou, gu);
-            cpl_store<V>(graw + ot, gt);
-        }
-    }
-    if (sums) {
-        __shared__ float sm[4][4];
-        cpl_block_sum<4>(acc, sm);
-        if (threadIdx.x < 4) part[((size_t)(4 * j) + threadIdx.x) * Q + qi] = acc[threadIdx.x];
-    }
-}
-
-// The backward of the REVERSE direction, y2 = (x2 - t) * exp(-s) (layers/coupling.py:95-101), from grad_y and the reverse's OUTPUT y:
-// d y2 / d x2 = E = exp(-s), d y2 / d t = -E, d y2 / d s = -y2, so the input is not needed (in a recorded reverse chain y is the tensor
-// the next layer keeps anyway).  Workgroups, partials and the nullptr rules as in finc_coupling_bwd_kernel.  gld: the gradient of the
-// log-det finc_coupling_rev_logdet_kernel reports (sum s, per image), d / d s = gld[img]; nullptr = none, and then every result has the
-// bits it had before this argument existed (the neutral element below is -0: v + -0 is v for every v, -0 included).
-template <int V>
-__global__ __launch_bounds__(CPL_THREADS) void finc_coupling_rev_bwd_kernel(const float *__restrict__ gy, const float *__restrict__ gld,
-                                                                            const float *__restrict__ y, const float *__restrict__ raw,
-                                                                            const float *__restrict__ a, const float *__restrict__ b,
-                                                                            float *__restrict__ gx, float *__restrict__ graw,
-                                                                            float *__restrict__ part, int half, int HW, int nv, int items,
-                                                                            int Q, int sums)
-{
-    const int j = (int)blockIdx.x / Q, qi = (int)blockIdx.x - j * Q;
-    const float au = a[2 * j], bu = b[2 * j], at = a[2 * j + 1];
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int idx = qi * CPL_THREADS + (int)threadIdx.x; idx < items; idx += Q * CPL_THREADS) {
-        const int img = idx / nv, p = (idx - img * nv) * V;
-        const size_t ibase = (size_t)img * (size_t)(2 * half) * (size_t)HW;
-        const size_t o1 = ibase + (size_t)j * HW + p, o2 = o1 + (size_t)half * HW;
-        const size_t ou = ibase + (size_t)(2 * j) * HW + p, ot = ou + HW;
-        float g1[V], g2[V], y2[V], u[V], t[V], gx2[V], gu[V], gt[V];
-        if (gx) cpl_load<V>(g1, gy + o1);
-        cpl_load<V>(g2, gy + o2);
-        cpl_load<V>(y2, y + o2);
-        cpl_load<V>(u, raw + ou);
-        if (sums) cpl_load<V>(t, raw + ot);
-        const float gl = gld ? gld[img] : -0.f;
-#pragma unroll
-        for (int e = 0; e < V; ++e) {
-            const float th = tanhf(0.5f * fmaf(au, u[e], bu));     // s = 2 th, d s / d h = 1 - th*th
-            gx2[e] = g2[e] * expf(-2.f * th);
-            const float ghu = (-(g2[e] * y2[e]) + gl) * fmaf(-th, th, 1.f), ght = -gx2[e];
             gu[e] = au * ghu;
             gt[e] = at * ght;
             if (sums) {
@@ -231,6 +203,12 @@ __global__ __launch_bounds__(CPL_THREADS) void finc_coupling_rev_bwd_kernel(cons
                 acc[3] += ght;
             }
         }
+        if constexpr (REBUILD) {
+            if (xo) {
+                cpl_store<V>(xo + o1, v1);
+                cpl_store<V>(xo + o2, x2);
+            }
+        }
         if (gx) {
             cpl_store<V>(gx + o1, g1);
             cpl_store<V>(gx + o2, gx2);
@@ -247,12 +225,30 @@ __global__ __launch_bounds__(CPL_THREADS) void finc_coupling_rev_bwd_kernel(cons
     }
 }
 
-// The backward of the FORWARD direction from the forward's OUTPUT y, which also rebuilds the forward's input (layers/coupling.py:79-101):
-// with d = y2 - t, x2 = d * exp(-s) (the arithmetic of finc_coupling_kernel's reverse direction, so the same bits), and
-// x2 * exp(s) = d: grad_x2 = grad_y2 * exp(s), grad_h[2j+1] = grad_y2, grad_h[2j] = (grad_y2 * d + gld[img]) * (1 - th^2).  What a
-// training step without stored activations runs per coupling: one launch instead of a reverse launch plus a backward launch; y and
-// raw are read once.  Workgroups and partials as in finc_coupling_bwd_kernel.  gld, xo, gx, graw may be nullptr; `sums` = 0 skips the
-// partials.  xo == y and gx == gy are allowed (a thread reads its pieces before it writes them, and nobody else touches them).
+// The three modes under the names and parameter lists they have always had (the __restrict__ of a kernel's own parameters holds
+// inside the body: without the rebuild nothing may overlap).
+template <int V>
+__global__ __launch_bounds__(CPL_THREADS) void finc_coupling_bwd_kernel(const float *__restrict__ gy, const float *__restrict__ gld,
+                                                                        const float *__restrict__ x, const float *__restrict__ raw,
+                                                                        const float *__restrict__ a, const float *__restrict__ b,
+                                                                        float *__restrict__ gx, float *__restrict__ graw,
+                                                                        float *__restrict__ part, int half, int HW, int nv, int items, int Q,
+                                                                        int sums)
+{
+    cpl_grad<V, FINC_GRAD_FWD>(gy, gld, x, raw, a, b, nullptr, gx, graw, part, half, HW, nv, items, Q, sums);
+}
+
+template <int V>
+__global__ __launch_bounds__(CPL_THREADS) void finc_coupling_rev_bwd_kernel(const float *__restrict__ gy, const float *__restrict__ gld,
+                                                                            const float *__restrict__ y, const float *__restrict__ raw,
+                                                                            const float *__restrict__ a, const float *__restrict__ b,
+                                                                            float *__restrict__ gx, float *__restrict__ graw,
+                                                                            float *__restrict__ part, int half, int HW, int nv, int items,
+                                                                            int Q, int sums)
+{
+    cpl_grad<V, FINC_GRAD_REV>(gy, gld, y, raw, a, b, nullptr, gx, graw, part, half, HW, nv, items, Q, sums);
+}
+
 template <int V>
 __global__ __launch_bounds__(CPL_THREADS) void finc_coupling_recon_kernel(const float *gy, const float *__restrict__ gld, const float *y,
                                                                           const float *__restrict__ raw, const float *__restrict__ a,
@@ -260,56 +256,7 @@ __global__ __launch_bounds__(CPL_THREADS) void finc_coupling_recon_kernel(const 
                                                                           float *__restrict__ graw, float *__restrict__ part, int half, int HW,
                                                                           int nv, int items, int Q, int sums)
 {
-    const int j = (int)blockIdx.x / Q, qi = (int)blockIdx.x - j * Q;
-    const float au = a[2 * j], bu = b[2 * j], at = a[2 * j + 1], bt = b[2 * j + 1];
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int idx = qi * CPL_THREADS + (int)threadIdx.x; idx < items; idx += Q * CPL_THREADS) {
-        const int img = idx / nv, p = (idx - img * nv) * V;
-        const size_t ibase = (size_t)img * (size_t)(2 * half) * (size_t)HW;
-        const size_t o1 = ibase + (size_t)j * HW + p, o2 = o1 + (size_t)half * HW;
-        const size_t ou = ibase + (size_t)(2 * j) * HW + p, ot = ou + HW;
-        float g1[V], g2[V], y1[V], y2[V], u[V], t[V], x2[V], gx2[V], gu[V], gt[V];
-        if (gx) cpl_load<V>(g1, gy + o1);
-        cpl_load<V>(g2, gy + o2);
-        if (xo) cpl_load<V>(y1, y + o1);
-        cpl_load<V>(y2, y + o2);
-        cpl_load<V>(u, raw + ou);
-        cpl_load<V>(t, raw + ot);
-        const float gl = gld ? gld[img] : 0.f;
-#pragma unroll
-        for (int e = 0; e < V; ++e) {
-            const float th = tanhf(0.5f * fmaf(au, u[e], bu));     // s = 2 th, d s / d h = 1 - th*th
-            const float s = 2.f * th, d = y2[e] - fmaf(at, t[e], bt);
-            x2[e] = d * expf(-s);
-            gx2[e] = g2[e] * expf(s);
-            const float gh = fmaf(g2[e], d, gl) * fmaf(-th, th, 1.f);
-            gu[e] = au * gh;
-            gt[e] = at * g2[e];
-            if (sums) {
-                acc[0] = fmaf(gh, u[e], acc[0]);
-                acc[1] += gh;
-                acc[2] = fmaf(g2[e], t[e], acc[2]);
-                acc[3] += g2[e];
-            }
-        }
-        if (xo) {
-            cpl_store<V>(xo + o1, y1);
-            cpl_store<V>(xo + o2, x2);
-        }
-        if (gx) {
-            cpl_store<V>(gx + o1, g1);
-            cpl_store<V>(gx + o2, gx2);
-        }
-        if (graw) {
-            cpl_store<V>(graw + ou, gu);
-            cpl_store<V>(graw + ot, gt);
-        }
-    }
-    if (sums) {
-        __shared__ float sm[4][4];
-        cpl_block_sum<4>(acc, sm);
-        if (threadIdx.x < 4) part[((size_t)(4 * j) + threadIdx.x) * Q + qi] = acc[threadIdx.x];
-    }
+    cpl_grad<V, FINC_GRAD_REBUILD>(gy, gld, y, raw, a, b, xo, gx, graw, part, half, HW, nv, items, Q, sums);
 }
 
 // One wave per output: out = sum of its n consecutive partials, lane l takes l, l + 64, ... and the lanes meet in a butterfly.
@@ -375,6 +322,31 @@ inline bool cpl_rows_fit(int B, int C, int HW)          // a channel's B * HW / 
 {
     return (size_t)C * HW * 4 < ((size_t)1 << 31) && (long long)B * HW < (1LL << 31) - (CPL_CHIP_WGS + 1) * CPL_THREADS;
 }
+template <typename... P>
+inline uintptr_t cpl_bits(const P *...p) { return (... | (uintptr_t)p); }     // every pointer's address bits (nullptr adds none)
+// A backward launch: `outer` channel units (pairs, channels) share B * HW / V items each in Q parts, a workgroup per (unit, part).
+// `ptrs`: cpl_bits of every activation pointer the launch touches.  Q = 0: the rows do not fit (cpl_rows_fit).
+struct CplGradPlan {
+    bool wide;
+    int nv, items, Q;
+    dim3 grid;
+};
+inline CplGradPlan cpl_grad_plan(int B, int C, int HW, int outer, uintptr_t ptrs)
+{
+    if (!cpl_rows_fit(B, C, HW)) return CplGradPlan{false, 0, 0, 0, dim3(0)};
+    const bool wide = cpl_wide(HW, ptrs);
+    const int nv = HW / (wide ? 4 : 1), items = B * nv, Q = cpl_parts(items, outer);
+    return CplGradPlan{wide, nv, items, Q, dim3((unsigned)((long long)outer * Q))};
+}
+// the tail of a backward with per-channel sums: output o of `outputs`, n partials each, to out_a / out_b (finc_coupling_reduce_kernel)
+inline int cpl_reduce_pairs(int sums, const float *ws, int outputs, int n, float *out_a, float *out_b, hipStream_t st)
+{
+    if (sums) {
+        hipLaunchKernelGGL(finc_coupling_reduce_kernel, dim3((unsigned)outputs), dim3(64), 0, st, ws, n, out_a, out_b, 1);
+        FINC_CHECK_LAUNCH();
+    }
+    return FINC_OK;
+}
 inline unsigned cpl_row_grid(long long items)           // grid-stride over rows, up to four chips' worth; 0: they do not index as unsigned
 {
     const long long wgs = (items + CPL_THREADS - 1) / CPL_THREADS, most = 4 * CPL_CHIP_WGS;
@@ -390,103 +362,47 @@ size_t finc_coupling_workspace_floats(int B, int C, int HW)
     return (size_t)(fwd > bwd ? fwd : bwd);
 }
 
+// logdet (either direction): the log-det of the FORWARD map, sum s per image -- in the reverse direction at the recovered input y
+// (B x P partials in `ws`, then the reduce); nullptr: none, and `ws` is not touched
 int finc_coupling_launch(const float *x, const float *raw, const float *a, const float *b, float *y, float *logdet, int B, int C, int HW,
                          int direction, float *ws, hipStream_t st)
 {
     const int half = C / 2;
     if ((size_t)C * HW * 4 >= ((size_t)1 << 31)) return FINC_ERR_BAD_DIMS;
-    const bool wide = cpl_wide(HW, (uintptr_t)x | (uintptr_t)raw | (uintptr_t)y);
+    const bool wide = cpl_wide(HW, cpl_bits(x, raw, y));
     const int nv = HW / (wide ? 4 : 1), items = half * nv, P = cpl_parts(items, B);
     if ((long long)B * P >= (1LL << 31)) return FINC_ERR_BAD_DIMS;
     const dim3 grid((unsigned)((long long)B * P)), block(CPL_THREADS);
-    const bool ld = direction > 0 && logdet;
-    const auto kernel = direction < 0 ? (wide ? finc_coupling_kernel<4, -1, false> : finc_coupling_kernel<1, -1, false>)
-                        : ld          ? (wide ? finc_coupling_kernel<4, 1, true> : finc_coupling_kernel<1, 1, true>)
-                                      : (wide ? finc_coupling_kernel<4, 1, false> : finc_coupling_kernel<1, 1, false>);
+    const auto kernel = !logdet ? (direction < 0 ? (wide ? finc_coupling_kernel<4, -1, false> : finc_coupling_kernel<1, -1, false>)
+                                                 : (wide ? finc_coupling_kernel<4, 1, false> : finc_coupling_kernel<1, 1, false>))
+                        : direction < 0 ? (wide ? finc_coupling_rev_logdet_kernel<4> : finc_coupling_rev_logdet_kernel<1>)
+                                        : (wide ? finc_coupling_kernel<4, 1, true> : finc_coupling_kernel<1, 1, true>);
     hipLaunchKernelGGL(kernel, grid, block, 0, st, x, raw, a, b, y, ws, half, HW, nv, items, P);
     FINC_CHECK_LAUNCH();
-    if (ld) {
+    if (logdet) {
         hipLaunchKernelGGL(finc_coupling_reduce_kernel, dim3((unsigned)B), dim3(64), 0, st, (const float *)ws, P, logdet, (float *)nullptr, 0);
         FINC_CHECK_LAUNCH();
     }
     return FINC_OK;
 }
 
-// The reverse direction with the forward map's log-det of the recovered input: the grid, the parts and the reduce of the forward
-// direction with its log-det (B x P partials: the forward bound of finc_coupling_workspace_floats covers them).
-int finc_coupling_reverse_logdet_launch(const float *x, const float *raw, const float *a, const float *b, float *y, float *logdet, int B,
-                                        int C, int HW, float *ws, hipStream_t st)
-{
-    const int half = C / 2;
-    if ((size_t)C * HW * 4 >= ((size_t)1 << 31)) return FINC_ERR_BAD_DIMS;
-    const bool wide = cpl_wide(HW, (uintptr_t)x | (uintptr_t)raw | (uintptr_t)y);
-    const int nv = HW / (wide ? 4 : 1), items = half * nv, P = cpl_parts(items, B);
-    if ((long long)B * P >= (1LL << 31)) return FINC_ERR_BAD_DIMS;
-    const dim3 grid((unsigned)((long long)B * P)), block(CPL_THREADS);
-    hipLaunchKernelGGL(wide ? finc_coupling_rev_logdet_kernel<4> : finc_coupling_rev_logdet_kernel<1>, grid, block, 0, st, x, raw, a, b, y,
-                       ws, half, HW, nv, items, P);
-    FINC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(finc_coupling_reduce_kernel, dim3((unsigned)B), dim3(64), 0, st, (const float *)ws, P, logdet, (float *)nullptr, 0);
-    FINC_CHECK_LAUNCH();
-    return FINC_OK;
-}
-
-int finc_coupling_backward_launch(const float *gy, const float *gld, const float *x, const float *raw, const float *a, const float *b,
-                                  float *gx, float *graw, float *ga, float *gb, int B, int C, int HW, float *ws, hipStream_t st)
+int finc_coupling_grad_launch(FincGradMode mode, const float *gy, const float *gld, const float *v, const float *raw, const float *a,
+                              const float *b, float *xo, float *gx, float *graw, float *ga, float *gb, int B, int C, int HW, float *ws,
+                              hipStream_t st)
 {
     const int half = C / 2, sums = (ga || gb) ? 1 : 0;
-    if (!cpl_rows_fit(B, C, HW)) return FINC_ERR_BAD_DIMS;
-    const bool wide = cpl_wide(HW, (uintptr_t)gy | (uintptr_t)x | (uintptr_t)raw | (uintptr_t)gx | (uintptr_t)graw);
-    const int nv = HW / (wide ? 4 : 1), items = B * nv, Q = cpl_parts(items, half);
-    const dim3 grid((unsigned)((long long)half * Q)), block(CPL_THREADS);
-    hipLaunchKernelGGL(wide ? finc_coupling_bwd_kernel<4> : finc_coupling_bwd_kernel<1>, grid, block, 0, st, gy, gld, x, raw, a, b, gx, graw,
-                       ws, half, HW, nv, items, Q, sums);
-    FINC_CHECK_LAUNCH();
-    if (sums) {
-        hipLaunchKernelGGL(finc_coupling_reduce_kernel, dim3((unsigned)(4 * half)), dim3(64), 0, st, (const float *)ws, Q, ga, gb, 1);
-        FINC_CHECK_LAUNCH();
+    const CplGradPlan p = cpl_grad_plan(B, C, HW, half, cpl_bits(gy, v, raw, xo, gx, graw));
+    if (!p.Q) return FINC_ERR_BAD_DIMS;
+    if (mode == FINC_GRAD_REBUILD) {
+        hipLaunchKernelGGL(p.wide ? finc_coupling_recon_kernel<4> : finc_coupling_recon_kernel<1>, p.grid, dim3(CPL_THREADS), 0, st, gy, gld, v,
+                           raw, a, b, xo, gx, graw, ws, half, HW, p.nv, p.items, p.Q, sums);
+    } else {
+        const auto kernel = mode == FINC_GRAD_REV ? (p.wide ? finc_coupling_rev_bwd_kernel<4> : finc_coupling_rev_bwd_kernel<1>)
+                                                  : (p.wide ? finc_coupling_bwd_kernel<4> : finc_coupling_bwd_kernel<1>);
+        hipLaunchKernelGGL(kernel, p.grid, dim3(CPL_THREADS), 0, st, gy, gld, v, raw, a, b, gx, graw, ws, half, HW, p.nv, p.items, p.Q, sums);
     }
-    return FINC_OK;
-}
-
-// the backward of direction +1 from its OUTPUT y, with the rebuilt input in xo: partials and reduce of finc_coupling_backward_launch
-int finc_coupling_backward_reconstruct_launch(const float *gy, const float *gld, const float *y, const float *raw, const float *a,
-                                              const float *b, float *xo, float *gx, float *graw, float *ga, float *gb, int B, int C, int HW,
-                                              float *ws, hipStream_t st)
-{
-    const int half = C / 2, sums = (ga || gb) ? 1 : 0;
-    if (!cpl_rows_fit(B, C, HW)) return FINC_ERR_BAD_DIMS;
-    const bool wide = cpl_wide(HW, (uintptr_t)gy | (uintptr_t)y | (uintptr_t)raw | (uintptr_t)xo | (uintptr_t)gx | (uintptr_t)graw);
-    const int nv = HW / (wide ? 4 : 1), items = B * nv, Q = cpl_parts(items, half);
-    const dim3 grid((unsigned)((long long)half * Q)), block(CPL_THREADS);
-    hipLaunchKernelGGL(wide ? finc_coupling_recon_kernel<4> : finc_coupling_recon_kernel<1>, grid, block, 0, st, gy, gld, y, raw, a, b, xo, gx,
-                       graw, ws, half, HW, nv, items, Q, sums);
     FINC_CHECK_LAUNCH();
-    if (sums) {
-        hipLaunchKernelGGL(finc_coupling_reduce_kernel, dim3((unsigned)(4 * half)), dim3(64), 0, st, (const float *)ws, Q, ga, gb, 1);
-        FINC_CHECK_LAUNCH();
-    }
-    return FINC_OK;
-}
-
-// gld: the gradient of the reverse's log-det output (finc_coupling_reverse_logdet_launch), or nullptr (the plain reverse)
-int finc_coupling_reverse_backward_launch(const float *gy, const float *gld, const float *y, const float *raw, const float *a,
-                                          const float *b, float *gx, float *graw, float *ga, float *gb, int B, int C, int HW, float *ws,
-                                          hipStream_t st)
-{
-    const int half = C / 2, sums = (ga || gb) ? 1 : 0;
-    if (!cpl_rows_fit(B, C, HW)) return FINC_ERR_BAD_DIMS;
-    const bool wide = cpl_wide(HW, (uintptr_t)gy | (uintptr_t)y | (uintptr_t)raw | (uintptr_t)gx | (uintptr_t)graw);
-    const int nv = HW / (wide ? 4 : 1), items = B * nv, Q = cpl_parts(items, half);
-    const dim3 grid((unsigned)((long long)half * Q)), block(CPL_THREADS);
-    hipLaunchKernelGGL(wide ? finc_coupling_rev_bwd_kernel<4> : finc_coupling_rev_bwd_kernel<1>, grid, block, 0, st, gy, gld, y, raw, a, b,
-                       gx, graw, ws, half, HW, nv, items, Q, sums);
-    FINC_CHECK_LAUNCH();
-    if (sums) {
-        hipLaunchKernelGGL(finc_coupling_reduce_kernel, dim3((unsigned)(4 * half)), dim3(64), 0, st, (const float *)ws, Q, ga, gb, 1);
-        FINC_CHECK_LAUNCH();
-    }
-    return FINC_OK;
+    return cpl_reduce_pairs(sums, ws, 4 * half, p.Q, ga, gb, st);
 }
 
 int finc_bias_relu_launch(const float *in, const float *bias, float *out, int B, int C, int HW, hipStream_t st)

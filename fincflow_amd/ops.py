@@ -402,6 +402,19 @@ def _coupling_args(x, raw, a, b, what="input"):
         raise _lib.FincError(f"finc_coupling: no kernel for {C} channels (the coupling splits an even channel count)")
 
 
+def _coupling_transform(entry, x, raw, a, b, direction, want_logdet, out):
+    """`finc_coupling_f32` (which takes the direction) or `finc_coupling_reverse_logdet_f32` behind their wrappers: (y, logdet)."""
+    out = _out_like(x, out)
+    B, C, H, W = x.shape
+    if x.numel() == 0:
+        return out, (torch.zeros(B, dtype=torch.float32, device=x.device) if want_logdet else None)
+    logdet = torch.empty(B, dtype=torch.float32, device=x.device) if want_logdet else None
+    nbytes = _lib.lib().finc_coupling_workspace_bytes(B, C, H * W) if want_logdet else None
+    _call(entry, x.device, x.data_ptr(), raw.data_ptr(), a.data_ptr(), b.data_ptr(), out.data_ptr(), _ptr(logdet), B, C, H * W, *direction,
+          *_ws_args(x.device, nbytes), _stream_ptr(x))
+    return out, logdet
+
+
 def finc_coupling(x, raw, a, b, direction=1, want_logdet=False, out=None):
     """The affine coupling behind its net (layers/coupling.py:79-101) as one streaming HIP launch: with h = a * raw + b per channel,
     s = 2 tanh(h[:, ::2] / 2), t = h[:, 1::2]:  y = cat(x1, x2 * exp(s) + t) (direction +1) or cat(x1, (x2 - t) * exp(-s)) (-1).
@@ -410,16 +423,28 @@ def finc_coupling(x, raw, a, b, direction=1, want_logdet=False, out=None):
     _coupling_args(x, raw, a, b)
     if direction not in (1, -1):
         raise ValueError("direction must be +1 (forward) or -1 (reverse)")
-    out = _out_like(x, out)
-    B, C, H, W = x.shape
-    want_logdet = bool(want_logdet) and direction == 1
-    if x.numel() == 0:
-        return out, (torch.zeros(B, dtype=torch.float32, device=x.device) if want_logdet else None)
-    logdet = torch.empty(B, dtype=torch.float32, device=x.device) if want_logdet else None
-    nbytes = _lib.lib().finc_coupling_workspace_bytes(B, C, H * W) if want_logdet else None
-    _call("finc_coupling_f32", x.device, x.data_ptr(), raw.data_ptr(), a.data_ptr(), b.data_ptr(), out.data_ptr(), _ptr(logdet), B, C,
-          H * W, direction, *_ws_args(x.device, nbytes), _stream_ptr(x))
-    return out, logdet
+    return _coupling_transform("finc_coupling_f32", x, raw, a, b, (direction,), bool(want_logdet) and direction == 1, out)
+
+
+def _coupling_grads(entry, grad_y, grad_logdet, v, raw, a, b, what, whose, need_acts, need_sums):
+    """One backward entry point of the coupling behind its wrapper: the checks, the outputs asked for -- `need_acts`: (x,) grad_x,
+    grad_raw; `need_sums`: grad_a, grad_b -- the workspace and the call.  `v`: the activation that entry point reads, "input" or
+    "output" (`what`) of `whose` pass; grad_logdet: a tuple, empty for the entry point that takes none."""
+    _coupling_args(v, raw, a, b, what)
+    _require_device(grad_y, "grad_output")
+    if grad_y.shape != v.shape or grad_y.device != v.device:
+        raise ValueError(f"grad_output must match {whose} in shape and device")
+    B, C, H, W = v.shape
+    for g in grad_logdet:
+        _per_image(g, "grad_logdet", v)
+    sums = tuple(torch.empty(C, dtype=torch.float32, device=v.device) if n else None for n in need_sums)
+    outs = tuple(torch.empty_like(v) if n else None for n in need_acts) + sums
+    if _nothing_to_launch(v, outs, sums):
+        return outs
+    nbytes = _lib.lib().finc_coupling_workspace_bytes(B, C, H * W) if any(need_sums) else None
+    _call(entry, v.device, grad_y.data_ptr(), *map(_ptr, grad_logdet), v.data_ptr(), raw.data_ptr(), a.data_ptr(), b.data_ptr(),
+          *map(_ptr, outs), B, C, H * W, *_ws_args(v.device, nbytes), _stream_ptr(v))
+    return outs
 
 
 def finc_coupling_backward(grad_y, grad_logdet, x, raw, a, b, need_gx=True, need_graw=True, need_ga=True, need_gb=True):
@@ -427,22 +452,8 @@ def finc_coupling_backward(grad_y, grad_logdet, x, raw, a, b, need_gx=True, need
     [B,C,H,W] and grad_logdet [B] or None (zeros): (grad_x, grad_raw, grad_a, grad_b), each computed only if asked for (None
     otherwise).  grad_x[:, :C/2] is grad_y[:, :C/2]: what reaches that half through the net is the caller's (autograd's).  s and exp(s)
     are recomputed from `raw`; the per-channel sums run in a fixed order: the same inputs give the same bits."""
-    _coupling_args(x, raw, a, b)
-    _require_device(grad_y, "grad_output")
-    if grad_y.shape != x.shape or grad_y.device != x.device:
-        raise ValueError("grad_output must match input in shape and device")
-    B, C, H, W = x.shape
-    _per_image(grad_logdet, "grad_logdet", x)
-    gx = torch.empty_like(x) if need_gx else None
-    graw = torch.empty_like(raw) if need_graw else None
-    ga = torch.empty(C, dtype=torch.float32, device=x.device) if need_ga else None
-    gb = torch.empty(C, dtype=torch.float32, device=x.device) if need_gb else None
-    if _nothing_to_launch(x, (gx, graw, ga, gb), (ga, gb)):
-        return gx, graw, ga, gb
-    nbytes = _lib.lib().finc_coupling_workspace_bytes(B, C, H * W) if (need_ga or need_gb) else None
-    _call("finc_coupling_backward_f32", x.device, grad_y.data_ptr(), _ptr(grad_logdet), x.data_ptr(), raw.data_ptr(), a.data_ptr(),
-          b.data_ptr(), _ptr(gx), _ptr(graw), _ptr(ga), _ptr(gb), B, C, H * W, *_ws_args(x.device, nbytes), _stream_ptr(x))
-    return gx, graw, ga, gb
+    return _coupling_grads("finc_coupling_backward_f32", grad_y, (grad_logdet,), x, raw, a, b, "input", "input", (need_gx, need_graw),
+                           (need_ga, need_gb))
 
 
 def finc_coupling_reverse_backward(grad_y, y, raw, a, b, need_gx=True, need_graw=True, need_ga=True, need_gb=True):
@@ -450,21 +461,8 @@ def finc_coupling_reverse_backward(grad_y, y, raw, a, b, need_gx=True, need_graw
     and the reverse's OUTPUT `y`: (grad_x, grad_raw, grad_a, grad_b), each computed only if asked for (None otherwise).
     grad_x[:, :C/2] is grad_y[:, :C/2]: what reaches that half through the net is the caller's (autograd's).  tanh and exp(-s) are
     recomputed from `raw`; the per-channel sums run in a fixed order: the same inputs give the same bits."""
-    _coupling_args(y, raw, a, b, "output")
-    _require_device(grad_y, "grad_output")
-    if grad_y.shape != y.shape or grad_y.device != y.device:
-        raise ValueError("grad_output must match the reverse's output in shape and device")
-    B, C, H, W = y.shape
-    gx = torch.empty_like(y) if need_gx else None
-    graw = torch.empty_like(raw) if need_graw else None
-    ga = torch.empty(C, dtype=torch.float32, device=y.device) if need_ga else None
-    gb = torch.empty(C, dtype=torch.float32, device=y.device) if need_gb else None
-    if _nothing_to_launch(y, (gx, graw, ga, gb), (ga, gb)):
-        return gx, graw, ga, gb
-    nbytes = _lib.lib().finc_coupling_workspace_bytes(B, C, H * W) if (need_ga or need_gb) else None
-    _call("finc_coupling_reverse_backward_f32", y.device, grad_y.data_ptr(), y.data_ptr(), raw.data_ptr(), a.data_ptr(), b.data_ptr(),
-          _ptr(gx), _ptr(graw), _ptr(ga), _ptr(gb), B, C, H * W, *_ws_args(y.device, nbytes), _stream_ptr(y))
-    return gx, graw, ga, gb
+    return _coupling_grads("finc_coupling_reverse_backward_f32", grad_y, (), y, raw, a, b, "output", "the reverse's output",
+                           (need_gx, need_graw), (need_ga, need_gb))
 
 
 def finc_coupling_reverse_logdet(x, raw, a, b, out=None):
@@ -473,37 +471,15 @@ def finc_coupling_reverse_logdet(x, raw, a, b, out=None):
     finc_coupling_reverse_logdet_f32; the reverse map's own log-Jacobian is its negative).  Returns (y, logdet); `out` may be `x`.
     One more small launch for the fixed-order sums: the same inputs give the same bits."""
     _coupling_args(x, raw, a, b)
-    out = _out_like(x, out)
-    B, C, H, W = x.shape
-    if x.numel() == 0:
-        return out, torch.zeros(B, dtype=torch.float32, device=x.device)
-    logdet = torch.empty(B, dtype=torch.float32, device=x.device)
-    nbytes = _lib.lib().finc_coupling_workspace_bytes(B, C, H * W)
-    _call("finc_coupling_reverse_logdet_f32", x.device, x.data_ptr(), raw.data_ptr(), a.data_ptr(), b.data_ptr(), out.data_ptr(),
-          logdet.data_ptr(), B, C, H * W, *_ws_args(x.device, nbytes), _stream_ptr(x))
-    return out, logdet
+    return _coupling_transform("finc_coupling_reverse_logdet_f32", x, raw, a, b, (), True, out)
 
 
 def finc_coupling_reverse_logdet_backward(grad_y, grad_logdet, y, raw, a, b, need_gx=True, need_graw=True, need_ga=True, need_gb=True):
     """Gradients of `finc_coupling_reverse_logdet` (include/finc.h: finc_coupling_reverse_logdet_backward_f32), given grad_y
     [B,C,H,W], grad_logdet [B] or None (zeros) and the reverse's OUTPUT `y`: (grad_x, grad_raw, grad_a, grad_b), each computed only
     if asked for (None otherwise).  With grad_logdet None every result has the bits of `finc_coupling_reverse_backward`."""
-    _coupling_args(y, raw, a, b, "output")
-    _require_device(grad_y, "grad_output")
-    if grad_y.shape != y.shape or grad_y.device != y.device:
-        raise ValueError("grad_output must match the reverse's output in shape and device")
-    B, C, H, W = y.shape
-    _per_image(grad_logdet, "grad_logdet", y)
-    gx = torch.empty_like(y) if need_gx else None
-    graw = torch.empty_like(raw) if need_graw else None
-    ga = torch.empty(C, dtype=torch.float32, device=y.device) if need_ga else None
-    gb = torch.empty(C, dtype=torch.float32, device=y.device) if need_gb else None
-    if _nothing_to_launch(y, (gx, graw, ga, gb), (ga, gb)):
-        return gx, graw, ga, gb
-    nbytes = _lib.lib().finc_coupling_workspace_bytes(B, C, H * W) if (need_ga or need_gb) else None
-    _call("finc_coupling_reverse_logdet_backward_f32", y.device, grad_y.data_ptr(), _ptr(grad_logdet), y.data_ptr(), raw.data_ptr(),
-          a.data_ptr(), b.data_ptr(), _ptr(gx), _ptr(graw), _ptr(ga), _ptr(gb), B, C, H * W, *_ws_args(y.device, nbytes), _stream_ptr(y))
-    return gx, graw, ga, gb
+    return _coupling_grads("finc_coupling_reverse_logdet_backward_f32", grad_y, (grad_logdet,), y, raw, a, b, "output",
+                           "the reverse's output", (need_gx, need_graw), (need_ga, need_gb))
 
 
 def finc_coupling_backward_reconstruct(grad_y, grad_logdet, y, raw, a, b, need_x=True, need_gx=True, need_graw=True, need_ga=True,
@@ -512,24 +488,8 @@ def finc_coupling_backward_reconstruct(grad_y, grad_logdet, y, raw, a, b, need_x
     in the same launch (include/finc.h: finc_coupling_backward_reconstruct_f32): (x, grad_x, grad_raw, grad_a, grad_b), each computed
     only if asked for (None otherwise).  `x` has the bits of `finc_coupling(y, raw, a, b, -1)`; grad_x[:, :C/2] is grad_y[:, :C/2] (the
     net's share is the caller's).  grad_logdet [B] or None (zeros).  Fixed-order sums: the same inputs give the same bits."""
-    _coupling_args(y, raw, a, b, "output")
-    _require_device(grad_y, "grad_output")
-    if grad_y.shape != y.shape or grad_y.device != y.device:
-        raise ValueError("grad_output must match the forward's output in shape and device")
-    B, C, H, W = y.shape
-    _per_image(grad_logdet, "grad_logdet", y)
-    x = torch.empty_like(y) if need_x else None
-    gx = torch.empty_like(y) if need_gx else None
-    graw = torch.empty_like(raw) if need_graw else None
-    ga = torch.empty(C, dtype=torch.float32, device=y.device) if need_ga else None
-    gb = torch.empty(C, dtype=torch.float32, device=y.device) if need_gb else None
-    if _nothing_to_launch(y, (x, gx, graw, ga, gb), (ga, gb)):
-        return x, gx, graw, ga, gb
-    nbytes = _lib.lib().finc_coupling_workspace_bytes(B, C, H * W) if (need_ga or need_gb) else None
-    _call("finc_coupling_backward_reconstruct_f32", y.device, grad_y.data_ptr(), _ptr(grad_logdet), y.data_ptr(), raw.data_ptr(),
-          a.data_ptr(), b.data_ptr(), _ptr(x), _ptr(gx), _ptr(graw), _ptr(ga), _ptr(gb), B, C, H * W, *_ws_args(y.device, nbytes),
-          _stream_ptr(y))
-    return x, gx, graw, ga, gb
+    return _coupling_grads("finc_coupling_backward_reconstruct_f32", grad_y, (grad_logdet,), y, raw, a, b, "output",
+                           "the forward's output", (need_x, need_gx, need_graw), (need_ga, need_gb))
 
 
 def _incoming_grads(like, grad_y, grad_logdet):
@@ -666,25 +626,33 @@ def finc_actnorm(x, log_scale, translation, direction=1, want_logdet=False, out=
     return out, logdet
 
 
+def _actnorm_grads(entry, grad_y, grad_logdet, v, log_scale, translation, what, whose, need_acts, need_sums):
+    """One backward entry point of ActNorm behind its wrapper: the checks, the outputs asked for -- `need_acts`: (x,) grad_x;
+    `need_sums`: grad_log_scale, grad_translation -- the workspace and the call.  `v`: the activation that entry point reads,
+    "input" or "output" (`what`) of `whose` pass; grad_logdet, translation: tuples, empty for an entry point that takes none."""
+    _actnorm_args(v, log_scale, translation[0] if translation else None, what)
+    _require_device(grad_y, "grad_output")
+    if grad_y.shape != v.shape or grad_y.device != v.device:
+        raise ValueError(f"grad_output must match {whose} in shape and device")
+    B, C, H, W = v.shape
+    for g in grad_logdet:
+        _per_image(g, "grad_logdet", v)
+    sums = tuple(torch.empty(C, dtype=torch.float32, device=v.device) if n else None for n in need_sums)
+    outs = tuple(torch.empty_like(v) if n else None for n in need_acts) + sums
+    if _nothing_to_launch(v, outs, sums):
+        return outs
+    nbytes = _lib.lib().finc_actnorm_workspace_bytes(B, C, H * W) if any(need_sums) else None
+    _call(entry, v.device, grad_y.data_ptr(), *map(_ptr, grad_logdet), v.data_ptr(), log_scale.data_ptr(),
+          *(t.data_ptr() for t in translation), *map(_ptr, outs), B, C, H * W, *_ws_args(v.device, nbytes), _stream_ptr(v))
+    return outs
+
+
 def finc_actnorm_backward(grad_y, grad_logdet, y, log_scale, need_gx=True, need_gls=True, need_gt=True):
     """Gradients of `finc_actnorm(..., direction=1, want_logdet=True)` (include/finc.h: finc_actnorm_backward_f32), given grad_y
     [B,C,H,W], grad_logdet [B] or None (zeros), the forward's OUTPUT `y` and log_scale: (grad_x, grad_log_scale, grad_translation),
     each computed only if asked for (None otherwise).  The per-channel sums run in a fixed order: the same inputs give the same bits."""
-    _actnorm_args(y, log_scale, None, "output")
-    _require_device(grad_y, "grad_output")
-    if grad_y.shape != y.shape or grad_y.device != y.device:
-        raise ValueError("grad_output must match the forward's output in shape and device")
-    B, C, H, W = y.shape
-    _per_image(grad_logdet, "grad_logdet", y)
-    gx = torch.empty_like(y) if need_gx else None
-    gls = torch.empty(C, dtype=torch.float32, device=y.device) if need_gls else None
-    gt = torch.empty(C, dtype=torch.float32, device=y.device) if need_gt else None
-    if _nothing_to_launch(y, (gx, gls, gt), (gls, gt)):
-        return gx, gls, gt
-    nbytes = _lib.lib().finc_actnorm_workspace_bytes(B, C, H * W) if (need_gls or need_gt) else None
-    _call("finc_actnorm_backward_f32", y.device, grad_y.data_ptr(), _ptr(grad_logdet), y.data_ptr(), log_scale.data_ptr(), _ptr(gx),
-          _ptr(gls), _ptr(gt), B, C, H * W, *_ws_args(y.device, nbytes), _stream_ptr(y))
-    return gx, gls, gt
+    return _actnorm_grads("finc_actnorm_backward_f32", grad_y, (grad_logdet,), y, log_scale, (), "output", "the forward's output",
+                          (need_gx,), (need_gls, need_gt))
 
 
 def finc_actnorm_backward_reconstruct(grad_y, grad_logdet, y, log_scale, translation, need_x=True, need_gx=True, need_gls=True,
@@ -693,42 +661,16 @@ def finc_actnorm_backward_reconstruct(grad_y, grad_logdet, y, log_scale, transla
     finc_actnorm_backward_reconstruct_f32): (x, grad_x, grad_log_scale, grad_translation), each computed only if asked for (None
     otherwise).  `x` has the bits of `finc_actnorm(y, log_scale, translation, -1)`.  One launch (plus the small fixed-order reduce
     with a per-channel gradient): the same inputs give the same bits."""
-    _actnorm_args(y, log_scale, translation, "output")
-    _require_device(grad_y, "grad_output")
-    if grad_y.shape != y.shape or grad_y.device != y.device:
-        raise ValueError("grad_output must match the forward's output in shape and device")
-    B, C, H, W = y.shape
-    _per_image(grad_logdet, "grad_logdet", y)
-    x = torch.empty_like(y) if need_x else None
-    gx = torch.empty_like(y) if need_gx else None
-    gls = torch.empty(C, dtype=torch.float32, device=y.device) if need_gls else None
-    gt = torch.empty(C, dtype=torch.float32, device=y.device) if need_gt else None
-    if _nothing_to_launch(y, (x, gx, gls, gt), (gls, gt)):
-        return x, gx, gls, gt
-    nbytes = _lib.lib().finc_actnorm_workspace_bytes(B, C, H * W) if (need_gls or need_gt) else None
-    _call("finc_actnorm_backward_reconstruct_f32", y.device, grad_y.data_ptr(), _ptr(grad_logdet), y.data_ptr(), log_scale.data_ptr(),
-          translation.data_ptr(), _ptr(x), _ptr(gx), _ptr(gls), _ptr(gt), B, C, H * W, *_ws_args(y.device, nbytes), _stream_ptr(y))
-    return x, gx, gls, gt
+    return _actnorm_grads("finc_actnorm_backward_reconstruct_f32", grad_y, (grad_logdet,), y, log_scale, (translation,), "output",
+                          "the forward's output", (need_x, need_gx), (need_gls, need_gt))
 
 
 def finc_actnorm_reverse_backward(grad_y, x, log_scale, need_gx=True, need_gls=True, need_gt=True):
     """Gradients of `finc_actnorm(..., direction=-1)` (include/finc.h: finc_actnorm_reverse_backward_f32), given grad_y [B,C,H,W],
     the reverse's INPUT `x` and log_scale: (grad_x, grad_log_scale, grad_translation), each computed only if asked for (None
     otherwise).  The per-channel sums run in a fixed order: the same inputs give the same bits."""
-    _actnorm_args(x, log_scale, None)
-    _require_device(grad_y, "grad_output")
-    if grad_y.shape != x.shape or grad_y.device != x.device:
-        raise ValueError("grad_output must match the reverse's input in shape and device")
-    B, C, H, W = x.shape
-    gx = torch.empty_like(x) if need_gx else None
-    gls = torch.empty(C, dtype=torch.float32, device=x.device) if need_gls else None
-    gt = torch.empty(C, dtype=torch.float32, device=x.device) if need_gt else None
-    if _nothing_to_launch(x, (gx, gls, gt), (gls, gt)):
-        return gx, gls, gt
-    nbytes = _lib.lib().finc_actnorm_workspace_bytes(B, C, H * W) if (need_gls or need_gt) else None
-    _call("finc_actnorm_reverse_backward_f32", x.device, grad_y.data_ptr(), x.data_ptr(), log_scale.data_ptr(), _ptr(gx), _ptr(gls),
-          _ptr(gt), B, C, H * W, *_ws_args(x.device, nbytes), _stream_ptr(x))
-    return gx, gls, gt
+    return _actnorm_grads("finc_actnorm_reverse_backward_f32", grad_y, (), x, log_scale, (), "input", "the reverse's input",
+                          (need_gx,), (need_gls, need_gt))
 
 
 def finc_actnorm_init(x, log_scale, translation):

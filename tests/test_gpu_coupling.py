@@ -113,6 +113,24 @@ def test_transform_in_place(dev):
         assert got is buf and torch.equal(got, want)
 
 
+def test_reverse_ignores_a_logdet_pointer_and_needs_no_workspace(dev):
+    """include/finc.h: finc_coupling_f32 ignores `logdet` in direction -1 (finc_coupling_reverse_logdet_f32 is the entry point that
+    sums there).  A log-det buffer handed in all the same keeps its bits, and the call succeeds without a workspace."""
+    from fincflow_amd import ops
+    shape = (2, 4, 4, 4)
+    x, raw, a, b, _, _ = case(shape)
+    xd, rawd, ad, bd = x.to(dev), raw.to(dev), a.to(dev), b.to(dev)
+    want, _ = ops.finc_coupling(xd, rawd, ad, bd, -1, False)
+    y, logdet = torch.zeros_like(xd), torch.full((shape[0],), -12345.5, device=dev)
+    status = ops._lib.lib().finc_coupling_f32(xd.data_ptr(), rawd.data_ptr(), ad.data_ptr(), bd.data_ptr(), y.data_ptr(), logdet.data_ptr(),
+                                              shape[0], shape[1], shape[2] * shape[3], -1, None, 0,
+                                              torch.cuda.current_stream(dev).cuda_stream)
+    torch.cuda.synchronize()
+    assert status == 0                                               # FINC_OK
+    assert torch.equal(logdet.cpu(), torch.full((shape[0],), -12345.5))
+    assert torch.equal(y, want)
+
+
 @pytest.mark.parametrize("with_logdet", [True, False])
 @pytest.mark.parametrize("shape", SHAPES)
 def test_all_four_gradients_against_float64_autograd(shape, with_logdet, dev):
