@@ -40,6 +40,7 @@ SYMBOLS = [
     "finc_coupling_reverse_backward_f32", "finc_actnorm_reverse_backward_f32",
     "finc_coupling_reverse_logdet_f32", "finc_coupling_reverse_logdet_backward_f32",
     "finc_actnorm_backward_reconstruct_f32", "finc_coupling_backward_reconstruct_f32",
+    "finc_backward_f64_workspace_bytes", "finc_backward_f64", "finc_check_invariant_f64",
 ]
 
 #: the ABI version this binding is written against (include/finc.h: finc_version)
@@ -59,6 +60,9 @@ SAMPLE_LOGDET_ABI_VERSION = 109
 #: the version that added the forward-direction backwards that rebuild the layer's input from its output
 #: (finc_actnorm_backward_reconstruct_f32, finc_coupling_backward_reconstruct_f32): what FlowSequential.invertible_backward launches
 INVERTIBLE_BACKWARD_ABI_VERSION = 110
+#: the version that added the double-precision backward of the forward conv and the invariant check on doubles (finc_backward_f64,
+#: finc_check_invariant_f64): what a float64 unit on the device trains and validates with
+F64_BACKWARD_ABI_VERSION = 111
 
 _lib = None
 
@@ -109,6 +113,10 @@ def lib():
                         f"(finc_actnorm_backward_reconstruct_f32, finc_coupling_backward_reconstruct_f32) came with "
                         f"{INVERTIBLE_BACKWARD_ABI_VERSION}: rebuild it "
                         "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
+    if have < F64_BACKWARD_ABI_VERSION:
+        raise FincError(f"{LIB_PATH} reports finc_version() = {have}, the double-precision backward (finc_backward_f64, "
+                        f"finc_check_invariant_f64) came with {F64_BACKWARD_ABI_VERSION}: rebuild it "
+                        "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
     L.finc_build_flags.restype = u
     L.finc_clear_fault.restype = i
     L.finc_status_string.restype = ctypes.c_char_p
@@ -150,6 +158,10 @@ def lib():
     L.finc_f64_workspace_bytes.argtypes = [i, i, i, i]
     L.finc_inverse_f64_algo.argtypes = run
     L.finc_forward_f64_algo.argtypes = run
+    L.finc_backward_f64_workspace_bytes.restype = sz
+    L.finc_backward_f64_workspace_bytes.argtypes = [i, i, i, i, i, i, i]
+    L.finc_backward_f64.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, u, vp, sz, vp]
+    L.finc_check_invariant_f64.argtypes = [vp, i, i, i, i, vp]
     L.finc_inverse_kernel_variant.argtypes = [i, i, i, i, i, i, i, ctypes.POINTER(ctypes.c_int)]
     L.finc_debug_attr_table_insert.argtypes = [i, sz]
     L.finc_debug_inverse_table_row.argtypes = [i, ctypes.POINTER(ctypes.c_int)]

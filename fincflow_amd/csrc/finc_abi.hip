@@ -52,15 +52,16 @@ __global__ void canonicalize_kernel(const T *__restrict__ ws, T *__restrict__ wc
 }
 
 // flag[0] = 0 if the corner tap is unit lower triangular in every group, else 1 + first bad index
-__global__ void invariant_kernel(const float *__restrict__ wc, int G, int Cq, int KH, int KW, int *flag)
+template <typename T>
+__global__ void invariant_kernel(const T *__restrict__ wc, int G, int Cq, int KH, int KW, int *flag)
 {
     const int total = G * Cq * Cq;
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
         const int kc = idx % Cq;
         const int c = (idx / Cq) % Cq;
         if (kc < c) continue;
-        const float v = wc[((size_t)idx * KH + (KH - 1)) * KW + (KW - 1)];
-        const bool ok = (kc == c) ? (v == 1.0f) : (v == 0.0f);
+        const T v = wc[((size_t)idx * KH + (KH - 1)) * KW + (KW - 1)];
+        const bool ok = (kc == c) ? (v == T(1)) : (v == T(0));
         if (!ok) atomicMax(flag, 1 + idx);
     }
 }
@@ -189,7 +190,7 @@ static int canonicalize(const T *w_stored, T *w_canon, int G, int Cq, int KH, in
 
 extern "C" {
 
-int finc_version(void) { return 110; }
+int finc_version(void) { return 111; }
 
 unsigned finc_build_flags(void)
 {
@@ -263,7 +264,8 @@ int finc_canonicalize_weights_f64(const double *w_stored, double *w_canon, int G
     return canonicalize<double>(w_stored, w_canon, G, Cq, KH, KW, orient, stream);
 }
 
-int finc_check_invariant_f32(const float *w_canon, int G, int Cq, int KH, int KW, finc_stream_t stream)
+extern "C++" template <typename T>
+static int check_invariant(const T *w_canon, int G, int Cq, int KH, int KW, finc_stream_t stream)
 {
     if (!w_canon) return FINC_ERR_NULL_POINTER;
     if (int e = check_shape(1, G, Cq, 1, 1, KH, KW)) return e;
@@ -280,11 +282,21 @@ int finc_check_invariant_f32(const float *w_canon, int G, int Cq, int KH, int KW
     int h_flag = 0;
     FINC_HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(int), st));
     const int blocks = (G * Cq * Cq + 255) / 256;
-    hipLaunchKernelGGL(invariant_kernel, dim3(blocks), dim3(256), 0, st, w_canon, G, Cq, KH, KW, d_flag);
+    hipLaunchKernelGGL(invariant_kernel<T>, dim3(blocks), dim3(256), 0, st, w_canon, G, Cq, KH, KW, d_flag);
     FINC_CHECK_LAUNCH();
     FINC_HIP_TRY(hipMemcpyAsync(&h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
     FINC_HIP_TRY(hipStreamSynchronize(st));
     return h_flag == 0 ? FINC_OK : FINC_ERR_INVARIANT;
+}
+
+int finc_check_invariant_f32(const float *w_canon, int G, int Cq, int KH, int KW, finc_stream_t stream)
+{
+    return check_invariant<float>(w_canon, G, Cq, KH, KW, stream);
+}
+
+int finc_check_invariant_f64(const double *w_canon, int G, int Cq, int KH, int KW, finc_stream_t stream)
+{
+    return check_invariant<double>(w_canon, G, Cq, KH, KW, stream);
 }
 
 int finc_debug_attr_table_insert(int device, size_t kernel_token)
@@ -873,6 +885,49 @@ int finc_backward_f32(const float *grad_z, const float *x, const float *w_canon,
     }
     if (!grad_x && !grad_w_canon) return FINC_OK;
     return finc_launch_backward_generic(grad_z, x, w_canon, grad_x, grad_w_canon, s, st);
+}
+
+// the fp64 backward's workspace: the transposed bank of the grad-input (finc_f64_packed_bytes), then the grad-weight partials from the
+// next 256-byte boundary.  The bound is a function of the bank, B and H alone, so it never shrinks when B, H or W grows.
+size_t finc_backward_f64_workspace_bytes(int B, int G, int Cq, int H, int W, int KH, int KW)
+{
+    if (B <= 0 || G <= 0 || Cq <= 0 || H <= 0 || W <= 0 || KH <= 0 || KW <= 0) return 256;
+    const size_t n = align256(finc_f64_packed_bytes(G, Cq, KH, KW)) + finc_f64_gradw_workspace_bound(B, G, Cq, H, KH, KW);
+    return n < 256 ? 256 : n;
+}
+
+int finc_backward_f64(const double *grad_z, const double *x, const double *w_canon, double *grad_x, double *grad_w_canon, int B, int G,
+                      int Cq, int H, int W, int KH, int KW, unsigned orient, void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    if (!grad_z || (!grad_x && !grad_w_canon)) return FINC_ERR_NULL_POINTER;
+    if (grad_x && !w_canon) return FINC_ERR_NULL_POINTER;
+    if (grad_w_canon && !x) return FINC_ERR_NULL_POINTER;
+    if (int e = check_shape(B, G, Cq, H, W, KH, KW)) return e;
+    if (off_boundary(7u, grad_z, x, w_canon, grad_x, grad_w_canon)) return FINC_ERR_ALIGNMENT;
+    if (grad_x == grad_z) return FINC_ERR_BAD_DIMS;
+    if (int e = finc_fault_gate(false)) return e;
+    FincShape s{B, G, Cq, H, W, KH, KW, orient};
+    hipStream_t st = (hipStream_t)stream;
+    // (a workspace off an 8-byte boundary counts as none, as in the finc_*_f64_algo calls)
+    const bool mfma = workspace && ((uintptr_t)workspace & 7u) == 0 && finc_f64_supported(s);
+    const size_t bank = align256(finc_f64_packed_bytes(G, Cq, KH, KW));
+    // grad_x: the forward kernel on the transposed bank, every group's orientation complemented (grid.y carries the slabs)
+    if (grad_x && mfma && workspace_bytes >= bank && (long long)B * G <= 65535) {
+        FincShape sb = s;
+        sb.orient = orient ^ ((G >= 16) ? 0xFFFFFFFFu : ((1u << (2 * G)) - 1u));
+        if (int e = finc_f64_launch(grad_z, w_canon, grad_x, workspace, sb, true, st, true)) return e;
+        grad_x = nullptr;
+    }
+    // grad_w: the pixels on the MFMA K dimension, partial tiles behind the bank, a fixed-order reduce with the corner-tap mask
+    if (grad_w_canon && mfma) {
+        const FincF64GradwPlan p = finc_f64_gradw_plan(s);
+        if (p.nrc && workspace_bytes >= bank + p.bytes) {
+            if (int e = finc_f64_gradw_launch(grad_z, x, grad_w_canon, (char *)workspace + bank, s, st)) return e;
+            grad_w_canon = nullptr;
+        }
+    }
+    if (!grad_x && !grad_w_canon) return FINC_OK;
+    return finc_launch_backward_generic_f64(grad_z, x, w_canon, grad_x, grad_w_canon, s, st);
 }
 
 // ---- backward through the inverse (finc_adjoint.h) ----

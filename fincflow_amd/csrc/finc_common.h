@@ -95,6 +95,8 @@ int finc_launch_inverse_strict_f64(const double *z, const double *wc, double *x,
 int finc_launch_forward_generic_f64(const double *x, const double *wc, double *z, const FincShape &s, hipStream_t st);
 int finc_launch_backward_generic(const float *gz, const float *x, const float *wc, float *gx, float *gw,
                                  const FincShape &s, hipStream_t st);
+int finc_launch_backward_generic_f64(const double *gz, const double *x, const double *wc, double *gx, double *gw,
+                                     const FincShape &s, hipStream_t st);
 bool finc_backward_generic_has_gradw(int KH, int KW);   // false: finc_launch_backward_generic answers a grad-weight with FINC_ERR_UNSUPPORTED
 
 // ---- inverse, MFMA wavefront kernel: finc_mfma.hip ----
@@ -258,7 +260,21 @@ size_t finc_gradw_workspace_bound(int G, int Cq, int KH, int KW, long long units
 bool finc_f64_supported(const FincShape &s);
 size_t finc_f64_packed_bytes(int G, int Cq, int KH, int KW);          // 0: no such kernel for this bank
 // packs the bank into `packed` (finc_f64_packed_bytes) and runs the inverse or the forward on it, all on `st`
-int finc_f64_launch(const double *in, const double *wc, double *out, void *packed, const FincShape &s, bool forward, hipStream_t st);
+// `transpose` (forward only): the bank with in/out channels exchanged -- with every group's orientation complemented, the grad-input
+int finc_f64_launch(const double *in, const double *wc, double *out, void *packed, const FincShape &s, bool forward, hipStream_t st,
+                    bool transpose = false);
+// weight gradient: pixels on the MFMA K dimension, one wave per (slab, row chunk), partial tiles in `workspace`, then a fixed-order
+// reduce with the corner-tap mask.  The grid is not capped: a wave takes exactly one unit.
+struct FincF64GradwPlan {
+    int nrc = 0, RC = 0;      // row chunks per slab (0: no kernel for this bank) of RC rows, the last one ragged
+    long long waves = 0;      // B * G * nrc one-wave workgroups
+    long long parts = 0;      // B * nrc partial tiles per (group, o, i, tap), summed in index order
+    size_t bytes = 0;         // of the partials
+};
+FincF64GradwPlan finc_f64_gradw_plan(const FincShape &s);
+// >= finc_f64_gradw_plan(s).bytes for every shape on this bank; never shrinks when B or H grows (0: no kernel for this bank)
+size_t finc_f64_gradw_workspace_bound(int B, int G, int Cq, int H, int KH, int KW);
+int finc_f64_gradw_launch(const double *gz, const double *x, double *gw, void *workspace, const FincShape &s, hipStream_t st);
 unsigned finc_build_flags_f64();
 
 // ---- per-pixel channel mixing (1x1 conv + folded affine): finc_mix.hip ----

@@ -45,7 +45,8 @@ struct DCfg {
 
 // -----------------------------------------------------------------------------------------------
 // Fragment packing in fp64 (one workgroup per group): fragment (tap, j, mt), lane (q, i) = M_tap[16 mt + i][4 j + q], M_z = Linv,
-// M_(a,b) = -(Linv * Wc[:, :, KH-1-a, KW-1-b]); forward: M_(a,b) = Wc[:, :, KH-1-a, KW-1-b] for all nine taps, (0,0) in the z slot.
+// M_(a,b) = -(Linv * Wc[:, :, KH-1-a, KW-1-b]); forward (1): M_(a,b) = Wc[:, :, KH-1-a, KW-1-b] for all nine taps, (0,0) in the z slot;
+// forward transposed (2): M_(a,b)[row][col] = Wc[col][row][KH-1-a][KW-1-b], the grad-input's bank.
 // -----------------------------------------------------------------------------------------------
 __global__ void pack_f64_kernel(const double *__restrict__ wc, double *__restrict__ packed, int Cq, int KH, int KW, int MT, int NK, int forward)
 {
@@ -72,7 +73,8 @@ __global__ void pack_f64_kernel(const double *__restrict__ wc, double *__restric
         const int widx = (KH - 1 - a) * KW + (KW - 1 - b);
         double v = 0.0;
         if (row < Cq && col < Cq) {
-            if (forward) v = wg[((size_t)row * Cq + col) * KK + widx];
+            if (forward == 2) v = wg[((size_t)col * Cq + row) * KK + widx];
+            else if (forward) v = wg[((size_t)row * Cq + col) * KK + widx];
             else if (tap == 0) v = Linv[row * Cq + col];
             else {
                 double s = 0.0;
@@ -302,18 +304,137 @@ __global__ __launch_bounds__(64) void finc_f64_forward_kernel(const double *__re
     }
 }
 
+// -----------------------------------------------------------------------------------------------
+// weight gradient: grad_w[o][i][tap (a, b)] = sum over the pixels of gz[o, h, w] * x[i, h - a, w - b] (canonical coordinates), the
+// pixels on the MFMA K dimension.  One wave per (slab, row chunk) walks its rows in groups of four pixels along W; lane (q, m) loads
+// pixel 4 s + q of channel 16 t + m: for gz that is the A operand of output tile t (row m, k-slot q), for x shifted by the tap the B
+// operand of input tile t (k-slot q, column m).  KH * KW * MT * MT accumulators of four doubles (Cq = 24: 36, 288 registers; one wave
+// per SIMD): register r of tile (to, ti) at lane (q, n) is grad_w[16 to + 4 r + q][16 ti + n].  Orientation, padded channels, the
+// image edge and the K remainder (a group that reaches beyond W) are out-of-range buffer offsets, which load zero -- in BOTH
+// operands of such a pixel, so that nothing non-finite next to it is multiplied.  The operands of the next group are requested
+// before the MFMAs of this one.  Each wave writes its tiles to partials[b * nrc + chunk][g][tap][to][ti][r][lane] with plain stores;
+// the reduce adds them in index order and writes the masked bank: the same bits run after run.
+// -----------------------------------------------------------------------------------------------
+template <int CQP, int KH, int KW>
+__global__ __launch_bounds__(64) void finc_f64_gradw_kernel(const double *__restrict__ gz, const double *__restrict__ x,
+                                                            double *__restrict__ partials, int G, int CQ, int H, int W, unsigned orient,
+                                                            int nrc, int RC)
+{
+    using C = DCfg<CQP, KH, KW>;
+    constexpr int MT = C::MT, NTAP = C::NTAP;
+    const int lane = threadIdx.x, q = lane >> 4, m = lane & 15;
+    const int unit = (int)blockIdx.x, chunk = unit % nrc, bg = unit / nrc, g = bg % G;
+    const unsigned o = finc_group_orient(orient, g);
+    const bool fh = (o & FINC_FLIP_H) != 0, fw = (o & FINC_FLIP_W) != 0;
+    const int HW = H * W;
+    const unsigned slab_bytes = (unsigned)CQ * (unsigned)HW * 8u;
+    const __amdgpu_buffer_rsrc_t rgz = __builtin_amdgcn_make_buffer_rsrc((void *)(gz + (size_t)bg * CQ * HW), 0, (int)slab_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void *)(x + (size_t)bg * CQ * HW), 0, (int)slab_bytes, 0x00020000);
+    unsigned chan_off[MT];
+#pragma unroll
+    for (int t = 0; t < MT; ++t) chan_off[t] = (16 * t + m) < CQ ? (unsigned)((16 * t + m) * HW * 8) : OFF_BAD_CHANNEL;
+    auto pix_off = [&](int r, int cc) { return (unsigned)(((fh ? H - 1 - r : r) * W + (fw ? W - 1 - cc : cc)) * 8); };
+    auto load = [&](const __amdgpu_buffer_rsrc_t &rs, unsigned off) {
+        return __builtin_bit_cast(double, __builtin_bit_cast(v2u, __builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, 0)));
+    };
+    v4d acc[NTAP][MT][MT];
+#pragma unroll
+    for (int tp = 0; tp < NTAP; ++tp)
+#pragma unroll
+        for (int to = 0; to < MT; ++to)
+#pragma unroll
+            for (int ti = 0; ti < MT; ++ti) acc[tp][to][ti] = (v4d){0.0, 0.0, 0.0, 0.0};
+    const int r0 = chunk * RC, r1 = r0 + RC < H ? r0 + RC : H;
+    double zn[MT], xn[NTAP][MT];                  // the operands of the next group
+    auto request = [&](int h, int c0) {
+        const int col = c0 + q;
+        const bool okz = h < r1 && col < W;
+        const unsigned zb = okz ? pix_off(h, col) : OFF_INVALID;
+#pragma unroll
+        for (int t = 0; t < MT; ++t) zn[t] = load(rgz, zb + chan_off[t]);
+#pragma unroll
+        for (int a = 0; a < KH; ++a)
+#pragma unroll
+            for (int b = 0; b < KW; ++b) {
+                const bool ok = okz && h - a >= 0 && col - b >= 0;
+                const unsigned xb = ok ? pix_off(h - a, col - b) : OFF_INVALID;
+#pragma unroll
+                for (int t = 0; t < MT; ++t) xn[a * KW + b][t] = load(rx, xb + chan_off[t]);
+            }
+    };
+    int h = r0, c0 = 0;
+    request(h, c0);
+    const int steps = (r1 - r0) * ((W + 3) >> 2);
+    for (int s = 0; s < steps; ++s) {
+        double zc[MT], xc[NTAP][MT];
+#pragma unroll
+        for (int t = 0; t < MT; ++t) zc[t] = zn[t];
+#pragma unroll
+        for (int tp = 0; tp < NTAP; ++tp)
+#pragma unroll
+            for (int t = 0; t < MT; ++t) xc[tp][t] = xn[tp][t];
+        c0 += 4;
+        if (c0 >= W) { c0 = 0; ++h; }
+        request(h, c0);                           // (behind the last group: row r1, every offset out of range)
+#pragma unroll
+        for (int tp = 0; tp < NTAP; ++tp)
+#pragma unroll
+            for (int to = 0; to < MT; ++to)
+#pragma unroll
+                for (int ti = 0; ti < MT; ++ti)
+                    acc[tp][to][ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(zc[to], xc[tp][ti], acc[tp][to][ti], 0, 0, 0);
+    }
+    constexpr int PER = NTAP * MT * MT * 256;     // doubles of one wave's tiles
+    double *out = partials + (((size_t)(bg / G) * nrc + chunk) * G + g) * PER + lane;
+#pragma unroll
+    for (int tp = 0; tp < NTAP; ++tp)
+#pragma unroll
+        for (int to = 0; to < MT; ++to)
+#pragma unroll
+            for (int ti = 0; ti < MT; ++ti) {
+                const v4d &am = acc[tp][to][ti];
+                double *t = out + ((tp * MT + to) * MT + ti) * 256;
+                t[0] = am.x; t[64] = am.y; t[128] = am.z; t[192] = am.w;
+            }
+}
+
+// One thread per element of the padded tiles [g][tap][to][ti][r][lane]: the `parts` partials of its (g, o, i, tap) in index order, then
+// the corner-tap mask (+0.0 where i >= o) and the store to grad_w_canon[g * Cq + o][i][KH-1-a][KW-1-b].
+__global__ void gradw_f64_reduce_kernel(const double *__restrict__ partials, double *__restrict__ gw, int G, int Cq, int KH, int KW, int MT,
+                                        long long parts)
+{
+    const int KK = KH * KW, per = KK * MT * MT * 256;
+    const int e = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (e >= G * per) return;
+    const int lane = e & 63, r = (e >> 6) & 3, f = e >> 8;
+    const int ti = f % MT, to = (f / MT) % MT, tap = (f / (MT * MT)) % KK, g = f / (MT * MT * KK);
+    const int oc = 16 * to + 4 * r + (lane >> 4), ic = 16 * ti + (lane & 15);
+    if (oc >= Cq || ic >= Cq) return;
+    const double *p = partials + e;                // (e = g * per + the element's place in a tile set)
+    const size_t stride = (size_t)G * per;
+    double s = 0.0;
+#pragma unroll 8
+    for (long long k = 0; k < parts; ++k) s += p[(size_t)k * stride];
+    const int a = tap / KW, b = tap % KW;
+    const int widx = (KH - 1 - a) * KW + (KW - 1 - b);
+    const bool masked = widx == KK - 1 && ic >= oc;
+    gw[((size_t)(g * Cq + oc) * Cq + ic) * KK + widx] = masked ? 0.0 : s;
+}
+
 typedef void (*f64inv_fn)(const double *, const double *, double *, int, int, int, int, int, int, unsigned, int, int, int);
 typedef void (*f64fwd_fn)(const double *, const double *, double *, int, int, int, int, unsigned);
+typedef void (*f64gw_fn)(const double *, const double *, double *, int, int, int, int, unsigned, int, int);
 struct DInst {
     int cqp, kh, kw, nfrag, lds_fixed, fslot;
     f64inv_fn inv;
     f64fwd_fn fwd;
+    f64gw_fn gradw;
 };
 template <int CQP, int KH, int KW>
 constexpr DInst make_dinst()
 {
     return DInst{CQP, KH, KW, DCfg<CQP, KH, KW>::NFRAG, DCfg<CQP, KH, KW>::lds_bytes(0), DCfg<CQP, KH, KW>::FSLOT,
-                 finc_f64_inverse_kernel<CQP, KH, KW>, finc_f64_forward_kernel<CQP, KH, KW>};
+                 finc_f64_inverse_kernel<CQP, KH, KW>, finc_f64_forward_kernel<CQP, KH, KW>, finc_f64_gradw_kernel<CQP, KH, KW>};
 }
 const DInst g_dinsts[] = {
     make_dinst<4, 3, 3>(), make_dinst<8, 3, 3>(), make_dinst<12, 3, 3>(), make_dinst<16, 3, 3>(), make_dinst<20, 3, 3>(), make_dinst<24, 3, 3>(),
@@ -346,13 +467,70 @@ size_t finc_f64_packed_bytes(int G, int Cq, int KH, int KW)
     return i ? (size_t)G * i->nfrag * 64 * sizeof(double) : 0;
 }
 
-int finc_f64_launch(const double *in, const double *wc, double *out, void *packed, const FincShape &s, bool forward, hipStream_t st)
+// Row chunks of the weight gradient: only a launch that leaves SIMDs idle (fewer slabs than the 1,024 one-wave slots of the chip) cuts
+// its slabs, into as many chunks of at least four rows as fill them.  B * nrc <= min(B * max(1, H / 4), max(B, 1024 / G)): the bound.
+constexpr long long GW_SLOTS = 1024;
+constexpr int GW_MIN_ROWS = 4;
+static size_t gradw_tile_doubles(const DInst *i)
+{
+    const int MT = (i->cqp + 15) / 16;
+    return (size_t)i->kh * i->kw * MT * MT * 256;
+}
+
+FincF64GradwPlan finc_f64_gradw_plan(const FincShape &s)
+{
+    FincF64GradwPlan p;
+    const DInst *i = find_dinst(s.Cq, s.KH, s.KW);
+    if (!i || !finc_f64_supported(s)) return p;
+    const long long units = (long long)s.B * s.G;
+    const int maxc = s.H / GW_MIN_ROWS > 0 ? s.H / GW_MIN_ROWS : 1;
+    long long want = GW_SLOTS / units;
+    want = want > maxc ? maxc : want < 1 ? 1 : want;
+    const int RC = (s.H + (int)want - 1) / (int)want, nrc = (s.H + RC - 1) / RC;
+    if (units * nrc > 0x7fffffffLL) return p;                               // (grid.x: the direct kernel takes such a batch)
+    p.nrc = nrc;
+    p.RC = RC;
+    p.waves = units * nrc;
+    p.parts = (long long)s.B * nrc;
+    p.bytes = (size_t)p.parts * s.G * gradw_tile_doubles(i) * sizeof(double);
+    return p;
+}
+
+size_t finc_f64_gradw_workspace_bound(int B, int G, int Cq, int H, int KH, int KW)
+{
+    const DInst *i = find_dinst(Cq, KH, KW);
+    if (!i) return 0;
+    const long long maxc = H / GW_MIN_ROWS > 0 ? H / GW_MIN_ROWS : 1;
+    const long long fill = (GW_SLOTS + G - 1) / G;
+    long long parts = B > fill ? B : fill;
+    if ((long long)B * maxc < parts) parts = (long long)B * maxc;
+    return (size_t)parts * G * gradw_tile_doubles(i) * sizeof(double);
+}
+
+int finc_f64_gradw_launch(const double *gz, const double *x, double *gw, void *workspace, const FincShape &s, hipStream_t st)
+{
+    const DInst *i = find_dinst(s.Cq, s.KH, s.KW);
+    const FincF64GradwPlan p = finc_f64_gradw_plan(s);
+    if (!i || !p.nrc) return FINC_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(i->gradw, dim3((unsigned)p.waves), dim3(64), 0, st, gz, x, (double *)workspace, s.G, s.Cq, s.H, s.W, s.orient, p.nrc,
+                       p.RC);
+    FINC_CHECK_LAUNCH();
+    const int MT = (i->cqp + 15) / 16;
+    const size_t total = (size_t)s.G * gradw_tile_doubles(i);
+    hipLaunchKernelGGL(gradw_f64_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const double *)workspace, gw, s.G, s.Cq,
+                       s.KH, s.KW, MT, p.parts);
+    FINC_CHECK_LAUNCH();
+    return FINC_OK;
+}
+
+int finc_f64_launch(const double *in, const double *wc, double *out, void *packed, const FincShape &s, bool forward, hipStream_t st,
+                    bool transpose)
 {
     const DInst *i = find_dinst(s.Cq, s.KH, s.KW);
     if (!i) return FINC_ERR_UNSUPPORTED;
     const int MT = (i->cqp + 15) / 16, NK = i->cqp / 4;
     hipLaunchKernelGGL(pack_f64_kernel, dim3(s.G), dim3(256), sizeof(double) * s.Cq * s.Cq, st, wc, (double *)packed, s.Cq, s.KH, s.KW, MT, NK,
-                       forward ? 1 : 0);
+                       forward ? (transpose ? 2 : 1) : 0);
     FINC_CHECK_LAUNCH();
     if (forward) {
         hipLaunchKernelGGL(i->fwd, dim3((s.W + 15) / 16, s.B * s.G), dim3(64), 0, st, in, (const double *)packed, out, s.G, s.Cq, s.H, s.W, s.orient);

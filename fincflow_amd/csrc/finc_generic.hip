@@ -109,8 +109,9 @@ __global__ void forward_generic_kernel(const T *__restrict__ x, const T *__restr
 }
 
 // grad_x[b,i,h,w] = sum_{o,a,b} wc[o,i,KH-1-a,KW-1-b] * gz[b,o,h+a,w+b]   (canonical coordinates)
-__global__ void backward_input_kernel(const float *__restrict__ gz, const float *__restrict__ wc,
-                                      float *__restrict__ gx, int B, int G, int Cq, int H, int W, int KH, int KW,
+template <typename T>
+__global__ void backward_input_kernel(const T *__restrict__ gz, const T *__restrict__ wc,
+                                      T *__restrict__ gx, int B, int G, int Cq, int H, int W, int KH, int KW,
                                       unsigned orient)
 {
     const size_t HW = (size_t)H * W;
@@ -125,13 +126,13 @@ __global__ void backward_input_kernel(const float *__restrict__ gz, const float 
         const unsigned o = finc_group_orient(orient, g);
         const int h = (o & FINC_FLIP_H) ? H - 1 - ph : ph;
         const int w = (o & FINC_FLIP_W) ? W - 1 - pw : pw;
-        const float *gg = gz + (ch - ic) * HW;
-        const float *wgp = wc + (size_t)g * Cq * Cq * KH * KW;
-        float acc = 0.f;
+        const T *gg = gz + (ch - ic) * HW;
+        const T *wgp = wc + (size_t)g * Cq * Cq * KH * KW;
+        T acc = 0;
         for (int oc = 0; oc < Cq; ++oc)
             for (int a = 0; a < KH && h + a < H; ++a)
                 for (int b = 0; b < KW && w + b < W; ++b)
-                    acc = fmaf(gg[(size_t)oc * HW + finc_pix(H, W, o, h + a, w + b)],
+                    acc = fma(gg[(size_t)oc * HW + finc_pix(H, W, o, h + a, w + b)],
                                wgp[(((size_t)oc * Cq + ic) * KH + (KH - 1 - a)) * KW + (KW - 1 - b)], acc);
         gx[idx] = acc;
     }
@@ -141,28 +142,29 @@ __global__ void backward_input_kernel(const float *__restrict__ gz, const float 
 // The corner tap of entries with i >= o is masked to 0 (PaddedConv2d.reset_gradients, layers/conv.py:98-99).
 constexpr int BW_BLOCK = 256;
 constexpr int BW_MAX_TAPS = 49;
-__global__ void backward_weight_kernel(const float *__restrict__ gz, const float *__restrict__ x,
-                                       float *__restrict__ gw, int B, int G, int Cq, int H, int W, int KH, int KW,
+template <typename T>
+__global__ void backward_weight_kernel(const T *__restrict__ gz, const T *__restrict__ x,
+                                       T *__restrict__ gw, int B, int G, int Cq, int H, int W, int KH, int KW,
                                        unsigned orient)
 {
-    __shared__ float red[BW_BLOCK];
+    __shared__ T red[BW_BLOCK];
     const int i = blockIdx.x % Cq;
     const int oc = (blockIdx.x / Cq) % Cq;
     const int g = blockIdx.x / (Cq * Cq);
     const unsigned o = finc_group_orient(orient, g);
     const size_t HW = (size_t)H * W;
     const int ntap = KH * KW;
-    float acc[BW_MAX_TAPS];
+    T acc[BW_MAX_TAPS];
 #pragma unroll
-    for (int t = 0; t < BW_MAX_TAPS; ++t) acc[t] = 0.f;
+    for (int t = 0; t < BW_MAX_TAPS; ++t) acc[t] = 0;
     const size_t n = (size_t)B * HW;
     for (size_t e = threadIdx.x; e < n; e += BW_BLOCK) {
         const int b = (int)(e / HW);
         const int r = (int)(e % HW);
         const int h = r / W, w = r % W; // canonical coordinates of the grad_z sample
         const size_t plane = ((size_t)b * G + g) * Cq;
-        const float gv = gz[(plane + oc) * HW + finc_pix(H, W, o, h, w)];
-        const float *xp = x + (plane + i) * HW;
+        const T gv = gz[(plane + oc) * HW + finc_pix(H, W, o, h, w)];
+        const T *xp = x + (plane + i) * HW;
 #pragma unroll 1
         for (int kh = 0; kh < KH; ++kh) {
             const int a = KH - 1 - kh;
@@ -170,7 +172,7 @@ __global__ void backward_weight_kernel(const float *__restrict__ gz, const float
             for (int kw = 0; kw < KW; ++kw) {
                 const int bb = KW - 1 - kw;
                 if (w - bb < 0) continue;
-                acc[kh * KW + kw] = fmaf(gv, xp[finc_pix(H, W, o, h - a, w - bb)], acc[kh * KW + kw]);
+                acc[kh * KW + kw] = fma(gv, xp[finc_pix(H, W, o, h - a, w - bb)], acc[kh * KW + kw]);
             }
         }
     }
@@ -183,7 +185,7 @@ __global__ void backward_weight_kernel(const float *__restrict__ gz, const float
         }
         if (threadIdx.x == 0) {
             const bool masked = (t == ntap - 1) && (i >= oc);
-            gw[(((size_t)(g * Cq + oc) * Cq + i) * ntap) + t] = masked ? 0.f : red[0];
+            gw[(((size_t)(g * Cq + oc) * Cq + i) * ntap) + t] = masked ? T(0) : red[0];
         }
         __syncthreads();
     }
@@ -238,24 +240,35 @@ int finc_launch_forward_generic_f64(const double *x, const double *wc, double *z
 // the direct grad-weight kernel keeps one accumulator per tap: filters beyond BW_MAX_TAPS taps have no grad-weight at all
 bool finc_backward_generic_has_gradw(int KH, int KW) { return KH * KW <= BW_MAX_TAPS; }
 
-int finc_launch_backward_generic(const float *gz, const float *x, const float *wc, float *gx, float *gw,
-                                 const FincShape &s, hipStream_t st)
+template <typename T>
+static int launch_backward_generic(const T *gz, const T *x, const T *wc, T *gx, T *gw, const FincShape &s, hipStream_t st)
 {
     if (gx) {
         size_t total = (size_t)s.B * s.G * s.Cq * s.H * s.W;
         size_t blocks = (total + 255) / 256;
         if (blocks > 256 * 32) blocks = 256 * 32;
-        hipLaunchKernelGGL(backward_input_kernel, dim3((unsigned)blocks), dim3(256), 0, st, gz, wc, gx, s.B, s.G,
+        hipLaunchKernelGGL(backward_input_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, gz, wc, gx, s.B, s.G,
                            s.Cq, s.H, s.W, s.KH, s.KW, s.orient);
         FINC_CHECK_LAUNCH();
     }
     if (gw) {
         if (s.KH * s.KW > BW_MAX_TAPS) return FINC_ERR_UNSUPPORTED;
-        hipLaunchKernelGGL(backward_weight_kernel, dim3(s.G * s.Cq * s.Cq), dim3(BW_BLOCK), 0, st, gz, x, gw, s.B,
+        hipLaunchKernelGGL(backward_weight_kernel<T>, dim3(s.G * s.Cq * s.Cq), dim3(BW_BLOCK), 0, st, gz, x, gw, s.B,
                            s.G, s.Cq, s.H, s.W, s.KH, s.KW, s.orient);
         FINC_CHECK_LAUNCH();
     }
     return FINC_OK;
+}
+
+int finc_launch_backward_generic(const float *gz, const float *x, const float *wc, float *gx, float *gw,
+                                 const FincShape &s, hipStream_t st)
+{
+    return launch_backward_generic<float>(gz, x, wc, gx, gw, s, st);
+}
+int finc_launch_backward_generic_f64(const double *gz, const double *x, const double *wc, double *gx, double *gw,
+                                     const FincShape &s, hipStream_t st)
+{
+    return launch_backward_generic<double>(gz, x, wc, gx, gw, s, st);
 }
 
 // -----------------------------------------------------------------------------------------------

@@ -535,7 +535,7 @@ class GaussianPrior(nn.Module):
         return -self.log_prob(input, context).sum(-1)
 
     def sample(self, n_samples, context=None):
-        x = torch.randn(n_samples, *self.size, device=self._anchor.device)
+        x = torch.randn(n_samples, *self.size, device=self._anchor.device, dtype=self._anchor.dtype)   # (model.double() draws doubles)
         return x, self.log_prob(x, context)
 
 

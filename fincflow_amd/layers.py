@@ -204,6 +204,8 @@ class PaddedConv2d(FlowLayer):
         the call sits inside `fincflow_amd.reverse_grad()` and autograd is recording: then the result is attached, with the HIP backward
         of `ops.inverse_reverse` behind it (the bias subtraction stays a differentiable PyTorch line)."""
         b = self.bias if self.bias is not None else self.conv.bias
+        if b is not None and b.dtype != x.dtype:      # (the subtraction below would promote the input past the launch's own check)
+            raise ValueError(f"input must be {b.dtype}, got {x.dtype}")
         if ops.reverse_grad_enabled() and _records_graph(x, self.conv.weight, b):
             if b is not None:
                 x = x - b.reshape(-1, x.shape[1], 1, 1)
@@ -434,7 +436,7 @@ class StandardNormal(nn.Module):
         return -0.5 * (z ** 2 + torch.log(torch.tensor(2 * torch.pi, device=z.device))).flatten(1).sum(1)
 
     def sample(self, n_samples, context=None):
-        return torch.randn(n_samples, *self.size, device=self._anchor.device), None
+        return torch.randn(n_samples, *self.size, device=self._anchor.device, dtype=self._anchor.dtype), None
 
 
 class _InvertibleRunFunction(torch.autograd.Function):

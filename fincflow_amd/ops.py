@@ -251,10 +251,11 @@ def canonicalize(w_stored, G, orient):
 
 
 def check_invariant(w_canon, G):
-    """Raises if the corner tap is not unit lower triangular (layers/conv.py:63-70).  Synchronises."""
-    _require_device(w_canon, "weights")
-    _call("finc_check_invariant_f32", w_canon.device, w_canon.data_ptr(), G, w_canon.shape[0] // G, w_canon.shape[2],
-          w_canon.shape[3], _stream_ptr(w_canon))
+    """Raises if the corner tap is not unit lower triangular (layers/conv.py:63-70).  Synchronises.  float32 or float64."""
+    dt = _float_dtype(w_canon, "weights")
+    _require_device(w_canon, "weights", dt)
+    _call("finc_check_invariant_f32" if dt == torch.float32 else "finc_check_invariant_f64", w_canon.device, w_canon.data_ptr(), G,
+          w_canon.shape[0] // G, w_canon.shape[2], w_canon.shape[3], _stream_ptr(w_canon))
 
 
 def _run(fn_name, act, w_canon, G, orient, algo, out):
@@ -296,7 +297,13 @@ def finc_forward(x, w_canon, G=4, orient=ORIENT_FASTFLOW, algo="auto", out=None)
 
 
 def finc_backward(grad_z, x, w_canon, G, orient, need_gx=True, need_gw=True):
-    _require_device(grad_z, "grad_output")
+    """(grad_x, grad_w_canon) of z = forward(x), each computed only if asked for (None otherwise); the corner-tap mask is applied
+    in-kernel.  float32 (finc_backward_f32) or float64 (finc_backward_f64), taken from `grad_z`: `x` and `w_canon` must match it."""
+    dt = _float_dtype(grad_z, "grad_output")
+    _require_device(grad_z, "grad_output", dt)
+    _require_device(w_canon, "kernel", dt)
+    if x is not None:
+        _require_device(x, "input", dt)
     B, Cq, H, W, KH, KW = _dims(grad_z, w_canon, G)
     gx = torch.empty_like(grad_z) if need_gx else None
     gw = torch.empty_like(w_canon) if need_gw else None
@@ -304,8 +311,12 @@ def finc_backward(grad_z, x, w_canon, G, orient, need_gx=True, need_gw=True):
         if gw is not None:
             gw.zero_()
         return gx, gw
-    _call("finc_backward_f32", grad_z.device, grad_z.data_ptr(), _ptr(x), w_canon.data_ptr(), _ptr(gx), _ptr(gw), B, G, Cq, H, W, KH, KW,
-          orient, *_ws_args(grad_z.device, _lib.lib().finc_backward_workspace_bytes(B, G, Cq, H, W, KH, KW)), _stream_ptr(grad_z))
+    if gx is None and gw is None:
+        return gx, gw
+    fn, ws = ("finc_backward_f32", "finc_backward_workspace_bytes") if dt == torch.float32 else \
+        ("finc_backward_f64", "finc_backward_f64_workspace_bytes")
+    _call(fn, grad_z.device, grad_z.data_ptr(), _ptr(x), w_canon.data_ptr(), _ptr(gx), _ptr(gw), B, G, Cq, H, W, KH, KW,
+          orient, *_ws_args(grad_z.device, getattr(_lib.lib(), ws)(B, G, Cq, H, W, KH, KW)), _stream_ptr(grad_z))
     return gx, gw
 
 
@@ -821,6 +832,11 @@ def _has_mfma(query, t, dims):
     return t.numel() != 0 and getattr(_lib.lib(), query)(*dims[1:]) == _lib.ALGO["mfma"]
 
 
+def _f64(bank):
+    """A float64 entry: the canonical bank and its check, no packed fragments of any kind."""
+    return bank.w_canon.dtype == torch.float64
+
+
 def _aligned16(t, out):
     """The packed inverse streams 16-byte pieces (a view into a larger allocation may be only 4-byte aligned; INTEGRATION.md: such
     calls fall back)."""
@@ -900,7 +916,7 @@ class PackedWeights:
     def _enter(self, t, weights, G, orient, validate=True):
         """What every launch starts with: the device's entry for this weight version, and (B, Cq, H, W, KH, KW) of activations `t`."""
         bank = self._get(weights, G, orient, validate)
-        _require_device(t, "input")
+        _require_device(t, "input", bank.w_canon.dtype)
         return bank, _dims(t, bank.w_canon, G)
 
     def forward(self, x, weights, G, orient, out=None, validate=True):
@@ -908,7 +924,8 @@ class PackedWeights:
         weight version that has not changed since the last call -- evaluation under grad, several micro-batches per
         optimiser step -- costs no cat / canonicalise / pack launch)."""
         bank, dims = self._enter(x, weights, G, orient, validate)
-        if not _has_mfma("finc_forward_algo_for", x, dims):
+        # (float64: finc_forward_f64_algo packs into the workspace per launch -- there are no cached fp64 fragments)
+        if _f64(bank) or not _has_mfma("finc_forward_algo_for", x, dims):
             return finc_forward(x, bank.w_canon, G, orient, out=out)
         packed = _packed(bank, "fwd", "finc_pack_forward_weights_f32", x, G, dims)
         if out is None:
@@ -920,6 +937,8 @@ class PackedWeights:
         """(forward(x) - translation) * exp(-log_scale) in ONE launch: the per-channel affine layer BEHIND the unit in the
         model (ActNorm.forward, layers/actnorm.py:39-46) folded into the forward bank -- filter rows scaled, accumulators
         started from the shift.  Returns None when the shape has no MFMA strip kernel (the caller runs the two layers)."""
+        if weights[0].dtype != torch.float32:        # (fp32 only: the caller runs the two layers)
+            return None
         bank, dims = self._enter(x, weights, G, orient)
         if not _has_mfma("finc_forward_algo_for", x, dims):
             return None
@@ -939,8 +958,8 @@ class PackedWeights:
         bank, dims = self._enter(z, weights, G, orient, validate)
         if out is None and z.numel():
             out = torch.empty_like(z)
-        # the packed launch needs an MFMA instantiation AND 16-byte aligned activations
-        if not (_has_mfma("finc_inverse_algo_for", z, dims) and _aligned16(z, out)):
+        # the packed launch needs fp32, an MFMA instantiation AND 16-byte aligned activations
+        if _f64(bank) or not (_has_mfma("finc_inverse_algo_for", z, dims) and _aligned16(z, out)):
             return finc_inverse(z, bank.w_canon, G, orient, out=out)
         return self._inverse_packed("finc_inverse_packed_f32", z, bank, out, G, dims, orient)
 
@@ -954,6 +973,7 @@ class PackedWeights:
         and the activations are 16-byte aligned, otherwise finc_inverse."""
         _require_device(grad_x, "grad_output")
         w_canon = bank.w_canon
+        _require_device(w_canon, "kernel")        # (fp32 only: ops.inverse_reverse refuses float64 before it gets here)
         dims = _dims(grad_x, w_canon, G)
         B, Cq, H, W, KH, KW = dims
         gw = torch.empty_like(w_canon) if need_gw else None
@@ -988,6 +1008,8 @@ class PackedWeights:
         """Linv_g = inverse of the unit lower triangular tap of the pixel itself (canonical tap [KH-1, KW-1],
         layers/conv.py:63-70), [G, Cq, Cq] fp32 (solved in fp64), cached per weight version: what a channel mix in front of
         the unit multiplies into its matrix so that `inverse_premultiplied` can skip the z-term."""
+        if weights[0].dtype != torch.float32:
+            raise ValueError(f"lead_inverse serves the fp32 premultiplied inverse only, got {weights[0].dtype} weights")
         bank = self._get(weights, G, orient)
         if bank.linv is None:
             wc = bank.w_canon
@@ -1002,7 +1024,9 @@ class PackedWeights:
 
     def premultiplied_supported(self, shape, weights, G, orient):
         """Does `inverse_premultiplied` exist for activations of this shape (the helper-wave form of the inverse: a problem
-        set that fills the chip, W % 16 == 0)?"""
+        set that fills the chip, W % 16 == 0)?  fp32 only."""
+        if weights[0].dtype != torch.float32:
+            return False
         w_canon = self._get(weights, G, orient).w_canon
         B, C, H, W = shape
         Cq, KH, KW = w_canon.shape[1], w_canon.shape[2], w_canon.shape[3]
@@ -1011,7 +1035,9 @@ class PackedWeights:
     def inverse_premultiplied(self, zp, weights, G, orient, out=None):
         """inverse(z) given zp = blockdiag(Linv) z (the channel mix in front of the unit applied Linv for free),
         ONE launch without the z-term's MFMAs.  None when the shape has no such kernel or the activations are not 16-byte
-        aligned (the caller runs the plain chain)."""
+        aligned (the caller runs the plain chain), and for anything but fp32."""
+        if weights[0].dtype != torch.float32:
+            return None
         bank, dims = self._enter(zp, weights, G, orient)
         if zp.numel() == 0 or not _lib.lib().finc_inverse_premultiplied_supported(dims[0], G, *dims[1:]):
             return None
@@ -1025,7 +1051,9 @@ class PackedWeights:
         """inverse(exp(log_scale) * y + translation) in ONE launch: the per-channel affine layer in front
         of the unit in the reverse chain (ActNorm.reverse, layers/actnorm.py:39-52) is folded into the packed bank.
         Returns None when the shape has no MFMA instantiation or the activations are not 16-byte aligned (the caller
-        then runs the two layers one after the other)."""
+        then runs the two layers one after the other), and for anything but fp32."""
+        if weights[0].dtype != torch.float32:
+            return None
         bank, dims = self._enter(y, weights, G, orient)
         if out is None and y.numel():
             out = torch.empty_like(y)

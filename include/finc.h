@@ -263,6 +263,31 @@ int finc_inverse_f64_algo(const double *z, const double *w_canon, double *x, int
                           unsigned orient, int algo, void *workspace, size_t workspace_bytes, finc_stream_t stream);
 int finc_forward_f64_algo(const double *x, const double *w_canon, double *z, int B, int G, int Cq, int H, int W, int KH, int KW,
                           unsigned orient, int algo, void *workspace, size_t workspace_bytes, finc_stream_t stream);
+/*
+ * Backward of the forward conv in double precision: finc_backward_f32's two gradients, argument for argument, on doubles.
+ *   grad_x = conv_transpose(grad_z, w)
+ *   grad_w_canon[o][i][kh][kw] = sum_{b,h,w} grad_z[b,o,h,w] * x[b,i,h-(KH-1-kh),w-(KW-1-kw)]
+ * with the corner-tap mask applied in-kernel: masked entries are written as +0.0.  grad_w_canon is OVERWRITTEN.  Either output may
+ * be NULL to skip it, not both; `x` is read for grad_w_canon only and `w_canon` for grad_x only (each may be NULL without its output);
+ * grad_x may not be grad_z.
+ * With a `workspace` of finc_backward_f64_workspace_bytes() bytes (8-byte aligned) the banks of finc_forward_f64_algo's matrix-core
+ * form (Cq <= 24 at 3x3, <= 32 at 2x2, on the maps that form takes) run both gradients on v_mfma_f64_16x16x4_f64: grad_x is the
+ * forward kernel on the bank packed transposed, every group's orientation complemented; grad_w has the pixels on the MFMA K dimension,
+ * one wavefront per (image, group, row chunk), partial tiles in the workspace and a reduce that adds them in index order (no atomics:
+ * the same inputs give the same bits).  Every other shape, and any call whose workspace is NULL, off an 8-byte boundary or too small,
+ * runs the direct kernels (one output per thread; grad_w: filters of at most 49 taps, FINC_ERR_UNSUPPORTED beyond, as in
+ * finc_backward_f32 -- grad_x is available for every filter).  Results are within 1e-12 of an fp64 autograd of the same convolution.
+ * finc_backward_f64_workspace_bytes is > 0 for any arguments and never shrinks when B, H or W grows.
+ * Status, checked in this order before any HIP call: a NULL required pointer (grad_z; both outputs; w_canon with grad_x; x with
+ * grad_w_canon) FINC_ERR_NULL_POINTER; the dims FINC_ERR_BAD_DIMS; a tensor pointer off an 8-byte boundary FINC_ERR_ALIGNMENT;
+ * grad_x == grad_z FINC_ERR_BAD_DIMS; then the sticky-fault rule below.  All launches are asynchronous on `stream`.
+ * finc_check_invariant_f64: finc_check_invariant_f32 on doubles (same conditions, same status; synchronises `stream`).
+ */
+size_t finc_backward_f64_workspace_bytes(int B, int G, int Cq, int H, int W, int KH, int KW);
+int finc_backward_f64(const double *grad_z, const double *x, const double *w_canon, double *grad_x, double *grad_w_canon, int B, int G,
+                      int Cq, int H, int W, int KH, int KW, unsigned orient, void *workspace, size_t workspace_bytes,
+                      finc_stream_t stream);
+int finc_check_invariant_f64(const double *w_canon, int G, int Cq, int KH, int KW, finc_stream_t stream);
 
 /*
  * SURVEY 8 f3, second half -- the 1x1 convolution next to the unit (layers/conv1x1.py:29-43: forward
