@@ -41,6 +41,7 @@ SYMBOLS = [
     "finc_coupling_reverse_logdet_f32", "finc_coupling_reverse_logdet_backward_f32",
     "finc_actnorm_backward_reconstruct_f32", "finc_coupling_backward_reconstruct_f32",
     "finc_backward_f64_workspace_bytes", "finc_backward_f64", "finc_check_invariant_f64",
+    "finc_debug_f64_plan",
 ]
 
 #: the ABI version this binding is written against (include/finc.h: finc_version)
@@ -63,6 +64,9 @@ INVERTIBLE_BACKWARD_ABI_VERSION = 110
 #: the version that added the double-precision backward of the forward conv and the invariant check on doubles (finc_backward_f64,
 #: finc_check_invariant_f64): what a float64 unit on the device trains and validates with
 F64_BACKWARD_ABI_VERSION = 111
+#: the version that added the float64 matrix-core kernels of the wider banks (29 .. 64 channels at 3x3, 33 .. 64 at 2x2: the M-split
+#: family of finc_f64.hip) and the plan query that says which family a shape takes (finc_debug_f64_plan)
+F64_WIDE_BANKS_ABI_VERSION = 112
 
 _lib = None
 
@@ -116,6 +120,10 @@ def lib():
     if have < F64_BACKWARD_ABI_VERSION:
         raise FincError(f"{LIB_PATH} reports finc_version() = {have}, the double-precision backward (finc_backward_f64, "
                         f"finc_check_invariant_f64) came with {F64_BACKWARD_ABI_VERSION}: rebuild it "
+                        "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
+    if have < F64_WIDE_BANKS_ABI_VERSION:
+        raise FincError(f"{LIB_PATH} reports finc_version() = {have}, the float64 matrix-core kernels of the 29 .. 64 channel banks "
+                        f"and their plan query (finc_debug_f64_plan) came with {F64_WIDE_BANKS_ABI_VERSION}: rebuild it "
                         "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
     L.finc_build_flags.restype = u
     L.finc_clear_fault.restype = i
@@ -172,6 +180,7 @@ def lib():
     L.finc_debug_set_forward_form.argtypes = [i]
     L.finc_debug_gradw_plan.argtypes = [i, i, i, i, i, i, i, i, ctypes.POINTER(ctypes.c_longlong)]
     L.finc_debug_conv_plan.argtypes = [i, i, i, i, i, i, i, i, ctypes.POINTER(ctypes.c_int)]
+    L.finc_debug_f64_plan.argtypes = [i, i, i, i, i, i, i, ctypes.POINTER(ctypes.c_int)]
     L.finc_mix_supported_f32.argtypes = [i]
     L.finc_mix_f32.argtypes = [vp, vp, vp, vp, i, i, i, vp]
     L.finc_mix_backward_workspace_bytes.restype = sz
@@ -274,6 +283,21 @@ def conv_plan(B, G, Cq, H, W, KH, KW, align=16):
     d = dict(zip(("form", "strip", "ns", "waves", "nrc", "RC"), (int(v) for v in info)))
     d["form"] = CONV_FORMS[d["form"]]
     return d
+
+
+F64_FAMILIES = ("none", "one_wave", "msplit")
+
+
+def f64_plan(B, G, Cq, H, W, KH, KW):
+    """What a float64 call on this shape launches (host-only; the launchers' own plan object): `family` 0 none (the reference-order and
+    direct kernels), 1 one wave per problem, 2 the M-split over a workgroup's waves; `cqp` the padded bank; the inverse's `waves` per
+    problem, `ppw` problems per workgroup, `lds` bytes per workgroup and `inv_grid`; `fwd_grid` (x, y) of the forward / grad-input;
+    the grad-weight's `gw_grid`, its `nrc` row chunks per slab of `RC` rows.  The forward's and the grad-weight's workgroups have one
+    wave in family 1 and `waves` (one per 16-row output tile) in family 2."""
+    info = (ctypes.c_int * 11)()
+    check(lib().finc_debug_f64_plan(B, G, Cq, H, W, KH, KW, info), "finc_debug_f64_plan")
+    v = [int(x) for x in info]
+    return dict(family=v[0], cqp=v[1], waves=v[2], ppw=v[3], lds=v[4], inv_grid=v[5], fwd_grid=(v[6], v[7]), gw_grid=v[8], nrc=v[9], RC=v[10])
 
 
 def set_forward_form(form):

@@ -190,7 +190,7 @@ static int canonicalize(const T *w_stored, T *w_canon, int G, int Cq, int KH, in
 
 extern "C" {
 
-int finc_version(void) { return 111; }
+int finc_version(void) { return 112; }
 
 unsigned finc_build_flags(void)
 {
@@ -808,6 +808,18 @@ int finc_debug_conv_plan(int B, int G, int Cq, int H, int W, int KH, int KW, int
     return finc_conv_plan_info(FincShape{B, G, Cq, H, W, KH, KW, 0}, align, info);
 }
 
+int finc_debug_f64_plan(int B, int G, int Cq, int H, int W, int KH, int KW, int *info)
+{
+    if (!info) return FINC_ERR_NULL_POINTER;
+    if (int e = check_shape(B, G, Cq, H, W, KH, KW)) return e;
+    const FincShape s{B, G, Cq, H, W, KH, KW, 0};
+    const FincF64Plan p = finc_f64_plan(s);
+    const FincF64GradwPlan gw = finc_f64_gradw_plan(s);
+    const long long v[11] = {p.family, p.cqp, p.waves, p.ppw, p.lds, p.inv_grid, p.fwd_grid_x, p.fwd_grid_y, p.waves ? gw.waves / p.waves : 0, gw.nrc, gw.RC};
+    for (int k = 0; k < 11; ++k) info[k] = p.family ? (int)v[k] : 0;
+    return FINC_OK;
+}
+
 int finc_debug_set_forward_form(int form) { return finc_wino_set_form(form); }
 
 int finc_debug_inverse_remainder_images(int B, int G, int Cq, int H, int W, int KH, int KW)
@@ -911,8 +923,9 @@ int finc_backward_f64(const double *grad_z, const double *x, const double *w_can
     // (a workspace off an 8-byte boundary counts as none, as in the finc_*_f64_algo calls)
     const bool mfma = workspace && ((uintptr_t)workspace & 7u) == 0 && finc_f64_supported(s);
     const size_t bank = align256(finc_f64_packed_bytes(G, Cq, KH, KW));
-    // grad_x: the forward kernel on the transposed bank, every group's orientation complemented (grid.y carries the slabs)
-    if (grad_x && mfma && workspace_bytes >= bank && (long long)B * G <= 65535) {
+    // grad_x: the forward kernel on the transposed bank, every group's orientation complemented (one-wave family: grid.y carries the
+    // slabs; the M-split family has everything on grid.x)
+    if (grad_x && mfma && workspace_bytes >= bank && (finc_f64_plan(s).family == 2 || (long long)B * G <= 65535)) {
         FincShape sb = s;
         sb.orient = orient ^ ((G >= 16) ? 0xFFFFFFFFu : ((1u << (2 * G)) - 1u));
         if (int e = finc_f64_launch(grad_z, w_canon, grad_x, workspace, sb, true, st, true)) return e;

@@ -256,7 +256,18 @@ size_t finc_gradw_workspace_bytes(const FincShape &s);  // room for the plans of
 // >= finc_gradw_workspace_bytes of every call on this bank with at most `units` = B * ceil(W / 16) strips; never shrinks when units grows
 size_t finc_gradw_workspace_bound(int G, int Cq, int KH, int KW, long long units);
 
-// ---- double precision on the matrix cores: finc_f64.hip (the c2 / c3 class of banks: Cq <= 24 at 3x3, <= 32 at 2x2) ----
+// ---- double precision on the matrix cores: finc_f64.hip.  Two families: one wave per problem (Cq <= 24 at 3x3, <= 32 at 2x2) and the
+// M-split over a workgroup's waves (29 .. 64 at 3x3, 33 .. 64 at 2x2); 25 .. 28 at 3x3, wider banks and other filters have neither ----
+// what a call on this shape launches: the one object the launchers, finc_f64_supported and finc_debug_f64_plan read
+struct FincF64Plan {
+    int family = 0;           // 0: no matrix-core kernel, 1: one wave per problem, 2: M-split
+    int cqp = 0;              // the padded bank
+    int waves = 0, ppw = 0;   // inverse: waves per problem, problems per workgroup
+    int lds = 0;              // inverse: bytes of LDS per workgroup
+    int P = 0, DF = 0;        // inverse: rows per band, slots of the FIFO of rows above a band
+    long long inv_grid = 0, fwd_grid_x = 0, fwd_grid_y = 0;
+};
+FincF64Plan finc_f64_plan(const FincShape &s);
 bool finc_f64_supported(const FincShape &s);
 size_t finc_f64_packed_bytes(int G, int Cq, int KH, int KW);          // 0: no such kernel for this bank
 // packs the bank into `packed` (finc_f64_packed_bytes) and runs the inverse or the forward on it, all on `st`
@@ -267,7 +278,7 @@ int finc_f64_launch(const double *in, const double *wc, double *out, void *packe
 // reduce with the corner-tap mask.  The grid is not capped: a wave takes exactly one unit.
 struct FincF64GradwPlan {
     int nrc = 0, RC = 0;      // row chunks per slab (0: no kernel for this bank) of RC rows, the last one ragged
-    long long waves = 0;      // B * G * nrc one-wave workgroups
+    long long waves = 0;      // B * G * nrc waves (M-split family: times the row tiles of the bank, the waves of one workgroup)
     long long parts = 0;      // B * nrc partial tiles per (group, o, i, tap), summed in index order
     size_t bytes = 0;         // of the partials
 };

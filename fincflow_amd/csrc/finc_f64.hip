@@ -13,6 +13,9 @@
 // one double per lane: 216 registers at Cq = 24 -- stays in registers for the whole kernel (one wave per SIMD: 512 registers).
 // A step is 9 * NK * MT MFMAs of 64 cycles (Cq = 24: 108 + 12 = 7,680 cycles), so everything else -- 48 LDS reads, the dword-pair
 // loads and stores of a lane's own pixel -- runs in their shadow.
+//
+// That is the first family: Cq <= 24 at 3x3, <= 32 at 2x2.  The banks of 29 .. 64 channels (3x3) and 33 .. 64 (2x2) run on a second
+// one further down, which splits a problem's 16-row output tiles over the waves of a workgroup.
 #include "finc_common.h"
 
 #include <type_traits>
@@ -421,45 +424,376 @@ __global__ void gradw_f64_reduce_kernel(const double *__restrict__ partials, dou
     gw[((size_t)(g * Cq + oc) * Cq + ic) * KK + widx] = masked ? 0.0 : s;
 }
 
+// -----------------------------------------------------------------------------------------------
+// The second family: banks of 29 .. 64 channels at 3x3 and 33 .. 64 at 2x2, padded to CQP = 32 / 48 / 64.  9 * NK * MT
+// fragments no longer fit one wave (CQP = 64: 576 doubles), so the bank is split over the MT 16-row output tiles: wave w of a problem
+// holds the slice [tap][j][w] (9 * NK doubles, 144 at CQP = 64), accumulates tile w alone and owns the k-steps 4 w .. 4 w + 3 of every
+// solved pixel -- its ring and FIFO words and its channels in memory.  Visitation, LDS cells and both store paths are the one-wave
+// kernel's.  Linv is folded into the bank, so the tiles of a pixel do not depend on each other within a step; what a wave reads of the
+// others is at least one step old, and ONE __syncthreads per step orders it.  Two things differ from the one-wave layout because the
+// waves of a step are no longer in program order: the FIFO is one slot deeper (the oldest read of a step, age KH + KW - 2 of the rows
+// above a band, would share its slot with the push of the same step), and a problem slot of the workgroup beyond the last problem runs
+// every step on a zero-length buffer resource (loads give 0, stores are dropped) so that the barrier count stays uniform.
+// -----------------------------------------------------------------------------------------------
+template <int CQP, int KH, int KW>
+struct MCfg : DCfg<CQP, KH, KW> {
+    static_assert(CQP % 16 == 0 && CQP >= 32 && CQP <= 64, "bank");
+    static constexpr int PPW = CQP == 32 ? 2 : 1;                 // problems per workgroup at most (as many as the LDS holds)
+};
+
+constexpr int msplit_threads(int cqp) { return 64 * (cqp / 16) * (cqp == 32 ? 2 : 1); }     // MT waves per problem, PPW problems
+
+template <int CQP, int KH, int KW>
+__global__ __launch_bounds__(msplit_threads(CQP), 1) void finc_f64_msplit_inverse_kernel(
+    const double *__restrict__ in, const double *__restrict__ packed, double *__restrict__ out, int G, int CQ, int H, int W, int P, int T,
+    unsigned orient, int DF, int nprob, int ppw)
+{
+    using C = MCfg<CQP, KH, KW>;
+    constexpr int MT = C::MT, NK = C::NK, CELL = C::CELL, HROWS = C::HROWS;
+    extern __shared__ __attribute__((aligned(16))) double lds_all[];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int w = wave % MT, prob = wave / MT;                    // the wave's row tile, its problem within the workgroup
+    const int bg = (int)blockIdx.x * ppw + prob;
+    const bool live = bg < nprob;                                 // (the grid has no workgroup without a first problem)
+    double *const ldsd = lds_all + (size_t)prob * (C::lds_bytes(DF) / 8);
+    char *const ldsb = reinterpret_cast<char *>(ldsd);
+    const int lane = threadIdx.x & 63, q = lane >> 4, p = lane & 15;
+    const int g = (live ? bg : 0) % G;
+    const unsigned o = finc_group_orient(orient, g);
+    const bool fh = (o & FINC_FLIP_H) != 0, fw = (o & FINC_FLIP_W) != 0;
+    const int HW = H * W;
+    const unsigned slab_bytes = live ? (unsigned)CQ * (unsigned)HW * 8u : 0u;
+    const size_t slab = live ? (size_t)bg * CQ * HW : 0;
+    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void *)(in + slab), 0, (int)slab_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc((void *)(out + slab), 0, (int)slab_bytes, 0x00020000);
+
+    for (int i = w * 64 + lane; i < C::lds_bytes(DF) / 8; i += 64 * MT) ldsd[i] = 0.0;
+
+    // the wave's slice of the bank: registers for the whole kernel
+    double fr[C::NTAP][NK];
+    const double *pk = packed + (size_t)g * C::NFRAG * 64 + (size_t)w * 64 + lane;
+#pragma unroll
+    for (int tp = 0; tp < C::NTAP; ++tp)
+#pragma unroll
+        for (int j = 0; j < NK; ++j) fr[tp][j] = pk[(size_t)((tp * NK + j) * MT) * 64];
+
+    auto ld = [&](int byte_off) { return *reinterpret_cast<const double *>(ldsb + byte_off); };
+    auto st = [&](int byte_off, double v) { *reinterpret_cast<double *>(ldsb + byte_off) = v; };
+
+    const int jz = 4 * w + 4;                    // Linv is lower triangular: tile w reads the k-steps j < jz of z
+    auto chan_off = [&](int j) { return (4 * j + q) < CQ ? (unsigned)((4 * j + q) * HW * 8) : OFF_BAD_CHANNEL; };
+    unsigned own_off[4];                         // the channels the wave stores: k-steps 4 w + r
+#pragma unroll
+    for (int r = 0; r < 4; ++r) own_off[r] = (16 * w + 4 * r + q) < CQ ? (unsigned)((16 * w + 4 * r + q) * HW * 8) : OFF_BAD_CHANNEL;
+    const int wpart = w * 32;                    // the wave's four doubles within a cell
+    int taddr[KH];
+#pragma unroll
+    for (int a = 0; a < KH; ++a) taddr[a] = C::RING_B + (lane - a) * CELL;
+    const bool pusher = HROWS > 0 && p >= P - HROWS && p < P;
+    const int push_cell = C::FIFO_B + (q * HROWS + (P - 1 - p)) * CELL + wpart;
+
+    int c = -p, row = p;
+    auto pix_off = [&](int r, int cc) { return (unsigned)(((fh ? H - 1 - r : r) * W + (fw ? W - 1 - cc : cc)) * 8); };
+    double zn[NK];
+    auto request = [&](int cc, int rr) {
+        const bool ok = cc >= 0 && rr < H && p < P;
+        const unsigned base = ok ? pix_off(rr, cc) : OFF_INVALID;
+#pragma unroll
+        for (int j = 0; j < NK; ++j) {
+            const v2u w2 = __builtin_bit_cast(v2u, __builtin_amdgcn_raw_buffer_load_b64(rin, (j < jz ? base : OFF_INVALID) + chan_off(j), 0, 0));
+            zn[j] = __builtin_bit_cast(double, w2);
+        }
+    };
+    request(c, row);
+    const bool W4 = (W & 3) == 0;
+    int slot = 0, fpush = 0;
+    __syncthreads();                             // the zero fill
+    for (int t = 0; t < T; ++t) {
+        double z[NK];
+#pragma unroll
+        for (int j = 0; j < NK; ++j) z[j] = zn[j];
+        const int cn = (c + 1 == W) ? 0 : c + 1, rn = (c + 1 == W) ? row + P : row;
+        request(cn, rn);
+        v4d acc = (v4d){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int j = 0; j < NK; ++j)
+            if (j < jz) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(fr[0][j], z[j], acc, 0, 0, 0);      // (uniform in the wave)
+#pragma unroll
+        for (int age = KH + KW - 2; age >= 1; --age)
+#pragma unroll
+            for (int a = 0; a < KH; ++a) {
+                const int b = age - a;
+                if (b < 0 || b >= KW) continue;
+                int sl = slot - age; if (sl < 0) sl += XS;
+                int fs = fpush - age - (W - P); fs %= DF; if (fs < 0) fs += DF;
+                int addr = taddr[a] + sl * (64 * CELL);
+                if (a > 0) addr = p >= a ? addr : C::FIFO_B + fs * C::FSLOT + (q * HROWS + (a - 1 - p)) * CELL;
+                if (b > 0) addr = c >= b ? addr : C::ZERO_B;
+                double x[NK];
+#pragma unroll
+                for (int j = 0; j < NK; ++j) x[j] = ld(addr + j * 8);
+#pragma unroll
+                for (int j = 0; j < NK; ++j) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(fr[a * KW + b][j], x[j], acc, 0, 0, 0);
+            }
+        // ---- the solved pixel's k-steps 4 w + r: register r at lane (q, p) = channel 16 w + 4 r + q
+        const bool started = c >= 0 && p < P;
+        const double xs[4] = {started ? acc.x : 0.0, started ? acc.y : 0.0, started ? acc.z : 0.0, started ? acc.w : 0.0};
+        const int cell = C::RING_B + slot * (64 * CELL) + lane * CELL + wpart;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) st(cell + r * 8, xs[r]);
+        if (pusher) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) st(push_cell + fpush * C::FSLOT + r * 8, xs[r]);
+        }
+        if (W4) {
+            // (the three columns before this one: the wave's own words of the lane's own cells)
+            const bool ok = started && row < H && (c & 3) == 3;
+            const unsigned base = ok ? pix_off(row, fw ? c : c - 3) : OFF_INVALID;
+            int s1 = slot - 1, s2 = slot - 2, s3 = slot - 3;
+            s1 = s1 < 0 ? s1 + XS : s1; s2 = s2 < 0 ? s2 + XS : s2; s3 = s3 < 0 ? s3 + XS : s3;
+            const int own = C::RING_B + lane * CELL + wpart;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const double x3 = ld(own + s3 * (64 * CELL) + r * 8), x2 = ld(own + s2 * (64 * CELL) + r * 8), x1 = ld(own + s1 * (64 * CELL) + r * 8);
+                const double lo0 = fw ? xs[r] : x3, lo1 = fw ? x1 : x2, hi0 = fw ? x2 : x1, hi1 = fw ? x3 : xs[r];
+                const v2u a0 = __builtin_bit_cast(v2u, lo0), a1 = __builtin_bit_cast(v2u, lo1), b0 = __builtin_bit_cast(v2u, hi0), b1 = __builtin_bit_cast(v2u, hi1);
+                __builtin_amdgcn_raw_buffer_store_b128((v4u){a0.x, a0.y, a1.x, a1.y}, rout, base + own_off[r], 0, 0);
+                asm volatile("s_nop 1");         // (the store hazard of the one-wave kernel)
+                __builtin_amdgcn_raw_buffer_store_b128((v4u){b0.x, b0.y, b1.x, b1.y}, rout, base + own_off[r] + 16, 0, 0);
+                asm volatile("s_nop 1");
+            }
+        } else {
+            const bool ok = started && row < H;
+            const unsigned base = ok ? pix_off(row, c) : OFF_INVALID;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, xs[r]), rout, base + own_off[r], 0, 0);
+        }
+        c = cn; row = rn;
+        ++slot; if (slot == XS) slot = 0;
+        ++fpush; if (fpush == DF) fpush = 0;
+        __syncthreads();                         // the step's cells are written: the next step's age-1 taps read every wave's words
+    }
+}
+
+// forward / grad-input of the second family: the strip kernel with the output row tile as one more launch dimension, the waves of a
+// workgroup (which go to the four SIMDs in turn and read the same input rows at the same time; one-wave workgroups do neither).
+// grid.x = slab * strips + strip; wave w holds the slice [tap][j][w], reads every input channel, stores its 16.
+template <int CQP, int KH, int KW>
+__global__ __launch_bounds__(64 * (CQP / 16), 1) void finc_f64_msplit_forward_kernel(const double *__restrict__ in, const double *__restrict__ packed,
+                                                                     double *__restrict__ out, int G, int CQ, int H, int W, unsigned orient, int ns)
+{
+    using C = MCfg<CQP, KH, KW>;
+    constexpr int MT = C::MT, NK = C::NK;
+    const int lane = threadIdx.x & 63, q = lane >> 4, p = lane & 15;
+    const int mt = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const unsigned unit = blockIdx.x;
+    const int strip = (int)(unit % (unsigned)ns), bg = (int)(unit / (unsigned)ns), g = bg % G;
+    const int w0 = strip * 16;
+    const unsigned o = finc_group_orient(orient, g);
+    const bool fh = (o & FINC_FLIP_H) != 0, fw = (o & FINC_FLIP_W) != 0;
+    const int HW = H * W;
+    const unsigned slab_bytes = (unsigned)CQ * (unsigned)HW * 8u;
+    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void *)(in + (size_t)bg * CQ * HW), 0, (int)slab_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc((void *)(out + (size_t)bg * CQ * HW), 0, (int)slab_bytes, 0x00020000);
+    double fr[C::NTAP][NK];
+    const double *pk = packed + (size_t)g * C::NFRAG * 64 + (size_t)mt * 64 + lane;
+#pragma unroll
+    for (int tp = 0; tp < C::NTAP; ++tp)
+#pragma unroll
+        for (int j = 0; j < NK; ++j) fr[tp][j] = pk[(size_t)((tp * NK + j) * MT) * 64];
+    unsigned chan_off[NK], own_off[4];
+#pragma unroll
+    for (int j = 0; j < NK; ++j) chan_off[j] = (4 * j + q) < CQ ? (unsigned)((4 * j + q) * HW * 8) : OFF_BAD_CHANNEL;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) own_off[r] = (16 * mt + 4 * r + q) < CQ ? (unsigned)((16 * mt + 4 * r + q) * HW * 8) : OFF_BAD_CHANNEL;
+    auto pix_off = [&](int r, int cc) { return (unsigned)(((fh ? H - 1 - r : r) * W + (fw ? W - 1 - cc : cc)) * 8); };
+    const int col = w0 + p;
+    for (int h = 0; h < H; ++h) {
+        v4d acc = (v4d){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int a = 0; a < KH; ++a)
+#pragma unroll
+            for (int b = 0; b < KW; ++b) {
+                const bool ok = h - a >= 0 && col - b >= 0 && col - b < W;
+                const unsigned base = ok ? pix_off(h - a, col - b) : OFF_INVALID;
+                double x[NK];
+#pragma unroll
+                for (int j = 0; j < NK; ++j) x[j] = __builtin_bit_cast(double, __builtin_bit_cast(v2u, __builtin_amdgcn_raw_buffer_load_b64(rin, base + chan_off[j], 0, 0)));
+#pragma unroll
+                for (int j = 0; j < NK; ++j) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(fr[a * KW + b][j], x[j], acc, 0, 0, 0);
+            }
+        const unsigned base = col < W ? pix_off(h, col) : OFF_INVALID;
+        const double v[4] = {acc.x, acc.y, acc.z, acc.w};
+#pragma unroll
+        for (int r = 0; r < 4; ++r) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, v[r]), rout, base + own_off[r], 0, 0);
+    }
+}
+
+// weight gradient of the second family: finc_f64_gradw_kernel with the output row tile as one more launch dimension, the waves of a
+// workgroup again (they read the same x).  grid.x = slab * nrc + chunk; wave `to` accumulates NTAP * MT tiles (its 16 output channels against every input tile:
+// 36 accumulators at CQP = 64) and writes them to the same partials layout, so the reduce is the first family's.
+template <int CQP, int KH, int KW>
+__global__ __launch_bounds__(64 * (CQP / 16), 1) void finc_f64_msplit_gradw_kernel(const double *__restrict__ gz, const double *__restrict__ x,
+                                                                   double *__restrict__ partials, int G, int CQ, int H, int W, unsigned orient,
+                                                                   int nrc, int RC)
+{
+    using C = MCfg<CQP, KH, KW>;
+    constexpr int MT = C::MT, NTAP = C::NTAP;
+    const int lane = threadIdx.x & 63, q = lane >> 4, m = lane & 15;
+    const int to = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const unsigned unit = blockIdx.x;
+    const int chunk = (int)(unit % (unsigned)nrc), bg = (int)(unit / (unsigned)nrc), g = bg % G;
+    const unsigned o = finc_group_orient(orient, g);
+    const bool fh = (o & FINC_FLIP_H) != 0, fw = (o & FINC_FLIP_W) != 0;
+    const int HW = H * W;
+    const unsigned slab_bytes = (unsigned)CQ * (unsigned)HW * 8u;
+    const __amdgpu_buffer_rsrc_t rgz = __builtin_amdgcn_make_buffer_rsrc((void *)(gz + (size_t)bg * CQ * HW), 0, (int)slab_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void *)(x + (size_t)bg * CQ * HW), 0, (int)slab_bytes, 0x00020000);
+    unsigned chan_off[MT];
+#pragma unroll
+    for (int t = 0; t < MT; ++t) chan_off[t] = (16 * t + m) < CQ ? (unsigned)((16 * t + m) * HW * 8) : OFF_BAD_CHANNEL;
+    const unsigned own_off = (16 * to + m) < CQ ? (unsigned)((16 * to + m) * HW * 8) : OFF_BAD_CHANNEL;
+    auto pix_off = [&](int r, int cc) { return (unsigned)(((fh ? H - 1 - r : r) * W + (fw ? W - 1 - cc : cc)) * 8); };
+    auto load = [&](const __amdgpu_buffer_rsrc_t &rs, unsigned off) {
+        return __builtin_bit_cast(double, __builtin_bit_cast(v2u, __builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, 0)));
+    };
+    v4d acc[NTAP][MT];
+#pragma unroll
+    for (int tp = 0; tp < NTAP; ++tp)
+#pragma unroll
+        for (int ti = 0; ti < MT; ++ti) acc[tp][ti] = (v4d){0.0, 0.0, 0.0, 0.0};
+    const int r0 = chunk * RC, r1 = r0 + RC < H ? r0 + RC : H;
+    double zn, xn[NTAP][MT];
+    auto request = [&](int h, int c0) {
+        const int col = c0 + q;
+        const bool okz = h < r1 && col < W;
+        zn = load(rgz, (okz ? pix_off(h, col) : OFF_INVALID) + own_off);
+#pragma unroll
+        for (int a = 0; a < KH; ++a)
+#pragma unroll
+            for (int b = 0; b < KW; ++b) {
+                const bool ok = okz && h - a >= 0 && col - b >= 0;
+                const unsigned xb = ok ? pix_off(h - a, col - b) : OFF_INVALID;
+#pragma unroll
+                for (int t = 0; t < MT; ++t) xn[a * KW + b][t] = load(rx, xb + chan_off[t]);
+            }
+    };
+    int h = r0, c0 = 0;
+    request(h, c0);
+    const int steps = (r1 - r0) * ((W + 3) >> 2);
+    for (int s = 0; s < steps; ++s) {
+        double xc[NTAP][MT];
+        const double zc = zn;
+#pragma unroll
+        for (int tp = 0; tp < NTAP; ++tp)
+#pragma unroll
+            for (int t = 0; t < MT; ++t) xc[tp][t] = xn[tp][t];
+        c0 += 4;
+        if (c0 >= W) { c0 = 0; ++h; }
+        request(h, c0);
+#pragma unroll
+        for (int tp = 0; tp < NTAP; ++tp)
+#pragma unroll
+            for (int ti = 0; ti < MT; ++ti) acc[tp][ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(zc, xc[tp][ti], acc[tp][ti], 0, 0, 0);
+    }
+    constexpr int PER = NTAP * MT * MT * 256;
+    double *outp = partials + (((size_t)(bg / G) * nrc + chunk) * G + g) * PER + lane;
+#pragma unroll
+    for (int tp = 0; tp < NTAP; ++tp)
+#pragma unroll
+        for (int ti = 0; ti < MT; ++ti) {
+            const v4d &am = acc[tp][ti];
+            double *t = outp + (size_t)((tp * MT + to) * MT + ti) * 256;
+            t[0] = am.x; t[64] = am.y; t[128] = am.z; t[192] = am.w;
+        }
+}
+
 typedef void (*f64inv_fn)(const double *, const double *, double *, int, int, int, int, int, int, unsigned, int, int, int);
 typedef void (*f64fwd_fn)(const double *, const double *, double *, int, int, int, int, unsigned);
+typedef void (*f64mfwd_fn)(const double *, const double *, double *, int, int, int, int, unsigned, int);
 typedef void (*f64gw_fn)(const double *, const double *, double *, int, int, int, int, unsigned, int, int);
 struct DInst {
     int cqp, kh, kw, nfrag, lds_fixed, fslot;
     f64inv_fn inv;
     f64fwd_fn fwd;
     f64gw_fn gradw;
+    int split, ppw;                  // second family: waves per problem (= row tiles) and problems per workgroup at most; 0: one wave
+    f64mfwd_fn mfwd;
 };
 template <int CQP, int KH, int KW>
 constexpr DInst make_dinst()
 {
     return DInst{CQP, KH, KW, DCfg<CQP, KH, KW>::NFRAG, DCfg<CQP, KH, KW>::lds_bytes(0), DCfg<CQP, KH, KW>::FSLOT,
-                 finc_f64_inverse_kernel<CQP, KH, KW>, finc_f64_forward_kernel<CQP, KH, KW>, finc_f64_gradw_kernel<CQP, KH, KW>};
+                 finc_f64_inverse_kernel<CQP, KH, KW>, finc_f64_forward_kernel<CQP, KH, KW>, finc_f64_gradw_kernel<CQP, KH, KW>, 0, 0, nullptr};
+}
+template <int CQP, int KH, int KW>
+constexpr DInst make_minst()
+{
+    using C = MCfg<CQP, KH, KW>;
+    return DInst{CQP, KH, KW, C::NFRAG, C::lds_bytes(0), C::FSLOT, finc_f64_msplit_inverse_kernel<CQP, KH, KW>, nullptr,
+                 finc_f64_msplit_gradw_kernel<CQP, KH, KW>, C::MT, C::PPW, finc_f64_msplit_forward_kernel<CQP, KH, KW>};
 }
 const DInst g_dinsts[] = {
     make_dinst<4, 3, 3>(), make_dinst<8, 3, 3>(), make_dinst<12, 3, 3>(), make_dinst<16, 3, 3>(), make_dinst<20, 3, 3>(), make_dinst<24, 3, 3>(),
     make_dinst<4, 2, 2>(), make_dinst<8, 2, 2>(), make_dinst<12, 2, 2>(), make_dinst<16, 2, 2>(), make_dinst<24, 2, 2>(), make_dinst<32, 2, 2>(),
+};
+// the second family takes what lies beyond the first: 29 .. 64 channels at 3x3 (25 .. 28 stay on the direct kernels), 33 .. 64 at 2x2;
+// a count in between runs on the next larger bank with its channels masked
+const DInst g_minsts[] = {
+    make_minst<32, 3, 3>(), make_minst<48, 3, 3>(), make_minst<64, 3, 3>(), make_minst<48, 2, 2>(), make_minst<64, 2, 2>(),
 };
 const DInst *find_dinst(int Cq, int KH, int KW)
 {
     const int cqp = (Cq + 3) / 4 * 4;
     for (const DInst &i : g_dinsts)
         if (i.cqp == cqp && i.kh == KH && i.kw == KW) return &i;
+    const bool k3 = KH == 3 && KW == 3, k2 = KH == 2 && KW == 2;
+    if (Cq > 64 || !((k3 && Cq >= 29) || (k2 && Cq >= 33))) return nullptr;
+    const int cqm = Cq <= 32 ? 32 : Cq <= 48 ? 48 : 64;
+    for (const DInst &i : g_minsts)
+        if (i.cqp == cqm && i.kh == KH && i.kw == KW) return &i;
     return nullptr;
 }
-int f64_fifo_depth(int W, int P, int KH, int KW) { return W - P + KH + KW - 2; }
+// slots of the FIFO of rows above a band.  The M-split kernel's waves are not in program order within a step, so the oldest read of a
+// step must not share its slot with the step's push: one slot more.
+int f64_fifo_depth(int W, int P, int KH, int KW, bool split) { return W - P + KH + KW - 2 + (split ? 1 : 0); }
+constexpr size_t F64_LDS_MAX = 160 * 1024;
 
 } // namespace
 
-bool finc_f64_supported(const FincShape &s)
+FincF64Plan finc_f64_plan(const FincShape &s)
 {
+    FincF64Plan p;
     const DInst *i = find_dinst(s.Cq, s.KH, s.KW);
-    if (!i || s.H < 1 || s.W < 1) return false;
+    if (!i || s.B < 1 || s.G < 1 || s.H < 1 || s.W < 1) return p;
     const int P = s.W < 16 ? s.W : 16;
-    if (P < s.KH - 1) return false;
-    if ((size_t)s.Cq * s.H * s.W * 8 >= ((size_t)1 << 30)) return false;     // buffer-offset range marks
-    return (size_t)i->lds_fixed + (size_t)f64_fifo_depth(s.W, P, s.KH, s.KW) * i->fslot <= 160 * 1024;
+    if (P < s.KH - 1) return p;
+    if ((size_t)s.Cq * s.H * s.W * 8 >= ((size_t)1 << 30)) return p;        // buffer-offset range marks
+    const int DF = f64_fifo_depth(s.W, P, s.KH, s.KW, i->split != 0);
+    const size_t per = (size_t)i->lds_fixed + (size_t)DF * i->fslot;        // LDS of one problem
+    if (per > F64_LDS_MAX) return p;
+    const long long nprob = (long long)s.B * s.G;
+    const int ns = (s.W + 15) / 16;
+    int ppw = i->split ? i->ppw : WPW;
+    while (ppw > 1 && per * ppw > F64_LDS_MAX) ppw >>= 1;
+    if (i->split) {
+        if (nprob < ppw) ppw = 1;
+        if (nprob * ns > 0x7fffffffLL) return p;                             // (grid.x of the forward)
+    }
+    p.family = i->split ? 2 : 1;
+    p.cqp = i->cqp;
+    p.waves = i->split ? i->split : 1;
+    p.ppw = ppw;
+    p.lds = (int)(per * ppw);
+    p.P = P;
+    p.DF = DF;
+    p.inv_grid = (nprob + ppw - 1) / ppw;
+    p.fwd_grid_x = i->split ? nprob * ns : ns;
+    p.fwd_grid_y = i->split ? 1 : nprob;
+    return p;
 }
+
+bool finc_f64_supported(const FincShape &s) { return finc_f64_plan(s).family != 0; }
 
 size_t finc_f64_packed_bytes(int G, int Cq, int KH, int KW)
 {
@@ -467,8 +801,9 @@ size_t finc_f64_packed_bytes(int G, int Cq, int KH, int KW)
     return i ? (size_t)G * i->nfrag * 64 * sizeof(double) : 0;
 }
 
-// Row chunks of the weight gradient: only a launch that leaves SIMDs idle (fewer slabs than the 1,024 one-wave slots of the chip) cuts
-// its slabs, into as many chunks of at least four rows as fill them.  B * nrc <= min(B * max(1, H / 4), max(B, 1024 / G)): the bound.
+// Row chunks of the weight gradient: only a launch that leaves SIMDs idle (fewer waves than the 1,024 one-wave slots of the chip) cuts
+// its slabs, into as many chunks of at least four rows as fill them.  A slab is one wave of the first family and one per row tile of the
+// second.  B * nrc <= min(B * max(1, H / 4), max(B, 1024 / (G * waves per slab))): the bound.
 constexpr long long GW_SLOTS = 1024;
 constexpr int GW_MIN_ROWS = 4;
 static size_t gradw_tile_doubles(const DInst *i)
@@ -482,15 +817,16 @@ FincF64GradwPlan finc_f64_gradw_plan(const FincShape &s)
     FincF64GradwPlan p;
     const DInst *i = find_dinst(s.Cq, s.KH, s.KW);
     if (!i || !finc_f64_supported(s)) return p;
+    const int per_slab = i->split ? i->split : 1;
     const long long units = (long long)s.B * s.G;
     const int maxc = s.H / GW_MIN_ROWS > 0 ? s.H / GW_MIN_ROWS : 1;
-    long long want = GW_SLOTS / units;
+    long long want = GW_SLOTS / (units * per_slab);
     want = want > maxc ? maxc : want < 1 ? 1 : want;
     const int RC = (s.H + (int)want - 1) / (int)want, nrc = (s.H + RC - 1) / RC;
     if (units * nrc > 0x7fffffffLL) return p;                               // (grid.x: the direct kernel takes such a batch)
     p.nrc = nrc;
     p.RC = RC;
-    p.waves = units * nrc;
+    p.waves = units * nrc * per_slab;
     p.parts = (long long)s.B * nrc;
     p.bytes = (size_t)p.parts * s.G * gradw_tile_doubles(i) * sizeof(double);
     return p;
@@ -501,7 +837,8 @@ size_t finc_f64_gradw_workspace_bound(int B, int G, int Cq, int H, int KH, int K
     const DInst *i = find_dinst(Cq, KH, KW);
     if (!i) return 0;
     const long long maxc = H / GW_MIN_ROWS > 0 ? H / GW_MIN_ROWS : 1;
-    const long long fill = (GW_SLOTS + G - 1) / G;
+    const long long per_group = (long long)G * (i->split ? i->split : 1);
+    const long long fill = (GW_SLOTS + per_group - 1) / per_group;
     long long parts = B > fill ? B : fill;
     if ((long long)B * maxc < parts) parts = (long long)B * maxc;
     return (size_t)parts * G * gradw_tile_doubles(i) * sizeof(double);
@@ -512,7 +849,8 @@ int finc_f64_gradw_launch(const double *gz, const double *x, double *gw, void *w
     const DInst *i = find_dinst(s.Cq, s.KH, s.KW);
     const FincF64GradwPlan p = finc_f64_gradw_plan(s);
     if (!i || !p.nrc) return FINC_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(i->gradw, dim3((unsigned)p.waves), dim3(64), 0, st, gz, x, (double *)workspace, s.G, s.Cq, s.H, s.W, s.orient, p.nrc,
+    const int per_slab = i->split ? i->split : 1;                           // (the M-split family: one workgroup of a wave per row tile)
+    hipLaunchKernelGGL(i->gradw, dim3((unsigned)(p.waves / per_slab)), dim3(64 * per_slab), 0, st, gz, x, (double *)workspace, s.G, s.Cq, s.H, s.W, s.orient, p.nrc,
                        p.RC);
     FINC_CHECK_LAUNCH();
     const int MT = (i->cqp + 15) / 16;
@@ -527,24 +865,23 @@ int finc_f64_launch(const double *in, const double *wc, double *out, void *packe
                     bool transpose)
 {
     const DInst *i = find_dinst(s.Cq, s.KH, s.KW);
-    if (!i) return FINC_ERR_UNSUPPORTED;
+    const FincF64Plan p = finc_f64_plan(s);
+    if (!i || !p.family) return FINC_ERR_UNSUPPORTED;
     const int MT = (i->cqp + 15) / 16, NK = i->cqp / 4;
     hipLaunchKernelGGL(pack_f64_kernel, dim3(s.G), dim3(256), sizeof(double) * s.Cq * s.Cq, st, wc, (double *)packed, s.Cq, s.KH, s.KW, MT, NK,
                        forward ? (transpose ? 2 : 1) : 0);
     FINC_CHECK_LAUNCH();
-    if (forward) {
-        hipLaunchKernelGGL(i->fwd, dim3((s.W + 15) / 16, s.B * s.G), dim3(64), 0, st, in, (const double *)packed, out, s.G, s.Cq, s.H, s.W, s.orient);
+    if (forward && i->split) {
+        hipLaunchKernelGGL(i->mfwd, dim3((unsigned)p.fwd_grid_x), dim3(64 * i->split), 0, st, in, (const double *)packed, out, s.G, s.Cq, s.H, s.W, s.orient,
+                           (s.W + 15) / 16);
+    } else if (forward) {
+        hipLaunchKernelGGL(i->fwd, dim3((unsigned)p.fwd_grid_x, (unsigned)p.fwd_grid_y), dim3(64), 0, st, in, (const double *)packed, out, s.G, s.Cq,
+                           s.H, s.W, s.orient);
     } else {
-        const int P = s.W < 16 ? s.W : 16;
-        const int NB = (s.H + P - 1) / P;
-        const int DF = f64_fifo_depth(s.W, P, s.KH, s.KW);
-        const size_t per_wave = (size_t)i->lds_fixed + (size_t)DF * i->fslot;
-        int wpw = WPW;
-        while (wpw > 1 && per_wave * wpw > 160 * 1024) wpw >>= 1;
-        const size_t lds = per_wave * wpw;
-        if (int e = finc_ensure_dynamic_lds((const void *)i->inv, lds)) return e;
-        hipLaunchKernelGGL(i->inv, dim3((s.B * s.G + wpw - 1) / wpw), dim3(64 * wpw), lds, st, in, (const double *)packed, out, s.G, s.Cq, s.H, s.W, P,
-                           NB * s.W + P - 1, s.orient, DF, s.B * s.G, wpw);
+        const int NB = (s.H + p.P - 1) / p.P;
+        if (int e = finc_ensure_dynamic_lds((const void *)i->inv, (size_t)p.lds)) return e;
+        hipLaunchKernelGGL(i->inv, dim3((unsigned)p.inv_grid), dim3(64 * p.waves * p.ppw), (size_t)p.lds, st, in, (const double *)packed, out, s.G,
+                           s.Cq, s.H, s.W, p.P, NB * s.W + p.P - 1, s.orient, p.DF, s.B * s.G, p.ppw);
     }
     FINC_CHECK_LAUNCH();
     return FINC_OK;

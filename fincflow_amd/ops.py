@@ -270,7 +270,8 @@ def _run(fn_name, act, w_canon, G, orient, algo, out):
     run = (act.data_ptr(), w_canon.data_ptr(), out.data_ptr(), B, G, Cq, H, W, KH, KW, orient)
     if dt == torch.float64:
         # strict: the reference-order fp64 kernels (bit-exact with the reference's Cython solver; no packed form, no workspace);
-        # auto / mfma: the matrix-core form where the bank has one (finc_f64.hip: Cq <= 24 at 3x3, <= 32 at 2x2), else strict
+        # auto / mfma: the matrix-core form where the bank has one (finc_f64.hip: Cq <= 24 at 3x3, <= 32 at 2x2 on one wave per
+        # problem, 29 .. 64 at 3x3 and 33 .. 64 at 2x2 split over a workgroup's waves), else strict
         fn64 = fn_name.replace("_f32", "_f64")
         if algo == "strict":
             _call(fn64, act.device, *run, _stream_ptr(act))

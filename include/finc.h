@@ -253,7 +253,10 @@ int finc_forward_f64(const double *x, const double *w_canon, double *z, int B, i
  * The same two calls with an algorithm choice (round 5): FINC_ALGO_STRICT = the reference-order kernels above; FINC_ALGO_AUTO /
  * FINC_ALGO_MFMA = the double-precision matrix-core form (finc_f64.hip: v_mfma_f64_16x16x4_f64, one wavefront per (image, group),
  * the reference's anti-diagonal visitation band by band, the in-pixel substitution folded into the bank in fp64) for the banks that
- * have one -- Cq <= 24 at 3x3 (configs[1], configs[2]), Cq <= 32 at 2x2; results within 1e-12 of the reference-order solve, not
+ * have one -- Cq <= 24 at 3x3 (configs[1], configs[2]), Cq <= 32 at 2x2, and since version 112 the wider banks of 29 .. 64 channels
+ * at 3x3 and 33 .. 64 at 2x2 on a second family that splits a problem's 16-row output tiles over the waves of a workgroup (one
+ * barrier per step; finc_debug_f64_plan says which family a shape takes; 25 .. 28 channels at 3x3, more than 64, 5x5 and non-square
+ * filters have none); results within 1e-12 of the reference-order solve, not
  * bit-equal to it (the order in which a pixel's terms are added differs).  AUTO falls back to the reference-order kernel for any
  * other shape or when `workspace` is NULL / smaller than finc_f64_workspace_bytes(); MFMA reports FINC_ERR_UNSUPPORTED /
  * FINC_ERR_WORKSPACE instead.  The workspace (8-byte aligned) holds the packed bank; the call packs and launches on `stream`.
@@ -271,9 +274,9 @@ int finc_forward_f64_algo(const double *x, const double *w_canon, double *z, int
  * be NULL to skip it, not both; `x` is read for grad_w_canon only and `w_canon` for grad_x only (each may be NULL without its output);
  * grad_x may not be grad_z.
  * With a `workspace` of finc_backward_f64_workspace_bytes() bytes (8-byte aligned) the banks of finc_forward_f64_algo's matrix-core
- * form (Cq <= 24 at 3x3, <= 32 at 2x2, on the maps that form takes) run both gradients on v_mfma_f64_16x16x4_f64: grad_x is the
+ * form (Cq <= 24 at 3x3, <= 32 at 2x2, 29 .. 64 at 3x3 and 33 .. 64 at 2x2 on the M-split family, on the maps that form takes) run both gradients on v_mfma_f64_16x16x4_f64: grad_x is the
  * forward kernel on the bank packed transposed, every group's orientation complemented; grad_w has the pixels on the MFMA K dimension,
- * one wavefront per (image, group, row chunk), partial tiles in the workspace and a reduce that adds them in index order (no atomics:
+ * one wavefront per (image, group, row chunk) -- and per 16-row output tile on the M-split family --, partial tiles in the workspace and a reduce that adds them in index order (no atomics:
  * the same inputs give the same bits).  Every other shape, and any call whose workspace is NULL, off an 8-byte boundary or too small,
  * runs the direct kernels (one output per thread; grad_w: filters of at most 49 taps, FINC_ERR_UNSUPPORTED beyond, as in
  * finc_backward_f32 -- grad_x is available for every filter).  Results are within 1e-12 of an fp64 autograd of the same convolution.
@@ -520,6 +523,14 @@ int finc_debug_gradw_plan(int B, int G, int Cq, int H, int W, int KH, int KW, in
  * Forms 3 and 7 have no row chunks and report nrc = 1, RC = H.  Each kernel's chunk arithmetic lives in one host function that its
  * launch and this query both call.  FINC_ERR_UNSUPPORTED: the direct kernel.  Host-only. */
 int finc_debug_conv_plan(int B, int G, int Cq, int H, int W, int KH, int KW, int align, int *info);
+/* What a float64 call on this shape launches, from the plan object the launchers themselves read (finc_f64.hip): info[11] = {family
+ * (0: no matrix-core kernel -- the reference-order and direct kernels run, everything else 0 too; 1: one wave per problem, Cq <= 24
+ * at 3x3 and <= 32 at 2x2; 2: the M-split over a workgroup's waves, 29 .. 64 channels at 3x3 and 33 .. 64 at 2x2), the padded bank
+ * CQP, waves per problem and problems per workgroup of the inverse, its LDS bytes per workgroup (fixed part + FIFO slots x slot bytes)
+ * and grid.x, grid.x and grid.y of the forward / grad-input, grid.x of the grad-weight, its row chunks per slab and rows per chunk}.
+ * The workgroups of the forward and the grad-weight have one wave in family 1 and one per 16-row output tile (= waves per problem)
+ * in family 2.  Host-only.  (The reference dispatches double for any shape on one kernel, cinc_cuda_kernel_level2.cu:117.) */
+int finc_debug_f64_plan(int B, int G, int Cq, int H, int W, int KH, int KW, int *info);
 int finc_debug_inverse_table_row(int row, int *info);
 int finc_debug_attr_table_insert(int device, size_t kernel_token);
 /* SYNCHRONOUS.  The helper-wave form of the inverse (form 3 of finc_inverse_kernel_variant) pairs each compute wave with a
