@@ -42,6 +42,9 @@ SYMBOLS = [
     "finc_actnorm_backward_reconstruct_f32", "finc_coupling_backward_reconstruct_f32",
     "finc_backward_f64_workspace_bytes", "finc_backward_f64", "finc_check_invariant_f64",
     "finc_debug_f64_plan",
+    "finc_coupling_rawbf16_f32", "finc_coupling_backward_rawbf16_f32", "finc_coupling_reverse_backward_rawbf16_f32",
+    "finc_coupling_reverse_logdet_rawbf16_f32", "finc_coupling_reverse_logdet_backward_rawbf16_f32",
+    "finc_coupling_backward_reconstruct_rawbf16_f32", "finc_bias_relu_bf16",
 ]
 
 #: the ABI version this binding is written against (include/finc.h: finc_version)
@@ -67,6 +70,9 @@ F64_BACKWARD_ABI_VERSION = 111
 #: the version that added the float64 matrix-core kernels of the wider banks (29 .. 64 channels at 3x3, 33 .. 64 at 2x2: the M-split
 #: family of finc_f64.hip) and the plan query that says which family a shape takes (finc_debug_f64_plan)
 F64_WIDE_BANKS_ABI_VERSION = 112
+#: the version that added the coupling's entry points on a bfloat16 `raw` / `grad_raw` (the six finc_coupling_*_rawbf16_f32) and
+#: finc_bias_relu_bf16: what a Coupling launches under torch.autocast(device_type="cuda", dtype=torch.bfloat16)
+AUTOCAST_ABI_VERSION = 113
 
 _lib = None
 
@@ -124,6 +130,10 @@ def lib():
     if have < F64_WIDE_BANKS_ABI_VERSION:
         raise FincError(f"{LIB_PATH} reports finc_version() = {have}, the float64 matrix-core kernels of the 29 .. 64 channel banks "
                         f"and their plan query (finc_debug_f64_plan) came with {F64_WIDE_BANKS_ABI_VERSION}: rebuild it "
+                        "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
+    if have < AUTOCAST_ABI_VERSION:
+        raise FincError(f"{LIB_PATH} reports finc_version() = {have}, the coupling's bfloat16 entry points (finc_coupling_rawbf16_f32 "
+                        f"and its five siblings, finc_bias_relu_bf16) came with {AUTOCAST_ABI_VERSION}: rebuild it "
                         "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
     L.finc_build_flags.restype = u
     L.finc_clear_fault.restype = i
@@ -209,6 +219,10 @@ def lib():
     L.finc_coupling_reverse_logdet_backward_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp]
     L.finc_actnorm_backward_reconstruct_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp]
     L.finc_coupling_backward_reconstruct_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp]
+    for name in ("finc_coupling", "finc_coupling_backward", "finc_coupling_reverse_backward", "finc_coupling_reverse_logdet",
+                 "finc_coupling_reverse_logdet_backward", "finc_coupling_backward_reconstruct"):
+        getattr(L, name + "_rawbf16_f32").argtypes = getattr(L, name + "_f32").argtypes       # (pointers are void * here)
+    L.finc_bias_relu_bf16.argtypes = L.finc_bias_relu_f32.argtypes
     for name in SYMBOLS:
         getattr(L, name)  # AttributeError here = header and library out of sync
     _lib = L

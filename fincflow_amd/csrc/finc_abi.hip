@@ -190,7 +190,7 @@ static int canonicalize(const T *w_stored, T *w_canon, int G, int Cq, int KH, in
 
 extern "C" {
 
-int finc_version(void) { return 112; }
+int finc_version(void) { return 113; }
 
 unsigned finc_build_flags(void)
 {
@@ -611,40 +611,91 @@ size_t finc_coupling_workspace_bytes(int B, int C, int HW)
     return padded_ws_bytes(finc_coupling_workspace_floats(B, C, HW) * sizeof(float));
 }
 
+// The coupling's entry points come in two families of one ladder each, and each ladder in two raw element types: float (the _f32
+// names) and bf16 given as its bits (the _rawbf16_f32 names: what a net under bf16 autocast hands over).  A bf16 pointer is held to
+// its 2 bytes, every other pointer to 4 as always.
+static int coupling_launch(const float *x, const float *raw, const float *a, const float *b, float *y, float *logdet, int B, int C, int HW,
+                           int direction, float *ws, hipStream_t st)
+{
+    return finc_coupling_launch(x, raw, a, b, y, logdet, B, C, HW, direction, ws, st);
+}
+static int coupling_launch(const float *x, const uint16_t *raw, const float *a, const float *b, float *y, float *logdet, int B, int C, int HW,
+                           int direction, float *ws, hipStream_t st)
+{
+    return finc_coupling_rawbf16_launch(x, raw, a, b, y, logdet, B, C, HW, direction, ws, st);
+}
+static int coupling_grad_launch(FincGradMode mode, const float *gy, const float *gld, const float *v, const float *raw, const float *a,
+                                const float *b, float *xo, float *gx, float *graw, float *ga, float *gb, int B, int C, int HW, float *ws,
+                                hipStream_t st)
+{
+    return finc_coupling_grad_launch(mode, gy, gld, v, raw, a, b, xo, gx, graw, ga, gb, B, C, HW, ws, st);
+}
+static int coupling_grad_launch(FincGradMode mode, const float *gy, const float *gld, const float *v, const uint16_t *raw, const float *a,
+                                const float *b, float *xo, float *gx, uint16_t *graw, float *ga, float *gb, int B, int C, int HW, float *ws,
+                                hipStream_t st)
+{
+    return finc_coupling_rawbf16_grad_launch(mode, gy, gld, v, raw, a, b, xo, gx, graw, ga, gb, B, C, HW, ws, st);
+}
+extern "C++" {
+template <typename R, typename... P>
+static bool raw_misaligned(const P *...p) { return off_boundary(sizeof(R) - 1, p...); }
+
+// The transform in either direction.  `with_logdet`: the entry point that always reports the log-det (logdet must be there, and so
+// must the workspace); otherwise logdet is optional and belongs to direction +1.
+template <typename R>
+static int coupling_transform(const float *x, const R *raw, const float *a, const float *b, float *y, float *logdet, int B, int C, int HW,
+                              int direction, bool with_logdet, void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    if (!x || !raw || !a || !b || !y || (with_logdet && !logdet)) return FINC_ERR_NULL_POINTER;
+    if (int e = pixel_dims(B, C, HW, true)) return e;
+    if (direction != 1 && direction != -1) return FINC_ERR_BAD_DIMS;
+    if ((const void *)y == (const void *)raw) return FINC_ERR_BAD_DIMS;
+    if (misaligned(x, a, b, y, logdet) || raw_misaligned<R>(raw)) return FINC_ERR_ALIGNMENT;
+    if (!finc_coupling_supported_f32(C)) return FINC_ERR_UNSUPPORTED;
+    const bool sums = with_logdet || (direction > 0 && logdet);
+    if (sums && workspace_short(workspace, workspace_bytes, finc_coupling_workspace_bytes(B, C, HW))) return FINC_ERR_WORKSPACE;
+    if (int e = finc_fault_gate(false)) return e;
+    return coupling_launch(x, raw, a, b, y, sums ? logdet : nullptr, B, C, HW, direction, (float *)workspace, (hipStream_t)stream);
+}
+
+} // extern "C++"
+
 int finc_coupling_f32(const float *x, const float *raw, const float *a, const float *b, float *y, float *logdet, int B, int C, int HW,
                       int direction, void *workspace, size_t workspace_bytes, finc_stream_t stream)
 {
-    if (!x || !raw || !a || !b || !y) return FINC_ERR_NULL_POINTER;
-    if (int e = pixel_dims(B, C, HW, true)) return e;
-    if (direction != 1 && direction != -1) return FINC_ERR_BAD_DIMS;
-    if (y == raw) return FINC_ERR_BAD_DIMS;
-    if (misaligned(x, raw, a, b, y, logdet)) return FINC_ERR_ALIGNMENT;
-    if (!finc_coupling_supported_f32(C)) return FINC_ERR_UNSUPPORTED;
-    const bool sums = direction > 0 && logdet;
-    if (sums && workspace_short(workspace, workspace_bytes, finc_coupling_workspace_bytes(B, C, HW))) return FINC_ERR_WORKSPACE;
-    if (int e = finc_fault_gate(false)) return e;
-    return finc_coupling_launch(x, raw, a, b, y, sums ? logdet : nullptr, B, C, HW, direction, (float *)workspace, (hipStream_t)stream);
+    return coupling_transform(x, raw, a, b, y, logdet, B, C, HW, direction, false, workspace, workspace_bytes, stream);
+}
+
+int finc_coupling_rawbf16_f32(const float *x, const uint16_t *raw, const float *a, const float *b, float *y, float *logdet, int B, int C,
+                              int HW, int direction, void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    return coupling_transform(x, raw, a, b, y, logdet, B, C, HW, direction, false, workspace, workspace_bytes, stream);
 }
 
 // Every backward of the coupling: `v` is the activation the mode reads (FincGradMode), x_out the rebuilt input of FINC_GRAD_REBUILD
 // alone, which also allows grad_x == grad_y (and x_out == v); no other output may be an input or another output.
-static int coupling_grad(FincGradMode mode, const float *grad_y, const float *grad_logdet, const float *v, const float *raw, const float *a,
-                         const float *b, float *x_out, float *grad_x, float *grad_raw, float *grad_a, float *grad_b, int B, int C, int HW,
+extern "C++" {
+template <typename R>
+static int coupling_grad(FincGradMode mode, const float *grad_y, const float *grad_logdet, const float *v, const R *raw, const float *a,
+                         const float *b, float *x_out, float *grad_x, R *grad_raw, float *grad_a, float *grad_b, int B, int C, int HW,
                          void *workspace, size_t workspace_bytes, finc_stream_t stream)
 {
+    const void *r = raw, *gr = grad_raw;
     if (!grad_y || !v || !raw || !a || !b || (!x_out && !grad_x && !grad_raw && !grad_a && !grad_b)) return FINC_ERR_NULL_POINTER;
     if (int e = pixel_dims(B, C, HW, true)) return e;
-    if (x_out && (x_out == grad_y || x_out == raw || x_out == grad_x || x_out == grad_raw)) return FINC_ERR_BAD_DIMS;
-    if (grad_x && ((grad_x == grad_y && mode != FINC_GRAD_REBUILD) || grad_x == v || grad_x == raw)) return FINC_ERR_BAD_DIMS;
-    if (grad_raw && (grad_raw == grad_y || grad_raw == v || grad_raw == raw || grad_raw == grad_x)) return FINC_ERR_BAD_DIMS;
-    if (misaligned(grad_y, grad_logdet, v, raw, a, b, x_out, grad_x, grad_raw, grad_a, grad_b)) return FINC_ERR_ALIGNMENT;
+    if (x_out && (x_out == grad_y || x_out == r || x_out == grad_x || x_out == gr)) return FINC_ERR_BAD_DIMS;
+    if (grad_x && ((grad_x == grad_y && mode != FINC_GRAD_REBUILD) || grad_x == v || grad_x == r)) return FINC_ERR_BAD_DIMS;
+    if (grad_raw && (gr == grad_y || gr == v || gr == r || gr == grad_x)) return FINC_ERR_BAD_DIMS;
+    if (misaligned(grad_y, grad_logdet, v, a, b, x_out, grad_x, grad_a, grad_b) || raw_misaligned<R>(raw, grad_raw)) return FINC_ERR_ALIGNMENT;
     if (!finc_coupling_supported_f32(C)) return FINC_ERR_UNSUPPORTED;
     if ((grad_a || grad_b) && workspace_short(workspace, workspace_bytes, finc_coupling_workspace_bytes(B, C, HW)))
         return FINC_ERR_WORKSPACE;
     if (int e = finc_fault_gate(false)) return e;
-    return finc_coupling_grad_launch(mode, grad_y, grad_logdet, v, raw, a, b, x_out, grad_x, grad_raw, grad_a, grad_b, B, C, HW,
-                                     (float *)workspace, (hipStream_t)stream);
+    return coupling_grad_launch(mode, grad_y, grad_logdet, v, raw, a, b, x_out, grad_x, grad_raw, grad_a, grad_b, B, C, HW,
+                                (float *)workspace, (hipStream_t)stream);
 }
+
+} // extern "C++"
 
 int finc_coupling_backward_f32(const float *grad_y, const float *grad_logdet, const float *x, const float *raw, const float *a,
                                const float *b, float *grad_x, float *grad_raw, float *grad_a, float *grad_b, int B, int C, int HW,
@@ -665,14 +716,7 @@ int finc_coupling_reverse_backward_f32(const float *grad_y, const float *y, cons
 int finc_coupling_reverse_logdet_f32(const float *x, const float *raw, const float *a, const float *b, float *y, float *logdet, int B,
                                      int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream)
 {
-    if (!x || !raw || !a || !b || !y || !logdet) return FINC_ERR_NULL_POINTER;
-    if (int e = pixel_dims(B, C, HW, true)) return e;
-    if (y == raw) return FINC_ERR_BAD_DIMS;
-    if (misaligned(x, raw, a, b, y, logdet)) return FINC_ERR_ALIGNMENT;
-    if (!finc_coupling_supported_f32(C)) return FINC_ERR_UNSUPPORTED;
-    if (workspace_short(workspace, workspace_bytes, finc_coupling_workspace_bytes(B, C, HW))) return FINC_ERR_WORKSPACE;
-    if (int e = finc_fault_gate(false)) return e;
-    return finc_coupling_launch(x, raw, a, b, y, logdet, B, C, HW, -1, (float *)workspace, (hipStream_t)stream);
+    return coupling_transform(x, raw, a, b, y, logdet, B, C, HW, -1, true, workspace, workspace_bytes, stream);
 }
 
 int finc_coupling_reverse_logdet_backward_f32(const float *grad_y, const float *grad_logdet, const float *y, const float *raw,
@@ -692,13 +736,71 @@ int finc_coupling_backward_reconstruct_f32(const float *grad_y, const float *gra
                          workspace_bytes, stream);
 }
 
-int finc_bias_relu_f32(const float *in, const float *bias, float *out, int B, int C, int HW, finc_stream_t stream)
+int finc_coupling_backward_rawbf16_f32(const float *grad_y, const float *grad_logdet, const float *x, const uint16_t *raw, const float *a,
+                                       const float *b, float *grad_x, uint16_t *grad_raw, float *grad_a, float *grad_b, int B, int C, int HW,
+                                       void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    return coupling_grad(FINC_GRAD_FWD, grad_y, grad_logdet, x, raw, a, b, nullptr, grad_x, grad_raw, grad_a, grad_b, B, C, HW, workspace,
+                         workspace_bytes, stream);
+}
+
+int finc_coupling_reverse_backward_rawbf16_f32(const float *grad_y, const float *y, const uint16_t *raw, const float *a, const float *b,
+                                               float *grad_x, uint16_t *grad_raw, float *grad_a, float *grad_b, int B, int C, int HW,
+                                               void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    return finc_coupling_reverse_logdet_backward_rawbf16_f32(grad_y, nullptr, y, raw, a, b, grad_x, grad_raw, grad_a, grad_b, B, C, HW,
+                                                             workspace, workspace_bytes, stream);
+}
+
+int finc_coupling_reverse_logdet_rawbf16_f32(const float *x, const uint16_t *raw, const float *a, const float *b, float *y, float *logdet,
+                                             int B, int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    return coupling_transform(x, raw, a, b, y, logdet, B, C, HW, -1, true, workspace, workspace_bytes, stream);
+}
+
+int finc_coupling_reverse_logdet_backward_rawbf16_f32(const float *grad_y, const float *grad_logdet, const float *y, const uint16_t *raw,
+                                                      const float *a, const float *b, float *grad_x, uint16_t *grad_raw, float *grad_a,
+                                                      float *grad_b, int B, int C, int HW, void *workspace, size_t workspace_bytes,
+                                                      finc_stream_t stream)
+{
+    return coupling_grad(FINC_GRAD_REV, grad_y, grad_logdet, y, raw, a, b, nullptr, grad_x, grad_raw, grad_a, grad_b, B, C, HW, workspace,
+                         workspace_bytes, stream);
+}
+
+int finc_coupling_backward_reconstruct_rawbf16_f32(const float *grad_y, const float *grad_logdet, const float *y, const uint16_t *raw,
+                                                   const float *a, const float *b, float *x_out, float *grad_x, uint16_t *grad_raw,
+                                                   float *grad_a, float *grad_b, int B, int C, int HW, void *workspace,
+                                                   size_t workspace_bytes, finc_stream_t stream)
+{
+    return coupling_grad(FINC_GRAD_REBUILD, grad_y, grad_logdet, y, raw, a, b, x_out, grad_x, grad_raw, grad_a, grad_b, B, C, HW, workspace,
+                         workspace_bytes, stream);
+}
+
+// bias + ReLU on fp32 or on bf16 bits (the bias is fp32 in both): one ladder
+extern "C++" {
+template <typename T>
+static int bias_relu(const T *in, const float *bias, T *out, int B, int C, int HW, finc_stream_t stream)
 {
     if (!in || !bias || !out) return FINC_ERR_NULL_POINTER;
     if (int e = pixel_dims(B, C, HW, false)) return e;
-    if (misaligned(in, bias, out)) return FINC_ERR_ALIGNMENT;
+    if (misaligned(bias) || raw_misaligned<T>(in, out)) return FINC_ERR_ALIGNMENT;
     if (int e = finc_fault_gate(false)) return e;
-    return finc_bias_relu_launch(in, bias, out, B, C, HW, (hipStream_t)stream);
+    if constexpr (sizeof(T) == 2)
+        return finc_bias_relu_bf16_launch(in, bias, out, B, C, HW, (hipStream_t)stream);
+    else
+        return finc_bias_relu_launch(in, bias, out, B, C, HW, (hipStream_t)stream);
+}
+
+} // extern "C++"
+
+int finc_bias_relu_f32(const float *in, const float *bias, float *out, int B, int C, int HW, finc_stream_t stream)
+{
+    return bias_relu(in, bias, out, B, C, HW, stream);
+}
+
+int finc_bias_relu_bf16(const uint16_t *in, const float *bias, uint16_t *out, int B, int C, int HW, finc_stream_t stream)
+{
+    return bias_relu(in, bias, out, B, C, HW, stream);
 }
 
 size_t finc_actnorm_workspace_bytes(int B, int C, int HW)

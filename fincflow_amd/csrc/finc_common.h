@@ -314,6 +314,14 @@ int finc_coupling_grad_launch(FincGradMode mode, const float *gy, const float *g
                               const float *b, float *xo, float *gx, float *graw, float *ga, float *gb, int B, int C, int HW, float *ws,
                               hipStream_t st);
 int finc_bias_relu_launch(const float *in, const float *bias, float *out, int B, int C, int HW, hipStream_t st);
+// The same three on bf16 tensors, given as their bits: raw and graw of the coupling (everything else stays fp32), in and out of the
+// bias + ReLU (the bias stays fp32).  The wide forms want the bf16 pointers on 8 bytes (coupling) or 16 (bias + ReLU).
+int finc_coupling_rawbf16_launch(const float *x, const uint16_t *raw, const float *a, const float *b, float *y, float *logdet, int B, int C,
+                                 int HW, int direction, float *ws, hipStream_t st);
+int finc_coupling_rawbf16_grad_launch(FincGradMode mode, const float *gy, const float *gld, const float *v, const uint16_t *raw,
+                                      const float *a, const float *b, float *xo, float *gx, uint16_t *graw, float *ga, float *gb, int B,
+                                      int C, int HW, float *ws, hipStream_t st);
+int finc_bias_relu_bf16_launch(const uint16_t *in, const float *bias, uint16_t *out, int B, int C, int HW, hipStream_t st);
 // ---- ActNorm (transform + log-det, its backward from the forward's OUTPUT, the data-dependent initialisation): finc_actnorm.h, same object ----
 // `ws` holds finc_actnorm_workspace_floats floats (backward with gls / gt, and the initialisation)
 size_t finc_actnorm_workspace_floats(int B, int C, int HW);

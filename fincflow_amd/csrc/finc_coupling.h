@@ -18,6 +18,12 @@
 // Layout: x, y [B][C][HW] fp32, raw [B][C][HW] with channel 2j = u_j (pre-activation of the log-scale) and 2j+1 = t_j (translation).
 // A thread owns V consecutive pixels of one channel pair j: V = 4 (16-byte pieces) when HW % 4 == 0 and every pointer is 16-byte
 // aligned, else V = 1 (dwords).  Every index is checked against the element count: nothing is read or written beyond a tensor.
+// The raw element type R is a parameter of the two bodies, float or __bf16 (a net that ran under bf16 autocast): a bf16 raw is read
+// as it lies (bf16 -> fp32 is a 16-bit shift, exact), 8-byte pieces in the wide form -- which then also needs raw and grad_raw on
+// 8 bytes -- and 2-byte elements in the narrow one; grad_raw is written in R, rounded to nearest even once, behind the fp32 sums.
+// Everything else -- x, y, the gradients of x, a, b, the log-det, the partials -- is fp32 in both, and the arithmetic is the same
+// lines: a bf16 raw gives the bits of the fp32 call on the same values.  The *_rawbf16_* kernels and finc_bias_relu_bf16_kernel
+// (bf16 in and out, fp32 bias and arithmetic, 16-byte pieces of 8) have names of their own: the fp32 kernels stay the ones they were.
 // Sums (log-det per image; grad_a, grad_b per channel) never use atomics: each workgroup reduces its share in a fixed order (wave
 // butterflies, then the four waves in LDS) and writes ONE partial to the workspace; finc_coupling_reduce_kernel adds the partials of
 // an output in a fixed order.  The same inputs give the same bits.
@@ -51,6 +57,46 @@ __device__ inline void cpl_store(float *p, const float (&d)[V])
     }
 }
 
+// bf16 elements travel as their bits (integer loads and stores of 2, 8 or 16 bytes: no 4-byte access ever touches a 2-byte element
+// on its own); up: the bits are the float's high half; down: the compiler's float -> __bf16 conversion, round to nearest even.
+typedef float cpl_v2f __attribute__((ext_vector_type(2)));
+typedef __bf16 cpl_v2h __attribute__((ext_vector_type(2)));
+__device__ inline void cpl_widen(float &lo, float &hi, unsigned w)
+{
+    lo = __uint_as_float(w << 16);
+    hi = __uint_as_float(w & 0xffff0000u);
+}
+__device__ inline unsigned cpl_narrow(float lo, float hi)
+{
+    cpl_v2f f;
+    f.x = lo; f.y = hi;
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(f, cpl_v2h));
+}
+template <int V>
+__device__ inline void cpl_load(float (&d)[V], const __bf16 *p)
+{
+    if constexpr (V == 8) {
+        const uint4 w = *reinterpret_cast<const uint4 *>(p);
+        cpl_widen(d[0], d[1], w.x); cpl_widen(d[2], d[3], w.y); cpl_widen(d[4], d[5], w.z); cpl_widen(d[6], d[7], w.w);
+    } else if constexpr (V == 4) {
+        const uint2 w = *reinterpret_cast<const uint2 *>(p);
+        cpl_widen(d[0], d[1], w.x); cpl_widen(d[2], d[3], w.y);
+    } else {
+        d[0] = __uint_as_float((unsigned)*reinterpret_cast<const unsigned short *>(p) << 16);
+    }
+}
+template <int V>
+__device__ inline void cpl_store(__bf16 *p, const float (&d)[V])
+{
+    if constexpr (V == 8) {
+        *reinterpret_cast<uint4 *>(p) = make_uint4(cpl_narrow(d[0], d[1]), cpl_narrow(d[2], d[3]), cpl_narrow(d[4], d[5]), cpl_narrow(d[6], d[7]));
+    } else if constexpr (V == 4) {
+        *reinterpret_cast<uint2 *>(p) = make_uint2(cpl_narrow(d[0], d[1]), cpl_narrow(d[2], d[3]));
+    } else {
+        *reinterpret_cast<unsigned short *>(p) = __builtin_bit_cast(unsigned short, (__bf16)d[0]);
+    }
+}
+
 // Sum of N values per thread over the 256 threads of a workgroup, in a fixed order; every thread returns with the totals in v[].
 template <int N>
 __device__ inline void cpl_block_sum(float (&v)[N], float (*sm)[4])
@@ -74,8 +120,8 @@ __device__ inline void cpl_block_sum(float (&v)[N], float (*sm)[4])
 // LOGDET: the workgroup's partial of sum s goes to part[blockIdx.x], in EITHER direction: what is summed is the FORWARD map's log-det,
 // sum_{j,p} s_j -- in the reverse direction that is the log-det of Coupling.forward at the recovered input y (s depends on the
 // untouched half only, which both directions share); the reverse map's own Jacobian is its negative.
-template <int V, int DIR, bool LOGDET>
-__device__ __forceinline__ void cpl_transform(const float *x, const float *__restrict__ raw, const float *__restrict__ a,
+template <int V, int DIR, bool LOGDET, typename R = float>
+__device__ __forceinline__ void cpl_transform(const float *x, const R *__restrict__ raw, const float *__restrict__ a,
                                               const float *__restrict__ b, float *y, float *__restrict__ part, int half, int HW, int nv,
                                               int items, int P)
 {
@@ -133,6 +179,16 @@ __global__ __launch_bounds__(CPL_THREADS) void finc_coupling_rev_logdet_kernel(c
     cpl_transform<V, -1, true>(x, raw, a, b, y, part, half, HW, nv, items, P);
 }
 
+// Either direction, with or without the partials, on a bf16 raw: the same body, R = __bf16.
+template <int V, int DIR, bool LOGDET>
+__global__ __launch_bounds__(CPL_THREADS) void finc_coupling_rawbf16_kernel(const float *x, const __bf16 *__restrict__ raw,
+                                                                            const float *__restrict__ a, const float *__restrict__ b,
+                                                                            float *y, float *__restrict__ part, int half, int HW, int nv,
+                                                                            int items, int P)
+{
+    cpl_transform<V, DIR, LOGDET, __bf16>(x, raw, a, b, y, part, half, HW, nv, items, P);
+}
+
 // Every backward of the coupling is ONE body, cpl_grad<V, MODE>; a mode (FincGradMode) is what it reads and the few lines of
 // arithmetic behind `if constexpr`:
 //   FINC_GRAD_FWD      of y2 = x2 * exp(s) + t, from `v` = the forward's INPUT x (layers/coupling.py:79-93).
@@ -150,11 +206,12 @@ __global__ __launch_bounds__(CPL_THREADS) void finc_coupling_rev_logdet_kernel(c
 // s and exp(s) are recomputed from raw (two transcendentals per element), not saved by the forward.
 // Workgroup = (channel pair j, part): Q parts per pair share its B * HW / V thread items, so the four per-channel sums of a
 // workgroup belong to ONE pair.  Partials: part[(4j + k) * Q + q], k = 0 grad_a[2j], 1 grad_b[2j], 2 grad_a[2j+1], 3 grad_b[2j+1].
-// gld (grad of the log-det, per image), xo, gx, graw may be nullptr; `sums` = 0 skips the partials.
-template <int V, int MODE>
-__device__ __forceinline__ void cpl_grad(const float *gy, const float *__restrict__ gld, const float *v, const float *__restrict__ raw,
+// gld (grad of the log-det, per image), xo, gx, graw may be nullptr; `sums` = 0 skips the partials.  R: the element type of raw and
+// of graw, which is rounded from the fp32 gu, gt behind the sums (the sums never see a rounded value).
+template <int V, int MODE, typename R = float>
+__device__ __forceinline__ void cpl_grad(const float *gy, const float *__restrict__ gld, const float *v, const R *__restrict__ raw,
                                          const float *__restrict__ a, const float *__restrict__ b, float *xo, float *gx,
-                                         float *__restrict__ graw, float *__restrict__ part, int half, int HW, int nv, int items, int Q,
+                                         R *__restrict__ graw, float *__restrict__ part, int half, int HW, int nv, int items, int Q,
                                          int sums)
 {
     constexpr bool REBUILD = MODE == FINC_GRAD_REBUILD;
@@ -259,6 +316,18 @@ __global__ __launch_bounds__(CPL_THREADS) void finc_coupling_recon_kernel(const 
     cpl_grad<V, FINC_GRAD_REBUILD>(gy, gld, y, raw, a, b, xo, gx, graw, part, half, HW, nv, items, Q, sums);
 }
 
+// The three modes on a bf16 raw (and a bf16 grad_raw): one kernel, the mode its parameter.  xo == v and gx == gy are the rebuild's.
+template <int V, int MODE>
+__global__ __launch_bounds__(CPL_THREADS) void finc_coupling_rawbf16_grad_kernel(const float *gy, const float *__restrict__ gld,
+                                                                                 const float *v, const __bf16 *__restrict__ raw,
+                                                                                 const float *__restrict__ a, const float *__restrict__ b,
+                                                                                 float *xo, float *gx, __bf16 *__restrict__ graw,
+                                                                                 float *__restrict__ part, int half, int HW, int nv,
+                                                                                 int items, int Q, int sums)
+{
+    cpl_grad<V, MODE, __bf16>(gy, gld, v, raw, a, b, xo, gx, graw, part, half, HW, nv, items, Q, sums);
+}
+
 // One wave per output: out = sum of its n consecutive partials, lane l takes l, l + 64, ... and the lanes meet in a butterfly.
 // pairs == 0: out_a[o] (the log-det of image o).  pairs == 1: output o = 4j + k goes to out_a / out_b as listed above; a nullptr
 // destination is neither summed nor written.
@@ -280,10 +349,10 @@ __global__ __launch_bounds__(64) void finc_coupling_reduce_kernel(const float *_
     if (threadIdx.x == 0) *dst = s;
 }
 
-// Thread item = V consecutive pixels of one (image, channel) row.  relu as torch.relu has it: a NaN stays a NaN.
-template <int V>
-__global__ __launch_bounds__(CPL_THREADS) void finc_bias_relu_kernel(const float *in, const float *__restrict__ bias, float *out, int C,
-                                                                     int HW, int nv, unsigned items)
+// Thread item = V consecutive pixels of one (image, channel) row.  relu as torch.relu has it: a NaN stays a NaN.  T: the element
+// type of in and out, float or __bf16 (the add and the max in fp32, rounded once).
+template <int V, typename T>
+__device__ __forceinline__ void cpl_bias_relu(const T *in, const float *__restrict__ bias, T *out, int C, int HW, int nv, unsigned items)
 {
     for (unsigned idx = blockIdx.x * CPL_THREADS + threadIdx.x; idx < items; idx += gridDim.x * CPL_THREADS) {
         const unsigned row = idx / (unsigned)nv, p = (idx - row * (unsigned)nv) * V;
@@ -298,6 +367,20 @@ __global__ __launch_bounds__(CPL_THREADS) void finc_bias_relu_kernel(const float
         }
         cpl_store<V>(out + o, v);
     }
+}
+
+template <int V>
+__global__ __launch_bounds__(CPL_THREADS) void finc_bias_relu_kernel(const float *in, const float *__restrict__ bias, float *out, int C,
+                                                                     int HW, int nv, unsigned items)
+{
+    cpl_bias_relu<V, float>(in, bias, out, C, HW, nv, items);
+}
+
+template <int V>
+__global__ __launch_bounds__(CPL_THREADS) void finc_bias_relu_bf16_kernel(const __bf16 *in, const float *__restrict__ bias, __bf16 *out,
+                                                                          int C, int HW, int nv, unsigned items)
+{
+    cpl_bias_relu<V, __bf16>(in, bias, out, C, HW, nv, items);
 }
 
 // workgroups that fill the chip at eight of these per compute unit
@@ -317,7 +400,9 @@ inline long long cpl_partials_bound(long long items, long long outer)
     const long long all = outer * ((items + CPL_THREADS - 1) / CPL_THREADS), cap = CPL_CHIP_WGS + outer;
     return all < cap ? all : cap;
 }
-inline bool cpl_wide(int HW, uintptr_t ptrs) { return HW % 4 == 0 && (ptrs & 15u) == 0; }
+// The wide form: HW in whole pieces, every fp32 activation pointer (`ptrs`) on 16 bytes and every bf16 one (`half_ptrs`: a bf16 raw
+// and grad_raw, whose piece of four pixels is 8 bytes) on 8.
+inline bool cpl_wide(int HW, uintptr_t ptrs, uintptr_t half_ptrs = 0) { return HW % 4 == 0 && (ptrs & 15u) == 0 && (half_ptrs & 7u) == 0; }
 inline bool cpl_rows_fit(int B, int C, int HW)          // a channel's B * HW / V items index as int with a full grid's stride beyond them
 {
     return (size_t)C * HW * 4 < ((size_t)1 << 31) && (long long)B * HW < (1LL << 31) - (CPL_CHIP_WGS + 1) * CPL_THREADS;
@@ -325,16 +410,17 @@ inline bool cpl_rows_fit(int B, int C, int HW)          // a channel's B * HW / 
 template <typename... P>
 inline uintptr_t cpl_bits(const P *...p) { return (... | (uintptr_t)p); }     // every pointer's address bits (nullptr adds none)
 // A backward launch: `outer` channel units (pairs, channels) share B * HW / V items each in Q parts, a workgroup per (unit, part).
-// `ptrs`: cpl_bits of every activation pointer the launch touches.  Q = 0: the rows do not fit (cpl_rows_fit).
+// `ptrs`: cpl_bits of every fp32 activation pointer the launch touches, `half_ptrs`: of every bf16 one.  Q = 0: the rows do not fit
+// (cpl_rows_fit).
 struct CplGradPlan {
     bool wide;
     int nv, items, Q;
     dim3 grid;
 };
-inline CplGradPlan cpl_grad_plan(int B, int C, int HW, int outer, uintptr_t ptrs)
+inline CplGradPlan cpl_grad_plan(int B, int C, int HW, int outer, uintptr_t ptrs, uintptr_t half_ptrs = 0)
 {
     if (!cpl_rows_fit(B, C, HW)) return CplGradPlan{false, 0, 0, 0, dim3(0)};
-    const bool wide = cpl_wide(HW, ptrs);
+    const bool wide = cpl_wide(HW, ptrs, half_ptrs);
     const int nv = HW / (wide ? 4 : 1), items = B * nv, Q = cpl_parts(items, outer);
     return CplGradPlan{wide, nv, items, Q, dim3((unsigned)((long long)outer * Q))};
 }
@@ -353,30 +439,36 @@ inline unsigned cpl_row_grid(long long items)           // grid-stride over rows
     return items >= (1LL << 32) - most * CPL_THREADS ? 0u : (unsigned)(wgs > most ? most : wgs);
 }
 
-} // namespace
-
-// floats: forward log-det partials (B images x P parts) and backward partials (4 sums x C/2 pairs x Q parts)
-size_t finc_coupling_workspace_floats(int B, int C, int HW)
+// The kernel of a transform / a backward for a raw element type: the fp32 ones under the names they have always had.
+template <typename R, int V, int DIR, bool LOGDET>
+constexpr auto cpl_transform_kernel()
 {
-    const long long half = C / 2, fwd = cpl_partials_bound(half * HW, B), bwd = 4 * cpl_partials_bound((long long)B * HW, half);
-    return (size_t)(fwd > bwd ? fwd : bwd);
+    if constexpr (sizeof(R) == 2) return finc_coupling_rawbf16_kernel<V, DIR, LOGDET>;
+    else if constexpr (DIR < 0 && LOGDET) return finc_coupling_rev_logdet_kernel<V>;
+    else return finc_coupling_kernel<V, DIR, LOGDET>;
 }
+// the address bits of raw-typed pointers that count towards the 16-byte rule (fp32) or the 8-byte rule (bf16)
+template <typename R, typename... P>
+inline uintptr_t cpl_bits16(const P *...p) { return sizeof(R) == 4 ? cpl_bits(p...) : 0; }
+template <typename R, typename... P>
+inline uintptr_t cpl_bits8(const P *...p) { return sizeof(R) == 2 ? cpl_bits(p...) : 0; }
 
 // logdet (either direction): the log-det of the FORWARD map, sum s per image -- in the reverse direction at the recovered input y
 // (B x P partials in `ws`, then the reduce); nullptr: none, and `ws` is not touched
-int finc_coupling_launch(const float *x, const float *raw, const float *a, const float *b, float *y, float *logdet, int B, int C, int HW,
-                         int direction, float *ws, hipStream_t st)
+template <typename R>
+int cpl_launch(const float *x, const R *raw, const float *a, const float *b, float *y, float *logdet, int B, int C, int HW, int direction,
+               float *ws, hipStream_t st)
 {
     const int half = C / 2;
     if ((size_t)C * HW * 4 >= ((size_t)1 << 31)) return FINC_ERR_BAD_DIMS;
-    const bool wide = cpl_wide(HW, cpl_bits(x, raw, y));
+    const bool wide = cpl_wide(HW, cpl_bits(x, y) | cpl_bits16<R>(raw), cpl_bits8<R>(raw));
     const int nv = HW / (wide ? 4 : 1), items = half * nv, P = cpl_parts(items, B);
     if ((long long)B * P >= (1LL << 31)) return FINC_ERR_BAD_DIMS;
     const dim3 grid((unsigned)((long long)B * P)), block(CPL_THREADS);
-    const auto kernel = !logdet ? (direction < 0 ? (wide ? finc_coupling_kernel<4, -1, false> : finc_coupling_kernel<1, -1, false>)
-                                                 : (wide ? finc_coupling_kernel<4, 1, false> : finc_coupling_kernel<1, 1, false>))
-                        : direction < 0 ? (wide ? finc_coupling_rev_logdet_kernel<4> : finc_coupling_rev_logdet_kernel<1>)
-                                        : (wide ? finc_coupling_kernel<4, 1, true> : finc_coupling_kernel<1, 1, true>);
+    const auto kernel = !logdet ? (direction < 0 ? (wide ? cpl_transform_kernel<R, 4, -1, false>() : cpl_transform_kernel<R, 1, -1, false>())
+                                                 : (wide ? cpl_transform_kernel<R, 4, 1, false>() : cpl_transform_kernel<R, 1, 1, false>()))
+                        : direction < 0 ? (wide ? cpl_transform_kernel<R, 4, -1, true>() : cpl_transform_kernel<R, 1, -1, true>())
+                                        : (wide ? cpl_transform_kernel<R, 4, 1, true>() : cpl_transform_kernel<R, 1, 1, true>());
     hipLaunchKernelGGL(kernel, grid, block, 0, st, x, raw, a, b, y, ws, half, HW, nv, items, P);
     FINC_CHECK_LAUNCH();
     if (logdet) {
@@ -386,36 +478,105 @@ int finc_coupling_launch(const float *x, const float *raw, const float *a, const
     return FINC_OK;
 }
 
-int finc_coupling_grad_launch(FincGradMode mode, const float *gy, const float *gld, const float *v, const float *raw, const float *a,
-                              const float *b, float *xo, float *gx, float *graw, float *ga, float *gb, int B, int C, int HW, float *ws,
-                              hipStream_t st)
+template <int V, int MODE>
+void cpl_grad_start(const CplGradPlan &p, hipStream_t st, const float *gy, const float *gld, const float *v, const float *raw, const float *a,
+                    const float *b, float *xo, float *gx, float *graw, float *ws, int half, int HW, int sums)
+{
+    if constexpr (MODE == FINC_GRAD_REBUILD)
+        hipLaunchKernelGGL(finc_coupling_recon_kernel<V>, p.grid, dim3(CPL_THREADS), 0, st, gy, gld, v, raw, a, b, xo, gx, graw, ws, half, HW,
+                           p.nv, p.items, p.Q, sums);
+    else
+        hipLaunchKernelGGL(MODE == FINC_GRAD_REV ? finc_coupling_rev_bwd_kernel<V> : finc_coupling_bwd_kernel<V>, p.grid, dim3(CPL_THREADS), 0,
+                           st, gy, gld, v, raw, a, b, gx, graw, ws, half, HW, p.nv, p.items, p.Q, sums);
+}
+template <int V, int MODE>
+void cpl_grad_start(const CplGradPlan &p, hipStream_t st, const float *gy, const float *gld, const float *v, const __bf16 *raw,
+                    const float *a, const float *b, float *xo, float *gx, __bf16 *graw, float *ws, int half, int HW, int sums)
+{
+    hipLaunchKernelGGL((finc_coupling_rawbf16_grad_kernel<V, MODE>), p.grid, dim3(CPL_THREADS), 0, st, gy, gld, v, raw, a, b, xo, gx, graw, ws,
+                       half, HW, p.nv, p.items, p.Q, sums);
+}
+
+template <typename R>
+int cpl_grad_launch(FincGradMode mode, const float *gy, const float *gld, const float *v, const R *raw, const float *a, const float *b,
+                    float *xo, float *gx, R *graw, float *ga, float *gb, int B, int C, int HW, float *ws, hipStream_t st)
 {
     const int half = C / 2, sums = (ga || gb) ? 1 : 0;
-    const CplGradPlan p = cpl_grad_plan(B, C, HW, half, cpl_bits(gy, v, raw, xo, gx, graw));
+    const CplGradPlan p = cpl_grad_plan(B, C, HW, half, cpl_bits(gy, v, xo, gx) | cpl_bits16<R>(raw, graw), cpl_bits8<R>(raw, graw));
     if (!p.Q) return FINC_ERR_BAD_DIMS;
+#define CPL_GRAD_START(V, MODE) cpl_grad_start<V, MODE>(p, st, gy, gld, v, raw, a, b, xo, gx, graw, ws, half, HW, sums)
     if (mode == FINC_GRAD_REBUILD) {
-        hipLaunchKernelGGL(p.wide ? finc_coupling_recon_kernel<4> : finc_coupling_recon_kernel<1>, p.grid, dim3(CPL_THREADS), 0, st, gy, gld, v,
-                           raw, a, b, xo, gx, graw, ws, half, HW, p.nv, p.items, p.Q, sums);
+        if (p.wide) CPL_GRAD_START(4, FINC_GRAD_REBUILD); else CPL_GRAD_START(1, FINC_GRAD_REBUILD);
+    } else if (mode == FINC_GRAD_REV) {
+        if (p.wide) CPL_GRAD_START(4, FINC_GRAD_REV); else CPL_GRAD_START(1, FINC_GRAD_REV);
     } else {
-        const auto kernel = mode == FINC_GRAD_REV ? (p.wide ? finc_coupling_rev_bwd_kernel<4> : finc_coupling_rev_bwd_kernel<1>)
-                                                  : (p.wide ? finc_coupling_bwd_kernel<4> : finc_coupling_bwd_kernel<1>);
-        hipLaunchKernelGGL(kernel, p.grid, dim3(CPL_THREADS), 0, st, gy, gld, v, raw, a, b, gx, graw, ws, half, HW, p.nv, p.items, p.Q, sums);
+        if (p.wide) CPL_GRAD_START(4, FINC_GRAD_FWD); else CPL_GRAD_START(1, FINC_GRAD_FWD);
     }
+#undef CPL_GRAD_START
     FINC_CHECK_LAUNCH();
     return cpl_reduce_pairs(sums, ws, 4 * half, p.Q, ga, gb, st);
 }
 
-int finc_bias_relu_launch(const float *in, const float *bias, float *out, int B, int C, int HW, hipStream_t st)
+} // namespace
+
+// floats: forward log-det partials (B images x P parts) and backward partials (4 sums x C/2 pairs x Q parts)
+size_t finc_coupling_workspace_floats(int B, int C, int HW)
 {
-    const bool wide = cpl_wide(HW, (uintptr_t)in | (uintptr_t)out);
-    const int nv = HW / (wide ? 4 : 1);
+    const long long half = C / 2, fwd = cpl_partials_bound(half * HW, B), bwd = 4 * cpl_partials_bound((long long)B * HW, half);
+    return (size_t)(fwd > bwd ? fwd : bwd);
+}
+
+int finc_coupling_launch(const float *x, const float *raw, const float *a, const float *b, float *y, float *logdet, int B, int C, int HW,
+                         int direction, float *ws, hipStream_t st)
+{
+    return cpl_launch<float>(x, raw, a, b, y, logdet, B, C, HW, direction, ws, st);
+}
+int finc_coupling_rawbf16_launch(const float *x, const uint16_t *raw, const float *a, const float *b, float *y, float *logdet, int B, int C,
+                                 int HW, int direction, float *ws, hipStream_t st)
+{
+    return cpl_launch<__bf16>(x, reinterpret_cast<const __bf16 *>(raw), a, b, y, logdet, B, C, HW, direction, ws, st);
+}
+
+int finc_coupling_grad_launch(FincGradMode mode, const float *gy, const float *gld, const float *v, const float *raw, const float *a,
+                              const float *b, float *xo, float *gx, float *graw, float *ga, float *gb, int B, int C, int HW, float *ws,
+                              hipStream_t st)
+{
+    return cpl_grad_launch<float>(mode, gy, gld, v, raw, a, b, xo, gx, graw, ga, gb, B, C, HW, ws, st);
+}
+int finc_coupling_rawbf16_grad_launch(FincGradMode mode, const float *gy, const float *gld, const float *v, const uint16_t *raw,
+                                      const float *a, const float *b, float *xo, float *gx, uint16_t *graw, float *ga, float *gb, int B,
+                                      int C, int HW, float *ws, hipStream_t st)
+{
+    return cpl_grad_launch<__bf16>(mode, gy, gld, v, reinterpret_cast<const __bf16 *>(raw), a, b, xo, gx, reinterpret_cast<__bf16 *>(graw), ga,
+                                   gb, B, C, HW, ws, st);
+}
+
+// fp32: 16-byte pieces of 4; bf16: 16-byte pieces of 8
+template <typename T>
+static int cpl_bias_relu_launch(const T *in, const float *bias, T *out, int B, int C, int HW, hipStream_t st)
+{
+    constexpr int V = 16 / (int)sizeof(T);
+    const bool wide = HW % V == 0 && (((uintptr_t)in | (uintptr_t)out) & 15u) == 0;
+    const int nv = HW / (wide ? V : 1);
     const long long items = (long long)B * C * nv;
     const unsigned wgs = cpl_row_grid(items);
     if (!wgs) return FINC_ERR_BAD_DIMS;
-    hipLaunchKernelGGL(wide ? finc_bias_relu_kernel<4> : finc_bias_relu_kernel<1>, dim3(wgs), dim3(CPL_THREADS), 0, st, in, bias, out, C, HW,
-                       nv, (unsigned)items);
+    if constexpr (sizeof(T) == 2)
+        hipLaunchKernelGGL(wide ? finc_bias_relu_bf16_kernel<8> : finc_bias_relu_bf16_kernel<1>, dim3(wgs), dim3(CPL_THREADS), 0, st, in, bias,
+                           out, C, HW, nv, (unsigned)items);
+    else
+        hipLaunchKernelGGL(wide ? finc_bias_relu_kernel<4> : finc_bias_relu_kernel<1>, dim3(wgs), dim3(CPL_THREADS), 0, st, in, bias, out, C, HW,
+                           nv, (unsigned)items);
     FINC_CHECK_LAUNCH();
     return FINC_OK;
+}
+int finc_bias_relu_launch(const float *in, const float *bias, float *out, int B, int C, int HW, hipStream_t st)
+{
+    return cpl_bias_relu_launch<float>(in, bias, out, B, C, HW, st);
+}
+int finc_bias_relu_bf16_launch(const uint16_t *in, const float *bias, uint16_t *out, int B, int C, int HW, hipStream_t st)
+{
+    return cpl_bias_relu_launch<__bf16>(reinterpret_cast<const __bf16 *>(in), bias, reinterpret_cast<__bf16 *>(out), B, C, HW, st);
 }
 
 #endif /* FINC_COUPLING_H */

@@ -35,6 +35,19 @@ from . import ops
 from .layers import FastFlowUnit, FlowLayer, FlowSequential, _hip_tensor, _param_needs, _params_on_device, _records_graph
 
 
+def _fp32_maps(x):
+    """The context in which a flow layer's own map runs its PyTorch lines: autocast off for the device of `x`.  The flow's maps stay
+    fp32 under autocast (invertibility and the log-det need it; only the coupling NET runs in the autocast dtype), and a convolution
+    left to autocast would hand bf16 to the next layer.  Outside autocast this changes nothing."""
+    return torch.autocast(x.device.type, enabled=False)
+
+
+def _autocast_dtype(x):
+    """The autocast dtype that is active for the device of `x`, or None."""
+    kind = x.device.type
+    return torch.get_autocast_dtype(kind) if torch.is_autocast_enabled(kind) else None
+
+
 class _DerivedValues:
     """A layer that keeps values derived from its parameters per parameter version (`ops.version_key`), each with its `ops.Ready`
     token: the stream it was built on and the event behind its fill, asked in front of every use.  A copy of the layer
@@ -200,7 +213,8 @@ class Conv1x1(_DerivedValues, FlowLayer):
     kernel: inference / sampling (no autograd graph) as one streaming launch (`ops.finc_mix`), `forward` under autograd through
     `ops.mix_forward` (backward: finc_mix_backward_f32), and so does `reverse` under autograd inside `ops.reverse_grad()` (what
     `FlowSequential.rsample` records), on `torch.inverse(W)` -- a recorded [C, C] op -- or, with W frozen, on the cached inverse.
-    Everything else -- CPU tensors, fp64, other channel counts, `reverse` under autograd outside that context -- keeps F.conv2d."""
+    Everything else -- CPU tensors, fp64, other channel counts, `reverse` under autograd outside that context -- keeps F.conv2d,
+    with autocast switched off around it: this layer is part of the flow's own map and stays fp32 under autocast."""
 
     _derived = ("_w_inv", "_inv_key", "_inv_ready", "_ld", "_ld_key", "_ld_ready", "_m_aff", "_b_aff", "_aff_key", "_aff_ready",
                 "_m_lead", "_b_lead", "_lead_key", "_lead_inv", "_lead_obj", "_lead_ready")
@@ -224,7 +238,8 @@ class Conv1x1(_DerivedValues, FlowLayer):
             return ops.finc_mix(x.contiguous(), self.W.detach().contiguous()), ldj
         if torch.is_grad_enabled() and self._hip_device(x):      # training: the same kernel under autograd
             return ops.mix_forward(x, self.W), ldj
-        return F.conv2d(x, self.W.view(self.n_channels, self.n_channels, 1, 1)), ldj
+        with _fp32_maps(x):
+            return F.conv2d(x, self.W.view(self.n_channels, self.n_channels, 1, 1)), ldj
 
     def _inverse_matrix(self):
         # the reference inverts W on every call (layers/conv1x1.py:37-39); cache it per weight version so that a
@@ -252,7 +267,8 @@ class Conv1x1(_DerivedValues, FlowLayer):
             w_inv = self._inverse_matrix()
         if self._hip_reverse_grad(z):
             return ops.mix_forward(z, w_inv)
-        return F.conv2d(z, w_inv.view(self.n_channels, self.n_channels, 1, 1))
+        with _fp32_maps(z):
+            return F.conv2d(z, w_inv.view(self.n_channels, self.n_channels, 1, 1))
 
     def invertible_backward_supported(self, x, context=None):
         return self._hip_device(x) and x.shape[1] == self.n_channels and _params_on_device(x, self.W)
@@ -364,7 +380,16 @@ class Coupling(_DerivedValues, FlowLayer):
     finc_coupling_backward_f32) and the net stays PyTorch; so does `reverse` under autograd inside `ops.reverse_grad()` (what
     `FlowSequential.rsample` records), through `ops.coupling_reverse` (backward: finc_coupling_reverse_backward_f32, from the saved
     OUTPUT).  Everything else -- CPU tensors, fp64, odd channel counts, `reverse` under autograd outside that context -- keeps the
-    PyTorch formula below."""
+    PyTorch formula below.
+
+    Under `torch.autocast(device_type="cuda", dtype=torch.bfloat16)` only the NET runs in bfloat16; x, y, the scale and shift and the
+    log-det stay fp32.  The net's bf16 output goes to the HIP transform as it lies (the `_rawbf16_f32` entry points: no cast of `raw`
+    in front, grad_raw written in bf16 for the net's backward), and the inference path's bias + ReLU runs in place on the bf16 hidden
+    tensor (finc_bias_relu_bf16).  The two paths round the hidden activations at different points there -- the recording path's
+    `Conv2d` adds its bf16 bias inside the convolution, the inference path adds the fp32 bias behind a bf16-rounded convolution -- so
+    `log_prob` with and without a graph differ at the bf16 level (1e-7 in fp32); each path is invertible in itself.  There are no
+    float16 kernels: under fp16 autocast the net runs as PyTorch has it and its output is upcast (`raw.float()`) for the fp32 entry
+    points.  The PyTorch formula lines upcast the net's output the same way, in front of the same h = a * raw + b."""
 
     _derived = ("_ab", "_ab_key", "_ab_ready")
 
@@ -400,7 +425,12 @@ class Coupling(_DerivedValues, FlowLayer):
 
     def _raw_train(self, x, context):
         n = self.net
-        return F.conv2d(n[:4](self._net_input(x, context)), n[4].weight, None, padding=1)
+        return self._kernel_raw(F.conv2d(n[:4](self._net_input(x, context)), n[4].weight, None, padding=1))
+
+    @staticmethod
+    def _kernel_raw(raw):
+        """`raw` as the transform takes it: fp32 and bfloat16 as they are; float16 (fp16 autocast has no kernels) upcast."""
+        return raw.float() if raw.dtype == torch.float16 else raw
 
     def _scale_shift(self):
         # h = a * raw + b with raw the last convolution WITHOUT its bias: Conv2dZero is (conv + bias) * exp(logs * factor)
@@ -431,6 +461,8 @@ class Coupling(_DerivedValues, FlowLayer):
     def _raw_inference(self, x, context):
         n = self.net
         with torch.no_grad():
+            if _autocast_dtype(x) == torch.float16 or ops.recorded_net_enabled():
+                return self._raw_train(x, context).contiguous()
             h = F.conv2d(self._net_input(x, context), n[0].weight, None, padding=1).contiguous()
             ops.finc_bias_relu(h, n[0].bias.detach(), out=h)
             h = F.conv2d(h, n[2].weight, None).contiguous()
@@ -440,7 +472,11 @@ class Coupling(_DerivedValues, FlowLayer):
     def _params(self, x, context):
         assert (context is not None) == self.uses_context
         x1, x2 = x[:, :self.half_channels], x[:, self.half_channels:]
-        h = self.net(x1 if context is None else torch.cat([x1, context], dim=1))
+        if _autocast_dtype(x) is None:
+            h = self.net(x1 if context is None else torch.cat([x1, context], dim=1))
+        else:                       # the net in the autocast dtype, its output upcast in front of h = a * raw + b (as on the HIP path)
+            a, b = self._scale_shift()
+            h = self._raw_train(x, context).to(x.dtype) * a.view(1, -1, 1, 1) + b.view(1, -1, 1, 1)
         log_s = 2.0 * torch.tanh(h[:, ::2] / 2.0)
         return x1, x2, log_s, h[:, 1::2]
 

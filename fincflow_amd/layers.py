@@ -445,11 +445,23 @@ class _InvertibleRunFunction(torch.autograd.Function):
     Forward: the no-grad pass of `FlowSequential.forward` over the run, folds included.  Saved: the run's OUTPUT and the context --
     nothing per layer.  Backward: the layers last to first, each rebuilding its input from its output and differentiating there; a
     rebuilt activation lives until the layer in front has consumed it.  The saved output is never written, so the backward can run
-    again under `retain_graph=True`."""
+    again under `retain_graph=True`.
+    Autocast: a backward runs outside the forward's autocast context, and a coupling's rebuilt input is only right if its net gives
+    `raw` the forward's bits.  So the autocast state of the forward (enabled, dtype) is kept and entered again around the backward, as
+    torch.utils.checkpoint does; and under autocast the forward runs its nets on the recording path (`ops.recorded_net`), the one the
+    backward differentiates.  Both passes run with autocast's weight cache off: a weight cast under no_grad (this forward) and cached
+    would be handed, without a graph, to the next recorded use inside the same autocast context -- the backward's, when it is called
+    there.  Outside autocast none of this changes a launch."""
 
     @staticmethod
     def forward(ctx, seq, run, x, context, *params):
-        out, logdet = seq._forward_layers(list(run), x, context, x.new_zeros(len(x)))
+        kind = x.device.type
+        ctx.autocast = (kind, torch.is_autocast_enabled(kind), torch.get_autocast_dtype(kind))
+        if ctx.autocast[1]:
+            with ops.recorded_net(), torch.autocast(kind, dtype=ctx.autocast[2], cache_enabled=False):
+                out, logdet = seq._forward_layers(list(run), x, context, x.new_zeros(len(x)))
+        else:
+            out, logdet = seq._forward_layers(list(run), x, context, x.new_zeros(len(x)))
         ctx.run = run
         ctx.counts = [len(list(m.parameters())) for m in run]
         ctx.save_for_backward(out, context)
@@ -463,11 +475,13 @@ class _InvertibleRunFunction(torch.autograd.Function):
         grad, gld = ops._incoming_grads(out, grad_out, grad_logdet)
         starts = [sum(ctx.counts[:k]) for k in range(len(ctx.run))]
         pgrads, gctx, y = [None] * len(need_p), None, out
+        kind, enabled, dtype = ctx.autocast
         for k in reversed(range(len(ctx.run))):
             upstream = need_x or need_ctx or any(need_p[:starts[k]])     # does anything in front of this layer want a gradient?
             needs = BackwardNeeds(input=k > 0 and upstream, grad_input=upstream, grad_context=need_ctx,
                                   params=tuple(need_p[starts[k]:starts[k] + ctx.counts[k]]))
-            y, grad, gc, pg = ctx.run[k].backward_from_output(y, grad, gld, context, needs)
+            with torch.autocast(kind, dtype=dtype, enabled=enabled, cache_enabled=False):
+                y, grad, gc, pg = ctx.run[k].backward_from_output(y, grad, gld, context, needs)
             pgrads[starts[k]:starts[k] + ctx.counts[k]] = pg
             if gc is not None:
                 gctx = gc if gctx is None else gctx + gc

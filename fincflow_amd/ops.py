@@ -41,6 +41,27 @@ def reverse_grad_enabled():
     return getattr(_reverse_grad, "depth", 0) > 0
 
 
+_recorded_net = threading.local()
+
+
+@contextlib.contextmanager
+def recorded_net():
+    """Inside this context a layer whose no-grad path computes its net in another way than its recording path does (glow.Coupling:
+    bias + ReLU fused behind bias-free convolutions) uses the recording path's arithmetic, without recording.  What
+    `FlowSequential.invertible_backward` enters around a run's forward under autocast: its backward rebuilds each input from the
+    output with the RECORDING path's net, and in a 16-bit dtype the two paths round at different points.  Per thread; nests."""
+    depth = getattr(_recorded_net, "depth", 0)
+    _recorded_net.depth = depth + 1
+    try:
+        yield
+    finally:
+        _recorded_net.depth = depth
+
+
+def recorded_net_enabled():
+    return getattr(_recorded_net, "depth", 0) > 0
+
+
 def _stream_ptr(t):
     return torch.cuda.current_stream(t.device).cuda_stream
 
@@ -401,9 +422,19 @@ def coupling_supported(C):
     return bool(_lib.lib().finc_coupling_supported_f32(int(C)))
 
 
+#: the element types of `raw` (the coupling net's output) that have kernels, and the suffix of their entry points: fp32, and
+#: bfloat16 for a net that ran under torch.autocast(device_type="cuda", dtype=torch.bfloat16).  Everything else stays fp32.
+_RAW_ENTRY = {torch.float32: "_f32", torch.bfloat16: "_rawbf16_f32"}
+
+
+def _coupling_entry(name, raw):
+    """`finc_coupling<name>` for the element type of `raw`."""
+    return "finc_coupling" + name + _RAW_ENTRY[raw.dtype]
+
+
 def _coupling_args(x, raw, a, b, what="input"):
     _require_device(x, what)
-    _require_device(raw, "raw")
+    _require_device(raw, "raw", raw.dtype if raw.dtype in _RAW_ENTRY else torch.float32)
     _require_device(a, "scale")
     _require_device(b, "shift")
     if x.dim() != 4 or raw.shape != x.shape or raw.device != x.device:
@@ -415,7 +446,9 @@ def _coupling_args(x, raw, a, b, what="input"):
 
 
 def _coupling_transform(entry, x, raw, a, b, direction, want_logdet, out):
-    """`finc_coupling_f32` (which takes the direction) or `finc_coupling_reverse_logdet_f32` behind their wrappers: (y, logdet)."""
+    """`finc_coupling_f32` (which takes the direction) or `finc_coupling_reverse_logdet_f32` behind their wrappers, or their
+    `_rawbf16_f32` siblings for a bfloat16 `raw` (`entry`: the name between "finc_coupling" and that suffix): (y, logdet), fp32."""
+    entry = _coupling_entry(entry, raw)
     out = _out_like(x, out)
     B, C, H, W = x.shape
     if x.numel() == 0:
@@ -431,18 +464,23 @@ def finc_coupling(x, raw, a, b, direction=1, want_logdet=False, out=None):
     """The affine coupling behind its net (layers/coupling.py:79-101) as one streaming HIP launch: with h = a * raw + b per channel,
     s = 2 tanh(h[:, ::2] / 2), t = h[:, 1::2]:  y = cat(x1, x2 * exp(s) + t) (direction +1) or cat(x1, (x2 - t) * exp(-s)) (-1).
     x, raw [B,C,H,W] fp32 contiguous on the device, C even; a, b [C].  Returns (y, logdet): logdet [B] = s summed per image when
-    `want_logdet` (forward direction; one more small launch, fixed-order sums), else None.  `out` may be `x`."""
+    `want_logdet` (forward direction; one more small launch, fixed-order sums), else None.  `out` may be `x`.
+    `raw` may also be bfloat16 (a net under bf16 autocast): it is read as it lies by finc_coupling_rawbf16_f32, no cast in front; x, a,
+    b, y and logdet stay fp32 and have the bits of the call on `raw.float()`.  The same holds for every coupling call below; the
+    backwards then return grad_raw in bfloat16 (the fp32 value rounded to nearest even once).  Any other dtype raises."""
     _coupling_args(x, raw, a, b)
     if direction not in (1, -1):
         raise ValueError("direction must be +1 (forward) or -1 (reverse)")
-    return _coupling_transform("finc_coupling_f32", x, raw, a, b, (direction,), bool(want_logdet) and direction == 1, out)
+    return _coupling_transform("", x, raw, a, b, (direction,), bool(want_logdet) and direction == 1, out)
 
 
 def _coupling_grads(entry, grad_y, grad_logdet, v, raw, a, b, what, whose, need_acts, need_sums):
     """One backward entry point of the coupling behind its wrapper: the checks, the outputs asked for -- `need_acts`: (x,) grad_x,
     grad_raw; `need_sums`: grad_a, grad_b -- the workspace and the call.  `v`: the activation that entry point reads, "input" or
-    "output" (`what`) of `whose` pass; grad_logdet: a tuple, empty for the entry point that takes none."""
+    "output" (`what`) of `whose` pass; grad_logdet: a tuple, empty for the entry point that takes none.  `entry`: the name between
+    "finc_coupling" and the suffix of `raw`'s element type; grad_raw is allocated like `raw` (bfloat16 for a bfloat16 `raw`)."""
     _coupling_args(v, raw, a, b, what)
+    entry = _coupling_entry(entry, raw)
     _require_device(grad_y, "grad_output")
     if grad_y.shape != v.shape or grad_y.device != v.device:
         raise ValueError(f"grad_output must match {whose} in shape and device")
@@ -450,7 +488,8 @@ def _coupling_grads(entry, grad_y, grad_logdet, v, raw, a, b, what, whose, need_
     for g in grad_logdet:
         _per_image(g, "grad_logdet", v)
     sums = tuple(torch.empty(C, dtype=torch.float32, device=v.device) if n else None for n in need_sums)
-    outs = tuple(torch.empty_like(v) if n else None for n in need_acts) + sums
+    acts = (v,) * (len(need_acts) - 1) + (raw,)                   # (x,) grad_x like the activations, grad_raw like raw
+    outs = tuple(torch.empty_like(t) if n else None for t, n in zip(acts, need_acts)) + sums
     if _nothing_to_launch(v, outs, sums):
         return outs
     nbytes = _lib.lib().finc_coupling_workspace_bytes(B, C, H * W) if any(need_sums) else None
@@ -464,7 +503,7 @@ def finc_coupling_backward(grad_y, grad_logdet, x, raw, a, b, need_gx=True, need
     [B,C,H,W] and grad_logdet [B] or None (zeros): (grad_x, grad_raw, grad_a, grad_b), each computed only if asked for (None
     otherwise).  grad_x[:, :C/2] is grad_y[:, :C/2]: what reaches that half through the net is the caller's (autograd's).  s and exp(s)
     are recomputed from `raw`; the per-channel sums run in a fixed order: the same inputs give the same bits."""
-    return _coupling_grads("finc_coupling_backward_f32", grad_y, (grad_logdet,), x, raw, a, b, "input", "input", (need_gx, need_graw),
+    return _coupling_grads("_backward", grad_y, (grad_logdet,), x, raw, a, b, "input", "input", (need_gx, need_graw),
                            (need_ga, need_gb))
 
 
@@ -473,7 +512,7 @@ def finc_coupling_reverse_backward(grad_y, y, raw, a, b, need_gx=True, need_graw
     and the reverse's OUTPUT `y`: (grad_x, grad_raw, grad_a, grad_b), each computed only if asked for (None otherwise).
     grad_x[:, :C/2] is grad_y[:, :C/2]: what reaches that half through the net is the caller's (autograd's).  tanh and exp(-s) are
     recomputed from `raw`; the per-channel sums run in a fixed order: the same inputs give the same bits."""
-    return _coupling_grads("finc_coupling_reverse_backward_f32", grad_y, (), y, raw, a, b, "output", "the reverse's output",
+    return _coupling_grads("_reverse_backward", grad_y, (), y, raw, a, b, "output", "the reverse's output",
                            (need_gx, need_graw), (need_ga, need_gb))
 
 
@@ -483,14 +522,14 @@ def finc_coupling_reverse_logdet(x, raw, a, b, out=None):
     finc_coupling_reverse_logdet_f32; the reverse map's own log-Jacobian is its negative).  Returns (y, logdet); `out` may be `x`.
     One more small launch for the fixed-order sums: the same inputs give the same bits."""
     _coupling_args(x, raw, a, b)
-    return _coupling_transform("finc_coupling_reverse_logdet_f32", x, raw, a, b, (), True, out)
+    return _coupling_transform("_reverse_logdet", x, raw, a, b, (), True, out)
 
 
 def finc_coupling_reverse_logdet_backward(grad_y, grad_logdet, y, raw, a, b, need_gx=True, need_graw=True, need_ga=True, need_gb=True):
     """Gradients of `finc_coupling_reverse_logdet` (include/finc.h: finc_coupling_reverse_logdet_backward_f32), given grad_y
     [B,C,H,W], grad_logdet [B] or None (zeros) and the reverse's OUTPUT `y`: (grad_x, grad_raw, grad_a, grad_b), each computed only
     if asked for (None otherwise).  With grad_logdet None every result has the bits of `finc_coupling_reverse_backward`."""
-    return _coupling_grads("finc_coupling_reverse_logdet_backward_f32", grad_y, (grad_logdet,), y, raw, a, b, "output",
+    return _coupling_grads("_reverse_logdet_backward", grad_y, (grad_logdet,), y, raw, a, b, "output",
                            "the reverse's output", (need_gx, need_graw), (need_ga, need_gb))
 
 
@@ -500,7 +539,7 @@ def finc_coupling_backward_reconstruct(grad_y, grad_logdet, y, raw, a, b, need_x
     in the same launch (include/finc.h: finc_coupling_backward_reconstruct_f32): (x, grad_x, grad_raw, grad_a, grad_b), each computed
     only if asked for (None otherwise).  `x` has the bits of `finc_coupling(y, raw, a, b, -1)`; grad_x[:, :C/2] is grad_y[:, :C/2] (the
     net's share is the caller's).  grad_logdet [B] or None (zeros).  Fixed-order sums: the same inputs give the same bits."""
-    return _coupling_grads("finc_coupling_backward_reconstruct_f32", grad_y, (grad_logdet,), y, raw, a, b, "output",
+    return _coupling_grads("_backward_reconstruct", grad_y, (grad_logdet,), y, raw, a, b, "output",
                            "the forward's output", (need_x, need_gx, need_graw), (need_ga, need_gb))
 
 
@@ -588,16 +627,19 @@ def coupling_reverse_logdet(x, raw, a, b):
 
 def finc_bias_relu(x, bias, out=None):
     """max(x + bias[c], 0) in one pass: the bias and the ReLU behind a convolution of the coupling net (layers/coupling.py:58-63).
-    x [B,C,H,W] fp32 contiguous on the device, bias [C]; `out` may be `x`.  Inference only: no autograd graph is recorded."""
-    _require_device(x, "input")
+    x [B,C,H,W] fp32 contiguous on the device, bias [C]; `out` may be `x`.  Inference only: no autograd graph is recorded.
+    `x` may also be bfloat16 (the output of a convolution under bf16 autocast; finc_bias_relu_bf16): `out` is bfloat16 then, the bias
+    stays fp32, the add and the max run in fp32 and are rounded once."""
+    bf16 = x.dtype == torch.bfloat16
+    _require_device(x, "input", x.dtype if bf16 else torch.float32)
     _require_device(bias, "bias")
     if x.dim() != 4 or bias.numel() != x.shape[1] or bias.device != x.device:
         raise ValueError("expected activations [B,C,H,W] and one bias entry per channel on the same device")
-    out = _out_like(x, out)
+    out = _out_like(x, out, x.dtype)
     if x.numel() == 0:
         return out
     B, C, H, W = x.shape
-    _call("finc_bias_relu_f32", x.device, x.data_ptr(), bias.data_ptr(), out.data_ptr(), B, C, H * W, _stream_ptr(x))
+    _call("finc_bias_relu_bf16" if bf16 else "finc_bias_relu_f32", x.device, x.data_ptr(), bias.data_ptr(), out.data_ptr(), B, C, H * W, _stream_ptr(x))
     return out
 
 

@@ -37,6 +37,7 @@
 #define FINC_H
 
 #include <stddef.h>
+#include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -52,7 +53,7 @@ enum finc_status {
     FINC_ERR_WORKSPACE = 4,    /* workspace NULL or smaller than finc_workspace_bytes() */
     FINC_ERR_LAUNCH = 5,       /* a HIP call failed; see finc_last_hip_error() */
     FINC_ERR_INVARIANT = 6,    /* unit-lower-triangular corner tap violated */
-    FINC_ERR_ALIGNMENT = 7     /* a pointer is not 4-byte (fp32) aligned */
+    FINC_ERR_ALIGNMENT = 7     /* a pointer is not aligned to its element: 4 bytes (fp32), 8 (fp64), 2 (bf16 bits) */
 };
 
 enum finc_algo {
@@ -380,6 +381,17 @@ int finc_mix_backward_f32(const float *grad_out, const float *in, const float *m
  * finc_bias_relu_f32: out = max(in + bias[c], 0) -- the Conv2d bias and the nn.ReLU behind the net's first two convolutions
  *   (layers/coupling.py:58-63) in one pass; in == out allowed.  Inference only (no backward).
  * Rows of HW floats move as 16-byte pieces when HW % 4 == 0 and every activation pointer is 16-byte aligned, as dwords otherwise.
+ * The _rawbf16_f32 siblings (version 113): the same six calls for a net that ran under bf16 autocast.  `raw` is bfloat16, given as
+ *   its bits (const uint16_t *), and is read as it lies -- bf16 -> fp32 is exact, so every fp32 output (y, logdet, x_out, grad_x,
+ *   grad_a, grad_b) has the BITS of the _f32 call on the same values widened; `grad_raw` (uint16_t *) is bfloat16 as well: the fp32
+ *   value the _f32 call writes, rounded to nearest even once (grad_a and grad_b are summed before that rounding).  x, y, a, b, every
+ *   other gradient, the log-det and the workspace (finc_coupling_workspace_bytes) stay fp32: the flow's own map keeps its
+ *   invertibility and its log-det in fp32.  Argument lists, refusals and their order, aliasing rules and status are the sibling's; a
+ *   bf16 pointer is held to 2 bytes (FINC_ERR_ALIGNMENT on an odd address), and the 16-byte-piece form additionally wants raw and
+ *   grad_raw on 8 bytes (four bf16 pixels), single 2-byte elements otherwise.
+ * finc_bias_relu_bf16: finc_bias_relu_f32 on bfloat16 activations (bits), bias fp32: the add and the max in fp32, rounded to nearest
+ *   even once; a NaN stays a NaN; in == out allowed.  16-byte pieces of eight when HW % 8 == 0 and both pointers are 16-byte aligned,
+ *   single elements otherwise.
  * Status: a NULL required pointer FINC_ERR_NULL_POINTER, non-positive dims FINC_ERR_BAD_DIMS, odd C FINC_ERR_UNSUPPORTED
  * (finc_coupling_supported_f32(C) == 0), a missing / short workspace where one is needed FINC_ERR_WORKSPACE.
  */
@@ -404,6 +416,26 @@ int finc_coupling_backward_reconstruct_f32(const float *grad_y, const float *gra
                                            float *grad_a, float *grad_b, int B, int C, int HW, void *workspace,
                                            size_t workspace_bytes, finc_stream_t stream);
 int finc_bias_relu_f32(const float *in, const float *bias, float *out, int B, int C, int HW, finc_stream_t stream);
+int finc_coupling_rawbf16_f32(const float *x, const uint16_t *raw, const float *a, const float *b, float *y, float *logdet, int B, int C,
+                              int HW, int direction, void *workspace, size_t workspace_bytes, finc_stream_t stream);
+int finc_coupling_backward_rawbf16_f32(const float *grad_y, const float *grad_logdet, const float *x, const uint16_t *raw,
+                                       const float *a, const float *b, float *grad_x, uint16_t *grad_raw, float *grad_a, float *grad_b,
+                                       int B, int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream);
+int finc_coupling_reverse_backward_rawbf16_f32(const float *grad_y, const float *y, const uint16_t *raw, const float *a, const float *b,
+                                               float *grad_x, uint16_t *grad_raw, float *grad_a, float *grad_b, int B, int C, int HW,
+                                               void *workspace, size_t workspace_bytes, finc_stream_t stream);
+int finc_coupling_reverse_logdet_rawbf16_f32(const float *x, const uint16_t *raw, const float *a, const float *b, float *y,
+                                             float *logdet, int B, int C, int HW, void *workspace, size_t workspace_bytes,
+                                             finc_stream_t stream);
+int finc_coupling_reverse_logdet_backward_rawbf16_f32(const float *grad_y, const float *grad_logdet, const float *y, const uint16_t *raw,
+                                                      const float *a, const float *b, float *grad_x, uint16_t *grad_raw, float *grad_a,
+                                                      float *grad_b, int B, int C, int HW, void *workspace, size_t workspace_bytes,
+                                                      finc_stream_t stream);
+int finc_coupling_backward_reconstruct_rawbf16_f32(const float *grad_y, const float *grad_logdet, const float *y, const uint16_t *raw,
+                                                   const float *a, const float *b, float *x_out, float *grad_x, uint16_t *grad_raw,
+                                                   float *grad_a, float *grad_b, int B, int C, int HW, void *workspace,
+                                                   size_t workspace_bytes, finc_stream_t stream);
+int finc_bias_relu_bf16(const uint16_t *in, const float *bias, uint16_t *out, int B, int C, int HW, finc_stream_t stream);
 
 /*
  * ActNorm (layers/actnorm.py:5-66) on its own kernels: activations [B][C][HW] fp32, log_scale and translation [C], any C >= 1
@@ -440,6 +472,17 @@ int finc_bias_relu_f32(const float *in, const float *bias, float *out, int B, in
  * finc_actnorm_workspace_bytes: one bound for the backward and the initialisation; > 0 for any arguments, never shrinks when B or
  *   HW grows.
  * Rows of HW floats move as 16-byte pieces when HW % 4 == 0 and every activation pointer is 16-byte aligned, as dwords otherwise.
+ * The _rawbf16_f32 siblings (version 113): the same six calls for a net that ran under bf16 autocast.  `raw` is bfloat16, given as
+ *   its bits (const uint16_t *), and is read as it lies -- bf16 -> fp32 is exact, so every fp32 output (y, logdet, x_out, grad_x,
+ *   grad_a, grad_b) has the BITS of the _f32 call on the same values widened; `grad_raw` (uint16_t *) is bfloat16 as well: the fp32
+ *   value the _f32 call writes, rounded to nearest even once (grad_a and grad_b are summed before that rounding).  x, y, a, b, every
+ *   other gradient, the log-det and the workspace (finc_coupling_workspace_bytes) stay fp32: the flow's own map keeps its
+ *   invertibility and its log-det in fp32.  Argument lists, refusals and their order, aliasing rules and status are the sibling's; a
+ *   bf16 pointer is held to 2 bytes (FINC_ERR_ALIGNMENT on an odd address), and the 16-byte-piece form additionally wants raw and
+ *   grad_raw on 8 bytes (four bf16 pixels), single 2-byte elements otherwise.
+ * finc_bias_relu_bf16: finc_bias_relu_f32 on bfloat16 activations (bits), bias fp32: the add and the max in fp32, rounded to nearest
+ *   even once; a NaN stays a NaN; in == out allowed.  16-byte pieces of eight when HW % 8 == 0 and both pointers are 16-byte aligned,
+ *   single elements otherwise.
  * Status: a NULL required pointer FINC_ERR_NULL_POINTER; non-positive / overflowing dims, a direction other than +1 / -1 or
  * forbidden aliasing FINC_ERR_BAD_DIMS; a pointer not 4-byte aligned FINC_ERR_ALIGNMENT; a missing / short workspace where one is
  * needed FINC_ERR_WORKSPACE -- checked in that order, before any HIP call.  The four launching calls take part in the
