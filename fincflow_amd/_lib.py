@@ -305,7 +305,8 @@ F64_FAMILIES = ("none", "one_wave", "msplit")
 def f64_plan(B, G, Cq, H, W, KH, KW):
     """What a float64 call on this shape launches (host-only; the launchers' own plan object): `family` 0 none (the reference-order and
     direct kernels), 1 one wave per problem, 2 the M-split over a workgroup's waves; `cqp` the padded bank; the inverse's `waves` per
-    problem, `ppw` problems per workgroup, `lds` bytes per workgroup and `inv_grid`; `fwd_grid` (x, y) of the forward / grad-input;
+    problem, `ppw` problems per workgroup, `lds` bytes per workgroup and `inv_grid`; `fwd_grid` (x, y) of the forward / grad-input -- slab and
+    strip on x, B * G * ceil(W / 16), and y = 1 in both families (0, 0 without a kernel);
     the grad-weight's `gw_grid`, its `nrc` row chunks per slab of `RC` rows.  The forward's and the grad-weight's workgroups have one
     wave in family 1 and `waves` (one per 16-row output tile) in family 2."""
     info = (ctypes.c_int * 11)()

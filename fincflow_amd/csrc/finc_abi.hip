@@ -511,7 +511,7 @@ static int run_f64_algo(const double *in, const double *w_canon, double *out, in
                        : finc_launch_inverse_strict_f64(in, w_canon, out, s, (hipStream_t)stream);
     }
     if (int e = finc_fault_gate(false)) return e;
-    return finc_f64_launch(in, w_canon, out, workspace, s, forward, (hipStream_t)stream);
+    return finc_f64_launch(in, w_canon, out, workspace, s, forward ? FINC_F64_FORWARD : FINC_F64_INVERSE, (hipStream_t)stream);
 }
 
 // the reference-order kernels: the strict path, which needs no workspace
@@ -1025,12 +1025,11 @@ int finc_backward_f64(const double *grad_z, const double *x, const double *w_can
     // (a workspace off an 8-byte boundary counts as none, as in the finc_*_f64_algo calls)
     const bool mfma = workspace && ((uintptr_t)workspace & 7u) == 0 && finc_f64_supported(s);
     const size_t bank = align256(finc_f64_packed_bytes(G, Cq, KH, KW));
-    // grad_x: the forward kernel on the transposed bank, every group's orientation complemented (one-wave family: grid.y carries the
-    // slabs; the M-split family has everything on grid.x)
-    if (grad_x && mfma && workspace_bytes >= bank && (finc_f64_plan(s).family == 2 || (long long)B * G <= 65535)) {
+    // grad_x: the forward kernel on the transposed bank, every group's orientation complemented
+    if (grad_x && mfma && workspace_bytes >= bank) {
         FincShape sb = s;
         sb.orient = orient ^ ((G >= 16) ? 0xFFFFFFFFu : ((1u << (2 * G)) - 1u));
-        if (int e = finc_f64_launch(grad_z, w_canon, grad_x, workspace, sb, true, st, true)) return e;
+        if (int e = finc_f64_launch(grad_z, w_canon, grad_x, workspace, sb, FINC_F64_GRAD_INPUT, st)) return e;
         grad_x = nullptr;
     }
     // grad_w: the pixels on the MFMA K dimension, partial tiles behind the bank, a fixed-order reduce with the corner-tap mask

@@ -256,24 +256,27 @@ size_t finc_gradw_workspace_bytes(const FincShape &s);  // room for the plans of
 // >= finc_gradw_workspace_bytes of every call on this bank with at most `units` = B * ceil(W / 16) strips; never shrinks when units grows
 size_t finc_gradw_workspace_bound(int G, int Cq, int KH, int KW, long long units);
 
-// ---- double precision on the matrix cores: finc_f64.hip.  Two families: one wave per problem (Cq <= 24 at 3x3, <= 32 at 2x2) and the
-// M-split over a workgroup's waves (29 .. 64 at 3x3, 33 .. 64 at 2x2); 25 .. 28 at 3x3, wider banks and other filters have neither ----
+// ---- double precision on the matrix cores: finc_f64.hip.  One body per kernel in two families: one wave per problem (Cq <= 24 at 3x3,
+// <= 32 at 2x2) and the M-split over a workgroup's waves (29 .. 64 at 3x3, 33 .. 64 at 2x2); 25 .. 28 at 3x3, wider banks and other
+// filters have neither ----
 // what a call on this shape launches: the one object the launchers, finc_f64_supported and finc_debug_f64_plan read
 struct FincF64Plan {
     int family = 0;           // 0: no matrix-core kernel, 1: one wave per problem, 2: M-split
     int cqp = 0;              // the padded bank
-    int waves = 0, ppw = 0;   // inverse: waves per problem, problems per workgroup
+    int waves = 0, ppw = 0;   // waves per problem (and per forward strip); inverse: problems per workgroup
     int lds = 0;              // inverse: bytes of LDS per workgroup
     int P = 0, DF = 0;        // inverse: rows per band, slots of the FIFO of rows above a band
+    // forward / grad-input, both families: slab and strip on grid.x (B * G * ceil(W / 16) <= 2^31 - 1), grid.y = 1
     long long inv_grid = 0, fwd_grid_x = 0, fwd_grid_y = 0;
 };
 FincF64Plan finc_f64_plan(const FincShape &s);
 bool finc_f64_supported(const FincShape &s);
 size_t finc_f64_packed_bytes(int G, int Cq, int KH, int KW);          // 0: no such kernel for this bank
-// packs the bank into `packed` (finc_f64_packed_bytes) and runs the inverse or the forward on it, all on `st`
-// `transpose` (forward only): the bank with in/out channels exchanged -- with every group's orientation complemented, the grad-input
-int finc_f64_launch(const double *in, const double *wc, double *out, void *packed, const FincShape &s, bool forward, hipStream_t st,
-                    bool transpose = false);
+// what finc_f64_launch packs and runs (the value is the pack kernel's `forward`).  Grad-input: the forward on the bank with in/out
+// channels exchanged -- called with every group's orientation complemented
+enum FincF64Mode { FINC_F64_INVERSE = 0, FINC_F64_FORWARD = 1, FINC_F64_GRAD_INPUT = 2 };
+// packs the bank into `packed` (finc_f64_packed_bytes) and runs the kernel of `mode` on it, all on `st`
+int finc_f64_launch(const double *in, const double *wc, double *out, void *packed, const FincShape &s, FincF64Mode mode, hipStream_t st);
 // weight gradient: pixels on the MFMA K dimension, one wave per (slab, row chunk), partial tiles in `workspace`, then a fixed-order
 // reduce with the corner-tap mask.  The grid is not capped: a wave takes exactly one unit.
 struct FincF64GradwPlan {

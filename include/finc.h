@@ -572,7 +572,9 @@ int finc_debug_conv_plan(int B, int G, int Cq, int H, int W, int KH, int KW, int
  * CQP, waves per problem and problems per workgroup of the inverse, its LDS bytes per workgroup (fixed part + FIFO slots x slot bytes)
  * and grid.x, grid.x and grid.y of the forward / grad-input, grid.x of the grad-weight, its row chunks per slab and rows per chunk}.
  * The workgroups of the forward and the grad-weight have one wave in family 1 and one per 16-row output tile (= waves per problem)
- * in family 2.  Host-only.  (The reference dispatches double for any shape on one kernel, cinc_cuda_kernel_level2.cu:117.) */
+ * in family 2.  Both families carry slab and strip of the forward on grid.x (B * G * ceil(W / 16)), so grid.y is 1 wherever there is
+ * a kernel -- family 1 had the slabs on grid.y until the two families' kernels became one body each; no symbol, argument list or
+ * packed layout changed with that, so finc_version() did not move.  Host-only.  (The reference dispatches double for any shape on one kernel, cinc_cuda_kernel_level2.cu:117.) */
 int finc_debug_f64_plan(int B, int G, int Cq, int H, int W, int KH, int KW, int *info);
 int finc_debug_inverse_table_row(int row, int *info);
 int finc_debug_attr_table_insert(int device, size_t kernel_token);

@@ -2,7 +2,7 @@
 at 2x2): the plan query's symbol, the ABI floor, and `_lib.f64_plan` against plan numbers written out by hand from the rules below
 (tests/plan_cases.py's way: nothing in the expected numbers calls the library).  No GPU is needed: every call here is host-only.
 
-The rules (finc_f64.hip: DCfg, MCfg, finc_f64_plan, finc_f64_gradw_plan), with CQP the padded bank, K the filter side:
+The rules (finc_f64.hip: DCfg, finc_f64_plan, finc_f64_gradw_plan), with CQP the padded bank, K the filter side:
     family 1   one wave per problem: CQP = Cq rounded up to 4, on the table 3x3 {4 .. 24}, 2x2 {4, 8, 12, 16, 24, 32}
     family 2   CQP = 32 / 48 / 64 for Cq in 29 .. 32 / 33 .. 48 / 49 .. 64 at 3x3, 48 / 64 for 33 .. 48 / 49 .. 64 at 2x2;
                waves per problem = CQP / 16; problems per workgroup 2 at CQP = 32 when two fit the LDS and there are two, else 1
@@ -10,7 +10,7 @@ The rules (finc_f64.hip: DCfg, MCfg, finc_f64_plan, finc_f64_gradw_plan), with C
                cell -> lds_fixed = 770 * CQP; a FIFO slot is 4 x (K - 1) cells -> FSLOT = 8 * (K - 1) * CQP; the FIFO has
                DF = W - P + 2 K - 2 slots (P = min(W, 16) rows per band), and one more in family 2; at most 160 KiB per workgroup
     inverse    grid = ceil(B * G / problems per workgroup)
-    forward    family 1: grid (ceil(W / 16), B * G) of one wave; family 2: grid.x = B * G * ceil(W / 16) workgroups of `waves`, grid.y = 1
+    forward    grid.x = B * G * ceil(W / 16) workgroups of `waves` (one wave in family 1), grid.y = 1
     grad-w     a slab is 1 wave (family 1) or a workgroup of `waves` (family 2); a launch of fewer than 1024 waves cuts its slabs into
                want = clamp(1024 // (B * G * waves per slab), 1, max(1, H // 4)) chunks: RC = ceil(H / want), nrc = ceil(H / RC),
                grid = B * G * nrc
@@ -85,8 +85,10 @@ HAND = {
     (1, 1, 64, 4, 122, 3, 3): plan(2, 64, 4, 1, 49280 + 111 * 1024, 1, (1 * 8, 1), 1 * 1, 1, 4),
     (1, 1, 64, 4, 123, 3, 3): NONE,
     # the first family, unchanged: c3 (cell 48 bytes: 18,480 + 52 * 384 per wave, four waves per workgroup) and a padded small bank
-    (256, 4, 24, 64, 64, 3, 3): plan(1, 24, 1, 4, 4 * (18480 + 52 * 384), 256, (4, 1024), 1024, 1, 64),
-    (2, 4, 3, 4, 4, 3, 3): plan(1, 4, 1, 4, 4 * (3080 + 4 * 64), 2, (1, 8), 8, 1, 4),
+    (256, 4, 24, 64, 64, 3, 3): plan(1, 24, 1, 4, 4 * (18480 + 52 * 384), 256, (4 * 1024, 1), 1024, 1, 64),
+    (2, 4, 3, 4, 4, 3, 3): plan(1, 4, 1, 4, 4 * (3080 + 4 * 64), 2, (1 * 8, 1), 8, 1, 4),
+    # more slabs than a grid's y dimension carries (65,535): CQP 4 at 2x2, FSLOT 32; W = 2: P = 2, DF = 0 + 2
+    (65536, 1, 4, 2, 2, 2, 2): plan(1, 4, 1, 4, 4 * (3080 + 2 * 32), 16384, (65536, 1), 65536, 1, 2),
     # no matrix-core kernel: 25 .. 28 channels at 3x3, 5x5, non-square, beyond 64 channels, the gaps of the 2x2 table
     (1, 1, 28, 5, 5, 3, 3): NONE,
     (2, 4, 25, 8, 8, 3, 3): NONE,

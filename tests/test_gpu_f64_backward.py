@@ -60,6 +60,8 @@ FALLBACK_CASES = {
     "k3x2_5x6": case(2, 4, 4, 5, 6, 3, 2),
 }
 ALL_CASES = {**MFMA_CASES, **FALLBACK_CASES}
+# one more slab than a grid's y dimension carries (65,535): 8 MiB per tensor, a test of its own below
+MANY_SLABS_CASES = {"many_slabs_2x2": case(65536, 1, 4, 2, 2, 2, 2)}
 
 
 def bank64(G, Cq, KH, KW, seed):
@@ -107,7 +109,7 @@ def grads_cpu(x, wc, gz, G, orient):
 @functools.lru_cache(maxsize=None)
 def problem(name):
     """Operands, the float64 CPU reference and the worst-case bound of one case: computed once, shared, never written to."""
-    dims, orient = ALL_CASES[name]
+    dims, orient = {**ALL_CASES, **MANY_SLABS_CASES}[name]
     B, G, Cq, H, W, KH, KW = dims
     rng = np.random.default_rng(sum(dims) + orient)
     x, gz = rng.standard_normal((B, G * Cq, H, W)), rng.standard_normal((B, G * Cq, H, W))
@@ -181,6 +183,31 @@ def test_backward_f64_against_cpu_autograd(name, dev):
     assert none is None and same_bits(gw, gw1)
     none, gw1s = on_side_stream(dev, lambda: ops.finc_backward(gz, x, wc, G, orient, need_gx=False))
     assert same_bits(gw, gw1s)
+    assert not _lib.fault_pending()
+
+
+def test_more_slabs_than_a_grid_y_carries(dev):
+    """B * G = 65,536 on the one-wave family: the forward under "mfma" runs (slab and strip share grid.x), the forward and
+    finc_backward's grad_x against float64 autograd on the CPU -- the last image on its own as well, so that a wrapped slab index
+    cannot hide in the maximum -- and the inverse under "mfma" takes the forward's output back to x."""
+    from fincflow_amd import _lib, ops
+    name = "many_slabs_2x2"
+    p = problem(name)
+    (B, G, Cq, H, W, KH, KW), orient = p["dims"], p["orient"]
+    assert B * G > 65535 and _lib.f64_plan(*p["dims"])["family"] == 1
+    x, gz, wc = t(p["x"], dev), t(p["gz"], dev), t(p["wc"], dev)
+    z = ops.finc_forward(x, wc, G, orient, algo="mfma")
+    gx, none = ops.finc_backward(gz, None, wc, G, orient, need_gw=False)
+    assert none is None
+    judge(name, "mfma", dict(z=z, gx=gx), ("z", "gx"))
+    for k, got in (("z", z), ("gx", gx)):
+        last = rel_err(got[-1].cpu().numpy(), p[k][-1])
+        print("f64_backward %s last image %s: %.3e" % (name, k, last))
+        assert last <= BAR, (name, "last image", k, last)
+    back = ops.finc_inverse(z, wc, G, orient, algo="mfma")
+    trip = rel_err(back.cpu().numpy(), p["x"]), rel_err(back[-1].cpu().numpy(), p["x"][-1])
+    print("f64_backward %s round trip: %.3e, last image %.3e" % (name, *trip))
+    assert max(trip) <= BAR, (name, "round trip", trip)
     assert not _lib.fault_pending()
 
 
