@@ -526,12 +526,12 @@ class FlowSequential(nn.Module):
                 params = mods[i + 1].forward_affine_params()
                 fused = module.forward_affine(input, *params) if params is not None else None
                 if fused is not None:
-                    logdet += mods[i + 1].logdet(input, context)      # (the unit's own logdet is 0)
+                    logdet = logdet + mods[i + 1].logdet(input, context)      # (the unit's own logdet is 0)
                     input = output = fused
                     i += 2
                     continue
             output, layer_logdet = module(input, context)
-            logdet += layer_logdet
+            logdet = logdet + layer_logdet        # (not in place: a Conv1x1 in front hands on a 0-dim log-det, the next layer's is [B])
             input = output
             i += 1
         return input, logdet

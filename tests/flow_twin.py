@@ -276,10 +276,10 @@ def error(got, want):
     return rel_err(got, want)
 
 
-def compare(tag, names, got, want, yard=None, bar=None, **fields):
+def compare(tag, names, got, want, yard=None, bar=None, kind="train_loop", **fields):
     """`got` (the HIP model) against `want` (the float64 twin), one `helpers.rel_err` per tensor; `yard`: the float32 twin's
     tensors, judged against `want` the same way -- the reference's own error, recorded beside the HIP one.  Appends one line to the
-    parity report and prints it; with a `bar`, asserts every HIP error under it.  Returns name -> error."""
+    parity report (under `kind`) and prints it; with a `bar`, asserts every HIP error under it.  Returns name -> error."""
     assert len(names) == len(got) == len(want) and (yard is None or len(yard) == len(want)), (tag, len(names), len(got), len(want))
     errs = {n: error(g, w) for n, g, w in zip(names, got, want)}
     yards = {n: error(y, w) for n, y, w in zip(names, yard, want)} if yard is not None else {}
@@ -287,9 +287,9 @@ def compare(tag, names, got, want, yard=None, bar=None, **fields):
     worst_yard = max(yards, key=yards.get) if yards else None
     line = dict(case=tag, tensors=len(names), hip=errs[worst], hip_at=worst, yardstick=yards.get(worst_yard), yardstick_at=worst_yard,
                 bar=bar, **fields)
-    report("train_loop", **line)
-    print("train_loop %s %s: HIP %.3e (%s), float32 twin %s, bar %s" % (
-        tag, fields or "", errs[worst], worst, "%.3e (%s)" % (yards[worst_yard], worst_yard) if yards else "-", bar))
+    report(kind, **line)
+    print("%s %s %s: HIP %.3e (%s), float32 twin %s, bar %s" % (
+        kind, tag, fields or "", errs[worst], worst, "%.3e (%s)" % (yards[worst_yard], worst_yard) if yards else "-", bar))
     if bar is not None:
         over = {n: e for n, e in errs.items() if not e <= bar}
         assert not over, (tag, fields, over, bar)
