@@ -45,6 +45,8 @@ SYMBOLS = [
     "finc_coupling_rawbf16_f32", "finc_coupling_backward_rawbf16_f32", "finc_coupling_reverse_backward_rawbf16_f32",
     "finc_coupling_reverse_logdet_rawbf16_f32", "finc_coupling_reverse_logdet_backward_rawbf16_f32",
     "finc_coupling_backward_reconstruct_rawbf16_f32", "finc_bias_relu_bf16",
+    "finc_split_prior_f32", "finc_split_prior_merge_f32", "finc_split_prior_backward_f32",
+    "finc_split_prior_rawbf16_f32", "finc_split_prior_merge_rawbf16_f32", "finc_split_prior_backward_rawbf16_f32",
 ]
 
 #: the ABI version this binding is written against (include/finc.h: finc_version)
@@ -73,6 +75,9 @@ F64_WIDE_BANKS_ABI_VERSION = 112
 #: the version that added the coupling's entry points on a bfloat16 `raw` / `grad_raw` (the six finc_coupling_*_rawbf16_f32) and
 #: finc_bias_relu_bf16: what a Coupling launches under torch.autocast(device_type="cuda", dtype=torch.bfloat16)
 AUTOCAST_ABI_VERSION = 113
+#: the version that added the split prior with its latent (finc_split_prior_f32, finc_split_prior_merge_f32,
+#: finc_split_prior_backward_f32 and their _rawbf16_f32 siblings): what SplitPrior.split / merge and FlowSequential.encode / decode launch
+SPLIT_LATENT_ABI_VERSION = 114
 
 _lib = None
 
@@ -134,6 +139,11 @@ def lib():
     if have < AUTOCAST_ABI_VERSION:
         raise FincError(f"{LIB_PATH} reports finc_version() = {have}, the coupling's bfloat16 entry points (finc_coupling_rawbf16_f32 "
                         f"and its five siblings, finc_bias_relu_bf16) came with {AUTOCAST_ABI_VERSION}: rebuild it "
+                        "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
+    if have < SPLIT_LATENT_ABI_VERSION:
+        raise FincError(f"{LIB_PATH} reports finc_version() = {have}, the split prior's entry points (finc_split_prior_f32, "
+                        f"finc_split_prior_merge_f32, finc_split_prior_backward_f32 and their bfloat16 siblings) came with "
+                        f"{SPLIT_LATENT_ABI_VERSION}: rebuild it "
                         "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
     L.finc_build_flags.restype = u
     L.finc_clear_fault.restype = i
@@ -223,6 +233,11 @@ def lib():
                  "finc_coupling_reverse_logdet_backward", "finc_coupling_backward_reconstruct"):
         getattr(L, name + "_rawbf16_f32").argtypes = getattr(L, name + "_f32").argtypes       # (pointers are void * here)
     L.finc_bias_relu_bf16.argtypes = L.finc_bias_relu_f32.argtypes
+    L.finc_split_prior_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp]
+    L.finc_split_prior_merge_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp]
+    L.finc_split_prior_backward_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp]
+    for name in ("finc_split_prior", "finc_split_prior_merge", "finc_split_prior_backward"):
+        getattr(L, name + "_rawbf16_f32").argtypes = getattr(L, name + "_f32").argtypes
     for name in SYMBOLS:
         getattr(L, name)  # AttributeError here = header and library out of sync
     _lib = L

@@ -190,7 +190,7 @@ static int canonicalize(const T *w_stored, T *w_canon, int G, int Cq, int KH, in
 
 extern "C" {
 
-int finc_version(void) { return 113; }
+int finc_version(void) { return 114; }
 
 unsigned finc_build_flags(void)
 {
@@ -614,48 +614,70 @@ size_t finc_coupling_workspace_bytes(int B, int C, int HW)
 // The coupling's entry points come in two families of one ladder each, and each ladder in two raw element types: float (the _f32
 // names) and bf16 given as its bits (the _rawbf16_f32 names: what a net under bf16 autocast hands over).  A bf16 pointer is held to
 // its 2 bytes, every other pointer to 4 as always.
-static int coupling_launch(const float *x, const float *raw, const float *a, const float *b, float *y, float *logdet, int B, int C, int HW,
-                           int direction, float *ws, hipStream_t st)
+static int coupling_launch(const float *x, const float *xb, const float *raw, const float *a, const float *b, float *y, float *yb,
+                           float *logdet, int B, int C, int HW, int direction, bool split, float *ws, hipStream_t st)
 {
-    return finc_coupling_launch(x, raw, a, b, y, logdet, B, C, HW, direction, ws, st);
+    return finc_coupling_launch(x, xb, raw, a, b, y, yb, logdet, B, C, HW, direction, split, ws, st);
 }
-static int coupling_launch(const float *x, const uint16_t *raw, const float *a, const float *b, float *y, float *logdet, int B, int C, int HW,
-                           int direction, float *ws, hipStream_t st)
+static int coupling_launch(const float *x, const float *xb, const uint16_t *raw, const float *a, const float *b, float *y, float *yb,
+                           float *logdet, int B, int C, int HW, int direction, bool split, float *ws, hipStream_t st)
 {
-    return finc_coupling_rawbf16_launch(x, raw, a, b, y, logdet, B, C, HW, direction, ws, st);
+    return finc_coupling_rawbf16_launch(x, xb, raw, a, b, y, yb, logdet, B, C, HW, direction, split, ws, st);
 }
-static int coupling_grad_launch(FincGradMode mode, const float *gy, const float *gld, const float *v, const float *raw, const float *a,
-                                const float *b, float *xo, float *gx, float *graw, float *ga, float *gb, int B, int C, int HW, float *ws,
-                                hipStream_t st)
+static int coupling_grad_launch(FincGradMode mode, const float *gy, const float *gz, const float *gld, const float *v, const float *raw,
+                                const float *a, const float *b, float *xo, float *gx, float *graw, float *ga, float *gb, int B, int C, int HW,
+                                float *ws, hipStream_t st)
 {
-    return finc_coupling_grad_launch(mode, gy, gld, v, raw, a, b, xo, gx, graw, ga, gb, B, C, HW, ws, st);
+    return finc_coupling_grad_launch(mode, gy, gz, gld, v, raw, a, b, xo, gx, graw, ga, gb, B, C, HW, ws, st);
 }
-static int coupling_grad_launch(FincGradMode mode, const float *gy, const float *gld, const float *v, const uint16_t *raw, const float *a,
-                                const float *b, float *xo, float *gx, uint16_t *graw, float *ga, float *gb, int B, int C, int HW, float *ws,
-                                hipStream_t st)
+static int coupling_grad_launch(FincGradMode mode, const float *gy, const float *gz, const float *gld, const float *v, const uint16_t *raw,
+                                const float *a, const float *b, float *xo, float *gx, uint16_t *graw, float *ga, float *gb, int B, int C,
+                                int HW, float *ws, hipStream_t st)
 {
-    return finc_coupling_rawbf16_grad_launch(mode, gy, gld, v, raw, a, b, xo, gx, graw, ga, gb, B, C, HW, ws, st);
+    return finc_coupling_rawbf16_grad_launch(mode, gy, gz, gld, v, raw, a, b, xo, gx, graw, ga, gb, B, C, HW, ws, st);
+}
+// do [p, p + n) and [q, q + m) share a byte?  (nullptr shares none)
+static bool bytes_overlap(const void *p, size_t n, const void *q, size_t m)
+{
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return p && q && a < b + m && b < a + n;
 }
 extern "C++" {
 template <typename R, typename... P>
 static bool raw_misaligned(const P *...p) { return off_boundary(sizeof(R) - 1, p...); }
 
-// The transform in either direction.  `with_logdet`: the entry point that always reports the log-det (logdet must be there, and so
-// must the workspace); otherwise logdet is optional and belongs to direction +1.
+// The transform in either direction, in one of four forms (one ladder):
+//   CPL_PLAIN    logdet is optional and belongs to direction +1;
+//   CPL_LOGDET   the entry point that always reports the log-det (logdet must be there, and so must the workspace);
+//   CPL_SPLIT    direction +1 with two half-tensor outputs y (x1) and yb (z2) and log p, all required (finc_split_prior_f32);
+//   CPL_MERGE    direction -1 with two half-tensor inputs x (x1) and xb (z2); log p optional (finc_split_prior_merge_f32).
+// xb and yb are nullptr in the first two.  In the last two the whole tensor and the two halves may not overlap each other.
+enum CplForm { CPL_PLAIN, CPL_LOGDET, CPL_SPLIT, CPL_MERGE };
 template <typename R>
-static int coupling_transform(const float *x, const R *raw, const float *a, const float *b, float *y, float *logdet, int B, int C, int HW,
-                              int direction, bool with_logdet, void *workspace, size_t workspace_bytes, finc_stream_t stream)
+static int coupling_transform(CplForm form, const float *x, const float *xb, const R *raw, const float *a, const float *b, float *y,
+                              float *yb, float *logdet, int B, int C, int HW, int direction, void *workspace, size_t workspace_bytes,
+                              finc_stream_t stream)
 {
-    if (!x || !raw || !a || !b || !y || (with_logdet && !logdet)) return FINC_ERR_NULL_POINTER;
+    const bool split = form == CPL_SPLIT || form == CPL_MERGE;
+    if (!x || !raw || !a || !b || !y || ((form == CPL_LOGDET || form == CPL_SPLIT) && !logdet) || (form == CPL_SPLIT && !yb) ||
+        (form == CPL_MERGE && !xb))
+        return FINC_ERR_NULL_POINTER;
     if (int e = pixel_dims(B, C, HW, true)) return e;
     if (direction != 1 && direction != -1) return FINC_ERR_BAD_DIMS;
-    if ((const void *)y == (const void *)raw) return FINC_ERR_BAD_DIMS;
-    if (misaligned(x, a, b, y, logdet) || raw_misaligned<R>(raw)) return FINC_ERR_ALIGNMENT;
+    if ((const void *)y == (const void *)raw || (yb && (const void *)yb == (const void *)raw)) return FINC_ERR_BAD_DIMS;
+    if (split) {
+        const size_t hb = (size_t)B * (size_t)(C / 2) * (size_t)HW * sizeof(float), wb = (size_t)B * (size_t)C * (size_t)HW * sizeof(float);
+        const void *h1 = form == CPL_SPLIT ? (const void *)y : x, *h2 = form == CPL_SPLIT ? (const void *)yb : xb;
+        const void *whole = form == CPL_SPLIT ? (const void *)x : y;
+        if (bytes_overlap(h1, hb, h2, hb) || bytes_overlap(h1, hb, whole, wb) || bytes_overlap(h2, hb, whole, wb)) return FINC_ERR_BAD_DIMS;
+    }
+    if (misaligned(x, xb, a, b, y, yb, logdet) || raw_misaligned<R>(raw)) return FINC_ERR_ALIGNMENT;
     if (!finc_coupling_supported_f32(C)) return FINC_ERR_UNSUPPORTED;
-    const bool sums = with_logdet || (direction > 0 && logdet);
+    const bool sums = form == CPL_LOGDET || form == CPL_SPLIT || (form == CPL_PLAIN ? direction > 0 && logdet : logdet != nullptr);
     if (sums && workspace_short(workspace, workspace_bytes, finc_coupling_workspace_bytes(B, C, HW))) return FINC_ERR_WORKSPACE;
     if (int e = finc_fault_gate(false)) return e;
-    return coupling_launch(x, raw, a, b, y, sums ? logdet : nullptr, B, C, HW, direction, (float *)workspace, (hipStream_t)stream);
+    return coupling_launch(x, xb, raw, a, b, y, yb, sums ? logdet : nullptr, B, C, HW, direction, split, (float *)workspace,
+                           (hipStream_t)stream);
 }
 
 } // extern "C++"
@@ -663,35 +685,39 @@ static int coupling_transform(const float *x, const R *raw, const float *a, cons
 int finc_coupling_f32(const float *x, const float *raw, const float *a, const float *b, float *y, float *logdet, int B, int C, int HW,
                       int direction, void *workspace, size_t workspace_bytes, finc_stream_t stream)
 {
-    return coupling_transform(x, raw, a, b, y, logdet, B, C, HW, direction, false, workspace, workspace_bytes, stream);
+    return coupling_transform(CPL_PLAIN, x, nullptr, raw, a, b, y, nullptr, logdet, B, C, HW, direction, workspace, workspace_bytes, stream);
 }
 
 int finc_coupling_rawbf16_f32(const float *x, const uint16_t *raw, const float *a, const float *b, float *y, float *logdet, int B, int C,
                               int HW, int direction, void *workspace, size_t workspace_bytes, finc_stream_t stream)
 {
-    return coupling_transform(x, raw, a, b, y, logdet, B, C, HW, direction, false, workspace, workspace_bytes, stream);
+    return coupling_transform(CPL_PLAIN, x, nullptr, raw, a, b, y, nullptr, logdet, B, C, HW, direction, workspace, workspace_bytes, stream);
 }
 
 // Every backward of the coupling: `v` is the activation the mode reads (FincGradMode), x_out the rebuilt input of FINC_GRAD_REBUILD
-// alone, which also allows grad_x == grad_y (and x_out == v); no other output may be an input or another output.
+// alone, which also allows grad_x == grad_y (and x_out == v); no other output may be an input or another output.  grad_z belongs to
+// FINC_GRAD_SPLIT (nullptr in every other mode): there grad_y and grad_z are the gradients of the two half tensors, and they and
+// grad_logdet (that of log p) may each be absent, not all three.
 extern "C++" {
 template <typename R>
-static int coupling_grad(FincGradMode mode, const float *grad_y, const float *grad_logdet, const float *v, const R *raw, const float *a,
-                         const float *b, float *x_out, float *grad_x, R *grad_raw, float *grad_a, float *grad_b, int B, int C, int HW,
+static int coupling_grad(FincGradMode mode, const float *grad_y, const float *grad_z, const float *grad_logdet, const float *v,
+                         const R *raw, const float *a, const float *b, float *x_out, float *grad_x, R *grad_raw, float *grad_a, float *grad_b, int B, int C, int HW,
                          void *workspace, size_t workspace_bytes, finc_stream_t stream)
 {
     const void *r = raw, *gr = grad_raw;
-    if (!grad_y || !v || !raw || !a || !b || (!x_out && !grad_x && !grad_raw && !grad_a && !grad_b)) return FINC_ERR_NULL_POINTER;
+    if ((mode == FINC_GRAD_SPLIT ? !grad_y && !grad_z && !grad_logdet : !grad_y) || !v || !raw || !a || !b ||
+        (!x_out && !grad_x && !grad_raw && !grad_a && !grad_b))
+        return FINC_ERR_NULL_POINTER;
     if (int e = pixel_dims(B, C, HW, true)) return e;
     if (x_out && (x_out == grad_y || x_out == r || x_out == grad_x || x_out == gr)) return FINC_ERR_BAD_DIMS;
-    if (grad_x && ((grad_x == grad_y && mode != FINC_GRAD_REBUILD) || grad_x == v || grad_x == r)) return FINC_ERR_BAD_DIMS;
-    if (grad_raw && (gr == grad_y || gr == v || gr == r || gr == grad_x)) return FINC_ERR_BAD_DIMS;
-    if (misaligned(grad_y, grad_logdet, v, a, b, x_out, grad_x, grad_a, grad_b) || raw_misaligned<R>(raw, grad_raw)) return FINC_ERR_ALIGNMENT;
+    if (grad_x && ((grad_x == grad_y && mode != FINC_GRAD_REBUILD) || grad_x == grad_z || grad_x == v || grad_x == r)) return FINC_ERR_BAD_DIMS;
+    if (grad_raw && (gr == grad_y || gr == grad_z || gr == v || gr == r || gr == grad_x)) return FINC_ERR_BAD_DIMS;
+    if (misaligned(grad_y, grad_z, grad_logdet, v, a, b, x_out, grad_x, grad_a, grad_b) || raw_misaligned<R>(raw, grad_raw)) return FINC_ERR_ALIGNMENT;
     if (!finc_coupling_supported_f32(C)) return FINC_ERR_UNSUPPORTED;
     if ((grad_a || grad_b) && workspace_short(workspace, workspace_bytes, finc_coupling_workspace_bytes(B, C, HW)))
         return FINC_ERR_WORKSPACE;
     if (int e = finc_fault_gate(false)) return e;
-    return coupling_grad_launch(mode, grad_y, grad_logdet, v, raw, a, b, x_out, grad_x, grad_raw, grad_a, grad_b, B, C, HW,
+    return coupling_grad_launch(mode, grad_y, grad_z, grad_logdet, v, raw, a, b, x_out, grad_x, grad_raw, grad_a, grad_b, B, C, HW,
                                 (float *)workspace, (hipStream_t)stream);
 }
 
@@ -701,7 +727,7 @@ int finc_coupling_backward_f32(const float *grad_y, const float *grad_logdet, co
                                const float *b, float *grad_x, float *grad_raw, float *grad_a, float *grad_b, int B, int C, int HW,
                                void *workspace, size_t workspace_bytes, finc_stream_t stream)
 {
-    return coupling_grad(FINC_GRAD_FWD, grad_y, grad_logdet, x, raw, a, b, nullptr, grad_x, grad_raw, grad_a, grad_b, B, C, HW, workspace,
+    return coupling_grad(FINC_GRAD_FWD, grad_y, nullptr, grad_logdet, x, raw, a, b, nullptr, grad_x, grad_raw, grad_a, grad_b, B, C, HW, workspace,
                          workspace_bytes, stream);
 }
 
@@ -716,7 +742,7 @@ int finc_coupling_reverse_backward_f32(const float *grad_y, const float *y, cons
 int finc_coupling_reverse_logdet_f32(const float *x, const float *raw, const float *a, const float *b, float *y, float *logdet, int B,
                                      int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream)
 {
-    return coupling_transform(x, raw, a, b, y, logdet, B, C, HW, -1, true, workspace, workspace_bytes, stream);
+    return coupling_transform(CPL_LOGDET, x, nullptr, raw, a, b, y, nullptr, logdet, B, C, HW, -1, workspace, workspace_bytes, stream);
 }
 
 int finc_coupling_reverse_logdet_backward_f32(const float *grad_y, const float *grad_logdet, const float *y, const float *raw,
@@ -724,7 +750,7 @@ int finc_coupling_reverse_logdet_backward_f32(const float *grad_y, const float *
                                               float *grad_b, int B, int C, int HW, void *workspace, size_t workspace_bytes,
                                               finc_stream_t stream)
 {
-    return coupling_grad(FINC_GRAD_REV, grad_y, grad_logdet, y, raw, a, b, nullptr, grad_x, grad_raw, grad_a, grad_b, B, C, HW, workspace,
+    return coupling_grad(FINC_GRAD_REV, grad_y, nullptr, grad_logdet, y, raw, a, b, nullptr, grad_x, grad_raw, grad_a, grad_b, B, C, HW, workspace,
                          workspace_bytes, stream);
 }
 
@@ -732,7 +758,7 @@ int finc_coupling_backward_reconstruct_f32(const float *grad_y, const float *gra
                                            const float *b, float *x_out, float *grad_x, float *grad_raw, float *grad_a, float *grad_b,
                                            int B, int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream)
 {
-    return coupling_grad(FINC_GRAD_REBUILD, grad_y, grad_logdet, y, raw, a, b, x_out, grad_x, grad_raw, grad_a, grad_b, B, C, HW, workspace,
+    return coupling_grad(FINC_GRAD_REBUILD, grad_y, nullptr, grad_logdet, y, raw, a, b, x_out, grad_x, grad_raw, grad_a, grad_b, B, C, HW, workspace,
                          workspace_bytes, stream);
 }
 
@@ -740,7 +766,7 @@ int finc_coupling_backward_rawbf16_f32(const float *grad_y, const float *grad_lo
                                        const float *b, float *grad_x, uint16_t *grad_raw, float *grad_a, float *grad_b, int B, int C, int HW,
                                        void *workspace, size_t workspace_bytes, finc_stream_t stream)
 {
-    return coupling_grad(FINC_GRAD_FWD, grad_y, grad_logdet, x, raw, a, b, nullptr, grad_x, grad_raw, grad_a, grad_b, B, C, HW, workspace,
+    return coupling_grad(FINC_GRAD_FWD, grad_y, nullptr, grad_logdet, x, raw, a, b, nullptr, grad_x, grad_raw, grad_a, grad_b, B, C, HW, workspace,
                          workspace_bytes, stream);
 }
 
@@ -755,7 +781,7 @@ int finc_coupling_reverse_backward_rawbf16_f32(const float *grad_y, const float 
 int finc_coupling_reverse_logdet_rawbf16_f32(const float *x, const uint16_t *raw, const float *a, const float *b, float *y, float *logdet,
                                              int B, int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream)
 {
-    return coupling_transform(x, raw, a, b, y, logdet, B, C, HW, -1, true, workspace, workspace_bytes, stream);
+    return coupling_transform(CPL_LOGDET, x, nullptr, raw, a, b, y, nullptr, logdet, B, C, HW, -1, workspace, workspace_bytes, stream);
 }
 
 int finc_coupling_reverse_logdet_backward_rawbf16_f32(const float *grad_y, const float *grad_logdet, const float *y, const uint16_t *raw,
@@ -763,7 +789,7 @@ int finc_coupling_reverse_logdet_backward_rawbf16_f32(const float *grad_y, const
                                                       float *grad_b, int B, int C, int HW, void *workspace, size_t workspace_bytes,
                                                       finc_stream_t stream)
 {
-    return coupling_grad(FINC_GRAD_REV, grad_y, grad_logdet, y, raw, a, b, nullptr, grad_x, grad_raw, grad_a, grad_b, B, C, HW, workspace,
+    return coupling_grad(FINC_GRAD_REV, grad_y, nullptr, grad_logdet, y, raw, a, b, nullptr, grad_x, grad_raw, grad_a, grad_b, B, C, HW, workspace,
                          workspace_bytes, stream);
 }
 
@@ -772,8 +798,50 @@ int finc_coupling_backward_reconstruct_rawbf16_f32(const float *grad_y, const fl
                                                    float *grad_a, float *grad_b, int B, int C, int HW, void *workspace,
                                                    size_t workspace_bytes, finc_stream_t stream)
 {
-    return coupling_grad(FINC_GRAD_REBUILD, grad_y, grad_logdet, y, raw, a, b, x_out, grad_x, grad_raw, grad_a, grad_b, B, C, HW, workspace,
+    return coupling_grad(FINC_GRAD_REBUILD, grad_y, nullptr, grad_logdet, y, raw, a, b, x_out, grad_x, grad_raw, grad_a, grad_b, B, C, HW, workspace,
                          workspace_bytes, stream);
+}
+
+// The split prior with its latent: the transform's ladder in its two split forms, the backward's ladder in its fourth mode.
+int finc_split_prior_f32(const float *x, const float *raw, const float *a, const float *b, float *x1, float *z2, float *log_p, int B, int C,
+                         int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    return coupling_transform(CPL_SPLIT, x, nullptr, raw, a, b, x1, z2, log_p, B, C, HW, 1, workspace, workspace_bytes, stream);
+}
+
+int finc_split_prior_rawbf16_f32(const float *x, const uint16_t *raw, const float *a, const float *b, float *x1, float *z2, float *log_p,
+                                 int B, int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    return coupling_transform(CPL_SPLIT, x, nullptr, raw, a, b, x1, z2, log_p, B, C, HW, 1, workspace, workspace_bytes, stream);
+}
+
+int finc_split_prior_merge_f32(const float *x1, const float *z2, const float *raw, const float *a, const float *b, float *x, float *log_p,
+                               int B, int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    return coupling_transform(CPL_MERGE, x1, z2, raw, a, b, x, nullptr, log_p, B, C, HW, -1, workspace, workspace_bytes, stream);
+}
+
+int finc_split_prior_merge_rawbf16_f32(const float *x1, const float *z2, const uint16_t *raw, const float *a, const float *b, float *x,
+                                       float *log_p, int B, int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    return coupling_transform(CPL_MERGE, x1, z2, raw, a, b, x, nullptr, log_p, B, C, HW, -1, workspace, workspace_bytes, stream);
+}
+
+int finc_split_prior_backward_f32(const float *grad_x1, const float *grad_z2, const float *grad_log_p, const float *x, const float *raw,
+                                  const float *a, const float *b, float *grad_x, float *grad_raw, float *grad_a, float *grad_b, int B,
+                                  int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    return coupling_grad(FINC_GRAD_SPLIT, grad_x1, grad_z2, grad_log_p, x, raw, a, b, nullptr, grad_x, grad_raw, grad_a, grad_b, B, C, HW,
+                         workspace, workspace_bytes, stream);
+}
+
+int finc_split_prior_backward_rawbf16_f32(const float *grad_x1, const float *grad_z2, const float *grad_log_p, const float *x,
+                                          const uint16_t *raw, const float *a, const float *b, float *grad_x, uint16_t *grad_raw,
+                                          float *grad_a, float *grad_b, int B, int C, int HW, void *workspace, size_t workspace_bytes,
+                                          finc_stream_t stream)
+{
+    return coupling_grad(FINC_GRAD_SPLIT, grad_x1, grad_z2, grad_log_p, x, raw, a, b, nullptr, grad_x, grad_raw, grad_a, grad_b, B, C, HW,
+                         workspace, workspace_bytes, stream);
 }
 
 // bias + ReLU on fp32 or on bf16 bits (the bias is fp32 in both): one ladder

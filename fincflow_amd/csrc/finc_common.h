@@ -304,26 +304,33 @@ int finc_mix_gradw_launch(const float *grad_out, const float *in, float *gm, flo
 
 // ---- the affine coupling's glue (transform + log-det, its backward, bias + ReLU): finc_coupling.h, compiled into finc_mix.o ----
 // Which backward of a per-pixel layer (a mode of the family's one kernel body and one launcher): of direction +1, of direction -1,
-// or of direction +1 from its OUTPUT with the direction's input rebuilt in the same pass (training without stored activations).
-enum FincGradMode { FINC_GRAD_FWD = 0, FINC_GRAD_REV = 1, FINC_GRAD_REBUILD = 2 };
+// of direction +1 from its OUTPUT with the direction's input rebuilt in the same pass (training without stored activations), or (the
+// coupling alone) of the split prior's forward: direction +1 with its outputs as two half tensors and a standard-normal score of the
+// second one in the per-image sum.
+enum FincGradMode { FINC_GRAD_FWD = 0, FINC_GRAD_REV = 1, FINC_GRAD_REBUILD = 2, FINC_GRAD_SPLIT = 3 };
 // C even; `ws` holds finc_coupling_workspace_floats floats (needed with logdet / ga / gb only); direction +1 forward, -1 reverse.
-// logdet[b] = sum s in EITHER direction: the FORWARD map's log-det, at the recovered input when direction is -1; nullptr: none
+// logdet[b] = sum s in EITHER direction: the FORWARD map's log-det, at the recovered input when direction is -1; nullptr: none.
+// `split` (glow.SplitPrior with its latent): the side that is NOT the whole [B][C][HW] tensor is two contiguous halves [B][C/2][HW] --
+// direction +1 writes y (the untouched half) and yb (z2) from the whole x, direction -1 reads x (x1) and xb (z2) and writes the whole
+// y -- and logdet becomes log p: sum s - 1/2 sum z2^2 - 1/2 (C/2) HW log 2 pi.  xb, yb: nullptr without `split`.
 size_t finc_coupling_workspace_floats(int B, int C, int HW);
-int finc_coupling_launch(const float *x, const float *raw, const float *a, const float *b, float *y, float *logdet, int B, int C, int HW,
-                         int direction, float *ws, hipStream_t st);
-// v: the forward's input (FINC_GRAD_FWD), the reverse's OUTPUT (FINC_GRAD_REV) or the forward's OUTPUT (FINC_GRAD_REBUILD, which also
-// writes the rebuilt input xo); gld: the gradient of the log-det per image; gld, xo, gx, graw, ga, gb may be nullptr
-int finc_coupling_grad_launch(FincGradMode mode, const float *gy, const float *gld, const float *v, const float *raw, const float *a,
-                              const float *b, float *xo, float *gx, float *graw, float *ga, float *gb, int B, int C, int HW, float *ws,
-                              hipStream_t st);
+int finc_coupling_launch(const float *x, const float *xb, const float *raw, const float *a, const float *b, float *y, float *yb,
+                         float *logdet, int B, int C, int HW, int direction, bool split, float *ws, hipStream_t st);
+// v: the forward's input (FINC_GRAD_FWD, FINC_GRAD_SPLIT), the reverse's OUTPUT (FINC_GRAD_REV) or the forward's OUTPUT
+// (FINC_GRAD_REBUILD, which also writes the rebuilt input xo); gld: the gradient of the log-det per image; gld, xo, gx, graw, ga, gb may
+// be nullptr.  FINC_GRAD_SPLIT: gy and gz are the gradients of the two half tensors (either may be nullptr: zeros), gld that of log p;
+// gz is nullptr in every other mode.
+int finc_coupling_grad_launch(FincGradMode mode, const float *gy, const float *gz, const float *gld, const float *v, const float *raw,
+                              const float *a, const float *b, float *xo, float *gx, float *graw, float *ga, float *gb, int B, int C, int HW,
+                              float *ws, hipStream_t st);
 int finc_bias_relu_launch(const float *in, const float *bias, float *out, int B, int C, int HW, hipStream_t st);
 // The same three on bf16 tensors, given as their bits: raw and graw of the coupling (everything else stays fp32), in and out of the
 // bias + ReLU (the bias stays fp32).  The wide forms want the bf16 pointers on 8 bytes (coupling) or 16 (bias + ReLU).
-int finc_coupling_rawbf16_launch(const float *x, const uint16_t *raw, const float *a, const float *b, float *y, float *logdet, int B, int C,
-                                 int HW, int direction, float *ws, hipStream_t st);
-int finc_coupling_rawbf16_grad_launch(FincGradMode mode, const float *gy, const float *gld, const float *v, const uint16_t *raw,
-                                      const float *a, const float *b, float *xo, float *gx, uint16_t *graw, float *ga, float *gb, int B,
-                                      int C, int HW, float *ws, hipStream_t st);
+int finc_coupling_rawbf16_launch(const float *x, const float *xb, const uint16_t *raw, const float *a, const float *b, float *y, float *yb,
+                                 float *logdet, int B, int C, int HW, int direction, bool split, float *ws, hipStream_t st);
+int finc_coupling_rawbf16_grad_launch(FincGradMode mode, const float *gy, const float *gz, const float *gld, const float *v,
+                                      const uint16_t *raw, const float *a, const float *b, float *xo, float *gx, uint16_t *graw, float *ga,
+                                      float *gb, int B, int C, int HW, float *ws, hipStream_t st);
 int finc_bias_relu_bf16_launch(const uint16_t *in, const float *bias, uint16_t *out, int B, int C, int HW, hipStream_t st);
 // ---- ActNorm (transform + log-det, its backward from the forward's OUTPUT, the data-dependent initialisation): finc_actnorm.h, same object ----
 // `ws` holds finc_actnorm_workspace_floats floats (backward with gls / gt, and the initialisation)

@@ -12,6 +12,9 @@
 //                               finc_coupling_rev_bwd_kernel (reverse direction, from its OUTPUT: what `reverse` under autograd
 //                               records inside ops.reverse_grad()) and finc_coupling_recon_kernel (forward direction from its OUTPUT,
 //                               which also writes the rebuilt input: the step of a training backward that stores no activations).
+//   * finc_splitprior_kernel    the split prior with its latent (glow.SplitPrior.split / merge): the transform with one side as two
+//                               half tensors, and log p = sum s - 1/2 sum z2^2 - c per image from the same pass; its backward,
+//                               finc_splitprior_bwd_kernel, is cpl_grad's fourth mode.
 //   * finc_coupling_rev_logdet_kernel  the reverse pass that also sums s per image: the sample and the forward log-det at the
 //                               sample in one pass (FlowSequential.sample_with_log_prob / rsample_with_log_prob).
 //   * finc_bias_relu_kernel     out = max(in + bias[c], 0), in place or not.
@@ -120,21 +123,32 @@ __device__ inline void cpl_block_sum(float (&v)[N], float (*sm)[4])
 // LOGDET: the workgroup's partial of sum s goes to part[blockIdx.x], in EITHER direction: what is summed is the FORWARD map's log-det,
 // sum_{j,p} s_j -- in the reverse direction that is the log-det of Coupling.forward at the recovered input y (s depends on the
 // untouched half only, which both directions share); the reverse map's own Jacobian is its negative.
-template <int V, int DIR, bool LOGDET, typename R = float>
-__device__ __forceinline__ void cpl_transform(const float *x, const R *__restrict__ raw, const float *__restrict__ a,
-                                              const float *__restrict__ b, float *y, float *__restrict__ part, int half, int HW, int nv,
-                                              int items, int P)
+// SPLIT (glow.SplitPrior with its latent): the side that is not the whole tensor is two contiguous halves [B][half][HW] -- DIR +1
+// writes y = the untouched half and yb = z2 (the split), DIR -1 reads x = x1 and xb = z2 (the merge); xb / yb are unused otherwise.
+// Nothing may overlap then.  The arithmetic lines are the same, so the halves carry the bits of the whole-tensor call.  With LOGDET
+// the partial is sum s - 1/2 sum z2^2, z2 the forward's output (DIR +1) or the reverse's input (DIR -1), and part 0 of every image
+// also takes -c (c = 1/2 half HW log 2 pi): the reduce then gives log p = the coupling's log-det + the standard-normal score of z2.
+template <int V, int DIR, bool LOGDET, typename R = float, bool SPLIT = false>
+__device__ __forceinline__ void cpl_transform(const float *x, const float *xb, const R *__restrict__ raw, const float *__restrict__ a,
+                                              const float *__restrict__ b, float *y, float *yb, float *__restrict__ part, float c, int half,
+                                              int HW, int nv, int items, int P)
 {
+    constexpr int NS = SPLIT && LOGDET ? 2 : 1;                            // sums per thread: s, and z2^2 for the split prior
     const int img = (int)blockIdx.x / P, pi = (int)blockIdx.x - img * P;
-    const size_t ibase = (size_t)img * (size_t)(2 * half) * (size_t)HW;
-    float ls[1] = {0.f};
+    const size_t ibase = (size_t)img * (size_t)(2 * half) * (size_t)HW, hbase = (size_t)img * (size_t)half * (size_t)HW;
+    float ls[NS] = {};
     for (int idx = pi * CPL_THREADS + (int)threadIdx.x; idx < items; idx += P * CPL_THREADS) {
         const int j = idx / nv, p = (idx - j * nv) * V;
-        const size_t o1 = ibase + (size_t)j * HW + p, o2 = o1 + (size_t)half * HW;
+        const size_t o1 = ibase + (size_t)j * HW + p, o2 = o1 + (size_t)half * HW, oh = hbase + (size_t)j * HW + p;
         const size_t ou = ibase + (size_t)(2 * j) * HW + p, ot = ou + HW;
         float x1[V], x2[V], u[V], t[V], y2[V];
-        cpl_load<V>(x1, x + o1);
-        cpl_load<V>(x2, x + o2);
+        if constexpr (SPLIT && DIR < 0) {
+            cpl_load<V>(x1, x + oh);
+            cpl_load<V>(x2, xb + oh);
+        } else {
+            cpl_load<V>(x1, x + o1);
+            cpl_load<V>(x2, x + o2);
+        }
         cpl_load<V>(u, raw + ou);
         cpl_load<V>(t, raw + ot);
         const float au = a[2 * j], bu = b[2 * j], at = a[2 * j + 1], bt = b[2 * j + 1];
@@ -145,18 +159,28 @@ __device__ __forceinline__ void cpl_transform(const float *x, const R *__restric
             if constexpr (DIR > 0) {
                 y2[e] = fmaf(x2[e], expf(s), tr);
                 if constexpr (LOGDET) ls[0] += s;
+                if constexpr (NS == 2) ls[NS - 1] = fmaf(y2[e], y2[e], ls[NS - 1]);
             } else {
                 y2[e] = (x2[e] - tr) * expf(-s);
                 if constexpr (LOGDET) ls[0] += s;
+                if constexpr (NS == 2) ls[NS - 1] = fmaf(x2[e], x2[e], ls[NS - 1]);
             }
         }
-        cpl_store<V>(y + o1, x1);
-        cpl_store<V>(y + o2, y2);
+        if constexpr (SPLIT && DIR > 0) {
+            cpl_store<V>(y + oh, x1);
+            cpl_store<V>(yb + oh, y2);
+        } else {
+            cpl_store<V>(y + o1, x1);
+            cpl_store<V>(y + o2, y2);
+        }
     }
     if constexpr (LOGDET) {
-        __shared__ float sm[1][4];
-        cpl_block_sum<1>(ls, sm);
-        if (threadIdx.x == 0) part[blockIdx.x] = ls[0];
+        __shared__ float sm[NS][4];
+        cpl_block_sum<NS>(ls, sm);
+        if (threadIdx.x == 0) {
+            if constexpr (NS == 2) part[blockIdx.x] = fmaf(-0.5f, ls[NS - 1], ls[0]) - (pi == 0 ? c : 0.f);
+            else part[blockIdx.x] = ls[0];
+        }
     }
 }
 
@@ -165,7 +189,7 @@ __global__ __launch_bounds__(CPL_THREADS) void finc_coupling_kernel(const float 
                                                                     const float *__restrict__ a, const float *__restrict__ b, float *y,
                                                                     float *__restrict__ part, int half, int HW, int nv, int items, int P)
 {
-    cpl_transform<V, DIR, LOGDET>(x, raw, a, b, y, part, half, HW, nv, items, P);
+    cpl_transform<V, DIR, LOGDET>(x, nullptr, raw, a, b, y, nullptr, part, 0.f, half, HW, nv, items, P);
 }
 
 // The reverse direction WITH the log-det partials (sampling with its log-density): cpl_transform<V, -1, true> under a name of its
@@ -176,7 +200,7 @@ __global__ __launch_bounds__(CPL_THREADS) void finc_coupling_rev_logdet_kernel(c
                                                                                float *y, float *__restrict__ part, int half, int HW, int nv,
                                                                                int items, int P)
 {
-    cpl_transform<V, -1, true>(x, raw, a, b, y, part, half, HW, nv, items, P);
+    cpl_transform<V, -1, true>(x, nullptr, raw, a, b, y, nullptr, part, 0.f, half, HW, nv, items, P);
 }
 
 // Either direction, with or without the partials, on a bf16 raw: the same body, R = __bf16.
@@ -186,7 +210,19 @@ __global__ __launch_bounds__(CPL_THREADS) void finc_coupling_rawbf16_kernel(cons
                                                                             float *y, float *__restrict__ part, int half, int HW, int nv,
                                                                             int items, int P)
 {
-    cpl_transform<V, DIR, LOGDET, __bf16>(x, raw, a, b, y, part, half, HW, nv, items, P);
+    cpl_transform<V, DIR, LOGDET, __bf16>(x, nullptr, raw, a, b, y, nullptr, part, 0.f, half, HW, nv, items, P);
+}
+
+// The split prior's two transforms (SPLIT): DIR +1 always with log p, DIR -1 with or without it; R = float or __bf16.  Nothing
+// overlaps here, so every pointer is __restrict__.
+template <int V, int DIR, bool LOGP, typename R>
+__global__ __launch_bounds__(CPL_THREADS) void finc_splitprior_kernel(const float *__restrict__ x, const float *__restrict__ xb,
+                                                                      const R *__restrict__ raw, const float *__restrict__ a,
+                                                                      const float *__restrict__ b, float *__restrict__ y,
+                                                                      float *__restrict__ yb, float *__restrict__ part, float c, int half,
+                                                                      int HW, int nv, int items, int P)
+{
+    cpl_transform<V, DIR, LOGP, R, true>(x, xb, raw, a, b, y, yb, part, c, half, HW, nv, items, P);
 }
 
 // Every backward of the coupling is ONE body, cpl_grad<V, MODE>; a mode (FincGradMode) is what it reads and the few lines of
@@ -203,20 +239,26 @@ __global__ __launch_bounds__(CPL_THREADS) void finc_coupling_rawbf16_kernel(cons
 //                      gld[img]) * (1 - th^2).  What a training step without stored activations runs per coupling: one launch instead
 //                      of a reverse launch plus a backward launch; y and raw are read once.  xo == v and gx == gy are allowed here (a
 //                      thread reads its pieces before it writes them, and nobody else touches them).
+//   FINC_GRAD_SPLIT    of the split prior's forward (cpl_transform<V, +1, true, R, true>: x1, z2, log p = sum s - 1/2 sum z2^2 - c),
+//                      from `v` = the forward's INPUT x.  gy = grad_x1 and gz = grad_z2 are contiguous HALVES [B][half][HW], gld =
+//                      grad_log_p; each may be nullptr (zeros).  E = exp(s) and z2 = fma(x2, E, t) are recomputed, G = grad_z2 -
+//                      grad_log_p[img] * z2 is what reaches z2 in all, and the FWD mode's lines follow with G in the place of g2.
+//                      gz is nullptr in every other mode.
 // s and exp(s) are recomputed from raw (two transcendentals per element), not saved by the forward.
 // Workgroup = (channel pair j, part): Q parts per pair share its B * HW / V thread items, so the four per-channel sums of a
 // workgroup belong to ONE pair.  Partials: part[(4j + k) * Q + q], k = 0 grad_a[2j], 1 grad_b[2j], 2 grad_a[2j+1], 3 grad_b[2j+1].
 // gld (grad of the log-det, per image), xo, gx, graw may be nullptr; `sums` = 0 skips the partials.  R: the element type of raw and
 // of graw, which is rounded from the fp32 gu, gt behind the sums (the sums never see a rounded value).
 template <int V, int MODE, typename R = float>
-__device__ __forceinline__ void cpl_grad(const float *gy, const float *__restrict__ gld, const float *v, const R *__restrict__ raw,
+__device__ __forceinline__ void cpl_grad(const float *gy, const float *gz, const float *__restrict__ gld, const float *v,
+                                         const R *__restrict__ raw,
                                          const float *__restrict__ a, const float *__restrict__ b, float *xo, float *gx,
                                          R *__restrict__ graw, float *__restrict__ part, int half, int HW, int nv, int items, int Q,
                                          int sums)
 {
-    constexpr bool REBUILD = MODE == FINC_GRAD_REBUILD;
+    constexpr bool REBUILD = MODE == FINC_GRAD_REBUILD, SPLIT = MODE == FINC_GRAD_SPLIT;
     const int j = (int)blockIdx.x / Q, qi = (int)blockIdx.x - j * Q;
-    const float au = a[2 * j], bu = b[2 * j], at = a[2 * j + 1], bt = REBUILD ? b[2 * j + 1] : 0.f;
+    const float au = a[2 * j], bu = b[2 * j], at = a[2 * j + 1], bt = REBUILD || SPLIT ? b[2 * j + 1] : 0.f;
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     for (int idx = qi * CPL_THREADS + (int)threadIdx.x; idx < items; idx += Q * CPL_THREADS) {
         const int img = idx / nv, p = (idx - img * nv) * V;
@@ -224,13 +266,21 @@ __device__ __forceinline__ void cpl_grad(const float *gy, const float *__restric
         const size_t o1 = ibase + (size_t)j * HW + p, o2 = o1 + (size_t)half * HW;
         const size_t ou = ibase + (size_t)(2 * j) * HW + p, ot = ou + HW;
         float g1[V], g2[V], v1[V], v2[V], u[V], t[V], x2[V], gx2[V], gu[V], gt[V];
-        if (gx) cpl_load<V>(g1, gy + o1);
-        cpl_load<V>(g2, gy + o2);
+        if constexpr (SPLIT) {
+            const size_t oh = (size_t)img * (size_t)half * (size_t)HW + (size_t)j * HW + p;
+#pragma unroll
+            for (int e = 0; e < V; ++e) g1[e] = g2[e] = 0.f;
+            if (gx && gy) cpl_load<V>(g1, gy + oh);
+            if (gz) cpl_load<V>(g2, gz + oh);
+        } else {
+            if (gx) cpl_load<V>(g1, gy + o1);
+            cpl_load<V>(g2, gy + o2);
+        }
         if constexpr (REBUILD)
             if (xo) cpl_load<V>(v1, v + o1);
         cpl_load<V>(v2, v + o2);
         cpl_load<V>(u, raw + ou);
-        if (REBUILD || sums) cpl_load<V>(t, raw + ot);
+        if (REBUILD || SPLIT || sums) cpl_load<V>(t, raw + ot);
         const float gl = gld ? gld[img] : (MODE == FINC_GRAD_REV ? -0.f : 0.f);
 #pragma unroll
         for (int e = 0; e < V; ++e) {
@@ -244,6 +294,11 @@ __device__ __forceinline__ void cpl_grad(const float *gy, const float *__restric
                 gx2[e] = g2[e] * expf(-2.f * th);
                 ghu = (-(g2[e] * v2[e]) + gl) * fmaf(-th, th, 1.f);
                 ght = -gx2[e];
+            } else if constexpr (SPLIT) {
+                const float E = expf(2.f * th), G = g2[e] - gl * fmaf(v2[e], E, fmaf(at, t[e], bt));
+                gx2[e] = G * E;
+                ghu = fmaf(gx2[e], v2[e], gl) * fmaf(-th, th, 1.f);
+                ght = G;
             } else {
                 const float s = 2.f * th, d = v2[e] - fmaf(at, t[e], bt);
                 x2[e] = d * expf(-s);
@@ -292,7 +347,7 @@ __global__ __launch_bounds__(CPL_THREADS) void finc_coupling_bwd_kernel(const fl
                                                                         float *__restrict__ part, int half, int HW, int nv, int items, int Q,
                                                                         int sums)
 {
-    cpl_grad<V, FINC_GRAD_FWD>(gy, gld, x, raw, a, b, nullptr, gx, graw, part, half, HW, nv, items, Q, sums);
+    cpl_grad<V, FINC_GRAD_FWD>(gy, nullptr, gld, x, raw, a, b, nullptr, gx, graw, part, half, HW, nv, items, Q, sums);
 }
 
 template <int V>
@@ -303,7 +358,7 @@ __global__ __launch_bounds__(CPL_THREADS) void finc_coupling_rev_bwd_kernel(cons
                                                                             float *__restrict__ part, int half, int HW, int nv, int items,
                                                                             int Q, int sums)
 {
-    cpl_grad<V, FINC_GRAD_REV>(gy, gld, y, raw, a, b, nullptr, gx, graw, part, half, HW, nv, items, Q, sums);
+    cpl_grad<V, FINC_GRAD_REV>(gy, nullptr, gld, y, raw, a, b, nullptr, gx, graw, part, half, HW, nv, items, Q, sums);
 }
 
 template <int V>
@@ -313,19 +368,33 @@ __global__ __launch_bounds__(CPL_THREADS) void finc_coupling_recon_kernel(const 
                                                                           float *__restrict__ graw, float *__restrict__ part, int half, int HW,
                                                                           int nv, int items, int Q, int sums)
 {
-    cpl_grad<V, FINC_GRAD_REBUILD>(gy, gld, y, raw, a, b, xo, gx, graw, part, half, HW, nv, items, Q, sums);
+    cpl_grad<V, FINC_GRAD_REBUILD>(gy, nullptr, gld, y, raw, a, b, xo, gx, graw, part, half, HW, nv, items, Q, sums);
 }
 
-// The three modes on a bf16 raw (and a bf16 grad_raw): one kernel, the mode its parameter.  xo == v and gx == gy are the rebuild's.
+// The split prior's backward (fp32 raw): the fourth mode under a name of its own; nothing may overlap.
+template <int V>
+__global__ __launch_bounds__(CPL_THREADS) void finc_splitprior_bwd_kernel(const float *__restrict__ gx1, const float *__restrict__ gz2,
+                                                                          const float *__restrict__ glp, const float *__restrict__ x,
+                                                                          const float *__restrict__ raw, const float *__restrict__ a,
+                                                                          const float *__restrict__ b, float *__restrict__ gx,
+                                                                          float *__restrict__ graw, float *__restrict__ part, int half, int HW,
+                                                                          int nv, int items, int Q, int sums)
+{
+    cpl_grad<V, FINC_GRAD_SPLIT>(gx1, gz2, glp, x, raw, a, b, nullptr, gx, graw, part, half, HW, nv, items, Q, sums);
+}
+
+// The four modes on a bf16 raw (and a bf16 grad_raw): one kernel, the mode its parameter.  xo == v and gx == gy are the rebuild's;
+// gz is the split's.
 template <int V, int MODE>
-__global__ __launch_bounds__(CPL_THREADS) void finc_coupling_rawbf16_grad_kernel(const float *gy, const float *__restrict__ gld,
-                                                                                 const float *v, const __bf16 *__restrict__ raw,
+__global__ __launch_bounds__(CPL_THREADS) void finc_coupling_rawbf16_grad_kernel(const float *gy, const float *gz,
+                                                                                 const float *__restrict__ gld, const float *v,
+                                                                                 const __bf16 *__restrict__ raw,
                                                                                  const float *__restrict__ a, const float *__restrict__ b,
                                                                                  float *xo, float *gx, __bf16 *__restrict__ graw,
                                                                                  float *__restrict__ part, int half, int HW, int nv,
                                                                                  int items, int Q, int sums)
 {
-    cpl_grad<V, MODE, __bf16>(gy, gld, v, raw, a, b, xo, gx, graw, part, half, HW, nv, items, Q, sums);
+    cpl_grad<V, MODE, __bf16>(gy, gz, gld, v, raw, a, b, xo, gx, graw, part, half, HW, nv, items, Q, sums);
 }
 
 // One wave per output: out = sum of its n consecutive partials, lane l takes l, l + 64, ... and the lanes meet in a butterfly.
@@ -454,22 +523,32 @@ template <typename R, typename... P>
 inline uintptr_t cpl_bits8(const P *...p) { return sizeof(R) == 2 ? cpl_bits(p...) : 0; }
 
 // logdet (either direction): the log-det of the FORWARD map, sum s per image -- in the reverse direction at the recovered input y
-// (B x P partials in `ws`, then the reduce); nullptr: none, and `ws` is not touched
+// (B x P partials in `ws`, then the reduce); nullptr: none, and `ws` is not touched.
+// split: the split prior's transforms (cpl_transform's SPLIT) -- xb / yb are the second half tensor of the side that has two, every
+// half-tensor pointer counts towards the 16-byte rule, and logdet is log p (direction +1 always has it).
 template <typename R>
-int cpl_launch(const float *x, const R *raw, const float *a, const float *b, float *y, float *logdet, int B, int C, int HW, int direction,
-               float *ws, hipStream_t st)
+int cpl_launch(const float *x, const float *xb, const R *raw, const float *a, const float *b, float *y, float *yb, float *logdet, int B,
+               int C, int HW, int direction, bool split, float *ws, hipStream_t st)
 {
     const int half = C / 2;
     if ((size_t)C * HW * 4 >= ((size_t)1 << 31)) return FINC_ERR_BAD_DIMS;
-    const bool wide = cpl_wide(HW, cpl_bits(x, y) | cpl_bits16<R>(raw), cpl_bits8<R>(raw));
+    const bool wide = cpl_wide(HW, cpl_bits(x, xb, y, yb) | cpl_bits16<R>(raw), cpl_bits8<R>(raw));
     const int nv = HW / (wide ? 4 : 1), items = half * nv, P = cpl_parts(items, B);
     if ((long long)B * P >= (1LL << 31)) return FINC_ERR_BAD_DIMS;
     const dim3 grid((unsigned)((long long)B * P)), block(CPL_THREADS);
-    const auto kernel = !logdet ? (direction < 0 ? (wide ? cpl_transform_kernel<R, 4, -1, false>() : cpl_transform_kernel<R, 1, -1, false>())
-                                                 : (wide ? cpl_transform_kernel<R, 4, 1, false>() : cpl_transform_kernel<R, 1, 1, false>()))
-                        : direction < 0 ? (wide ? cpl_transform_kernel<R, 4, -1, true>() : cpl_transform_kernel<R, 1, -1, true>())
-                                        : (wide ? cpl_transform_kernel<R, 4, 1, true>() : cpl_transform_kernel<R, 1, 1, true>());
-    hipLaunchKernelGGL(kernel, grid, block, 0, st, x, raw, a, b, y, ws, half, HW, nv, items, P);
+    if (split) {
+        const float c = (float)(0.5 * (double)half * (double)HW * 1.8378770664093454835606594728112);        // log(2 pi)
+        const auto kernel = direction > 0 ? (wide ? finc_splitprior_kernel<4, 1, true, R> : finc_splitprior_kernel<1, 1, true, R>)
+                            : logdet      ? (wide ? finc_splitprior_kernel<4, -1, true, R> : finc_splitprior_kernel<1, -1, true, R>)
+                                          : (wide ? finc_splitprior_kernel<4, -1, false, R> : finc_splitprior_kernel<1, -1, false, R>);
+        hipLaunchKernelGGL(kernel, grid, block, 0, st, x, xb, raw, a, b, y, yb, ws, c, half, HW, nv, items, P);
+    } else {
+        const auto kernel = !logdet ? (direction < 0 ? (wide ? cpl_transform_kernel<R, 4, -1, false>() : cpl_transform_kernel<R, 1, -1, false>())
+                                                     : (wide ? cpl_transform_kernel<R, 4, 1, false>() : cpl_transform_kernel<R, 1, 1, false>()))
+                            : direction < 0 ? (wide ? cpl_transform_kernel<R, 4, -1, true>() : cpl_transform_kernel<R, 1, -1, true>())
+                                            : (wide ? cpl_transform_kernel<R, 4, 1, true>() : cpl_transform_kernel<R, 1, 1, true>());
+        hipLaunchKernelGGL(kernel, grid, block, 0, st, x, raw, a, b, y, ws, half, HW, nv, items, P);
+    }
     FINC_CHECK_LAUNCH();
     if (logdet) {
         hipLaunchKernelGGL(finc_coupling_reduce_kernel, dim3((unsigned)B), dim3(64), 0, st, (const float *)ws, P, logdet, (float *)nullptr, 0);
@@ -479,10 +558,13 @@ int cpl_launch(const float *x, const R *raw, const float *a, const float *b, flo
 }
 
 template <int V, int MODE>
-void cpl_grad_start(const CplGradPlan &p, hipStream_t st, const float *gy, const float *gld, const float *v, const float *raw, const float *a,
-                    const float *b, float *xo, float *gx, float *graw, float *ws, int half, int HW, int sums)
+void cpl_grad_start(const CplGradPlan &p, hipStream_t st, const float *gy, const float *gz, const float *gld, const float *v,
+                    const float *raw, const float *a, const float *b, float *xo, float *gx, float *graw, float *ws, int half, int HW, int sums)
 {
-    if constexpr (MODE == FINC_GRAD_REBUILD)
+    if constexpr (MODE == FINC_GRAD_SPLIT)
+        hipLaunchKernelGGL(finc_splitprior_bwd_kernel<V>, p.grid, dim3(CPL_THREADS), 0, st, gy, gz, gld, v, raw, a, b, gx, graw, ws, half, HW,
+                           p.nv, p.items, p.Q, sums);
+    else if constexpr (MODE == FINC_GRAD_REBUILD)
         hipLaunchKernelGGL(finc_coupling_recon_kernel<V>, p.grid, dim3(CPL_THREADS), 0, st, gy, gld, v, raw, a, b, xo, gx, graw, ws, half, HW,
                            p.nv, p.items, p.Q, sums);
     else
@@ -490,22 +572,24 @@ void cpl_grad_start(const CplGradPlan &p, hipStream_t st, const float *gy, const
                            st, gy, gld, v, raw, a, b, gx, graw, ws, half, HW, p.nv, p.items, p.Q, sums);
 }
 template <int V, int MODE>
-void cpl_grad_start(const CplGradPlan &p, hipStream_t st, const float *gy, const float *gld, const float *v, const __bf16 *raw,
-                    const float *a, const float *b, float *xo, float *gx, __bf16 *graw, float *ws, int half, int HW, int sums)
+void cpl_grad_start(const CplGradPlan &p, hipStream_t st, const float *gy, const float *gz, const float *gld, const float *v,
+                    const __bf16 *raw, const float *a, const float *b, float *xo, float *gx, __bf16 *graw, float *ws, int half, int HW, int sums)
 {
-    hipLaunchKernelGGL((finc_coupling_rawbf16_grad_kernel<V, MODE>), p.grid, dim3(CPL_THREADS), 0, st, gy, gld, v, raw, a, b, xo, gx, graw, ws,
-                       half, HW, p.nv, p.items, p.Q, sums);
+    hipLaunchKernelGGL((finc_coupling_rawbf16_grad_kernel<V, MODE>), p.grid, dim3(CPL_THREADS), 0, st, gy, gz, gld, v, raw, a, b, xo, gx, graw,
+                       ws, half, HW, p.nv, p.items, p.Q, sums);
 }
 
 template <typename R>
-int cpl_grad_launch(FincGradMode mode, const float *gy, const float *gld, const float *v, const R *raw, const float *a, const float *b,
-                    float *xo, float *gx, R *graw, float *ga, float *gb, int B, int C, int HW, float *ws, hipStream_t st)
+int cpl_grad_launch(FincGradMode mode, const float *gy, const float *gz, const float *gld, const float *v, const R *raw, const float *a,
+                    const float *b, float *xo, float *gx, R *graw, float *ga, float *gb, int B, int C, int HW, float *ws, hipStream_t st)
 {
     const int half = C / 2, sums = (ga || gb) ? 1 : 0;
-    const CplGradPlan p = cpl_grad_plan(B, C, HW, half, cpl_bits(gy, v, xo, gx) | cpl_bits16<R>(raw, graw), cpl_bits8<R>(raw, graw));
+    const CplGradPlan p = cpl_grad_plan(B, C, HW, half, cpl_bits(gy, gz, v, xo, gx) | cpl_bits16<R>(raw, graw), cpl_bits8<R>(raw, graw));
     if (!p.Q) return FINC_ERR_BAD_DIMS;
-#define CPL_GRAD_START(V, MODE) cpl_grad_start<V, MODE>(p, st, gy, gld, v, raw, a, b, xo, gx, graw, ws, half, HW, sums)
-    if (mode == FINC_GRAD_REBUILD) {
+#define CPL_GRAD_START(V, MODE) cpl_grad_start<V, MODE>(p, st, gy, gz, gld, v, raw, a, b, xo, gx, graw, ws, half, HW, sums)
+    if (mode == FINC_GRAD_SPLIT) {
+        if (p.wide) CPL_GRAD_START(4, FINC_GRAD_SPLIT); else CPL_GRAD_START(1, FINC_GRAD_SPLIT);
+    } else if (mode == FINC_GRAD_REBUILD) {
         if (p.wide) CPL_GRAD_START(4, FINC_GRAD_REBUILD); else CPL_GRAD_START(1, FINC_GRAD_REBUILD);
     } else if (mode == FINC_GRAD_REV) {
         if (p.wide) CPL_GRAD_START(4, FINC_GRAD_REV); else CPL_GRAD_START(1, FINC_GRAD_REV);
@@ -526,29 +610,29 @@ size_t finc_coupling_workspace_floats(int B, int C, int HW)
     return (size_t)(fwd > bwd ? fwd : bwd);
 }
 
-int finc_coupling_launch(const float *x, const float *raw, const float *a, const float *b, float *y, float *logdet, int B, int C, int HW,
-                         int direction, float *ws, hipStream_t st)
+int finc_coupling_launch(const float *x, const float *xb, const float *raw, const float *a, const float *b, float *y, float *yb,
+                         float *logdet, int B, int C, int HW, int direction, bool split, float *ws, hipStream_t st)
 {
-    return cpl_launch<float>(x, raw, a, b, y, logdet, B, C, HW, direction, ws, st);
+    return cpl_launch<float>(x, xb, raw, a, b, y, yb, logdet, B, C, HW, direction, split, ws, st);
 }
-int finc_coupling_rawbf16_launch(const float *x, const uint16_t *raw, const float *a, const float *b, float *y, float *logdet, int B, int C,
-                                 int HW, int direction, float *ws, hipStream_t st)
+int finc_coupling_rawbf16_launch(const float *x, const float *xb, const uint16_t *raw, const float *a, const float *b, float *y, float *yb,
+                                 float *logdet, int B, int C, int HW, int direction, bool split, float *ws, hipStream_t st)
 {
-    return cpl_launch<__bf16>(x, reinterpret_cast<const __bf16 *>(raw), a, b, y, logdet, B, C, HW, direction, ws, st);
+    return cpl_launch<__bf16>(x, xb, reinterpret_cast<const __bf16 *>(raw), a, b, y, yb, logdet, B, C, HW, direction, split, ws, st);
 }
 
-int finc_coupling_grad_launch(FincGradMode mode, const float *gy, const float *gld, const float *v, const float *raw, const float *a,
-                              const float *b, float *xo, float *gx, float *graw, float *ga, float *gb, int B, int C, int HW, float *ws,
-                              hipStream_t st)
+int finc_coupling_grad_launch(FincGradMode mode, const float *gy, const float *gz, const float *gld, const float *v, const float *raw,
+                              const float *a, const float *b, float *xo, float *gx, float *graw, float *ga, float *gb, int B, int C, int HW,
+                              float *ws, hipStream_t st)
 {
-    return cpl_grad_launch<float>(mode, gy, gld, v, raw, a, b, xo, gx, graw, ga, gb, B, C, HW, ws, st);
+    return cpl_grad_launch<float>(mode, gy, gz, gld, v, raw, a, b, xo, gx, graw, ga, gb, B, C, HW, ws, st);
 }
-int finc_coupling_rawbf16_grad_launch(FincGradMode mode, const float *gy, const float *gld, const float *v, const uint16_t *raw,
-                                      const float *a, const float *b, float *xo, float *gx, uint16_t *graw, float *ga, float *gb, int B,
-                                      int C, int HW, float *ws, hipStream_t st)
+int finc_coupling_rawbf16_grad_launch(FincGradMode mode, const float *gy, const float *gz, const float *gld, const float *v,
+                                      const uint16_t *raw, const float *a, const float *b, float *xo, float *gx, uint16_t *graw, float *ga,
+                                      float *gb, int B, int C, int HW, float *ws, hipStream_t st)
 {
-    return cpl_grad_launch<__bf16>(mode, gy, gld, v, reinterpret_cast<const __bf16 *>(raw), a, b, xo, gx, reinterpret_cast<__bf16 *>(graw), ga,
-                                   gb, B, C, HW, ws, st);
+    return cpl_grad_launch<__bf16>(mode, gy, gz, gld, v, reinterpret_cast<const __bf16 *>(raw), a, b, xo, gx,
+                                   reinterpret_cast<__bf16 *>(graw), ga, gb, B, C, HW, ws, st);
 }
 
 // fp32: 16-byte pieces of 4; bf16: 16-byte pieces of 8

@@ -20,7 +20,9 @@ Reference semantics followed:
   Conv1x1        layers/conv1x1.py:8-49          orthogonal init, ldj = H*W*log|det W|
   Coupling       layers/coupling.py:46-113       affine, net = conv3x3-ReLU-conv1x1-ReLU-Conv2dZero, log_s = 2*tanh(h/2);
                  on the device the part behind the net is one HIP launch (ops.finc_coupling)
-  SplitPrior     layers/splitprior.py:7-41       Coupling + factor out the second half under a standard normal
+  SplitPrior     layers/splitprior.py:7-41       Coupling + factor out the second half under a standard normal; `split` / `merge`
+                 hand that half out and take it back (FlowSequential.encode / decode), one HIP launch each (ops.finc_split_prior,
+                 ops.finc_split_prior_merge, ops.split_prior_forward)
   Normalization, LogitTransform, Dequantization  layers/normalize.py, transforms.py:6-19, dequantize.py
   GaussianPrior  train/losses.py:17-45           standard-normal base (log_prob per sample, sample(n))
 """
@@ -576,12 +578,71 @@ class GaussianPrior(nn.Module):
 
 
 class SplitPrior(FlowLayer):
+    """layers/splitprior.py:7-41: a coupling whose second output half is factored out under `base`.  `forward` / `reverse` are the
+    reference's protocol: `forward` scores that half and drops it, `reverse` draws a fresh one.  `split` / `merge` are the same two
+    maps with the half handed out and taken back -- what `FlowSequential.encode` / `decode` walk, an exact round trip -- and on the
+    device, with a `GaussianPrior` base, one HIP launch each (`ops.finc_split_prior`, `ops.finc_split_prior_merge`: the transform,
+    the two half tensors and log p = log-det + the base's score from one pass; no `cat`, no slices, no PyTorch log-prob chain)."""
+
     def __init__(self, input_size, distribution, width=512):
         super().__init__()
         assert len(input_size) == 3
         self.n_channels = input_size[0]
         self.transform = Coupling(input_size, width=width)
         self.base = distribution((self.n_channels // 2, input_size[1], input_size[2]))
+
+    def _hip_latent(self, *halves_or_input):
+        """Do the split prior's own kernels serve these tensors?  The coupling's conditions, and a base that is exactly the standard
+        normal the kernels score (a subclass or another distribution keeps `base.log_prob`)."""
+        t = halves_or_input[0]
+        return (type(self.base) is GaussianPrior and self.transform._hip_device(t) and tuple(t.shape[2:]) == self.base.size[1:]
+                and all(_hip_tensor(h) and h.shape == t.shape and h.device == t.device for h in halves_or_input[1:]))
+
+    def split(self, input, context=None):
+        """`forward` with the factored-out half handed back: `(x1, z2, log_p)`, log_p [B] = what `forward` returns as its second value
+        (the coupling's log-det plus log p(z2) under the base).  The three paths of `Coupling.forward`: without a graph the net on
+        `_raw_inference` and `ops.finc_split_prior`; while autograd records, `_raw_train` and `ops.split_prior_forward` (backward:
+        finc_split_prior_backward_f32); the PyTorch lines for everything else -- CPU tensors, fp64, odd channel counts, a base that
+        is not exactly `GaussianPrior`.  Under bf16 autocast the net's bf16 output goes to the `_rawbf16_f32` entry points as it
+        lies; under fp16 autocast it is upcast, as everywhere in `Coupling`."""
+        t, half = self.transform, self.n_channels // 2
+        if input.dim() == 4 and input.shape[1] == self.n_channels and self._hip_latent(input):
+            if t._hip(input, context):
+                x = input.contiguous()
+                a, b = t._scale_shift_cached()
+                return ops.finc_split_prior(x, t._raw_inference(x, context), a, b)
+            if t._hip_train(input, context):
+                a, b = t._scale_shift()
+                return ops.split_prior_forward(input, t._raw_train(input, context), a, b)
+        x, ldj = t(input, context)
+        z2 = x[:, half:]
+        return x[:, :half], z2, self.base.log_prob(z2) + ldj
+
+    def draw(self, n_samples, context=None, temperature=1.0):
+        """The factored-out half as `reverse` draws it, times `temperature` (applied to what `base.sample` returns, so that any base
+        with that interface serves; at 1 the draw is handed on untouched)."""
+        z2 = self.base.sample(n_samples, context)[0]
+        return z2 if temperature == 1 else z2 * temperature
+
+    def merge(self, x1, z2=None, context=None, temperature=1.0, with_log_prob=False):
+        """The inverse of `split`: x from the kept half `x1` and the factored-out half `z2` (None: drawn from the base, times
+        `temperature`); with `with_log_prob`, `(x, log_p)` with log_p [B] = `split`'s value at x.  Without a graph, on the device: the
+        net on `x1` itself and `ops.finc_split_prior_merge` -- no `cat`.  While autograd records (inside `ops.reverse_grad()` that is
+        the HIP path of `Coupling.reverse` / `reverse_with_logdet`) and everywhere else: `cat`, the coupling's reverse and
+        `base.log_prob`, the lines of `reverse` / `reverse_with_logdet`."""
+        if z2 is None:
+            z2 = self.draw(len(x1), context, temperature)
+        t = self.transform
+        records = torch.is_grad_enabled() and (z2.requires_grad or t._records_graph(x1, context))
+        if not records and x1.dim() == 4 and x1.shape[1] == self.n_channels // 2 and self._hip_latent(x1, z2):
+            x1, z2 = x1.contiguous(), z2.contiguous()
+            a, b = t._scale_shift_cached()
+            return ops.finc_split_prior_merge(x1, z2, t._raw_inference(x1, context), a, b, want_log_p=with_log_prob)
+        whole = torch.cat([x1, z2], dim=1)
+        if not with_log_prob:
+            return t.reverse(whole, context)
+        out, ldj = t.reverse_with_logdet(whole, context)
+        return out, self.base.log_prob(z2) + ldj
 
     def forward(self, input, context=None):
         x, ldj = self.transform(input, context)

@@ -507,16 +507,31 @@ class FlowSequential(nn.Module):
         yield from self.sequence_modules
 
     def forward(self, input, context=None, compute_expensive=False):
-        mods = list(self.sequence_modules)
-        if self.invertible_backward and torch.is_grad_enabled():
-            output, logdet = self._forward_invertible(mods, input, context)
-        else:
-            output, logdet = self._forward_layers(mods, input, context)
+        output, logdet = self._forward_stack(input, context)
         logprob = self.base_distribution.log_prob(output)
         return output, logprob + logdet
 
-    def _forward_layers(self, mods, input, context, logdet=0):
-        """`mods` in order on `input`: (output, `logdet` plus the sum of their log-dets)."""
+    def _forward_stack(self, input, context, latents=None):
+        mods = list(self.sequence_modules)
+        if self.invertible_backward and torch.is_grad_enabled():
+            return self._forward_invertible(mods, input, context, latents)
+        return self._forward_layers(mods, input, context, latents=latents)
+
+    def encode(self, input, context=None):
+        """The complete latent code of `input` and its log-density: `(zs, log_prob)`.  `zs` is a list -- the half that every layer
+        with a `split` (glow.SplitPrior) factors out, in forward order, then the stack's output -- and log_prob [B] is what
+        `forward(input, context)[1]` is.  `forward` throws those halves away; with them `decode(zs)` is the exact inverse
+        (`reconstruct` is not, in a stack with split layers).  The walk is `forward`'s, `fuse_affine` folds and `invertible_backward`
+        runs included, and it is differentiable: a loss on log_prob reaches every parameter, through a split layer's own HIP
+        backward on the device."""
+        zs = []
+        output, logdet = self._forward_stack(input, context, zs)
+        zs.append(output)
+        return zs, self.base_distribution.log_prob(output) + logdet
+
+    def _forward_layers(self, mods, input, context, logdet=0, latents=None):
+        """`mods` in order on `input`: (output, `logdet` plus the sum of their log-dets).  `latents`: a list that receives what
+        every layer with a `split` factors out (`encode`); None: the layers' `forward`."""
         i = 0
         while i < len(mods):
             module = mods[i]
@@ -530,7 +545,11 @@ class FlowSequential(nn.Module):
                     input = output = fused
                     i += 2
                     continue
-            output, layer_logdet = module(input, context)
+            if latents is not None and hasattr(module, "split"):
+                output, latent, layer_logdet = module.split(input, context)
+                latents.append(latent)
+            else:
+                output, layer_logdet = module(input, context)
             logdet = logdet + layer_logdet        # (not in place: a Conv1x1 in front hands on a 0-dim log-det, the next layer's is [B])
             input = output
             i += 1
@@ -557,9 +576,10 @@ class FlowSequential(nn.Module):
             j += 1
         return j
 
-    def _forward_invertible(self, mods, input, context):
+    def _forward_invertible(self, mods, input, context, latents=None):
         """`_forward_layers` with every run of two or more supporting layers that has something to differentiate behind one
-        `_InvertibleRunFunction`; every other layer runs as it always has, with its stored activations."""
+        `_InvertibleRunFunction`; every other layer runs as it always has, with its stored activations.  (A layer with a `split`
+        supports no invertible backward: it ends a run and is walked here.)"""
         logdet = 0
         i = 0
         while i < len(mods):
@@ -572,7 +592,11 @@ class FlowSequential(nn.Module):
                     logdet = logdet + run_logdet
                     i = j
                     continue
-            output, layer_logdet = mods[i](input, context)
+            if latents is not None and hasattr(mods[i], "split"):
+                output, latent, layer_logdet = mods[i].split(input, context)
+                latents.append(latent)
+            else:
+                output, layer_logdet = mods[i](input, context)
             logdet = logdet + layer_logdet
             input = output
             i += 1
@@ -587,13 +611,15 @@ class FlowSequential(nn.Module):
     #: let the channel mix in front of a FastFlowUnit (reverse chain) apply the unit's blockdiag(Linv) as well
     fuse_lead = True
 
-    def _reverse_chain(self, input, context, fuse=None, with_logdet=False):
+    def _reverse_chain(self, input, context, fuse=None, with_logdet=False, latents=None):
         """The layers' reverses, last layer first.  `with_logdet`: returns `(x, logdet[B])`, the sum of the layers' FORWARD log-dets
         at their recovered inputs (`reverse_with_logdet`), in the same pass: every fold below stays, and a folded per-channel affine
         layer or channel mix adds its term -- parameters only, a few [C]-sized ops or a cached number -- beside the fused launch (the
-        unit's own is zero)."""
+        unit's own is zero).  `latents`: the factored-out halves of the layers with a `merge`, in FORWARD order (`decode`): each such
+        layer takes its own through `merge` instead of drawing one in `reverse`, and its log p takes the log-det's place."""
         fuse = self.fuse_affine if fuse is None else fuse
         mods = list(reversed(self.sequence_modules))
+        latents = None if latents is None else list(latents)
         logdet = input.new_zeros(len(input)) if with_logdet else None
         i = 0
         while i < len(mods):
@@ -634,7 +660,16 @@ class FlowSequential(nn.Module):
                     input = fused
                     i += 2
                     continue
-            if with_logdet:
+            if latents is not None and hasattr(m, "merge"):
+                latent = latents.pop()
+                if latent.shape != input.shape:
+                    raise ValueError(f"the latent of a split layer has shape {tuple(latent.shape)}, its layer expects {tuple(input.shape)}")
+                if with_logdet:
+                    input, layer_logdet = m.merge(input, latent, context, with_log_prob=True)
+                    logdet = logdet + layer_logdet
+                else:
+                    input = m.merge(input, latent, context)
+            elif with_logdet:
                 input, layer_logdet = m.reverse_with_logdet(input, context)
                 logdet = logdet + layer_logdet
             else:
@@ -643,12 +678,60 @@ class FlowSequential(nn.Module):
             i += 1
         return (input, logdet) if with_logdet else input
 
-    def sample(self, n_samples, context=None, compute_expensive=False, also_true_inverse=False):
+    def _split_layers(self):
+        return [m for m in self.sequence_modules if hasattr(m, "split")]
+
+    def decode(self, zs, context=None, with_log_prob=False):
+        """The inverse of `encode`: x from the complete latent code `zs` (the split layers' halves in forward order, then the stack's
+        output), through `_reverse_chain` with every fold kept and every split layer's `merge`.  With `with_log_prob`: `(x, log_q)`,
+        log_q [B] = base.log_prob(zs[-1]) + the layers' forward log-dets at their recovered inputs, the merges' log p among them --
+        `log_prob(x)` from the same pass, as `sample_with_log_prob` builds it.  ValueError for a list of the wrong length or a
+        latent of the wrong shape.  Nothing is drawn here, so the call can be captured in a graph; the grad mode is the caller's
+        (under `torch.no_grad()` the HIP paths of `sample`); the fault word is checked as in `sample`."""
+        zs = list(zs)
+        if len(zs) != len(self._split_layers()) + 1:
+            raise ValueError(f"expected {len(self._split_layers()) + 1} latents (one per split layer, then the stack's output), "
+                             f"got {len(zs)}")
+        z, size = zs[-1], getattr(self.base_distribution, "size", None)
+        if size is not None and tuple(z.shape[1:]) != tuple(size):
+            raise ValueError(f"the last latent has shape {tuple(z.shape)}, the base distribution expects [B, {', '.join(map(str, size))}]")
+        if any(len(t) != len(z) for t in zs):
+            raise ValueError("the latents hold different numbers of images")
+        if with_log_prob:
+            x, logdet = self._reverse_chain(z, context, with_logdet=True, latents=zs[:-1])
+            out = (x, self.base_distribution.log_prob(z) + logdet)
+        else:
+            out = x = self._reverse_chain(z, context, latents=zs[:-1])
+        if x.is_cuda:
+            _lib.raise_if_faulted("FlowSequential.decode")
+        return out
+
+    def draw_latents(self, n_samples, context=None, temperature=1.0):
+        """A complete latent code drawn from the model's priors, each draw times `temperature` (applied to what a prior's `sample`
+        returns): the list `decode` takes.  The draws are made in the order `sample` makes them -- the base first, then the split
+        layers from the last to the first -- so from one seed `decode(draw_latents(n))` is `sample(n)[0]`."""
+        z = self.base_distribution.sample(n_samples, context)[0]
+        zs = [z if temperature == 1 else z * temperature]
+        for m in reversed(self._split_layers()):
+            zs.append(m.draw(n_samples, context, temperature))
+        return zs[::-1]
+
+    def sample(self, n_samples, context=None, compute_expensive=False, also_true_inverse=False, temperature=1.0):
         """layers/flowsequential.py:89-115: returns `(input, input_true)` -- the runner unpacks two values
         (train/experiment.py:311-335).  No layer of the hot path is a ModifiedGradFlowLayer, so the "true inverse"
         differs from the regular sample only in how it is evaluated: it re-runs the reverse chain from the same z
         layer by layer (no affine fold), an independent check of the fused launch.  Without `also_true_inverse` (or with
-        `compute_expensive`) the second value IS the first, as in the reference (`input_true = input`)."""
+        `compute_expensive`) the second value IS the first, as in the reference (`input_true = input`).
+        `temperature`: every prior's draw times that number (Glow samples at about 0.7).  At 1.0 the path is the one it always was;
+        otherwise it is `decode(draw_latents(n_samples, context, temperature), context)`, and the second value follows the same
+        rule: with `also_true_inverse` (and without `compute_expensive`) the same latents once more through the reverse chain without
+        its folds, else the first value itself."""
+        if temperature != 1.0:
+            zs = self.draw_latents(n_samples, context, temperature)
+            x = self.decode(zs, context)
+            if not compute_expensive and also_true_inverse:
+                return x, self._reverse_chain(zs[-1], context, fuse=False, latents=zs[:-1])
+            return x, x
         z, _ = self.base_distribution.sample(n_samples, context)
         x = self._reverse_chain(z, context)
         if not compute_expensive and also_true_inverse:
@@ -663,11 +746,16 @@ class FlowSequential(nn.Module):
             _lib.raise_if_faulted("FlowSequential.sample")
         return x, x_true
 
-    def rsample(self, n_samples, context=None):
+    def rsample(self, n_samples, context=None, temperature=1.0):
         """A reparameterised sample: x = reverse(z), z drawn from the base, with the reverse chain RECORDED for autograd (grad enabled,
         inside `reverse_grad()`: the fused folds step aside, the units' inverses are differentiable), so that a loss on x reaches
         every parameter -- reverse-KL training, adversarial fine-tuning of the sampler.  Returns x alone, attached to the graph; the
-        fault word is checked as in `sample`."""
+        fault word is checked as in `sample`.  `temperature` as in `sample`: at 1.0 today's path, otherwise `decode` of tempered
+        `draw_latents`, recorded the same way."""
+        if temperature != 1.0:
+            zs = self.draw_latents(n_samples, context, temperature)
+            with torch.enable_grad(), ops.reverse_grad():
+                return self.decode(zs, context)
         z, _ = self.base_distribution.sample(n_samples, context)
         with torch.enable_grad(), ops.reverse_grad():
             x = self._reverse_chain(z, context)
@@ -702,5 +790,8 @@ class FlowSequential(nn.Module):
         return x, log_q
 
     def reconstruct(self, input, context=None, compute_expensive=False):
+        """`forward` then the reverse chain on its output.  In a stack with split layers (glow.SplitPrior) this is NOT the input
+        again: `forward` drops the halves those layers factor out and the reverse chain draws fresh ones.  The exact round trip
+        there is `decode(encode(input)[0])`."""
         z = self.forward(input, context)[0]
         return self._reverse_chain(z, context)

@@ -427,37 +427,48 @@ def coupling_supported(C):
 _RAW_ENTRY = {torch.float32: "_f32", torch.bfloat16: "_rawbf16_f32"}
 
 
-def _coupling_entry(name, raw):
-    """`finc_coupling<name>` for the element type of `raw`."""
-    return "finc_coupling" + name + _RAW_ENTRY[raw.dtype]
+def _coupling_entry(name, raw, family="finc_coupling"):
+    """`finc_coupling<name>` (or `<family><name>`: "finc_split_prior") for the element type of `raw`."""
+    return family + name + _RAW_ENTRY[raw.dtype]
 
 
-def _coupling_args(x, raw, a, b, what="input"):
-    _require_device(x, what)
+def _coupling_args(x, raw, a, b, what="input", halves=()):
+    """`halves`: the split prior's half tensors [B,C/2,H,W] that the call reads or writes (None: absent); `x` None: a call whose
+    whole tensor is its output (`finc_split_prior_merge`)."""
+    if x is not None:
+        _require_device(x, what)
     _require_device(raw, "raw", raw.dtype if raw.dtype in _RAW_ENTRY else torch.float32)
     _require_device(a, "scale")
     _require_device(b, "shift")
-    if x.dim() != 4 or raw.shape != x.shape or raw.device != x.device:
+    if raw.dim() != 4 or (x is not None and (raw.shape != x.shape or raw.device != x.device)):
         raise ValueError(f"expected {what} [B,C,H,W] and the coupling net's output of the same shape on the same device")
-    C = x.shape[1]
-    _per_channel(x, "scale and shift", a, b)
+    C = raw.shape[1]
+    for h in halves:
+        if h is not None:
+            _require_device(h, "half tensor")
+            if h.shape != (raw.shape[0], C // 2) + raw.shape[2:] or h.device != raw.device:
+                raise ValueError("expected half tensors [B,C/2,H,W] beside the coupling net's output [B,C,H,W], on the same device")
+    _per_channel(raw, "scale and shift", a, b)
     if not coupling_supported(C):
         raise _lib.FincError(f"finc_coupling: no kernel for {C} channels (the coupling splits an even channel count)")
 
 
-def _coupling_transform(entry, x, raw, a, b, direction, want_logdet, out):
+def _coupling_transform(entry, x, raw, a, b, direction, want_logdet, out, family="finc_coupling"):
     """`finc_coupling_f32` (which takes the direction) or `finc_coupling_reverse_logdet_f32` behind their wrappers, or their
-    `_rawbf16_f32` siblings for a bfloat16 `raw` (`entry`: the name between "finc_coupling" and that suffix): (y, logdet), fp32."""
-    entry = _coupling_entry(entry, raw)
-    out = _out_like(x, out)
-    B, C, H, W = x.shape
-    if x.numel() == 0:
-        return out, (torch.zeros(B, dtype=torch.float32, device=x.device) if want_logdet else None)
-    logdet = torch.empty(B, dtype=torch.float32, device=x.device) if want_logdet else None
+    `_rawbf16_f32` siblings for a bfloat16 `raw` (`entry`: the name between "finc_coupling" and that suffix): (y, logdet), fp32.
+    The split prior's transforms (`family` "finc_split_prior") have two half tensors on one side: `x` or `out` is then the tuple of
+    them, in the entry point's order, and the result is (*out, log_p)."""
+    entry = _coupling_entry(entry, raw, family)
+    ins = x if isinstance(x, tuple) else (x,)
+    outs = out if isinstance(out, tuple) else (_out_like(x, out),)
+    B, C, H, W = raw.shape
+    if raw.numel() == 0:
+        return outs + (torch.zeros(B, dtype=torch.float32, device=raw.device) if want_logdet else None,)
+    logdet = torch.empty(B, dtype=torch.float32, device=raw.device) if want_logdet else None
     nbytes = _lib.lib().finc_coupling_workspace_bytes(B, C, H * W) if want_logdet else None
-    _call(entry, x.device, x.data_ptr(), raw.data_ptr(), a.data_ptr(), b.data_ptr(), out.data_ptr(), _ptr(logdet), B, C, H * W, *direction,
-          *_ws_args(x.device, nbytes), _stream_ptr(x))
-    return out, logdet
+    _call(entry, raw.device, *map(_ptr, ins), raw.data_ptr(), a.data_ptr(), b.data_ptr(), *map(_ptr, outs), _ptr(logdet), B, C, H * W,
+          *direction, *_ws_args(raw.device, nbytes), _stream_ptr(raw))
+    return outs + (logdet,)
 
 
 def finc_coupling(x, raw, a, b, direction=1, want_logdet=False, out=None):
@@ -474,16 +485,21 @@ def finc_coupling(x, raw, a, b, direction=1, want_logdet=False, out=None):
     return _coupling_transform("", x, raw, a, b, (direction,), bool(want_logdet) and direction == 1, out)
 
 
-def _coupling_grads(entry, grad_y, grad_logdet, v, raw, a, b, what, whose, need_acts, need_sums):
+def _coupling_grads(entry, grad_y, grad_logdet, v, raw, a, b, what, whose, need_acts, need_sums, family="finc_coupling"):
     """One backward entry point of the coupling behind its wrapper: the checks, the outputs asked for -- `need_acts`: (x,) grad_x,
     grad_raw; `need_sums`: grad_a, grad_b -- the workspace and the call.  `v`: the activation that entry point reads, "input" or
     "output" (`what`) of `whose` pass; grad_logdet: a tuple, empty for the entry point that takes none.  `entry`: the name between
-    "finc_coupling" and the suffix of `raw`'s element type; grad_raw is allocated like `raw` (bfloat16 for a bfloat16 `raw`)."""
-    _coupling_args(v, raw, a, b, what)
-    entry = _coupling_entry(entry, raw)
-    _require_device(grad_y, "grad_output")
-    if grad_y.shape != v.shape or grad_y.device != v.device:
-        raise ValueError(f"grad_output must match {whose} in shape and device")
+    "finc_coupling" (or `family`) and the suffix of `raw`'s element type; grad_raw is allocated like `raw` (bfloat16 for a bfloat16
+    `raw`).  grad_y as a tuple: the gradients of the split prior's two half tensors, each of which may be None (absent: NULL)."""
+    if isinstance(grad_y, tuple):
+        _coupling_args(v, raw, a, b, what, halves=grad_y)
+    else:
+        _coupling_args(v, raw, a, b, what)
+        _require_device(grad_y, "grad_output")
+        if grad_y.shape != v.shape or grad_y.device != v.device:
+            raise ValueError(f"grad_output must match {whose} in shape and device")
+        grad_y = (grad_y,)
+    entry = _coupling_entry(entry, raw, family)
     B, C, H, W = v.shape
     for g in grad_logdet:
         _per_image(g, "grad_logdet", v)
@@ -493,7 +509,7 @@ def _coupling_grads(entry, grad_y, grad_logdet, v, raw, a, b, what, whose, need_
     if _nothing_to_launch(v, outs, sums):
         return outs
     nbytes = _lib.lib().finc_coupling_workspace_bytes(B, C, H * W) if any(need_sums) else None
-    _call(entry, v.device, grad_y.data_ptr(), *map(_ptr, grad_logdet), v.data_ptr(), raw.data_ptr(), a.data_ptr(), b.data_ptr(),
+    _call(entry, v.device, *map(_ptr, grad_y), *map(_ptr, grad_logdet), v.data_ptr(), raw.data_ptr(), a.data_ptr(), b.data_ptr(),
           *map(_ptr, outs), B, C, H * W, *_ws_args(v.device, nbytes), _stream_ptr(v))
     return outs
 
@@ -623,6 +639,77 @@ def coupling_reverse_logdet(x, raw, a, b):
     """`finc_coupling_reverse_logdet(x, raw, a, b)` under autograd: returns (y, logdet), gradients for `x`, `raw`, `a` and `b`, each
     computed only where needed."""
     return _FincCouplingReverseLogdetFunction.apply(x, raw, a, b)
+
+
+def finc_split_prior(x, raw, a, b, out=None):
+    """`finc_coupling(x, raw, a, b, +1)` with its two output halves as tensors of their own and the second one scored under a standard
+    normal, in one launch (include/finc.h: finc_split_prior_f32): (x1, z2, log_p) with x1 = x[:, :C/2], z2 = x2 * exp(s) + t -- the
+    bits of the two halves of `finc_coupling`'s y -- and log_p [B] = sum s - 1/2 sum z2^2 - 1/2 (C/2) H W log 2 pi, what
+    `glow.SplitPrior.forward` reports as its second value.  `out`: a pair (x1, z2) of contiguous [B,C/2,H,W] tensors to write into;
+    they may overlap neither `x` nor each other.  Fixed-order sums: the same inputs give the same bits."""
+    _coupling_args(x, raw, a, b, halves=out or ())
+    if out is None:
+        B, C, H, W = x.shape
+        out = tuple(torch.empty(B, C // 2, H, W, dtype=torch.float32, device=x.device) for _ in range(2))
+    elif len(out) != 2 or any(t is None for t in out):
+        raise ValueError("out must be the pair (x1, z2)")
+    return _coupling_transform("", x, raw, a, b, (), True, tuple(out), family="finc_split_prior")
+
+
+def finc_split_prior_merge(x1, z2, raw, a, b, want_log_p=False, out=None):
+    """The inverse of `finc_split_prior`: x = `finc_coupling(cat(x1, z2), raw, a, b, -1)[0]`, bit for bit, without the `cat`
+    (include/finc.h: finc_split_prior_merge_f32).  x1, z2 [B,C/2,H,W] fp32 contiguous, raw [B,C,H,W] the net's output on x1.  Returns
+    x, or (x, log_p) with `want_log_p`: log_p [B] is what `finc_split_prior` reports at x, from the same pass.  `out` [B,C,H,W] may
+    overlap neither half."""
+    if x1 is None or z2 is None:
+        raise ValueError("finc_split_prior_merge needs both halves")
+    _coupling_args(None, raw, a, b, halves=(x1, z2))
+    if out is None:
+        out = torch.empty(raw.shape, dtype=torch.float32, device=raw.device)
+    else:
+        _require_device(out, "output")
+        if out.shape != raw.shape or out.device != raw.device:
+            raise ValueError("output must be [B,C,H,W] like the coupling net's output, on its device")
+    x, log_p = _coupling_transform("_merge", (x1, z2), raw, a, b, (), bool(want_log_p), (out,), family="finc_split_prior")
+    return (x, log_p) if want_log_p else x
+
+
+def finc_split_prior_backward(grad_x1, grad_z2, grad_log_p, x, raw, a, b, need_gx=True, need_graw=True, need_ga=True, need_gb=True):
+    """Gradients of `finc_split_prior` (include/finc.h: finc_split_prior_backward_f32), given the gradients of its three results --
+    grad_x1, grad_z2 [B,C/2,H,W], grad_log_p [B]; each may be None (absent, handed over as NULL), not all three -- and the forward's
+    input `x`: (grad_x, grad_raw, grad_a, grad_b), each computed only if asked for (None otherwise).  grad_x[:, :C/2] is grad_x1: what
+    reaches that half through the net is the caller's (autograd's).  z2 and exp(s) are recomputed from `raw`."""
+    return _coupling_grads("_backward", (grad_x1, grad_z2), (grad_log_p,), x, raw, a, b, "input", "input", (need_gx, need_graw),
+                           (need_ga, need_gb), family="finc_split_prior")
+
+
+class _FincSplitPriorFunction(torch.autograd.Function):
+    """`finc_split_prior` under autograd: (x1, z2, log_p) and their backward on the HIP kernel.  A result nobody used arrives as None
+    and goes to the kernel as NULL."""
+
+    @staticmethod
+    def forward(ctx, x, raw, a, b):
+        x, raw, a, b = x.contiguous(), raw.contiguous(), a.contiguous(), b.contiguous()
+        x1, z2, log_p = finc_split_prior(x, raw, a, b)
+        ctx.save_for_backward(x, raw, a, b)
+        ctx.set_materialize_grads(False)
+        return x1, z2, log_p
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_x1, grad_z2, grad_log_p):
+        x, raw, a, b = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        grads = [None if g is None else g.contiguous() for g in (grad_x1, grad_z2, grad_log_p)]
+        if all(g is None for g in grads):
+            return None, None, None, None
+        return finc_split_prior_backward(*grads, x, raw, a, b, need_gx=need[0], need_graw=need[1], need_ga=need[2], need_gb=need[3])
+
+
+def split_prior_forward(x, raw, a, b):
+    """`finc_split_prior(x, raw, a, b)` under autograd: returns (x1, z2, log_p), gradients for `x`, `raw`, `a` and `b`, each computed
+    only where needed."""
+    return _FincSplitPriorFunction.apply(x, raw, a, b)
 
 
 def finc_bias_relu(x, bias, out=None):

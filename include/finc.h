@@ -392,6 +392,27 @@ int finc_mix_backward_f32(const float *grad_out, const float *in, const float *m
  * finc_bias_relu_bf16: finc_bias_relu_f32 on bfloat16 activations (bits), bias fp32: the add and the max in fp32, rounded to nearest
  *   even once; a NaN stays a NaN; in == out allowed.  16-byte pieces of eight when HW % 8 == 0 and both pointers are 16-byte aligned,
  *   single elements otherwise.
+ * The split prior with its latent (version 114; layers/splitprior.py:7-41 with the factored-out half handed back): the coupling
+ * above whose second output half z2 is scored under a standard normal, with the two halves as tensors of their own.  x1, z2
+ * [B][half][HW] fp32 contiguous, x [B][C][HW], D = half * HW, c = D / 2 * log(2 pi).
+ * finc_split_prior_f32: direction +1 with two outputs, x1 = x[:, :half] and z2[:, j] = x[:, half+j] * exp(s_j) + t_j -- the bits of
+ *   the two halves of finc_coupling_f32(direction +1) -- and log_p[b] = sum_{j,p} s_j - 1/2 sum_{j,p} z2^2 - c: the coupling's
+ *   log-det plus the standard-normal log-density of z2, what SplitPrior.forward reports, from the pass that had z2 in registers
+ *   (-c is added inside the launch).  x1, z2 and log_p are required, and so is a workspace of finc_coupling_workspace_bytes().
+ * finc_split_prior_merge_f32: direction -1 with two inputs: x[:, :half] = x1, x[:, half+j] = (z2[:, j] - t_j) * exp(-s_j): the bits of
+ *   finc_coupling_f32(direction -1) on cat(x1, z2), without that cat.  `log_p` [B] is optional: with it (and the workspace) the
+ *   call reports the value finc_split_prior_f32 reports at the result x, sum s - 1/2 sum z2^2 - c from the z2 it was handed;
+ *   NULL: no partials are written and the workspace is not touched.
+ * finc_split_prior_backward_f32: the gradients of finc_split_prior_f32 given grad_x1, grad_z2 [B][half][HW] and grad_log_p [B]
+ *   -- each may be NULL (zeros), not all three -- and the forward's INPUT x.  With E = exp(s) and z2 = x2 * E + t recomputed from
+ *   raw and G = grad_z2 - grad_log_p[b] * z2:
+ *     grad_x[:, :half] = grad_x1,   grad_x[:, half+j] = G * E_j,
+ *     grad_h[:, 2j+1] = G,   grad_h[:, 2j] = (G * E_j * x[:, half+j] + grad_log_p[b]) * (1 - s_j^2 / 4),
+ *   grad_raw, grad_a and grad_b from grad_h as for finc_coupling_backward_f32; outputs, workspace and status as there.
+ * Aliasing: x1, z2 and x may not overlap each other, nor may an output be raw (FINC_ERR_BAD_DIMS); the backward's outputs may
+ *   alias no input and not each other.  The sums are fixed-order without atomics: the same inputs give the same bits.  The
+ *   16-byte-piece form wants every activation pointer of the call, the half tensors included, on 16 bytes.  Each has its
+ *   _rawbf16_f32 sibling, under the rules of the six above.
  * Status: a NULL required pointer FINC_ERR_NULL_POINTER, non-positive dims FINC_ERR_BAD_DIMS, odd C FINC_ERR_UNSUPPORTED
  * (finc_coupling_supported_f32(C) == 0), a missing / short workspace where one is needed FINC_ERR_WORKSPACE.
  */
@@ -436,6 +457,23 @@ int finc_coupling_backward_reconstruct_rawbf16_f32(const float *grad_y, const fl
                                                    float *grad_a, float *grad_b, int B, int C, int HW, void *workspace,
                                                    size_t workspace_bytes, finc_stream_t stream);
 int finc_bias_relu_bf16(const uint16_t *in, const float *bias, uint16_t *out, int B, int C, int HW, finc_stream_t stream);
+int finc_split_prior_f32(const float *x, const float *raw, const float *a, const float *b, float *x1, float *z2, float *log_p, int B,
+                         int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream);
+int finc_split_prior_merge_f32(const float *x1, const float *z2, const float *raw, const float *a, const float *b, float *x,
+                               float *log_p, int B, int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream);
+int finc_split_prior_backward_f32(const float *grad_x1, const float *grad_z2, const float *grad_log_p, const float *x,
+                                  const float *raw, const float *a, const float *b, float *grad_x, float *grad_raw, float *grad_a,
+                                  float *grad_b, int B, int C, int HW, void *workspace, size_t workspace_bytes,
+                                  finc_stream_t stream);
+int finc_split_prior_rawbf16_f32(const float *x, const uint16_t *raw, const float *a, const float *b, float *x1, float *z2,
+                                 float *log_p, int B, int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream);
+int finc_split_prior_merge_rawbf16_f32(const float *x1, const float *z2, const uint16_t *raw, const float *a, const float *b, float *x,
+                                       float *log_p, int B, int C, int HW, void *workspace, size_t workspace_bytes,
+                                       finc_stream_t stream);
+int finc_split_prior_backward_rawbf16_f32(const float *grad_x1, const float *grad_z2, const float *grad_log_p, const float *x,
+                                          const uint16_t *raw, const float *a, const float *b, float *grad_x, uint16_t *grad_raw,
+                                          float *grad_a, float *grad_b, int B, int C, int HW, void *workspace,
+                                          size_t workspace_bytes, finc_stream_t stream);
 
 /*
  * ActNorm (layers/actnorm.py:5-66) on its own kernels: activations [B][C][HW] fp32, log_scale and translation [C], any C >= 1
