@@ -47,6 +47,7 @@ SYMBOLS = [
     "finc_coupling_backward_reconstruct_rawbf16_f32", "finc_bias_relu_bf16",
     "finc_split_prior_f32", "finc_split_prior_merge_f32", "finc_split_prior_backward_f32",
     "finc_split_prior_rawbf16_f32", "finc_split_prior_merge_rawbf16_f32", "finc_split_prior_backward_rawbf16_f32",
+    "finc_image_workspace_bytes", "finc_image_encode_u8_f32", "finc_image_encode_f32", "finc_image_decode_f32", "finc_image_decode_u8",
 ]
 
 #: the ABI version this binding is written against (include/finc.h: finc_version)
@@ -78,6 +79,9 @@ AUTOCAST_ABI_VERSION = 113
 #: the version that added the split prior with its latent (finc_split_prior_f32, finc_split_prior_merge_f32,
 #: finc_split_prior_backward_f32 and their _rawbf16_f32 siblings): what SplitPrior.split / merge and FlowSequential.encode / decode launch
 SPLIT_LATENT_ABI_VERSION = 114
+#: the version that added the image boundary (finc_image_encode_u8_f32, finc_image_encode_f32, finc_image_decode_f32,
+#: finc_image_decode_u8): what FlowSequential.fuse_image_boundary and sample_uint8 launch
+IMAGE_BOUNDARY_ABI_VERSION = 115
 
 _lib = None
 
@@ -144,6 +148,11 @@ def lib():
         raise FincError(f"{LIB_PATH} reports finc_version() = {have}, the split prior's entry points (finc_split_prior_f32, "
                         f"finc_split_prior_merge_f32, finc_split_prior_backward_f32 and their bfloat16 siblings) came with "
                         f"{SPLIT_LATENT_ABI_VERSION}: rebuild it "
+                        "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
+    if have < IMAGE_BOUNDARY_ABI_VERSION:
+        raise FincError(f"{LIB_PATH} reports finc_version() = {have}, the image boundary's entry points (finc_image_encode_u8_f32, "
+                        f"finc_image_encode_f32, finc_image_decode_f32, finc_image_decode_u8) came with "
+                        f"{IMAGE_BOUNDARY_ABI_VERSION}: rebuild it "
                         "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
     L.finc_build_flags.restype = u
     L.finc_clear_fault.restype = i
@@ -238,6 +247,13 @@ def lib():
     L.finc_split_prior_backward_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp]
     for name in ("finc_split_prior", "finc_split_prior_merge", "finc_split_prior_backward"):
         getattr(L, name + "_rawbf16_f32").argtypes = getattr(L, name + "_f32").argtypes
+    fl = ctypes.c_float
+    L.finc_image_workspace_bytes.restype = sz
+    L.finc_image_workspace_bytes.argtypes = [i, i, i, i, i]
+    L.finc_image_encode_u8_f32.argtypes = [vp, vp, vp, vp, i, i, i, i, i, fl, fl, fl, fl, fl, vp, sz, vp]
+    L.finc_image_encode_f32.argtypes = L.finc_image_encode_u8_f32.argtypes
+    L.finc_image_decode_f32.argtypes = [vp, vp, vp, i, i, i, i, i, fl, fl, fl, fl, vp, sz, vp]
+    L.finc_image_decode_u8.argtypes = L.finc_image_decode_f32.argtypes
     for name in SYMBOLS:
         getattr(L, name)  # AttributeError here = header and library out of sync
     _lib = L

@@ -190,7 +190,7 @@ static int canonicalize(const T *w_stored, T *w_canon, int G, int Cq, int KH, in
 
 extern "C" {
 
-int finc_version(void) { return 114; }
+int finc_version(void) { return 115; }
 
 unsigned finc_build_flags(void)
 {
@@ -869,6 +869,99 @@ int finc_bias_relu_f32(const float *in, const float *bias, float *out, int B, in
 int finc_bias_relu_bf16(const uint16_t *in, const float *bias, uint16_t *out, int B, int C, int HW, finc_stream_t stream)
 {
     return bias_relu(in, bias, out, B, C, HW, stream);
+}
+
+// ---- the image boundary (finc_image.h): B, C, H, W are the image's; `squeeze` 1: the other side is [B][4C][H/2][W/2] ----
+static int image_dims(int B, int C, int H, int W, int squeeze)
+{
+    if (H <= 0 || W <= 0 || (long long)H * W >= (1LL << 31)) return FINC_ERR_BAD_DIMS;
+    if (int e = pixel_dims(B, C, H * W, false)) return e;
+    if ((squeeze != 0 && squeeze != 1) || (squeeze && (H % 2 || W % 2))) return FINC_ERR_BAD_DIMS;
+    return (size_t)C * H * W * 4 >= ((size_t)1 << 31) ? FINC_ERR_BAD_DIMS : FINC_OK;           // (cpl_launch's limit: int offsets per image)
+}
+
+size_t finc_image_workspace_bytes(int B, int C, int H, int W, int squeeze)
+{
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return 256;
+    return padded_ws_bytes(finc_image_workspace_floats(B, C, H, W, squeeze) * sizeof(float));
+}
+
+extern "C++" {
+static int image_encode_launch(const uint8_t *img, const float *noise, float *out, float *logdet, int B, int C, int H, int W, int squeeze,
+                               float m, float c, float hi, float c2, float ldc, float *ws, hipStream_t st)
+{
+    return finc_image_encode_u8_launch(img, noise, out, logdet, B, C, H, W, squeeze, m, c, hi, c2, ldc, ws, st);
+}
+static int image_encode_launch(const float *img, const float *noise, float *out, float *logdet, int B, int C, int H, int W, int squeeze,
+                               float m, float c, float hi, float c2, float ldc, float *ws, hipStream_t st)
+{
+    return finc_image_encode_f32_launch(img, noise, out, logdet, B, C, H, W, squeeze, m, c, hi, c2, ldc, ws, st);
+}
+static int image_decode_launch(const float *z, uint8_t *out, float *logdet, int B, int C, int H, int W, int unsqueeze, float inv_m, float off,
+                               float hi, float ldc, float *ws, hipStream_t st)
+{
+    return finc_image_decode_u8_launch(z, out, logdet, B, C, H, W, unsqueeze, inv_m, off, hi, ldc, ws, st);
+}
+static int image_decode_launch(const float *z, float *out, float *logdet, int B, int C, int H, int W, int unsqueeze, float inv_m, float off,
+                               float hi, float ldc, float *ws, hipStream_t st)
+{
+    return finc_image_decode_f32_launch(z, out, logdet, B, C, H, W, unsqueeze, inv_m, off, hi, ldc, ws, st);
+}
+
+// One ladder per direction, T the pixel type (uint8_t, float).  In place (out on the input) only where nothing is permuted and both
+// sides are fp32; a uint8 tensor has no alignment rule.
+template <typename T>
+static int image_encode(const T *img, const float *noise, float *out, float *logdet, int B, int C, int H, int W, int squeeze, float m,
+                        float c, float hi, float c2, float ldc, void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    if (!img || !out || !logdet) return FINC_ERR_NULL_POINTER;
+    if (int e = image_dims(B, C, H, W, squeeze)) return e;
+    if ((squeeze || sizeof(T) != 4) && ((const void *)out == (const void *)img)) return FINC_ERR_BAD_DIMS;
+    if (squeeze && out == noise) return FINC_ERR_BAD_DIMS;
+    if (misaligned(noise, out, logdet) || (sizeof(T) == 4 && misaligned(img))) return FINC_ERR_ALIGNMENT;
+    if (workspace_short(workspace, workspace_bytes, finc_image_workspace_bytes(B, C, H, W, squeeze))) return FINC_ERR_WORKSPACE;
+    if (int e = finc_fault_gate(false)) return e;
+    return image_encode_launch(img, noise, out, logdet, B, C, H, W, squeeze, m, c, hi, c2, ldc, (float *)workspace, (hipStream_t)stream);
+}
+
+template <typename T>
+static int image_decode(const float *z, T *out, float *logdet, int B, int C, int H, int W, int unsqueeze, float inv_m, float off, float hi,
+                        float ldc, void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    if (!z || !out) return FINC_ERR_NULL_POINTER;
+    if (int e = image_dims(B, C, H, W, unsqueeze)) return e;
+    if (sizeof(T) == 1 && !(hi >= 1.f && hi <= 256.f)) return FINC_ERR_BAD_DIMS;                 // the clamp's top must fit a byte
+    if ((unsqueeze || sizeof(T) != 4) && ((const void *)out == (const void *)z)) return FINC_ERR_BAD_DIMS;
+    if (misaligned(z, logdet) || (sizeof(T) == 4 && misaligned(out))) return FINC_ERR_ALIGNMENT;
+    if (logdet && workspace_short(workspace, workspace_bytes, finc_image_workspace_bytes(B, C, H, W, unsqueeze))) return FINC_ERR_WORKSPACE;
+    if (int e = finc_fault_gate(false)) return e;
+    return image_decode_launch(z, out, logdet, B, C, H, W, unsqueeze, inv_m, off, hi, ldc, (float *)workspace, (hipStream_t)stream);
+}
+} // extern "C++"
+
+int finc_image_encode_u8_f32(const uint8_t *img, const float *noise, float *out, float *logdet, int B, int C, int H, int W, int squeeze,
+                             float mult, float lo, float hi, float hi_comp, float logdet_const, void *workspace, size_t workspace_bytes,
+                             finc_stream_t stream)
+{
+    return image_encode(img, noise, out, logdet, B, C, H, W, squeeze, mult, lo, hi, hi_comp, logdet_const, workspace, workspace_bytes, stream);
+}
+
+int finc_image_encode_f32(const float *img, const float *noise, float *out, float *logdet, int B, int C, int H, int W, int squeeze, float mult,
+                          float lo, float hi, float hi_comp, float logdet_const, void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    return image_encode(img, noise, out, logdet, B, C, H, W, squeeze, mult, lo, hi, hi_comp, logdet_const, workspace, workspace_bytes, stream);
+}
+
+int finc_image_decode_f32(const float *z, float *out, float *logdet, int B, int C, int H, int W, int unsqueeze, float inv_mult, float off,
+                          float hi, float logdet_const, void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    return image_decode(z, out, logdet, B, C, H, W, unsqueeze, inv_mult, off, hi, logdet_const, workspace, workspace_bytes, stream);
+}
+
+int finc_image_decode_u8(const float *z, uint8_t *out, float *logdet, int B, int C, int H, int W, int unsqueeze, float inv_mult, float off,
+                         float hi, float logdet_const, void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    return image_decode(z, out, logdet, B, C, H, W, unsqueeze, inv_mult, off, hi, logdet_const, workspace, workspace_bytes, stream);
 }
 
 size_t finc_actnorm_workspace_bytes(int B, int C, int HW)

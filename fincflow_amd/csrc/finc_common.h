@@ -342,6 +342,18 @@ int finc_actnorm_launch(const float *x, const float *ls, const float *tr, float 
 int finc_actnorm_grad_launch(FincGradMode mode, const float *gy, const float *gld, const float *v, const float *ls, const float *tr,
                              float *xo, float *gx, float *gls, float *gt, int B, int C, int HW, float *ws, hipStream_t st);
 int finc_actnorm_init_launch(const float *x, float *ls, float *tr, int B, int C, int HW, float *ws, hipStream_t st);
+// ---- the image boundary (dequantise + normalise + logit + squeeze in one launch, and back): finc_image.h, same object ----
+// B, C, H, W: the IMAGE side; with (un)squeeze the other side is [B][4C][H/2][W/2].  `ws` holds finc_image_workspace_floats floats
+// (the encode always, the decode with logdet).  noise and the decode's logdet may be nullptr.
+size_t finc_image_workspace_floats(int B, int C, int H, int W, int squeeze);
+int finc_image_encode_u8_launch(const uint8_t *img, const float *noise, float *out, float *logdet, int B, int C, int H, int W, int squeeze,
+                                float m, float c, float hi, float c2, float ldc, float *ws, hipStream_t st);
+int finc_image_encode_f32_launch(const float *img, const float *noise, float *out, float *logdet, int B, int C, int H, int W, int squeeze,
+                                 float m, float c, float hi, float c2, float ldc, float *ws, hipStream_t st);
+int finc_image_decode_f32_launch(const float *z, float *out, float *logdet, int B, int C, int H, int W, int unsqueeze, float inv_m, float off,
+                                 float hi, float ldc, float *ws, hipStream_t st);
+int finc_image_decode_u8_launch(const float *z, uint8_t *out, float *logdet, int B, int C, int H, int W, int unsqueeze, float inv_m, float off,
+                                float hi, float ldc, float *ws, hipStream_t st);
 // ---- backward through the unit's inverse (adjoint bank, lead product, the weight gradient's sign): finc_adjoint.h, same object ----
 // w_adj [G*Cq][Cq][KH][KW]: the canonical bank whose inverse (orientation complemented) is the adjoint solve up to the lead product;
 // lead_t [C][C]: blockdiag(Linv_g^T), row = output channel

@@ -257,6 +257,7 @@ int finc_mix_launch(const float *in, const float *mat, const float *bias, float 
 }
 
 #include "finc_coupling.h"
+#include "finc_image.h"
 #include "finc_actnorm.h"
 #include "finc_adjoint.h"
 

@@ -24,6 +24,8 @@ Reference semantics followed:
                  hand that half out and take it back (FlowSequential.encode / decode), one HIP launch each (ops.finc_split_prior,
                  ops.finc_split_prior_merge, ops.split_prior_forward)
   Normalization, LogitTransform, Dequantization  layers/normalize.py, transforms.py:6-19, dequantize.py
+                 with `FlowSequential.fuse_image_boundary` these and the first Squeeze are one HIP launch each way
+                 (ops.finc_image_encode, ops.finc_image_decode: uint8 or fp32 images in, fp32 or uint8 images out)
   GaussianPrior  train/losses.py:17-45           standard-normal base (log_prob per sample, sample(n))
 """
 import math

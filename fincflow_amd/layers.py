@@ -11,6 +11,7 @@ so a reference `FlowSequential` (layers/flowsequential.py:21-44,89-115) or
 `FastFlowStep` (fastflow_cifar_multi_gpu.py:224-256) can hold them unchanged.
 The arithmetic runs in libfinc_hip.so; there is no CPU path.
 """
+import math
 from abc import ABCMeta, abstractmethod
 from typing import NamedTuple
 
@@ -439,6 +440,23 @@ class StandardNormal(nn.Module):
         return torch.randn(n_samples, *self.size, device=self._anchor.device, dtype=self._anchor.dtype), None
 
 
+def _image_boundary_layers(mods):
+    """The image boundary at the head of `mods` (forward order): `(normalisations, length, squeeze)` for exactly [Dequantization, one
+    or more Normalization with buffers (not learnable), LogitTransform, (Squeeze)] -- `length` counts the Squeeze when `squeeze` -- or
+    None for anything else: a learnable Normalization, a subclass, a layer in between."""
+    from . import glow
+    if len(mods) < 3 or type(mods[0]) is not glow.Dequantization:
+        return None
+    j = 1
+    while (j < len(mods) and type(mods[j]) is glow.Normalization
+           and not any(isinstance(p, nn.Parameter) for p in (mods[j].scale, mods[j].translation))):
+        j += 1
+    if j == 1 or j >= len(mods) or type(mods[j]) is not glow.LogitTransform:
+        return None
+    squeeze = j + 1 < len(mods) and type(mods[j + 1]) is glow.Squeeze
+    return list(mods[1:j]), j + 1 + int(squeeze), squeeze
+
+
 class _InvertibleRunFunction(torch.autograd.Function):
     """A run of layers that support `backward_from_output`, as one autograd node (FlowSequential.invertible_backward).
     Inputs: the activation, the context, every parameter of the run.  Outputs: the run's output and its summed log-det [B].
@@ -533,6 +551,10 @@ class FlowSequential(nn.Module):
         """`mods` in order on `input`: (output, `logdet` plus the sum of their log-dets).  `latents`: a list that receives what
         every layer with a `split` factors out (`encode`); None: the layers' `forward`."""
         i = 0
+        head = self._encode_image(mods, input) if self.fuse_image_boundary else None
+        if head is not None:
+            i, input, head_logdet = head
+            logdet = logdet + head_logdet
         while i < len(mods):
             module = mods[i]
             # density evaluation: a FastFlowUnit followed by an (initialised) per-channel affine layer is one launch
@@ -582,6 +604,9 @@ class FlowSequential(nn.Module):
         supports no invertible backward: it ends a run and is walked here.)"""
         logdet = 0
         i = 0
+        head = self._encode_image(mods, input) if self.fuse_image_boundary else None
+        if head is not None:          # (a Squeeze the encode took is not part of the invertible run behind it)
+            i, input, logdet = head
         while i < len(mods):
             j = self._invertible_run_end(mods, i, input, context)
             if j - i >= 2:
@@ -610,20 +635,99 @@ class FlowSequential(nn.Module):
     fuse_affine = True
     #: let the channel mix in front of a FastFlowUnit (reverse chain) apply the unit's blockdiag(Linv) as well
     fuse_lead = True
+    #: the image boundary on its HIP kernels: the prefix [Dequantization, Normalization(s), LogitTransform, (Squeeze)]
+    #: of `forward` / `encode` is ONE launch (`ops.finc_image_encode`) and so is the tail of the reverse chain
+    #: (`ops.finc_image_decode`), for uint8 or fp32 device images.  Off by default, set per instance: the fused encode computes 1 - y
+    #: from the integer pixel and is right at saturated pixels where the layers' lines are not, so its bits are not theirs.
+    fuse_image_boundary = False
 
-    def _reverse_chain(self, input, context, fuse=None, with_logdet=False, latents=None):
+    def image_boundary_constants(self):
+        """What the image boundary's kernels take, composed in float64 from the Normalization buffers' values, or None -- a stack
+        without the boundary layers, or a first use inside a stream capture (reading the buffers is a device -> host copy).  With y =
+        (..((v - t1) / s1 - t2) / s2..): `mult` = 1 / prod s, `lo` = y at v = 0, `hi` = s1 (the number of grey levels), `hi_comp` = 1 -
+        lo - mult * hi (so that 1 - y = mult * (hi - v) + hi_comp), `inv_mult` and `off` of the reverse v = inv_mult * y + off, and
+        `sum_log_scale` = sum log s (the per-image log-det constant is -D times it).  Cached per `ops.version_key` of the buffers."""
+        found = _image_boundary_layers(list(self.sequence_modules))
+        if found is None:
+            return None
+        bufs = [b for n in found[0] for b in (n.translation, n.scale)]
+        key = ops.version_key(*bufs)
+        if getattr(self, "_image_key", None) != key:
+            if bufs[0].is_cuda and ops._capturing():
+                return None
+            with torch.no_grad():
+                vals = torch.cat([b.detach().double().reshape(1) for b in bufs]).tolist()
+            mult, lo, inv_mult, off, sum_log = 1.0, 0.0, 1.0, 0.0, 0.0
+            for t, s in zip(vals[0::2], vals[1::2]):
+                mult, lo, sum_log = mult / s, (lo - t) / s, sum_log + math.log(s)
+            for t, s in reversed(list(zip(vals[0::2], vals[1::2]))):
+                inv_mult, off = inv_mult * s, off * s + t
+            hi = vals[1]
+            self._image_consts = dict(mult=mult, lo=lo, hi=hi, hi_comp=1.0 - lo - mult * hi, inv_mult=inv_mult, off=off,
+                                      sum_log_scale=sum_log)
+            self._image_key = key
+        return self._image_consts
+
+    def _encode_image(self, mods, input):
+        """The image boundary at the head of `mods` as one launch on `input`: `(layers consumed, output, logdet[B])`, or None where
+        the layers run as they always have -- no boundary at the head, a tensor that is not a 4-D uint8 / fp32 device tensor, an input
+        that requires grad (the encode has no backward), odd sides in front of a Squeeze (left to the layer), constants not yet
+        cached inside a stream capture.  The noise is the layer's draw: `torch.rand` of the image's shape, fp32, on its device."""
+        found = _image_boundary_layers(mods)
+        if (found is None or not input.is_cuda or input.dim() != 4 or input.dtype not in (torch.uint8, torch.float32)
+                or input.requires_grad or input.numel() == 0):
+            return None
+        k = self.image_boundary_constants() if mods[0] is self.sequence_modules[0] else None
+        if k is None:
+            return None
+        _, n, squeeze = found
+        if squeeze and (input.shape[2] % 2 or input.shape[3] % 2):
+            n, squeeze = n - 1, False
+        noise = torch.rand(input.shape, dtype=torch.float32, device=input.device)
+        out, logdet = ops.finc_image_encode(input.contiguous(), noise, mult=k["mult"], lo=k["lo"], hi=k["hi"], hi_comp=k["hi_comp"],
+                                            logdet_const=-input[0].numel() * k["sum_log_scale"], squeeze=squeeze)
+        return n, out, logdet
+
+    def _decode_image(self, input, squeeze, with_logdet, dtype):
+        """The tail of the reverse chain on `input`, the activation in front of the boundary's reverse: x, or `(x, logdet[B])`."""
+        k = self.image_boundary_constants()
+        ldc = -input[0].numel() * k["sum_log_scale"] if with_logdet else None
+        return ops.finc_image_decode(input.contiguous(), inv_mult=k["inv_mult"], off=k["off"], hi=k["hi"], logdet_const=ldc,
+                                     unsqueeze=squeeze, dtype=dtype)
+
+    def _image_tail(self, input, squeeze):
+        """Does one decode launch serve `input` at the boundary's end of the reverse chain?  An fp32 4-D device tensor that records
+        no graph, four channels per image channel in front of a Squeeze, the constants at hand."""
+        if not _hip_tensor(input) or _records_graph(input) or input.numel() == 0 or (squeeze and input.shape[1] % 4):
+            return False
+        return self.image_boundary_constants() is not None
+
+    def _reverse_chain(self, input, context, fuse=None, with_logdet=False, latents=None, image_dtype=torch.float32):
         """The layers' reverses, last layer first.  `with_logdet`: returns `(x, logdet[B])`, the sum of the layers' FORWARD log-dets
         at their recovered inputs (`reverse_with_logdet`), in the same pass: every fold below stays, and a folded per-channel affine
         layer or channel mix adds its term -- parameters only, a few [C]-sized ops or a cached number -- beside the fused launch (the
         unit's own is zero).  `latents`: the factored-out halves of the layers with a `merge`, in FORWARD order (`decode`): each such
-        layer takes its own through `merge` instead of drawing one in `reverse`, and its log p takes the log-det's place."""
+        layer takes its own through `merge` instead of drawing one in `reverse`, and its log p takes the log-det's place.
+        With `fuse_image_boundary` the image boundary's reverse at the end of the chain is one launch (`_decode_image`) that writes
+        `image_dtype` (fp32: the layers' floor; uint8: clamped, `sample_uint8`); `fuse=False`, the layer-by-layer check of `sample`,
+        keeps the layers there too."""
+        layer_by_layer = fuse is False
         fuse = self.fuse_affine if fuse is None else fuse
         mods = list(reversed(self.sequence_modules))
         latents = None if latents is None else list(latents)
         logdet = input.new_zeros(len(input)) if with_logdet else None
+        boundary = _image_boundary_layers(list(self.sequence_modules)) if self.fuse_image_boundary and not layer_by_layer else None
+        tail = len(mods) - boundary[1] if boundary is not None else -1       # where the image boundary's reverse begins
         i = 0
         while i < len(mods):
             m = mods[i]
+            if i == tail and self._image_tail(input, boundary[2]):
+                out = self._decode_image(input, boundary[2], with_logdet, image_dtype)
+                if with_logdet:
+                    input, logdet = out[0], logdet + out[1]
+                else:
+                    input = out
+                break
             if (fuse and i + 1 < len(mods) and hasattr(m, "reverse_affine_params")
                     and isinstance(mods[i + 1], FastFlowUnit) and not torch.is_grad_enabled()):
                 fused = mods[i + 1].reverse_affine(input, *m.reverse_affine_params())
@@ -795,3 +899,27 @@ class FlowSequential(nn.Module):
         there is `decode(encode(input)[0])`."""
         z = self.forward(input, context)[0]
         return self._reverse_chain(z, context)
+
+    def sample_uint8(self, n_samples, context=None, temperature=1.0):
+        """`n_samples` images as uint8 [n, C, H, W]: `sample(n_samples, context, temperature=temperature)[0]` clamped to the grey
+        levels [0, hi - 1] (hi: the first Normalization's scale, 256) and cast -- from one seed the same draws.  Needs the image
+        boundary layers at the head of the stack (ValueError without them).  With `fuse_image_boundary` the decode launch writes the
+        bytes itself; otherwise the layers' fp32 result is clamped and cast.  Runs under `torch.no_grad()`."""
+        if _image_boundary_layers(list(self.sequence_modules)) is None:
+            raise ValueError("sample_uint8 needs the image boundary at the head of the stack: Dequantization, Normalization layers "
+                             "with fixed buffers, LogitTransform (create_model(preprocess=True))")
+        with torch.no_grad():
+            zs = self.draw_latents(n_samples, context, temperature)
+            x = self._reverse_chain(zs[-1], context, latents=zs[:-1], image_dtype=torch.uint8)
+            if x.dtype != torch.uint8:
+                k = self.image_boundary_constants()
+                if k is None:
+                    raise RuntimeError("sample_uint8 reads the Normalization buffers on its first call: call it once outside the capture")
+                x = x.clamp(0, k["hi"] - 1).to(torch.uint8)
+        if x.is_cuda:
+            _lib.raise_if_faulted("FlowSequential.sample_uint8")
+        return x
+
+    def bits_per_dim(self, input, context=None):
+        """-log_prob(input) / (D ln 2) per image, [B]: D the number of values of one image."""
+        return -self.log_prob(input, context) / (input[0].numel() * math.log(2.0))

@@ -730,6 +730,76 @@ def finc_bias_relu(x, bias, out=None):
     return out
 
 
+def _image_sides(t, squeeze, squeezed_side):
+    """((B, C, H, W) of the image, the other side's shape) from a tensor of either side of the image boundary."""
+    if t.dim() != 4:
+        raise ValueError("expected a tensor [B,C,H,W]")
+    B, C, H, W = t.shape
+    if not squeeze:
+        return (B, C, H, W), (B, C, H, W)
+    if squeezed_side:
+        if C % 4:
+            raise ValueError("a squeezed tensor has 4 channels per image channel")
+        return (B, C // 4, 2 * H, 2 * W), (B, C, H, W)
+    if H % 2 or W % 2:
+        raise ValueError("squeeze needs an even height and width")
+    return (B, C, H, W), (B, 4 * C, H // 2, W // 2)
+
+
+def _image_out(t, shape, out, dtype):
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=t.device)
+    return _out_like(t.new_empty((), dtype=dtype).expand(shape), out, dtype)
+
+
+def _image_call(name, t, ptrs, dims, flag, consts, logdet, needs_ws):
+    nbytes = _lib.lib().finc_image_workspace_bytes(*dims, flag) if needs_ws else None
+    _call(name, t.device, *ptrs, _ptr(logdet), *dims, flag, *(float(v) for v in consts), *_ws_args(t.device, nbytes), _stream_ptr(t))
+
+
+def finc_image_encode(img, noise=None, *, mult, lo, hi, hi_comp, logdet_const, squeeze=True, out=None):
+    """The image boundary in one HIP launch (include/finc.h: finc_image_encode_u8_f32 / finc_image_encode_f32): what Dequantization,
+    the Normalization layers, LogitTransform and the first Squeeze compute.  img [B,C,H,W] uint8 or fp32 (whole numbers), contiguous on
+    the device; noise fp32 of the same shape or None (zero).  Per element y = mult * (img + noise) + lo and 1 - y = mult * ((hi - img) -
+    noise) + hi_comp -- the caller composes the four numbers in double precision, hi_comp = 1 - lo - mult * hi -- and the result is
+    log y - log(1 - y), [B,4C,H/2,W/2] in the reference's squeeze order (`squeeze`) or [B,C,H,W].  Returns (y, logdet): logdet [B] =
+    logdet_const - sum(log y + log(1 - y)) per image, fixed-order sums.  `out` may be `img` for fp32 pixels without squeeze."""
+    u8 = img.dtype == torch.uint8
+    _require_device(img, "image", torch.uint8 if u8 else torch.float32)
+    dims, shape = _image_sides(img, squeeze, False)
+    if noise is not None:
+        _require_device(noise, "noise")
+        if noise.shape != img.shape or noise.device != img.device:
+            raise ValueError("noise must match the image in shape and device")
+    out = _image_out(img, shape, out, torch.float32)
+    logdet = torch.empty(dims[0], dtype=torch.float32, device=img.device)
+    if _nothing_to_launch(img, (out,), (logdet,)):
+        return out, logdet
+    _image_call("finc_image_encode_u8_f32" if u8 else "finc_image_encode_f32", img, (img.data_ptr(), _ptr(noise), out.data_ptr()), dims,
+                int(bool(squeeze)), (mult, lo, hi, hi_comp, logdet_const), logdet, True)
+    return out, logdet
+
+
+def finc_image_decode(z, *, inv_mult, off, hi, logdet_const=None, unsqueeze=True, dtype=torch.float32, out=None):
+    """The inverse of `finc_image_encode` up to the floor, in one HIP launch (finc_image_decode_f32 / finc_image_decode_u8): z fp32
+    [B,4C,h,w] (`unsqueeze`: the image is [B,C,2h,2w]) or [B,C,H,W]; v = sigmoid(z) * inv_mult + off.  `dtype` torch.float32: floor(v),
+    not clamped (what Dequantization.reverse returns); torch.uint8: floor(v) clamped to [0, hi - 1].  With `logdet_const`: (x, logdet),
+    logdet [B] = logdet_const + sum(|z| + 2 log(1 + exp(-|z|))) per image -- the log-det `finc_image_encode` reports at the value in
+    front of the floor; without: x alone.  `out`: a contiguous image-shaped tensor of `dtype` to write into; an fp32 one may be `z`
+    without `unsqueeze`."""
+    if dtype not in (torch.float32, torch.uint8):
+        raise ValueError("finc_image_decode writes float32 or uint8")
+    _require_device(z, "input")
+    dims, _ = _image_sides(z, unsqueeze, True)
+    out = _image_out(z, dims, out, dtype)
+    want = logdet_const is not None
+    logdet = torch.empty(dims[0], dtype=torch.float32, device=z.device) if want else None
+    if not _nothing_to_launch(z, (out,), (logdet,)):
+        _image_call("finc_image_decode_u8" if dtype == torch.uint8 else "finc_image_decode_f32", z, (z.data_ptr(), out.data_ptr()), dims,
+                    int(bool(unsqueeze)), (inv_mult, off, hi, logdet_const if want else 0.0), logdet, want)
+    return (out, logdet) if want else out
+
+
 def actnorm_supported():
     """ActNorm's kernels take any channel count, and a library without them does not load (fincflow_amd._lib: ACTNORM_ABI_VERSION):
     True once the library is loaded, no call into it per layer and pass."""

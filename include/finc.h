@@ -543,6 +543,44 @@ int finc_actnorm_init_f32(const float *x, float *log_scale, float *translation, 
                           size_t workspace_bytes, finc_stream_t stream);
 
 /*
+ * The image boundary (version 115; layers/dequantize.py, layers/normalize.py, layers/transforms.py:6-19, layers/squeeze.py:5-41): what
+ * every model starts with -- Dequantization, Normalization(s), LogitTransform, Squeeze -- as ONE streaming launch per direction.
+ * B, C, H, W describe the IMAGE side in every call; with squeeze / unsqueeze = 1 the other side is [B][4C][H/2][W/2] in the
+ * reference's channel order, side[b][4c + 2dy + dx][h][w] <-> image[b][c][2h + dy][2w + dx] (odd H or W: FINC_ERR_BAD_DIMS), with 0
+ * it is [B][C][H][W].
+ * finc_image_encode_u8_f32 / finc_image_encode_f32: per element, x the pixel (uint8, or fp32 holding the same numbers) and u the
+ *   noise (fp32, image-shaped; NULL = 0):  yl = fma(mult, x + u, lo);  yr = fma(mult, (hi - x) - u, hi_comp);  out = log yl - log yr;
+ *   logdet[b] = logdet_const + sum over the image of -(log yl + log yr).  For y = ((x + u - t1) / s1 - t2) / s2 the caller composes,
+ *   in double precision, mult = 1 / (s1 s2), lo = -t1 / (s1 s2) - t2 / s2, hi = s1, hi_comp = 1 - lo - mult hi (so yr = 1 - y without
+ *   ever rounding y: hi - x is exact) and logdet_const = -C H W (log s1 + log s2).  The two entry points give the same bits on the
+ *   same numbers.  `logdet` [B] and the workspace are required.  out == img: allowed for fp32 pixels without squeeze, refused with
+ *   squeeze (it permutes: FINC_ERR_BAD_DIMS), as is out == noise.
+ * finc_image_decode_f32 / finc_image_decode_u8: z fp32 on the squeezed side;  v = fma(sigmoid(z), inv_mult, off);  the fp32 output
+ *   is floor(v), not clamped (Dequantization.reverse); the uint8 output is floor(v) clamped to [0, hi - 1] (1 <= hi <= 256, else
+ *   FINC_ERR_BAD_DIMS; a NaN gives 0).  `logdet` (optional; needs the workspace): logdet_const + sum over the image of |z| + 2
+ *   log(1 + exp(-|z|)), the FORWARD map's log-det at the recovered value.  out == z: allowed for the fp32 output without unsqueeze.
+ * The per-image sums run in a fixed order (no atomics): the same inputs give the same bits.  With squeeze a thread moves two image
+ * rows of 8 pixels and four 16-byte pieces of the other side when W % 8 == 0, every fp32 tensor is 16-byte aligned and a uint8 one
+ * 8-byte aligned; one 2 x 2 patch in dwords (bytes) otherwise.  Without squeeze: 16-byte pieces of four when H W % 4 == 0, fp32
+ * tensors are 16-byte and a uint8 one 4-byte aligned; single elements otherwise.
+ * finc_image_workspace_bytes: > 0 for any arguments, never shrinks when B, H or W grows.
+ * Status: a NULL required pointer FINC_ERR_NULL_POINTER; non-positive / odd / overflowing dims (an image of 2 GiB or more as fp32),
+ * squeeze other than 0 / 1 or forbidden aliasing FINC_ERR_BAD_DIMS; an fp32 pointer not 4-byte aligned FINC_ERR_ALIGNMENT; a missing
+ * / short workspace where one is needed FINC_ERR_WORKSPACE -- in that order, before any HIP call; then the sticky-fault rule below.
+ */
+size_t finc_image_workspace_bytes(int B, int C, int H, int W, int squeeze);
+int finc_image_encode_u8_f32(const uint8_t *img, const float *noise, float *out, float *logdet, int B, int C, int H, int W, int squeeze,
+                             float mult, float lo, float hi, float hi_comp, float logdet_const, void *workspace, size_t workspace_bytes,
+                             finc_stream_t stream);
+int finc_image_encode_f32(const float *img, const float *noise, float *out, float *logdet, int B, int C, int H, int W, int squeeze,
+                          float mult, float lo, float hi, float hi_comp, float logdet_const, void *workspace, size_t workspace_bytes,
+                          finc_stream_t stream);
+int finc_image_decode_f32(const float *z, float *out, float *logdet, int B, int C, int H, int W, int unsqueeze, float inv_mult, float off,
+                          float hi, float logdet_const, void *workspace, size_t workspace_bytes, finc_stream_t stream);
+int finc_image_decode_u8(const float *z, uint8_t *out, float *logdet, int B, int C, int H, int W, int unsqueeze, float inv_mult, float off,
+                         float hi, float logdet_const, void *workspace, size_t workspace_bytes, finc_stream_t stream);
+
+/*
  * Introspection (tests, diagnostics; no reference counterpart).
  * finc_inverse_kernel_variant: which MFMA inverse kernel FINC_ALGO_AUTO / finc_inverse_packed_f32 launches for this
  *   problem.  info[8] = {Cq padded to 4, waves per problem (K-split), problems per workgroup, 3 = sector pairing with
