@@ -190,7 +190,7 @@ static int canonicalize(const T *w_stored, T *w_canon, int G, int Cq, int KH, in
 
 extern "C" {
 
-int finc_version(void) { return 115; }
+int finc_version(void) { return 116; }
 
 unsigned finc_build_flags(void)
 {
@@ -652,11 +652,13 @@ static bool raw_misaligned(const P *...p) { return off_boundary(sizeof(R) - 1, p
 //   CPL_SPLIT    direction +1 with two half-tensor outputs y (x1) and yb (z2) and log p, all required (finc_split_prior_f32);
 //   CPL_MERGE    direction -1 with two half-tensor inputs x (x1) and xb (z2); log p optional (finc_split_prior_merge_f32).
 // xb and yb are nullptr in the first two.  In the last two the whole tensor and the two halves may not overlap each other.
+// `gauss` (the last two forms, fp32 raw): the Gaussianized split's arithmetic behind the same ladder (finc_gauss_split_f32,
+// finc_gauss_split_merge_f32).
 enum CplForm { CPL_PLAIN, CPL_LOGDET, CPL_SPLIT, CPL_MERGE };
 template <typename R>
 static int coupling_transform(CplForm form, const float *x, const float *xb, const R *raw, const float *a, const float *b, float *y,
                               float *yb, float *logdet, int B, int C, int HW, int direction, void *workspace, size_t workspace_bytes,
-                              finc_stream_t stream)
+                              finc_stream_t stream, bool gauss = false)
 {
     const bool split = form == CPL_SPLIT || form == CPL_MERGE;
     if (!x || !raw || !a || !b || !y || ((form == CPL_LOGDET || form == CPL_SPLIT) && !logdet) || (form == CPL_SPLIT && !yb) ||
@@ -676,6 +678,10 @@ static int coupling_transform(CplForm form, const float *x, const float *xb, con
     const bool sums = form == CPL_LOGDET || form == CPL_SPLIT || (form == CPL_PLAIN ? direction > 0 && logdet : logdet != nullptr);
     if (sums && workspace_short(workspace, workspace_bytes, finc_coupling_workspace_bytes(B, C, HW))) return FINC_ERR_WORKSPACE;
     if (int e = finc_fault_gate(false)) return e;
+    if constexpr (sizeof(R) == 4)
+        if (gauss)
+            return finc_gauss_split_launch(x, xb, raw, a, b, y, yb, sums ? logdet : nullptr, B, C, HW, direction, (float *)workspace,
+                                           (hipStream_t)stream);
     return coupling_launch(x, xb, raw, a, b, y, yb, sums ? logdet : nullptr, B, C, HW, direction, split, (float *)workspace,
                            (hipStream_t)stream);
 }
@@ -702,7 +708,7 @@ extern "C++" {
 template <typename R>
 static int coupling_grad(FincGradMode mode, const float *grad_y, const float *grad_z, const float *grad_logdet, const float *v,
                          const R *raw, const float *a, const float *b, float *x_out, float *grad_x, R *grad_raw, float *grad_a, float *grad_b, int B, int C, int HW,
-                         void *workspace, size_t workspace_bytes, finc_stream_t stream)
+                         void *workspace, size_t workspace_bytes, finc_stream_t stream, bool gauss = false)
 {
     const void *r = raw, *gr = grad_raw;
     if ((mode == FINC_GRAD_SPLIT ? !grad_y && !grad_z && !grad_logdet : !grad_y) || !v || !raw || !a || !b ||
@@ -717,6 +723,10 @@ static int coupling_grad(FincGradMode mode, const float *grad_y, const float *gr
     if ((grad_a || grad_b) && workspace_short(workspace, workspace_bytes, finc_coupling_workspace_bytes(B, C, HW)))
         return FINC_ERR_WORKSPACE;
     if (int e = finc_fault_gate(false)) return e;
+    if constexpr (sizeof(R) == 4)
+        if (gauss)                                                          // (FINC_GRAD_SPLIT under the Gaussianized split's law)
+            return finc_gauss_split_grad_launch(grad_y, grad_z, grad_logdet, v, raw, a, b, grad_x, grad_raw, grad_a, grad_b, B, C, HW,
+                                                (float *)workspace, (hipStream_t)stream);
     return coupling_grad_launch(mode, grad_y, grad_z, grad_logdet, v, raw, a, b, x_out, grad_x, grad_raw, grad_a, grad_b, B, C, HW,
                                 (float *)workspace, (hipStream_t)stream);
 }
@@ -842,6 +852,27 @@ int finc_split_prior_backward_rawbf16_f32(const float *grad_x1, const float *gra
 {
     return coupling_grad(FINC_GRAD_SPLIT, grad_x1, grad_z2, grad_log_p, x, raw, a, b, nullptr, grad_x, grad_raw, grad_a, grad_b, B, C, HW,
                          workspace, workspace_bytes, stream);
+}
+
+// The Gaussianized split (glow.Split): the split prior's two ladders, in front of the kernels of the other arithmetic law.
+int finc_gauss_split_f32(const float *x, const float *raw, const float *a, const float *b, float *x1, float *z2, float *log_p, int B, int C,
+                         int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    return coupling_transform(CPL_SPLIT, x, nullptr, raw, a, b, x1, z2, log_p, B, C, HW, 1, workspace, workspace_bytes, stream, true);
+}
+
+int finc_gauss_split_merge_f32(const float *x1, const float *z2, const float *raw, const float *a, const float *b, float *x, float *log_p,
+                               int B, int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    return coupling_transform(CPL_MERGE, x1, z2, raw, a, b, x, nullptr, log_p, B, C, HW, -1, workspace, workspace_bytes, stream, true);
+}
+
+int finc_gauss_split_backward_f32(const float *grad_x1, const float *grad_z2, const float *grad_log_p, const float *x, const float *raw,
+                                  const float *a, const float *b, float *grad_x, float *grad_raw, float *grad_a, float *grad_b, int B,
+                                  int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    return coupling_grad(FINC_GRAD_SPLIT, grad_x1, grad_z2, grad_log_p, x, raw, a, b, nullptr, grad_x, grad_raw, grad_a, grad_b, B, C, HW,
+                         workspace, workspace_bytes, stream, true);
 }
 
 // bias + ReLU on fp32 or on bf16 bits (the bias is fp32 in both): one ladder

@@ -332,6 +332,16 @@ int finc_coupling_rawbf16_grad_launch(FincGradMode mode, const float *gy, const 
                                       const uint16_t *raw, const float *a, const float *b, float *xo, float *gx, uint16_t *graw, float *ga,
                                       float *gb, int B, int C, int HW, float *ws, hipStream_t st);
 int finc_bias_relu_bf16_launch(const uint16_t *in, const float *bias, uint16_t *out, int B, int C, int HW, hipStream_t st);
+// The Gaussianized split (glow.Split): the two `split` forms of finc_coupling_launch and the FINC_GRAD_SPLIT mode of
+// finc_coupling_grad_launch under another arithmetic law -- raw channel 2j is the pre-activation of the mean m, 2j+1 that of the
+// log-scale logs; direction +1: y = x1, yb = z2 = (x2 - m) * exp(-logs), direction -1: the whole y from x = x1 and xb = z2 with
+// x2 = z2 * exp(logs) + m; log_p = -sum logs - 1/2 sum z2^2 - 1/2 (C/2) HW log 2 pi (nullptr with direction -1: none, `ws` untouched).
+// The same geometry, workspace and pointer rules; fp32 raw only.
+int finc_gauss_split_launch(const float *x, const float *xb, const float *raw, const float *a, const float *b, float *y, float *yb,
+                            float *log_p, int B, int C, int HW, int direction, float *ws, hipStream_t st);
+int finc_gauss_split_grad_launch(const float *gx1, const float *gz2, const float *glp, const float *x, const float *raw, const float *a,
+                                 const float *b, float *gx, float *graw, float *ga, float *gb, int B, int C, int HW, float *ws,
+                                 hipStream_t st);
 // ---- ActNorm (transform + log-det, its backward from the forward's OUTPUT, the data-dependent initialisation): finc_actnorm.h, same object ----
 // `ws` holds finc_actnorm_workspace_floats floats (backward with gls / gt, and the initialisation)
 size_t finc_actnorm_workspace_floats(int B, int C, int HW);

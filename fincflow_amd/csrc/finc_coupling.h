@@ -15,6 +15,10 @@
 //   * finc_splitprior_kernel    the split prior with its latent (glow.SplitPrior.split / merge): the transform with one side as two
 //                               half tensors, and log p = sum s - 1/2 sum z2^2 - c per image from the same pass; its backward,
 //                               finc_splitprior_bwd_kernel, is cpl_grad's fourth mode.
+//   * finc_gauss_split_kernel   the Gaussianized split (glow.Split: layers/split.py:24-52): the split prior's two bodies under another
+//                               arithmetic law (CPL_LAW_GAUSS) -- raw channel 2j = the mean's pre-activation, 2j+1 = the log-scale's,
+//                               z2 = (x2 - m) * exp(-logs), log p = -sum logs - 1/2 sum z2^2 - c; its backward is
+//                               finc_gauss_split_bwd_kernel.  fp32 raw only.
 //   * finc_coupling_rev_logdet_kernel  the reverse pass that also sums s per image: the sample and the forward log-det at the
 //                               sample in one pass (FlowSequential.sample_with_log_prob / rsample_with_log_prob).
 //   * finc_bias_relu_kernel     out = max(in + bias[c], 0), in place or not.
@@ -37,6 +41,9 @@ namespace {
 
 typedef float cpl_v4f __attribute__((ext_vector_type(4)));
 constexpr int CPL_THREADS = 256;
+// The arithmetic law of a body: the affine coupling's (s = 2 tanh(h[2j] / 2), t = h[2j+1]: y2 = x2 * exp(s) + t) or the Gaussianized
+// split's (m = h[2j], logs = h[2j+1]: z2 = (x2 - m) * exp(-logs)), which exists in the SPLIT forms only.
+constexpr int CPL_LAW_COUPLING = 0, CPL_LAW_GAUSS = 1;
 
 template <int V>
 __device__ inline void cpl_load(float (&d)[V], const float *p)
@@ -128,11 +135,14 @@ __device__ inline void cpl_block_sum(float (&v)[N], float (*sm)[4])
 // Nothing may overlap then.  The arithmetic lines are the same, so the halves carry the bits of the whole-tensor call.  With LOGDET
 // the partial is sum s - 1/2 sum z2^2, z2 the forward's output (DIR +1) or the reverse's input (DIR -1), and part 0 of every image
 // also takes -c (c = 1/2 half HW log 2 pi): the reduce then gives log p = the coupling's log-det + the standard-normal score of z2.
-template <int V, int DIR, bool LOGDET, typename R = float, bool SPLIT = false>
+// LAW = CPL_LAW_GAUSS (SPLIT only): u is the pre-activation of the mean and t that of the log-scale, DIR +1 is z2 = (x2 - m) *
+// exp(-logs), DIR -1 is x2 = z2 * exp(logs) + m, and the first sum is -sum logs (the split's log-det) in both.
+template <int V, int DIR, bool LOGDET, typename R = float, bool SPLIT = false, int LAW = CPL_LAW_COUPLING>
 __device__ __forceinline__ void cpl_transform(const float *x, const float *xb, const R *__restrict__ raw, const float *__restrict__ a,
                                               const float *__restrict__ b, float *y, float *yb, float *__restrict__ part, float c, int half,
                                               int HW, int nv, int items, int P)
 {
+    static_assert(LAW == CPL_LAW_COUPLING || SPLIT, "the Gaussianized law has the split forms only");
     constexpr int NS = SPLIT && LOGDET ? 2 : 1;                            // sums per thread: s, and z2^2 for the split prior
     const int img = (int)blockIdx.x / P, pi = (int)blockIdx.x - img * P;
     const size_t ibase = (size_t)img * (size_t)(2 * half) * (size_t)HW, hbase = (size_t)img * (size_t)half * (size_t)HW;
@@ -154,16 +164,27 @@ __device__ __forceinline__ void cpl_transform(const float *x, const float *xb, c
         const float au = a[2 * j], bu = b[2 * j], at = a[2 * j + 1], bt = b[2 * j + 1];
 #pragma unroll
         for (int e = 0; e < V; ++e) {
-            const float s = 2.f * tanhf(0.5f * fmaf(au, u[e], bu));
-            const float tr = fmaf(at, t[e], bt);
-            if constexpr (DIR > 0) {
-                y2[e] = fmaf(x2[e], expf(s), tr);
-                if constexpr (LOGDET) ls[0] += s;
-                if constexpr (NS == 2) ls[NS - 1] = fmaf(y2[e], y2[e], ls[NS - 1]);
+            if constexpr (LAW == CPL_LAW_GAUSS) {
+                const float m = fmaf(au, u[e], bu), logs = fmaf(at, t[e], bt);
+                if constexpr (DIR > 0) y2[e] = (x2[e] - m) * expf(-logs);
+                else y2[e] = fmaf(x2[e], expf(logs), m);
+                if constexpr (LOGDET) {
+                    const float z = DIR > 0 ? y2[e] : x2[e];
+                    ls[0] -= logs;
+                    ls[NS - 1] = fmaf(z, z, ls[NS - 1]);
+                }
             } else {
-                y2[e] = (x2[e] - tr) * expf(-s);
-                if constexpr (LOGDET) ls[0] += s;
-                if constexpr (NS == 2) ls[NS - 1] = fmaf(x2[e], x2[e], ls[NS - 1]);
+                const float s = 2.f * tanhf(0.5f * fmaf(au, u[e], bu));
+                const float tr = fmaf(at, t[e], bt);
+                if constexpr (DIR > 0) {
+                    y2[e] = fmaf(x2[e], expf(s), tr);
+                    if constexpr (LOGDET) ls[0] += s;
+                    if constexpr (NS == 2) ls[NS - 1] = fmaf(y2[e], y2[e], ls[NS - 1]);
+                } else {
+                    y2[e] = (x2[e] - tr) * expf(-s);
+                    if constexpr (LOGDET) ls[0] += s;
+                    if constexpr (NS == 2) ls[NS - 1] = fmaf(x2[e], x2[e], ls[NS - 1]);
+                }
             }
         }
         if constexpr (SPLIT && DIR > 0) {
@@ -225,6 +246,17 @@ __global__ __launch_bounds__(CPL_THREADS) void finc_splitprior_kernel(const floa
     cpl_transform<V, DIR, LOGP, R, true>(x, xb, raw, a, b, y, yb, part, c, half, HW, nv, items, P);
 }
 
+// The Gaussianized split's two transforms: the same forms (DIR +1 always with log p, DIR -1 with or without it) under CPL_LAW_GAUSS.
+template <int V, int DIR, bool LOGP>
+__global__ __launch_bounds__(CPL_THREADS) void finc_gauss_split_kernel(const float *__restrict__ x, const float *__restrict__ xb,
+                                                                       const float *__restrict__ raw, const float *__restrict__ a,
+                                                                       const float *__restrict__ b, float *__restrict__ y,
+                                                                       float *__restrict__ yb, float *__restrict__ part, float c, int half,
+                                                                       int HW, int nv, int items, int P)
+{
+    cpl_transform<V, DIR, LOGP, float, true, CPL_LAW_GAUSS>(x, xb, raw, a, b, y, yb, part, c, half, HW, nv, items, P);
+}
+
 // Every backward of the coupling is ONE body, cpl_grad<V, MODE>; a mode (FincGradMode) is what it reads and the few lines of
 // arithmetic behind `if constexpr`:
 //   FINC_GRAD_FWD      of y2 = x2 * exp(s) + t, from `v` = the forward's INPUT x (layers/coupling.py:79-93).
@@ -243,20 +275,23 @@ __global__ __launch_bounds__(CPL_THREADS) void finc_splitprior_kernel(const floa
 //                      from `v` = the forward's INPUT x.  gy = grad_x1 and gz = grad_z2 are contiguous HALVES [B][half][HW], gld =
 //                      grad_log_p; each may be nullptr (zeros).  E = exp(s) and z2 = fma(x2, E, t) are recomputed, G = grad_z2 -
 //                      grad_log_p[img] * z2 is what reaches z2 in all, and the FWD mode's lines follow with G in the place of g2.
-//                      gz is nullptr in every other mode.
+//                      gz is nullptr in every other mode.  With LAW = CPL_LAW_GAUSS (this mode only) the forward is the Gaussianized
+//                      split's: E = exp(-logs) and z2 = (x2 - m) * E are recomputed, G = grad_z2 - grad_log_p[img] * z2,
+//                      grad_x2 = G * E, grad_h[2j] (the mean's) = -grad_x2, grad_h[2j+1] (the log-scale's) = -(G * z2 + grad_log_p).
 // s and exp(s) are recomputed from raw (two transcendentals per element), not saved by the forward.
 // Workgroup = (channel pair j, part): Q parts per pair share its B * HW / V thread items, so the four per-channel sums of a
 // workgroup belong to ONE pair.  Partials: part[(4j + k) * Q + q], k = 0 grad_a[2j], 1 grad_b[2j], 2 grad_a[2j+1], 3 grad_b[2j+1].
 // gld (grad of the log-det, per image), xo, gx, graw may be nullptr; `sums` = 0 skips the partials.  R: the element type of raw and
 // of graw, which is rounded from the fp32 gu, gt behind the sums (the sums never see a rounded value).
-template <int V, int MODE, typename R = float>
+template <int V, int MODE, typename R = float, int LAW = CPL_LAW_COUPLING>
 __device__ __forceinline__ void cpl_grad(const float *gy, const float *gz, const float *__restrict__ gld, const float *v,
                                          const R *__restrict__ raw,
                                          const float *__restrict__ a, const float *__restrict__ b, float *xo, float *gx,
                                          R *__restrict__ graw, float *__restrict__ part, int half, int HW, int nv, int items, int Q,
                                          int sums)
 {
-    constexpr bool REBUILD = MODE == FINC_GRAD_REBUILD, SPLIT = MODE == FINC_GRAD_SPLIT;
+    constexpr bool REBUILD = MODE == FINC_GRAD_REBUILD, SPLIT = MODE == FINC_GRAD_SPLIT, GAUSS = LAW == CPL_LAW_GAUSS;
+    static_assert(!GAUSS || SPLIT, "the Gaussianized law has the split mode only");
     const int j = (int)blockIdx.x / Q, qi = (int)blockIdx.x - j * Q;
     const float au = a[2 * j], bu = b[2 * j], at = a[2 * j + 1], bt = REBUILD || SPLIT ? b[2 * j + 1] : 0.f;
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
@@ -284,27 +319,34 @@ __device__ __forceinline__ void cpl_grad(const float *gy, const float *gz, const
         const float gl = gld ? gld[img] : (MODE == FINC_GRAD_REV ? -0.f : 0.f);
 #pragma unroll
         for (int e = 0; e < V; ++e) {
-            const float th = tanhf(0.5f * fmaf(au, u[e], bu));     // s = 2 th, d s / d h = 1 - s*s/4 = 1 - th*th
             float ghu, ght;                                        // the gradients of h[2j] and h[2j+1]
-            if constexpr (MODE == FINC_GRAD_FWD) {
-                gx2[e] = g2[e] * expf(2.f * th);
-                ghu = fmaf(gx2[e], v2[e], gl) * fmaf(-th, th, 1.f);
-                ght = g2[e];
-            } else if constexpr (MODE == FINC_GRAD_REV) {
-                gx2[e] = g2[e] * expf(-2.f * th);
-                ghu = (-(g2[e] * v2[e]) + gl) * fmaf(-th, th, 1.f);
-                ght = -gx2[e];
-            } else if constexpr (SPLIT) {
-                const float E = expf(2.f * th), G = g2[e] - gl * fmaf(v2[e], E, fmaf(at, t[e], bt));
+            if constexpr (GAUSS) {
+                const float m = fmaf(au, u[e], bu), E = expf(-fmaf(at, t[e], bt)), z = (v2[e] - m) * E, G = g2[e] - gl * z;
                 gx2[e] = G * E;
-                ghu = fmaf(gx2[e], v2[e], gl) * fmaf(-th, th, 1.f);
-                ght = G;
+                ghu = -gx2[e];
+                ght = -fmaf(G, z, gl);
             } else {
-                const float s = 2.f * th, d = v2[e] - fmaf(at, t[e], bt);
-                x2[e] = d * expf(-s);
-                gx2[e] = g2[e] * expf(s);
-                ghu = fmaf(g2[e], d, gl) * fmaf(-th, th, 1.f);
-                ght = g2[e];
+                const float th = tanhf(0.5f * fmaf(au, u[e], bu));     // s = 2 th, d s / d h = 1 - s*s/4 = 1 - th*th
+                if constexpr (MODE == FINC_GRAD_FWD) {
+                    gx2[e] = g2[e] * expf(2.f * th);
+                    ghu = fmaf(gx2[e], v2[e], gl) * fmaf(-th, th, 1.f);
+                    ght = g2[e];
+                } else if constexpr (MODE == FINC_GRAD_REV) {
+                    gx2[e] = g2[e] * expf(-2.f * th);
+                    ghu = (-(g2[e] * v2[e]) + gl) * fmaf(-th, th, 1.f);
+                    ght = -gx2[e];
+                } else if constexpr (SPLIT) {
+                    const float E = expf(2.f * th), G = g2[e] - gl * fmaf(v2[e], E, fmaf(at, t[e], bt));
+                    gx2[e] = G * E;
+                    ghu = fmaf(gx2[e], v2[e], gl) * fmaf(-th, th, 1.f);
+                    ght = G;
+                } else {
+                    const float s = 2.f * th, d = v2[e] - fmaf(at, t[e], bt);
+                    x2[e] = d * expf(-s);
+                    gx2[e] = g2[e] * expf(s);
+                    ghu = fmaf(g2[e], d, gl) * fmaf(-th, th, 1.f);
+                    ght = g2[e];
+                }
             }
             gu[e] = au * ghu;
             gt[e] = at * ght;
@@ -381,6 +423,18 @@ __global__ __launch_bounds__(CPL_THREADS) void finc_splitprior_bwd_kernel(const 
                                                                           int nv, int items, int Q, int sums)
 {
     cpl_grad<V, FINC_GRAD_SPLIT>(gx1, gz2, glp, x, raw, a, b, nullptr, gx, graw, part, half, HW, nv, items, Q, sums);
+}
+
+// The Gaussianized split's backward: the same mode under CPL_LAW_GAUSS; nothing may overlap.
+template <int V>
+__global__ __launch_bounds__(CPL_THREADS) void finc_gauss_split_bwd_kernel(const float *__restrict__ gx1, const float *__restrict__ gz2,
+                                                                           const float *__restrict__ glp, const float *__restrict__ x,
+                                                                           const float *__restrict__ raw, const float *__restrict__ a,
+                                                                           const float *__restrict__ b, float *__restrict__ gx,
+                                                                           float *__restrict__ graw, float *__restrict__ part, int half, int HW,
+                                                                           int nv, int items, int Q, int sums)
+{
+    cpl_grad<V, FINC_GRAD_SPLIT, float, CPL_LAW_GAUSS>(gx1, gz2, glp, x, raw, a, b, nullptr, gx, graw, part, half, HW, nv, items, Q, sums);
 }
 
 // The four modes on a bf16 raw (and a bf16 grad_raw): one kernel, the mode its parameter.  xo == v and gx == gy are the rebuild's;
@@ -525,8 +579,9 @@ inline uintptr_t cpl_bits8(const P *...p) { return sizeof(R) == 2 ? cpl_bits(p..
 // logdet (either direction): the log-det of the FORWARD map, sum s per image -- in the reverse direction at the recovered input y
 // (B x P partials in `ws`, then the reduce); nullptr: none, and `ws` is not touched.
 // split: the split prior's transforms (cpl_transform's SPLIT) -- xb / yb are the second half tensor of the side that has two, every
-// half-tensor pointer counts towards the 16-byte rule, and logdet is log p (direction +1 always has it).
-template <typename R>
+// half-tensor pointer counts towards the 16-byte rule, and logdet is log p (direction +1 always has it).  LAW = CPL_LAW_GAUSS (with
+// `split` and an fp32 raw): the same geometry in front of finc_gauss_split_kernel.
+template <typename R, int LAW = CPL_LAW_COUPLING>
 int cpl_launch(const float *x, const float *xb, const R *raw, const float *a, const float *b, float *y, float *yb, float *logdet, int B,
                int C, int HW, int direction, bool split, float *ws, hipStream_t st)
 {
@@ -538,10 +593,17 @@ int cpl_launch(const float *x, const float *xb, const R *raw, const float *a, co
     const dim3 grid((unsigned)((long long)B * P)), block(CPL_THREADS);
     if (split) {
         const float c = (float)(0.5 * (double)half * (double)HW * 1.8378770664093454835606594728112);        // log(2 pi)
-        const auto kernel = direction > 0 ? (wide ? finc_splitprior_kernel<4, 1, true, R> : finc_splitprior_kernel<1, 1, true, R>)
-                            : logdet      ? (wide ? finc_splitprior_kernel<4, -1, true, R> : finc_splitprior_kernel<1, -1, true, R>)
-                                          : (wide ? finc_splitprior_kernel<4, -1, false, R> : finc_splitprior_kernel<1, -1, false, R>);
-        hipLaunchKernelGGL(kernel, grid, block, 0, st, x, xb, raw, a, b, y, yb, ws, c, half, HW, nv, items, P);
+        if constexpr (LAW == CPL_LAW_GAUSS) {
+            const auto kernel = direction > 0 ? (wide ? finc_gauss_split_kernel<4, 1, true> : finc_gauss_split_kernel<1, 1, true>)
+                                : logdet      ? (wide ? finc_gauss_split_kernel<4, -1, true> : finc_gauss_split_kernel<1, -1, true>)
+                                              : (wide ? finc_gauss_split_kernel<4, -1, false> : finc_gauss_split_kernel<1, -1, false>);
+            hipLaunchKernelGGL(kernel, grid, block, 0, st, x, xb, raw, a, b, y, yb, ws, c, half, HW, nv, items, P);
+        } else {
+            const auto kernel = direction > 0 ? (wide ? finc_splitprior_kernel<4, 1, true, R> : finc_splitprior_kernel<1, 1, true, R>)
+                                : logdet      ? (wide ? finc_splitprior_kernel<4, -1, true, R> : finc_splitprior_kernel<1, -1, true, R>)
+                                              : (wide ? finc_splitprior_kernel<4, -1, false, R> : finc_splitprior_kernel<1, -1, false, R>);
+            hipLaunchKernelGGL(kernel, grid, block, 0, st, x, xb, raw, a, b, y, yb, ws, c, half, HW, nv, items, P);
+        }
     } else {
         const auto kernel = !logdet ? (direction < 0 ? (wide ? cpl_transform_kernel<R, 4, -1, false>() : cpl_transform_kernel<R, 1, -1, false>())
                                                      : (wide ? cpl_transform_kernel<R, 4, 1, false>() : cpl_transform_kernel<R, 1, 1, false>()))
@@ -579,7 +641,7 @@ void cpl_grad_start(const CplGradPlan &p, hipStream_t st, const float *gy, const
                        ws, half, HW, p.nv, p.items, p.Q, sums);
 }
 
-template <typename R>
+template <typename R, int LAW = CPL_LAW_COUPLING>
 int cpl_grad_launch(FincGradMode mode, const float *gy, const float *gz, const float *gld, const float *v, const R *raw, const float *a,
                     const float *b, float *xo, float *gx, R *graw, float *ga, float *gb, int B, int C, int HW, float *ws, hipStream_t st)
 {
@@ -587,7 +649,10 @@ int cpl_grad_launch(FincGradMode mode, const float *gy, const float *gz, const f
     const CplGradPlan p = cpl_grad_plan(B, C, HW, half, cpl_bits(gy, gz, v, xo, gx) | cpl_bits16<R>(raw, graw), cpl_bits8<R>(raw, graw));
     if (!p.Q) return FINC_ERR_BAD_DIMS;
 #define CPL_GRAD_START(V, MODE) cpl_grad_start<V, MODE>(p, st, gy, gz, gld, v, raw, a, b, xo, gx, graw, ws, half, HW, sums)
-    if (mode == FINC_GRAD_SPLIT) {
+    if constexpr (LAW == CPL_LAW_GAUSS) {                                  // (FINC_GRAD_SPLIT, fp32 raw)
+        const auto kernel = p.wide ? finc_gauss_split_bwd_kernel<4> : finc_gauss_split_bwd_kernel<1>;
+        hipLaunchKernelGGL(kernel, p.grid, dim3(CPL_THREADS), 0, st, gy, gz, gld, v, raw, a, b, gx, graw, ws, half, HW, p.nv, p.items, p.Q, sums);
+    } else if (mode == FINC_GRAD_SPLIT) {
         if (p.wide) CPL_GRAD_START(4, FINC_GRAD_SPLIT); else CPL_GRAD_START(1, FINC_GRAD_SPLIT);
     } else if (mode == FINC_GRAD_REBUILD) {
         if (p.wide) CPL_GRAD_START(4, FINC_GRAD_REBUILD); else CPL_GRAD_START(1, FINC_GRAD_REBUILD);
@@ -621,11 +686,23 @@ int finc_coupling_rawbf16_launch(const float *x, const float *xb, const uint16_t
     return cpl_launch<__bf16>(x, xb, reinterpret_cast<const __bf16 *>(raw), a, b, y, yb, logdet, B, C, HW, direction, split, ws, st);
 }
 
+int finc_gauss_split_launch(const float *x, const float *xb, const float *raw, const float *a, const float *b, float *y, float *yb,
+                            float *log_p, int B, int C, int HW, int direction, float *ws, hipStream_t st)
+{
+    return cpl_launch<float, CPL_LAW_GAUSS>(x, xb, raw, a, b, y, yb, log_p, B, C, HW, direction, true, ws, st);
+}
+
 int finc_coupling_grad_launch(FincGradMode mode, const float *gy, const float *gz, const float *gld, const float *v, const float *raw,
                               const float *a, const float *b, float *xo, float *gx, float *graw, float *ga, float *gb, int B, int C, int HW,
                               float *ws, hipStream_t st)
 {
     return cpl_grad_launch<float>(mode, gy, gz, gld, v, raw, a, b, xo, gx, graw, ga, gb, B, C, HW, ws, st);
+}
+int finc_gauss_split_grad_launch(const float *gx1, const float *gz2, const float *glp, const float *x, const float *raw, const float *a,
+                                 const float *b, float *gx, float *graw, float *ga, float *gb, int B, int C, int HW, float *ws,
+                                 hipStream_t st)
+{
+    return cpl_grad_launch<float, CPL_LAW_GAUSS>(FINC_GRAD_SPLIT, gx1, gz2, glp, x, raw, a, b, nullptr, gx, graw, ga, gb, B, C, HW, ws, st);
 }
 int finc_coupling_rawbf16_grad_launch(FincGradMode mode, const float *gy, const float *gz, const float *gld, const float *v,
                                       const uint16_t *raw, const float *a, const float *b, float *xo, float *gx, uint16_t *graw, float *ga,

@@ -23,6 +23,10 @@ Reference semantics followed:
   SplitPrior     layers/splitprior.py:7-41       Coupling + factor out the second half under a standard normal; `split` / `merge`
                  hand that half out and take it back (FlowSequential.encode / decode), one HIP launch each (ops.finc_split_prior,
                  ops.finc_split_prior_merge, ops.split_prior_forward)
+  Split          layers/split.py:4-52            the Gaussianized split (`Gaussianize`): the second half modelled as N(m, exp(logs)^2) with
+                 (m, logs) from ONE zero-initialised 3x3 convolution of the first; the `split` / `merge` / `draw` protocol of SplitPrior,
+                 one HIP launch each behind that convolution (ops.finc_gauss_split, ops.finc_gauss_split_merge,
+                 ops.gauss_split_forward)
   Normalization, LogitTransform, Dequantization  layers/normalize.py, transforms.py:6-19, dequantize.py
                  with `FlowSequential.fuse_image_boundary` these and the first Squeeze are one HIP launch each way
                  (ops.finc_image_encode, ops.finc_image_decode: uint8 or fp32 images in, fp32 or uint8 images out)
@@ -665,6 +669,153 @@ class SplitPrior(FlowLayer):
         return self.forward(input, context)[1]
 
 
+class Gaussianize(_DerivedValues, nn.Module):
+    """layers/split.py:24-52 (RealNVP 3.6 / figure 4b): x2 ~ N(m, exp(logs)^2) with (m, logs) the even and odd output channels of
+    `net(x1) * exp(log_scale_factor)`, `net` one zero-initialised 3x3 convolution.  Parameter names and shapes are the reference's.
+    `forward(x1, x2) -> (z2, logdet)` and `reverse(x1, z2) -> x2` are its PyTorch lines; the helpers below are what `Split` hands to
+    the HIP kernels: `raw` = the convolution WITHOUT its bias, and h = a * raw + b with a = exp(log_scale_factor), b = bias * a (the
+    convention of `Coupling._scale_shift`).  Under autocast only the convolution runs in the autocast dtype; its output is upcast in
+    front of h, in the PyTorch lines and on the HIP path alike."""
+
+    _derived = ("_ab", "_ab_key", "_ab_ready")
+
+    def __init__(self, n_channels):
+        super().__init__()
+        self.net = nn.Conv2d(n_channels, 2 * n_channels, kernel_size=3, padding=1)
+        self.log_scale_factor = nn.Parameter(torch.zeros(2 * n_channels, 1, 1))
+        with torch.no_grad():
+            self.net.weight.zero_()
+            self.net.bias.zero_()
+
+    def _records_graph(self, *tensors):
+        return torch.is_grad_enabled() and (any(t.requires_grad for t in tensors) or any(p.requires_grad for p in self.parameters()))
+
+    def _scale_shift(self):
+        a = torch.exp(self.log_scale_factor).reshape(-1)
+        return a, self.net.bias * a
+
+    def _scale_shift_cached(self):
+        # once per parameter version, as Coupling._scale_shift_cached (nothing is cached during a stream capture)
+        key = ops.version_key(self.log_scale_factor, self.net.bias) + (self.log_scale_factor.device,)
+        if getattr(self, "_ab_key", None) == key:
+            self._ab_ready.wait(*self._ab)
+            return self._ab
+        with torch.no_grad():
+            a, b = self._scale_shift()
+            ab = (a.contiguous(), b.contiguous())
+        if not (self.log_scale_factor.is_cuda and ops._capturing()):
+            self._ab, self._ab_key, self._ab_ready = ab, key, ops.Ready(self.log_scale_factor.device)
+        return ab
+
+    def _raw(self, x1):
+        """The convolution without its bias, fp32 whatever autocast made of it (there are no bf16 / fp16 kernels behind it)."""
+        raw = F.conv2d(x1, self.net.weight, None, padding=1)
+        return raw if raw.dtype == x1.dtype else raw.to(x1.dtype)
+
+    def _raw_inference(self, x1):
+        with torch.no_grad():
+            return self._raw(x1).contiguous()
+
+    def _mean_logs(self, x1):
+        if _autocast_dtype(x1) is None:
+            h = self.net(x1) * self.log_scale_factor.exp()                      # layers/split.py:41
+        else:
+            a, b = self._scale_shift()
+            h = self._raw(x1) * a.view(1, -1, 1, 1) + b.view(1, -1, 1, 1)
+        return h[:, 0::2], h[:, 1::2]
+
+    def forward(self, x1, x2):
+        m, logs = self._mean_logs(x1)
+        return (x2 - m) * torch.exp(-logs), -logs.flatten(start_dim=1).sum(-1)
+
+    def reverse(self, x1, z2):
+        return self.reverse_with_logdet(x1, z2)[0]
+
+    def reverse_with_logdet(self, x1, z2):
+        """x2 and the FORWARD map's log-det at it, -sum logs (logs depends on x1 only, which both directions share)."""
+        m, logs = self._mean_logs(x1)
+        return m + z2 * torch.exp(logs), -logs.flatten(start_dim=1).sum(-1)
+
+
+class Split(FlowLayer):
+    """layers/split.py:4-22 as the FlowLayer of fastflow_cifar_multi_gpu.py:77-105: the level boundary of Glow / RealNVP.  The
+    second half of the channels is factored out as z2 = (x2 - m) * exp(-logs) and scored under `base`; (m, logs) cost ONE 3x3
+    convolution of the kept half, where `SplitPrior` runs a whole coupling net.  The interface is `SplitPrior`'s: `forward` scores
+    z2 and drops it, `reverse` draws a fresh one, `split` / `merge` / `draw` hand it out and take it back (`FlowSequential.encode` /
+    `decode` / `draw_latents` / `sample(temperature=)`).  On the device, with fp32 tensors and a base that is exactly
+    `GaussianPrior`, everything behind the convolution is one HIP launch: `ops.finc_gauss_split` / `ops.finc_gauss_split_merge`
+    without a graph, `ops.gauss_split_forward` (backward: finc_gauss_split_backward_f32) while autograd records `split` /
+    `forward`.  Everything else -- CPU tensors, float64, another base, a `merge` that autograd records (inside
+    `ops.reverse_grad()` too) -- keeps the PyTorch lines, which are differentiable as they are.  The layer takes no part in an
+    invertible run (`FlowSequential.invertible_backward` ends one at it, as at a `SplitPrior`)."""
+
+    def __init__(self, input_size, distribution):
+        super().__init__()
+        assert len(input_size) == 3
+        self.n_channels = input_size[0]
+        self.gaussianize = Gaussianize(self.n_channels // 2)
+        self.base = distribution((self.n_channels // 2, input_size[1], input_size[2]))
+
+    def _hip_latent(self, *halves_or_input):
+        """Do the kernels serve these tensors?  fp32 [B,C,H,W] on the device with the parameters beside them, an even channel count
+        with a kernel, and a base that is exactly the standard normal the kernels score."""
+        t = halves_or_input[0]
+        return (type(self.base) is GaussianPrior and _hip_tensor(t) and self.n_channels % 2 == 0
+                and ops.coupling_supported(self.n_channels) and tuple(t.shape[2:]) == self.base.size[1:]
+                and _params_on_device(t, *self.gaussianize.parameters())
+                and all(_hip_tensor(h) and h.shape == t.shape and h.device == t.device for h in halves_or_input[1:]))
+
+    def split(self, input, context=None):
+        """`forward` with the factored-out half handed back: `(x1, z2, log_p)`, log_p [B] = the split's log-det, -sum logs, plus
+        log p(z2) under the base."""
+        g, half = self.gaussianize, self.n_channels // 2
+        if input.dim() == 4 and input.shape[1] == self.n_channels and self._hip_latent(input):
+            if not g._records_graph(input):
+                x = input.contiguous()
+                a, b = g._scale_shift_cached()
+                return ops.finc_gauss_split(x, g._raw_inference(x[:, :half]), a, b)
+            a, b = g._scale_shift()
+            return ops.gauss_split_forward(input, g._raw(input[:, :half]), a, b)
+        x1 = input[:, :half]
+        z2, ldj = g(x1, input[:, half:])
+        return x1, z2, self.base.log_prob(z2) + ldj
+
+    def draw(self, n_samples, context=None, temperature=1.0):
+        """The factored-out half as `reverse` draws it, times `temperature` (at 1 the draw is handed on untouched)."""
+        z2 = self.base.sample(n_samples, context)[0]
+        return z2 if temperature == 1 else z2 * temperature
+
+    def merge(self, x1, z2=None, context=None, temperature=1.0, with_log_prob=False):
+        """The inverse of `split`: x from the kept half `x1` and the factored-out half `z2` (None: drawn from the base, times
+        `temperature`); with `with_log_prob`, `(x, log_p)` with log_p [B] = `split`'s value at x.  Without a graph, on the device: the
+        convolution of `x1` and `ops.finc_gauss_split_merge`, which writes the whole x -- no `cat`.  While autograd records, and
+        everywhere else: the PyTorch lines."""
+        if z2 is None:
+            z2 = self.draw(len(x1), context, temperature)
+        g = self.gaussianize
+        if (not g._records_graph(x1, z2) and x1.dim() == 4 and x1.shape[1] == self.n_channels // 2 and self._hip_latent(x1, z2)):
+            x1, z2 = x1.contiguous(), z2.contiguous()
+            a, b = g._scale_shift_cached()
+            return ops.finc_gauss_split_merge(x1, z2, g._raw_inference(x1), a, b, want_log_p=with_log_prob)
+        x2, ldj = g.reverse_with_logdet(x1, z2)
+        x = torch.cat([x1, x2], dim=1)
+        return (x, self.base.log_prob(z2) + ldj) if with_log_prob else x
+
+    def forward(self, input, context=None):
+        x1, _, log_p = self.split(input, context)
+        return x1, log_p
+
+    def reverse(self, input, context=None):
+        return self.merge(input, None, context)
+
+    def reverse_with_logdet(self, input, context=None):
+        """Mirrors `forward`: the drawn half's density under the base plus the split's log-det at the result."""
+        return self.merge(input, None, context, with_log_prob=True)
+
+    def logdet(self, input, context=None):
+        return self.forward(input, context)[1]
+
+
 class Normalization(FlowLayer):
     def __init__(self, translation, scale, learnable=False):
         super().__init__()
@@ -728,9 +879,10 @@ class Dequantization(FlowLayer):
 
 
 def create_model(num_blocks=3, block_size=32, actnorm=False, split_prior=False, image_size=(3, 32, 32),
-                 preprocess=True, coupling_width=512):
+                 preprocess=True, coupling_width=512, gaussianize_split=False):
     """fastflow/fastflow_cifar.py:35-63: Squeeze -> [FastFlowUnit, (ActNorm), Conv1x1, Coupling] x block_size
-    (-> SplitPrior) per block, under a standard-normal base."""
+    (-> SplitPrior) per block, under a standard-normal base.  `gaussianize_split` (with `split_prior`): the level boundary is the
+    Gaussianized `Split` instead of a `SplitPrior`, the switch of fastflow_cifar_multi_gpu.py:264-265."""
     size = tuple(image_size)
     layers = []
     if preprocess:
@@ -747,6 +899,6 @@ def create_model(num_blocks=3, block_size=32, actnorm=False, split_prior=False, 
             layers.append(Conv1x1(size[0]))
             layers.append(Coupling(size, width=coupling_width))
         if split_prior and level < num_blocks - 1:
-            layers.append(SplitPrior(size, GaussianPrior, width=coupling_width))
+            layers.append(Split(size, GaussianPrior) if gaussianize_split else SplitPrior(size, GaussianPrior, width=coupling_width))
             size = (size[0] // 2, size[1], size[2])
     return FlowSequential(GaussianPrior(size), *layers)

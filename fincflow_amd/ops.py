@@ -712,6 +712,86 @@ def split_prior_forward(x, raw, a, b):
     return _FincSplitPriorFunction.apply(x, raw, a, b)
 
 
+def _gauss_split_raw(raw):
+    """The Gaussianized split has fp32 kernels only (no `_rawbf16_f32` siblings): a net under autocast hands `raw.float()` over."""
+    _require_device(raw, "raw")
+
+
+def finc_gauss_split(x, raw, a, b, out=None):
+    """The Gaussianized split (layers/split.py:24-52; include/finc.h: finc_gauss_split_f32) in one launch: (x1, z2, log_p) with
+    x1 = x[:, :C/2], and, for h = a * raw + b per channel, m = h[:, 0::2], logs = h[:, 1::2]: z2 = (x2 - m) * exp(-logs) and
+    log_p [B] = -sum logs - 1/2 sum z2^2 - 1/2 (C/2) H W log 2 pi, the split's log-det plus the standard-normal score of z2.
+    x, raw [B,C,H,W] fp32 contiguous on the device, raw the 3x3 convolution of x1 WITHOUT its bias; a, b [C].  `out`: a pair
+    (x1, z2) of contiguous [B,C/2,H,W] tensors to write into; they may overlap neither `x` nor each other.  Fixed-order sums: the
+    same inputs give the same bits."""
+    _gauss_split_raw(raw)
+    _coupling_args(x, raw, a, b, halves=out or ())
+    if out is None:
+        B, C, H, W = x.shape
+        out = tuple(torch.empty(B, C // 2, H, W, dtype=torch.float32, device=x.device) for _ in range(2))
+    elif len(out) != 2 or any(t is None for t in out):
+        raise ValueError("out must be the pair (x1, z2)")
+    return _coupling_transform("", x, raw, a, b, (), True, tuple(out), family="finc_gauss_split")
+
+
+def finc_gauss_split_merge(x1, z2, raw, a, b, want_log_p=False, out=None):
+    """The inverse of `finc_gauss_split` (include/finc.h: finc_gauss_split_merge_f32): x[:, :C/2] = x1, x[:, C/2:] = z2 * exp(logs)
+    + m, written whole by one launch, without a `cat`.  x1, z2 [B,C/2,H,W] fp32 contiguous, raw [B,C,H,W] the convolution's output on
+    x1.  Returns x, or (x, log_p) with `want_log_p`: log_p [B] is what `finc_gauss_split` reports at x, from the same pass.  `out`
+    [B,C,H,W] may overlap neither half."""
+    if x1 is None or z2 is None:
+        raise ValueError("finc_gauss_split_merge needs both halves")
+    _gauss_split_raw(raw)
+    _coupling_args(None, raw, a, b, halves=(x1, z2))
+    if out is None:
+        out = torch.empty(raw.shape, dtype=torch.float32, device=raw.device)
+    else:
+        _require_device(out, "output")
+        if out.shape != raw.shape or out.device != raw.device:
+            raise ValueError("output must be [B,C,H,W] like the convolution's output, on its device")
+    x, log_p = _coupling_transform("_merge", (x1, z2), raw, a, b, (), bool(want_log_p), (out,), family="finc_gauss_split")
+    return (x, log_p) if want_log_p else x
+
+
+def finc_gauss_split_backward(grad_x1, grad_z2, grad_log_p, x, raw, a, b, need_gx=True, need_graw=True, need_ga=True, need_gb=True):
+    """Gradients of `finc_gauss_split` (include/finc.h: finc_gauss_split_backward_f32), given the gradients of its three results --
+    grad_x1, grad_z2 [B,C/2,H,W], grad_log_p [B]; each may be None (absent, handed over as NULL), not all three -- and the forward's
+    input `x`: (grad_x, grad_raw, grad_a, grad_b), each computed only if asked for (None otherwise).  grad_x[:, :C/2] is grad_x1: what
+    reaches that half through the convolution is the caller's (autograd's).  z2 and exp(-logs) are recomputed from `raw`."""
+    _gauss_split_raw(raw)
+    return _coupling_grads("_backward", (grad_x1, grad_z2), (grad_log_p,), x, raw, a, b, "input", "input", (need_gx, need_graw),
+                           (need_ga, need_gb), family="finc_gauss_split")
+
+
+class _FincGaussSplitFunction(torch.autograd.Function):
+    """`finc_gauss_split` under autograd: (x1, z2, log_p) and their backward on the HIP kernel.  A result nobody used arrives as None
+    and goes to the kernel as NULL."""
+
+    @staticmethod
+    def forward(ctx, x, raw, a, b):
+        x, raw, a, b = x.contiguous(), raw.contiguous(), a.contiguous(), b.contiguous()
+        x1, z2, log_p = finc_gauss_split(x, raw, a, b)
+        ctx.save_for_backward(x, raw, a, b)
+        ctx.set_materialize_grads(False)
+        return x1, z2, log_p
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_x1, grad_z2, grad_log_p):
+        x, raw, a, b = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        grads = [None if g is None else g.contiguous() for g in (grad_x1, grad_z2, grad_log_p)]
+        if all(g is None for g in grads):
+            return None, None, None, None
+        return finc_gauss_split_backward(*grads, x, raw, a, b, need_gx=need[0], need_graw=need[1], need_ga=need[2], need_gb=need[3])
+
+
+def gauss_split_forward(x, raw, a, b):
+    """`finc_gauss_split(x, raw, a, b)` under autograd: returns (x1, z2, log_p), gradients for `x`, `raw`, `a` and `b`, each computed
+    only where needed."""
+    return _FincGaussSplitFunction.apply(x, raw, a, b)
+
+
 def finc_bias_relu(x, bias, out=None):
     """max(x + bias[c], 0) in one pass: the bias and the ReLU behind a convolution of the coupling net (layers/coupling.py:58-63).
     x [B,C,H,W] fp32 contiguous on the device, bias [C]; `out` may be `x`.  Inference only: no autograd graph is recorded.

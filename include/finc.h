@@ -476,6 +476,39 @@ int finc_split_prior_backward_rawbf16_f32(const float *grad_x1, const float *gra
                                           size_t workspace_bytes, finc_stream_t stream);
 
 /*
+ * The Gaussianized split (version 116; layers/split.py:4-52, Glow figure 2 / RealNVP figure 4b): the level boundary that models the
+ * second half of the channels as N(m, exp(logs)^2), with (m, logs) from ONE convolution of the first half.  The tensors, the
+ * argument lists, the workspace (finc_coupling_workspace_bytes), the 16-byte-piece rule, the aliasing rules and the refusal order are
+ * those of finc_split_prior_f32 / _merge_f32 / _backward_f32 above; what differs is the arithmetic.  raw [B][C][HW] fp32 is that
+ * convolution's output WITHOUT its bias, h = a[c] * raw + b[c] (a = exp(log_scale_factor), b = bias * a), and per channel j < half
+ * and pixel  m = h[:, 2j]  (even channels: the mean),  logs = h[:, 2j+1]  (odd channels: the log-scale);  D = half * HW,
+ * c = D / 2 * log(2 pi).
+ * finc_gauss_split_f32: x1 = x[:, :half], z2[:, j] = (x[:, half+j] - m_j) * exp(-logs_j), and log_p[b] = -sum_{j,p} logs_j -
+ *   1/2 sum_{j,p} z2^2 - c: the split's log-det plus the standard-normal log-density of z2, from the pass that had z2 in registers.
+ *   x1, z2, log_p and the workspace are required.
+ * finc_gauss_split_merge_f32: x[:, :half] = x1, x[:, half+j] = z2[:, j] * exp(logs_j) + m_j (one fma), without a cat.  `log_p` [B]
+ *   is optional: with it (and the workspace) the call reports the value finc_gauss_split_f32 reports at the result x, from the z2
+ *   it was handed; NULL: no partials are written and the workspace is not touched.
+ * finc_gauss_split_backward_f32: the gradients of finc_gauss_split_f32 given grad_x1, grad_z2 [B][half][HW] and grad_log_p [B] --
+ *   each may be NULL (zeros), not all three -- and the forward's INPUT x.  With E = exp(-logs) and z2 = (x2 - m) * E recomputed
+ *   from raw and G = grad_z2 - grad_log_p[b] * z2:
+ *     grad_x[:, :half] = grad_x1,   grad_x[:, half+j] = G * E_j,
+ *     grad_h[:, 2j] = -G * E_j,   grad_h[:, 2j+1] = -(G * z2 + grad_log_p[b]),
+ *   grad_raw[c] = a[c] * grad_h[c], grad_a[c] = sum grad_h * raw, grad_b[c] = sum grad_h (fixed-order sums through the workspace, no
+ *   atomics: the same inputs give the same bits); each output may be NULL, not all four.  What reaches x[:, :half] through the
+ *   convolution is the caller's (autograd's).
+ * There are no _rawbf16_f32 siblings: a net under autocast hands its output over upcast.
+ */
+int finc_gauss_split_f32(const float *x, const float *raw, const float *a, const float *b, float *x1, float *z2, float *log_p, int B,
+                         int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream);
+int finc_gauss_split_merge_f32(const float *x1, const float *z2, const float *raw, const float *a, const float *b, float *x,
+                               float *log_p, int B, int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream);
+int finc_gauss_split_backward_f32(const float *grad_x1, const float *grad_z2, const float *grad_log_p, const float *x,
+                                  const float *raw, const float *a, const float *b, float *grad_x, float *grad_raw, float *grad_a,
+                                  float *grad_b, int B, int C, int HW, void *workspace, size_t workspace_bytes,
+                                  finc_stream_t stream);
+
+/*
  * ActNorm (layers/actnorm.py:5-66) on its own kernels: activations [B][C][HW] fp32, log_scale and translation [C], any C >= 1
  * (up to FINC_MAX_CQ * FINC_MAX_GROUPS), HW >= 1.
  * finc_actnorm_f32: direction +1: y = (x - translation[c]) * exp(-log_scale[c]) (layers/actnorm.py:34); direction -1:
