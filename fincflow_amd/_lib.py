@@ -49,6 +49,7 @@ SYMBOLS = [
     "finc_split_prior_rawbf16_f32", "finc_split_prior_merge_rawbf16_f32", "finc_split_prior_backward_rawbf16_f32",
     "finc_image_workspace_bytes", "finc_image_encode_u8_f32", "finc_image_encode_f32", "finc_image_decode_f32", "finc_image_decode_u8",
     "finc_gauss_split_f32", "finc_gauss_split_merge_f32", "finc_gauss_split_backward_f32",
+    "finc_split_prior_merge_backward_f32", "finc_split_prior_merge_backward_rawbf16_f32", "finc_gauss_split_merge_backward_f32",
 ]
 
 #: the ABI version this binding is written against (include/finc.h: finc_version)
@@ -86,6 +87,9 @@ IMAGE_BOUNDARY_ABI_VERSION = 115
 #: the version that added the Gaussianized split (finc_gauss_split_f32, finc_gauss_split_merge_f32, finc_gauss_split_backward_f32):
 #: what glow.Split.split / merge launch
 GAUSS_SPLIT_ABI_VERSION = 116
+#: the version that added the backward of the two merges (finc_split_prior_merge_backward_f32, its _rawbf16_f32 sibling,
+#: finc_gauss_split_merge_backward_f32): what a recorded SplitPrior.merge / Split.merge with `hip_recorded_merge` launches
+MERGE_BACKWARD_ABI_VERSION = 117
 
 _lib = None
 
@@ -162,6 +166,11 @@ def lib():
         raise FincError(f"{LIB_PATH} reports finc_version() = {have}, the Gaussianized split's entry points (finc_gauss_split_f32, "
                         f"finc_gauss_split_merge_f32, finc_gauss_split_backward_f32) came with "
                         f"{GAUSS_SPLIT_ABI_VERSION}: rebuild it "
+                        "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
+    if have < MERGE_BACKWARD_ABI_VERSION:
+        raise FincError(f"{LIB_PATH} reports finc_version() = {have}, the backward of the merges "
+                        f"(finc_split_prior_merge_backward_f32, its bfloat16 sibling, finc_gauss_split_merge_backward_f32) came with "
+                        f"{MERGE_BACKWARD_ABI_VERSION}: rebuild it "
                         "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
     L.finc_build_flags.restype = u
     L.finc_clear_fault.restype = i
@@ -265,6 +274,9 @@ def lib():
     L.finc_image_decode_u8.argtypes = L.finc_image_decode_f32.argtypes
     for name in ("finc_split_prior", "finc_split_prior_merge", "finc_split_prior_backward"):    # (the same argument lists)
         getattr(L, name.replace("split_prior", "gauss_split") + "_f32").argtypes = getattr(L, name + "_f32").argtypes
+    L.finc_split_prior_merge_backward_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp]
+    L.finc_split_prior_merge_backward_rawbf16_f32.argtypes = L.finc_split_prior_merge_backward_f32.argtypes
+    L.finc_gauss_split_merge_backward_f32.argtypes = L.finc_split_prior_merge_backward_f32.argtypes
     for name in SYMBOLS:
         getattr(L, name)  # AttributeError here = header and library out of sync
     _lib = L

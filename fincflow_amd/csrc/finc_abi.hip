@@ -190,7 +190,7 @@ static int canonicalize(const T *w_stored, T *w_canon, int G, int Cq, int KH, in
 
 extern "C" {
 
-int finc_version(void) { return 116; }
+int finc_version(void) { return 117; }
 
 unsigned finc_build_flags(void)
 {
@@ -703,7 +703,9 @@ int finc_coupling_rawbf16_f32(const float *x, const uint16_t *raw, const float *
 // Every backward of the coupling: `v` is the activation the mode reads (FincGradMode), x_out the rebuilt input of FINC_GRAD_REBUILD
 // alone, which also allows grad_x == grad_y (and x_out == v); no other output may be an input or another output.  grad_z belongs to
 // FINC_GRAD_SPLIT (nullptr in every other mode): there grad_y and grad_z are the gradients of the two half tensors, and they and
-// grad_logdet (that of log p) may each be absent, not all three.
+// grad_logdet (that of log p) may each be absent, not all three.  FINC_GRAD_MERGE: grad_y is the gradient of the WHOLE tensor and v
+// the merge's output; it or grad_logdet may be absent, not both; grad_x (grad_x1) and x_out (grad_z2) are HALF tensors, and no output
+// may share a byte with an input or with another output.
 extern "C++" {
 template <typename R>
 static int coupling_grad(FincGradMode mode, const float *grad_y, const float *grad_z, const float *grad_logdet, const float *v,
@@ -711,10 +713,23 @@ static int coupling_grad(FincGradMode mode, const float *grad_y, const float *gr
                          void *workspace, size_t workspace_bytes, finc_stream_t stream, bool gauss = false)
 {
     const void *r = raw, *gr = grad_raw;
-    if ((mode == FINC_GRAD_SPLIT ? !grad_y && !grad_z && !grad_logdet : !grad_y) || !v || !raw || !a || !b ||
-        (!x_out && !grad_x && !grad_raw && !grad_a && !grad_b))
+    if ((mode == FINC_GRAD_SPLIT   ? !grad_y && !grad_z && !grad_logdet
+         : mode == FINC_GRAD_MERGE ? !grad_y && !grad_logdet
+                                   : !grad_y) ||
+        !v || !raw || !a || !b || (!x_out && !grad_x && !grad_raw && !grad_a && !grad_b))
         return FINC_ERR_NULL_POINTER;
     if (int e = pixel_dims(B, C, HW, true)) return e;
+    if (mode == FINC_GRAD_MERGE) {
+        const size_t n = (size_t)B * (size_t)C * (size_t)HW, wb = n * sizeof(float), hb = wb / 2, cb = (size_t)C * sizeof(float);
+        const void *in[] = {grad_y, grad_logdet, v, r, a, b}, *out[] = {grad_x, x_out, gr, grad_a, grad_b};
+        const size_t in_bytes[] = {wb, (size_t)B * sizeof(float), wb, n * sizeof(R), cb, cb}, out_bytes[] = {hb, hb, n * sizeof(R), cb, cb};
+        for (int o = 0; o < 5; ++o) {
+            for (int i = 0; i < 6; ++i)
+                if (bytes_overlap(out[o], out_bytes[o], in[i], in_bytes[i])) return FINC_ERR_BAD_DIMS;
+            for (int q = 0; q < o; ++q)
+                if (bytes_overlap(out[o], out_bytes[o], out[q], out_bytes[q])) return FINC_ERR_BAD_DIMS;
+        }
+    }
     if (x_out && (x_out == grad_y || x_out == r || x_out == grad_x || x_out == gr)) return FINC_ERR_BAD_DIMS;
     if (grad_x && ((grad_x == grad_y && mode != FINC_GRAD_REBUILD) || grad_x == grad_z || grad_x == v || grad_x == r)) return FINC_ERR_BAD_DIMS;
     if (grad_raw && (gr == grad_y || gr == grad_z || gr == v || gr == r || gr == grad_x)) return FINC_ERR_BAD_DIMS;
@@ -724,9 +739,9 @@ static int coupling_grad(FincGradMode mode, const float *grad_y, const float *gr
         return FINC_ERR_WORKSPACE;
     if (int e = finc_fault_gate(false)) return e;
     if constexpr (sizeof(R) == 4)
-        if (gauss)                                                          // (FINC_GRAD_SPLIT under the Gaussianized split's law)
-            return finc_gauss_split_grad_launch(grad_y, grad_z, grad_logdet, v, raw, a, b, grad_x, grad_raw, grad_a, grad_b, B, C, HW,
-                                                (float *)workspace, (hipStream_t)stream);
+        if (gauss)                                       // (FINC_GRAD_SPLIT or FINC_GRAD_MERGE under the Gaussianized split's law)
+            return finc_gauss_split_grad_launch(mode, grad_y, grad_z, grad_logdet, v, raw, a, b, x_out, grad_x, grad_raw, grad_a, grad_b, B,
+                                                C, HW, (float *)workspace, (hipStream_t)stream);
     return coupling_grad_launch(mode, grad_y, grad_z, grad_logdet, v, raw, a, b, x_out, grad_x, grad_raw, grad_a, grad_b, B, C, HW,
                                 (float *)workspace, (hipStream_t)stream);
 }
@@ -872,6 +887,32 @@ int finc_gauss_split_backward_f32(const float *grad_x1, const float *grad_z2, co
                                   int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream)
 {
     return coupling_grad(FINC_GRAD_SPLIT, grad_x1, grad_z2, grad_log_p, x, raw, a, b, nullptr, grad_x, grad_raw, grad_a, grad_b, B, C, HW,
+                         workspace, workspace_bytes, stream, true);
+}
+
+// The backward of the two merges, from the merge's OUTPUT: the backward's ladder in its fifth mode, under either law.
+int finc_split_prior_merge_backward_f32(const float *grad_x, const float *grad_log_p, const float *x, const float *raw, const float *a,
+                                        const float *b, float *grad_x1, float *grad_z2, float *grad_raw, float *grad_a, float *grad_b,
+                                        int B, int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    return coupling_grad(FINC_GRAD_MERGE, grad_x, nullptr, grad_log_p, x, raw, a, b, grad_z2, grad_x1, grad_raw, grad_a, grad_b, B, C, HW,
+                         workspace, workspace_bytes, stream);
+}
+
+int finc_split_prior_merge_backward_rawbf16_f32(const float *grad_x, const float *grad_log_p, const float *x, const uint16_t *raw,
+                                                const float *a, const float *b, float *grad_x1, float *grad_z2, uint16_t *grad_raw,
+                                                float *grad_a, float *grad_b, int B, int C, int HW, void *workspace,
+                                                size_t workspace_bytes, finc_stream_t stream)
+{
+    return coupling_grad(FINC_GRAD_MERGE, grad_x, nullptr, grad_log_p, x, raw, a, b, grad_z2, grad_x1, grad_raw, grad_a, grad_b, B, C, HW,
+                         workspace, workspace_bytes, stream);
+}
+
+int finc_gauss_split_merge_backward_f32(const float *grad_x, const float *grad_log_p, const float *x, const float *raw, const float *a,
+                                        const float *b, float *grad_x1, float *grad_z2, float *grad_raw, float *grad_a, float *grad_b,
+                                        int B, int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    return coupling_grad(FINC_GRAD_MERGE, grad_x, nullptr, grad_log_p, x, raw, a, b, grad_z2, grad_x1, grad_raw, grad_a, grad_b, B, C, HW,
                          workspace, workspace_bytes, stream, true);
 }
 

@@ -306,8 +306,9 @@ int finc_mix_gradw_launch(const float *grad_out, const float *in, float *gm, flo
 // Which backward of a per-pixel layer (a mode of the family's one kernel body and one launcher): of direction +1, of direction -1,
 // of direction +1 from its OUTPUT with the direction's input rebuilt in the same pass (training without stored activations), or (the
 // coupling alone) of the split prior's forward: direction +1 with its outputs as two half tensors and a standard-normal score of the
-// second one in the per-image sum.
-enum FincGradMode { FINC_GRAD_FWD = 0, FINC_GRAD_REV = 1, FINC_GRAD_REBUILD = 2, FINC_GRAD_SPLIT = 3 };
+// second one in the per-image sum; or (the coupling alone) of the split prior's merge, direction -1 with its inputs as two half
+// tensors and the same score, from its OUTPUT.
+enum FincGradMode { FINC_GRAD_FWD = 0, FINC_GRAD_REV = 1, FINC_GRAD_REBUILD = 2, FINC_GRAD_SPLIT = 3, FINC_GRAD_MERGE = 4 };
 // C even; `ws` holds finc_coupling_workspace_floats floats (needed with logdet / ga / gb only); direction +1 forward, -1 reverse.
 // logdet[b] = sum s in EITHER direction: the FORWARD map's log-det, at the recovered input when direction is -1; nullptr: none.
 // `split` (glow.SplitPrior with its latent): the side that is NOT the whole [B][C][HW] tensor is two contiguous halves [B][C/2][HW] --
@@ -319,7 +320,8 @@ int finc_coupling_launch(const float *x, const float *xb, const float *raw, cons
 // v: the forward's input (FINC_GRAD_FWD, FINC_GRAD_SPLIT), the reverse's OUTPUT (FINC_GRAD_REV) or the forward's OUTPUT
 // (FINC_GRAD_REBUILD, which also writes the rebuilt input xo); gld: the gradient of the log-det per image; gld, xo, gx, graw, ga, gb may
 // be nullptr.  FINC_GRAD_SPLIT: gy and gz are the gradients of the two half tensors (either may be nullptr: zeros), gld that of log p;
-// gz is nullptr in every other mode.
+// gz is nullptr in every other mode.  FINC_GRAD_MERGE: gy = grad_x (whole) and gld = grad_log_p, either may be nullptr; v = the
+// merge's OUTPUT x; the results for the two half tensors are gx = grad_x1 and xo = grad_z2 [B][C/2][HW].
 int finc_coupling_grad_launch(FincGradMode mode, const float *gy, const float *gz, const float *gld, const float *v, const float *raw,
                               const float *a, const float *b, float *xo, float *gx, float *graw, float *ga, float *gb, int B, int C, int HW,
                               float *ws, hipStream_t st);
@@ -336,12 +338,13 @@ int finc_bias_relu_bf16_launch(const uint16_t *in, const float *bias, uint16_t *
 // finc_coupling_grad_launch under another arithmetic law -- raw channel 2j is the pre-activation of the mean m, 2j+1 that of the
 // log-scale logs; direction +1: y = x1, yb = z2 = (x2 - m) * exp(-logs), direction -1: the whole y from x = x1 and xb = z2 with
 // x2 = z2 * exp(logs) + m; log_p = -sum logs - 1/2 sum z2^2 - 1/2 (C/2) HW log 2 pi (nullptr with direction -1: none, `ws` untouched).
-// The same geometry, workspace and pointer rules; fp32 raw only.
+// The same geometry, workspace and pointer rules; fp32 raw only.  The backward takes FINC_GRAD_SPLIT or FINC_GRAD_MERGE, with the
+// pointers as finc_coupling_grad_launch reads them in that mode.
 int finc_gauss_split_launch(const float *x, const float *xb, const float *raw, const float *a, const float *b, float *y, float *yb,
                             float *log_p, int B, int C, int HW, int direction, float *ws, hipStream_t st);
-int finc_gauss_split_grad_launch(const float *gx1, const float *gz2, const float *glp, const float *x, const float *raw, const float *a,
-                                 const float *b, float *gx, float *graw, float *ga, float *gb, int B, int C, int HW, float *ws,
-                                 hipStream_t st);
+int finc_gauss_split_grad_launch(FincGradMode mode, const float *gy, const float *gz, const float *glp, const float *v, const float *raw,
+                                 const float *a, const float *b, float *xo, float *gx, float *graw, float *ga, float *gb, int B, int C,
+                                 int HW, float *ws, hipStream_t st);
 // ---- ActNorm (transform + log-det, its backward from the forward's OUTPUT, the data-dependent initialisation): finc_actnorm.h, same object ----
 // `ws` holds finc_actnorm_workspace_floats floats (backward with gls / gt, and the initialisation)
 size_t finc_actnorm_workspace_floats(int B, int C, int HW);

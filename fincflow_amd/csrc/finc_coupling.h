@@ -19,6 +19,9 @@
 //                               arithmetic law (CPL_LAW_GAUSS) -- raw channel 2j = the mean's pre-activation, 2j+1 = the log-scale's,
 //                               z2 = (x2 - m) * exp(-logs), log p = -sum logs - 1/2 sum z2^2 - c; its backward is
 //                               finc_gauss_split_bwd_kernel.  fp32 raw only.
+//   * finc_splitprior_merge_bwd_kernel, finc_gauss_merge_bwd_kernel  the backward of the two merges (the split forms in direction
+//                               -1) from the merge's OUTPUT x: cpl_grad's fifth mode under either law -- what a recorded
+//                               glow.SplitPrior.merge / glow.Split.merge launches inside ops.reverse_grad().
 //   * finc_coupling_rev_logdet_kernel  the reverse pass that also sums s per image: the sample and the forward log-det at the
 //                               sample in one pass (FlowSequential.sample_with_log_prob / rsample_with_log_prob).
 //   * finc_bias_relu_kernel     out = max(in + bias[c], 0), in place or not.
@@ -278,6 +281,16 @@ __global__ __launch_bounds__(CPL_THREADS) void finc_gauss_split_kernel(const flo
 //                      gz is nullptr in every other mode.  With LAW = CPL_LAW_GAUSS (this mode only) the forward is the Gaussianized
 //                      split's: E = exp(-logs) and z2 = (x2 - m) * E are recomputed, G = grad_z2 - grad_log_p[img] * z2,
 //                      grad_x2 = G * E, grad_h[2j] (the mean's) = -grad_x2, grad_h[2j+1] (the log-scale's) = -(G * z2 + grad_log_p).
+//   FINC_GRAD_MERGE    of the split prior's merge (cpl_transform<V, -1, LOGP, R, true>: x2 = (z2 - t) * exp(-s), log p = sum s -
+//                      1/2 sum z2^2 - c), from `v` = the merge's OUTPUT x, the convention of FINC_GRAD_REV.  gy = grad_x [B][C][HW]
+//                      and gld = grad_log_p, either may be nullptr (zeros); the two results of the untouched side are contiguous
+//                      HALVES [B][half][HW]: gx = grad_x1 (the first half of grad_x, copied: the direct share only) and xo = grad_z2.
+//                      With g2 = grad_x's second half and E = exp(-s): grad_z2 = g2 * E - grad_log_p * z2, z2 = fma(x2, exp(s), t)
+//                      recomputed only when there is a grad_log_p; grad_t = -(g2 * E), grad_s = -(g2 * x2) + grad_log_p: the REV
+//                      mode's expression trees, so that without grad_log_p grad_raw, grad_a, grad_b and grad_z2 carry that mode's
+//                      bits.  With LAW = CPL_LAW_GAUSS the merge is the Gaussianized split's, x2 = z2 * exp(logs) + m, log p =
+//                      -sum logs - 1/2 sum z2^2 - c: d = x2 - m, z2 = d * exp(-logs), grad_z2 = g2 * exp(logs) - grad_log_p * z2,
+//                      grad_h[2j] = g2, grad_h[2j+1] = g2 * d - grad_log_p.
 // s and exp(s) are recomputed from raw (two transcendentals per element), not saved by the forward.
 // Workgroup = (channel pair j, part): Q parts per pair share its B * HW / V thread items, so the four per-channel sums of a
 // workgroup belong to ONE pair.  Partials: part[(4j + k) * Q + q], k = 0 grad_a[2j], 1 grad_b[2j], 2 grad_a[2j+1], 3 grad_b[2j+1].
@@ -290,10 +303,11 @@ __device__ __forceinline__ void cpl_grad(const float *gy, const float *gz, const
                                          R *__restrict__ graw, float *__restrict__ part, int half, int HW, int nv, int items, int Q,
                                          int sums)
 {
-    constexpr bool REBUILD = MODE == FINC_GRAD_REBUILD, SPLIT = MODE == FINC_GRAD_SPLIT, GAUSS = LAW == CPL_LAW_GAUSS;
-    static_assert(!GAUSS || SPLIT, "the Gaussianized law has the split mode only");
+    constexpr bool REBUILD = MODE == FINC_GRAD_REBUILD, SPLIT = MODE == FINC_GRAD_SPLIT, MERGE = MODE == FINC_GRAD_MERGE;
+    constexpr bool GAUSS = LAW == CPL_LAW_GAUSS;
+    static_assert(!GAUSS || SPLIT || MERGE, "the Gaussianized law has the split and merge modes");
     const int j = (int)blockIdx.x / Q, qi = (int)blockIdx.x - j * Q;
-    const float au = a[2 * j], bu = b[2 * j], at = a[2 * j + 1], bt = REBUILD || SPLIT ? b[2 * j + 1] : 0.f;
+    const float au = a[2 * j], bu = b[2 * j], at = a[2 * j + 1], bt = REBUILD || SPLIT || MERGE ? b[2 * j + 1] : 0.f;
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     for (int idx = qi * CPL_THREADS + (int)threadIdx.x; idx < items; idx += Q * CPL_THREADS) {
         const int img = idx / nv, p = (idx - img * nv) * V;
@@ -307,6 +321,11 @@ __device__ __forceinline__ void cpl_grad(const float *gy, const float *gz, const
             for (int e = 0; e < V; ++e) g1[e] = g2[e] = 0.f;
             if (gx && gy) cpl_load<V>(g1, gy + oh);
             if (gz) cpl_load<V>(g2, gz + oh);
+        } else if constexpr (MERGE) {
+#pragma unroll
+            for (int e = 0; e < V; ++e) g1[e] = g2[e] = 0.f;
+            if (gx && gy) cpl_load<V>(g1, gy + o1);
+            if (gy) cpl_load<V>(g2, gy + o2);
         } else {
             if (gx) cpl_load<V>(g1, gy + o1);
             cpl_load<V>(g2, gy + o2);
@@ -315,12 +334,17 @@ __device__ __forceinline__ void cpl_grad(const float *gy, const float *gz, const
             if (xo) cpl_load<V>(v1, v + o1);
         cpl_load<V>(v2, v + o2);
         cpl_load<V>(u, raw + ou);
-        if (REBUILD || SPLIT || sums) cpl_load<V>(t, raw + ot);
-        const float gl = gld ? gld[img] : (MODE == FINC_GRAD_REV ? -0.f : 0.f);
+        if (REBUILD || SPLIT || (MERGE && (GAUSS || gld)) || sums) cpl_load<V>(t, raw + ot);
+        const float gl = gld ? gld[img] : (MODE == FINC_GRAD_REV || (MERGE && !GAUSS) ? -0.f : 0.f);
 #pragma unroll
         for (int e = 0; e < V; ++e) {
             float ghu, ght;                                        // the gradients of h[2j] and h[2j+1]
-            if constexpr (GAUSS) {
+            if constexpr (GAUSS && MERGE) {
+                const float logs = fmaf(at, t[e], bt), d = v2[e] - fmaf(au, u[e], bu), gE = g2[e] * expf(logs);
+                gx2[e] = gld ? fmaf(-gl, d * expf(-logs), gE) : gE;
+                ghu = g2[e];
+                ght = fmaf(g2[e], d, -gl);
+            } else if constexpr (GAUSS) {
                 const float m = fmaf(au, u[e], bu), E = expf(-fmaf(at, t[e], bt)), z = (v2[e] - m) * E, G = g2[e] - gl * z;
                 gx2[e] = G * E;
                 ghu = -gx2[e];
@@ -335,6 +359,11 @@ __device__ __forceinline__ void cpl_grad(const float *gy, const float *gz, const
                     gx2[e] = g2[e] * expf(-2.f * th);
                     ghu = (-(g2[e] * v2[e]) + gl) * fmaf(-th, th, 1.f);
                     ght = -gx2[e];
+                } else if constexpr (MERGE) {
+                    const float gE = g2[e] * expf(-2.f * th);
+                    gx2[e] = gld ? fmaf(-gl, fmaf(v2[e], expf(2.f * th), fmaf(at, t[e], bt)), gE) : gE;
+                    ghu = (-(g2[e] * v2[e]) + gl) * fmaf(-th, th, 1.f);
+                    ght = -gE;
                 } else if constexpr (SPLIT) {
                     const float E = expf(2.f * th), G = g2[e] - gl * fmaf(v2[e], E, fmaf(at, t[e], bt));
                     gx2[e] = G * E;
@@ -363,7 +392,11 @@ __device__ __forceinline__ void cpl_grad(const float *gy, const float *gz, const
                 cpl_store<V>(xo + o2, x2);
             }
         }
-        if (gx) {
+        if constexpr (MERGE) {
+            const size_t oh = (size_t)img * (size_t)half * (size_t)HW + (size_t)j * HW + p;
+            if (gx) cpl_store<V>(gx + oh, g1);
+            if (xo) cpl_store<V>(xo + oh, gx2);
+        } else if (gx) {
             cpl_store<V>(gx + o1, g1);
             cpl_store<V>(gx + o2, gx2);
         }
@@ -435,6 +468,41 @@ __global__ __launch_bounds__(CPL_THREADS) void finc_gauss_split_bwd_kernel(const
                                                                            int nv, int items, int Q, int sums)
 {
     cpl_grad<V, FINC_GRAD_SPLIT, float, CPL_LAW_GAUSS>(gx1, gz2, glp, x, raw, a, b, nullptr, gx, graw, part, half, HW, nv, items, Q, sums);
+}
+
+// The merges' backward, from the merge's OUTPUT x: the fifth mode under names of its own -- the split prior's on an fp32 and on a
+// bf16 raw, the Gaussianized split's (fp32 raw).  gx1 and gz2 are the half tensors it writes; nothing may overlap.
+template <int V>
+__global__ __launch_bounds__(CPL_THREADS) void finc_splitprior_merge_bwd_kernel(const float *__restrict__ gx, const float *__restrict__ glp,
+                                                                                const float *__restrict__ x, const float *__restrict__ raw,
+                                                                                const float *__restrict__ a, const float *__restrict__ b,
+                                                                                float *__restrict__ gx1, float *__restrict__ gz2,
+                                                                                float *__restrict__ graw, float *__restrict__ part, int half,
+                                                                                int HW, int nv, int items, int Q, int sums)
+{
+    cpl_grad<V, FINC_GRAD_MERGE>(gx, nullptr, glp, x, raw, a, b, gz2, gx1, graw, part, half, HW, nv, items, Q, sums);
+}
+
+template <int V>
+__global__ __launch_bounds__(CPL_THREADS) void finc_splitprior_merge_rawbf16_bwd_kernel(const float *__restrict__ gx, const float *__restrict__ glp,
+                                                                                        const float *__restrict__ x, const __bf16 *__restrict__ raw,
+                                                                                        const float *__restrict__ a, const float *__restrict__ b,
+                                                                                        float *__restrict__ gx1, float *__restrict__ gz2,
+                                                                                        __bf16 *__restrict__ graw, float *__restrict__ part,
+                                                                                        int half, int HW, int nv, int items, int Q, int sums)
+{
+    cpl_grad<V, FINC_GRAD_MERGE, __bf16>(gx, nullptr, glp, x, raw, a, b, gz2, gx1, graw, part, half, HW, nv, items, Q, sums);
+}
+
+template <int V>
+__global__ __launch_bounds__(CPL_THREADS) void finc_gauss_merge_bwd_kernel(const float *__restrict__ gx, const float *__restrict__ glp,
+                                                                           const float *__restrict__ x, const float *__restrict__ raw,
+                                                                           const float *__restrict__ a, const float *__restrict__ b,
+                                                                           float *__restrict__ gx1, float *__restrict__ gz2,
+                                                                           float *__restrict__ graw, float *__restrict__ part, int half, int HW,
+                                                                           int nv, int items, int Q, int sums)
+{
+    cpl_grad<V, FINC_GRAD_MERGE, float, CPL_LAW_GAUSS>(gx, nullptr, glp, x, raw, a, b, gz2, gx1, graw, part, half, HW, nv, items, Q, sums);
 }
 
 // The four modes on a bf16 raw (and a bf16 grad_raw): one kernel, the mode its parameter.  xo == v and gx == gy are the rebuild's;
@@ -623,7 +691,10 @@ template <int V, int MODE>
 void cpl_grad_start(const CplGradPlan &p, hipStream_t st, const float *gy, const float *gz, const float *gld, const float *v,
                     const float *raw, const float *a, const float *b, float *xo, float *gx, float *graw, float *ws, int half, int HW, int sums)
 {
-    if constexpr (MODE == FINC_GRAD_SPLIT)
+    if constexpr (MODE == FINC_GRAD_MERGE)
+        hipLaunchKernelGGL(finc_splitprior_merge_bwd_kernel<V>, p.grid, dim3(CPL_THREADS), 0, st, gy, gld, v, raw, a, b, gx, xo, graw, ws, half,
+                           HW, p.nv, p.items, p.Q, sums);
+    else if constexpr (MODE == FINC_GRAD_SPLIT)
         hipLaunchKernelGGL(finc_splitprior_bwd_kernel<V>, p.grid, dim3(CPL_THREADS), 0, st, gy, gz, gld, v, raw, a, b, gx, graw, ws, half, HW,
                            p.nv, p.items, p.Q, sums);
     else if constexpr (MODE == FINC_GRAD_REBUILD)
@@ -637,8 +708,12 @@ template <int V, int MODE>
 void cpl_grad_start(const CplGradPlan &p, hipStream_t st, const float *gy, const float *gz, const float *gld, const float *v,
                     const __bf16 *raw, const float *a, const float *b, float *xo, float *gx, __bf16 *graw, float *ws, int half, int HW, int sums)
 {
-    hipLaunchKernelGGL((finc_coupling_rawbf16_grad_kernel<V, MODE>), p.grid, dim3(CPL_THREADS), 0, st, gy, gz, gld, v, raw, a, b, xo, gx, graw,
-                       ws, half, HW, p.nv, p.items, p.Q, sums);
+    if constexpr (MODE == FINC_GRAD_MERGE)
+        hipLaunchKernelGGL(finc_splitprior_merge_rawbf16_bwd_kernel<V>, p.grid, dim3(CPL_THREADS), 0, st, gy, gld, v, raw, a, b, gx, xo, graw, ws,
+                           half, HW, p.nv, p.items, p.Q, sums);
+    else
+        hipLaunchKernelGGL((finc_coupling_rawbf16_grad_kernel<V, MODE>), p.grid, dim3(CPL_THREADS), 0, st, gy, gz, gld, v, raw, a, b, xo, gx,
+                           graw, ws, half, HW, p.nv, p.items, p.Q, sums);
 }
 
 template <typename R, int LAW = CPL_LAW_COUPLING>
@@ -649,9 +724,18 @@ int cpl_grad_launch(FincGradMode mode, const float *gy, const float *gz, const f
     const CplGradPlan p = cpl_grad_plan(B, C, HW, half, cpl_bits(gy, gz, v, xo, gx) | cpl_bits16<R>(raw, graw), cpl_bits8<R>(raw, graw));
     if (!p.Q) return FINC_ERR_BAD_DIMS;
 #define CPL_GRAD_START(V, MODE) cpl_grad_start<V, MODE>(p, st, gy, gz, gld, v, raw, a, b, xo, gx, graw, ws, half, HW, sums)
-    if constexpr (LAW == CPL_LAW_GAUSS) {                                  // (FINC_GRAD_SPLIT, fp32 raw)
-        const auto kernel = p.wide ? finc_gauss_split_bwd_kernel<4> : finc_gauss_split_bwd_kernel<1>;
-        hipLaunchKernelGGL(kernel, p.grid, dim3(CPL_THREADS), 0, st, gy, gz, gld, v, raw, a, b, gx, graw, ws, half, HW, p.nv, p.items, p.Q, sums);
+    if constexpr (LAW == CPL_LAW_GAUSS) {                                  // (FINC_GRAD_SPLIT or FINC_GRAD_MERGE, fp32 raw)
+        if (mode == FINC_GRAD_MERGE) {
+            const auto kernel = p.wide ? finc_gauss_merge_bwd_kernel<4> : finc_gauss_merge_bwd_kernel<1>;
+            hipLaunchKernelGGL(kernel, p.grid, dim3(CPL_THREADS), 0, st, gy, gld, v, raw, a, b, gx, xo, graw, ws, half, HW, p.nv, p.items, p.Q,
+                               sums);
+        } else {
+            const auto kernel = p.wide ? finc_gauss_split_bwd_kernel<4> : finc_gauss_split_bwd_kernel<1>;
+            hipLaunchKernelGGL(kernel, p.grid, dim3(CPL_THREADS), 0, st, gy, gz, gld, v, raw, a, b, gx, graw, ws, half, HW, p.nv, p.items, p.Q,
+                               sums);
+        }
+    } else if (mode == FINC_GRAD_MERGE) {
+        if (p.wide) CPL_GRAD_START(4, FINC_GRAD_MERGE); else CPL_GRAD_START(1, FINC_GRAD_MERGE);
     } else if (mode == FINC_GRAD_SPLIT) {
         if (p.wide) CPL_GRAD_START(4, FINC_GRAD_SPLIT); else CPL_GRAD_START(1, FINC_GRAD_SPLIT);
     } else if (mode == FINC_GRAD_REBUILD) {
@@ -698,11 +782,11 @@ int finc_coupling_grad_launch(FincGradMode mode, const float *gy, const float *g
 {
     return cpl_grad_launch<float>(mode, gy, gz, gld, v, raw, a, b, xo, gx, graw, ga, gb, B, C, HW, ws, st);
 }
-int finc_gauss_split_grad_launch(const float *gx1, const float *gz2, const float *glp, const float *x, const float *raw, const float *a,
-                                 const float *b, float *gx, float *graw, float *ga, float *gb, int B, int C, int HW, float *ws,
-                                 hipStream_t st)
+int finc_gauss_split_grad_launch(FincGradMode mode, const float *gy, const float *gz, const float *glp, const float *v, const float *raw,
+                                 const float *a, const float *b, float *xo, float *gx, float *graw, float *ga, float *gb, int B, int C,
+                                 int HW, float *ws, hipStream_t st)
 {
-    return cpl_grad_launch<float, CPL_LAW_GAUSS>(FINC_GRAD_SPLIT, gx1, gz2, glp, x, raw, a, b, nullptr, gx, graw, ga, gb, B, C, HW, ws, st);
+    return cpl_grad_launch<float, CPL_LAW_GAUSS>(mode, gy, gz, glp, v, raw, a, b, xo, gx, graw, ga, gb, B, C, HW, ws, st);
 }
 int finc_coupling_rawbf16_grad_launch(FincGradMode mode, const float *gy, const float *gz, const float *gld, const float *v,
                                       const uint16_t *raw, const float *a, const float *b, float *xo, float *gx, uint16_t *graw, float *ga,

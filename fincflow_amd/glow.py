@@ -22,11 +22,12 @@ Reference semantics followed:
                  on the device the part behind the net is one HIP launch (ops.finc_coupling)
   SplitPrior     layers/splitprior.py:7-41       Coupling + factor out the second half under a standard normal; `split` / `merge`
                  hand that half out and take it back (FlowSequential.encode / decode), one HIP launch each (ops.finc_split_prior,
-                 ops.finc_split_prior_merge, ops.split_prior_forward)
+                 ops.finc_split_prior_merge, ops.split_prior_forward); with `hip_recorded_merge` a `merge` recorded inside
+                 ops.reverse_grad() too (ops.split_prior_merge)
   Split          layers/split.py:4-52            the Gaussianized split (`Gaussianize`): the second half modelled as N(m, exp(logs)^2) with
                  (m, logs) from ONE zero-initialised 3x3 convolution of the first; the `split` / `merge` / `draw` protocol of SplitPrior,
                  one HIP launch each behind that convolution (ops.finc_gauss_split, ops.finc_gauss_split_merge,
-                 ops.gauss_split_forward)
+                 ops.gauss_split_forward; with `hip_recorded_merge` ops.gauss_split_merge for a recorded `merge`)
   Normalization, LogitTransform, Dequantization  layers/normalize.py, transforms.py:6-19, dequantize.py
                  with `FlowSequential.fuse_image_boundary` these and the first Squeeze are one HIP launch each way
                  (ops.finc_image_encode, ops.finc_image_decode: uint8 or fp32 images in, fp32 or uint8 images out)
@@ -588,7 +589,14 @@ class SplitPrior(FlowLayer):
     reference's protocol: `forward` scores that half and drops it, `reverse` draws a fresh one.  `split` / `merge` are the same two
     maps with the half handed out and taken back -- what `FlowSequential.encode` / `decode` walk, an exact round trip -- and on the
     device, with a `GaussianPrior` base, one HIP launch each (`ops.finc_split_prior`, `ops.finc_split_prior_merge`: the transform,
-    the two half tensors and log p = log-det + the base's score from one pass; no `cat`, no slices, no PyTorch log-prob chain)."""
+    the two half tensors and log p = log-det + the base's score from one pass; no `cat`, no slices, no PyTorch log-prob chain).
+    `hip_recorded_merge` (per instance, off by default; `create_model(hip_recorded_merge=True)` sets it): a `merge` that autograd
+    records inside `ops.reverse_grad()` is then that one launch as well, with ONE HIP backward (`ops.split_prior_merge`:
+    finc_split_prior_merge_backward_f32) in place of `cat`, the coupling's reverse and the `base.log_prob` chain; its sums round
+    differently from those lines, which is why it is a switch."""
+
+    #: record `merge` inside `ops.reverse_grad()` as one HIP launch with a HIP backward of its own (see the class docstring)
+    hip_recorded_merge = False
 
     def __init__(self, input_size, distribution, width=512):
         super().__init__()
@@ -635,12 +643,17 @@ class SplitPrior(FlowLayer):
         `temperature`); with `with_log_prob`, `(x, log_p)` with log_p [B] = `split`'s value at x.  Without a graph, on the device: the
         net on `x1` itself and `ops.finc_split_prior_merge` -- no `cat`.  While autograd records (inside `ops.reverse_grad()` that is
         the HIP path of `Coupling.reverse` / `reverse_with_logdet`) and everywhere else: `cat`, the coupling's reverse and
-        `base.log_prob`, the lines of `reverse` / `reverse_with_logdet`."""
+        `base.log_prob`, the lines of `reverse` / `reverse_with_logdet`.  With `hip_recorded_merge` set, a merge recorded inside
+        `ops.reverse_grad()` is instead the net on `x1` itself (`_raw_train`) and `ops.split_prior_merge`: one launch, one HIP backward."""
         if z2 is None:
             z2 = self.draw(len(x1), context, temperature)
         t = self.transform
         records = torch.is_grad_enabled() and (z2.requires_grad or t._records_graph(x1, context))
-        if not records and x1.dim() == 4 and x1.shape[1] == self.n_channels // 2 and self._hip_latent(x1, z2):
+        hip_recorded = records and self.hip_recorded_merge and ops.reverse_grad_enabled()
+        if (not records or hip_recorded) and x1.dim() == 4 and x1.shape[1] == self.n_channels // 2 and self._hip_latent(x1, z2):
+            if hip_recorded:
+                a, b = t._scale_shift()
+                return ops.split_prior_merge(x1, z2, t._raw_train(x1, context), a, b, want_log_p=with_log_prob)
             x1, z2 = x1.contiguous(), z2.contiguous()
             a, b = t._scale_shift_cached()
             return ops.finc_split_prior_merge(x1, z2, t._raw_inference(x1, context), a, b, want_log_p=with_log_prob)
@@ -747,7 +760,13 @@ class Split(FlowLayer):
     without a graph, `ops.gauss_split_forward` (backward: finc_gauss_split_backward_f32) while autograd records `split` /
     `forward`.  Everything else -- CPU tensors, float64, another base, a `merge` that autograd records (inside
     `ops.reverse_grad()` too) -- keeps the PyTorch lines, which are differentiable as they are.  The layer takes no part in an
-    invertible run (`FlowSequential.invertible_backward` ends one at it, as at a `SplitPrior`)."""
+    invertible run (`FlowSequential.invertible_backward` ends one at it, as at a `SplitPrior`).
+    `hip_recorded_merge` (per instance, off by default; `create_model(hip_recorded_merge=True)` sets it): a `merge` that autograd
+    records inside `ops.reverse_grad()` is then the convolution and ONE launch with ONE HIP backward (`ops.gauss_split_merge`:
+    finc_gauss_split_merge_backward_f32) -- `reverse` / `reverse_with_logdet` are `merge` on a draw and follow it."""
+
+    #: record `merge` inside `ops.reverse_grad()` as one HIP launch with a HIP backward of its own (see the class docstring)
+    hip_recorded_merge = False
 
     def __init__(self, input_size, distribution):
         super().__init__()
@@ -789,11 +808,17 @@ class Split(FlowLayer):
         """The inverse of `split`: x from the kept half `x1` and the factored-out half `z2` (None: drawn from the base, times
         `temperature`); with `with_log_prob`, `(x, log_p)` with log_p [B] = `split`'s value at x.  Without a graph, on the device: the
         convolution of `x1` and `ops.finc_gauss_split_merge`, which writes the whole x -- no `cat`.  While autograd records, and
-        everywhere else: the PyTorch lines."""
+        everywhere else: the PyTorch lines -- unless `hip_recorded_merge` is set and the merge is recorded inside
+        `ops.reverse_grad()`: then the recorded convolution of `x1` and `ops.gauss_split_merge`, one launch with one HIP backward."""
         if z2 is None:
             z2 = self.draw(len(x1), context, temperature)
         g = self.gaussianize
-        if (not g._records_graph(x1, z2) and x1.dim() == 4 and x1.shape[1] == self.n_channels // 2 and self._hip_latent(x1, z2)):
+        records = g._records_graph(x1, z2)
+        hip_recorded = records and self.hip_recorded_merge and ops.reverse_grad_enabled()
+        if (not records or hip_recorded) and x1.dim() == 4 and x1.shape[1] == self.n_channels // 2 and self._hip_latent(x1, z2):
+            if hip_recorded:
+                a, b = g._scale_shift()
+                return ops.gauss_split_merge(x1, z2, g._raw(x1), a, b, want_log_p=with_log_prob)
             x1, z2 = x1.contiguous(), z2.contiguous()
             a, b = g._scale_shift_cached()
             return ops.finc_gauss_split_merge(x1, z2, g._raw_inference(x1), a, b, want_log_p=with_log_prob)
@@ -879,10 +904,11 @@ class Dequantization(FlowLayer):
 
 
 def create_model(num_blocks=3, block_size=32, actnorm=False, split_prior=False, image_size=(3, 32, 32),
-                 preprocess=True, coupling_width=512, gaussianize_split=False):
+                 preprocess=True, coupling_width=512, gaussianize_split=False, hip_recorded_merge=False):
     """fastflow/fastflow_cifar.py:35-63: Squeeze -> [FastFlowUnit, (ActNorm), Conv1x1, Coupling] x block_size
     (-> SplitPrior) per block, under a standard-normal base.  `gaussianize_split` (with `split_prior`): the level boundary is the
-    Gaussianized `Split` instead of a `SplitPrior`, the switch of fastflow_cifar_multi_gpu.py:264-265."""
+    Gaussianized `Split` instead of a `SplitPrior`, the switch of fastflow_cifar_multi_gpu.py:264-265.  `hip_recorded_merge`: the
+    boundaries record their `merge` inside `ops.reverse_grad()` on the HIP kernels (`SplitPrior.hip_recorded_merge`)."""
     size = tuple(image_size)
     layers = []
     if preprocess:
@@ -900,5 +926,7 @@ def create_model(num_blocks=3, block_size=32, actnorm=False, split_prior=False, 
             layers.append(Coupling(size, width=coupling_width))
         if split_prior and level < num_blocks - 1:
             layers.append(Split(size, GaussianPrior) if gaussianize_split else SplitPrior(size, GaussianPrior, width=coupling_width))
+            if hip_recorded_merge:
+                layers[-1].hip_recorded_merge = True
             size = (size[0] // 2, size[1], size[2])
     return FlowSequential(GaussianPrior(size), *layers)

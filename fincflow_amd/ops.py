@@ -485,27 +485,35 @@ def finc_coupling(x, raw, a, b, direction=1, want_logdet=False, out=None):
     return _coupling_transform("", x, raw, a, b, (direction,), bool(want_logdet) and direction == 1, out)
 
 
-def _coupling_grads(entry, grad_y, grad_logdet, v, raw, a, b, what, whose, need_acts, need_sums, family="finc_coupling"):
+def _coupling_grads(entry, grad_y, grad_logdet, v, raw, a, b, what, whose, need_acts, need_sums, family="finc_coupling",
+                    half_outs=False):
     """One backward entry point of the coupling behind its wrapper: the checks, the outputs asked for -- `need_acts`: (x,) grad_x,
     grad_raw; `need_sums`: grad_a, grad_b -- the workspace and the call.  `v`: the activation that entry point reads, "input" or
     "output" (`what`) of `whose` pass; grad_logdet: a tuple, empty for the entry point that takes none.  `entry`: the name between
     "finc_coupling" (or `family`) and the suffix of `raw`'s element type; grad_raw is allocated like `raw` (bfloat16 for a bfloat16
-    `raw`).  grad_y as a tuple: the gradients of the split prior's two half tensors, each of which may be None (absent: NULL)."""
+    `raw`).  grad_y as a tuple: the gradients of the split prior's two half tensors, each of which may be None (absent: NULL).
+    `half_outs` (the merges' backward): grad_y is the gradient of the whole tensor and may be None (absent: NULL), and the
+    activation-like outputs in front of grad_raw are half tensors [B,C/2,H,W]."""
     if isinstance(grad_y, tuple):
         _coupling_args(v, raw, a, b, what, halves=grad_y)
     else:
         _coupling_args(v, raw, a, b, what)
-        _require_device(grad_y, "grad_output")
-        if grad_y.shape != v.shape or grad_y.device != v.device:
-            raise ValueError(f"grad_output must match {whose} in shape and device")
+        if grad_y is not None or not half_outs:
+            _require_device(grad_y, "grad_output")
+            if grad_y.shape != v.shape or grad_y.device != v.device:
+                raise ValueError(f"grad_output must match {whose} in shape and device")
         grad_y = (grad_y,)
     entry = _coupling_entry(entry, raw, family)
     B, C, H, W = v.shape
     for g in grad_logdet:
         _per_image(g, "grad_logdet", v)
     sums = tuple(torch.empty(C, dtype=torch.float32, device=v.device) if n else None for n in need_sums)
-    acts = (v,) * (len(need_acts) - 1) + (raw,)                   # (x,) grad_x like the activations, grad_raw like raw
-    outs = tuple(torch.empty_like(t) if n else None for t, n in zip(acts, need_acts)) + sums
+    if half_outs:
+        outs = tuple(torch.empty(B, C // 2, H, W, dtype=v.dtype, device=v.device) if n else None for n in need_acts[:-1])
+        outs += (torch.empty_like(raw) if need_acts[-1] else None,) + sums
+    else:
+        acts = (v,) * (len(need_acts) - 1) + (raw,)               # (x,) grad_x like the activations, grad_raw like raw
+        outs = tuple(torch.empty_like(t) if n else None for t, n in zip(acts, need_acts)) + sums
     if _nothing_to_launch(v, outs, sums):
         return outs
     nbytes = _lib.lib().finc_coupling_workspace_bytes(B, C, H * W) if any(need_sums) else None
@@ -790,6 +798,96 @@ def gauss_split_forward(x, raw, a, b):
     """`finc_gauss_split(x, raw, a, b)` under autograd: returns (x1, z2, log_p), gradients for `x`, `raw`, `a` and `b`, each computed
     only where needed."""
     return _FincGaussSplitFunction.apply(x, raw, a, b)
+
+
+def _merge_backward(family, grad_x, grad_log_p, x, raw, a, b, needs):
+    if grad_x is None and grad_log_p is None:
+        raise ValueError(f"{family}_merge_backward needs grad_x or grad_log_p")
+    return _coupling_grads("_merge_backward", grad_x, (grad_log_p,), x, raw, a, b, "output", "the merge's output", needs[:3], needs[3:],
+                           family=family, half_outs=True)
+
+
+def finc_split_prior_merge_backward(grad_x, grad_log_p, x, raw, a, b, need_gx1=True, need_gz2=True, need_graw=True, need_ga=True,
+                                    need_gb=True):
+    """Gradients of `finc_split_prior_merge(..., want_log_p=True)` (include/finc.h: finc_split_prior_merge_backward_f32), given
+    grad_x [B,C,H,W] and grad_log_p [B] -- either may be None (absent, handed over as NULL), not both -- and the merge's OUTPUT `x`:
+    (grad_x1, grad_z2, grad_raw, grad_a, grad_b), each computed only if asked for (None otherwise).  grad_x1, grad_z2 [B,C/2,H,W];
+    grad_x1 is grad_x[:, :C/2]: what reaches x1 through the net is the caller's (autograd's).  z2, tanh and exp(-s) are recomputed
+    from `raw`; a bfloat16 `raw` gives a bfloat16 grad_raw.  With grad_log_p None, grad_z2, grad_raw, grad_a and grad_b have the bits
+    of `finc_coupling_reverse_backward` on the same arguments.  Fixed-order sums: the same inputs give the same bits."""
+    return _merge_backward("finc_split_prior", grad_x, grad_log_p, x, raw, a, b, (need_gx1, need_gz2, need_graw, need_ga, need_gb))
+
+
+def finc_gauss_split_merge_backward(grad_x, grad_log_p, x, raw, a, b, need_gx1=True, need_gz2=True, need_graw=True, need_ga=True,
+                                    need_gb=True):
+    """Gradients of `finc_gauss_split_merge(..., want_log_p=True)` (include/finc.h: finc_gauss_split_merge_backward_f32), given
+    grad_x [B,C,H,W] and grad_log_p [B] -- either may be None (absent, handed over as NULL), not both -- and the merge's OUTPUT `x`:
+    (grad_x1, grad_z2, grad_raw, grad_a, grad_b), each computed only if asked for (None otherwise).  grad_x1 is grad_x[:, :C/2]: what
+    reaches x1 through the convolution is the caller's (autograd's).  z2 and exp(logs) are recomputed from `raw` (fp32 only)."""
+    _gauss_split_raw(raw)
+    return _merge_backward("finc_gauss_split", grad_x, grad_log_p, x, raw, a, b, (need_gx1, need_gz2, need_graw, need_ga, need_gb))
+
+
+def _merge_record(ctx, merge, x1, z2, raw, a, b, want_log_p):
+    """The forward of a merge's Function.  Saved: the OUTPUT x -- the tensor the next layer of a reverse chain keeps anyway -- with
+    raw, a and b."""
+    x1, z2, raw, a, b = x1.contiguous(), z2.contiguous(), raw.contiguous(), a.contiguous(), b.contiguous()
+    out = merge(x1, z2, raw, a, b, want_log_p=want_log_p)
+    ctx.save_for_backward(out[0] if want_log_p else out, raw, a, b)
+    ctx.set_materialize_grads(False)
+    return out
+
+
+def _merge_differentiate(ctx, merge_backward, grad_x, grad_log_p):
+    """The backward of a merge's Function: ONE launch, only what `needs_input_grad` asks for.  A result nobody used arrives as None
+    and goes to the kernel as NULL."""
+    x, raw, a, b = ctx.saved_tensors
+    need = ctx.needs_input_grad
+    grads = [None if g is None else g.contiguous() for g in (grad_x, grad_log_p)]
+    if all(g is None for g in grads):
+        return (None,) * 6
+    return merge_backward(*grads, x, raw, a, b, need_gx1=need[0], need_gz2=need[1], need_graw=need[2], need_ga=need[3],
+                          need_gb=need[4]) + (None,)
+
+
+class _FincSplitPriorMergeFunction(torch.autograd.Function):
+    """`finc_split_prior_merge` under autograd (inside `reverse_grad()`): x, or (x, log_p), and their backward on the HIP kernel
+    (finc_split_prior_merge_backward_f32 / _rawbf16_f32)."""
+
+    @staticmethod
+    def forward(ctx, x1, z2, raw, a, b, want_log_p):
+        return _merge_record(ctx, finc_split_prior_merge, x1, z2, raw, a, b, want_log_p)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_x, grad_log_p=None):
+        return _merge_differentiate(ctx, finc_split_prior_merge_backward, grad_x, grad_log_p)
+
+
+class _FincGaussSplitMergeFunction(torch.autograd.Function):
+    """`finc_gauss_split_merge` under autograd (inside `reverse_grad()`): x, or (x, log_p), and their backward on the HIP kernel
+    (finc_gauss_split_merge_backward_f32)."""
+
+    @staticmethod
+    def forward(ctx, x1, z2, raw, a, b, want_log_p):
+        return _merge_record(ctx, finc_gauss_split_merge, x1, z2, raw, a, b, want_log_p)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_x, grad_log_p=None):
+        return _merge_differentiate(ctx, finc_gauss_split_merge_backward, grad_x, grad_log_p)
+
+
+def split_prior_merge(x1, z2, raw, a, b, want_log_p=False):
+    """`finc_split_prior_merge(x1, z2, raw, a, b, want_log_p)` under autograd: x, or (x, log_p), with gradients for `x1` (the direct
+    share), `z2`, `raw`, `a` and `b`, each computed only where needed, from ONE backward launch."""
+    return _FincSplitPriorMergeFunction.apply(x1, z2, raw, a, b, bool(want_log_p))
+
+
+def gauss_split_merge(x1, z2, raw, a, b, want_log_p=False):
+    """`finc_gauss_split_merge(x1, z2, raw, a, b, want_log_p)` under autograd: x, or (x, log_p), with gradients for `x1` (the direct
+    share), `z2`, `raw`, `a` and `b`, each computed only where needed, from ONE backward launch."""
+    return _FincGaussSplitMergeFunction.apply(x1, z2, raw, a, b, bool(want_log_p))
 
 
 def finc_bias_relu(x, bias, out=None):

@@ -509,6 +509,40 @@ int finc_gauss_split_backward_f32(const float *grad_x1, const float *grad_z2, co
                                   finc_stream_t stream);
 
 /*
+ * The backward of the two merges (version 117): what a recorded glow.SplitPrior.merge / glow.Split.merge launches inside
+ * ops.reverse_grad().  Each differentiates its merge from the merge's OUTPUT x [B][C][HW] (the convention of
+ * finc_coupling_reverse_backward_f32: the next layer of a reverse chain keeps x anyway), given grad_x [B][C][HW] and grad_log_p [B] --
+ * either may be NULL (zeros), not both -- with raw, a, b as the merge had them.  With g2 = grad_x[:, half+j], x2 = x[:, half+j],
+ * glp = grad_log_p[b] and h = a * raw + b:
+ * finc_split_prior_merge_backward_f32 (of finc_split_prior_merge_f32: x2 = (z2 - t) * exp(-s), log p = sum s - 1/2 sum z2^2 - c):
+ *   s = 2 tanh(h[:, 2j] / 2), E = exp(-s), z2 = x2 * exp(s) + t recomputed from raw:
+ *     grad_z2 = g2 * E - glp * z2,   grad_t = -g2 * E,   grad_s = -g2 * x2 + glp,
+ *     grad_h[:, 2j] = grad_s * (1 - (s/2)^2),   grad_h[:, 2j+1] = grad_t.
+ *   With grad_log_p NULL, grad_z2, grad_raw, grad_a and grad_b carry the bits of finc_coupling_reverse_backward_f32 on the same
+ *   (grad_x, x, raw, a, b), grad_z2 those of the second half of its grad_x.
+ * finc_split_prior_merge_backward_rawbf16_f32: the same on a bf16 raw; grad_raw is written in bf16, rounded once behind the fp32 sums.
+ * finc_gauss_split_merge_backward_f32 (of finc_gauss_split_merge_f32: x2 = z2 * exp(logs) + m, log p = -sum logs - 1/2 sum z2^2 - c;
+ *   fp32 raw only):  d = x2 - m, z2 = d * exp(-logs):
+ *     grad_z2 = g2 * exp(logs) - glp * z2,   grad_h[:, 2j] = g2,   grad_h[:, 2j+1] = g2 * d - glp.
+ * All three: grad_x1 [B][half][HW] = grad_x[:, :half], the direct share only, copied by the same threads (what reaches x1 through the
+ * net or the convolution is the caller's, autograd's); grad_z2 [B][half][HW]; grad_raw[c] = a[c] * grad_h[c] like raw; grad_a[c] =
+ * sum grad_h * raw, grad_b[c] = sum grad_h (fixed-order sums through the workspace, finc_coupling_workspace_bytes, no atomics: the same
+ * inputs give the same bits).  Each output may be NULL, not all five.  No output may share a byte with an input or with another
+ * output (FINC_ERR_BAD_DIMS).  The 16-byte-piece rule counts every pointer of the call, the half tensors included.  Refusal order:
+ * NULL -> dims and overlap -> alignment -> channel count -> workspace.
+ */
+int finc_split_prior_merge_backward_f32(const float *grad_x, const float *grad_log_p, const float *x, const float *raw, const float *a,
+                                        const float *b, float *grad_x1, float *grad_z2, float *grad_raw, float *grad_a, float *grad_b,
+                                        int B, int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream);
+int finc_split_prior_merge_backward_rawbf16_f32(const float *grad_x, const float *grad_log_p, const float *x, const uint16_t *raw,
+                                                const float *a, const float *b, float *grad_x1, float *grad_z2, uint16_t *grad_raw,
+                                                float *grad_a, float *grad_b, int B, int C, int HW, void *workspace,
+                                                size_t workspace_bytes, finc_stream_t stream);
+int finc_gauss_split_merge_backward_f32(const float *grad_x, const float *grad_log_p, const float *x, const float *raw, const float *a,
+                                        const float *b, float *grad_x1, float *grad_z2, float *grad_raw, float *grad_a, float *grad_b,
+                                        int B, int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream);
+
+/*
  * ActNorm (layers/actnorm.py:5-66) on its own kernels: activations [B][C][HW] fp32, log_scale and translation [C], any C >= 1
  * (up to FINC_MAX_CQ * FINC_MAX_GROUPS), HW >= 1.
  * finc_actnorm_f32: direction +1: y = (x - translation[c]) * exp(-log_scale[c]) (layers/actnorm.py:34); direction -1:
