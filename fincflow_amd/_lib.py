@@ -50,6 +50,7 @@ SYMBOLS = [
     "finc_image_workspace_bytes", "finc_image_encode_u8_f32", "finc_image_encode_f32", "finc_image_decode_f32", "finc_image_decode_u8",
     "finc_gauss_split_f32", "finc_gauss_split_merge_f32", "finc_gauss_split_backward_f32",
     "finc_split_prior_merge_backward_f32", "finc_split_prior_merge_backward_rawbf16_f32", "finc_gauss_split_merge_backward_f32",
+    "finc_plu_supported_f32", "finc_plu_compose_f32", "finc_plu_compose_backward_f32",
 ]
 
 #: the ABI version this binding is written against (include/finc.h: finc_version)
@@ -90,6 +91,9 @@ GAUSS_SPLIT_ABI_VERSION = 116
 #: the version that added the backward of the two merges (finc_split_prior_merge_backward_f32, its _rawbf16_f32 sibling,
 #: finc_gauss_split_merge_backward_f32): what a recorded SplitPrior.merge / Split.merge with `hip_recorded_merge` launches
 MERGE_BACKWARD_ABI_VERSION = 117
+#: the version that added the PLU-parametrised 1x1 convolution's parameter work (finc_plu_supported_f32, finc_plu_compose_f32,
+#: finc_plu_compose_backward_f32): what glow.Conv1x1LU launches
+PLU_ABI_VERSION = 118
 
 _lib = None
 
@@ -171,6 +175,10 @@ def lib():
         raise FincError(f"{LIB_PATH} reports finc_version() = {have}, the backward of the merges "
                         f"(finc_split_prior_merge_backward_f32, its bfloat16 sibling, finc_gauss_split_merge_backward_f32) came with "
                         f"{MERGE_BACKWARD_ABI_VERSION}: rebuild it "
+                        "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
+    if have < PLU_ABI_VERSION:
+        raise FincError(f"{LIB_PATH} reports finc_version() = {have}, the PLU-parametrised 1x1 convolution's entry points "
+                        f"(finc_plu_compose_f32, finc_plu_compose_backward_f32) came with {PLU_ABI_VERSION}: rebuild it "
                         "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
     L.finc_build_flags.restype = u
     L.finc_clear_fault.restype = i
@@ -277,6 +285,9 @@ def lib():
     L.finc_split_prior_merge_backward_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp]
     L.finc_split_prior_merge_backward_rawbf16_f32.argtypes = L.finc_split_prior_merge_backward_f32.argtypes
     L.finc_gauss_split_merge_backward_f32.argtypes = L.finc_split_prior_merge_backward_f32.argtypes
+    L.finc_plu_supported_f32.argtypes = [i]
+    L.finc_plu_compose_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, vp]
+    L.finc_plu_compose_backward_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp]
     for name in SYMBOLS:
         getattr(L, name)  # AttributeError here = header and library out of sync
     _lib = L

@@ -190,7 +190,7 @@ static int canonicalize(const T *w_stored, T *w_canon, int G, int Cq, int KH, in
 
 extern "C" {
 
-int finc_version(void) { return 117; }
+int finc_version(void) { return 118; }
 
 unsigned finc_build_flags(void)
 {
@@ -1307,6 +1307,55 @@ int finc_negate_f32(float *p, size_t n, finc_stream_t stream)
     if (misaligned(p)) return FINC_ERR_ALIGNMENT;
     if (int e = finc_fault_gate(false)) return e;
     return finc_negate_launch(p, n, (hipStream_t)stream);
+}
+
+// ---- the PLU-parametrised 1x1 convolution's parameter work (finc_plu.h) ----
+int finc_plu_supported_f32(int C) { return finc_plu_supported(C) ? 1 : 0; }
+
+// does an output share a byte with one of the five inputs, with `extra` (the incoming gradients) or with an earlier output?
+// sizes in floats: [C][C] matrices, [C] vectors, one-float scalars
+struct PluSpan { const void *p; size_t n; };
+static bool plu_overlap(const PluSpan *in, int n_in, const PluSpan *out, int n_out)
+{
+    for (int o = 0; o < n_out; ++o) {
+        for (int i = 0; i < n_in; ++i)
+            if (bytes_overlap(out[o].p, out[o].n * 4, in[i].p, in[i].n * 4)) return true;
+        for (int q = 0; q < o; ++q)
+            if (bytes_overlap(out[o].p, out[o].n * 4, out[q].p, out[q].n * 4)) return true;
+    }
+    return false;
+}
+
+int finc_plu_compose_f32(const float *lower, const float *upper, const float *log_s, const float *sign_s, const int *perm, float *w,
+                         float *w_inv, float *logdet, int C, finc_stream_t stream)
+{
+    if (!lower || !upper || !log_s || !sign_s || !perm || (!w && !w_inv && !logdet)) return FINC_ERR_NULL_POINTER;
+    if (C < 1) return FINC_ERR_BAD_DIMS;
+    const size_t cc = (size_t)C * C, c = (size_t)C;
+    const PluSpan in[] = {{lower, cc}, {upper, cc}, {log_s, c}, {sign_s, c}, {perm, c}}, out[] = {{w, cc}, {w_inv, cc}, {logdet, 1}};
+    if (plu_overlap(in, 5, out, 3)) return FINC_ERR_BAD_DIMS;
+    if (misaligned(lower, upper, log_s, sign_s, w, w_inv, logdet) || misaligned(perm)) return FINC_ERR_ALIGNMENT;
+    if (!finc_plu_supported(C)) return FINC_ERR_UNSUPPORTED;
+    if (int e = finc_fault_gate(false)) return e;
+    return finc_plu_compose_launch(lower, upper, log_s, sign_s, perm, w, w_inv, logdet, C, (hipStream_t)stream);
+}
+
+int finc_plu_compose_backward_f32(const float *grad_w, const float *grad_logdet, const float *lower, const float *upper,
+                                  const float *log_s, const float *sign_s, const int *perm, float *grad_lower, float *grad_upper,
+                                  float *grad_log_s, int C, finc_stream_t stream)
+{
+    if (!grad_w || !lower || !upper || !log_s || !sign_s || !perm || (!grad_lower && !grad_upper && !grad_log_s)) return FINC_ERR_NULL_POINTER;
+    if (C < 1) return FINC_ERR_BAD_DIMS;
+    const size_t cc = (size_t)C * C, c = (size_t)C;
+    const PluSpan in[] = {{grad_w, cc}, {grad_logdet, 1}, {lower, cc}, {upper, cc}, {log_s, c}, {sign_s, c}, {perm, c}},
+                  out[] = {{grad_lower, cc}, {grad_upper, cc}, {grad_log_s, c}};
+    if (plu_overlap(in, 7, out, 3)) return FINC_ERR_BAD_DIMS;
+    if (misaligned(grad_w, grad_logdet, lower, upper, log_s, sign_s, grad_lower, grad_upper, grad_log_s) || misaligned(perm))
+        return FINC_ERR_ALIGNMENT;
+    if (!finc_plu_supported(C)) return FINC_ERR_UNSUPPORTED;
+    if (int e = finc_fault_gate(false)) return e;
+    return finc_plu_compose_bwd_launch(grad_w, grad_logdet, lower, upper, log_s, sign_s, perm, grad_lower, grad_upper, grad_log_s, C,
+                                       (hipStream_t)stream);
 }
 
 // the one-call form's workspace: the adjoint bank, lead_t, one activation-sized buffer (y, when the caller skips grad_z), then what the

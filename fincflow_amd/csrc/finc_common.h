@@ -374,3 +374,13 @@ int finc_adjoint_weights_launch(const float *wc, float *w_adj, float *lead_t, in
 // v <- blockdiag(L^-T) v in place: finc_mix_launch where the channel count has an instantiation, the grouped kernel otherwise
 int finc_lead_launch(float *v, const float *lead_t, int B, int G, int Cq, int HW, hipStream_t st);
 int finc_negate_launch(float *p, size_t n, hipStream_t st);
+// ---- the PLU-parametrised 1x1 convolution's parameter work (W, W^-1, log|det W| and their backward): finc_plu.h, same object ----
+// the widest matrix the compose kernels take: the staged rows of a workgroup are 88 bytes of LDS per channel
+constexpr int FINC_PLU_MAX_C = 512;
+bool finc_plu_supported(int C);
+// any of w [C][C], w_inv [C][C], logdet (one float), each nullptr when not wanted
+int finc_plu_compose_launch(const float *lower, const float *upper, const float *log_s, const float *sign_s, const int *perm, float *w,
+                            float *w_inv, float *logdet, int C, hipStream_t st);
+// from gw = dl/dW [C][C] and g_ld = dl/dlogdet (one float or nullptr): any of g_lower, g_upper [C][C], g_log_s [C]
+int finc_plu_compose_bwd_launch(const float *gw, const float *g_ld, const float *lower, const float *upper, const float *log_s,
+                                const float *sign_s, const int *perm, float *g_lower, float *g_upper, float *g_log_s, int C, hipStream_t st);

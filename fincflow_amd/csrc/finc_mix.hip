@@ -260,5 +260,6 @@ int finc_mix_launch(const float *in, const float *mat, const float *bias, float 
 #include "finc_image.h"
 #include "finc_actnorm.h"
 #include "finc_adjoint.h"
+#include "finc_plu.h"
 
 unsigned finc_build_flags_mix() { return FINC_BUILD_FLAGS; }

@@ -366,6 +366,242 @@ class Conv1x1(_DerivedValues, FlowLayer):
         raise NotImplementedError
 
 
+def _plu_factor(W):
+    """W = P L U on the CPU in float64: (lower, upper, log_s, sign_s, perm) with W[r] = (L (U + diag(sign_s * exp(log_s))))[perm[r]]
+    (torch.linalg.lu's P: perm = P.argmax(1)); the triangles strict, zero elsewhere."""
+    A = torch.as_tensor(W).detach().to("cpu", torch.float64)
+    if A.dim() != 2 or A.shape[0] != A.shape[1] or A.shape[0] < 1:
+        raise ValueError("expected a square matrix")
+    P, L, U = torch.linalg.lu(A)
+    d = U.diagonal()
+    if not bool(torch.isfinite(d).all() and (d != 0).all()):
+        raise ValueError("the matrix is singular: it has no PLU parametrisation with a finite log_s")
+    return L.tril(-1), U.triu(1), d.abs().log(), d.sign(), P.argmax(1).to(torch.int32)
+
+
+def _check_permutation(perm, n):
+    """On the host, once, where `perm` is set: the kernels cannot report a bad entry without a synchronisation per call."""
+    p = torch.as_tensor(perm).detach().cpu().reshape(-1)
+    if p.dtype.is_floating_point or p.numel() != n or not torch.equal(p.long().sort()[0], torch.arange(n)):
+        raise ValueError("perm must be a permutation of 0 .. %d" % (n - 1))
+
+
+class Conv1x1LU(Conv1x1):
+    """The 1x1 convolution in Glow's PLU parametrisation (Kingma & Dhariwal 2018, 3.2): W = P L (U + diag(s)) with a fixed permutation
+    and a fixed sign of s, so that log|det W| = sum(log_s) and W^-1 is two triangular solves -- no factorisation and no host
+    synchronisation on any path.  Parameters `lower`, `upper` [C, C] (strict triangles), `log_s` [C]; buffers `sign_s` [C], `perm` [C]
+    int32 (W[r] = (L Ut)[perm[r]]).  Constructed from the orthogonal matrix `Conv1x1` draws (the same np.random calls: one seed gives
+    both layers the same matrix), factorised on the CPU in float64.
+
+    On the device in fp32 up to `ops.plu_supported` (512 channels), W, W^-1 and the log-det come from ONE HIP launch
+    (`ops.finc_plu_compose`): recorded per call while autograd records through the parameters (`ops.plu_compose`, its backward one
+    launch), otherwise cached per parameter version with an `ops.Ready` token.  Everything `Conv1x1` does with its matrix -- the mix
+    kernel, the folds of FlowSequential, `backward_from_output` -- this layer does with the composed one.  CPU tensors, float64 and
+    wider matrices run the written-out composition in PyTorch (`dense`, `_compose_torch`).  `W` is that composition, read-only."""
+
+    _derived = Conv1x1._derived + ("_plu", "_plu_key", "_plu_ready")
+
+    def __init__(self, n_channels):
+        FlowLayer.__init__(self)
+        self.n_channels = n_channels
+        q = np.linalg.qr(np.random.randn(n_channels, n_channels))[0]
+        self._set_factors(_plu_factor(torch.from_numpy(q)), torch.float32)
+
+    def _set_factors(self, factors, dtype, device=None):
+        lower, upper, log_s, sign_s, perm = factors
+        _check_permutation(perm, self.n_channels)
+        self.lower = nn.Parameter(lower.to(device=device, dtype=dtype))
+        self.upper = nn.Parameter(upper.to(device=device, dtype=dtype))
+        self.log_s = nn.Parameter(log_s.to(device=device, dtype=dtype))
+        self.register_buffer("sign_s", sign_s.to(device=device, dtype=dtype))
+        self.register_buffer("perm", perm.to(device=device))
+
+    @classmethod
+    def from_dense(cls, W):
+        """The layer whose matrix is `W` [C, C] (a tensor or an array): factorised on the CPU in float64, stored in float32 (float64
+        for a float64 `W`) on W's device."""
+        W = torch.as_tensor(W)
+        layer = cls.__new__(cls)
+        FlowLayer.__init__(layer)
+        layer.n_channels = W.shape[0]
+        layer._set_factors(_plu_factor(W), torch.float64 if W.dtype == torch.float64 else torch.float32, W.device)
+        return layer
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        if prefix + "perm" in state_dict:
+            _check_permutation(state_dict[prefix + "perm"], self.n_channels)
+        return super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+    # ---- the written-out composition: the PyTorch lines (differentiable as they are) ----
+    def _triangles(self):
+        eye = torch.eye(self.n_channels, dtype=self.lower.dtype, device=self.lower.device)
+        return torch.tril(self.lower, -1) + eye, torch.triu(self.upper, 1) + torch.diag(self.sign_s * torch.exp(self.log_s)), eye
+
+    def _compose_torch(self, need_w=True, need_winv=True, need_logdet=True):
+        w = w_inv = logdet = None
+        with _fp32_maps(self.lower):
+            L, Ut, eye = self._triangles()
+            rows = self.perm.long()
+            if need_w:
+                w = (L @ Ut).index_select(0, rows)
+            if need_winv:                        # column r: Ut^-1 L^-1 e_perm[r]
+                y = torch.linalg.solve_triangular(L, eye.index_select(1, rows), upper=False, unitriangular=True)
+                w_inv = torch.linalg.solve_triangular(Ut, y, upper=True)
+            if need_logdet:
+                logdet = self.log_s.sum()
+        return w, w_inv, logdet
+
+    def dense(self):
+        """The composed matrix [C, C] by the PyTorch lines, recorded when autograd records."""
+        return self._compose_torch(True, False, False)[0]
+
+    @property
+    def W(self):
+        return self.dense()
+
+    # ---- where W, W^-1 and log|det W| come from ----
+    def _factors(self):
+        return self.lower, self.upper, self.log_s
+
+    def _plu_kernel(self):
+        p = self.lower
+        return (p.is_cuda and all(q.dtype == torch.float32 and q.device == p.device for q in (p, self.upper, self.log_s, self.sign_s))
+                and self.perm.device == p.device and ops.plu_supported(self.n_channels))
+
+    def _records(self):
+        return torch.is_grad_enabled() and any(p.requires_grad for p in self._factors())
+
+    def _recorded(self, need_w, need_winv, need_logdet):
+        """One recorded composition: `ops.plu_compose` (one launch, its backward another) or the PyTorch lines."""
+        if self._plu_kernel():
+            return ops.plu_compose(self.lower, self.upper, self.log_s, self.sign_s, self.perm, need_w, need_winv, need_logdet)
+        return self._compose_torch(need_w, need_winv, need_logdet)
+
+    def _values(self):
+        """(W, W^-1, log|det W|) without a graph, per parameter version as `Conv1x1._inverse_matrix` keeps its inverse: one compose
+        launch fills all three."""
+        p = self.lower
+        key = ops.version_key(p, self.upper, self.log_s, self.sign_s, self.perm) + (p.device, p.dtype)
+        if getattr(self, "_plu_key", None) != key:
+            with torch.no_grad():
+                if self._plu_kernel():
+                    self._plu = ops.finc_plu_compose(p.detach().contiguous(), self.upper.detach().contiguous(),
+                                                     self.log_s.detach().contiguous(), self.sign_s, self.perm)
+                else:
+                    self._plu = tuple(t.contiguous() for t in self._compose_torch())
+            self._plu_key, self._plu_ready = key, ops.Ready(p.device)
+            self._aff_key = None
+        else:
+            self._plu_ready.wait(*self._plu)
+        return self._plu
+
+    def _inverse_matrix(self):
+        return self._values()[1]
+
+    def _log_abs_det(self):
+        if self._records():
+            return self._recorded(False, False, True)[2]
+        return self._values()[2]
+
+    def _hip(self, x):
+        return not _records_graph(x, *self._factors()) and self._hip_device(x)
+
+    def _hip_reverse_grad(self, z):
+        return ops.reverse_grad_enabled() and _records_graph(z, *self._factors()) and self._hip_device(z)
+
+    # ---- the layer ----
+    def forward(self, x, context=None):
+        h, w = x.shape[2:]
+        if not self._plu_kernel():               # the PyTorch lines
+            mat, ld = (self.W if self._records() else self._values()[0]), self._log_abs_det()
+        elif self._records():
+            mat, _, ld = self._recorded(True, False, True)
+        else:
+            mat, _, ld = self._values()
+        ldj = h * w * ld
+        if self._hip(x):
+            return ops.finc_mix(x.contiguous(), mat), ldj
+        if torch.is_grad_enabled() and self._hip_device(x):
+            return ops.mix_forward(x, mat), ldj
+        with _fp32_maps(x):
+            return F.conv2d(x, mat.view(self.n_channels, self.n_channels, 1, 1)), ldj
+
+    def _reverse_on(self, z, w_inv):
+        if self._hip(z):
+            return ops.finc_mix(z.contiguous(), w_inv)
+        if self._hip_reverse_grad(z):
+            return ops.mix_forward(z, w_inv)
+        with _fp32_maps(z):
+            return F.conv2d(z, w_inv.view(self.n_channels, self.n_channels, 1, 1))
+
+    def reverse(self, z, context=None):
+        return self._reverse_on(z, self._recorded(False, True, False)[1] if self._records() else self._inverse_matrix())
+
+    def reverse_with_logdet(self, z, context=None):
+        if not (self._records() and self._plu_kernel()):
+            return super().reverse_with_logdet(z, context)
+        _, w_inv, ld = self._recorded(False, True, True)        # one recorded composition for both
+        out = self._reverse_on(z, w_inv)
+        return out, (out.shape[2] * out.shape[3] * ld).expand(len(out))
+
+    def invertible_backward_supported(self, x, context=None):
+        return (self._hip_device(x) and x.shape[1] == self.n_channels and _params_on_device(x, *self._factors())
+                and self._plu_kernel())
+
+    def backward_from_output(self, output, grad_output, grad_logdet, context, needs):
+        """x = finc_mix(output, W^-1) and finc_mix_backward at (grad_output, x) on the cached matrices, then ONE compose-backward
+        launch from grad_mat to the parameters; the log-det's share, H * W * sum_b grad_logdet[b], is added to every grad_log_s
+        there (no W^-T)."""
+        params, asked = _param_needs(self, needs)
+        want = {id(p): a for p, a in zip(params, asked)}
+        need_gw = any(asked)
+        mat, w_inv, _ = self._values()
+        x = ops.finc_mix(output.contiguous(), w_inv) if (needs.input or need_gw) else None
+        gx, gw, _ = ops.finc_mix_backward(grad_output.contiguous(), x, mat, need_gx=needs.grad_input, need_gm=need_gw)
+        grads = {}
+        if need_gw:
+            h, w = output.shape[2:]
+            gld = None if grad_logdet is None else ((h * w) * grad_logdet.sum()).float().contiguous()
+            grads = dict(zip(map(id, self._factors()), ops.finc_plu_compose_backward(
+                gw, gld, self.lower.detach().contiguous(), self.upper.detach().contiguous(), self.log_s.detach().contiguous(),
+                self.sign_s, self.perm, *(want.get(id(p), False) for p in self._factors()))))
+        return x, gx, None, [grads.get(id(p)) for p in params]
+
+
+def convert_conv1x1(model, to="lu"):
+    """Swap every 1x1 convolution of a `FlowSequential` for its other parametrisation with the same matrix, in `sequence_modules`
+    and in the registered children: `to="lu"` a `Conv1x1` becomes a `Conv1x1LU` (factorised on the CPU in float64), `to="dense"` the
+    reverse (composed in float64).  The new layers keep the old ones' dtype and device; optimisers hold the old parameters and have to
+    be rebuilt.  Returns `model`."""
+    if to not in ("lu", "dense"):
+        raise ValueError('to must be "lu" or "dense"')
+    mods = list(model.sequence_modules)
+    for i, m in enumerate(mods):
+        if to == "lu" and type(m) is Conv1x1:
+            new = Conv1x1LU.from_dense(m.W.detach())
+        elif to == "dense" and isinstance(m, Conv1x1LU):
+            new = Conv1x1.__new__(Conv1x1)
+            FlowLayer.__init__(new)
+            new.n_channels = m.n_channels
+            with torch.no_grad():
+                p = m.lower
+                twin = Conv1x1LU.__new__(Conv1x1LU)
+                FlowLayer.__init__(twin)
+                twin.n_channels = m.n_channels
+                twin._set_factors(tuple(t.detach().cpu().double() if t.is_floating_point() else t.detach().cpu()
+                                        for t in (m.lower, m.upper, m.log_s, m.sign_s, m.perm)), torch.float64)
+                new.W = nn.Parameter(twin.dense().to(device=p.device, dtype=p.dtype))
+        else:
+            continue
+        new.train(m.training)
+        mods[i] = new
+        for name, child in list(model.named_children()):
+            if child is m:
+                setattr(model, name, new)
+    model.sequence_modules = tuple(mods)
+    return model
+
+
 class Conv2dZero(nn.Module):
     """Zero-initialised 3x3 conv with a learned per-channel log-scale (layers/coupling.py:10-43)."""
 
@@ -904,11 +1140,12 @@ class Dequantization(FlowLayer):
 
 
 def create_model(num_blocks=3, block_size=32, actnorm=False, split_prior=False, image_size=(3, 32, 32),
-                 preprocess=True, coupling_width=512, gaussianize_split=False, hip_recorded_merge=False):
+                 preprocess=True, coupling_width=512, gaussianize_split=False, hip_recorded_merge=False, lu_conv1x1=False):
     """fastflow/fastflow_cifar.py:35-63: Squeeze -> [FastFlowUnit, (ActNorm), Conv1x1, Coupling] x block_size
     (-> SplitPrior) per block, under a standard-normal base.  `gaussianize_split` (with `split_prior`): the level boundary is the
     Gaussianized `Split` instead of a `SplitPrior`, the switch of fastflow_cifar_multi_gpu.py:264-265.  `hip_recorded_merge`: the
-    boundaries record their `merge` inside `ops.reverse_grad()` on the HIP kernels (`SplitPrior.hip_recorded_merge`)."""
+    boundaries record their `merge` inside `ops.reverse_grad()` on the HIP kernels (`SplitPrior.hip_recorded_merge`).  `lu_conv1x1`:
+    every 1x1 convolution in Glow's PLU parametrisation (`Conv1x1LU`: the same matrices from the same seed, no factorisation per call)."""
     size = tuple(image_size)
     layers = []
     if preprocess:
@@ -922,7 +1159,7 @@ def create_model(num_blocks=3, block_size=32, actnorm=False, split_prior=False, 
             layers.append(FastFlowUnit(size[0], size[0], (3, 3)))
             if actnorm:
                 layers.append(ActNorm(size[0]))
-            layers.append(Conv1x1(size[0]))
+            layers.append(Conv1x1LU(size[0]) if lu_conv1x1 else Conv1x1(size[0]))
             layers.append(Coupling(size, width=coupling_width))
         if split_prior and level < num_blocks - 1:
             layers.append(Split(size, GaussianPrior) if gaussianize_split else SplitPrior(size, GaussianPrior, width=coupling_width))

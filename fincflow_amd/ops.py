@@ -418,6 +418,101 @@ def mix_forward(x, mat, bias=None):
     return _FincMixFunction.apply(x, mat, bias)
 
 
+def plu_supported(C):
+    """Does the library compose a [C, C] matrix from its PLU parameters (1 <= C <= 512)?"""
+    return bool(_lib.lib().finc_plu_supported_f32(int(C)))
+
+
+def _plu_args(lower, upper, log_s, sign_s, perm):
+    for t, name in ((lower, "lower"), (upper, "upper"), (log_s, "log_s"), (sign_s, "sign_s")):
+        _require_device(t, name)
+    _require_device(perm, "perm", torch.int32)
+    C = log_s.numel()
+    if C < 1 or lower.shape != (C, C) or upper.shape != (C, C) or sign_s.shape != (C,) or perm.shape != (C,) or log_s.dim() != 1:
+        raise ValueError("expected lower, upper [C,C] and log_s, sign_s, perm [C]")
+    if any(t.device != lower.device for t in (upper, log_s, sign_s, perm)):
+        raise ValueError("the PLU parameters must be on one device")
+    return C
+
+
+def finc_plu_compose(lower, upper, log_s, sign_s, perm, need_w=True, need_winv=True, need_logdet=True):
+    """The matrix of a PLU-parametrised 1x1 convolution (glow.Conv1x1LU), its inverse and its log-det in ONE HIP launch:
+    W = P L Ut with L = strict_lower(lower) + I, Ut = strict_upper(upper) + diag(sign_s * exp(log_s)), W[r] = (L Ut)[perm[r]];
+    W^-1 by two triangular solves per column; log|det W| = sum(log_s), 0-dim.  lower, upper [C,C], log_s, sign_s [C] fp32, perm [C]
+    int32 contiguous on the device.  Returns (w, w_inv, logdet), each computed only if asked for (None otherwise).  Computed in
+    fp64, rounded to fp32 once, in a fixed order: the same inputs give the same bits.  Nothing is recorded for autograd
+    (`plu_compose` does that)."""
+    C = _plu_args(lower, upper, log_s, sign_s, perm)
+    if not (need_w or need_winv or need_logdet):
+        return None, None, None
+    w = torch.empty_like(lower) if need_w else None
+    w_inv = torch.empty_like(lower) if need_winv else None
+    logdet = torch.empty((), dtype=torch.float32, device=lower.device) if need_logdet else None
+    _call("finc_plu_compose_f32", lower.device, lower.data_ptr(), upper.data_ptr(), log_s.data_ptr(), sign_s.data_ptr(), perm.data_ptr(),
+          _ptr(w), _ptr(w_inv), _ptr(logdet), C, _stream_ptr(lower))
+    return w, w_inv, logdet
+
+
+def finc_plu_compose_backward(grad_w, grad_logdet, lower, upper, log_s, sign_s, perm, need_glower=True, need_gupper=True,
+                              need_glog_s=True):
+    """Gradients of `finc_plu_compose` (include/finc.h: finc_plu_compose_backward_f32) from grad_w [C,C] = dl/dW and grad_logdet
+    (0-dim or None: zero): (grad_lower, grad_upper, grad_log_s), each computed only if asked for (None otherwise), ONE launch.  The
+    entries outside the strict triangles are exact zeros, written by the kernel.  (A gradient through W^-1 is folded into grad_w
+    first: `plu_compose` does that.)"""
+    C = _plu_args(lower, upper, log_s, sign_s, perm)
+    _require_device(grad_w, "grad_w")
+    if grad_w.shape != (C, C) or grad_w.device != lower.device:
+        raise ValueError("grad_w must be [C,C] on the parameters' device")
+    if grad_logdet is not None:
+        _require_device(grad_logdet, "grad_logdet")
+        if grad_logdet.numel() != 1 or grad_logdet.device != lower.device:
+            raise ValueError("grad_logdet must hold one value on the parameters' device")
+    gl = torch.empty_like(lower) if need_glower else None
+    gu = torch.empty_like(upper) if need_gupper else None
+    gs = torch.empty_like(log_s) if need_glog_s else None
+    if gl is None and gu is None and gs is None:
+        return gl, gu, gs
+    _call("finc_plu_compose_backward_f32", lower.device, grad_w.data_ptr(), _ptr(grad_logdet), lower.data_ptr(), upper.data_ptr(),
+          log_s.data_ptr(), sign_s.data_ptr(), perm.data_ptr(), _ptr(gl), _ptr(gu), _ptr(gs), C, _stream_ptr(lower))
+    return gl, gu, gs
+
+
+class _FincPluComposeFunction(torch.autograd.Function):
+    """`finc_plu_compose` under autograd: (w, w_inv, logdet) recorded as one node, its backward one launch.  A gradient that arrives
+    through w_inv is folded into the one on w first, dl/dW = grad_w - W^-T grad_winv W^-T (two [C, C] matmuls, in fp64)."""
+
+    @staticmethod
+    def forward(ctx, lower, upper, log_s, sign_s, perm, need_w, need_winv, need_logdet):
+        lower, upper, log_s = lower.contiguous(), upper.contiguous(), log_s.contiguous()
+        w, w_inv, logdet = finc_plu_compose(lower, upper, log_s, sign_s, perm, need_w, need_winv, need_logdet)
+        ctx.save_for_backward(lower, upper, log_s, sign_s, perm, w_inv)
+        ctx.set_materialize_grads(False)
+        return w, w_inv, logdet
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_w, grad_winv, grad_logdet):
+        lower, upper, log_s, sign_s, perm, w_inv = ctx.saved_tensors
+        need = ctx.needs_input_grad[:3]
+        if grad_winv is not None:
+            wt = w_inv.t().double()              # (in fp64 like the kernels: at cond(W) in the thousands an fp32 product is the error)
+            through = wt @ grad_winv.double() @ wt
+            grad_w = (-through if grad_w is None else grad_w.double() - through).float()
+        if grad_logdet is not None:
+            grad_logdet = grad_logdet.contiguous()
+        if grad_w is None:                       # the log-det alone: every grad_log_s is grad_logdet, nothing reaches the triangles
+            gs = grad_logdet.expand(log_s.shape).clone() if (need[2] and grad_logdet is not None) else None
+            return (None, None, gs) + (None,) * 5
+        gl, gu, gs = finc_plu_compose_backward(grad_w.contiguous(), grad_logdet, lower, upper, log_s, sign_s, perm, *need)
+        return (gl, gu, gs) + (None,) * 5
+
+
+def plu_compose(lower, upper, log_s, sign_s, perm, need_w=True, need_winv=True, need_logdet=True):
+    """`finc_plu_compose` under autograd: gradients for lower, upper and log_s, each computed only where needed, in one launch;
+    an output nobody asked for is None and costs nothing."""
+    return _FincPluComposeFunction.apply(lower, upper, log_s, sign_s, perm, bool(need_w), bool(need_winv), bool(need_logdet))
+
+
 def coupling_supported(C):
     return bool(_lib.lib().finc_coupling_supported_f32(int(C)))
 

@@ -543,6 +543,34 @@ int finc_gauss_split_merge_backward_f32(const float *grad_x, const float *grad_l
                                         int B, int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream);
 
 /*
+ * The PLU-parametrised 1x1 convolution's parameter work (version 118; Kingma & Dhariwal 2018, section 3.2): what glow.Conv1x1LU
+ * launches.  The layer keeps  W = P L Ut  with  L = strict_lower(lower) + I,  Ut = strict_upper(upper) + diag(sign_s * exp(log_s)),
+ * M = L Ut  and  W[r][:] = M[perm[r]][:]:  lower, upper [C][C] row-major fp32 (only the strict triangles are read), log_s, sign_s [C]
+ * fp32, perm [C] int32, a permutation of 0 .. C-1.  The per-pixel product with W or W^-1 is finc_mix_f32's.
+ * finc_plu_supported_f32: 1 for 1 <= C <= 512, the widths the two entry points take (C is a runtime argument; the bound is the LDS of
+ *   the rows a workgroup stages, 88 bytes per channel), else 0.
+ * finc_plu_compose_f32: ONE launch that writes any of  w [C][C] = W,  w_inv [C][C] = W^-1 (column r = Ut^-1 L^-1 e_perm[r]: two
+ *   triangular solves, no pivoting)  and  logdet (one float) = sum(log_s) = log|det W|;  at least one non-NULL.  All arithmetic in fp64,
+ *   every output rounded to fp32 once, every sum in a fixed order, no atomics: the same inputs give the same bits.
+ * finc_plu_compose_backward_f32: from grad_w [C][C] = dl/dW and grad_logdet (one float, NULL = 0), with G_M[perm[r]][:] = grad_w[r][:]:
+ *     grad_lower = strict_lower(G_M Ut^T),   grad_upper = strict_upper(L^T G_M),
+ *     grad_log_s[i] = (L^T G_M)[i][i] * sign_s[i] * exp(log_s[i]) + grad_logdet,
+ *   each wanted or not by pointer (not all three NULL): one fp64 dot product in a fixed order per entry, ONE launch.  The entries of
+ *   grad_lower on and above the diagonal and of grad_upper on and below it are written as +0 by the kernel.  (A gradient that arrives
+ *   through W^-1 is folded into grad_w by the caller: grad_w - W^-T grad_winv W^-T.)
+ * `perm` lives in device memory, so neither the host nor the kernels trust it: an entry outside [0, C) is never used as an index.  It
+ *   makes row r of w and column r of w_inv NaN; in the backward the row of G_M that no entry names reads as NaN.  Nothing else is touched.
+ * No output may share a byte with an input or with another output (FINC_ERR_BAD_DIMS).  No workspace.  Refusal order: NULL -> dims
+ * (C < 1, overlap) -> alignment (4 bytes, perm included) -> a width without a kernel (FINC_ERR_UNSUPPORTED) -> the fault gate.
+ */
+int finc_plu_supported_f32(int C);
+int finc_plu_compose_f32(const float *lower, const float *upper, const float *log_s, const float *sign_s, const int *perm, float *w,
+                         float *w_inv, float *logdet, int C, finc_stream_t stream);
+int finc_plu_compose_backward_f32(const float *grad_w, const float *grad_logdet, const float *lower, const float *upper,
+                                  const float *log_s, const float *sign_s, const int *perm, float *grad_lower, float *grad_upper,
+                                  float *grad_log_s, int C, finc_stream_t stream);
+
+/*
  * ActNorm (layers/actnorm.py:5-66) on its own kernels: activations [B][C][HW] fp32, log_scale and translation [C], any C >= 1
  * (up to FINC_MAX_CQ * FINC_MAX_GROUPS), HW >= 1.
  * finc_actnorm_f32: direction +1: y = (x - translation[c]) * exp(-log_scale[c]) (layers/actnorm.py:34); direction -1:
