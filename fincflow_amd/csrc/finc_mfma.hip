@@ -313,8 +313,12 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
         __builtin_amdgcn_make_buffer_rsrc((void *)(out + (size_t)bg_out * CQ * HW), 0, (int)slab_bytes, 0x00020000);
     const int D = W - P + 1;                  // FIFO depth (steps between a band's last rows and the next band's first)
     const int fifo_n = D * SS;
+    constexpr bool PAIR2 = finc_pair2_form<C>(HLP);   // stage 2 of the paired tile, and the row shifts read from LDS, run in this form
+    static_assert(!PAIR2 || (KH - 1 + KW) < 6, "row shifts from LDS: written for operands that rotate in place");
     // LDS: [exchange buffer (K-split only)] then per wave: z ring | x ring | FIFO + trash
-    const int wave_lds = C::ZRING + C::XRING + fifo_n + SS + 64;
+    // PAIR2: z ring | per k-step: x ring block, FIFO block (finc_tile.h: finc_ls_jstride)
+    constexpr int XJ = PAIR2 ? finc_ls_jstride(KH) : C::XSLOTS * 64;          // x ring: floats per k-step
+    const int wave_lds = PAIR2 ? C::ZRING + NKD * XJ : C::ZRING + C::XRING + fifo_n + SS + 64;
     float *const lds_p = lds + prob * (C::XCH + NW * wave_lds);
     float *xch = lds_p;
     float *zring = lds_p + C::XCH + wv * wave_lds;
@@ -331,7 +335,7 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
         const int lo = ((rr >> 2) ^ ((0x3200 >> (4 * (rr & 3))) & 3)) | ((qq & 1) << 2);
         return lo | (((rr & 3) | ((qq >> 1) << 2)) << 3);
     };
-    float *fifo = xring + C::XRING;
+    float *fifo = xring + C::XRING;           // (PAIR2: a FIFO block behind every k-step's x-ring block instead, finc_ls_fifo)
     const int trash = fifo_n + lane;          // per-lane scratch word(s): lanes that neither push nor pop point here
     // HLP: the three progress words of this problem, behind the four problems' rings
     const unsigned flag_a = (unsigned)(uintptr_t)(lds + 4 * wave_lds + 4 * prob);   // +0: A, +4: B, +8: B2, +12: A1 (bytes)
@@ -380,7 +384,6 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
     constexpr int NSMALL = (NFRAG / MT) * C::NSM, NSR = (NSMALL + 3) / 4;
     float af[NFRAG];
     float afs[NSR > 0 ? NSR : 1];
-    constexpr bool PAIR2 = finc_pair2_form<C>(HLP);   // stage 2 of the paired tile runs in this form
     constexpr int NPAIRF = PAIR2 ? C::NPAIR : C::NPAIR1;
     float afp[C::PAIR ? NPAIRF : 1];          // paired fragments: [0, NK) = (0,1)|(0,2), [NK, 2NK) = (1,0)|(1,1), [2NK, 3NK) = (2,0)|(2,1)
     // block fragment s belongs to a tap whose blocks ride on a paired tile: taps 1..4 = (0,1) (0,2) (1,0) (1,1); stage 2: 6, 7 = (2,0) (2,1)
@@ -460,7 +463,13 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
         for (int mt = 0; mt < MT; ++mt)
             bias[mt] = (v4f){pb[(4 * mt + 0) * 64], pb[(4 * mt + 1) * 64], pb[(4 * mt + 2) * 64], pb[(4 * mt + 3) * 64]};
     }
-    for (int i = lane; i < fifo_n + SS + 64; i += 64) fifo[i] = 0.f;
+    if constexpr (PAIR2) {                    // every k-step's FIFO block
+        for (int i = FINC_LS_XBLOCK + lane; i < XJ; i += 64)
+#pragma unroll
+            for (int j = 0; j < NKD; ++j) xring[j * XJ + i] = 0.f;
+    } else {
+        for (int i = lane; i < fifo_n + SS + 64; i += 64) fifo[i] = 0.f;
+    }
 
     // ---- per-lane HBM stream state -------------------------------------------------------------
     const int fl4 = -((p + 3) >> 2);          // floor(-p/4): first 4-column group this lane ever needs
@@ -681,7 +690,7 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
         if (cls != WP && p < P) {              // (divergent) own row: first group of its next pair; partner: second group, due now
 #pragma unroll
             for (int j = 0; j < NKD; ++j) {
-                const float *xo = xring + j * C::XSLOTS * 64, *xp = xring + j * C::XSLOTS * 64;
+                const float *xo = xring + j * XJ, *xp = xring + j * XJ;
                 XS[WP ^ 1][j][0] = xo[xown[0]];
                 XS[WP ^ 1][j][1] = xo[xown[1]];
                 XS[WP ^ 1][j][2] = xo[xown[2]];
@@ -915,10 +924,31 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
     float *pop_p[KH];                         // = fifo + pop_base + ((fslot+1) % D) * pop_stride
 #pragma unroll
     for (int a = 1; a < KH; ++a) pop_p[a] = fifo + pop_base[a] + (D > 1 ? pop_stride[a] : 0);
+    // PAIR2: S_a(t) is READ from LDS (finc_tile.h: finc_ls_src, finc_ls_push and the per-lane constants that move the pointers) --
+    // one pointer per a and one for the push.  Ring-side lanes follow the x ring's time slots, FIFO-side lanes the FIFO slot, a
+    // ring of D - 1 slots that a step reads and then overwrites.  The state before step -4: time slot 4, FIFO slot 0.
+    const int ls_slots = D > 1 ? D - 1 : 0x7fffffff;   // (D = 1: no FIFO, the slot counter never wraps)
+    float *rd_p[KH];
+    int rd_step[KH], rd_rew8[KH], rd_rewR[KH], push_rew8 = 0, push_rewR = 0, push_step = 0;
+    if constexpr (PAIR2) {
+        const bool pushes = finc_ls_pushes(KH, P, D, lane);
+        push_p = xring + finc_ls_push(KH, P, D, lane, 4, 0);
+        push_step = finc_ls_step(KH, pushes);
+        push_rew8 = finc_ls_rewind8(pushes);
+        push_rewR = finc_ls_rewindR(KH, D, pushes);
+#pragma unroll
+        for (int a = 1; a < KH; ++a) {
+            const bool pops = finc_ls_pops(a, D, lane);
+            rd_p[a] = xring + finc_ls_src(KH, a, D, lane, 4, 0);
+            rd_step[a] = finc_ls_step(KH, pops);
+            rd_rew8[a] = finc_ls_rewind8(pops);
+            rd_rewR[a] = finc_ls_rewindR(KH, D, pops);
+        }
+    }
     // (exec-masked pushes / pops instead of the trash words: 1.2 % slower, profiles/r02/notes/ab30)
     auto fifo_push = [&](const float (&v)[NK]) {
 #pragma unroll
-        for (int j = 0; j < NK; ++j) push_p[j * JS] = v[j];
+        for (int j = 0; j < NK; ++j) push_p[j * (PAIR2 ? XJ : JS)] = v[j];
     };
     auto fifo_pop_all = [&]() {
 #pragma unroll
@@ -927,20 +957,50 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
             for (int j = 0; j < NK; ++j) fv[a][j] = pop_p[a][j * JS];
         }
     };
+    // PAIR2, behind the x-ring write of the step and BEFORE its push (the FIFO slot read here is the one the push overwrites)
+    auto shift_lds = [&](auto ph_c) {
+        constexpr int PHX = decltype(ph_c)::value;
+        if constexpr (PAIR2) {
+#pragma unroll
+            for (int a = 1; a < KH; ++a)
+#pragma unroll
+                for (int j = 0; j < NK; ++j) Q[a][PHX][j] = rd_p[a][j * XJ];
+        }
+    };
+    auto ls_rewind8 = [&]() {                 // PAIR2, behind the advance of the step of time slot 7
+        if constexpr (PAIR2) {
+            push_p -= push_rew8;
+#pragma unroll
+            for (int a = 1; a < KH; ++a) rd_p[a] -= rd_rew8[a];
+        }
+    };
     auto fifo_advance = [&]() {               // one v_add per pointer; the rewinds are real scalar branches (1 in D steps)
         ++fslot;
-        push_p += push_stride;
+        if constexpr (PAIR2) {                // one slot counter for the reads and the push
+            push_p += push_step;
 #pragma unroll
-        for (int a = 1; a < KH; ++a) pop_p[a] += pop_stride[a];
-        if (__builtin_expect(fslot == D, 0)) {
-            FINC_COLD();
-            fslot = 0;
-            push_p = fifo + push_base;
-        }
-        if (__builtin_expect(fslot + 1 == D, 0)) {
-            FINC_COLD();
+            for (int a = 1; a < KH; ++a) rd_p[a] += rd_step[a];
+            if (__builtin_expect(fslot == ls_slots, 0)) {
+                FINC_COLD();
+                fslot = 0;
+                push_p -= push_rewR;
 #pragma unroll
-            for (int a = 1; a < KH; ++a) pop_p[a] = fifo + pop_base[a];
+                for (int a = 1; a < KH; ++a) rd_p[a] -= rd_rewR[a];
+            }
+        } else {
+            push_p += push_stride;
+#pragma unroll
+            for (int a = 1; a < KH; ++a) pop_p[a] += pop_stride[a];
+            if (__builtin_expect(fslot == D, 0)) {
+                FINC_COLD();
+                fslot = 0;
+                push_p = fifo + push_base;
+            }
+            if (__builtin_expect(fslot + 1 == D, 0)) {
+                FINC_COLD();
+#pragma unroll
+                for (int a = 1; a < KH; ++a) pop_p[a] = fifo + pop_base[a];
+            }
         }
     };
     // S_a(t) for a >= 1: row_shr:a(src), lanes p < a take the FIFO value.
@@ -1119,6 +1179,10 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
             float zraw[NKZ], zv[NKZ], xpk[NKD];
             float xown[NKD];                          // K-split: this wave's own share of the registers it finalises
             v4f accn[MT];
+            // PAIR2: phase A reads S_1 of the previous step, which that step's post2 fetched from LDS three chunks of MFMAs ago.  Left
+            // to itself hipcc waits for it BEHIND this step's z read (lgkmcnt(0): a whole LDS round trip in front of the first MFMAs);
+            // a wait it can see, in front of the z read and of the flag peek, costs nothing -- the data has long arrived.
+            if constexpr (PAIR2 && FINC_ABLATE < 2) __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0), vmcnt and expcnt open
             if constexpr (HLP && PH == 0) {            // the landing of the previous window must be in the ring (peeked in step 3)
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 if (__builtin_expect(__builtin_amdgcn_readfirstlane(peek_b) < win, 0)) { FINC_COLD(); FINC_HLP_LATE(0); flag_wait(IC<1>{}, win); }
@@ -1326,10 +1390,12 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
                     }
                 }
 #pragma unroll
-                for (int j = 0; j < NKD; ++j) xring[j * C::XSLOTS * 64 + PH * 64 + xwin] = xpk[j]; // slot = t & 7
+                for (int j = 0; j < NKD; ++j) xring[j * XJ + PH * 64 + xwin] = xpk[j]; // slot = t & 7
                 if constexpr (KH > 1) {
-                    fifo_push(xpk);
-                    fifo_pop_all();
+                    if constexpr (!PAIR2) {            // (PAIR2: the row shifts' reads take the FIFO slot first, then the push: post2)
+                        fifo_push(xpk);
+                        fifo_pop_all();
+                    }
                 }
                 if constexpr (C::PAIR) {               // S_0(t) IS the accumulator set; its wrap zeroing follows the shifts (post2)
 #pragma unroll
@@ -1347,7 +1413,14 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
                 }
             };
             auto post2 = [&]() {
-                if constexpr (FINC_ABLATE < 2) shift_all(xpk, ph_c);
+                if constexpr (FINC_ABLATE < 2) {
+                    if constexpr (PAIR2) {
+                        shift_lds(ph_c);
+                        fifo_push(xpk);
+                    } else {
+                        shift_all(xpk, ph_c);
+                    }
+                }
                 if constexpr (C::PAIR && FINC_ABLATE < 2) {
                     // the x-ring write, the FIFO push and the shifts have read the pixel: now a lane whose next position starts a
                     // row loses it as tap (0,1) -- in place, so the hot path needs no copy of the accumulators
@@ -1414,6 +1487,7 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
             if (nslot == 12) { nslot = 0; zrd -= 12 * 64; }
             if constexpr (PH == 3) { xwin ^= 256; ++win; }
             fifo_advance();
+            if constexpr (PAIR2 && PH == 3 && decltype(wp_c)::value == 1) ls_rewind8();   // (t & 7 == 7)
             FINC_STAMP_AT(8);                           // segment 8: advance
         };
 
@@ -1468,6 +1542,7 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
             if (nslot == 12) { nslot = 0; zrd -= 12 * 64; }
             xwin ^= 256;
             fifo_advance();
+            if constexpr (PAIR2) ls_rewind8();   // (step -1: time slot 7)
         }
         // 32-byte I/O alternates two register sets with the window: two windows per iteration (Tend % 8 == 0)
         for (int t0 = 0; t0 < Tend; t0 += SEC ? 8 : 4) {
@@ -1904,10 +1979,15 @@ static InvPlan inverse_plan(const FincShape &s)
     const size_t lds = lds_bytes(*i, s.W, P);
     const bool s64 = s.W % 16 == 0 && i->fn_s64 && !finc_no_s64();
     // helper waves: 4 problems per 8-wave workgroup; their rings + 3 progress words each must fit one CU's LDS
-    const bool hlp = s64 && i->fn_hlp && problems % 4 == 0 && 4 * lds + 64 <= 160 * 1024 && !finc_no_hlp();
+    // (the paired helper-wave forms read their row shifts from LDS and keep a FIFO block of fixed depth behind every k-step of the
+    // x ring -- finc_tile.h, finc_ls_jstride: 39.9 KB per wave whatever the width, against 40.6 KB of the plain layout at W = 64)
+    const bool ls = finc_pair_bank(i->cqp, i->kh, i->kw) && i->nw == 1;       // finc_pair2_form of the helper-wave forms
+    const size_t lds_hlp = ls ? sizeof(float) * ((size_t)i->wnkz * 12 * 64 + (size_t)i->wnkd * finc_ls_jstride(i->kh)) : lds;
+    const bool hlp = s64 && i->fn_hlp && problems % 4 == 0 && 4 * lds + 64 <= 160 * 1024 && 4 * lds_hlp + 64 <= 160 * 1024 &&
+                     (!ls || s.W - P + 1 <= FINC_LS_DMAX) && !finc_no_hlp();
     p.io = hlp ? 3 : s64 ? 2 : s.W % 8 == 0 ? 1 : 0;
     p.fn = hlp ? i->fn_hlp : s64 ? i->fn_s64 : s.W % 8 == 0 ? i->fn_sec : i->fn;
-    p.lds = hlp ? 4 * lds + 64 : lds;
+    p.lds = hlp ? 4 * lds_hlp + 64 : lds;
     p.grid = hlp ? s.B * s.G / 4 : s.B * s.G / i->npw;
     p.block = hlp ? 512 : 64 * i->nw * i->npw;
 

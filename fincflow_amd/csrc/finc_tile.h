@@ -101,3 +101,44 @@ __host__ __device__ inline size_t finc_pair_offset(int G, int npack, int npair, 
 {
     return ((size_t)G * npack + (size_t)g * npair + f) * 64;
 }
+
+// Row shifts read from LDS (finc_wave_kernel, the helper-wave paired forms: finc_pair2_form; P = 16 there).  S_a(t) of lane (q, p):
+// lanes p >= a take the pixel lane p - a wrote to the x ring in this very step, lanes p < a the pixel lane P - a + p of the band
+// above solved D - 1 steps ago -- ONE LDS read per operand register with a per-lane address instead of a DPP move merged with a
+// FIFO pop.  A k-step's offset is an immediate of the instruction, the same for all 64 lanes, so ring lanes and FIFO lanes must
+// share the k-step stride: the FIFO block of a k-step lies right behind its x-ring block (finc_big.hip lays its rings out the
+// same way), and the stride is a multiple of 64 floats so that two k-steps still go into one ds_*2st64 instruction:
+//   k-step block = [x ring: 8 time slots x 64 lanes][FIFO: FINC_LS_DMAX - 1 slots x JS floats],  JS = 4 k-slots x (KH - 1) rows.
+// The FIFO is a ring of D - 1 slots: a step READS its slot (pushed D - 1 steps ago) and then pushes into the same slot, in program
+// order -- LDS executes a wave's operations in order.  D = 1 (W = 16) has no FIFO: the pixel lane P - a + p solved in this very step
+// is the x-ring cell 16 lanes above the one the shift formula names.  Lanes that push nothing write their own x-ring cell again
+// (the value the x-ring write of the same step put there), so no trash words are needed.  The stride is a constant of the build:
+// the block holds the deepest FIFO the form runs (W = 64: D = 49), which makes a wave's LDS 39.9 KB at 24 channels whatever the
+// width -- less than the 40.6 KB of the plain layout at W = 64, more on narrower maps, where it costs nothing (the z and x rings
+// alone let only one 4-problem workgroup onto a compute unit).  All values are float indices relative to the x ring of k-step 0.
+constexpr int FINC_LS_DMAX = 49, FINC_LS_XBLOCK = 8 * 64;
+__host__ __device__ constexpr int finc_ls_js(int KH) { return 4 * (KH - 1); }
+__host__ __device__ constexpr int finc_ls_jstride(int KH) { return FINC_LS_XBLOCK + finc_ls_js(KH) * (FINC_LS_DMAX - 1); }
+// x-ring cell of `lane` in time slot t & 7
+__host__ __device__ constexpr int finc_ls_xcell(int slot, int lane) { return slot * 64 + lane; }
+// FIFO word of slot `fslot` (0 .. D-2), k-slot q, row l (0 .. KH-2) of the band's last KH - 1 rows
+__host__ __device__ constexpr int finc_ls_fifo(int KH, int fslot, int q, int l) { return FINC_LS_XBLOCK + fslot * finc_ls_js(KH) + q * (KH - 1) + l; }
+// does `lane` push into the FIFO (rows P-(KH-1) .. P-1 of a band) / read S_a from it (rows 0 .. a-1)?
+__host__ __device__ constexpr bool finc_ls_pushes(int KH, int P, int D, int lane) { return D > 1 && (lane & 15) >= P - (KH - 1) && (lane & 15) < P; }
+__host__ __device__ constexpr bool finc_ls_pops(int a, int D, int lane) { return D > 1 && (lane & 15) < a; }
+// where `lane` writes its pixel behind the x-ring write of time slot `slot`, FIFO slot `fslot`
+__host__ __device__ constexpr int finc_ls_push(int KH, int P, int D, int lane, int slot, int fslot)
+{
+    return finc_ls_pushes(KH, P, D, lane) ? finc_ls_fifo(KH, fslot, lane >> 4, (lane & 15) - (P - (KH - 1))) : finc_ls_xcell(slot, lane);
+}
+// where `lane` reads S_a in the step of time slot `slot`, FIFO slot `fslot`
+__host__ __device__ constexpr int finc_ls_src(int KH, int a, int D, int lane, int slot, int fslot)
+{
+    if (finc_ls_pops(a, D, lane)) return finc_ls_fifo(KH, fslot, lane >> 4, KH - 1 - a + (lane & 15));
+    return finc_ls_xcell(slot, (lane & 15) >= a ? lane - a : lane - a + 16);
+}
+// The kernel keeps ONE pointer per a (and one for the push) and moves it by per-lane constants: `step` after every step, back by
+// `rewind8` behind the step of time slot 7 and back by `rewindR` when the FIFO slot wraps (fifo: the lane is on the FIFO side).
+__host__ __device__ constexpr int finc_ls_step(int KH, bool fifo) { return fifo ? finc_ls_js(KH) : 64; }
+__host__ __device__ constexpr int finc_ls_rewind8(bool fifo) { return fifo ? 0 : FINC_LS_XBLOCK; }
+__host__ __device__ constexpr int finc_ls_rewindR(int KH, int D, bool fifo) { return fifo ? (D - 1) * finc_ls_js(KH) : 0; }

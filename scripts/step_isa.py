@@ -46,10 +46,17 @@ def klass(op):
 def mix(path, key):
     body = next(v for k, v in functions(path).items() if key in k)
     labels = {m.group(1): i for i, l in enumerate(body) if (m := re.match(r"^(\.LBB\d+_\d+):", l))}
+    # a cold block laid out behind the loop ends in a branch back into it: that is no loop latch
+    cold_line, start = [False] * len(body), 0
+    for i, l in enumerate(body + [".LBB0_0:"]):
+        if re.match(r"^(\.LBB\d+_\d+):", l) or re.match(r"^; %bb\.", l):
+            if any("cold path" in x for x in body[start:i]):
+                cold_line[start:i] = [True] * (i - start)
+            start = i
     loops = []
     for i, l in enumerate(body):
         m = re.match(r"\s+s_c?branch\S*\s+(?:\S+,\s*)?(\.LBB\d+_\d+)", l)
-        if m and labels.get(m.group(1), i) < i:
+        if m and labels.get(m.group(1), i) < i and not cold_line[i]:
             a = labels[m.group(1)]
             loops.append((sum("v_mfma" in x for x in body[a:i]), a, i))
     most = max(n for n, _, _ in loops)
