@@ -29,6 +29,8 @@ Reference semantics followed:
                  one HIP launch each behind that convolution (ops.finc_gauss_split, ops.finc_gauss_split_merge,
                  ops.gauss_split_forward; with `hip_recorded_merge` ops.gauss_split_merge for a recorded `merge`)
   Normalization, LogitTransform, Dequantization  layers/normalize.py, transforms.py:6-19, dequantize.py
+                 (Dequantization owns the reference's UniformDistribution, layers/distributions/uniform.py, whose buffer `empty`
+                 every reference checkpoint holds as `0.distribution.empty`)
                  with `FlowSequential.fuse_image_boundary` these and the first Squeeze are one HIP launch each way
                  (ops.finc_image_encode, ops.finc_image_decode: uint8 or fp32 images in, fp32 or uint8 images out)
   GaussianPrior  train/losses.py:17-45           standard-normal base (log_prob per sample, sample(n))
@@ -1117,11 +1119,40 @@ class LogitTransform(FlowLayer):
         return (-torch.log(input) - torch.log(1 - input)).flatten(start_dim=1).sum(-1)
 
 
-class Dequantization(FlowLayer):
-    """Uniform dequantisation (layers/dequantize.py + distributions/uniform.py): forward adds U[0,1) noise."""
+class UniformDistribution(nn.Module):
+    """U[0, 1)^size with the interface of layers/distributions/uniform.py:6-37.  The reference registers a buffer `empty` (:14) to
+    know its device, so every checkpoint its `create_model` writes holds `0.distribution.empty`: the buffer is kept, under that
+    name, and the key sets of the two projects are equal in both directions."""
 
     def __init__(self, size=None):
         super().__init__()
+        self.size = None if size is None else tuple(size)
+        self.dim = None if size is None else int(np.prod(size))
+        self.register_buffer('empty', torch.zeros(1))
+
+    def forward(self, input, context=None):
+        return self.log_prob(input, context)
+
+    def log_prob(self, input, context=None):
+        inside = (input >= 0) & (input <= 1.)
+        return torch.where(inside, torch.zeros_like(input), torch.full_like(input, -1e30)).flatten(start_dim=1).sum(-1)
+
+    def sample(self, n_samples, context=None):
+        return torch.rand((n_samples, *self.size), device=self.empty.device), 0.
+
+
+class Dequantization(FlowLayer):
+    """Uniform dequantisation (layers/dequantize.py + distributions/uniform.py): forward adds U[0,1) noise.  `distribution` is the
+    reference's child module (`Dequantization(UniformDistribution(size))` there, layers/dequantize.py:7-10; a module handed in is
+    kept as it is) and carries its `empty` buffer into the state dict.  The noise itself is drawn on the input's device, in the
+    input's shape, whatever `size` says."""
+
+    def __init__(self, size=None):
+        super().__init__()
+        if isinstance(size, nn.Module):
+            self.distribution, size = size, getattr(size, "size", None)
+        else:
+            self.distribution = UniformDistribution(size)
         self.size = size
 
     def forward(self, input, context=None):

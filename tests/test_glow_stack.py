@@ -38,6 +38,10 @@ def test_create_model_topology():
     keys = set(m.state_dict().keys())
     assert "5.conv_tl.conv.weight" in keys and "6.log_scale" in keys and "7.W" in keys
     assert "8.net.0.weight" in keys and "8.net.4.logs" in keys
+    # the preprocessing layers' share of a reference checkpoint: its UniformDistribution's buffer and the two Normalizations' (the
+    # complete lists, in order, against the reference's own: tests/test_reference_model_host.py)
+    assert [k for k in m.state_dict() if int(k.split(".")[0]) < 4] == ["0.distribution.empty", "1.translation", "1.scale",
+                                                                      "2.translation", "2.scale"]
     assert m.base_distribution.size == (48, 4, 4)
 
 
