@@ -51,6 +51,7 @@ SYMBOLS = [
     "finc_gauss_split_f32", "finc_gauss_split_merge_f32", "finc_gauss_split_backward_f32",
     "finc_split_prior_merge_backward_f32", "finc_split_prior_merge_backward_rawbf16_f32", "finc_gauss_split_merge_backward_f32",
     "finc_plu_supported_f32", "finc_plu_compose_f32", "finc_plu_compose_backward_f32",
+    "finc_debug_pixel_plan",
 ]
 
 #: the ABI version this binding is written against (include/finc.h: finc_version)
@@ -94,6 +95,9 @@ MERGE_BACKWARD_ABI_VERSION = 117
 #: the version that added the PLU-parametrised 1x1 convolution's parameter work (finc_plu_supported_f32, finc_plu_compose_f32,
 #: finc_plu_compose_backward_f32): what glow.Conv1x1LU launches
 PLU_ABI_VERSION = 118
+#: the version that added the host-only plan query of the per-pixel layers' three launch rules (finc_debug_pixel_plan): what
+#: `pixel_plan` and the launch-regime tests of the coupling, ActNorm, bias + ReLU, the lead product and the mix read
+PIXEL_PLAN_ABI_VERSION = 119
 
 _lib = None
 
@@ -180,6 +184,10 @@ def lib():
         raise FincError(f"{LIB_PATH} reports finc_version() = {have}, the PLU-parametrised 1x1 convolution's entry points "
                         f"(finc_plu_compose_f32, finc_plu_compose_backward_f32) came with {PLU_ABI_VERSION}: rebuild it "
                         "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
+    if have < PIXEL_PLAN_ABI_VERSION:
+        raise FincError(f"{LIB_PATH} reports finc_version() = {have}, the per-pixel layers' launch-plan query "
+                        f"(finc_debug_pixel_plan) came with {PIXEL_PLAN_ABI_VERSION}: rebuild it "
+                        "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
     L.finc_build_flags.restype = u
     L.finc_clear_fault.restype = i
     L.finc_status_string.restype = ctypes.c_char_p
@@ -236,6 +244,7 @@ def lib():
     L.finc_debug_gradw_plan.argtypes = [i, i, i, i, i, i, i, i, ctypes.POINTER(ctypes.c_longlong)]
     L.finc_debug_conv_plan.argtypes = [i, i, i, i, i, i, i, i, ctypes.POINTER(ctypes.c_int)]
     L.finc_debug_f64_plan.argtypes = [i, i, i, i, i, i, i, ctypes.POINTER(ctypes.c_int)]
+    L.finc_debug_pixel_plan.argtypes = [i, i, i, i, i, i, i, i, ctypes.POINTER(ctypes.c_longlong)]
     L.finc_mix_supported_f32.argtypes = [i]
     L.finc_mix_f32.argtypes = [vp, vp, vp, vp, i, i, i, vp]
     L.finc_mix_backward_workspace_bytes.restype = sz
@@ -362,6 +371,30 @@ def conv_plan(B, G, Cq, H, W, KH, KW, align=16):
     d = dict(zip(("form", "strip", "ns", "waves", "nrc", "RC"), (int(v) for v in info)))
     d["form"] = CONV_FORMS[d["form"]]
     return d
+
+
+#: finc_debug_pixel_plan's launch rules and, per rule, the entry-point families (include/finc.h FincPixelRule / FincPixelFamily)
+PIXEL_RULES = {"rows": 0, "parts": 1, "mix": 2}
+PIXEL_FAMILIES = {"rows": {"channel_rows": 0, "lead": 1, "negate": 2},
+                  "parts": {"transform": 0, "coupling_grad": 1, "actnorm_grad": 2},
+                  "mix": {"mix": 0}}
+
+
+def pixel_plan(rule, family, B, C, HW, align=16, elem_bytes=4, groups=0):
+    """What a per-pixel call on [B][C][HW] launches when its activation pointers are `align` bytes aligned (host-only; answered by
+    the functions the launchers call).  `rule`: "rows" (grid-stride; families "channel_rows": ActNorm's transform and bias + ReLU --
+    `elem_bytes` 2 is finc_bias_relu_bf16 --, "lead": the grouped lead product with `groups` = G, "negate": finc_negate_f32 on
+    B * C * HW elements), "parts" ((outer, part) workgroups; "transform": outer = B, "coupling_grad": outer = C / 2, "actnorm_grad":
+    outer = C; `elem_bytes` 2: a bf16 raw), "mix" (family "mix").  Returns `io` (elements per thread item; the mix: pixels per lane),
+    `threads` per workgroup, `grid`, `parts` (P or Q; the mix: waves of the grid; rows: 0), `items` (of one outer unit; the mix:
+    chunks), `trips` of the busiest thread or wave, `outer`, `lds` bytes.  None: FINC_ERR_UNSUPPORTED (no mix instantiation for C; a
+    "lead" whose channel count has one and runs the mix)."""
+    info = (ctypes.c_longlong * 8)()
+    st = lib().finc_debug_pixel_plan(PIXEL_RULES[rule], PIXEL_FAMILIES[rule][family], int(groups), B, C, HW, int(align), int(elem_bytes), info)
+    if st == 3:
+        return None
+    check(st, "finc_debug_pixel_plan")
+    return dict(zip(("io", "threads", "grid", "parts", "items", "trips", "outer", "lds"), (int(v) for v in info)))
 
 
 F64_FAMILIES = ("none", "one_wave", "msplit")

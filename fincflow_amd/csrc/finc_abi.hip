@@ -190,7 +190,7 @@ static int canonicalize(const T *w_stored, T *w_canon, int G, int Cq, int KH, in
 
 extern "C" {
 
-int finc_version(void) { return 118; }
+int finc_version(void) { return 119; }
 
 unsigned finc_build_flags(void)
 {
@@ -1141,6 +1141,16 @@ int finc_debug_conv_plan(int B, int G, int Cq, int H, int W, int KH, int KW, int
     if (int e = check_shape(B, G, Cq, H, W, KH, KW)) return e;
     if (align != 4 && align != 8 && align != 16) return FINC_ERR_BAD_DIMS;
     return finc_conv_plan_info(FincShape{B, G, Cq, H, W, KH, KW, 0}, align, info);
+}
+
+// (answers from the functions the per-pixel launchers call: finc_mix.hip finc_pixel_plan_info)
+int finc_debug_pixel_plan(int rule, int family, int groups, int B, int C, int HW, int align, int elem_bytes, long long *info)
+{
+    if (!info) return FINC_ERR_NULL_POINTER;
+    if (B < 1 || C < 1 || HW < 1) return FINC_ERR_BAD_DIMS;
+    if (align != 4 && align != 8 && align != 16) return FINC_ERR_BAD_DIMS;
+    if (elem_bytes != 4 && elem_bytes != 2) return FINC_ERR_BAD_DIMS;
+    return finc_pixel_plan_info(rule, family, groups, B, C, HW, align, elem_bytes, info);
 }
 
 int finc_debug_f64_plan(int B, int G, int Cq, int H, int W, int KH, int KW, int *info)

@@ -248,11 +248,12 @@ size_t finc_actnorm_workspace_floats(int B, int C, int HW)
 int finc_actnorm_launch(const float *x, const float *ls, const float *tr, float *y, float *logdet, int B, int C, int HW, int direction,
                         hipStream_t st)
 {
-    const bool wide = cpl_wide(HW, (uintptr_t)x | (uintptr_t)y);
-    const int nv = HW / (wide ? 4 : 1);
-    const long long items = (long long)B * C * nv;
-    const unsigned wgs = cpl_row_grid(items);
-    if (!wgs) return FINC_ERR_BAD_DIMS;
+    const CplRowPlan rp = cpl_row_plan((long long)B * C, HW, 4, (uintptr_t)x | (uintptr_t)y);
+    if (!rp.wgs) return FINC_ERR_BAD_DIMS;
+    const bool wide = rp.wide;
+    const int nv = rp.nv;
+    const long long items = rp.items;
+    const unsigned wgs = rp.wgs;
     const auto kernel = direction > 0 ? (wide ? finc_actnorm_kernel<4, 1> : finc_actnorm_kernel<1, 1>)
                                       : (wide ? finc_actnorm_kernel<4, -1> : finc_actnorm_kernel<1, -1>);
     hipLaunchKernelGGL(kernel, dim3(wgs), dim3(CPL_THREADS), 0, st, x, ls, tr, y, logdet, B, C, HW, nv, (unsigned)items);

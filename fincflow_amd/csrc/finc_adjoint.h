@@ -114,23 +114,30 @@ int finc_lead_launch(float *v, const float *lead_t, int B, int G, int Cq, int HW
 {
     const int C = G * Cq;
     if (finc_mix_supported(C)) return finc_mix_launch(v, lead_t, nullptr, v, B, C, HW, st);
-    const bool wide = cpl_wide(HW, (uintptr_t)v);
-    const int nv = HW / (wide ? 4 : 1);
-    const long long items = (long long)B * G * nv;
-    const unsigned wgs = cpl_row_grid(items);
-    if (!wgs) return FINC_ERR_BAD_DIMS;
+    const CplRowPlan rp = cpl_row_plan((long long)B * G, HW, 4, (uintptr_t)v);      // a row: the V pixels of one (image, group)
+    if (!rp.wgs) return FINC_ERR_BAD_DIMS;
+    const bool wide = rp.wide;
+    const int nv = rp.nv;
+    const long long items = rp.items;
+    const unsigned wgs = rp.wgs;
     hipLaunchKernelGGL(wide ? finc_lead_grouped_kernel<4> : finc_lead_grouped_kernel<1>, dim3(wgs), dim3(CPL_THREADS), 0, st, v, lead_t, G, Cq,
                        HW, nv, (unsigned)items);
     FINC_CHECK_LAUNCH();
     return FINC_OK;
 }
 
+// the negate's grid: one pass of 256 threads per workgroup, at most 1024 workgroups, grid-stride beyond (n < 2^31)
+static inline unsigned adj_negate_grid(size_t n)
+{
+    const size_t wgs = (n + 255) / 256;
+    return (unsigned)(wgs > 1024 ? 1024 : wgs);
+}
+
 int finc_negate_launch(float *p, size_t n, hipStream_t st)
 {
     if (n == 0) return FINC_OK;
     if (n >= ((size_t)1 << 31)) return FINC_ERR_BAD_DIMS;
-    unsigned wgs = (unsigned)((n + 255) / 256);
-    if (wgs > 1024) wgs = 1024;
+    const unsigned wgs = adj_negate_grid(n);
     hipLaunchKernelGGL(finc_negate_kernel, dim3(wgs), dim3(256), 0, st, p, (unsigned)n);
     FINC_CHECK_LAUNCH();
     return FINC_OK;

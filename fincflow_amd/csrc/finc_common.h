@@ -374,6 +374,11 @@ int finc_adjoint_weights_launch(const float *wc, float *w_adj, float *lead_t, in
 // v <- blockdiag(L^-T) v in place: finc_mix_launch where the channel count has an instantiation, the grouped kernel otherwise
 int finc_lead_launch(float *v, const float *lead_t, int B, int G, int Cq, int HW, hipStream_t st);
 int finc_negate_launch(float *p, size_t n, hipStream_t st);
+// ---- what a per-pixel call would launch, by launch rule (finc_debug_pixel_plan): finc_mix.hip, from the launchers' own functions ----
+// rule / family as FincPixelRule / FincPixelFamily of include/finc.h; `groups`: FINC_PIXEL_LEAD's G; `align`: 4, 8 or 16, the common
+// alignment of the activation pointers; `elem_bytes`: 4, or 2 for the bf16 raw of the coupling / the bf16 tensors of bias + ReLU.
+// info[8] = {io, threads, grid, parts, items, trips, outer, lds}.  Launches nothing.
+int finc_pixel_plan_info(int rule, int family, int groups, int B, int C, int HW, int align, int elem_bytes, long long *info);
 // ---- the PLU-parametrised 1x1 convolution's parameter work (W, W^-1, log|det W| and their backward): finc_plu.h, same object ----
 // the widest matrix the compose kernels take: the staged rows of a workgroup are 88 bytes of LDS per channel
 constexpr int FINC_PLU_MAX_C = 512;

@@ -629,6 +629,36 @@ inline unsigned cpl_row_grid(long long items)           // grid-stride over rows
     const long long wgs = (items + CPL_THREADS - 1) / CPL_THREADS, most = 4 * CPL_CHIP_WGS;
     return items >= (1LL << 32) - most * CPL_THREADS ? 0u : (unsigned)(wgs > most ? most : wgs);
 }
+// A grid-stride launch over `rows` rows of HW elements: pieces of V elements (16 bytes) when HW is whole pieces and every pointer of
+// `ptrs` is on 16 bytes, single elements otherwise.  wgs = 0: cpl_row_grid's refusal.  What the launchers of ActNorm's transform,
+// bias + ReLU and the grouped lead product run, and what finc_pixel_plan_info reports.
+struct CplRowPlan {
+    bool wide;
+    int nv;
+    long long items;
+    unsigned wgs;
+};
+inline CplRowPlan cpl_row_plan(long long rows, int HW, int V, uintptr_t ptrs)
+{
+    const bool wide = HW % V == 0 && (ptrs & 15u) == 0;
+    const int nv = HW / (wide ? V : 1);
+    const long long items = rows * nv;
+    return CplRowPlan{wide, nv, items, cpl_row_grid(items)};
+}
+// A transform launch: B images share half * HW / V items each in P parts, a workgroup per (image, part).  P = 0: the dimensions do
+// not fit (FINC_ERR_BAD_DIMS).  `ptrs` / `half_ptrs` as cpl_wide reads them.
+struct CplTransformPlan {
+    bool wide;
+    int nv, items, P;
+};
+inline CplTransformPlan cpl_transform_plan(int B, int C, int HW, uintptr_t ptrs, uintptr_t half_ptrs = 0)
+{
+    if ((size_t)C * HW * 4 >= ((size_t)1 << 31)) return CplTransformPlan{false, 0, 0, 0};
+    const bool wide = cpl_wide(HW, ptrs, half_ptrs);
+    const int nv = HW / (wide ? 4 : 1), items = (C / 2) * nv, P = cpl_parts(items, B);
+    if ((long long)B * P >= (1LL << 31)) return CplTransformPlan{false, 0, 0, 0};
+    return CplTransformPlan{wide, nv, items, P};
+}
 
 // The kernel of a transform / a backward for a raw element type: the fp32 ones under the names they have always had.
 template <typename R, int V, int DIR, bool LOGDET>
@@ -654,10 +684,10 @@ int cpl_launch(const float *x, const float *xb, const R *raw, const float *a, co
                int C, int HW, int direction, bool split, float *ws, hipStream_t st)
 {
     const int half = C / 2;
-    if ((size_t)C * HW * 4 >= ((size_t)1 << 31)) return FINC_ERR_BAD_DIMS;
-    const bool wide = cpl_wide(HW, cpl_bits(x, xb, y, yb) | cpl_bits16<R>(raw), cpl_bits8<R>(raw));
-    const int nv = HW / (wide ? 4 : 1), items = half * nv, P = cpl_parts(items, B);
-    if ((long long)B * P >= (1LL << 31)) return FINC_ERR_BAD_DIMS;
+    const CplTransformPlan tp = cpl_transform_plan(B, C, HW, cpl_bits(x, xb, y, yb) | cpl_bits16<R>(raw), cpl_bits8<R>(raw));
+    if (!tp.P) return FINC_ERR_BAD_DIMS;
+    const bool wide = tp.wide;
+    const int nv = tp.nv, items = tp.items, P = tp.P;
     const dim3 grid((unsigned)((long long)B * P)), block(CPL_THREADS);
     if (split) {
         const float c = (float)(0.5 * (double)half * (double)HW * 1.8378770664093454835606594728112);        // log(2 pi)
@@ -801,11 +831,12 @@ template <typename T>
 static int cpl_bias_relu_launch(const T *in, const float *bias, T *out, int B, int C, int HW, hipStream_t st)
 {
     constexpr int V = 16 / (int)sizeof(T);
-    const bool wide = HW % V == 0 && (((uintptr_t)in | (uintptr_t)out) & 15u) == 0;
-    const int nv = HW / (wide ? V : 1);
-    const long long items = (long long)B * C * nv;
-    const unsigned wgs = cpl_row_grid(items);
-    if (!wgs) return FINC_ERR_BAD_DIMS;
+    const CplRowPlan rp = cpl_row_plan((long long)B * C, HW, V, (uintptr_t)in | (uintptr_t)out);
+    if (!rp.wgs) return FINC_ERR_BAD_DIMS;
+    const bool wide = rp.wide;
+    const int nv = rp.nv;
+    const long long items = rp.items;
+    const unsigned wgs = rp.wgs;
     if constexpr (sizeof(T) == 2)
         hipLaunchKernelGGL(wide ? finc_bias_relu_bf16_kernel<8> : finc_bias_relu_bf16_kernel<1>, dim3(wgs), dim3(CPL_THREADS), 0, st, in, bias,
                            out, C, HW, nv, (unsigned)items);

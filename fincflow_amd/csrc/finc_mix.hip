@@ -185,6 +185,7 @@ typedef void (*mix_fn)(const float *, const float *, const float *, float *, int
 struct MixInst {
     int C;
     mix_fn fn[3][2];   // [1, 2 or 4 pixels per lane][4- or 16-wave workgroup]; nullptr = not instantiated
+    int wgw[3][2];     // the WGW each entry was compiled with (its __launch_bounds__ is 64 * WGW): what a launch's block size is read from
 };
 template <int C>
 constexpr MixInst make_mix()
@@ -194,12 +195,16 @@ constexpr MixInst make_mix()
     constexpr int kb = NK <= 32 ? NK : 24;
     constexpr bool wide16 = 2 * kb + 8 * MTN + 2 * MTN + 24 <= 128;       // two pixels per lane within 128 registers
     constexpr bool quad = MTN <= 6;                                       // four pixels per lane: 204 registers at C = 96, 2 waves per SIMD
-    MixInst m{C, {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}}};
-    if constexpr (big_lds) m.fn[0][0] = finc_mix_kernel<MTN, NK, 1, 16>; else m.fn[0][0] = finc_mix_kernel<MTN, NK, 1, 4>;
-    m.fn[0][1] = finc_mix_kernel<MTN, NK, 1, 16>;
-    if constexpr (!big_lds) m.fn[1][0] = finc_mix_kernel<MTN, NK, 2, 4>;
-    if constexpr (wide16) m.fn[1][1] = finc_mix_kernel<MTN, NK, 2, 16>;
-    if constexpr (quad) { m.fn[2][0] = finc_mix_kernel<MTN, NK, 4, 4>; m.fn[2][1] = finc_mix_kernel<MTN, NK, 4, 8>; }
+    MixInst m{C, {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}}, {{0, 0}, {0, 0}, {0, 0}}};
+    if constexpr (big_lds) { m.fn[0][0] = finc_mix_kernel<MTN, NK, 1, 16>; m.wgw[0][0] = 16; }
+    else { m.fn[0][0] = finc_mix_kernel<MTN, NK, 1, 4>; m.wgw[0][0] = 4; }
+    m.fn[0][1] = finc_mix_kernel<MTN, NK, 1, 16>; m.wgw[0][1] = 16;
+    if constexpr (!big_lds) { m.fn[1][0] = finc_mix_kernel<MTN, NK, 2, 4>; m.wgw[1][0] = 4; }
+    if constexpr (wide16) { m.fn[1][1] = finc_mix_kernel<MTN, NK, 2, 16>; m.wgw[1][1] = 16; }
+    if constexpr (quad) {
+        m.fn[2][0] = finc_mix_kernel<MTN, NK, 4, 4>; m.wgw[2][0] = 4;
+        m.fn[2][1] = finc_mix_kernel<MTN, NK, 4, 8>; m.wgw[2][1] = 8;
+    }
     return m;
 }
 // every channel count of the reference's model scripts (4*Cq, Cq in {1,2,3,4,6,12,16,24,48}) and the powers of two between
@@ -213,45 +218,66 @@ const MixInst *find_mix(int C)
     return nullptr;
 }
 
+// What a call launches: the one place this is decided.  finc_mix_launch runs the plan, finc_pixel_plan_info (finc_debug_pixel_plan)
+// reports it.  `ptrs`: the address bits of in and out.  status != FINC_OK: nothing to launch.
+struct MixPlan {
+    int status = FINC_OK;
+    mix_fn fn = nullptr;
+    int px = 1;                // pixels per lane
+    int big = 0;               // one large workgroup per CU
+    int wgw = 4;               // waves per workgroup of the chosen instantiation
+    size_t lds = 0;            // fragment bytes per workgroup
+    int wgs_per_cu = 1;
+    int cpi = 0;               // chunks of 16 * px pixels per image
+    long long total = 0;       // chunks in all: wave w takes w, w + nwaves, ...
+    long long wgs = 0;         // grid.x
+};
+MixPlan mix_plan(int B, int C, int HW, uintptr_t ptrs)
+{
+    MixPlan p;
+    const MixInst *m = find_mix(C);
+    if (!m) { p.status = FINC_ERR_UNSUPPORTED; return p; }
+    if ((size_t)C * HW * 4 >= ((size_t)1 << 31)) { p.status = FINC_ERR_BAD_DIMS; return p; }
+    p.lds = (size_t)((C + 15) / 16) * (C / 4 + 1) * 64 * sizeof(float);
+    // big = one large workgroup per CU once there is enough work to give every wave of the chip several chunks
+    const long long chunks1 = (long long)B * ((HW + 15) / 16);
+    p.big = chunks1 >= 4LL * 256 * 16 ? 1 : 0;
+    // PX pixels per lane need PX*4-byte aligned rows: HW % PX == 0 and aligned bases
+    int pxi = (HW % 4 == 0 && (ptrs & 15u) == 0 && HW >= 64) ? 2 : (HW % 2 == 0 && (ptrs & 7u) == 0 && HW >= 32) ? 1 : 0;
+    int wb = p.big;
+    while (pxi > 0 && !m->fn[pxi][wb]) {       // that combination is not instantiated (registers / LDS): other size, then narrower
+        if (m->fn[pxi][wb ^ 1]) { wb ^= 1; break; }
+        --pxi;
+    }
+    if (!m->fn[pxi][wb]) wb ^= 1;
+    p.fn = m->fn[pxi][wb];
+    if (!p.fn) { p.status = FINC_ERR_UNSUPPORTED; return p; }
+    p.px = 1 << pxi;
+    p.wgw = m->wgw[pxi][wb];
+    p.cpi = (HW + 16 * p.px - 1) / (16 * p.px);
+    p.total = (long long)B * p.cpi;
+    if (p.total >= (1LL << 31)) { p.status = FINC_ERR_BAD_DIMS; return p; }
+    // persistent: enough workgroups to fill the chip at this kernel's occupancy, each wave loops over its chunks
+    const int waves_cu = pxi == 2 ? 8 : 16;    // four pixels per lane: 2 waves per SIMD
+    p.wgs_per_cu = (int)((160 * 1024) / p.lds);
+    if (p.wgs_per_cu > waves_cu / p.wgw) p.wgs_per_cu = waves_cu / p.wgw;
+    if (p.wgs_per_cu < 1) p.wgs_per_cu = 1;
+    p.wgs = (p.total + p.wgw - 1) / p.wgw;
+    if (p.wgs > 256LL * p.wgs_per_cu) p.wgs = 256LL * p.wgs_per_cu;
+    return p;
+}
+
 } // namespace
 
 bool finc_mix_supported(int C) { return find_mix(C) != nullptr; }
 
 int finc_mix_launch(const float *in, const float *mat, const float *bias, float *out, int B, int C, int HW, hipStream_t st, bool transposed)
 {
-    const MixInst *m = find_mix(C);
-    if (!m) return FINC_ERR_UNSUPPORTED;
-    if ((size_t)C * HW * 4 >= ((size_t)1 << 31)) return FINC_ERR_BAD_DIMS;
-    const size_t lds = (size_t)((C + 15) / 16) * (C / 4 + 1) * 64 * sizeof(float);
-    // PX pixels per lane need PX*4-byte aligned rows: HW % PX == 0 and aligned bases
-    const uintptr_t ptrs = (uintptr_t)in | (uintptr_t)out;
-    // big = one large workgroup per CU once there is enough work to give every wave of the chip several chunks
-    const long long chunks1 = (long long)B * ((HW + 15) / 16);
-    const int big = chunks1 >= 4LL * 256 * 16 ? 1 : 0;
-    int pxi = (HW % 4 == 0 && (ptrs & 15u) == 0 && HW >= 64) ? 2 : (HW % 2 == 0 && (ptrs & 7u) == 0 && HW >= 32) ? 1 : 0;
-    int wb = big;
-    while (pxi > 0 && !m->fn[pxi][wb]) {       // that combination is not instantiated (registers / LDS): other size, then narrower
-        if (m->fn[pxi][wb ^ 1]) { wb ^= 1; break; }
-        --pxi;
-    }
-    if (!m->fn[pxi][wb]) wb ^= 1;
-    const mix_fn fn = m->fn[pxi][wb];
-    if (!fn) return FINC_ERR_UNSUPPORTED;
-    const int px = 1 << pxi;
-    // waves per workgroup of the chosen instantiation (make_mix)
-    const int wgw = lds > 80 * 1024 ? 16 : wb == 0 ? 4 : pxi == 2 ? 8 : 16;
-    const int cpi = (HW + 16 * px - 1) / (16 * px);
-    const long long total = (long long)B * cpi;
-    if (total >= (1LL << 31)) return FINC_ERR_BAD_DIMS;
-    if (int e = finc_ensure_dynamic_lds((const void *)fn, lds)) return e;
-    // persistent: enough workgroups to fill the chip at this kernel's occupancy, each wave loops over its chunks
-    const int waves_cu = pxi == 2 ? 8 : 16;    // four pixels per lane: 2 waves per SIMD
-    int wgs_per_cu = (int)((160 * 1024) / lds);
-    if (wgs_per_cu > waves_cu / wgw) wgs_per_cu = waves_cu / wgw;
-    if (wgs_per_cu < 1) wgs_per_cu = 1;
-    long long wgs = (total + wgw - 1) / wgw;
-    if (wgs > 256LL * wgs_per_cu) wgs = 256LL * wgs_per_cu;
-    hipLaunchKernelGGL(fn, dim3((unsigned)wgs), dim3(64 * wgw), lds, st, in, mat, bias, out, C, HW, cpi, (int)total, transposed ? 1 : 0);
+    const MixPlan p = mix_plan(B, C, HW, (uintptr_t)in | (uintptr_t)out);
+    if (p.status != FINC_OK) return p.status;
+    if (int e = finc_ensure_dynamic_lds((const void *)p.fn, p.lds)) return e;
+    hipLaunchKernelGGL(p.fn, dim3((unsigned)p.wgs), dim3(64 * p.wgw), p.lds, st, in, mat, bias, out, C, HW, p.cpi, (int)p.total,
+                       transposed ? 1 : 0);
     FINC_CHECK_LAUNCH();
     return FINC_OK;
 }
@@ -261,5 +287,64 @@ int finc_mix_launch(const float *in, const float *mat, const float *bias, float 
 #include "finc_actnorm.h"
 #include "finc_adjoint.h"
 #include "finc_plu.h"
+
+// What a per-pixel call would launch (finc_debug_pixel_plan): answered from the functions the launchers above call -- cpl_row_plan /
+// cpl_row_grid, adj_negate_grid, cpl_transform_plan, cpl_grad_plan, mix_plan -- on address bits made up from `align`, the common
+// alignment of the activation pointers.  info[8] = {io, threads per workgroup, grid.x, parts, items, trips, outer, LDS bytes}.
+int finc_pixel_plan_info(int rule, int family, int groups, int B, int C, int HW, int align, int elem_bytes, long long *info)
+{
+    const uintptr_t bits = (uintptr_t)align;                         // 4, 8, 16: the low address bits of a pointer of that class
+    auto put = [&](long long io, long long threads, long long grid, long long parts, long long items, long long per_trip, long long outer,
+                   long long lds) {
+        const long long v[8] = {io, threads, grid, parts, items, items > 0 ? (items + per_trip - 1) / per_trip : 0, outer, lds};
+        for (int k = 0; k < 8; ++k) info[k] = v[k];
+        return FINC_OK;
+    };
+    if (rule == FINC_PIXEL_ROWS) {
+        if (family == FINC_PIXEL_NEGATE) {                           // finc_negate_launch on n = B * C * HW elements
+            const long long n = (long long)B * C * HW;
+            if (n >= (1LL << 31)) return FINC_ERR_BAD_DIMS;
+            const unsigned wgs = adj_negate_grid((size_t)n);
+            return put(1, 256, wgs, 0, n, 256LL * wgs, 0, 0);
+        }
+        long long rows = (long long)B * C;
+        int V = 16 / elem_bytes;                                     // bias + ReLU on bf16: pieces of 8
+        if (family == FINC_PIXEL_LEAD) {                             // finc_lead_launch's grouped kernel (fp32)
+            if (groups < 1 || C % groups || elem_bytes != 4) return FINC_ERR_BAD_DIMS;
+            if (finc_mix_supported(C)) return FINC_ERR_UNSUPPORTED;  // that call runs the mix: FINC_PIXEL_MIX answers
+            rows = (long long)B * groups;
+            V = 4;
+        } else if (family != FINC_PIXEL_CHANNEL_ROWS) {
+            return FINC_ERR_BAD_DIMS;
+        }
+        const CplRowPlan rp = cpl_row_plan(rows, HW, V, bits);
+        if (!rp.wgs) return FINC_ERR_BAD_DIMS;
+        return put(rp.wide ? V : 1, CPL_THREADS, rp.wgs, 0, rp.items, (long long)CPL_THREADS * rp.wgs, 0, 0);
+    }
+    if (rule == FINC_PIXEL_PARTS) {
+        // a bf16 raw / grad_raw: the fp32 pointers count towards the 16-byte rule, the bf16 ones towards the 8-byte rule
+        const uintptr_t half_bits = elem_bytes == 2 ? bits : 0;
+        if (family == FINC_PIXEL_TRANSFORM) {
+            if (C % 2) return FINC_ERR_BAD_DIMS;
+            const CplTransformPlan tp = cpl_transform_plan(B, C, HW, bits, half_bits);
+            if (!tp.P) return FINC_ERR_BAD_DIMS;
+            return put(tp.wide ? 4 : 1, CPL_THREADS, (long long)B * tp.P, tp.P, tp.items, (long long)CPL_THREADS * tp.P, B, 0);
+        }
+        if (family != FINC_PIXEL_COUPLING_GRAD && family != FINC_PIXEL_ACTNORM_GRAD) return FINC_ERR_BAD_DIMS;
+        if (family == FINC_PIXEL_COUPLING_GRAD && C % 2) return FINC_ERR_BAD_DIMS;
+        if (family == FINC_PIXEL_ACTNORM_GRAD && elem_bytes != 4) return FINC_ERR_BAD_DIMS;
+        const int outer = family == FINC_PIXEL_COUPLING_GRAD ? C / 2 : C;
+        const CplGradPlan gp = cpl_grad_plan(B, C, HW, outer, bits, half_bits);
+        if (!gp.Q) return FINC_ERR_BAD_DIMS;
+        return put(gp.wide ? 4 : 1, CPL_THREADS, gp.grid.x, gp.Q, gp.items, (long long)CPL_THREADS * gp.Q, outer, 0);
+    }
+    if (rule == FINC_PIXEL_MIX) {
+        if (elem_bytes != 4) return FINC_ERR_BAD_DIMS;
+        const MixPlan p = mix_plan(B, C, HW, bits);
+        if (p.status != FINC_OK) return p.status;
+        return put(p.px, 64LL * p.wgw, p.wgs, p.wgs * p.wgw, p.total, p.wgs * p.wgw, B, (long long)p.lds);
+    }
+    return FINC_ERR_BAD_DIMS;
+}
 
 unsigned finc_build_flags_mix() { return FINC_BUILD_FLAGS; }

@@ -737,6 +737,33 @@ int finc_debug_gradw_plan(int B, int G, int Cq, int H, int W, int KH, int KW, in
  * Forms 3 and 7 have no row chunks and report nrc = 1, RC = H.  Each kernel's chunk arithmetic lives in one host function that its
  * launch and this query both call.  FINC_ERR_UNSUPPORTED: the direct kernel.  Host-only. */
 int finc_debug_conv_plan(int B, int G, int Cq, int H, int W, int KH, int KW, int align, int *info);
+/* The three launch rules of the per-pixel layers (everything beside the unit), and the entry-point families that fix a rule's
+ * outer count (version 119). */
+typedef enum {
+    FINC_PIXEL_ROWS = 0,   /* grid-stride: at most 8192 workgroups of 256 threads, a thread loops with idx += gridDim.x * 256 */
+    FINC_PIXEL_PARTS = 1,  /* (outer, part) workgroups: P parts share an outer unit's items, a thread loops with idx += P * 256 */
+    FINC_PIXEL_MIX = 2     /* finc_mix_f32's persistent chunk loop: a wave loops with chunk += waves of the grid */
+} FincPixelRule;
+typedef enum {
+    /* FINC_PIXEL_ROWS */
+    FINC_PIXEL_CHANNEL_ROWS = 0,  /* rows of one (image, channel): finc_actnorm_f32, finc_bias_relu_f32, finc_bias_relu_bf16 (elem_bytes 2) */
+    FINC_PIXEL_LEAD = 1,          /* the grouped kernel of finc_lead_product_f32: rows of one (image, group), `groups` = G */
+    FINC_PIXEL_NEGATE = 2,        /* finc_negate_f32 on n = B * C * HW elements (its own cap: 1024 workgroups) */
+    /* FINC_PIXEL_PARTS */
+    FINC_PIXEL_TRANSFORM = 0,     /* outer = B: every coupling, split and merge transform, with or without the log-det */
+    FINC_PIXEL_COUPLING_GRAD = 1, /* outer = C / 2 channel pairs: every backward of the coupling and the splits */
+    FINC_PIXEL_ACTNORM_GRAD = 2   /* outer = C channels: ActNorm's backwards and finc_actnorm_init_f32 */
+} FincPixelFamily;
+/* What a per-pixel call on [B][C][HW] would launch when every activation pointer it takes is aligned to `align` bytes (4, 8 or 16)
+ * and no better, answered by the functions the launchers themselves call; launches nothing.  `elem_bytes`: 4, or 2 for the calls on
+ * bf16 tensors (the coupling's raw / grad_raw, bias + ReLU's in / out).  `groups`: G of FINC_PIXEL_LEAD, ignored otherwise.
+ * info[8] = {io: elements per thread item (1, 4, 8) -- the mix: pixels per lane (1, 2, 4); threads per workgroup; grid.x; parts:
+ * P or Q of FINC_PIXEL_PARTS, the waves of the grid for the mix, 0 for FINC_PIXEL_ROWS; items: thread items (of one outer unit
+ * under FINC_PIXEL_PARTS) -- the mix: chunks of 16 * io pixels; trips: passes the busiest thread (wave) makes through its loop;
+ * outer; bytes of LDS per workgroup (the mix)}.  trips >= 2: the loop's stride is exercised.  FINC_ERR_UNSUPPORTED: no mix
+ * instantiation for C -- or, for FINC_PIXEL_LEAD, there is one and the call runs the mix.  Host-only.  (No reference counterpart:
+ * the reference's layers are chains of elementwise PyTorch launches, layers/{coupling,actnorm,conv1x1}.py.) */
+int finc_debug_pixel_plan(int rule, int family, int groups, int B, int C, int HW, int align, int elem_bytes, long long *info);
 /* What a float64 call on this shape launches, from the plan object the launchers themselves read (finc_f64.hip): info[11] = {family
  * (0: no matrix-core kernel -- the reference-order and direct kernels run, everything else 0 too; 1: one wave per problem, Cq <= 24
  * at 3x3 and <= 32 at 2x2; 2: the M-split over a workgroup's waves, 29 .. 64 channels at 3x3 and 33 .. 64 at 2x2), the padded bank

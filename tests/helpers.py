@@ -43,13 +43,14 @@ def fake_ptr(v):
     return ctypes.c_void_p(v)
 
 
-def offset_view(t, dev):
-    """A contiguous device copy of `t` that starts one float into its allocation: 4-byte aligned, not 16."""
+def offset_view(t, dev, lead=1):
+    """A contiguous device copy of `t` that starts `lead` elements into its allocation.  One float: 4-byte aligned, not 8 or 16; two
+    floats: 8-byte aligned, not 16 (the alignment class of the mix's two-pixel form and of F(2,5))."""
     import torch
-    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=dev)
-    v = buf[1:].view(t.shape)
+    buf = torch.empty(t.numel() + lead, dtype=t.dtype, device=dev)
+    v = buf[lead:].view(t.shape)
     v.copy_(t)
-    assert v.is_contiguous() and v.data_ptr() % 16 == 4
+    assert v.is_contiguous() and v.data_ptr() % 16 == (lead * t.element_size()) % 16
     return v
 
 
@@ -219,13 +220,13 @@ def fuzz_case(rng, case):
 # ---------------------------------------------------------------------------
 # guard bands and problem isolation (tests/test_gpu_bounds.py on the GPU, tests/test_bounds_host.py for the helpers themselves)
 # ---------------------------------------------------------------------------
-GUARD_BITS = {4: 0x7FC0BEEF, 8: 0x7FF80000_00C0BEEF}      # one quiet NaN per element size, recognisable in a dump
+GUARD_BITS = {2: 0x7FCB, 4: 0x7FC0BEEF, 8: 0x7FF80000_00C0BEEF}      # one quiet NaN per element size (2: bfloat16), recognisable in a dump
 
 
 def _as_ints(t):
     import torch
-    assert t.dtype in (torch.float32, torch.float64), t.dtype
-    return t.view(torch.int32 if t.element_size() == 4 else torch.int64)
+    assert t.dtype in (torch.float32, torch.float64, torch.bfloat16), t.dtype
+    return t.view({2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
 
 
 def guard_elements(t):

@@ -23,6 +23,17 @@ def test_library_exists_and_loads():
     assert _lib.build_flags() == 0
 
 
+def test_version_is_119_and_a_118_library_is_told_to_rebuild(tmp_path):
+    """finc_debug_pixel_plan came with 119: the binding names it as its newest floor, the header declares it, and a library one
+    version older is refused with the reason."""
+    from helpers import load_stub_library
+    assert _lib.PIXEL_PLAN_ABI_VERSION == 119 and _lib.PLU_ABI_VERSION == 118
+    assert _lib.lib().finc_version() >= _lib.PIXEL_PLAN_ABI_VERSION
+    assert "finc_debug_pixel_plan" in header_symbols() and "finc_debug_pixel_plan" in _lib.SYMBOLS
+    out = load_stub_library(tmp_path, 118)
+    assert "= 118" in out and "119" in out and "rebuild it" in out and "finc_debug_pixel_plan" in out, out
+
+
 def test_every_declared_symbol_is_exported():
     syms = header_symbols()
     assert len(syms) >= 15

@@ -57,24 +57,25 @@ def orient_of(G):
 # ---------------------------------------------------------------------------------------------------------------------------------
 class Result:
     def __init__(self):
-        self.outs, self.bad, self.nguard = {}, [], 0
+        self.outs, self.bad, self.nguard, self.ptrs = {}, [], 0, {}
 
 
-def run(dev, sym, argf, ins, outs, ws=None, guard=False, lead=(), alias=None):
+def run(dev, sym, argf, ins, outs, ws=None, guard=False, lead=(), alias=None, lead_floats=1):
     """`sym(*argf(pointers, workspace pointer, workspace bytes))`.  `ins`: name -> device tensor (None = a NULL pointer); `outs`:
     name -> (shape, dtype), NaN on entry; `ws`: workspace bytes (None = NULL), NaN on entry; `lead`: the names that start one float
-    into their allocation (the dword forms); `alias`: output name -> the input it is written over (the in-place forms).  `guard`:
-    every tensor sits between guards; Result.bad names the guards that were written, Result.nguard counts the elements checked."""
+    into their allocation (the dword forms; `lead_floats` = 2: two, the 8-byte class); `alias`: output name -> the input it is written
+    over (the in-place forms).  `guard`: every tensor sits between guards; Result.bad names the guards that were written, Result.nguard
+    counts the elements checked; Result.ptrs: the addresses the call was handed."""
     from fincflow_amd import _lib
     res, views, bufs = Result(), {}, []
 
     def place(name, src):
         if guard:
-            v, b = guarded(src, dev, 1 if name in lead else 0)
+            v, b = guarded(src, dev, lead_floats if name in lead else 0)
             bufs.append((name, b, v))
             res.nguard += b.numel() - v.numel()
             return v
-        return offset_view(src, dev) if name in lead else src.clone()
+        return offset_view(src, dev, lead_floats) if name in lead else src.clone()
 
     for name, src in ins.items():
         views[name] = None if src is None else place(name, src)
@@ -89,6 +90,7 @@ def run(dev, sym, argf, ins, outs, ws=None, guard=False, lead=(), alias=None):
         st = getattr(_lib.lib(), sym)(*argf(ptr, None if wsv is None else wsv.data_ptr(), ws or 0))
     torch.cuda.synchronize(dev)
     _lib.check(st, sym)
+    res.ptrs = ptr
     res.outs = {k: views[k].clone() for k in outs}
     res.bad = ["%s: %s guard written" % (name, side) for name, b, v in bufs for side in broken_guards(b, v)]
     assert all(guards_intact(b, v) == (not broken_guards(b, v)) for _, b, v in bufs)

@@ -72,16 +72,22 @@ def gradw_wpg_rule(p, G):
 def test_plan_invariants_sweep(bank):
     Cq, KH, KW = bank
     ws_bytes = _lib.lib().finc_backward_workspace_bytes
-    seen, conv_seen, walked, chunked = set(), set(), 0, 0
+    seen, conv_seen, walked, chunked, wino5_at_8 = set(), set(), 0, 0, 0
     for G in (1, 2, 4):
         for B in SWEEP_B:
             for W in SWEEP_W:
                 for H in SWEEP_H:
                     dims = (B, G, Cq, H, W, KH, KW)
                     room = ws_bytes(*dims)
-                    for align in (4, 16):
+                    for align in (4, 8, 16):
                         p = _lib.gradw_plan(*dims, align=align)
                         ctx = (dims, align, p)
+                        if align == 8:
+                            # 8-byte pointers are float-aligned pointers to every kernel but F(2,5), which moves 8-byte pairs
+                            c4, c8 = _lib.conv_plan(*dims, align=4), _lib.conv_plan(*dims, align=8)
+                            assert p == _lib.gradw_plan(*dims, align=4), ctx
+                            assert c8 == c4 or (c8["form"] == "winograd25" and c8 == _lib.conv_plan(*dims, align=16) and W % 2 == 0), (dims, c4, c8)
+                            wino5_at_8 += c8 is not None and c8["form"] == "winograd25"
                         if p["form"] == "direct":
                             assert p["bytes"] == 0 and p["grid"] == 0, ctx
                         else:
@@ -91,7 +97,7 @@ def test_plan_invariants_sweep(bank):
                             wpg, waves = gradw_wpg_rule(p, G)
                             assert p["wpg"] == wpg and p["grid"] * p["block"] == G * waves * wpg * 64, ctx
                             assert 0 < p["bytes"] <= room, ctx + (room,)
-                            assert align == 16 or p["form"] == "dword", ctx          # 16-byte pieces need 16-byte aligned rows
+                            assert align == 16 or p["form"] == "dword", ctx          # 16-byte pieces need 16-byte aligned rows (8 is not enough)
                             seen.add(p["form"])
                             walked += p["units"] > p["wpg"]
                         if align == 16:
@@ -113,6 +119,7 @@ def test_plan_invariants_sweep(bank):
     # the sweep is not vacuous: this bank has an MFMA grad-weight form that walks, and a forward that splits its rows (the
     # streaming-bank kernel and the big banks' M-split have no row chunks)
     assert seen and walked and (chunked or conv_seen <= {"stream", "msplit"}), (bank, seen, conv_seen, walked, chunked)
+    assert bool(wino5_at_8) == ("winograd25" in conv_seen), (bank, conv_seen, wino5_at_8)      # F(2,5) banks take it at 8 bytes too
 
 
 def test_plan_queries_refuse_bad_arguments():
