@@ -52,6 +52,8 @@ SYMBOLS = [
     "finc_split_prior_merge_backward_f32", "finc_split_prior_merge_backward_rawbf16_f32", "finc_gauss_split_merge_backward_f32",
     "finc_plu_supported_f32", "finc_plu_compose_f32", "finc_plu_compose_backward_f32",
     "finc_debug_pixel_plan",
+    "finc_spline_supported_f32", "finc_spline_workspace_bytes", "finc_spline_f32", "finc_spline_backward_f32",
+    "finc_spline_reverse_backward_f32",
 ]
 
 #: the ABI version this binding is written against (include/finc.h: finc_version)
@@ -98,6 +100,9 @@ PLU_ABI_VERSION = 118
 #: the version that added the host-only plan query of the per-pixel layers' three launch rules (finc_debug_pixel_plan): what
 #: `pixel_plan` and the launch-regime tests of the coupling, ActNorm, bias + ReLU, the lead product and the mix read
 PIXEL_PLAN_ABI_VERSION = 119
+#: the version that added the rational-quadratic spline (finc_spline_f32, finc_spline_backward_f32,
+#: finc_spline_reverse_backward_f32) and its family of the plan query: what glow.SplineActivation launches
+SPLINE_ABI_VERSION = 120
 
 _lib = None
 
@@ -187,6 +192,11 @@ def lib():
     if have < PIXEL_PLAN_ABI_VERSION:
         raise FincError(f"{LIB_PATH} reports finc_version() = {have}, the per-pixel layers' launch-plan query "
                         f"(finc_debug_pixel_plan) came with {PIXEL_PLAN_ABI_VERSION}: rebuild it "
+                        "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
+    if have < SPLINE_ABI_VERSION:
+        raise FincError(f"{LIB_PATH} reports finc_version() = {have}, the rational-quadratic spline's entry points "
+                        f"(finc_spline_f32, finc_spline_backward_f32, finc_spline_reverse_backward_f32) came with "
+                        f"{SPLINE_ABI_VERSION}: rebuild it "
                         "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
     L.finc_build_flags.restype = u
     L.finc_clear_fault.restype = i
@@ -297,6 +307,12 @@ def lib():
     L.finc_plu_supported_f32.argtypes = [i]
     L.finc_plu_compose_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, vp]
     L.finc_plu_compose_backward_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp]
+    L.finc_spline_supported_f32.argtypes = [i]
+    L.finc_spline_workspace_bytes.restype = sz
+    L.finc_spline_workspace_bytes.argtypes = [i, i, i, i, i]
+    L.finc_spline_f32.argtypes = [vp, vp, i, i, fl, i, vp, vp, i, i, i, vp, sz, vp]
+    L.finc_spline_backward_f32.argtypes = [vp, vp, vp, vp, i, i, fl, vp, vp, i, i, i, vp, sz, vp]
+    L.finc_spline_reverse_backward_f32.argtypes = L.finc_spline_backward_f32.argtypes
     for name in SYMBOLS:
         getattr(L, name)  # AttributeError here = header and library out of sync
     _lib = L
@@ -376,7 +392,7 @@ def conv_plan(B, G, Cq, H, W, KH, KW, align=16):
 #: finc_debug_pixel_plan's launch rules and, per rule, the entry-point families (include/finc.h FincPixelRule / FincPixelFamily)
 PIXEL_RULES = {"rows": 0, "parts": 1, "mix": 2}
 PIXEL_FAMILIES = {"rows": {"channel_rows": 0, "lead": 1, "negate": 2},
-                  "parts": {"transform": 0, "coupling_grad": 1, "actnorm_grad": 2},
+                  "parts": {"transform": 0, "coupling_grad": 1, "actnorm_grad": 2, "spline": 4},
                   "mix": {"mix": 0}}
 
 
@@ -385,7 +401,8 @@ def pixel_plan(rule, family, B, C, HW, align=16, elem_bytes=4, groups=0):
     the functions the launchers call).  `rule`: "rows" (grid-stride; families "channel_rows": ActNorm's transform and bias + ReLU --
     `elem_bytes` 2 is finc_bias_relu_bf16 --, "lead": the grouped lead product with `groups` = G, "negate": finc_negate_f32 on
     B * C * HW elements), "parts" ((outer, part) workgroups; "transform": outer = B, "coupling_grad": outer = C / 2, "actnorm_grad":
-    outer = C; `elem_bytes` 2: a bf16 raw), "mix" (family "mix").  Returns `io` (elements per thread item; the mix: pixels per lane),
+    outer = C; `elem_bytes` 2: a bf16 raw; "spline": every spline call, outer = ceil(C * HW / 256) blocks of positions, items =
+    256 * B, io 1 whatever the alignment), "mix" (family "mix").  Returns `io` (elements per thread item; the mix: pixels per lane),
     `threads` per workgroup, `grid`, `parts` (P or Q; the mix: waves of the grid; rows: 0), `items` (of one outer unit; the mix:
     chunks), `trips` of the busiest thread or wave, `outer`, `lds` bytes.  None: FINC_ERR_UNSUPPORTED (no mix instantiation for C; a
     "lead" whose channel count has one and runs the mix)."""

@@ -190,7 +190,7 @@ static int canonicalize(const T *w_stored, T *w_canon, int G, int Cq, int KH, in
 
 extern "C" {
 
-int finc_version(void) { return 119; }
+int finc_version(void) { return 120; }
 
 unsigned finc_build_flags(void)
 {
@@ -1107,6 +1107,71 @@ int finc_actnorm_init_f32(const float *x, float *log_scale, float *translation, 
     if (workspace_short(workspace, workspace_bytes, finc_actnorm_workspace_bytes(B, C, HW))) return FINC_ERR_WORKSPACE;
     if (int e = finc_fault_gate(false)) return e;
     return finc_actnorm_init_launch(x, log_scale, translation, B, C, HW, (float *)workspace, (hipStream_t)stream);
+}
+
+// ---- the rational-quadratic spline (finc_spline.h) ----
+int finc_spline_supported_f32(int K) { return (K >= 2 && K <= 16) ? 1 : 0; }
+
+static bool spline_table_bad(int C, int HW, int K, int P) { return !finc_spline_supported_f32(K) || (P != 1 && (long long)P != (long long)C * HW); }
+
+size_t finc_spline_workspace_bytes(int B, int C, int HW, int K, int P)
+{
+    if (pixel_counts_bad(B, C, HW, false) || spline_table_bad(C, HW, K, P)) return 256;
+    return padded_ws_bytes(finc_spline_workspace_floats(B, C, HW, K, P) * sizeof(float));
+}
+
+// (C * HW * 4 >= 2^31 is the launcher's FINC_ERR_BAD_DIMS; judged here so that it comes before the alignment)
+static int spline_dims(int B, int C, int HW, float tail_bound)
+{
+    if (int e = pixel_dims(B, C, HW, false)) return e;
+    if ((size_t)C * HW * 4 >= ((size_t)1 << 31)) return FINC_ERR_BAD_DIMS;
+    return (tail_bound > 0.f && tail_bound < INFINITY) ? FINC_OK : FINC_ERR_BAD_DIMS;
+}
+
+int finc_spline_f32(const float *x, const float *table, int P, int K, float tail_bound, int direction, float *y, float *logdet, int B,
+                    int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    if (!x || !table || !y) return FINC_ERR_NULL_POINTER;
+    if (int e = spline_dims(B, C, HW, tail_bound)) return e;
+    if (direction != 1 && direction != -1) return FINC_ERR_BAD_DIMS;
+    if (misaligned(x, table, y, logdet)) return FINC_ERR_ALIGNMENT;
+    if (spline_table_bad(C, HW, K, P)) return FINC_ERR_UNSUPPORTED;
+    if (logdet && workspace_short(workspace, workspace_bytes, finc_spline_workspace_bytes(B, C, HW, K, P))) return FINC_ERR_WORKSPACE;
+    if (int e = finc_fault_gate(false)) return e;
+    return finc_spline_launch(x, table, P, K, tail_bound, direction, y, logdet, B, C, HW, (float *)workspace, (hipStream_t)stream);
+}
+
+// Both backwards of the spline: `x` is the input of the pass the mode differentiates (FincGradMode).  grad_x == grad_y is the one
+// allowed overlap.
+static int spline_grad(FincGradMode mode, const float *grad_y, const float *grad_logdet, const float *x, const float *table, int P, int K,
+                       float tail_bound, float *grad_x, float *grad_table, int B, int C, int HW, void *workspace, size_t workspace_bytes,
+                       finc_stream_t stream)
+{
+    if ((!grad_y && !grad_logdet) || !x || !table || (!grad_x && !grad_table)) return FINC_ERR_NULL_POINTER;
+    if (int e = spline_dims(B, C, HW, tail_bound)) return e;
+    if (grad_x && grad_x == x) return FINC_ERR_BAD_DIMS;
+    if (misaligned(grad_y, grad_logdet, x, table, grad_x, grad_table)) return FINC_ERR_ALIGNMENT;
+    if (spline_table_bad(C, HW, K, P)) return FINC_ERR_UNSUPPORTED;
+    if (grad_table && workspace_short(workspace, workspace_bytes, finc_spline_workspace_bytes(B, C, HW, K, P))) return FINC_ERR_WORKSPACE;
+    if (int e = finc_fault_gate(false)) return e;
+    return finc_spline_grad_launch(mode, grad_y, grad_logdet, x, table, P, K, tail_bound, grad_x, grad_table, B, C, HW, (float *)workspace,
+                                   (hipStream_t)stream);
+}
+
+int finc_spline_backward_f32(const float *grad_y, const float *grad_logdet, const float *x, const float *table, int P, int K,
+                             float tail_bound, float *grad_x, float *grad_table, int B, int C, int HW, void *workspace,
+                             size_t workspace_bytes, finc_stream_t stream)
+{
+    return spline_grad(FINC_GRAD_FWD, grad_y, grad_logdet, x, table, P, K, tail_bound, grad_x, grad_table, B, C, HW, workspace, workspace_bytes,
+                       stream);
+}
+
+int finc_spline_reverse_backward_f32(const float *grad_y, const float *grad_logdet, const float *x, const float *table, int P, int K,
+                                     float tail_bound, float *grad_x, float *grad_table, int B, int C, int HW, void *workspace,
+                                     size_t workspace_bytes, finc_stream_t stream)
+{
+    return spline_grad(FINC_GRAD_REV, grad_y, grad_logdet, x, table, P, K, tail_bound, grad_x, grad_table, B, C, HW, workspace, workspace_bytes,
+                       stream);
 }
 
 int finc_debug_backward_variant(int B, int G, int Cq, int H, int W, int KH, int KW, int *info)

@@ -355,6 +355,16 @@ int finc_actnorm_launch(const float *x, const float *ls, const float *tr, float 
 int finc_actnorm_grad_launch(FincGradMode mode, const float *gy, const float *gld, const float *v, const float *ls, const float *tr,
                              float *xo, float *gx, float *gls, float *gt, int B, int C, int HW, float *ws, hipStream_t st);
 int finc_actnorm_init_launch(const float *x, float *ls, float *tr, int B, int C, int HW, float *ws, hipStream_t st);
+// ---- the rational-quadratic spline (element-wise, linear tails): finc_spline.h, same object ----
+// table [3 (K + 1)][P] knot-major (cumwidths, cumheights, derivatives), P = 1 or C * HW, 2 <= K <= 16 (the caller's checks); `ws`
+// holds finc_spline_workspace_floats floats (needed with logdet / grad_table only).  logdet[b]: the FORWARD map's log-det in either
+// direction.  x of the grad launch: the INPUT of the differentiated pass, the forward's (FINC_GRAD_FWD) or the reverse's
+// (FINC_GRAD_REV); gy, gld, gx, gt may be nullptr.
+size_t finc_spline_workspace_floats(int B, int C, int HW, int K, int P);
+int finc_spline_launch(const float *x, const float *table, int P, int K, float tb, int direction, float *y, float *logdet, int B, int C,
+                       int HW, float *ws, hipStream_t st);
+int finc_spline_grad_launch(FincGradMode mode, const float *gy, const float *gld, const float *x, const float *table, int P, int K, float tb,
+                            float *gx, float *gt, int B, int C, int HW, float *ws, hipStream_t st);
 // ---- the image boundary (dequantise + normalise + logit + squeeze in one launch, and back): finc_image.h, same object ----
 // B, C, H, W: the IMAGE side; with (un)squeeze the other side is [B][4C][H/2][W/2].  `ws` holds finc_image_workspace_floats floats
 // (the encode always, the decode with logdet).  noise and the decode's logdet may be nullptr.

@@ -285,6 +285,7 @@ int finc_mix_launch(const float *in, const float *mat, const float *bias, float 
 #include "finc_coupling.h"
 #include "finc_image.h"
 #include "finc_actnorm.h"
+#include "finc_spline.h"
 #include "finc_adjoint.h"
 #include "finc_plu.h"
 
@@ -329,6 +330,13 @@ int finc_pixel_plan_info(int rule, int family, int groups, int B, int C, int HW,
             const CplTransformPlan tp = cpl_transform_plan(B, C, HW, bits, half_bits);
             if (!tp.P) return FINC_ERR_BAD_DIMS;
             return put(tp.wide ? 4 : 1, CPL_THREADS, (long long)B * tp.P, tp.P, tp.items, (long long)CPL_THREADS * tp.P, B, 0);
+        }
+        if (family == FINC_PIXEL_SPLINE) {                           // every spline launch: outer = blocks of 256 positions, dwords
+            if (elem_bytes != 4) return FINC_ERR_BAD_DIMS;
+            const SplPlan sp = spl_plan(B, C, HW);
+            if (!sp.Q) return FINC_ERR_BAD_DIMS;
+            return put(1, CPL_THREADS, (long long)sp.blocks * sp.Q, sp.Q, (long long)B * CPL_THREADS, (long long)CPL_THREADS * sp.Q, sp.blocks,
+                       0);
         }
         if (family != FINC_PIXEL_COUPLING_GRAD && family != FINC_PIXEL_ACTNORM_GRAD) return FINC_ERR_BAD_DIMS;
         if (family == FINC_PIXEL_COUPLING_GRAD && C % 2) return FINC_ERR_BAD_DIMS;

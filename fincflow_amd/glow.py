@@ -219,6 +219,156 @@ class ActNorm(FlowLayer):
         return -self.log_scale.sum().expand(input.size(0)) * pixels
 
 
+def rq_spline_lines(v, cumwidths, cumheights, derivatives, tail_bound, inverse):
+    """rational_quadratic.py:117-175 between [-tail_bound, tail_bound] and the identity outside, on knots that broadcast against
+    `v.shape + (K + 1,)`, restated without masks or host synchronisations: an element outside the range, or a NaN, is computed at 0
+    in its place and `torch.where` keeps the input there -- so its arithmetic is finite and, as in the kernels, it adds exactly
+    nothing to the knots' gradients (a NaN carried through the unselected branch would reach every summed gradient as 0 * NaN); the
+    inverse's discriminant is clamped at 0 instead of asserted.
+    Returns (out, log-derivative of the FORWARD map per element -- in the inverse at the recovered input, minus what the reference's
+    inverse returns).  Differentiable in `v` and the knots."""
+    K, tb = cumwidths.shape[-1] - 1, tail_bound
+    cw, ch, d = (k.expand(*v.shape, K + 1) for k in (cumwidths, cumheights, derivatives))
+    inside = (v >= -tb) & (v <= tb)
+    u = torch.where(inside, v, torch.zeros_like(v))
+    # the knots <= u counted, minus one; knot K stays out of the count, so u == tail_bound lands in the last bin
+    idx = ((u.unsqueeze(-1) >= (ch if inverse else cw)[..., :K]).sum(dim=-1) - 1).clamp(0, K - 1).unsqueeze(-1)
+    pick = lambda t, o=0: t.gather(-1, idx + o).squeeze(-1)
+    cw0, ch0, d0, d1 = pick(cw), pick(ch), pick(d), pick(d, 1)
+    w, h = pick(cw, 1) - cw0, pick(ch, 1) - ch0
+    delta = h / w
+    sd = d0 + d1 - 2 * delta
+    if inverse:
+        dy = u - ch0
+        a = dy * sd + h * (delta - d0)
+        b = h * d0 - dy * sd
+        c = -delta * dy
+        disc = (b.pow(2) - 4 * a * c).clamp(min=0)
+        th = (2 * c) / (-b - torch.sqrt(disc))
+        out = th * w + cw0
+    else:
+        th = (u - cw0) / w
+    tm = th * (1 - th)
+    den = delta + sd * tm
+    if not inverse:
+        out = ch0 + h * (delta * th.pow(2) + d0 * tm) / den
+    dnum = delta.pow(2) * (d1 * th.pow(2) + 2 * delta * tm + d0 * (1 - th).pow(2))
+    lad = torch.log(dnum) - 2 * torch.log(den)
+    return torch.where(inside, out, v), torch.where(inside, lad, torch.zeros_like(lad))
+
+
+class SplineActivation(_DerivedValues, FlowLayer):
+    """layers/activations.py SplineActivation: the element-wise monotone rational-quadratic spline with linear tails
+    (layers/splines/rational_quadratic.py), with the reference's constructor, parameter names, shapes and initialisation.  The three
+    parameters are composed into the knot table [3 * (n_bins + 1), P] (cumwidths, cumheights, derivatives; P = 1, or one row per
+    position with `individual_weights`) by the PyTorch lines of `_knots` -- parameter-sized work, recorded while a graph records,
+    otherwise cached per parameter version -- and the map over the activations runs on the HIP spline kernels: fp32 4-D device
+    tensors of this layer's `input_size`, fp32 parameters on the same device, 2 <= n_bins <= 16.  `forward` is one launch plus the
+    log-det's small reduce (`ops.finc_spline`; under autograd `ops.spline_forward`), `reverse` and `reverse_with_logdet` likewise,
+    recorded inside `ops.reverse_grad()` (`ops.spline_reverse`, `ops.spline_reverse_logdet`).  Everything else -- CPU tensors, fp64,
+    2-D inputs, other bin counts, `reverse` under autograd outside that context -- runs `_lines`: the same spline restated without
+    masks, gathers of masked elements or host synchronisations (`torch.where` on the range, the discriminant clamped at 0), which is
+    differentiable as it stands.  The map stays fp32 under autocast."""
+
+    _derived = ("_tab", "_tab_key", "_tab_ready")
+    min_bin_width = min_bin_height = min_derivative = 1e-3
+
+    def __init__(self, input_size, n_bins=5, tail_bound=10., individual_weights=False):
+        super().__init__()
+        self.input_size = tuple(input_size)
+        self.n_bins = n_bins
+        self.tail_bound = tail_bound
+        self.individual_weights = individual_weights
+        lead = (1, *self.input_size) if individual_weights else ()
+        self.unnormalized_widths = nn.Parameter(torch.randn(*lead, n_bins) * 0.01)
+        self.unnormalized_heights = nn.Parameter(torch.randn(*lead, n_bins) * 0.01)
+        self.unnormalized_derivatives = nn.Parameter(torch.randn(*lead, n_bins - 1) * 0.01)
+
+    def _params(self):
+        return self.unnormalized_widths, self.unnormalized_heights, self.unnormalized_derivatives
+
+    def _knots(self):
+        """(cumwidths, cumheights, derivatives), each [P, n_bins + 1]: rational_quadratic.py:97-115 with the padded end derivatives of
+        :38-46 (the end knots are pinned by concatenation instead of an in-place write: the same values, and no gradient either)."""
+        K, tb = self.n_bins, self.tail_bound
+        if self.min_bin_width * K > 1.0 or self.min_bin_height * K > 1.0:
+            raise ValueError('Minimal bin width or height too large for the number of bins')
+        uw, uh, ud = (p.reshape(-1, p.shape[-1]) for p in self._params())
+
+        def cumulative(u, floor):
+            part = floor + (1 - floor * K) * F.softmax(u, dim=-1)
+            cum = 2 * tb * torch.cumsum(part, dim=-1) - tb
+            ends = cum.new_full((cum.shape[0], 1), tb)
+            return torch.cat([-ends, cum[:, :-1], ends], dim=-1)
+
+        constant = float(np.log(np.exp(1 - self.min_derivative) - 1))
+        derivatives = self.min_derivative + F.softplus(F.pad(ud, pad=(1, 1)) + constant)
+        return cumulative(uw, self.min_bin_width), cumulative(uh, self.min_bin_height), derivatives
+
+    def _compose(self):
+        """The knot table as the kernels read it: [3 * (n_bins + 1), P], knot-major."""
+        with _fp32_maps(self.unnormalized_widths):
+            return torch.cat([k.t() for k in self._knots()], dim=0).contiguous()
+
+    def _table(self):
+        params = self._params()
+        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            return self._compose()                                  # recorded: grad_table reaches the parameters through these lines
+        key = ops.version_key(*params) + (params[0].device,)
+        if getattr(self, "_tab_key", None) != key:
+            with torch.no_grad():
+                self._tab = self._compose()
+            self._tab_key, self._tab_ready = key, ops.Ready(params[0].device)
+        else:
+            self._tab_ready.wait(self._tab)
+        return self._tab
+
+    def _lines(self, v, inverse):
+        """The spline on `v` in PyTorch: (out, log-derivative of the FORWARD map per element, at `v` or at the recovered input)."""
+        K = self.n_bins
+        with _fp32_maps(v):
+            shape = (1, *self.input_size, K + 1) if self.individual_weights else (K + 1,)
+            return rq_spline_lines(v, *(k.reshape(shape) for k in self._knots()), self.tail_bound, inverse)
+
+    def _hip_device(self, x):
+        return (_hip_tensor(x) and tuple(x.shape[1:]) == self.input_size and _params_on_device(x, *self._params())
+                and ops.spline_supported(self.n_bins))
+
+    def _records_graph(self, x):
+        return _records_graph(x, *self._params())
+
+    def forward(self, input, context=None):
+        if self._hip_device(input):
+            if self._records_graph(input):
+                return ops.spline_forward(input, self._table(), self.tail_bound)
+            return ops.finc_spline(input.contiguous(), self._table(), self.tail_bound, 1, True)
+        out, lad = self._lines(input, False)
+        return out, lad.flatten(start_dim=1).sum(dim=-1)
+
+    def _hip_reverse_grad(self, x):
+        """`reverse` while autograd records inside `ops.reverse_grad()`: the HIP launch with a backward of its own."""
+        return ops.reverse_grad_enabled() and self._records_graph(x) and self._hip_device(x)
+
+    def reverse(self, input, context=None):
+        if self._hip_reverse_grad(input):
+            return ops.spline_reverse(input, self._table(), self.tail_bound)
+        if self._hip_device(input) and not self._records_graph(input):
+            return ops.finc_spline(input.contiguous(), self._table(), self.tail_bound, -1)[0]
+        return self._lines(input, True)[0]
+
+    def reverse_with_logdet(self, input, context=None):
+        """`reverse` and the forward log-det at its result from the same pass."""
+        if self._hip_reverse_grad(input):
+            return ops.spline_reverse_logdet(input, self._table(), self.tail_bound)
+        if self._hip_device(input) and not self._records_graph(input):
+            return ops.finc_spline(input.contiguous(), self._table(), self.tail_bound, -1, True)
+        out, lad = self._lines(input, True)
+        return out, lad.flatten(start_dim=1).sum(dim=-1)
+
+    def logdet(self, input, context=None):
+        return self.forward(input, context)[1]
+
+
 class Conv1x1(_DerivedValues, FlowLayer):
     """layers/conv1x1.py:8-49.  Device tensors in fp32 with a channel count the library instantiates run on the HIP mixing
     kernel: inference / sampling (no autograd graph) as one streaming launch (`ops.finc_mix`), `forward` under autograd through

@@ -1225,6 +1225,156 @@ def actnorm_reverse(x, log_scale, translation):
     return _FincActNormReverseFunction.apply(x, log_scale, translation)
 
 
+def spline_supported(K):
+    """Bin counts the spline kernels take (include/finc.h: finc_spline_supported_f32): 2 .. 16."""
+    return bool(_lib.lib().finc_spline_supported_f32(int(K)))
+
+
+def _spline_args(x, table, what="input"):
+    """The checks of every spline wrapper; returns (B, C, HW, K, P) as the entry points take them."""
+    _require_device(x, what)
+    _require_device(table, "table")
+    if x.dim() != 4:
+        raise ValueError(f"expected {what} [B,C,H,W]")
+    if table.dim() != 2 or table.shape[0] % 3 or table.device != x.device:
+        raise ValueError("table must be [3 * (K + 1), P] (cumwidths, cumheights, derivatives; knot-major) on the activations' device")
+    B, C, H, W = x.shape
+    K, P = table.shape[0] // 3 - 1, table.shape[1]
+    if not spline_supported(K) or P not in (1, C * H * W):
+        raise ValueError(f"no spline kernel for K = {K} bins with P = {P} table rows on {C} x {H} x {W} positions (2 <= K <= 16; P = 1 or C*H*W)")
+    return B, C, H * W, K, P
+
+
+def finc_spline(x, table, tail_bound, direction=1, want_logdet=False, out=None):
+    """The rational-quadratic spline with linear tails (layers/splines/rational_quadratic.py) as one streaming HIP launch, from its
+    knot table [3 * (K + 1), P] (include/finc.h: finc_spline_f32): direction +1 the map, -1 its inverse.  Returns (y, logdet): logdet
+    [B], when `want_logdet`, is the FORWARD map's log-det in either direction (in direction -1 at the recovered input), summed in a
+    fixed order by a second small launch.  `out` may be `x`.  Nothing is recorded for autograd."""
+    B, C, HW, K, P = _spline_args(x, table)
+    if direction not in (1, -1):
+        raise ValueError("direction must be +1 (forward) or -1 (reverse)")
+    out = _out_like(x, out)
+    want_logdet = bool(want_logdet)
+    if x.numel() == 0:
+        return out, (torch.zeros(B, dtype=torch.float32, device=x.device) if want_logdet else None)
+    logdet = torch.empty(B, dtype=torch.float32, device=x.device) if want_logdet else None
+    nbytes = _lib.lib().finc_spline_workspace_bytes(B, C, HW, K, P) if want_logdet else None
+    _call("finc_spline_f32", x.device, x.data_ptr(), table.data_ptr(), P, K, float(tail_bound), direction, out.data_ptr(), _ptr(logdet),
+          B, C, HW, *_ws_args(x.device, nbytes), _stream_ptr(x))
+    return out, logdet
+
+
+def _spline_grads(entry, grad_y, grad_logdet, x, table, tail_bound, what, whose, need_gx, need_gt):
+    """One backward entry point of the spline behind its wrapper: the checks, the outputs asked for, the workspace and the call.
+    grad_y or grad_logdet may be None (zeros), not both."""
+    B, C, HW, K, P = _spline_args(x, table, what)
+    if grad_y is None and grad_logdet is None:
+        raise ValueError("grad_output and grad_logdet are both absent")
+    if grad_y is not None:
+        _require_device(grad_y, "grad_output")
+        if grad_y.shape != x.shape or grad_y.device != x.device:
+            raise ValueError(f"grad_output must match {whose} in shape and device")
+    _per_image(grad_logdet, "grad_logdet", x)
+    gt = torch.empty_like(table) if need_gt else None
+    outs = (torch.empty_like(x) if need_gx else None, gt)
+    if _nothing_to_launch(x, outs, (gt,)):
+        return outs
+    nbytes = _lib.lib().finc_spline_workspace_bytes(B, C, HW, K, P) if need_gt else None
+    _call(entry, x.device, _ptr(grad_y), _ptr(grad_logdet), x.data_ptr(), table.data_ptr(), P, K, float(tail_bound), *map(_ptr, outs),
+          B, C, HW, *_ws_args(x.device, nbytes), _stream_ptr(x))
+    return outs
+
+
+def finc_spline_backward(grad_y, grad_logdet, x, table, tail_bound, need_gx=True, need_gt=True):
+    """Gradients of `finc_spline(..., direction=1, want_logdet=True)` (include/finc.h: finc_spline_backward_f32) from the forward's
+    INPUT `x`: (grad_x, grad_table), each computed only if asked for (None otherwise).  grad_table is the gradient of the knot table
+    as laid out; the chain to the unnormalised parameters is PyTorch's.  Fixed-order sums: the same inputs give the same bits."""
+    return _spline_grads("finc_spline_backward_f32", grad_y, grad_logdet, x, table, tail_bound, "input", "the forward's input", need_gx,
+                         need_gt)
+
+
+def finc_spline_reverse_backward(grad_x, grad_logdet, y, table, tail_bound, need_gx=True, need_gt=True):
+    """Gradients of `finc_spline(y, ..., direction=-1)` (include/finc.h: finc_spline_reverse_backward_f32) from the reverse's INPUT `y`
+    (the position in the bin is the quadratic's root again: taken from the stored output it cancels in a narrow bin), grad_x the
+    gradient of its output, grad_logdet that of the log-det it returned (None: it returned none): (grad_y, grad_table), as above."""
+    return _spline_grads("finc_spline_reverse_backward_f32", grad_x, grad_logdet, y, table, tail_bound, "input", "the reverse's input",
+                         need_gx, need_gt)
+
+
+class _FincSplineFunction(torch.autograd.Function):
+    """`finc_spline` in the forward direction under autograd: (y, logdet) and their backward on the HIP kernels, from the saved input."""
+
+    @staticmethod
+    def forward(ctx, x, table, tail_bound):
+        x, table = x.contiguous(), table.contiguous()
+        y, logdet = finc_spline(x, table, tail_bound, 1, True)
+        ctx.save_for_backward(x, table)
+        ctx.tail_bound = tail_bound
+        return y, logdet
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y, grad_logdet):
+        x, table = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        return (*finc_spline_backward(*_incoming_grads(x, grad_y, grad_logdet), x, table, ctx.tail_bound, need_gx=need[0], need_gt=need[1]),
+                None)
+
+
+class _FincSplineReverseFunction(torch.autograd.Function):
+    """`finc_spline` in the reverse direction under autograd (inside `reverse_grad()`), saved: its INPUT."""
+
+    @staticmethod
+    def forward(ctx, y, table, tail_bound):
+        y, table = y.contiguous(), table.contiguous()
+        x = finc_spline(y, table, tail_bound, -1)[0]
+        ctx.save_for_backward(y, table)
+        ctx.tail_bound = tail_bound
+        return x
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_x):
+        y, table = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        return (*finc_spline_reverse_backward(grad_x.contiguous(), None, y, table, ctx.tail_bound, need_gx=need[0], need_gt=need[1]), None)
+
+
+class _FincSplineReverseLogdetFunction(torch.autograd.Function):
+    """The reverse with the forward log-det at its result, one pass; saved: its input y."""
+
+    @staticmethod
+    def forward(ctx, y, table, tail_bound):
+        y, table = y.contiguous(), table.contiguous()
+        x, logdet = finc_spline(y, table, tail_bound, -1, True)
+        ctx.save_for_backward(y, table)
+        ctx.tail_bound = tail_bound
+        return x, logdet
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_x, grad_logdet):
+        y, table = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        return (*finc_spline_reverse_backward(*_incoming_grads(y, grad_x, grad_logdet), y, table, ctx.tail_bound, need_gx=need[0],
+                                              need_gt=need[1]), None)
+
+
+def spline_forward(x, table, tail_bound):
+    """`finc_spline(x, table, tail_bound, +1, want_logdet=True)` under autograd: (y, logdet), gradients for `x` and `table`."""
+    return _FincSplineFunction.apply(x, table, tail_bound)
+
+
+def spline_reverse(y, table, tail_bound):
+    """`finc_spline(y, table, tail_bound, -1)[0]` under autograd: gradients for `y` and `table`."""
+    return _FincSplineReverseFunction.apply(y, table, tail_bound)
+
+
+def spline_reverse_logdet(y, table, tail_bound):
+    """`finc_spline(y, table, tail_bound, -1, want_logdet=True)` under autograd: (x, forward log-det at x)."""
+    return _FincSplineReverseLogdetFunction.apply(y, table, tail_bound)
+
+
 def inverse(input, kernel, output):
     """Drop-in for the reference extension's `inverse` (cinc_cuda_level2.cpp:19-32).
 

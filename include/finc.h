@@ -638,6 +638,44 @@ int finc_actnorm_init_f32(const float *x, float *log_scale, float *translation, 
                           size_t workspace_bytes, finc_stream_t stream);
 
 /*
+ * The element-wise monotone rational-quadratic spline with linear tails (version 120; layers/activations.py SplineActivation,
+ * layers/splines/rational_quadratic.py): activations [B][C][HW] fp32.  The calls read a KNOT TABLE, not the unnormalised parameters:
+ *   table[(a * (K + 1) + k) * P + p],  a = 0 cumwidths, 1 cumheights, 2 derivatives (rational_quadratic.py:97-115, the padded end
+ *   derivatives included), knot k of K + 1, table row p of P.  P = 1: one spline for all elements; P = C * HW: one per position
+ *   (individual_weights=True).  2 <= K <= 16 (finc_spline_supported_f32).  Knots must increase; cumwidths[0] = cumheights[0] =
+ *   -tail_bound and cumwidths[K] = cumheights[K] = tail_bound as the reference pins them.
+ * finc_spline_f32: direction +1 is :161-175, direction -1 is :135-159 with the discriminant clamped at 0 before the square root (the
+ *   reference asserts it non-negative on the host; there is no host round trip here).  The bin is the reference's: the knots <= x
+ *   counted, minus one, x == tail_bound in the last bin.  Outside [-tail_bound, tail_bound], and for NaN, y is x's bits and the
+ *   log-derivative 0.  `logdet` [B] (optional; needs the workspace): in EITHER direction the FORWARD map's log-det per image, in
+ *   direction -1 at the recovered input (minus what the reference's inverse returns), summed in a fixed order -- the same inputs give
+ *   the same bits.  y == x is allowed.
+ * finc_spline_backward_f32: gradients of direction +1 from its saved INPUT x: grad_x = grad_y f'(x) + grad_logdet[b] dlog f'/dx and
+ *   grad_table [3 (K + 1)][P], the gradient of the table as laid out above (an element adds to its own bin's two knots per array; a
+ *   tail element adds nothing and hands grad_y through), a fixed-order sum over the batch (P > 1) or over everything (P = 1); it needs
+ *   the workspace.  grad_y and grad_logdet may be NULL (zeros), not both; grad_x and grad_table may be NULL, not both.
+ * finc_spline_reverse_backward_f32: gradients of direction -1 (dx/dy = 1 / f'(x), dx/dtable = -(df/dtable) / f'(x)) from its saved
+ *   INPUT, handed over as `x`: the position of the recovered value in its bin is the root of the reverse's quadratic, recomputed
+ *   here -- taken as a quotient from the stored output it cancels in a narrow bin, and the log-det's gradient with it.
+ *   grad_logdet: of the log-det that call returned, NULL when it returned none.  Otherwise as above.
+ *   grad_x == grad_y is allowed in both; grad_x == x is FINC_ERR_BAD_DIMS.
+ * Refusal order: NULL -> dims (non-positive or overflowing, a direction other than +1 / -1, a tail_bound that is not positive and
+ * finite, forbidden aliasing) FINC_ERR_BAD_DIMS -> a pointer not 4-byte aligned FINC_ERR_ALIGNMENT -> K outside 2..16 or a P that is
+ * neither 1 nor C * HW FINC_ERR_UNSUPPORTED -> a missing / short workspace where one is needed FINC_ERR_WORKSPACE -> the sticky-fault
+ * rule below.
+ */
+int finc_spline_supported_f32(int K);
+size_t finc_spline_workspace_bytes(int B, int C, int HW, int K, int P);
+int finc_spline_f32(const float *x, const float *table, int P, int K, float tail_bound, int direction, float *y, float *logdet, int B,
+                    int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream);
+int finc_spline_backward_f32(const float *grad_y, const float *grad_logdet, const float *x, const float *table, int P, int K,
+                             float tail_bound, float *grad_x, float *grad_table, int B, int C, int HW, void *workspace,
+                             size_t workspace_bytes, finc_stream_t stream);
+int finc_spline_reverse_backward_f32(const float *grad_y, const float *grad_logdet, const float *x, const float *table, int P, int K,
+                                     float tail_bound, float *grad_x, float *grad_table, int B, int C, int HW, void *workspace,
+                                     size_t workspace_bytes, finc_stream_t stream);
+
+/*
  * The image boundary (version 115; layers/dequantize.py, layers/normalize.py, layers/transforms.py:6-19, layers/squeeze.py:5-41): what
  * every model starts with -- Dequantization, Normalization(s), LogitTransform, Squeeze -- as ONE streaming launch per direction.
  * B, C, H, W describe the IMAGE side in every call; with squeeze / unsqueeze = 1 the other side is [B][4C][H/2][W/2] in the
@@ -752,7 +790,11 @@ typedef enum {
     /* FINC_PIXEL_PARTS */
     FINC_PIXEL_TRANSFORM = 0,     /* outer = B: every coupling, split and merge transform, with or without the log-det */
     FINC_PIXEL_COUPLING_GRAD = 1, /* outer = C / 2 channel pairs: every backward of the coupling and the splits */
-    FINC_PIXEL_ACTNORM_GRAD = 2   /* outer = C channels: ActNorm's backwards and finc_actnorm_init_f32 */
+    FINC_PIXEL_ACTNORM_GRAD = 2,  /* outer = C channels: ActNorm's backwards and finc_actnorm_init_f32 */
+    FINC_PIXEL_SPLINE = 4         /* (version 120; 3 stays FINC_ERR_BAD_DIMS, the unknown family that callers written against 119
+                                     probe with) outer = ceil(C * HW / 256) blocks of positions: every spline call, transform and
+                                     backward, P = 1 and P = C * HW alike; items = 256 * B (a lane walks the images b = q, q + Q, ...),
+                                     io = 1 (dwords) whatever the alignment */
 } FincPixelFamily;
 /* What a per-pixel call on [B][C][HW] would launch when every activation pointer it takes is aligned to `align` bytes (4, 8 or 16)
  * and no better, answered by the functions the launchers themselves call; launches nothing.  `elem_bytes`: 4, or 2 for the calls on
