@@ -25,6 +25,12 @@
 //
 // direction +1 is :161-175.  direction -1 is :135-159 with root = 2c / (-b - sqrt(disc)); disc is CLAMPED at 0 before the square
 // root: the reference asserts disc >= 0 on the host and would stop on a rounding-negative value, a kernel has no host round trip.
+// The root is a position in the bin: it is CLAMPED to [0, 1] and x to [cw0, cw1] (spl_root; the reverse and the reverse's backward
+// both use it).  A root of 1 + 1e-4 makes the log-det's d1 th^2 + 2 delta th (1 - th) + d0 (1 - th)^2 negative -- a NaN log q from a
+// finite in-range input -- and puts x outside its bin.  The clamp is a backstop: the quadratic is solved from the NEARER knot (the
+// upper half of a bin through the spline's mirror image), where c is small and b^2 - 4ac does not cancel as it does in fp32 one ulp
+// from the far knot of a steep bin beside a flat one, and in whichever of 2c / (-b - sqrt) and (-b + sqrt) / 2a adds two numbers of
+// one sign, so that x is monotone in y down to consecutive floats.
 // Outside [-tail_bound, tail_bound], and for NaN, the output is the input's bits and the log-derivative is 0.
 // logdet[b], when asked for, is the FORWARD map's log-det in either direction (in direction -1 at the recovered input: minus what the
 // reference's inverse returns), summed in a fixed order: lanes in a butterfly, one partial per wave and image in the workspace,
@@ -99,14 +105,22 @@ __device__ __forceinline__ void spl_forward(const SplBin &s, float x, float &y, 
 
 // rational_quadratic.py:135-159; ld is the forward map's log-derivative at the root (the reference returns its negative)
 // the position in the bin at which the spline takes the value y (:135-148)
-__device__ __forceinline__ float spl_root(const SplBin &s, float y)
+// Solved from the NEARER knot (the spline is its own mirror image under th -> 1 - th, d0 <-> d1, y - ch0 -> ch1 - y): `upper` says
+// which, r is the distance from that knot in [0, 1] (clamped: see the header comment), the return value the position th.
+__device__ __forceinline__ float spl_root(const SplBin &s, float y, bool &upper, float &r)
 {
 #pragma clang fp contract(off)
     const float w = s.cw1 - s.cw0, h = s.ch1 - s.ch0, delta = h / w;
-    const float sd = s.d0 + s.d1 - 2.f * delta, dy = y - s.ch0;
-    const float a = dy * sd + h * (delta - s.d0), b = h * s.d0 - dy * sd, c = -delta * dy;
+    const float sd = s.d0 + s.d1 - 2.f * delta;
+    upper = 2.f * (y - s.ch0) > h;
+    const float dy = upper ? s.ch1 - y : y - s.ch0, da = upper ? s.d1 : s.d0;
+    const float a = dy * sd + h * (delta - da), b = h * da - dy * sd, c = -delta * dy;
     const float disc = fmaxf(b * b - 4.f * a * c, 0.f);              // (the reference asserts disc >= 0 on the host instead)
-    return (2.f * c) / (-b - sqrtf(disc));
+    // the form that adds two numbers of one sign: the reference's for b >= 0; for b < 0 (a flat bin between large derivatives:
+    // -b - sqrt cancels) the other one, and a > 0 there because a + b = h delta > 0
+    const float sq = sqrtf(disc), num = b >= 0.f ? 2.f * c : sq - b, den = b >= 0.f ? -b - sq : 2.f * a;
+    r = fminf(fmaxf(num / den, 0.f), 1.f);
+    return upper ? 1.f - r : r;
 }
 
 __device__ __forceinline__ void spl_inverse(const SplBin &s, float y, float &x, float &ld)
@@ -114,8 +128,10 @@ __device__ __forceinline__ void spl_inverse(const SplBin &s, float y, float &x, 
 #pragma clang fp contract(off)
     const float w = s.cw1 - s.cw0, h = s.ch1 - s.ch0, delta = h / w;
     const float sd = s.d0 + s.d1 - 2.f * delta;
-    const float root = spl_root(s, y);
-    x = root * w + s.cw0;
+    bool upper;
+    float r;
+    const float root = spl_root(s, y, upper, r);
+    x = fminf(fmaxf(upper ? s.cw1 - r * w : r * w + s.cw0, s.cw0), s.cw1);   // (the rounded w + cw0 can pass the knot by half an ulp of w)
     const float omt = 1.f - root, tm = root * omt, den = delta + sd * tm;
     const float dnum = delta * delta * (s.d1 * root * root + 2.f * delta * tm + s.d0 * omt * omt);
     ld = logf(dnum) - 2.f * logf(den);
@@ -167,17 +183,20 @@ __global__ __launch_bounds__(CPL_THREADS) void finc_spline_kernel(const float *x
 // 1 / w, loses the digits (measured at 16 bins on [-3, 3]: 1.6e-5 of the largest gradient from the stored x, against 1.7e-7 for
 // PyTorch's fp32 lines, which differentiate the root).
 template <int MODE>
-__device__ __forceinline__ float spl_adjoint(const SplBin &s, float th, float g, float Lb, float (&gk)[6])
+__device__ __forceinline__ float spl_adjoint(const SplBin &s, float th, float omt, float g, float Lb, float (&gk)[6])
 {
     const float w = s.cw1 - s.cw0, h = s.ch1 - s.ch0, iw = 1.f / w, delta = h * iw;
-    const float omt = 1.f - th, tm = th * omt;
+    const float tm = th * omt;
+    // 1 - 2 th; the reverse mode is handed 1 - th as the root gave it (solved from the upper knot it IS the root: 1 - (1 - r) would
+    // round a root of 1e-7 to a multiple of 6e-8), and takes the difference from that
+    const float omtt = MODE == FINC_GRAD_REV ? omt - th : 1.f - 2.f * th;
     const float sd = s.d0 + s.d1 - 2.f * delta;
     const float r = delta * th * th + s.d0 * tm, N = h * r, D = delta + sd * tm;
     const float q = s.d1 * th * th + 2.f * delta * tm + s.d0 * omt * omt, dnum = delta * delta * q;
     const float iD = 1.f / D, idn = 1.f / dnum;
     float yb = g, out = 0.f;
     if constexpr (MODE == FINC_GRAD_REV) {
-        const float lth = idn * delta * delta * (2.f * s.d1 * th - 2.f * s.d0 * omt) + (2.f * delta * delta * delta * idn - 2.f * sd * iD) * (1.f - 2.f * th);
+        const float lth = idn * delta * delta * (2.f * s.d1 * th - 2.f * s.d0 * omt) + (2.f * delta * delta * delta * idn - 2.f * sd * iD) * omtt;
         out = (g + Lb * lth * iw) * (D * D * idn);
         yb = -out;
     }
@@ -192,14 +211,25 @@ __device__ __forceinline__ float spl_adjoint(const SplBin &s, float th, float g,
     deltab -= 2.f * sb;
     float hb = Nb * r;
     const float rb = Nb * h;
-    deltab += rb * th * th;
+    if constexpr (MODE == FINC_GRAD_REV) {
+        // dy/ddelta = h th^2 / D - N (1 - 2 tm) / D^2 = h tm (d1 th^2 - d0 (1 - th)^2) / D^2: the two terms of the left form are equal to
+        // tm, and yb = -u is the size of dL/dx (1e3 in a steep bin) -- the log-det's share of Db stays as it was
+        const float DbL = -2.f * Lb * iD;
+        deltab = dnb * (2.f * delta * q + 2.f * delta * delta * tm) + DbL - 2.f * DbL * tm +
+                 yb * h * tm * (s.d1 * th * th - s.d0 * omt * omt) * iD * iD;
+    } else {
+        deltab += rb * th * th;
+    }
     thb += rb * 2.f * delta * th;
     d0b += rb * tm;
     tmb += rb * s.d0;
-    thb += tmb * (1.f - 2.f * th);
+    thb += tmb * omtt;
+    // (yb f' + Lb dL/dx at yb = -u is -g exactly; summed from its terms it carries the rounding of Lb dL/dx)
+    if constexpr (MODE == FINC_GRAD_REV) thb = -g * w;
     hb += deltab * iw;
     const float xb = thb * iw, wb = -(deltab * delta + thb * th) * iw;
-    gk[0] = -xb - wb;
+    // cw0's: -xb - wb = (deltab delta - thb (1 - th)) / w; near the upper knot the two terms of the left form are equal to 1 - th
+    gk[0] = MODE == FINC_GRAD_REV ? (deltab * delta - thb * omt) * iw : -xb - wb;
     gk[1] = wb;
     gk[2] = yb - hb;
     gk[3] = hb;
@@ -244,7 +274,17 @@ __device__ __forceinline__ void spl_grad(const float *gy, const float *__restric
             if (v >= -tb && v <= tb) {
                 const SplBin s = spl_find<KB, MODE == FINC_GRAD_REV>(t, v, K);
                 float gk[6];
-                out = spl_adjoint<MODE>(s, MODE == FINC_GRAD_REV ? spl_root(s, v) : (v - s.cw0) / (s.cw1 - s.cw0), g, Lb, gk);
+                float th, omt;
+                if constexpr (MODE == FINC_GRAD_REV) {
+                    bool upper;
+                    float r;
+                    th = spl_root(s, v, upper, r);
+                    omt = upper ? r : 1.f - r;
+                } else {
+                    th = (v - s.cw0) / (s.cw1 - s.cw0);
+                    omt = 1.f - th;
+                }
+                out = spl_adjoint<MODE>(s, th, omt, g, Lb, gk);
 #pragma unroll
                 for (int j = 0; j < KB; ++j) {
                     const bool m = s.bin == j;

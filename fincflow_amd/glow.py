@@ -234,18 +234,40 @@ def rq_spline_lines(v, cumwidths, cumheights, derivatives, tail_bound, inverse):
     # the knots <= u counted, minus one; knot K stays out of the count, so u == tail_bound lands in the last bin
     idx = ((u.unsqueeze(-1) >= (ch if inverse else cw)[..., :K]).sum(dim=-1) - 1).clamp(0, K - 1).unsqueeze(-1)
     pick = lambda t, o=0: t.gather(-1, idx + o).squeeze(-1)
-    cw0, ch0, d0, d1 = pick(cw), pick(ch), pick(d), pick(d, 1)
-    w, h = pick(cw, 1) - cw0, pick(ch, 1) - ch0
+    cw0, cw1, ch0, d0, d1 = pick(cw), pick(cw, 1), pick(ch), pick(d), pick(d, 1)
+    w, h = cw1 - cw0, pick(ch, 1) - ch0
     delta = h / w
     sd = d0 + d1 - 2 * delta
     if inverse:
-        dy = u - ch0
-        a = dy * sd + h * (delta - d0)
-        b = h * d0 - dy * sd
+        # The quadratic is solved from the NEARER knot: the spline is its own mirror image under th -> 1 - th, d0 <-> d1,
+        # y - ch0 -> ch1 - y.  Seen from the far knot b^2 and 4ac cancel as y nears it (error 1e-7 (delta / d)^2 in fp32: enough to
+        # put the root of a steep bin beside a flat one at 1 + 1e-4); seen from the near one c is small.
+        upper = 2 * (u - ch0) > h
+        dy = torch.where(upper, pick(ch, 1) - u, u - ch0)
+        da = torch.where(upper, d1, d0)
+        a = dy * sd + h * (delta - da)
+        b = h * da - dy * sd
         c = -delta * dy
-        disc = (b.pow(2) - 4 * a * c).clamp(min=0)
-        th = (2 * c) / (-b - torch.sqrt(disc))
-        out = th * w + cw0
+        disc = b.pow(2) - 4 * a * c
+        # clamped at 0, and the square root taken where it is positive only: autograd's sqrt'(0) = inf times the clamp's 0 is a NaN
+        # in every summed knot gradient (beside a steep bin's knot b^2 and 4ac, both ~1e7, cancel to 0 in fp32)
+        positive = disc > 0
+        root = torch.where(positive, torch.sqrt(torch.where(positive, disc, torch.ones_like(disc))), torch.zeros_like(disc))
+        # the root in [0, 1] in the form that adds, never subtracts, two numbers of one sign: 2c / (-b - sqrt) for b >= 0 (the
+        # reference's), (-b + sqrt) / 2a for b < 0 -- a flat bin between large derivatives, where -b - sqrt cancels (a + b =
+        # h delta > 0, so a > 0 there)
+        stable = b >= 0
+        r = torch.where(stable, 2 * c, root - b) / torch.where(stable, -b - root, 2 * a)
+        # A position in the bin: kept inside [0, 1].  Outside it d1 th^2 + 2 delta tm + d0 (1 - th)^2 can go negative and its log
+        # is NaN, from a finite in-range input, and `out` leaves the bin.  The value alone is clamped, straight-through for autograd
+        # (r - r.detach() is an exact zero): the kernels' adjoint is analytic at the clamped position, a plain clamp would zero the
+        # gradient there.
+        r = r.detach().clamp(0, 1) + (r - r.detach())
+        th = torch.where(upper, 1 - r, r)
+        out = torch.where(upper, cw1 - r * w, r * w + cw0)
+        # (and so is the result, the same way: at r = 1 the rounded w + cw0 can land half an ulp of w beyond the knot -- or beyond
+        # tail_bound, where the next layer would take it for a tail element)
+        out = torch.minimum(torch.maximum(out, cw0), cw1).detach() + (out - out.detach())
     else:
         th = (u - cw0) / w
     tm = th * (1 - th)
