@@ -22,6 +22,7 @@
 // LDS (one workgroup per CU): per k-step the x ring (2 KB) and the FIFO block behind it (1,704 B: 53 slots), then the z ring
 // (3 KB per k-step): 24 x 6,824 = 163,776 of the 163,840 bytes: maps up to 64 wide.
 #include "finc_common.h"
+#include "finc_device.h"
 #include "finc_tile.h"
 
 #include <stdlib.h>
@@ -31,14 +32,8 @@
 
 namespace {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
 
-constexpr unsigned OFF_INVALID = 0x80000000u;     // voffset beyond any slab: buffer loads return 0, stores are dropped
-constexpr unsigned OFF_BAD_CHANNEL = 0x40000000u;  // added to a valid offset it still lands beyond the slab (< 1 GiB)
 
-template <int I>
-using IC = std::integral_constant<int, I>;
-#define FINC_SB() __builtin_amdgcn_sched_barrier(0)
 
 constexpr int XSLOTS = 8;        // x ring: the pixels of the last 8 steps (taps reach back KH + KW - 2 = 4, the stores 7)
 constexpr int RING_J = 2048;     // a k-step's x ring (8 slots x 64 lanes) ...
@@ -116,8 +111,8 @@ __global__ __launch_bounds__(64 * NWV) void finc_big_kernel(const float *__restr
     const bool fh = (o & FINC_FLIP_H) != 0, fw = (o & FINC_FLIP_W) != 0;
     const int HW = H * W;
     const unsigned slab_bytes = (unsigned)CQ * (unsigned)HW * 4u;
-    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void *)(in + (size_t)bg * CQ * HW), 0, (int)slab_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc((void *)(out + (size_t)bg * CQ * HW), 0, (int)slab_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rin = FINC_SLAB_RSRC(in, (size_t)bg * CQ * HW, slab_bytes);
+    const __amdgpu_buffer_rsrc_t rout = FINC_SLAB_RSRC(out, (size_t)bg * CQ * HW, slab_bytes);
 
     for (int i = threadIdx.x; i < C::LDS_BYTES / 4; i += 64 * NWV) lds[i] = 0.f;
 
@@ -467,8 +462,8 @@ __global__ __launch_bounds__(64 * NWV) void finc_bigfwd_kernel(const float *__re
     const bool fh = (o & FINC_FLIP_H) != 0, fw = (o & FINC_FLIP_W) != 0;
     const int HW = H * W;
     const unsigned slab_bytes = (unsigned)CQ * (unsigned)HW * 4u;
-    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void *)(in + (size_t)bg * CQ * HW), 0, (int)slab_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc((void *)(out + (size_t)bg * CQ * HW), 0, (int)slab_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rin = FINC_SLAB_RSRC(in, (size_t)bg * CQ * HW, slab_bytes);
+    const __amdgpu_buffer_rsrc_t rout = FINC_SLAB_RSRC(out, (size_t)bg * CQ * HW, slab_bytes);
     for (int i = threadIdx.x; i < NSLOT * SLOT_B / 4; i += 64 * NWV) lds[i] = 0.f;
 
     float fr[C::NREG];
@@ -494,7 +489,6 @@ __global__ __launch_bounds__(64 * NWV) void finc_bigfwd_kernel(const float *__re
     }
     // ---- the fetch of one row: lane l < 20*NB takes piece l % 5 (canonical columns 16*strip - 4 + 4*piece ..) of channel row
     // l / 5 of this wave's 4*NB input channels
-    typedef unsigned v4u __attribute__((ext_vector_type(4)));
     struct Row { v4u v[NF]; };
     bool fetcher[NF];
     unsigned fbase[NF];
@@ -695,7 +689,7 @@ bool finc_big_supported(int Cq, int H, int W, int KH, int KW)
     const BInst *i = find_binst(Cq, KH, KW);
     if (!i || H < 1 || W < 16 || W % 4 != 0) return false;
     if (!i->fn && W < 48) return false;                                    // (a wide-only row)
-    return (size_t)Cq * H * W * 4 < ((size_t)1 << 30);                     // buffer-offset range marks (OFF_BAD_CHANNEL)
+    return finc_slab_in_range(Cq, H, W, 4);                                // buffer-offset range marks (OFF_BAD_CHANNEL)
 }
 
 size_t finc_big_packed_bytes(int G, int Cq, int KH, int KW)
@@ -729,10 +723,9 @@ int finc_big_launch(const float *in, const void *packed, float *out, const FincS
     const BInst *i = find_binst(s.Cq, s.KH, s.KW);
     if (!i || !finc_big_supported(s.Cq, s.H, s.W, s.KH, s.KW)) return FINC_ERR_UNSUPPORTED;
     if (((uintptr_t)in & 15u) || ((uintptr_t)out & 15u)) return FINC_ERR_ALIGNMENT;
-    const int P = 16;
-    // steps of one problem: NB*W + P - 1; the last group of lane P-1 leaves in window NB*W/4 + 4, at step NB*W + 18; the loop is
-    // unrolled by UNROLL and runs u = 0 .. Tr
-    const int T = ((s.H + P - 1) / P) * s.W + P - 1;
+    // steps of one problem: T = NB*W + P - 1 with P = 16 (finc_big_supported: W >= 16); the last group of lane P-1 leaves in window
+    // NB*W/4 + 4, at step NB*W + 18; the loop is unrolled by UNROLL and runs u = 0 .. Tr
+    const int T = finc_bands(s).T;
     const int Tr = (T + 4 + UNROLL - 1) / UNROLL * UNROLL - 1;
     const bool wide = big_wide(s.W, s.KH, s.KW) || !i->fn;
     const big_fn fn = wide ? i->fn_wide : i->fn;
@@ -758,7 +751,7 @@ bool finc_bigfwd_takes(const FincShape &s, int align)
     const BFInst *i = find_bfinst(s.Cq, s.KH, s.KW);
     if (!i || off || s.W % 4 != 0 || s.W < 4 || s.H < 1) return false;       // (16-byte pieces)
     if (align < 16) return false;
-    return (size_t)s.Cq * s.H * s.W * 4 < ((size_t)1 << 30);
+    return finc_slab_in_range(s.Cq, s.H, s.W, 4);
 }
 
 int finc_bigfwd_pack(const float *wc, void *packed, int G, int Cq, int KH, int KW, bool transpose, hipStream_t st, const float *scale,

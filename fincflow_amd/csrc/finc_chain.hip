@@ -1,7 +1,7 @@
 // Short-step inverse for the SMALL banks on the under-filled chip (gfx950 / CDNA4 only): Cq <= 16, B*G problems that do
 // not outnumber the compute units -- configs[1] (C = 48, 32x32), the units of the CIFAR Glow stack (Cq = 3, 6, 12).
 //
-// There the inverse is a chain of NB*W + P - 1 dependent steps (the reference's anti-diagonal order,
+// There the inverse is a chain of T = NB*W + P - 1 dependent steps (finc_bands, finc_common.h; the reference's anti-diagonal order,
 // cinc_cuda_kernel_level2.cu:49-56,98-111, band by band) and its time is the LENGTH OF A STEP.  The role-split kernel
 // (finc_split.hip) cut the step by dependence -- one wave carries the recurrence, three prepare everything else -- and
 // its step still took 1,100 cycles at Cq = 12, of which 150 were the recurrence wave's MFMAs (profiles/r05/notes): the
@@ -33,6 +33,7 @@
 // Same packed bank as the wavefront kernel (finc_mfma_pack), same lanes (lane p owns rows p, P+p, ... and trails lane
 // p-1 by one step), same visitation, exact fp32 MFMA; only the order in which a pixel's partial sums are added differs.
 #include "finc_common.h"
+#include "finc_device.h"
 #include "finc_tile.h"
 
 #include <stdlib.h>
@@ -42,62 +43,8 @@
 
 namespace {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-constexpr unsigned OFF_INVALID = 0x80000000u;     // voffset beyond any slab: buffer loads return 0, stores are dropped
-constexpr unsigned OFF_BAD_CHANNEL = 0x40000000u;  // added to a valid offset it still lands beyond the slab (< 1 GiB)
-
-template <int I>
-using IC = std::integral_constant<int, I>;
-#define FINC_SB() __builtin_amdgcn_sched_barrier(0)
-
-// channel held by k-slot q of register j of a solved pixel (finc_mfma.hip chan_d)
-__host__ __device__ constexpr int chan_d(int MTB, int j, int q)
-{
-    if (j < 4 * MTB) return 16 * (j >> 2) + 4 * q + (j & 3);
-    return 16 * MTB + 4 * (j - 4 * MTB) + q;
-}
-
-__device__ inline float row_shr1(float old, float src)   // lane i of each 16-lane row <- lane i-1; lane 0 keeps `old`
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, src),
-                                                                 0x111, 0xf, 0xf, false));
-}
-
-// the taps B prepares (a + b >= 2), ordered by a + b (then row-major)
-template <int KH, int KW>
-struct BTaps {
-    static constexpr int count()
-    {
-        int n = 0;
-        for (int a = 0; a < KH; ++a)
-            for (int b = 0; b < KW; ++b) n += (a + b >= 2);
-        return n;
-    }
-    static constexpr int find(int i, bool want_a)
-    {
-        for (int sum = 2; sum <= KH + KW - 2; ++sum)
-            for (int a = 0; a < KH; ++a)
-                for (int b = 0; b < KW; ++b)
-                    if (a + b == sum && i-- == 0) return want_a ? a : b;
-        return 0;
-    }
-    static constexpr int a_of(int i) { return find(i, true); }
-    static constexpr int b_of(int i) { return find(i, false); }
-};
-
-#ifdef FINC_SPLIT_STAMP   // diagnostic build: busy cycles (barrier exit -> next barrier arrival) per wave of workgroup 0
+#ifdef FINC_SPLIT_STAMP   // diagnostic build (coarse stamps: finc_device.h FINC_ST_BEGIN / FINC_ST_END), per wave of workgroup 0
 __device__ unsigned long long finc_chain_stamps[32];
-#define FINC_ST_BEGIN() unsigned long long st_b_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_b_)::"memory")
-#define FINC_ST_END()                                                                                                     \
-    do {                                                                                                                  \
-        unsigned long long st_e_;                                                                                         \
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_e_)::"memory");             \
-        st_busy += st_e_ - st_b_;                                                                                         \
-    } while (0)
-#else
-#define FINC_ST_BEGIN() do { } while (0)
-#define FINC_ST_END() do { } while (0)
 #endif
 #if defined(FINC_SPLIT_STAMP) && FINC_SPLIT_STAMP == 2   // fine stamps: raw s_memtime values at three points of a step, summed per segment
 #undef FINC_ST_BEGIN
@@ -141,7 +88,7 @@ struct LCfg {
     static constexpr int MTB = CQP / 16;          // the packed bank's tiling (finc_mfma.hip Cfg): one 16-row tile, or 4-row blocks
     static constexpr int NK = CQP / 4;            // k-steps = registers of a solved pixel = output blocks
     static constexpr int MT = MTB ? 1 : NK;
-    static constexpr int NTAP = KH * KW, NCH = BTaps<KH, KW>::count();
+    static constexpr int NTAP = KH * KW, NCH = BySumTaps<KH, KW>::count();
     static constexpr int NPACK = (NK + (NTAP - 1) * NK) * MT + 8 * MT;   // finc_mfma.hip Cfg::NPACK (NW = 1)
     static_assert(NBW >= 1 && NBW <= 3, "B waves");
     // LDS (bytes): ring slots | what the B waves prepared [parity][wave][lane] | z ring [k-step][slab][lane] | FIFO [slot][halo cell]
@@ -169,7 +116,7 @@ __global__ __launch_bounds__(64 * (2 + NBW)) void finc_chain_kernel(const float 
 {
     using C = LCfg<CQP, KH, KW, NBW>;
     constexpr int MTB = C::MTB, MT = C::MT, NK = C::NK, NCH = C::NCH;
-    using BT = BTaps<KH, KW>;
+    using BT = BySumTaps<KH, KW>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     char *const ldsb = reinterpret_cast<char *>(lds);
     // roles: 0 = A, 1..NBW = B, NBW + 1 = the I/O wave.  A workgroup's waves go to the four SIMDs in turn, so with five waves the
@@ -183,8 +130,8 @@ __global__ __launch_bounds__(64 * (2 + NBW)) void finc_chain_kernel(const float 
     const bool fh = (o & FINC_FLIP_H) != 0, fw = (o & FINC_FLIP_W) != 0;
     const int HW = H * W;
     const unsigned slab_bytes = (unsigned)CQ * (unsigned)HW * 4u;
-    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void *)(in + (size_t)bg * CQ * HW), 0, (int)slab_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc((void *)(out + (size_t)bg * CQ * HW), 0, (int)slab_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rin = FINC_SLAB_RSRC(in, (size_t)bg * CQ * HW, slab_bytes);
+    const __amdgpu_buffer_rsrc_t rout = FINC_SLAB_RSRC(out, (size_t)bg * CQ * HW, slab_bytes);
     const bool direct = W == P;                 // the band below starts the very step a row above it is solved: A writes the halo itself
 #ifdef FINC_SPLIT_STAMP
     const unsigned long long st_entry = __builtin_amdgcn_s_memtime();
@@ -296,7 +243,7 @@ __global__ __launch_bounds__(64 * (2 + NBW)) void finc_chain_kernel(const float 
                         const float v0 = fv.x, v1 = fv.y, v2 = fv.z, v3 = fv.w;
                         const float vs[4] = {v0, v1, v2, v3};
 #pragma unroll
-                        for (int j = 0; j < NK; ++j) q1[j] = row_shr1(vs[j], xs[j]);
+                        for (int j = 0; j < NK; ++j) q1[j] = row_shr<1>(vs[j], xs[j]);
                         // (all four registers of the read stay reserved until here: a register of the tuple that is never used -- NK < 4 --
                         // gets reused by the allocator at once, and the wait for the read that then guards it lands between the MFMAs)
                         asm volatile("" ::"v"(fv));
@@ -433,7 +380,7 @@ __global__ __launch_bounds__(64 * (2 + NBW)) void finc_chain_kernel(const float 
     // One copy of the code per B wave (`bi` is a compile-time constant inside): a step must not contain role branches.
     auto run_b = [&](auto bi_c) {
     constexpr int bi = decltype(bi_c)::value;
-    constexpr int NT = (NCH + NBW - 1 - bi) / NBW;                          // its taps: items bi, bi + NBW, ... of BTaps (a + b == 2 first)
+    constexpr int NT = (NCH + NBW - 1 - bi) / NBW;                          // its taps: items bi, bi + NBW, ... of BySumTaps (a + b == 2 first)
     constexpr int NZ = (NK + NBW - 1 - bi) / NBW;                           // its k-steps of the z-term: bi, bi + NBW, ...
     const int arow = chan_d(MTB, p & 3, p >> 2);                            // (A's tile: row i = 4q' + r <-> channel chan_d(r, q'))
     const bool arow_ok = MTB ? true : (p & 3) < NK;
@@ -650,9 +597,9 @@ bool finc_chain_takes(const FincShape &s)
     if (chain_off()) return false;
     const CInst *i = find_cinst(s.Cq, s.KH, s.KW);
     if (!i || s.H < 1 || s.W < 1 || s.W % 4 != 0) return false;
-    const int P = s.W < 16 ? s.W : 16;
+    const int P = finc_bands(s).P;
     if (P < s.KH - 1) return false;
-    if ((size_t)s.Cq * s.H * s.W * 4 >= ((size_t)1 << 30)) return false;
+    if (!finc_slab_in_range(s.Cq, s.H, s.W, 4)) return false;
     return (size_t)i->lds_fixed + 2 * (size_t)fifo_depth(s.W, P) * FSLOT_B <= 160 * 1024;
 }
 
@@ -660,11 +607,10 @@ int finc_chain_info(const FincShape &s, int *waves, int *lds, int *steps)
 {
     const CInst *i = find_cinst(s.Cq, s.KH, s.KW);
     if (!i) return FINC_ERR_UNSUPPORTED;
-    const int P = s.W < 16 ? s.W : 16;
-    const int NB = (s.H + P - 1) / P;
+    const FincBands b = finc_bands(s);
     *waves = 2 + i->nbw;
-    *lds = i->lds_fixed + 2 * fifo_depth(s.W, P) * FSLOT_B;
-    *steps = NB * s.W + P - 1;
+    *lds = i->lds_fixed + 2 * fifo_depth(s.W, b.P) * FSLOT_B;
+    *steps = b.T;
     return FINC_OK;
 }
 
@@ -672,11 +618,10 @@ int finc_chain_launch(const float *in, const void *packed, float *out, const Fin
 {
     const CInst *i = find_cinst(s.Cq, s.KH, s.KW);
     if (!i) return FINC_ERR_UNSUPPORTED;
-    const int P = s.W < 16 ? s.W : 16;
-    const int NB = (s.H + P - 1) / P;
+    const FincBands b = finc_bands(s);
+    const int P = b.P, T = b.T;
     const int DF = fifo_depth(s.W, P);
     const size_t lds = (size_t)i->lds_fixed + 2 * (size_t)DF * FSLOT_B;
-    const int T = NB * s.W + P - 1;
     // the kernel runs the iterations u = 0 .. Tr + 1; the last store -- lane P - 1's last group, solved by step T - 1 -- leaves in the
     // store phase of window NB * W / 4 + P / 4, i.e. in iteration u = T + 3 (W, P multiples of 4: T = 3 mod 4, u = 2 mod 4)
     const int Tr = T + 2;

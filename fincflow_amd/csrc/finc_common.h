@@ -88,6 +88,23 @@ struct FincShape {
     unsigned orient;
 };
 
+// The kernels that mark a lane's buffer offset (OFF_INVALID, OFF_BAD_CHANNEL: finc_device.h) take slabs [Cq][H][W] shorter than 1 GiB
+// only: a marked offset must land beyond the slab and below 2^32.  Every launch rule of such a kernel asks this one predicate.
+constexpr bool finc_slab_in_range(int Cq, int H, int W, int elem_bytes) { return (size_t)Cq * H * W * elem_bytes < ((size_t)1 << 30); }
+
+// Band geometry of an inverse: lane p of a wave owns rows p, P + p, ... of the map, so the H rows form NB bands of P rows, solved one
+// after the other; a band takes W steps and lane p trails lane p - 1 by one step, so the last lane finishes P - 1 steps behind the
+// first: T = NB * W + P - 1 dependent steps in all (the reference's anti-diagonal order, band by band).
+struct FincBands {
+    int P, NB, T;
+};
+inline FincBands finc_bands(const FincShape &s)
+{
+    const int P = s.W < 16 ? s.W : 16;
+    const int NB = P > 0 ? (s.H + P - 1) / P : 0;   // (callers reject W < 1 themselves, some only after asking)
+    return {P, NB, NB * s.W + P - 1};
+}
+
 // ---- generic (reference-order) kernels: finc_generic.hip ----
 int finc_launch_inverse_strict(const float *z, const float *wc, float *x, const FincShape &s, hipStream_t st);
 int finc_launch_forward_generic(const float *x, const float *wc, float *z, const FincShape &s, hipStream_t st);

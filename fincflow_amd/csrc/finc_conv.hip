@@ -18,6 +18,7 @@
 // (DESIGN.md 3.2), so finc_backward_f32 calls this kernel with `transpose` fragments and orient ^ 3 per group.
 // Replaces F.pad + cuDNN conv (layers/conv.py:102-107) x4 + chunk/cat (fastflow.py:31-50).
 #include "finc_common.h"
+#include "finc_device.h"
 #include "finc_tile.h"
 
 #include <type_traits>
@@ -25,21 +26,9 @@
 
 namespace {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
 
-constexpr unsigned OFF_INVALID = 0x80000000u;
-constexpr unsigned OFF_BAD_CHANNEL = 0x40000000u;
 
-template <int I>
-using IC = std::integral_constant<int, I>;
 
-template <int N>
-__device__ inline float row_shr(float old, float src)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old),
-                                                                 __builtin_bit_cast(int, src), 0x110 + N, 0xf, 0xf,
-                                                                 false));
-}
 template <int N>
 __device__ inline float row_shl(float src)
 {
@@ -96,7 +85,6 @@ __global__ __launch_bounds__(64 * NW)
     constexpr int IPITCH = 24;                            // floats per channel row (48 and 80 -- conflict-free for all 64 lanes -- time the same: ab27)
     constexpr int NII = (5 * CQP + 63) / 64;              // dwordx4 load instructions per row
     __shared__ __attribute__((aligned(16))) float istg[WIDE ? CQP * IPITCH + 4 : 4];
-    typedef unsigned v4u __attribute__((ext_vector_type(4)));
     v4u ostv[NOI];                                        // WIDE: the result row read back, waiting for the next step
     unsigned ost_row = 0;                                 // ... its (scalar) row offset
     bool ost_ok = false;                                  // ... and whether that row exists in this chunk (else its stores are dropped)
@@ -125,9 +113,9 @@ __global__ __launch_bounds__(64 * NW)
     const int HW = H * W;
     const unsigned slab_bytes = (unsigned)CQ * (unsigned)HW * 4u;
     const __amdgpu_buffer_rsrc_t rin =
-        __builtin_amdgcn_make_buffer_rsrc((void *)(in + (size_t)bg * CQ * HW), 0, (int)slab_bytes, 0x00020000);
+        FINC_SLAB_RSRC(in, (size_t)bg * CQ * HW, slab_bytes);
     const __amdgpu_buffer_rsrc_t rout =
-        __builtin_amdgcn_make_buffer_rsrc((void *)(out + (size_t)bg * CQ * HW), 0, (int)slab_bytes, 0x00020000);
+        FINC_SLAB_RSRC(out, (size_t)bg * CQ * HW, slab_bytes);
 
     // 16-row-tile fragments: one register each; 4-row-block fragments: four to a register, selected by the MFMA's ABID
     // (finc_tile.h).  The packed bank in memory keeps one 64-lane fragment per (tap, k-step, tile): a lane of a packed
@@ -210,8 +198,8 @@ __global__ __launch_bounds__(64 * NW)
         float *const out_slab = out + (size_t)bg * CQ * HW;
         // a row's buffer resource: the slab, or EMPTY when the row does not exist (loads give 0, stores are dropped);
         // row validity is wave-uniform: one scalar select, and the row's byte offset rides in the scalar offset
-        auto rsrc_in = [&](bool ok) { return __builtin_amdgcn_make_buffer_rsrc((void *)in_slab, 0, ok ? (int)slab_bytes : 0, 0x00020000); };
-        auto rsrc_out = [&](bool ok) { return __builtin_amdgcn_make_buffer_rsrc((void *)out_slab, 0, ok ? (int)slab_bytes : 0, 0x00020000); };
+        auto rsrc_in = [&](bool ok) { return FINC_SLAB_RSRC_IF(in_slab, 0, slab_bytes, ok); };
+        auto rsrc_out = [&](bool ok) { return FINC_SLAB_RSRC_IF(out_slab, 0, slab_bytes, ok); };
         auto rowbytes = [&](int h) { return (unsigned)((fh ? H - 1 - h : h) * W) * 4u; };
         const int r0 = blockIdx.y * RC, r1 = r0 + RC < H ? r0 + RC : H;
         const int ms = fw ? W - 16 - strip * 16 : strip * 16;       // memory column where the strip's sector starts
@@ -624,7 +612,7 @@ bool finc_conv_supported(int Cq, int H, int W, int KH, int KW)
 {
     if (stream_bank(Cq, KH, KW)) return finc_stream_supported(Cq, H, W, KH, KW, false);
     if (!find_conv(Cq, KH, KW)) return false;
-    if ((size_t)Cq * H * W * 4 >= ((size_t)1 << 30)) return false;
+    if (!finc_slab_in_range(Cq, H, W, 4)) return false;
     return true;
 }
 

@@ -26,6 +26,7 @@
 // beyond the last problem runs every step on a zero-length buffer resource (loads give 0, stores are dropped) so that the barrier
 // count stays uniform.
 #include "finc_common.h"
+#include "finc_device.h"
 
 #include <type_traits>
 #include <utility>
@@ -33,11 +34,7 @@
 namespace {
 
 typedef double v4d __attribute__((ext_vector_type(4)));
-typedef unsigned v2u __attribute__((ext_vector_type(2)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
 
-constexpr unsigned OFF_INVALID = 0x80000000u;     // voffset beyond any slab: buffer loads return 0, stores are dropped
-constexpr unsigned OFF_BAD_CHANNEL = 0x40000000u;
 
 constexpr int XS = 6;             // x ring slots: taps reach back KH + KW - 2 <= 4 steps
 constexpr int WPW = 4;            // inverse, one wave per problem: problems (= waves) per workgroup
@@ -110,7 +107,7 @@ __global__ void pack_f64_kernel(const double *__restrict__ wc, double *__restric
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t slab_rsrc(const double *t, int bg, int CQ, int HW)
 {
     const unsigned slab_bytes = (unsigned)CQ * (unsigned)HW * 8u;
-    return __builtin_amdgcn_make_buffer_rsrc((void *)(t + (size_t)bg * CQ * HW), 0, (int)slab_bytes, 0x00020000);
+    return FINC_SLAB_RSRC(t, (size_t)bg * CQ * HW, slab_bytes);
 }
 // byte offset of canonical pixel (r, cc) within a channel; fh, fw: the FINC_FLIP_* bits of the group's orientation
 __device__ __forceinline__ unsigned pix_byte_off(bool fh, bool fw, int H, int W, int r, int cc)
@@ -518,9 +515,9 @@ FincF64Plan finc_f64_plan(const FincShape &s)
     FincF64Plan p;
     const DInst *i = find_dinst(s.Cq, s.KH, s.KW);
     if (!i || s.B < 1 || s.G < 1 || s.H < 1 || s.W < 1) return p;
-    const int P = s.W < 16 ? s.W : 16;
+    const int P = finc_bands(s).P;
     if (P < s.KH - 1) return p;
-    if ((size_t)s.Cq * s.H * s.W * 8 >= ((size_t)1 << 30)) return p;        // buffer-offset range marks
+    if (!finc_slab_in_range(s.Cq, s.H, s.W, 8)) return p;                   // buffer-offset range marks
     const int DF = f64_fifo_depth(s.W, P, s.KH, s.KW, i->split);
     const size_t per = (size_t)i->lds_fixed + (size_t)DF * i->fslot;        // LDS of one problem
     if (per > F64_LDS_MAX) return p;

@@ -3,6 +3,7 @@
 // written by every MFMA of the kernel and read once, at the very end, so they belong in AGPRs (this file is compiled
 // WITHOUT -amdgpu-mfma-vgpr-form), which leaves the 256 VGPRs of a one-wave-per-SIMD kernel to the operand slots.
 #include "finc_common.h"
+#include "finc_device.h"
 #include "finc_tile.h"
 
 #include <stdlib.h>
@@ -12,13 +13,8 @@
 
 namespace {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
 
-constexpr unsigned OFF_INVALID = 0x80000000u;
-constexpr unsigned OFF_BAD_CHANNEL = 0x40000000u;
 
-template <int I>
-using IC = std::integral_constant<int, I>;
 
 // -----------------------------------------------------------------------------------------------
 // grad_w: gw[o][i][KH-1-a][KW-1-b] = sum_{image, h, w} gz[o,h,w] * x[i,h-a,w-b]  per group.
@@ -57,8 +53,8 @@ __global__ __launch_bounds__(64) void finc_gradw_kernel(const float *__restrict_
     for (int u = wslot; u < B * NS; u += WPG) {
         const int b = u / NS, strip = u % NS;
         const size_t slab = ((size_t)b * G + g) * CQ * HW;
-        const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void *)(gz + slab), 0, (int)slab_bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void *)(x + slab), 0, (int)slab_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rg = FINC_SLAB_RSRC(gz, slab, slab_bytes);
+        const __amdgpu_buffer_rsrc_t rx = FINC_SLAB_RSRC(x, slab, slab_bytes);
         // lane offsets: pixel 4kk+q of the strip, shifted left by b columns for x (invalid columns -> beyond the slab)
         unsigned og[MT][4], ox[KW][MT][4];
 #pragma unroll
@@ -173,7 +169,6 @@ __global__ __launch_bounds__(64) void finc_gradw_staged_kernel(const float *__re
     constexpr int XP = 24, GP = 20;                                     // tile pitches (floats): [channel][4 halo + 16], [channel][16]
     constexpr int NXI = (5 * CQP + 63) / 64, NGI = (4 * CQP + 63) / 64; // dwordx4 loads per row
     static_assert(KW <= 5, "the halo is one 16-byte piece");
-    typedef unsigned v4u __attribute__((ext_vector_type(4)));
     __shared__ __attribute__((aligned(16))) float xt[16 * MT * XP + 4];
     __shared__ __attribute__((aligned(16))) float gt[16 * MT * GP + 4];
     const int lane = threadIdx.x;
@@ -221,38 +216,19 @@ __global__ __launch_bounds__(64) void finc_gradw_staged_kernel(const float *__re
         const int b = u / NS, strip = u % NS;
         const size_t slab = ((size_t)b * G + g) * CQ * HW;
         auto rsrc = [&](const float *base, bool ok) {
-            return __builtin_amdgcn_make_buffer_rsrc((void *)(base + slab), 0, ok ? (int)slab_bytes : 0, 0x00020000);
+            return FINC_SLAB_RSRC_IF(base, slab, slab_bytes, ok);
         };
         const int ms = fw ? W - 16 - strip * 16 : strip * 16;           // memory column where the strip's sector starts
         const int hm = fw ? ms + 16 : ms - 4;                           // ... and the piece holding the columns left of it
         unsigned lvx[NXI], lvg[NGI];
         int lwx[NXI], lwg[NGI];
 #pragma unroll
-        for (int i = 0; i < NXI; ++i) {
-            const int t = 64 * i + lane;
-            lvx[i] = OFF_BAD_CHANNEL;
-            lwx[i] = 16 * MT * XP;                                      // scratch piece behind the tile
-            if (t < 4 * CQP) {
-                const int c = t >> 2, k = t & 3;
-                // (W % 4 == 0: a piece is inside the row or outside -- the last strip of a row that is not a multiple of 16 wide)
-                if (c < CQ && ms + 4 * k >= 0 && ms + 4 * k < W) lvx[i] = (unsigned)c * HW * 4u + (unsigned)(ms + 4 * k) * 4u;
-                lwx[i] = c * XP + (fw ? 0 : 4) + 4 * k;
-            } else if (t < 5 * CQP) {
-                const int c = t - 4 * CQP;
-                if (c < CQ && hm >= 0 && hm < W) lvx[i] = (unsigned)c * HW * 4u + (unsigned)hm * 4u;
-                lwx[i] = c * XP + (fw ? 16 : 0);
-            }
+        for (int i = 0; i < NXI; ++i) {                                 // (finc_tile.h: the strip-piece map; scratch piece behind the tile)
+            FINC_STRIP_PIECE(lvx[i], lwx[i], 64 * i + lane, 4, CQP, 0, CQ, HW, W, ms, hm, fw, XP, 4, 16 * MT * XP, true)
         }
 #pragma unroll
         for (int i = 0; i < NGI; ++i) {
-            const int t = 64 * i + lane;
-            lvg[i] = OFF_BAD_CHANNEL;
-            lwg[i] = 16 * MT * GP;
-            if (t < 4 * CQP) {
-                const int c = t >> 2, k = t & 3;
-                if (c < CQ && ms + 4 * k >= 0 && ms + 4 * k < W) lvg[i] = (unsigned)c * HW * 4u + (unsigned)(ms + 4 * k) * 4u;
-                lwg[i] = c * GP + 4 * k;
-            }
+            FINC_STRIP_PIECE(lvg[i], lwg[i], 64 * i + lane, 4, CQP, 0, CQ, HW, W, ms, hm, fw, GP, 0, 16 * MT * GP, false)
         }
         auto rowbytes = [&](int h) { return (unsigned)((fh ? H - 1 - h : h) * W) * 4u; };
         // pieces in flight: TWO rows ahead (one wave per SIMD: nobody else hides a row's HBM latency), two register sets by
@@ -384,7 +360,6 @@ __global__ __launch_bounds__(64) void finc_gradw_tiled_kernel(const float *__res
     constexpr int XP = 24, GP = 20;
     constexpr int NXI = 2;                                              // 16 channels x (4 pieces + the halo piece) = 80 load slots
     static_assert(KW <= 5, "the halo is one 16-byte piece");
-    typedef unsigned v4u __attribute__((ext_vector_type(4)));
     __shared__ __attribute__((aligned(16))) float xt[16 * XP + 4];
     __shared__ __attribute__((aligned(16))) float gt[16 * GP + 4];
     const int lane = threadIdx.x;
@@ -415,28 +390,19 @@ __global__ __launch_bounds__(64) void finc_gradw_tiled_kernel(const float *__res
         const int b = u / NS, strip = u % NS;
         const size_t slab = ((size_t)b * G + g) * CQ * HW;
         auto rsrc = [&](const float *base, bool ok) {
-            return __builtin_amdgcn_make_buffer_rsrc((void *)(base + slab), 0, ok ? (int)slab_bytes : 0, 0x00020000);
+            return FINC_SLAB_RSRC_IF(base, slab, slab_bytes, ok);
         };
         const int ms = fw ? W - 16 - strip * 16 : strip * 16;
         const int hm = fw ? ms + 16 : ms - 4;
         unsigned lvx[NXI], lvg;
         int lwx[NXI], lwg;
 #pragma unroll
-        for (int i = 0; i < NXI; ++i) {
-            const int t = 64 * i + lane;
-            lvx[i] = OFF_BAD_CHANNEL;
-            lwx[i] = 16 * XP;                                           // scratch piece behind the tile
-            if (t < 64) {
-                const int c = t >> 2, k = t & 3;
-                if (cx + c < CQ && ms + 4 * k >= 0 && ms + 4 * k < W) lvx[i] = (unsigned)(cx + c) * HW * 4u + (unsigned)(ms + 4 * k) * 4u;
-                lwx[i] = c * XP + (fw ? 0 : 4) + 4 * k;
-            } else if (t < 80) {
-                const int c = t - 64;
-                if (cx + c < CQ && hm >= 0 && hm < W) lvx[i] = (unsigned)(cx + c) * HW * 4u + (unsigned)hm * 4u;
-                lwx[i] = c * XP + (fw ? 16 : 0);
-            }
+        for (int i = 0; i < NXI; ++i) {                                 // (finc_tile.h: the strip-piece map; scratch piece behind the tile)
+            FINC_STRIP_PIECE(lvx[i], lwx[i], 64 * i + lane, 4, 16, cx, CQ, HW, W, ms, hm, fw, XP, 4, 16 * XP, true)
         }
         {
+            // the gz tile's one slot per lane: FINC_STRIP_PIECE(lvg, lwg, lane, 4, 16, cg, ..., GP, 0, 16 * GP, false) written as a select --
+            // the expansion's branch costs finc_gradw_tiled_kernel<3, 5> four VGPRs (profiles/device_prelude/isa_identity.txt)
             const int c = lane >> 2, k = lane & 3;
             lvg = (cg + c < CQ && ms + 4 * k >= 0 && ms + 4 * k < W) ? (unsigned)(cg + c) * HW * 4u + (unsigned)(ms + 4 * k) * 4u : OFF_BAD_CHANNEL;
             lwg = c * GP + 4 * k;
@@ -614,8 +580,6 @@ __device__ __forceinline__ void gradw_wino_body(const float *__restrict__ gz, co
     constexpr int NLD = (LOADX ? NXI : 0) + (LOADG ? NPC : 0);          // loads of this wave per row
     constexpr int TST = CQP * XP + 4;                                   // floats per tile buffer (XP == GP)
     static_assert(XP == GP && (TST * 4) % 16 == 0, "");
-    typedef unsigned v4u __attribute__((ext_vector_type(4)));
-    typedef float v2f __attribute__((ext_vector_type(2)));
     const int lane = threadIdx.x & 63;
     const int q = lane >> 4, n = lane & 15;
     const int HW = H * W;
@@ -667,44 +631,29 @@ __device__ __forceinline__ void gradw_wino_body(const float *__restrict__ gz, co
     // load lanes: set i, lane -> (channel c, memory tile k); lanes behind the bank park their piece in the scratch piece
     int lwg[NPC];
 #pragma unroll
-    for (int i = 0; i < NPC; ++i) {
-        const int t = 64 * i + lane;
-        lwg[i] = t < NT * CQP ? (t / NT) * GP + 4 * (t % NT) : CQP * GP;
+    for (int i = 0; i < NPC; ++i) {                                     // (the landing half of the strip-piece map: it does not depend on the strip)
+        [[maybe_unused]] unsigned voff;
+        FINC_STRIP_PIECE(voff, lwg[i], 64 * i + lane, NT, CQP, 0, CQ, HW, W, 0, 0, FW, GP, 0, CQP * GP, false)
     }
 
     for (int u = wslot; u < B * NS; u += WPG) {
         const int b = u / NS, strip = u % NS;
         const size_t slab = ((size_t)b * G + g) * CQ * HW;
         auto rsrc = [&](const float *base, bool ok) {
-            return __builtin_amdgcn_make_buffer_rsrc((void *)(base + slab), 0, ok ? (int)slab_bytes : 0, 0x00020000);
+            return FINC_SLAB_RSRC_IF(base, slab, slab_bytes, ok);
         };
         const int ms = FW ? W - SWC - strip * SWC : strip * SWC;         // memory column where the strip starts
         const int hm = FW ? ms + SWC : ms - 4;                          // ... and the piece holding the columns left of it
         unsigned lvx[NXI], lvg[NPC];
         int lwx[NXI];
 #pragma unroll
-        for (int i = 0; i < NXI; ++i) {
-            const int t = 64 * i + lane;
-            lvx[i] = OFF_BAD_CHANNEL;
-            lwx[i] = CQP * XP;                                          // scratch piece behind the tile
-            if (t < NT * CQP) {
-                const int c = t / NT, k = t % NT;
-                if (c < CQ && ms + 4 * k >= 0 && ms + 4 * k < W) lvx[i] = (unsigned)c * HW * 4u + (unsigned)(ms + 4 * k) * 4u;
-                lwx[i] = c * XP + (FW ? 0 : 4) + 4 * k;
-            } else if (t < (NT + 1) * CQP) {
-                const int c = t - NT * CQP;
-                if (c < CQ && hm >= 0 && hm < W) lvx[i] = (unsigned)c * HW * 4u + (unsigned)hm * 4u;
-                lwx[i] = c * XP + (FW ? SWC : 0);
-            }
+        for (int i = 0; i < NXI; ++i) {                                 // (finc_tile.h: the strip-piece map; scratch piece behind the tile)
+            FINC_STRIP_PIECE(lvx[i], lwx[i], 64 * i + lane, NT, CQP, 0, CQ, HW, W, ms, hm, FW, XP, 4, CQP * XP, true)
         }
 #pragma unroll
-        for (int i = 0; i < NPC; ++i) {
-            const int t = 64 * i + lane;
-            lvg[i] = OFF_BAD_CHANNEL;
-            if (t < NT * CQP) {
-                const int c = t / NT, k = t % NT;
-                if (c < CQ && ms + 4 * k >= 0 && ms + 4 * k < W) lvg[i] = (unsigned)c * HW * 4u + (unsigned)(ms + 4 * k) * 4u;
-            }
+        for (int i = 0; i < NPC; ++i) {                                 // (... and its offset half: lwg above)
+            [[maybe_unused]] int lds;
+            FINC_STRIP_PIECE(lvg[i], lds, 64 * i + lane, NT, CQP, 0, CQ, HW, W, ms, hm, FW, GP, 0, CQP * GP, false)
         }
         auto rowbytes = [&](int h) { return (unsigned)((fhh ? H - 1 - h : h) * W) * 4u; };
         v4u LX[PD][NXI], LG[PD][NPC];                                   // pieces in flight, PD rows ahead, by row % PD
@@ -1012,8 +961,6 @@ __device__ __forceinline__ void gradw_winot_body(const float *__restrict__ gz, c
     constexpr int XP = SWC + 4, GP = SWC + 4;
     constexpr int NGI = (16 * NP + 63) / 64, NXI = (16 * (NP + 1) + 63) / 64, NLD = NGI + NXI;
     constexpr int PD = 2;
-    typedef unsigned v4u __attribute__((ext_vector_type(4)));
-    typedef float v2f __attribute__((ext_vector_type(2)));
     const int lane = threadIdx.x;
     const int q = lane >> 4, n = lane & 15;
     const int HW = H * W;
@@ -1034,43 +981,28 @@ __device__ __forceinline__ void gradw_winot_body(const float *__restrict__ gz, c
     }
     int lwg[NGI];
 #pragma unroll
-    for (int i = 0; i < NGI; ++i) {
-        const int t = 64 * i + lane;
-        lwg[i] = t < 16 * NP ? (t / NP) * GP + 4 * (t % NP) : 16 * GP;
+    for (int i = 0; i < NGI; ++i) {                                     // (the landing half of the strip-piece map: it does not depend on the strip)
+        [[maybe_unused]] unsigned voff;
+        FINC_STRIP_PIECE(voff, lwg[i], 64 * i + lane, NP, 16, cg, CQ, HW, W, 0, 0, FW, GP, 0, 16 * GP, false)
     }
     for (int u = wslot; u < B * NS; u += WPG) {
         const int b = u / NS, strip = u % NS;
         const size_t slab = ((size_t)b * G + g) * CQ * HW;
         auto rsrc = [&](const float *base, bool ok) {
-            return __builtin_amdgcn_make_buffer_rsrc((void *)(base + slab), 0, ok ? (int)slab_bytes : 0, 0x00020000);
+            return FINC_SLAB_RSRC_IF(base, slab, slab_bytes, ok);
         };
         const int ms = FW ? W - SWC - strip * SWC : strip * SWC;
         const int hm = FW ? ms + SWC : ms - 4;
         unsigned lvx[NXI], lvg[NGI];
         int lwx[NXI];
 #pragma unroll
-        for (int i = 0; i < NXI; ++i) {
-            const int t = 64 * i + lane;
-            lvx[i] = OFF_BAD_CHANNEL;
-            lwx[i] = 16 * XP;
-            if (t < 16 * NP) {
-                const int c = t / NP, k = t % NP;
-                if (cx + c < CQ && ms + 4 * k >= 0 && ms + 4 * k < W) lvx[i] = (unsigned)(cx + c) * HW * 4u + (unsigned)(ms + 4 * k) * 4u;
-                lwx[i] = c * XP + (FW ? 0 : 4) + 4 * k;
-            } else if (t < 16 * (NP + 1)) {
-                const int c = t - 16 * NP;
-                if (cx + c < CQ && hm >= 0 && hm < W) lvx[i] = (unsigned)(cx + c) * HW * 4u + (unsigned)hm * 4u;
-                lwx[i] = c * XP + (FW ? SWC : 0);
-            }
+        for (int i = 0; i < NXI; ++i) {                                 // (finc_tile.h: the strip-piece map; scratch piece behind the tile)
+            FINC_STRIP_PIECE(lvx[i], lwx[i], 64 * i + lane, NP, 16, cx, CQ, HW, W, ms, hm, FW, XP, 4, 16 * XP, true)
         }
 #pragma unroll
-        for (int i = 0; i < NGI; ++i) {
-            const int t = 64 * i + lane;
-            lvg[i] = OFF_BAD_CHANNEL;
-            if (t < 16 * NP) {
-                const int c = t / NP, k = t % NP;
-                if (cg + c < CQ && ms + 4 * k >= 0 && ms + 4 * k < W) lvg[i] = (unsigned)(cg + c) * HW * 4u + (unsigned)(ms + 4 * k) * 4u;
-            }
+        for (int i = 0; i < NGI; ++i) {                                 // (... and its offset half: lwg above)
+            [[maybe_unused]] int lds;
+            FINC_STRIP_PIECE(lvg[i], lds, 64 * i + lane, NP, 16, cg, CQ, HW, W, ms, hm, FW, GP, 0, 16 * GP, false)
         }
         auto rowbytes = [&](int h) { return (unsigned)((fhh ? H - 1 - h : h) * W) * 4u; };
         v4u LX[PD][NXI], LG[PD][NGI];
@@ -1537,7 +1469,6 @@ __global__ __launch_bounds__((64 * WO * WI)) void finc_mix_gradw_kernel(const fl
     static_assert(TO * WO == MT && TI * WI == MT, "the waves' tiles cover the tile grid");
     static_assert(WO * WI == 1 || C % 16 == 0, "a partial tile is only tested for where the tile index is a constant");
     static_assert(V == 1 || V == 4, "dwords or 16-byte pieces");
-    typedef unsigned v4u __attribute__((ext_vector_type(4)));
     const int lane = threadIdx.x & 63;
     const int q = lane >> 4, m = lane & 15;
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -1567,9 +1498,9 @@ __global__ __launch_bounds__((64 * WO * WI)) void finc_mix_gradw_kernel(const fl
         const int cc = live ? chunk : 0;
         const int b = __builtin_amdgcn_readfirstlane(cc / chunks_per_image), ci = cc - b * chunks_per_image;
         const __amdgpu_buffer_rsrc_t rg =
-            __builtin_amdgcn_make_buffer_rsrc((void *)(go + (size_t)b * C * HW), 0, (int)img_bytes, 0x00020000);
+            FINC_SLAB_RSRC(go, (size_t)b * C * HW, img_bytes);
         const __amdgpu_buffer_rsrc_t rx =
-            __builtin_amdgcn_make_buffer_rsrc((void *)(x + (size_t)b * C * HW), 0, (int)img_bytes, 0x00020000);
+            FINC_SLAB_RSRC(x, (size_t)b * C * HW, img_bytes);
         const int pix = ci * 16 + 4 * q;
         if constexpr (V == 4) {
             const bool ok = live && pix < HW;                      // (HW % 4 == 0: a piece is inside the row or outside)

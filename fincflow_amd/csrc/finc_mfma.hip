@@ -37,6 +37,7 @@
 //
 // The forward has no recurrence and uses a different, simpler mapping: finc_conv.hip.
 #include "finc_common.h"
+#include "finc_device.h"
 #include "finc_tile.h"
 
 #include <stdlib.h>
@@ -47,10 +48,6 @@
 #include <vector>
 
 namespace {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef unsigned v2u __attribute__((ext_vector_type(2)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
 
 template <int CQP_, int KH_, int KW_, int NW_ = 1>
 struct Cfg {
@@ -98,15 +95,6 @@ struct Cfg {
     static constexpr int XCH = (NW > 1 && !XALIAS) ? NW * NW * NKD * 64 : 0;
 };
 
-// channel held by k-slot q of k-step j of an operand made from solved pixels: registers of the 16-row tiles first
-// (D layout: reg r of tile mt, lane row q = channel 16mt + 4q + r), then one register per 4-row block (channel
-// 16*MTB + 4sb + q after the reduce-transpose of pack_d)
-__host__ __device__ inline int chan_d(int MTB, int j, int q)
-{
-    if (j < 4 * MTB) return 16 * (j >> 2) + 4 * q + (j & 3);
-    return 16 * MTB + 4 * (j - 4 * MTB) + q;
-}
-
 // Stage 2 of the paired tile keeps a second tile alive beside the first (+4 VGPRs in the compute role) and runs in the helper-wave
 // forms only.  Their compute role is held to 128 architectural VGPRs beside the helper, and how many it needs is the compiler's
 // answer, not a quantity this file can compute: hlp_fits (make_inst) budgets the helper role and the pinned fragments only.  So the
@@ -115,15 +103,6 @@ __host__ __device__ inline int chan_d(int MTB, int j, int q)
 // scratch, and a helper-wave form may not exceed 128 VGPRs or 128 AGPRs (a spill there is a wrong result, not a slow one: hlp_fits).
 template <class C>
 __host__ __device__ constexpr bool finc_pair2_form(bool hlp) { return C::PAIR && hlp; }
-
-template <int N>
-__device__ inline float row_shr(float old, float src)
-{
-    // lane i of each 16-lane row <- lane i-N; lanes i < N keep `old`
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old),
-                                                                 __builtin_bit_cast(int, src), 0x110 + N, 0xf, 0xf,
-                                                                 false));
-}
 
 template <int A>
 struct ShiftOp {
@@ -153,9 +132,9 @@ __device__ inline void pack_d(const v4f (&acc)[C::MT], float (&xpk)[C::NKDT])
     for (int sb = 0; sb < C::NSM; ++sb) xpk[4 * C::MTB + sb] = finc_block_reduce(acc[C::MTB + sb]);
 }
 
-// taps of the inverse's phase B (a+b >= 2), row-major
+// taps of the inverse's phase B (a+b >= 2), row-major (the role-split and short-step inverses order them by a + b: finc_device.h BySumTaps)
 template <int KH, int KW>
-struct BTaps {
+struct RowMajorTaps {
     static constexpr int count()
     {
         int n = 0;
@@ -179,7 +158,6 @@ struct BTaps {
     }
 };
 
-#define FINC_SB() __builtin_amdgcn_sched_barrier(0)
 // Put at the top of a rarely taken, wave-uniform branch body: an opaque volatile asm cannot be speculated, so the
 // compiler keeps a real (scalar) branch instead of if-converting the body into per-step v_cndmask work.
 #define FINC_COLD() asm volatile("; cold path")
@@ -191,8 +169,6 @@ struct BTaps {
 #ifndef FINC_ABLATE_IO   // timing-only bit mask: 1 no loads, 2 no stores, 4 no landing, 8 no x-ring read
 #define FINC_ABLATE_IO 0
 #endif
-template <int I>
-using IC = std::integral_constant<int, I>;
 
 // Diagnostic build only (-DFINC_STAMP, scripts/stamp.sh): s_memtime stamps at the region boundaries of a step,
 // accumulated per (step & 3, segment) for ONE wave over the steady-state steps and left in a buffer of their own.
@@ -228,9 +204,6 @@ extern "C" int finc_debug_hlp_late(unsigned *h) { return (int)hipMemcpyFromSymbo
 #else
 #define FINC_HLP_LATE(k) do { } while (0)
 #endif
-
-constexpr unsigned OFF_INVALID = 0x80000000u;    // voffset beyond any slab: buffer loads return 0, stores are dropped
-constexpr unsigned OFF_BAD_CHANNEL = 0x40000000u; // added to a valid offset it still lands beyond the slab (< 1 GiB)
 
 // -----------------------------------------------------------------------------------------------
 // The kernel.  grid = B*G workgroups of one wavefront.
@@ -308,9 +281,9 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
     const unsigned slab_bytes = (unsigned)CQ * (unsigned)HW * 4u;
     const int bg_in = bg, bg_out = bg;
     const __amdgpu_buffer_rsrc_t rin =
-        __builtin_amdgcn_make_buffer_rsrc((void *)(in + (size_t)bg_in * CQ * HW), 0, (int)slab_bytes, 0x00020000);
+        FINC_SLAB_RSRC(in, (size_t)bg_in * CQ * HW, slab_bytes);
     const __amdgpu_buffer_rsrc_t rout =
-        __builtin_amdgcn_make_buffer_rsrc((void *)(out + (size_t)bg_out * CQ * HW), 0, (int)slab_bytes, 0x00020000);
+        FINC_SLAB_RSRC(out, (size_t)bg_out * CQ * HW, slab_bytes);
     const int D = W - P + 1;                  // FIFO depth (steps between a band's last rows and the next band's first)
     const int fifo_n = D * SS;
     constexpr bool PAIR2 = finc_pair2_form<C>(HLP);   // stage 2 of the paired tile, and the row shifts read from LDS, run in this form
@@ -1113,7 +1086,7 @@ __global__ __launch_bounds__(HLP ? 512 : 64 * NW * NPW) void finc_wave_kernel(co
         // =========================== inverse ===========================
         constexpr int FZ = 0;                          // z-term fragments: j*MT + mt
         constexpr int FT = NKZ * MT;                   // tap fragments: FT + (((a*KW+b)-1)*NK + j)*MT + mt
-        using BT = BTaps<KH, KW>;
+        using BT = RowMajorTaps<KH, KW>;
         constexpr int NCH = BT::count();
         v4f acc[MT];
 #pragma unroll
@@ -1933,7 +1906,7 @@ static InvForm inverse_form(int Cq, int H, int W, int KH, int KW)
     // or, on maps too wide for that, finc_big.hip does
     if (!find_inst(padded_cq(Cq, KH, KW), KH, KW, -1, W))
         return finc_big_wide_bank(Cq, KH, KW) && finc_big_supported(Cq, H, W, KH, KW) ? INV_WIDE : INV_NONE;
-    if ((size_t)Cq * H * W * 4 >= ((size_t)1 << 30)) return INV_NONE;   // buffer-offset range marks (OFF_BAD_CHANNEL)
+    if (!finc_slab_in_range(Cq, H, W, 4)) return INV_NONE;   // buffer-offset range marks (OFF_BAD_CHANNEL)
     return INV_TABLE;
 }
 
@@ -1954,7 +1927,7 @@ static InvPlan inverse_plan(const FincShape &s)
     if (p.form == INV_STREAM) return p;
 
     const long long problems = (long long)s.B * s.G;
-    const int cqp = padded_cq(s.Cq, s.KH, s.KW), P = s.W < 16 ? s.W : 16;
+    const int cqp = padded_cq(s.Cq, s.KH, s.KW), P = finc_bands(s).P;
     const Inst *i = find_inst(cqp, s.KH, s.KW, problems, s.W);
     if (!i) return InvPlan{};                  // (not reached: the row that takes any count takes these)
     if (i->nw == 1 && i->npw == 1 && problems % 2 == 0) {
@@ -2168,9 +2141,9 @@ int finc_mfma_launch(const float *in, const void *packed, float *out, const Finc
         return finc_mfma_launch(in + off, packed, out + off, tail, st, false);
     }
     const wave_fn fn = zpre ? p.inst->fn_zpre : p.fn;
-    const int P = s.W < 16 ? s.W : 16;
-    const int NB = (s.H + P - 1) / P;
-    const int Tend = s.W % 8 == 0 ? (NB * s.W + P - 1 + 7) / 8 * 8 : (NB * s.W + P - 1 + 3) / 4 * 4;  // 32-byte I/O: x8 loop
+    const FincBands b = finc_bands(s);
+    const int P = b.P;
+    const int Tend = s.W % 8 == 0 ? (b.T + 7) / 8 * 8 : (b.T + 3) / 4 * 4;  // 32-byte I/O: x8 loop
     if (int e = finc_ensure_dynamic_lds((const void *)fn, p.lds)) return e;
     if (p.io == 3) {
         if (int e = finc_fault_gate(true, st)) return e;   // (arms the device's fault word if no packing call has: never inside a capture)

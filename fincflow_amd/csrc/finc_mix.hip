@@ -18,11 +18,10 @@
 //     touches them.
 // Latency is hidden by occupancy, not by software pipelining: <= 128 registers, 4 workgroups of 4 waves per CU.
 #include "finc_common.h"
+#include "finc_device.h"
 
 namespace {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef float v2f __attribute__((ext_vector_type(2)));
 
 constexpr unsigned MIX_INVALID = 0x80000000u;
 
@@ -41,7 +40,6 @@ struct PixVec<1> {
 };
 template <>
 struct PixVec<2> {
-    typedef unsigned v2u __attribute__((ext_vector_type(2)));
     static __device__ inline void load(float (&d)[2], __amdgpu_buffer_rsrc_t r, unsigned voff, int soff)
     {
         const v2u v = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
@@ -60,7 +58,6 @@ struct PixVec<2> {
 
 template <>
 struct PixVec<4> {
-    typedef unsigned v4u __attribute__((ext_vector_type(4)));
     static __device__ inline void load(float (&d)[4], __amdgpu_buffer_rsrc_t r, unsigned voff, int soff)
     {
         const v4u v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
@@ -131,9 +128,9 @@ __global__ __launch_bounds__((64 * WGW)) void finc_mix_kernel(const float *__res
     for (int chunk = wave; chunk < total_chunks; chunk += nwaves) {
         const int b = __builtin_amdgcn_readfirstlane(chunk / chunks_per_image), ci = chunk - b * chunks_per_image;   // (the small kernels divide on the VALU: say it again)
         const __amdgpu_buffer_rsrc_t rin =
-            __builtin_amdgcn_make_buffer_rsrc((void *)(in + (size_t)b * C * HW), 0, (int)img_bytes, 0x00020000);
+            FINC_SLAB_RSRC(in, (size_t)b * C * HW, img_bytes);
         const __amdgpu_buffer_rsrc_t rout =
-            __builtin_amdgcn_make_buffer_rsrc((void *)(out + (size_t)b * C * HW), 0, (int)img_bytes, 0x00020000);
+            FINC_SLAB_RSRC(out, (size_t)b * C * HW, img_bytes);
         const int pix = ci * 16 * PX + p * PX;
         const bool ok = pix < HW;              // (PX > 1: HW % PX == 0, so a lane's pixels are valid together)
         const unsigned base = ok ? (unsigned)pix * 4u + rowpart : MIX_INVALID;

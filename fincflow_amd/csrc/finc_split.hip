@@ -43,6 +43,7 @@
 // the launch's words -- so nothing is cleared between launches and a captured launch can be replayed.  Every wait is bounded;
 // one that gives up sets the device's fault word (include/finc.h) exactly like the helper-wave protocol of the wavefront kernel.
 #include "finc_common.h"
+#include "finc_device.h"
 #include "finc_tile.h"
 
 #include <stdlib.h>
@@ -54,67 +55,11 @@
 
 namespace {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-constexpr unsigned OFF_INVALID = 0x80000000u;     // voffset beyond any slab: buffer loads return 0, stores are dropped
-constexpr unsigned OFF_BAD_CHANNEL = 0x40000000u;  // added to a valid offset it still lands beyond the slab (< 1 GiB)
-
-template <int I>
-using IC = std::integral_constant<int, I>;
-#define FINC_SB() __builtin_amdgcn_sched_barrier(0)
-
-// channel held by k-slot q of register j of a solved pixel (finc_mfma.hip chan_d: the D layout of the 16-row tiles, then one
-// register per reduced 4-row block)
-__host__ __device__ inline int chan_d(int MTB, int j, int q)
-{
-    if (j < 4 * MTB) return 16 * (j >> 2) + 4 * q + (j & 3);
-    return 16 * MTB + 4 * (j - 4 * MTB) + q;
-}
-
-__device__ inline float row_shr1(float old, float src)   // lane i of each 16-lane row <- lane i-1; lane 0 keeps `old`
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, src),
-                                                                 0x111, 0xf, 0xf, false));
-}
-
-// the taps B prepares (a + b >= 2), ordered by a + b (then row-major): the taps with a + b == 2 come first -- they are the
-// only ones that need the pixel solved in the step before, so shared out round-robin every B wave gets one of them
-template <int KH, int KW>
-struct BTaps {
-    static constexpr int count()
-    {
-        int n = 0;
-        for (int a = 0; a < KH; ++a)
-            for (int b = 0; b < KW; ++b) n += (a + b >= 2);
-        return n;
-    }
-    static constexpr int find(int i, bool want_a)
-    {
-        for (int sum = 2; sum <= KH + KW - 2; ++sum)
-            for (int a = 0; a < KH; ++a)
-                for (int b = 0; b < KW; ++b)
-                    if (a + b == sum && i-- == 0) return want_a ? a : b;
-        return 0;
-    }
-    static constexpr int a_of(int i) { return find(i, true); }
-    static constexpr int b_of(int i) { return find(i, false); }
-};
-
 #ifdef FINC_BSP_TRACE     // diagnostic build: one record per band-split job (scripts/bsp_trace.py)
 __device__ unsigned long long finc_bsp_trace[1 + 4 * 4096];   // [0] = records; then {job, blockIdx | xcc << 16 | bands << 24, start, end (s_memrealtime)}
 #endif
-#ifdef FINC_SPLIT_STAMP   // diagnostic build: busy cycles (barrier exit -> next barrier arrival) per wave of workgroup 0, summed over the steps
+#ifdef FINC_SPLIT_STAMP   // diagnostic build (finc_device.h FINC_ST_BEGIN / FINC_ST_END): per wave of workgroup 0, summed over the steps
 __device__ unsigned long long finc_split_stamps[16];
-#define FINC_ST_BEGIN() unsigned long long st_b_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_b_)::"memory")
-#define FINC_ST_END()                                                                                                     \
-    do {                                                                                                                  \
-        unsigned long long st_e_;                                                                                         \
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_e_)::"memory");             \
-        st_busy += st_e_ - st_b_;                                                                                         \
-    } while (0)
-#else
-#define FINC_ST_BEGIN() do { } while (0)
-#define FINC_ST_END() do { } while (0)
 #endif
 
 constexpr int XSLOTS = 8;        // x ring: the pixels of the last 8 steps (taps reach back KH + KW - 2 <= 8 steps)
@@ -134,7 +79,7 @@ constexpr int UNROLL = 8;        // steps per iteration of the B waves' loop: tw
 template <int CQP, int KH, int KW, int NBW>
 struct SCfg {
     static constexpr int MTB = CQP / 16, NSM = (CQP % 16) / 4, MT = MTB + NSM, NK = CQP / 4, NTAP = KH * KW;
-    static constexpr int NCH = BTaps<KH, KW>::count();
+    static constexpr int NCH = BySumTaps<KH, KW>::count();
     static constexpr int JS = 4 * (KH - 1);                       // FIFO: floats per slot and k-step (4 k-slots x (KH-1) lanes)
     static constexpr int NPACK = (NK + (NTAP - 1) * NK) * MT + 8 * MT;   // finc_mfma.hip Cfg::NPACK (NW = 1)
     // LDS (bytes): x ring | FIFO | z ring | partial accumulators [parity][B wave][tile][lane] (v4f)
@@ -159,7 +104,7 @@ __global__ __launch_bounds__(64 * (1 + NBW)) void finc_split_kernel(const float 
 {
     using C = SCfg<CQP, KH, KW, NBW>;
     constexpr int MT = C::MT, MTB = C::MTB, NK = C::NK, NCH = C::NCH, JS = C::JS;
-    using BT = BTaps<KH, KW>;
+    using BT = BySumTaps<KH, KW>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     char *const ldsb = reinterpret_cast<char *>(lds);
     const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // 0: A, 1..NBW: B
@@ -221,8 +166,8 @@ __global__ __launch_bounds__(64 * (1 + NBW)) void finc_split_kernel(const float 
     const bool fh = (o & FINC_FLIP_H) != 0, fw = (o & FINC_FLIP_W) != 0;
     const int HW = H * W;
     const unsigned slab_bytes = (unsigned)CQ * (unsigned)HW * 4u;
-    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void *)(in + (size_t)bg * CQ * HW), 0, (int)slab_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc((void *)(out + (size_t)bg * CQ * HW), 0, (int)slab_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rin = FINC_SLAB_RSRC(in, (size_t)bg * CQ * HW, slab_bytes);
+    const __amdgpu_buffer_rsrc_t rout = FINC_SLAB_RSRC(out, (size_t)bg * CQ * HW, slab_bytes);
 
     for (int i = threadIdx.x; i < C::LDS_BYTES / 4; i += 64 * (1 + NBW)) lds[i] = 0.f;
 
@@ -304,7 +249,7 @@ __global__ __launch_bounds__(64 * (1 + NBW)) void finc_split_kernel(const float 
 #pragma unroll
             for (int j = 0; j < NK; ++j) fv0[j] = ld(pop_r + fp0 * (JS * 4) + j * JSTRIDE);
 #pragma unroll
-            for (int j = 0; j < NK; ++j) q1[j] = row_shr1(fv0[j], 0.f);
+            for (int j = 0; j < NK; ++j) q1[j] = row_shr<1>(fv0[j], 0.f);
         }
         __syncthreads();                       // (iteration t = -1: the B waves prepare step 0)
         unsigned long long st_busy = 0;
@@ -387,7 +332,7 @@ __global__ __launch_bounds__(64 * (1 + NBW)) void finc_split_kernel(const float 
                     for (int j = 0; j < NK; ++j) fv[j] = ld(pop_r + fpop * (JS * 4) + j * JSTRIDE);
                 }
 #pragma unroll
-                for (int j = 0; j < NK; ++j) q1[j] = row_shr1(fv[j], xpk[j]);
+                for (int j = 0; j < NK; ++j) q1[j] = row_shr<1>(fv[j], xpk[j]);
             }
 #pragma unroll
             for (int j = 0; j < NK; ++j) q0[j] = xpk[j];
@@ -587,7 +532,7 @@ __global__ __launch_bounds__(64 * (1 + NBW)) void finc_split_kernel(const float 
     // progress words: one per (problem, image band, B wave) behind the claim words = that wave's store windows complete, counted from
     // the start of THAT band
     const int nwords = BSP ? 2 + nprob * nwg + nprob * nwg * NBW : 0;
-    const __amdgpu_buffer_rsrc_t rsync = __builtin_amdgcn_make_buffer_rsrc((void *)sync, 0, nwords * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsync = FINC_SLAB_RSRC(sync, 0, (unsigned)(nwords * 4));
     auto band_word = [&](int band) { return (unsigned)(2 + nprob * nwg + (bg * nwg + band) * NBW + bi) * 4u; };
     unsigned its_flag = BSP && wg >= 1 ? band_word(wg - 1) : 0u;
     unsigned seen_raw = 0;                     // the progress word as last fetched (asynchronously, once per window)
@@ -980,8 +925,7 @@ bool bsp_off()
 // per band exceeds what chaining costs)
 int bsp_nwg(const SInst &i, const FincShape &s)
 {
-    const int P = s.W < 16 ? s.W : 16;
-    const int NB = (s.H + P - 1) / P;
+    const int NB = finc_bands(s).NB;
     const long long problems = (long long)s.B * s.G;
     if (bsp_off() || i.kh < 2 || NB < 2 || s.W < 64 || 2 * problems > device_cus()) return 1;
     if (2 + problems * NB * (1 + i.nbw) > BSP_SLOT_WORDS) return 1;          // ticket, done, one claim word and NBW progress words per band
@@ -1086,7 +1030,8 @@ FincSplitPlan finc_split_plan(const FincShape &s)
     FincSplitPlan p;
     const long long problems = (long long)s.B * s.G;
     const SInst *i = find_sinst(s.Cq, s.KH, s.KW);
-    const int P = s.W < 16 ? s.W : 16;
+    const FincBands bands = finc_bands(s);
+    const int P = bands.P;
     if (problems > split_max_problems()) {
         // two problems per compute unit: only the short-step form, which still beats the wavefront kernel's table (its workgroup is
         // 45 KB of LDS and five waves) -- C = 48, 32x32, B = 128: 40.3 against 57.3 us; the maps of the CIFAR stack at its sampling
@@ -1099,7 +1044,7 @@ FincSplitPlan finc_split_plan(const FincShape &s)
         // 80 us).  The short-step form has no FIFO-width limit; this kernel's FIFO of a k-step must fit.
         p.chain = finc_chain_takes(s) && !(i && i->cqp == 16 && fifo_fits(*i, s.W, P) && bsp_nwg(*i, s) > 1);
         p.takes = p.chain || (i && s.H >= 1 && s.W >= 1 && P >= s.KH - 1 && s.W % 4 == 0 &&   // (16-byte pieces)
-                              (size_t)s.Cq * s.H * s.W * 4 < ((size_t)1 << 30) &&             // buffer-offset range marks (OFF_BAD_CHANNEL)
+                              finc_slab_in_range(s.Cq, s.H, s.W, 4) &&                         // buffer-offset range marks (OFF_BAD_CHANNEL)
                               fifo_fits(*i, s.W, P));
     }
     if (!p.takes) return p;
@@ -1107,7 +1052,7 @@ FincSplitPlan finc_split_plan(const FincShape &s)
         (void)finc_chain_info(s, &p.waves, &p.lds, &p.steps);
         return p;
     }
-    const int NB = (s.H + P - 1) / P;
+    const int NB = bands.NB;
     p.row = (int)(i - g_sinsts);
     p.nwg = bsp_nwg(*i, s);
     p.waves = 1 + i->nbw;
@@ -1121,8 +1066,7 @@ int finc_split_launch(const float *in, const void *packed, float *out, const Fin
     if (p.chain) return finc_chain_launch(in, packed, out, s, st);   // the small banks' short-step form (finc_chain.hip)
     if (p.row < 0) return FINC_ERR_UNSUPPORTED;
     const SInst *i = &g_sinsts[p.row];
-    const int P = s.W < 16 ? s.W : 16;
-    const int NB = (s.H + P - 1) / P;
+    const int P = finc_bands(s).P, NB = finc_bands(s).NB;
     const size_t lds = (size_t)i->lds_bytes;
     int nwg = p.nwg;
     unsigned *slot = nullptr;

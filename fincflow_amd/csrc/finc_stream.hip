@@ -22,10 +22,10 @@
 // channels are one-wave problems (NW = 1, MT = 1..3: four problems per compute unit, one per SIMD), wider ones take a
 // workgroup of four waves (MT = 1..4 tiles each: 64, 128, 192, 256 padded channels).
 #include "finc_common.h"
+#include "finc_device.h"
 
 namespace {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 // FINC_STREAM_ABLATE (timing-only builds, wrong results): 1 = the bank is not re-read (the fragments of the first units stay),
 // 2 = no MFMAs, 4 = no operand loads (z / halo rows), 8 = every wave starts the bank stream at block 0, 16 = no stores;
@@ -590,6 +590,8 @@ bool finc_stream_supported(int Cq, int H, int W, int KH, int KW, bool inverse)
     if (!finc_stream_bank_ok(Cq, KH, KW) || H < 1 || W < 1) return false;
     const Geo q = make_geo(Cq, W, KH, KW, inverse);
     if (q.lds > 160 * 1024) return false;
+    // NOT finc_slab_in_range: this bound counts ELEMENTS of a slab, not bytes (so it admits slabs of up to 4 GiB).  Kept exactly as it
+    // has been; whether it is the intended bound is an open question
     if ((size_t)Cq * H * W >= ((size_t)1 << 30)) return false;
     if ((long long)((H + 15) / 16) * q.Wp + 64 >= (1LL << 30)) return false;
     return true;

@@ -8,13 +8,22 @@
 #pragma once
 #include <stddef.h>
 
-typedef float finc_v4f __attribute__((ext_vector_type(4)));
-typedef unsigned finc_v2u __attribute__((ext_vector_type(2)));
+#include "finc_device.h"
+
+// Channel held by k-slot q of k-step (= register) j of an operand made from solved pixels: registers of the 16-row tiles first (D
+// layout: reg r of tile mt, lane row q = channel 16mt + 4q + r), then one register per 4-row block (channel 16*MTB + 4sb + q after
+// the reduce-transpose of finc_block_reduce).  The packer, the compute waves and the store side of every inverse that runs on the
+// wavefront kernel's packed bank (finc_mfma.hip, finc_split.hip, finc_chain.hip) read this one definition.
+__host__ __device__ constexpr int chan_d(int MTB, int j, int q)
+{
+    if (j < 4 * MTB) return 16 * (j >> 2) + 4 * q + (j & 3);
+    return 16 * MTB + 4 * (j - 4 * MTB) + q;
+}
 
 // one accumulator update: tile index mt < MTB is a 16-row tile, otherwise a 4-row block; `a` = the matching fragment
 // (16-row tile: lane (q,i) = W[16mt+i][k-slot q]; 4-row block: lane (q,i) = W[16*MTB + 4sb + (i&3)][k-slot q])
 template <int MTB>
-__device__ inline void finc_mma(finc_v4f &acc, int mt, float a, float b)
+__device__ inline void finc_mma(v4f &acc, int mt, float a, float b)
 {
     if (mt < MTB) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
     else acc = __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, acc, 0, 0, 0);
@@ -25,7 +34,7 @@ __device__ inline void finc_mma(finc_v4f &acc, int mt, float a, float b)
 // of 4 (= the 4 pixel quads of one k-slot) and every block of a group takes A from the group's block ABID.  So lane
 // (q, 4a + i) of a packed register holds fragment a's value for (row i, k-slot q), and ABID = a selects it: the 4-row
 // blocks of a filter bank cost a quarter of the registers (c3: 108 -> 27), same instruction, same rate.
-__device__ inline void finc_mma_small(finc_v4f &acc, float a4, float b, int abid)
+__device__ inline void finc_mma_small(v4f &acc, float a4, float b, int abid)
 {
     switch (abid & 3) {   // (the builtin wants literals; the switch folds once the loops are unrolled)
     case 0: acc = __builtin_amdgcn_mfma_f32_4x4x1f32(a4, b, acc, 2, 0, 0); break;
@@ -38,21 +47,21 @@ __device__ inline void finc_mma_small(finc_v4f &acc, float a4, float b, int abid
 // A 4-row block's register i holds, in lane row q', the k-slot-q' PARTIAL sum of channel base+i.  Sum over the 4 lane
 // rows and leave channel base+q in lane row q: a 4x4 transpose-reduce (rows two apart by v_permlane32_swap + add,
 // rows one apart by v_permlane16_swap + add; 6 VALU).
-__device__ inline float finc_block_reduce(const finc_v4f &acc)
+__device__ inline float finc_block_reduce(const v4f &acc)
 {
     // NB: __builtin_bit_cast applied directly to an ext-vector ELEMENT silently reads element 0 with this compiler;
     // always go through scalar temporaries.
     const float r0 = acc.x, r1 = acc.y, r2 = acc.z, r3 = acc.w;
     // v_permlane32_swap(v, s): new v = [v.lanes 0-31, s.lanes 0-31], new s = [v.lanes 32-63, s.lanes 32-63]
-    const finc_v2u a = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, r0), __builtin_bit_cast(unsigned, r2),
+    const v2u a = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, r0), __builtin_bit_cast(unsigned, r2),
                                                         false, false);
-    const finc_v2u b = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, r1), __builtin_bit_cast(unsigned, r3),
+    const v2u b = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, r1), __builtin_bit_cast(unsigned, r3),
                                                         false, false);
     const unsigned a0 = a.x, a1 = a.y, b0 = b.x, b1 = b.y;
     const float s02 = __builtin_bit_cast(float, a0) + __builtin_bit_cast(float, a1); // rows 0,1: r0 ; rows 2,3: r2
     const float s13 = __builtin_bit_cast(float, b0) + __builtin_bit_cast(float, b1); // rows 0,1: r1 ; rows 2,3: r3
     // v_permlane16_swap(v, s): new v = [v.row0, s.row0, v.row2, s.row2], new s = [v.row1, s.row1, v.row3, s.row3]
-    const finc_v2u c = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, s02), __builtin_bit_cast(unsigned, s13),
+    const v2u c = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, s02), __builtin_bit_cast(unsigned, s13),
                                                         false, false);
     const unsigned c0 = c.x, c1 = c.y;
     return __builtin_bit_cast(float, c0) + __builtin_bit_cast(float, c1);
@@ -142,3 +151,49 @@ __host__ __device__ constexpr int finc_ls_src(int KH, int a, int D, int lane, in
 __host__ __device__ constexpr int finc_ls_step(int KH, bool fifo) { return fifo ? finc_ls_js(KH) : 64; }
 __host__ __device__ constexpr int finc_ls_rewind8(bool fifo) { return fifo ? 0 : FINC_LS_XBLOCK; }
 __host__ __device__ constexpr int finc_ls_rewindR(int KH, int D, bool fifo) { return fifo ? (D - 1) * finc_ls_js(KH) : 0; }
+
+// Strip-piece map of the grad-weight kernels (finc_gradw.hip: staged, tiled, Winograd, Winograd tile-pair).  A wave stages a strip
+// of 4*np columns of `rows` channel rows (channels c0 .. c0 + rows - 1 of a slab [CQ][H][W]) in an LDS tile [channel][pitch floats],
+// one 16-byte piece per load slot t = 64 * i + lane:
+//   slots t < np * rows            row piece k = t % np of channel row c = t / np: memory columns ms + 4k .. ms + 4k + 3;
+//   then, with `halo`, `rows` more  the halo piece of channel row t - np * rows: memory columns hm .. hm + 3, the four columns to the
+//                                  left of the strip in canonical order -- hm = ms - 4, or mirrored hm = ms + 4 * np;
+//   every slot behind those        nothing to load: lanes behind the bank park their piece in the scratch piece `scratch`.
+// The slot's byte offset in the slab (row offset not included: the kernels add (h * W) * 4 as the load's scalar offset) is that of
+// (channel c0 + c, column) -- or OFF_BAD_CHANNEL (finc_device.h) when the channel lies behind the bank (>= CQ: the bank is padded, or
+// the 16-channel window of a tile pair reaches past it) or the column outside the row.  W % 4 == 0 and ms % 4 == 0: a piece is inside
+// the row or outside, never astride -- outside are the pieces of the last strip of a row whose width is no multiple of the strip's
+// (a strip wider than the whole row included) and the halo piece of the first strip.
+// The landing address (floats) keeps memory order: row piece k at lead + 4k with the halo piece in front of it at 0 (lead = 4 for an
+// x tile, 0 for a gz tile, which has no halo) -- canonical column c of the strip at tile column lead + c -- or, mirrored, row piece k
+// at 4k and the halo piece BEHIND the row pieces at 4 * np: canonical column c at tile column 4 * np - 1 - c, and the columns left of
+// the strip at 4 * np upwards.  The kernels' read maps (xrd, grd) are written against exactly this.
+// Known sibling: the staged forward of finc_conv.hip has the same loop without the column test (its launch rule differs).
+// A macro that the kernels expand in place, and a function of it for the host test: a call in the kernels' set-up, a forced inline
+// included, moved registers and instructions of the whole kernel (profiles/device_prelude/isa_identity.txt), the expansion moves none.
+#define FINC_STRIP_PIECE(voff, lds, t, np, rows, c0, CQ, HW, W, ms, hm, mirrored, pitch, lead, scratch, halo)                    \
+    {                                                                                                                            \
+        (voff) = OFF_BAD_CHANNEL;                                                                                                \
+        (lds) = (scratch);                                                                                                       \
+        if ((t) < (np) * (rows)) {                                                                                               \
+            const int c_ = (t) / (np), k_ = (t) % (np);                                                                          \
+            if ((c0) + c_ < (CQ) && (ms) + 4 * k_ >= 0 && (ms) + 4 * k_ < (W))                                                   \
+                (voff) = (unsigned)((c0) + c_) * (HW) * 4u + (unsigned)((ms) + 4 * k_) * 4u;                                     \
+            (lds) = c_ * (pitch) + ((mirrored) ? 0 : (lead)) + 4 * k_;                                                           \
+        } else if ((halo) && (t) < ((np) + 1) * (rows)) {                                                                        \
+            const int c_ = (t) - (np) * (rows);                                                                                  \
+            if ((c0) + c_ < (CQ) && (hm) >= 0 && (hm) < (W)) (voff) = (unsigned)((c0) + c_) * (HW) * 4u + (unsigned)(hm) * 4u;   \
+            (lds) = c_ * (pitch) + ((mirrored) ? 4 * (np) : 0);                                                                  \
+        }                                                                                                                        \
+    }
+struct FincStripPiece {
+    unsigned voff;   // byte offset in the slab, or OFF_BAD_CHANNEL
+    int lds;         // landing address in the tile, floats
+};
+__host__ __device__ constexpr FincStripPiece finc_strip_piece(int t, int np, int rows, int c0, int CQ, int HW, int W, int ms, int hm,
+                                                              bool mirrored, int pitch, int lead, int scratch, bool halo)
+{
+    FincStripPiece p{};
+    FINC_STRIP_PIECE(p.voff, p.lds, t, np, rows, c0, CQ, HW, W, ms, hm, mirrored, pitch, lead, scratch, halo)
+    return p;
+}

@@ -23,6 +23,7 @@
 // leaves as one dwordx2 per output register (16 lanes = 128 contiguous bytes).  The transformed rows h, h-1, h-2 stay in
 // registers (3 rotating slots); the bank -- 3 x 4 x NK x MT fragments -- is register-resident; no LDS.
 #include "finc_common.h"
+#include "finc_device.h"
 #include "finc_tile.h"
 
 #include <stdlib.h>
@@ -34,16 +35,8 @@
 
 namespace {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef unsigned v2u __attribute__((ext_vector_type(2)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
 
-constexpr unsigned OFF_INVALID = 0x80000000u;
-constexpr unsigned OFF_BAD_CHANNEL = 0x40000000u;
 
-template <int I>
-using IC = std::integral_constant<int, I>;
-#define FINC_SB() __builtin_amdgcn_sched_barrier(0)
 #define FINC_SB4() do { if constexpr (!(FINC_WINO_ABLATE & 256)) __builtin_amdgcn_sched_barrier(0); } while (0)   // (256: F(4,3) without its scheduling barriers)
 #ifndef FINC_WINO_ABLATE   // timing-only bits (results wrong): 1 no loads, 2 no stores, 4 no MFMAs of the row taps 1 and 2, 8 no LDS slots
                            // (F(4,3): 8 no LDS reads, 16 no output transform, 32 no input transform, 64 no LDS writes)
@@ -282,8 +275,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void fi
     const bool fh = (o & FINC_FLIP_H) != 0, fw = (o & FINC_FLIP_W) != 0;
     const int HW = H * W;
     const unsigned slab_bytes = (unsigned)CQ * (unsigned)HW * 4u;
-    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void *)(in + (size_t)bg * CQ * HW), 0, (int)slab_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc((void *)(out + (size_t)bg * CQ * HW), 0, (int)slab_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rin = FINC_SLAB_RSRC(in, (size_t)bg * CQ * HW, slab_bytes);
+    const __amdgpu_buffer_rsrc_t rout = FINC_SLAB_RSRC(out, (size_t)bg * CQ * HW, slab_bytes);
     if (strip == 0) {
         if (fw) wino_walk<CQP, true, true>(rin, rout, packed, vlds, g, CQ, H, W, strip, RC, fh);
         else wino_walk<CQP, false, true>(rin, rout, packed, vlds, g, CQ, H, W, strip, RC, fh);
@@ -319,7 +312,6 @@ __device__ __forceinline__ void wino4_walk(const __amdgpu_buffer_rsrc_t rin, con
     using C = WCfg<CQP, 4>;
     constexpr int MT = C::MT, MTB = C::MTB, NSM = C::NSM, NK = C::NK, NF = C::NF, NFRAG = C::NFRAG;
     constexpr int NB = CQP >= 20 ? 1 : 2;                 // rows of loads in flight (see below)
-    typedef float v2f __attribute__((ext_vector_type(2)));
     const int lane = threadIdx.x & 63;
     const int q = lane >> 4, p = lane & 15;
     const int HW = H * W;
@@ -571,8 +563,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     const bool fh = (o & FINC_FLIP_H) != 0, fw = (o & FINC_FLIP_W) != 0;
     const int HW = H * W;
     const unsigned slab_bytes = (unsigned)CQ * (unsigned)HW * 4u;
-    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void *)(in + (size_t)bg * CQ * HW), 0, (int)slab_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc((void *)(out + (size_t)bg * CQ * HW), 0, (int)slab_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rin = FINC_SLAB_RSRC(in, (size_t)bg * CQ * HW, slab_bytes);
+    const __amdgpu_buffer_rsrc_t rout = FINC_SLAB_RSRC(out, (size_t)bg * CQ * HW, slab_bytes);
     if (fw) wino4_walk<CQP, true>(rin, rout, packed, vlds, g, CQ, H, W, strip, RC, fh);
     else wino4_walk<CQP, false>(rin, rout, packed, vlds, g, CQ, H, W, strip, RC, fh);
 }
@@ -593,8 +585,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     const bool fh = (o & FINC_FLIP_H) != 0, fw = (o & FINC_FLIP_W) != 0;
     const int HW = H * W;
     const unsigned slab_bytes = (unsigned)CQ * (unsigned)HW * 4u;
-    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void *)(in + (size_t)bg * CQ * HW), 0, (int)slab_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc((void *)(out + (size_t)bg * CQ * HW), 0, (int)slab_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rin = FINC_SLAB_RSRC(in, (size_t)bg * CQ * HW, slab_bytes);
+    const __amdgpu_buffer_rsrc_t rout = FINC_SLAB_RSRC(out, (size_t)bg * CQ * HW, slab_bytes);
     if (fw) wino4_walk<CQP, true>(rin, rout, packed, vlds, g, CQ, H, W, strip, RC, fh);
     else wino4_walk<CQP, false>(rin, rout, packed, vlds, g, CQ, H, W, strip, RC, fh);
 }
@@ -694,7 +686,7 @@ size_t finc_wino_packed_bytes(int G, int Cq, int KH, int KW)
 bool finc_wino_takes(const FincShape &s, int align)
 {
     if (s.KH != 3 || s.KW != 3 || s.W % 4 != 0 || s.W < 4 || finc_no_wino() || !find_winst(s.Cq)) return false;
-    if ((size_t)s.Cq * s.H * s.W * 4 >= ((size_t)1 << 30)) return false;
+    if (!finc_slab_in_range(s.Cq, s.H, s.W, 4)) return false;
     return align >= 16;                                                    // a row arrives as 16-byte windows
 }
 

@@ -15,6 +15,7 @@
 //     frequency 1 enters all four outputs with weight +1, so a folded shift rides in as its start value.
 // LDS: 4 x NK x 64 x 24 bytes (98 KB at Cq = 64) + the shift: one workgroup per compute unit, one wave per SIMD.
 #include "finc_common.h"
+#include "finc_device.h"
 #include "finc_tile.h"
 
 #include <stdlib.h>
@@ -24,17 +25,8 @@
 
 namespace {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef float v2f __attribute__((ext_vector_type(2)));
-typedef unsigned v2u __attribute__((ext_vector_type(2)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
 
-constexpr unsigned OFF_INVALID = 0x80000000u;
-constexpr unsigned OFF_BAD_CHANNEL = 0x40000000u;
 
-template <int I>
-using IC = std::integral_constant<int, I>;
-#define FINC_SB() __builtin_amdgcn_sched_barrier(0)
 
 template <int CQP>
 struct W4mCfg {
@@ -205,8 +197,8 @@ __global__ __launch_bounds__(64 * (CQP / 16)) __attribute__((amdgpu_waves_per_eu
     const bool fh = (o & FINC_FLIP_H) != 0, fw = (o & FINC_FLIP_W) != 0;
     const int HW = H * W;
     const unsigned slab_bytes = (unsigned)CQ * (unsigned)HW * 4u;
-    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void *)(in + (size_t)bg * CQ * HW), 0, (int)slab_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc((void *)(out + (size_t)bg * CQ * HW), 0, (int)slab_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rin = FINC_SLAB_RSRC(in, (size_t)bg * CQ * HW, slab_bytes);
+    const __amdgpu_buffer_rsrc_t rout = FINC_SLAB_RSRC(out, (size_t)bg * CQ * HW, slab_bytes);
     if (fw) wino4m_walk<CQP, true>(rin, rout, packed, lds4m, g, CQ, H, W, strip, RC, fh);
     else wino4m_walk<CQP, false>(rin, rout, packed, lds4m, g, CQ, H, W, strip, RC, fh);
 }
@@ -248,7 +240,7 @@ bool finc_wino4m_takes(const FincShape &s, int align)
     if (s.KH != 3 || s.KW != 3 || !find_w4m(s.Cq) || finc_wino_disabled()) return false;
     if (s.W % 4 != 0 || s.W < 4) return false;
     if (align < 16) return false;                                          // a row arrives as 16-byte windows
-    if ((size_t)s.Cq * s.H * s.W * 4 >= ((size_t)1 << 30)) return false;
+    if (!finc_slab_in_range(s.Cq, s.H, s.W, 4)) return false;
     // strips of 64 columns: at least three quarters of what they cover is image, and enough workgroups for the chip
     const int NS = (s.W + 63) / 64;
     return 4 * s.W >= 3 * NS * 64 && (long long)s.B * s.G * NS * (s.H >= 16 ? s.H / 8 : 1) >= 32;

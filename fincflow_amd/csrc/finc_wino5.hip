@@ -27,6 +27,7 @@
 // output register (16 lanes = 128 contiguous bytes).  The transformed rows h-1 .. h-4 wait in LDS (a lane reads back only
 // what it wrote: no barrier for them).
 #include "finc_common.h"
+#include "finc_device.h"
 #include "finc_tile.h"
 
 #include <stdlib.h>
@@ -36,15 +37,8 @@
 
 namespace {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef unsigned v2u __attribute__((ext_vector_type(2)));
 
-constexpr unsigned OFF_INVALID = 0x80000000u;
-constexpr unsigned OFF_BAD_CHANNEL = 0x40000000u;
 
-template <int I>
-using IC = std::integral_constant<int, I>;
-#define FINC_SB() __builtin_amdgcn_sched_barrier(0)
 
 template <int CQP, int NW>
 struct W5Cfg {
@@ -321,8 +315,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
     const bool fh = (o & FINC_FLIP_H) != 0, fw = (o & FINC_FLIP_W) != 0;
     const int HW = H * W;
     const unsigned slab_bytes = (unsigned)CQ * (unsigned)HW * 4u;
-    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void *)(in + (size_t)bg * CQ * HW), 0, (int)slab_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc((void *)(out + (size_t)bg * CQ * HW), 0, (int)slab_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rin = FINC_SLAB_RSRC(in, (size_t)bg * CQ * HW, slab_bytes);
+    const __amdgpu_buffer_rsrc_t rout = FINC_SLAB_RSRC(out, (size_t)bg * CQ * HW, slab_bytes);
     if (fw) wino5_walk<CQP, NW, true>(rin, rout, packed, lds5, g, CQ, H, W, strip, RC, fh);
     else wino5_walk<CQP, NW, false>(rin, rout, packed, lds5, g, CQ, H, W, strip, RC, fh);
 }
@@ -412,7 +406,7 @@ bool finc_wino5_takes(const FincShape &s, int align)
     if (s.KH != 5 || s.KW != 5 || no_wino5() || !find_w5(s.Cq)) return false;
     if (s.W % 2 != 0 || s.W < 2) return false;                             // pairs
     if (align < 8) return false;                                           // 8-byte pieces
-    return (size_t)s.Cq * s.H * s.W * 4 < ((size_t)1 << 30);
+    return finc_slab_in_range(s.Cq, s.H, s.W, 4);
 }
 
 int finc_wino5_pack(const float *wc, void *packed, int G, int Cq, bool transpose, hipStream_t st, const float *scale, const float *shift)

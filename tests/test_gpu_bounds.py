@@ -456,6 +456,9 @@ CONV_CASES = {
     "ksplit_padded_w20": ((3, 4, 44, 10, 20, 3, 3), 0, "strip", "tiled", 2),
     "ksplit_wino_tiled_gradw": ((3, 4, 48, 10, 36, 3, 3), 0, "strip", "winograd_tiled", 2),
     "gradw_dword_c3_bank": ((3, 4, 24, 9, 18, 3, 3), 0, "strip", "dword", 1),
+    # the staged grad-weight kernel with all three of: a strip wider than the row (pieces past its end, mirrored before its start), a
+    # mirrored group, and Cq below the padded bank (tiled, winograd, winograd_tiled have such cases above: *_padded_w20, *_w24)
+    "gradw_staged_padded_w4": ((2, 2, 1, 5, 4, 3, 3), 0, "winograd", "staged", 1),
     # a big bank on a width with W % 4 != 0: the 8-wave K-split row of the strip kernel on dword loads, the direct grad-weight
     "big_strip_odd_width": ((3, 1, 65, 9, 18, 3, 3), 0, "strip", "direct", 8),
     # a filter no MFMA kernel takes (a side of 8 .. 15 is legal): the generic forward / grad-input / grad-weight kernels, no packed

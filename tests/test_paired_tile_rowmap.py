@@ -28,6 +28,12 @@ SHIM = r"""
 #include "finc_tile.h"
 int main(int argc, char **argv)
 {
+    if (argc == 2) {                              // "chan": chan_d over every padded bank of up to 4 tiles + 3 blocks
+        for (int cqp = 4; cqp <= 76; cqp += 4)
+            for (int j = 0; j < cqp / 4; ++j)
+                for (int q = 0; q < 4; ++q) printf("C %d %d %d %d\n", cqp, j, q, chan_d(cqp / 16, j, q));
+        return 0;
+    }
     const int cqp = atoi(argv[1]), G = atoi(argv[2]), npack = atoi(argv[3]);
     const int MTB = cqp / 16, NKD = cqp / 4, npair = 2 * NKD;
     printf("B %d\n", finc_pair_bank(cqp, 3, 3) ? 1 : 0);
@@ -62,6 +68,11 @@ def shim(tmp_path_factory):
         elems = {(int(r[1]), int(r[2])): tuple(int(v) for v in r[3:]) for r in rows if r[0] == "E"}
         offs = {(int(r[1]), int(r[2])): int(r[3]) for r in rows if r[0] == "O"}
         return bank, elems, offs
+
+    def chan():
+        out = subprocess.run([str(exe), "chan"], check=True, capture_output=True, text=True, timeout=60).stdout
+        return {tuple(int(v) for v in l.split()[1:4]): int(l.split()[4]) for l in out.splitlines()}
+    run.chan = chan
     return run
 
 
@@ -81,6 +92,20 @@ def test_paired_fragment_rows_match_the_row_map(cqp, shim):
                 # registers 0,1 of the product are operand registers 4*MTB + r of the solved pixel, k-slot = lane row qq
                 if r < 2:
                     assert want[0] == chan_d(MTB, 4 * MTB + r, qq)
+
+
+def test_chan_d_matches_the_wave_model_and_is_a_bijection(shim):
+    """finc_tile.h's chan_d -- the one definition the packer, the compute waves and the store side of finc_mfma.hip, finc_split.hip and
+    finc_chain.hip read -- against its Python twin: MTB = 0 .. 4 tiles, 0 .. 3 blocks behind them, every k-step and k-slot; and over
+    those (j, q) it names every channel of the padded bank exactly once."""
+    got = shim.chan()
+    banks = [16 * mtb + r for mtb in range(5) for r in (0, 4, 8, 12) if 16 * mtb + r]
+    assert sorted({c for c, _, _ in got}) == banks
+    for cqp in banks:
+        MTB, NK = cqp // 16, cqp // 4
+        vals = [got[(cqp, j, q)] for j in range(NK) for q in range(4)]
+        assert vals == [chan_d(MTB, j, q) for j in range(NK) for q in range(4)], cqp
+        assert sorted(vals) == list(range(cqp)), cqp
 
 
 def test_banks_that_pair(shim):
