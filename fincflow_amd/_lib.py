@@ -54,6 +54,8 @@ SYMBOLS = [
     "finc_debug_pixel_plan",
     "finc_spline_supported_f32", "finc_spline_workspace_bytes", "finc_spline_f32", "finc_spline_backward_f32",
     "finc_spline_reverse_backward_f32",
+    "finc_activation_supported_f32", "finc_debug_activation_trips", "finc_activation_workspace_bytes", "finc_activation_f32",
+    "finc_activation_backward_f32",
 ]
 
 #: the ABI version this binding is written against (include/finc.h: finc_version)
@@ -103,6 +105,9 @@ PIXEL_PLAN_ABI_VERSION = 119
 #: the version that added the rational-quadratic spline (finc_spline_f32, finc_spline_backward_f32,
 #: finc_spline_reverse_backward_f32) and its family of the plan query: what glow.SplineActivation launches
 SPLINE_ABI_VERSION = 120
+#: the version that added the smooth invertible activations (finc_activation_f32, finc_activation_backward_f32) and their family of
+#: the plan query: what glow.SmoothLeakyRelu, LeakyRelu, LearnableLeakyRelu and SmoothTanh launch
+ACTIVATION_ABI_VERSION = 121
 
 _lib = None
 
@@ -197,6 +202,10 @@ def lib():
         raise FincError(f"{LIB_PATH} reports finc_version() = {have}, the rational-quadratic spline's entry points "
                         f"(finc_spline_f32, finc_spline_backward_f32, finc_spline_reverse_backward_f32) came with "
                         f"{SPLINE_ABI_VERSION}: rebuild it "
+                        "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
+    if have < ACTIVATION_ABI_VERSION:
+        raise FincError(f"{LIB_PATH} reports finc_version() = {have}, the smooth invertible activations' entry points "
+                        f"(finc_activation_f32, finc_activation_backward_f32) came with {ACTIVATION_ABI_VERSION}: rebuild it "
                         "(`make -C fincflow_amd/csrc`)" + (" or unset FINCFLOW_LIB" if LIB_OVERRIDE else ""))
     L.finc_build_flags.restype = u
     L.finc_clear_fault.restype = i
@@ -313,6 +322,12 @@ def lib():
     L.finc_spline_f32.argtypes = [vp, vp, i, i, fl, i, vp, vp, i, i, i, vp, sz, vp]
     L.finc_spline_backward_f32.argtypes = [vp, vp, vp, vp, i, i, fl, vp, vp, i, i, i, vp, sz, vp]
     L.finc_spline_reverse_backward_f32.argtypes = L.finc_spline_backward_f32.argtypes
+    L.finc_activation_supported_f32.argtypes = [i]
+    L.finc_debug_activation_trips.argtypes = [i]
+    L.finc_activation_workspace_bytes.restype = sz
+    L.finc_activation_workspace_bytes.argtypes = [i, i, i]
+    L.finc_activation_f32.argtypes = [i, fl, fl, vp, i, vp, vp, vp, i, i, i, vp, sz, vp]
+    L.finc_activation_backward_f32.argtypes = [i, fl, fl, vp, i, vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp]
     for name in SYMBOLS:
         getattr(L, name)  # AttributeError here = header and library out of sync
     _lib = L
@@ -392,7 +407,7 @@ def conv_plan(B, G, Cq, H, W, KH, KW, align=16):
 #: finc_debug_pixel_plan's launch rules and, per rule, the entry-point families (include/finc.h FincPixelRule / FincPixelFamily)
 PIXEL_RULES = {"rows": 0, "parts": 1, "mix": 2}
 PIXEL_FAMILIES = {"rows": {"channel_rows": 0, "lead": 1, "negate": 2},
-                  "parts": {"transform": 0, "coupling_grad": 1, "actnorm_grad": 2, "spline": 4},
+                  "parts": {"transform": 0, "coupling_grad": 1, "actnorm_grad": 2, "spline": 4, "activation": 5},
                   "mix": {"mix": 0}}
 
 
@@ -402,7 +417,8 @@ def pixel_plan(rule, family, B, C, HW, align=16, elem_bytes=4, groups=0):
     `elem_bytes` 2 is finc_bias_relu_bf16 --, "lead": the grouped lead product with `groups` = G, "negate": finc_negate_f32 on
     B * C * HW elements), "parts" ((outer, part) workgroups; "transform": outer = B, "coupling_grad": outer = C / 2, "actnorm_grad":
     outer = C; `elem_bytes` 2: a bf16 raw; "spline": every spline call, outer = ceil(C * HW / 256) blocks of positions, items =
-    256 * B, io 1 whatever the alignment), "mix" (family "mix").  Returns `io` (elements per thread item; the mix: pixels per lane),
+    256 * B, io 1 whatever the alignment; "activation": every call of the smooth invertible activations, outer = B, items = C * HW / io
+    with io 4 when C * HW % 4 == 0 at `align` 16), "mix" (family "mix").  Returns `io` (elements per thread item; the mix: pixels per lane),
     `threads` per workgroup, `grid`, `parts` (P or Q; the mix: waves of the grid; rows: 0), `items` (of one outer unit; the mix:
     chunks), `trips` of the busiest thread or wave, `outer`, `lds` bytes.  None: FINC_ERR_UNSUPPORTED (no mix instantiation for C; a
     "lead" whose channel count has one and runs the mix)."""

@@ -190,7 +190,7 @@ static int canonicalize(const T *w_stored, T *w_canon, int G, int Cq, int KH, in
 
 extern "C" {
 
-int finc_version(void) { return 120; }
+int finc_version(void) { return 121; }
 
 unsigned finc_build_flags(void)
 {
@@ -1172,6 +1172,64 @@ int finc_spline_reverse_backward_f32(const float *grad_y, const float *grad_logd
 {
     return spline_grad(FINC_GRAD_REV, grad_y, grad_logdet, x, table, P, K, tail_bound, grad_x, grad_table, B, C, HW, workspace, workspace_bytes,
                        stream);
+}
+
+// ---- the smooth invertible activations (finc_activation.h) ----
+int finc_activation_supported_f32(int kind) { return finc_activation_trips(kind) >= 0 ? 1 : 0; }
+int finc_debug_activation_trips(int kind) { return finc_activation_trips(kind); }
+
+size_t finc_activation_workspace_bytes(int B, int C, int HW)
+{
+    return pixel_counts_bad(B, C, HW, false) ? 256 : padded_ws_bytes(finc_activation_workspace_floats(B, C, HW) * sizeof(float));
+}
+
+// (C * HW * 4 >= 2^31 is the launcher's FINC_ERR_BAD_DIMS; judged here so that it comes before the alignment)
+static int activation_dims(int B, int C, int HW)
+{
+    if (int e = pixel_dims(B, C, HW, false)) return e;
+    return (size_t)C * HW * 4 >= ((size_t)1 << 31) ? FINC_ERR_BAD_DIMS : FINC_OK;
+}
+
+// the host's parameter checks: a > 0 (and b > 0 for the smooth tanh), finite; the slope pointer for the learnable kind and no other
+static bool activation_kind_bad(int kind, float p0, float p1, const float *slope_dev)
+{
+    if (!finc_activation_supported_f32(kind)) return true;
+    if (kind == FINC_ACT_LEARNABLE_LEAKY_RELU) return !slope_dev;
+    if (slope_dev || !(p0 > 0.f && p0 < INFINITY)) return true;
+    return kind == FINC_ACT_SMOOTH_TANH && !(p1 > 0.f && p1 < INFINITY);
+}
+
+int finc_activation_f32(int kind, float p0, float p1, const float *slope_dev, int direction, const float *x, float *y, float *logdet,
+                        int B, int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    if (!x || !y) return FINC_ERR_NULL_POINTER;
+    if (int e = activation_dims(B, C, HW)) return e;
+    if (direction != 1 && direction != -1) return FINC_ERR_BAD_DIMS;
+    if (misaligned(x, y, logdet, slope_dev)) return FINC_ERR_ALIGNMENT;
+    if (activation_kind_bad(kind, p0, p1, slope_dev)) return FINC_ERR_UNSUPPORTED;
+    if (logdet && workspace_short(workspace, workspace_bytes, finc_activation_workspace_bytes(B, C, HW))) return FINC_ERR_WORKSPACE;
+    if (int e = finc_fault_gate(false)) return e;
+    return finc_activation_launch(kind, p0, p1, slope_dev, direction, x, y, logdet, B, C, HW, (float *)workspace, (hipStream_t)stream);
+}
+
+// Every backward of the activations: `v` is the activation the mode reads (FincGradMode).  grad_x == grad_y and x_out == v are the two
+// allowed overlaps.
+int finc_activation_backward_f32(int kind, float p0, float p1, const float *slope_dev, int mode, const float *grad_y,
+                                 const float *grad_logdet, const float *v, float *x_out, float *grad_x, float *grad_slope, int B, int C,
+                                 int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream)
+{
+    if ((!grad_y && !grad_logdet) || !v || (!x_out && !grad_x && !grad_slope)) return FINC_ERR_NULL_POINTER;
+    if (int e = activation_dims(B, C, HW)) return e;
+    if (mode != FINC_GRAD_FWD && mode != FINC_GRAD_REV && mode != FINC_GRAD_REBUILD) return FINC_ERR_BAD_DIMS;
+    if (grad_x && grad_x == v) return FINC_ERR_BAD_DIMS;
+    if (x_out && (x_out == grad_y || x_out == grad_x)) return FINC_ERR_BAD_DIMS;
+    if (misaligned(grad_y, grad_logdet, v, x_out, grad_x, grad_slope, slope_dev)) return FINC_ERR_ALIGNMENT;
+    if (activation_kind_bad(kind, p0, p1, slope_dev)) return FINC_ERR_UNSUPPORTED;
+    if ((x_out && mode != FINC_GRAD_REBUILD) || (grad_slope && kind != FINC_ACT_LEARNABLE_LEAKY_RELU)) return FINC_ERR_UNSUPPORTED;
+    if (grad_slope && workspace_short(workspace, workspace_bytes, finc_activation_workspace_bytes(B, C, HW))) return FINC_ERR_WORKSPACE;
+    if (int e = finc_fault_gate(false)) return e;
+    return finc_activation_grad_launch(kind, p0, p1, slope_dev, (FincGradMode)mode, grad_y, grad_logdet, v, x_out, grad_x, grad_slope, B, C,
+                                       HW, (float *)workspace, (hipStream_t)stream);
 }
 
 int finc_debug_backward_variant(int B, int G, int Cq, int H, int W, int KH, int KW, int *info)

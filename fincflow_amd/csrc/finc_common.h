@@ -382,6 +382,17 @@ int finc_spline_launch(const float *x, const float *table, int P, int K, float t
                        int HW, float *ws, hipStream_t st);
 int finc_spline_grad_launch(FincGradMode mode, const float *gy, const float *gld, const float *x, const float *table, int P, int K, float tb,
                             float *gx, float *gt, int B, int C, int HW, float *ws, hipStream_t st);
+// ---- the smooth invertible activations (element-wise on [B][C * HW]): finc_activation.h, same object ----
+// kind: FincActivationKind; p0, p1 its parameters (a; a, b), `slope` the learnable kind's device pointer (nullptr otherwise); `ws` holds
+// finc_activation_workspace_floats floats (needed with logdet / gs only).  logdet[b]: the FORWARD map's log-det in either direction.
+// v of the grad launch: the forward's INPUT (FINC_GRAD_FWD), the reverse's OUTPUT (FINC_GRAD_REV) or the forward's OUTPUT
+// (FINC_GRAD_REBUILD, which also writes the rebuilt input xo); gy, gld, xo, gx, gs may be nullptr.
+size_t finc_activation_workspace_floats(int B, int C, int HW);
+int finc_activation_trips(int kind);
+int finc_activation_launch(int kind, float p0, float p1, const float *slope, int direction, const float *x, float *y, float *logdet, int B,
+                           int C, int HW, float *ws, hipStream_t st);
+int finc_activation_grad_launch(int kind, float p0, float p1, const float *slope, FincGradMode mode, const float *gy, const float *gld,
+                                const float *v, float *xo, float *gx, float *gs, int B, int C, int HW, float *ws, hipStream_t st);
 // ---- the image boundary (dequantise + normalise + logit + squeeze in one launch, and back): finc_image.h, same object ----
 // B, C, H, W: the IMAGE side; with (un)squeeze the other side is [B][4C][H/2][W/2].  `ws` holds finc_image_workspace_floats floats
 // (the encode always, the decode with logdet).  noise and the decode's logdet may be nullptr.

@@ -283,6 +283,7 @@ int finc_mix_launch(const float *in, const float *mat, const float *bias, float 
 #include "finc_image.h"
 #include "finc_actnorm.h"
 #include "finc_spline.h"
+#include "finc_activation.h"
 #include "finc_adjoint.h"
 #include "finc_plu.h"
 
@@ -334,6 +335,12 @@ int finc_pixel_plan_info(int rule, int family, int groups, int B, int C, int HW,
             if (!sp.Q) return FINC_ERR_BAD_DIMS;
             return put(1, CPL_THREADS, (long long)sp.blocks * sp.Q, sp.Q, (long long)B * CPL_THREADS, (long long)CPL_THREADS * sp.Q, sp.blocks,
                        0);
+        }
+        if (family == FINC_PIXEL_ACTIVATION) {                       // every activation launch: outer = B, items = C * HW / io
+            if (elem_bytes != 4) return FINC_ERR_BAD_DIMS;
+            const ActPlan ap = act_plan(B, C, HW, bits);
+            if (!ap.P) return FINC_ERR_BAD_DIMS;
+            return put(ap.wide ? 4 : 1, CPL_THREADS, (long long)B * ap.P, ap.P, ap.items, (long long)CPL_THREADS * ap.P, B, 0);
         }
         if (family != FINC_PIXEL_COUPLING_GRAD && family != FINC_PIXEL_ACTNORM_GRAD) return FINC_ERR_BAD_DIMS;
         if (family == FINC_PIXEL_COUPLING_GRAD && C % 2) return FINC_ERR_BAD_DIMS;

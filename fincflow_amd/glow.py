@@ -391,6 +391,266 @@ class SplineActivation(_DerivedValues, FlowLayer):
         return self.forward(input, context)[1]
 
 
+#: Newton trips of the smooth activations' bracketed inverse, here and in the kernels (finc_activation.h ACT_TRIPS): over the parameter
+#: box of DESIGN 3.26 the worst case is at its fp32 floor after 7, plus 2 of margin
+ACTIVATION_TRIPS = 9
+_FLT_MAX = 3.4028234663852886e38
+
+
+def bracketed_newton(t, f_and_prime, lo, hi, x, trips=ACTIVATION_TRIPS):
+    """`trips` Newton steps on f(x) = t from `x`, kept inside [lo, hi]: each trip shrinks the bracket on the sign of f(x) - t and
+    replaces a step that LEAVES it by the midpoint (a step onto an end is inside).  The same count for every element, written with
+    `torch.where`: no masks, no host synchronisation.  The arithmetic of finc_activation.h act_inverse."""
+    for _ in range(trips):
+        f, fp = f_and_prime(x)
+        r = f - t
+        hi = torch.where(r > 0, x, hi)
+        lo = torch.where(r < 0, x, lo)
+        xn = x - r / fp
+        x = torch.where((xn >= lo) & (xn <= hi), xn, lo + 0.5 * (hi - lo))
+    return x
+
+
+class _Activation(FlowLayer):
+    """What the four element-wise activations of layers/activations.py share: the dispatch of `SplineActivation` -- fp32 device
+    tensors of two or more dimensions run on the HIP activation kernels (`ops.finc_activation`; under autograd
+    `ops.activation_forward`, and for `reverse` / `reverse_with_logdet` inside `ops.reverse_grad()` `ops.activation_reverse` /
+    `ops.activation_reverse_logdet`); CPU tensors, float64 and `reverse` under autograd outside that context run the layer's PyTorch
+    lines (`_lines`).  `backward_from_output` is ONE launch (finc_activation_backward_f32, rebuild mode): the layer's input with the
+    bits `reverse` returns and the gradients taken there, so the layers join `FlowSequential.invertible_backward` runs.  The map stays
+    fp32 under autocast."""
+    kind = None
+
+    def _numbers(self):
+        """(p0, p1) of the entry points."""
+        return 0.0, 0.0
+
+    def _slope(self):
+        """The learnable kind's slope as a tensor of one element (recorded while a graph records); None otherwise."""
+        return None
+
+    def _lines(self, v, inverse):
+        """(out, log-derivative of the FORWARD map per element, at `v` or at the recovered input), differentiable."""
+        raise NotImplementedError
+
+    def _hip_device(self, x):
+        return x.is_cuda and x.dtype == torch.float32 and x.dim() >= 2 and _params_on_device(x, *self.parameters())
+
+    def _records_graph(self, x):
+        return _records_graph(x, *self.parameters())
+
+    def _hip_reverse_grad(self, x):
+        """`reverse` while autograd records inside `ops.reverse_grad()`: the HIP launch with a backward of its own."""
+        return ops.reverse_grad_enabled() and self._records_graph(x) and self._hip_device(x)
+
+    def _detached_slope(self):
+        with torch.no_grad():
+            return self._slope()
+
+    def forward(self, input, context=None):
+        if self._hip_device(input):
+            if self._records_graph(input):
+                return ops.activation_forward(input, self.kind, *self._numbers(), self._slope())
+            return ops.finc_activation(input.contiguous(), self.kind, *self._numbers(), self._detached_slope(), 1, True)
+        out, lad = self._lines(input, False)
+        return out, lad.flatten(start_dim=1).sum(dim=-1)
+
+    def reverse(self, input, context=None):
+        if self._hip_reverse_grad(input):
+            return ops.activation_reverse(input, self.kind, *self._numbers(), self._slope())
+        if self._hip_device(input) and not self._records_graph(input):
+            return ops.finc_activation(input.contiguous(), self.kind, *self._numbers(), self._detached_slope(), -1)[0]
+        return self._lines(input, True)[0]
+
+    def reverse_with_logdet(self, input, context=None):
+        """`reverse` and the forward log-det at its result from the same pass."""
+        if self._hip_reverse_grad(input):
+            return ops.activation_reverse_logdet(input, self.kind, *self._numbers(), self._slope())
+        if self._hip_device(input) and not self._records_graph(input):
+            return ops.finc_activation(input.contiguous(), self.kind, *self._numbers(), self._detached_slope(), -1, True)
+        out, lad = self._lines(input, True)
+        return out, lad.flatten(start_dim=1).sum(dim=-1)
+
+    def logdet(self, input, context=None):
+        return self.forward(input, context)[1]
+
+    def invertible_backward_supported(self, input, context=None):
+        return self._hip_device(input)
+
+    def backward_from_output(self, output, grad_output, grad_logdet, context, needs):
+        """ONE launch: x = f^-1(output) with the inverse kernel's arithmetic and the forward's gradients at that x."""
+        params, asked = _param_needs(self, needs)
+        x, gx, gs = ops.finc_activation_backward(grad_output.contiguous(), grad_logdet, output.contiguous(), self.kind, *self._numbers(),
+                                                 self._detached_slope(), "rebuild", need_x=needs.input, need_gx=needs.grad_input,
+                                                 need_gs=any(asked))
+        return x, gx, None, self._slope_chain(gs) if params else []
+
+    def _slope_chain(self, grad_slope):
+        return []
+
+
+def _positive(name, value):
+    value = float(value)
+    if not (0.0 < value < math.inf):
+        raise ValueError(f"{name} must be positive and finite, got {value}")
+    return value
+
+
+def _magnitude(x):
+    """|x| as a select: the values of `abs`, and the derivative +1 at 0 where autograd's `abs` has 0 -- the maps built on it are smooth
+    there, and their gradient at an input of exactly 0 is to be the analytic one."""
+    return torch.where(x < 0, -x, x)
+
+
+def _softplus_and_sigmoid(x):
+    """softplus as max(x, 0) + log1p(exp(-|x|)) and the sigmoid from the same exponential (the maximum as a select too: `clamp` hands
+    a gradient of 1 through at 0, and with |x|'s 0 beside it softplus'(0) would come out as 1 instead of 1/2)."""
+    e = torch.exp(-_magnitude(x))
+    return torch.where(x < 0, torch.zeros_like(x), x) + torch.log1p(e), torch.where(x >= 0, 1 / (1 + e), e / (1 + e))
+
+
+def _implicit_inverse(y, solve, f_and_prime):
+    """The result of `solve(y)` (no graph) with the derivative of an inverse function attached: dx/dy = 1 / f'(x), ONE f' at the
+    result instead of the unrolled iteration; the log-derivative is then taken at that x, so its gradient reaches y as L' / f'."""
+    with torch.no_grad():
+        x = solve(y.detach())
+        fp = f_and_prime(x)[1]
+    if y.requires_grad and torch.is_grad_enabled():
+        x = x + (y - y.detach()) / fp                        # (the value is x exactly: y - y.detach() is an exact zero)
+    lad = torch.log(f_and_prime(x)[1])
+    nan = torch.isnan(y)
+    return torch.where(nan, y, x), torch.where(nan, torch.zeros_like(lad), lad)
+
+
+class SmoothLeakyRelu(_Activation):
+    """layers/activations.py:36-54: f(x) = alpha x + (1 - alpha) softplus(x), the reference's constructor.  `reverse` is the bracketed
+    Newton iteration of `bracketed_newton` with ACTIVATION_TRIPS trips where the reference runs 100 unbracketed steps: x lies between
+    g^-1(y) and g^-1(y - (1 - alpha) ln 2), g the leaky ReLU of slope alpha, and the start is g^-1(y).  Accuracy is claimed at alpha
+    among 0.01, 0.1, 0.3, 0.9, 1.0, 1.5, the points the sweep of DESIGN 3.26 covers; elsewhere the result is finite and inside the bracket."""
+    kind = "smooth_leaky_relu"
+
+    def __init__(self, alpha=0.3):
+        super().__init__()
+        self.alpha = _positive("alpha", alpha)
+
+    def _numbers(self):
+        return self.alpha, 0.0
+
+    def _map(self, x):
+        a = self.alpha
+        sp, s = _softplus_and_sigmoid(x)
+        return a * x + (1 - a) * sp, a + (1 - a) * s
+
+    def _solve(self, y):
+        a = self.alpha
+        ginv = lambda v: torch.where(v < 0, v / a, v).clamp(-_FLT_MAX, _FLT_MAX)
+        g1, g2 = ginv(y), ginv(y - (1 - a) * math.log(2.0))
+        return bracketed_newton(y, self._map, torch.minimum(g1, g2), torch.maximum(g1, g2), g1)
+
+    def _lines(self, v, inverse):
+        with _fp32_maps(v):
+            if inverse:
+                return _implicit_inverse(v, self._solve, self._map)
+            f, fp = self._map(v)
+            lad = torch.log(fp)
+            return f, torch.where(torch.isnan(v), torch.zeros_like(lad), lad)
+
+
+class SmoothTanh(_Activation):
+    """layers/activations.py:108-123: f(x) = tanh(alpha x) + beta x, the reference's constructor; sech^2 is 4 e / (1 + e)^2 with
+    e = exp(-2 |alpha x|) (cosh overflows, 1 - tanh^2 cancels).  `reverse` is the bracketed Newton iteration on |y| (f is odd), between
+    max(|y| / (alpha + beta), (|y| - 1) / beta) and |y| / beta, from the lower end: the reference's unbracketed iteration cycles for
+    (alpha, beta) = (3, 0.05).  Accuracy is claimed at (alpha, beta) among (1, 0.1), (3, 0.05), (8, 0.01), (0.5, 1), (0.1, 0.01), the
+    points the sweep of DESIGN 3.26 covers; elsewhere, a finite bracketed value."""
+    kind = "smooth_tanh"
+
+    def __init__(self, alpha=1.0, beta=0.1):
+        super().__init__()
+        self.alpha = _positive("alpha", alpha)
+        self.beta = _positive("beta", beta)
+
+    def _numbers(self):
+        return self.alpha, self.beta
+
+    def _map(self, x):
+        a, b = self.alpha, self.beta
+        u = a * x
+        e = torch.exp(-2 * _magnitude(u))
+        t = (1 - e) / (1 + e)
+        return torch.where(u < 0, -t, t) + b * x, b + a * (4 * e / ((1 + e) * (1 + e)))
+
+    def _solve(self, y):
+        a, b = self.alpha, self.beta
+        t = y.abs()
+        hi = (t / b).clamp(max=_FLT_MAX)
+        lo = torch.minimum(torch.maximum(t / (a + b), (t - 1) / b), hi)
+        x = bracketed_newton(t, self._map, lo, hi, lo)
+        return torch.where(y < 0, -x, x)
+
+    def _lines(self, v, inverse):
+        with _fp32_maps(v):
+            if inverse:
+                return _implicit_inverse(v, self._solve, self._map)
+            f, fp = self._map(v)
+            lad = torch.log(fp)
+            return f, torch.where(torch.isnan(v), torch.zeros_like(lad), lad)
+
+
+def _leaky_lines(v, alpha, inverse):
+    """x < 0 ? alpha x : x and back (x < 0 strictly, as the reference compares), `alpha` a number or a tensor of one element.  The
+    unselected branch is computed at 0: a NaN carried through it would reach the slope's summed gradient as 0 * NaN."""
+    alpha = torch.as_tensor(alpha, dtype=v.dtype, device=v.device)
+    neg = v < 0
+    u = torch.where(neg, v, torch.zeros_like(v))
+    out = torch.where(neg, u / alpha if inverse else alpha * u, v)
+    return out, torch.where(neg, torch.log(alpha).expand_as(v), torch.zeros_like(v))
+
+
+class LeakyRelu(_Activation):
+    """layers/activations.py:57-79, the reference's constructor."""
+    kind = "leaky_relu"
+
+    def __init__(self, alpha=0.1):
+        super().__init__()
+        self.alpha = _positive("alpha", alpha)
+
+    def _numbers(self):
+        return self.alpha, 0.0
+
+    def _lines(self, v, inverse):
+        with _fp32_maps(v):
+            return _leaky_lines(v, self.alpha, inverse)
+
+
+class LearnableLeakyRelu(_Activation):
+    """layers/activations.py:82-105: the leaky ReLU with slope sigmoid(alpha_logit) + 0.5, the reference's parameter name, shape [1]
+    and initialisation.  `alpha_logit -> alpha` is one recorded, parameter-sized PyTorch line; the kernels read the slope from that
+    device tensor, so nothing goes to the host and the layer can be captured in a HIP graph.  The slope's gradient comes from the
+    backward launch (a fixed-order sum) and reaches `alpha_logit` through that line."""
+    kind = "learnable_leaky_relu"
+
+    def __init__(self):
+        super().__init__()
+        self.alpha_logit = nn.Parameter(torch.zeros([1]))
+
+    def get_alpha(self):
+        with _fp32_maps(self.alpha_logit):
+            return torch.sigmoid(self.alpha_logit) + .5
+
+    def _slope(self):
+        return self.get_alpha()
+
+    def _slope_chain(self, grad_slope):
+        if grad_slope is None:
+            return [None]
+        s = torch.sigmoid(self.alpha_logit.detach())
+        return [grad_slope.view_as(s) * s * (1 - s)]
+
+    def _lines(self, v, inverse):
+        with _fp32_maps(v):
+            return _leaky_lines(v, self.get_alpha(), inverse)
+
+
 class Conv1x1(_DerivedValues, FlowLayer):
     """layers/conv1x1.py:8-49.  Device tensors in fp32 with a channel count the library instantiates run on the HIP mixing
     kernel: inference / sampling (no autograd graph) as one streaming launch (`ops.finc_mix`), `forward` under autograd through

@@ -8,6 +8,7 @@ RuntimeError for non-device / non-contiguous tensors.  `finc_inverse` /
 chunk/cat copies: fastflow.py:78-100 collapses into one launch).
 """
 import contextlib
+import math
 import threading
 
 import torch
@@ -1373,6 +1374,179 @@ def spline_reverse(y, table, tail_bound):
 def spline_reverse_logdet(y, table, tail_bound):
     """`finc_spline(y, table, tail_bound, -1, want_logdet=True)` under autograd: (x, forward log-det at x)."""
     return _FincSplineReverseLogdetFunction.apply(y, table, tail_bound)
+
+
+#: include/finc.h FincActivationKind
+ACTIVATION_KINDS = {"smooth_leaky_relu": 0, "leaky_relu": 1, "learnable_leaky_relu": 2, "smooth_tanh": 3}
+#: include/finc.h finc_activation_backward_f32's `mode`
+ACTIVATION_MODES = {"forward": 0, "reverse": 1, "rebuild": 2}
+
+
+def activation_supported(kind):
+    """Does the library have the kernels of this kind (a name of ACTIVATION_KINDS)?"""
+    return kind in ACTIVATION_KINDS and bool(_lib.lib().finc_activation_supported_f32(ACTIVATION_KINDS[kind]))
+
+
+def activation_inverse_trips(kind):
+    """The fixed trip count of the kind's inverse on the device (0: the leaky kinds' select and division)."""
+    return int(_lib.lib().finc_debug_activation_trips(ACTIVATION_KINDS[kind]))
+
+
+def _activation_args(x, kind, p0, p1, slope, what="input"):
+    """The checks of every activation wrapper; returns (kind code, p0, p1, slope pointer, B, C, HW) as the entry points take them: a
+    tensor of two or more dimensions is [B, C, everything else], which the kernels walk as [B, C * HW]."""
+    _require_device(x, what)
+    if x.dim() < 2:
+        raise ValueError(f"expected {what} with a batch dimension and at least one more")
+    if kind not in ACTIVATION_KINDS:
+        raise ValueError(f"unknown activation kind {kind!r} (one of {sorted(ACTIVATION_KINDS)})")
+    if kind == "learnable_leaky_relu":
+        if slope is None:
+            raise ValueError("the learnable kind reads its slope from a device tensor of one element")
+        _require_device(slope, "slope")
+        if slope.numel() != 1 or slope.device != x.device:
+            raise ValueError("slope must hold one element, on the activations' device")
+    else:
+        if slope is not None:
+            raise ValueError(f"{kind} takes its parameters as numbers, not a slope tensor")
+        bad = [p for p in ((p0, p1) if kind == "smooth_tanh" else (p0,)) if not (0.0 < float(p) < math.inf)]
+        if bad:
+            raise ValueError(f"{kind}: parameters must be positive and finite, got {bad}")
+    hw = 1
+    for d in x.shape[2:]:
+        hw *= d
+    return ACTIVATION_KINDS[kind], float(p0), float(p1), _ptr(slope), x.shape[0], x.shape[1], hw
+
+
+def finc_activation(x, kind, p0=0.0, p1=0.0, slope=None, direction=1, want_logdet=False, out=None):
+    """One of the smooth invertible activations (layers/activations.py SmoothLeakyRelu, LeakyRelu, LearnableLeakyRelu, SmoothTanh) as one
+    streaming HIP launch (include/finc.h: finc_activation_f32): direction +1 the map, -1 its inverse -- for the two smooth kinds a
+    bracketed Newton iteration with a fixed trip count, in registers.  `kind`: a name of ACTIVATION_KINDS; `p0`, `p1`: its parameters
+    (alpha; alpha, beta); `slope`: the learnable kind's slope as a device tensor of one element (no host synchronisation).  Returns
+    (y, logdet): logdet [B], when `want_logdet`, is the FORWARD map's log-det in either direction (in direction -1 at the recovered
+    input), summed in a fixed order by a second small launch.  `out` may be `x`.  Nothing is recorded for autograd."""
+    code, p0, p1, sp, B, C, HW = _activation_args(x, kind, p0, p1, slope)
+    if direction not in (1, -1):
+        raise ValueError("direction must be +1 (forward) or -1 (reverse)")
+    out = _out_like(x, out)
+    want_logdet = bool(want_logdet)
+    if x.numel() == 0:
+        return out, (torch.zeros(B, dtype=torch.float32, device=x.device) if want_logdet else None)
+    logdet = torch.empty(B, dtype=torch.float32, device=x.device) if want_logdet else None
+    nbytes = _lib.lib().finc_activation_workspace_bytes(B, C, HW) if want_logdet else None
+    _call("finc_activation_f32", x.device, code, p0, p1, sp, direction, x.data_ptr(), out.data_ptr(), _ptr(logdet), B, C, HW,
+          *_ws_args(x.device, nbytes), _stream_ptr(x))
+    return out, logdet
+
+
+def finc_activation_backward(grad_y, grad_logdet, v, kind, p0=0.0, p1=0.0, slope=None, mode="forward", need_x=False, need_gx=True,
+                             need_gs=False, out=None):
+    """Every backward of the activations (include/finc.h: finc_activation_backward_f32), by `mode`: "forward" from the forward's INPUT,
+    "reverse" of direction -1 from its OUTPUT (grad_y: the gradient that reaches that output), "rebuild" from the forward's OUTPUT,
+    which also returns the rebuilt input (`need_x`) with the bits direction -1 gives.  Returns (x, grad_input, grad_slope), each
+    computed only if asked for (None otherwise); grad_slope [1] belongs to the learnable kind.  grad_y or grad_logdet may be None
+    (zeros), not both.  `out`: where grad_input goes (it may be `grad_y`).  Fixed-order sums: the same inputs give the same bits."""
+    code, p0, p1, sp, B, C, HW = _activation_args(v, kind, p0, p1, slope, "activation")
+    if mode not in ACTIVATION_MODES:
+        raise ValueError(f"mode must be one of {sorted(ACTIVATION_MODES)}")
+    if need_x and mode != "rebuild":
+        raise ValueError("only the rebuild mode returns the input")
+    if need_gs and kind != "learnable_leaky_relu":
+        raise ValueError("only the learnable kind has a slope gradient")
+    if grad_y is None and grad_logdet is None:
+        raise ValueError("grad_output and grad_logdet are both absent")
+    if grad_y is not None:
+        _require_device(grad_y, "grad_output")
+        if grad_y.shape != v.shape or grad_y.device != v.device:
+            raise ValueError("grad_output must match the activation in shape and device")
+    _per_image(grad_logdet, "grad_logdet", v)
+    gs = torch.empty(1, dtype=torch.float32, device=v.device) if need_gs else None
+    outs = (torch.empty_like(v) if need_x else None, _out_like(v, out) if need_gx else None, gs)
+    if _nothing_to_launch(v, outs, (gs,)):
+        return outs
+    nbytes = _lib.lib().finc_activation_workspace_bytes(B, C, HW) if need_gs else None
+    _call("finc_activation_backward_f32", v.device, code, p0, p1, sp, ACTIVATION_MODES[mode], _ptr(grad_y), _ptr(grad_logdet), v.data_ptr(),
+          *map(_ptr, outs), B, C, HW, *_ws_args(v.device, nbytes), _stream_ptr(v))
+    return outs
+
+
+def _activation_backward(ctx, mode, grad_y, grad_logdet):
+    v, slope = ctx.saved_tensors if ctx.has_slope else (*ctx.saved_tensors, None)
+    need = ctx.needs_input_grad
+    _, gx, gs = finc_activation_backward(grad_y, grad_logdet, v, ctx.kind, ctx.p0, ctx.p1, slope, mode, need_gx=need[0],
+                                         need_gs=ctx.has_slope and need[1])
+    return gx, (gs.view(ctx.slope_shape) if gs is not None else None), None, None, None
+
+
+def _activation_record(ctx, saved, slope, kind, p0, p1):
+    ctx.has_slope = slope is not None
+    ctx.slope_shape = slope.shape if slope is not None else None
+    ctx.save_for_backward(*((saved, slope) if slope is not None else (saved,)))
+    ctx.kind, ctx.p0, ctx.p1 = kind, p0, p1
+
+
+class _FincActivationFunction(torch.autograd.Function):
+    """`finc_activation` in the forward direction under autograd: (y, logdet) and their backward on the HIP kernel, from the saved input."""
+
+    @staticmethod
+    def forward(ctx, x, slope, kind, p0, p1):
+        x = x.contiguous()
+        slope = slope.contiguous() if slope is not None else None
+        y, logdet = finc_activation(x, kind, p0, p1, slope, 1, True)
+        _activation_record(ctx, x, slope, kind, p0, p1)
+        return y, logdet
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y, grad_logdet):
+        return _activation_backward(ctx, "forward", *_incoming_grads(ctx.saved_tensors[0], grad_y, grad_logdet))
+
+
+class _FincActivationReverseFunction(torch.autograd.Function):
+    """`finc_activation` in the reverse direction under autograd (inside `reverse_grad()`), saved: its OUTPUT."""
+
+    @staticmethod
+    def forward(ctx, y, slope, kind, p0, p1):
+        slope = slope.contiguous() if slope is not None else None
+        x = finc_activation(y.contiguous(), kind, p0, p1, slope, -1)[0]
+        _activation_record(ctx, x, slope, kind, p0, p1)
+        return x
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_x):
+        return _activation_backward(ctx, "reverse", grad_x.contiguous(), None)
+
+
+class _FincActivationReverseLogdetFunction(torch.autograd.Function):
+    """The reverse with the forward log-det at its result, one pass; saved: its output x."""
+
+    @staticmethod
+    def forward(ctx, y, slope, kind, p0, p1):
+        slope = slope.contiguous() if slope is not None else None
+        x, logdet = finc_activation(y.contiguous(), kind, p0, p1, slope, -1, True)
+        _activation_record(ctx, x, slope, kind, p0, p1)
+        return x, logdet
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_x, grad_logdet):
+        return _activation_backward(ctx, "reverse", *_incoming_grads(ctx.saved_tensors[0], grad_x, grad_logdet))
+
+
+def activation_forward(x, kind, p0=0.0, p1=0.0, slope=None):
+    """`finc_activation(x, ..., +1, want_logdet=True)` under autograd: (y, logdet), gradients for `x` and `slope`."""
+    return _FincActivationFunction.apply(x, slope, kind, p0, p1)
+
+
+def activation_reverse(y, kind, p0=0.0, p1=0.0, slope=None):
+    """`finc_activation(y, ..., -1)[0]` under autograd: gradients for `y` and `slope`."""
+    return _FincActivationReverseFunction.apply(y, slope, kind, p0, p1)
+
+
+def activation_reverse_logdet(y, kind, p0=0.0, p1=0.0, slope=None):
+    """`finc_activation(y, ..., -1, want_logdet=True)` under autograd: (x, forward log-det at x)."""
+    return _FincActivationReverseLogdetFunction.apply(y, slope, kind, p0, p1)
 
 
 def inverse(input, kernel, output):

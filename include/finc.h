@@ -676,6 +676,57 @@ int finc_spline_reverse_backward_f32(const float *grad_y, const float *grad_logd
                                      size_t workspace_bytes, finc_stream_t stream);
 
 /*
+ * The smooth invertible activations (version 121; layers/activations.py SmoothLeakyRelu :36-54, LeakyRelu :57-79, LearnableLeakyRelu
+ * :82-105, SmoothTanh :108-123): element-wise maps on activations [B][C][HW] fp32, which the kernels walk as [B][C * HW].  With x the
+ * forward's input, f the forward map and L = log f':
+ *   FINC_ACT_SMOOTH_LEAKY_RELU (p0 = a)          f = a x + (1 - a) softplus(x),  f' = a + (1 - a) sigmoid(x)
+ *   FINC_ACT_LEAKY_RELU (p0 = a)                 f = x < 0 ? a x : x,            f' = x < 0 ? a : 1   (x < 0 strictly, as the reference)
+ *   FINC_ACT_LEARNABLE_LEAKY_RELU                the same with a = *slope_dev, a DEVICE pointer (no host round trip); p0, p1 ignored
+ *   FINC_ACT_SMOOTH_TANH (p0 = a, p1 = b)        f = tanh(a x) + b x,            f' = b + a sech^2(a x)
+ * A NaN passes through with log-derivative 0.  finc_activation_supported_f32: 1 for these four kinds, 0 otherwise.
+ * finc_activation_f32: direction +1 is f, direction -1 its inverse -- a select and a division for the leaky kinds; for the smooth kinds
+ *   a Newton iteration inside an analytic bracket with a FIXED trip count (finc_debug_activation_trips; a step that leaves the
+ *   bracket is replaced by the midpoint), so every finite y gives a finite x inside the bracket, where the reference's 100 unbracketed
+ *   steps cycle for SmoothTanh(3, 0.05).  Accuracy is claimed AT the parameters the sweep of DESIGN 3.26 covers -- a among 0.01, 0.1,
+ *   0.3, 0.9, 1.0, 1.5 (smooth leaky ReLU), (a, b) among (1, 0.1), (3, 0.05), (8, 0.01), (0.5, 1), (0.1, 0.01) (smooth tanh) -- and
+ *   nowhere between or beyond them: there the result is bracketed and finite, no more.  `logdet` [B]
+ *   (optional; needs the workspace): in EITHER direction the FORWARD map's log-det per image, in direction -1 at the recovered input,
+ *   summed in a fixed order that does not depend on the batch size -- the same inputs give the same bits, and y has the same bits
+ *   with and without it.  y == x is allowed.
+ * finc_activation_backward_f32: every backward, by `mode` (0 forward, 1 reverse, 2 rebuild):
+ *   0  from v = the forward's INPUT x:   grad_x = grad_y f'(x) + grad_logdet[b] L'(x);
+ *   1  of direction -1, from v = its OUTPUT x (grad_y here is the gradient that reaches that output, grad_logdet that of the log-det
+ *      the call returned):   grad_x (the gradient of the reverse's input) = (grad_y + grad_logdet[b] L'(x)) / f'(x);
+ *   2  from v = the forward's OUTPUT y: x = f^-1(y) with the bits direction -1 returns, written to x_out when given, and the mode-0
+ *      gradients at that x in the same launch.
+ *   grad_y, grad_logdet may be NULL (zeros), not both; x_out (mode 2 only), grad_x, grad_slope may be NULL, not all.  grad_slope [1]
+ *   (the learnable kind only; needs the workspace): the slope's gradient, a fixed-order sum.  grad_x == grad_y and x_out == v are
+ *   allowed; grad_x == v, x_out == grad_y and x_out == grad_x are FINC_ERR_BAD_DIMS.
+ * Thread items are 16-byte pieces of four when C * HW % 4 == 0 (whatever HW is) and every activation pointer is 16-byte aligned, single
+ * elements otherwise.
+ * Refusal order: NULL -> dims (non-positive or overflowing, a direction other than +1 / -1, an unknown mode, forbidden aliasing)
+ * FINC_ERR_BAD_DIMS -> a pointer not 4-byte aligned FINC_ERR_ALIGNMENT -> an unknown kind, a parameter that is not positive and finite,
+ * a slope_dev that is missing for the learnable kind or given for another, x_out outside mode 2, grad_slope for another kind
+ * FINC_ERR_UNSUPPORTED -> a missing / short workspace where one is needed FINC_ERR_WORKSPACE -> the sticky-fault rule below.
+ */
+typedef enum {
+    FINC_ACT_SMOOTH_LEAKY_RELU = 0,
+    FINC_ACT_LEAKY_RELU = 1,
+    FINC_ACT_LEARNABLE_LEAKY_RELU = 2,
+    FINC_ACT_SMOOTH_TANH = 3
+} FincActivationKind;
+int finc_activation_supported_f32(int kind);
+/* Introspection (tests; no reference counterpart): the fixed trip count of the kind's inverse as the kernels were compiled, 0 for
+ * the leaky kinds, -1 for an unknown kind.  Host-only. */
+int finc_debug_activation_trips(int kind);
+size_t finc_activation_workspace_bytes(int B, int C, int HW);
+int finc_activation_f32(int kind, float p0, float p1, const float *slope_dev, int direction, const float *x, float *y, float *logdet,
+                        int B, int C, int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream);
+int finc_activation_backward_f32(int kind, float p0, float p1, const float *slope_dev, int mode, const float *grad_y,
+                                 const float *grad_logdet, const float *v, float *x_out, float *grad_x, float *grad_slope, int B, int C,
+                                 int HW, void *workspace, size_t workspace_bytes, finc_stream_t stream);
+
+/*
  * The image boundary (version 115; layers/dequantize.py, layers/normalize.py, layers/transforms.py:6-19, layers/squeeze.py:5-41): what
  * every model starts with -- Dequantization, Normalization(s), LogitTransform, Squeeze -- as ONE streaming launch per direction.
  * B, C, H, W describe the IMAGE side in every call; with squeeze / unsqueeze = 1 the other side is [B][4C][H/2][W/2] in the
@@ -791,10 +842,12 @@ typedef enum {
     FINC_PIXEL_TRANSFORM = 0,     /* outer = B: every coupling, split and merge transform, with or without the log-det */
     FINC_PIXEL_COUPLING_GRAD = 1, /* outer = C / 2 channel pairs: every backward of the coupling and the splits */
     FINC_PIXEL_ACTNORM_GRAD = 2,  /* outer = C channels: ActNorm's backwards and finc_actnorm_init_f32 */
-    FINC_PIXEL_SPLINE = 4         /* (version 120; 3 stays FINC_ERR_BAD_DIMS, the unknown family that callers written against 119
+    FINC_PIXEL_SPLINE = 4,        /* (version 120; 3 stays FINC_ERR_BAD_DIMS, the unknown family that callers written against 119
                                      probe with) outer = ceil(C * HW / 256) blocks of positions: every spline call, transform and
                                      backward, P = 1 and P = C * HW alike; items = 256 * B (a lane walks the images b = q, q + Q, ...),
                                      io = 1 (dwords) whatever the alignment */
+    FINC_PIXEL_ACTIVATION = 5     /* (version 121) outer = B: every call of the smooth invertible activations, transform and backward;
+                                     items = C * HW / io, io = 4 when C * HW % 4 == 0 (whatever HW is) and `align` is 16, else 1 */
 } FincPixelFamily;
 /* What a per-pixel call on [B][C][HW] would launch when every activation pointer it takes is aligned to `align` bytes (4, 8 or 16)
  * and no better, answered by the functions the launchers themselves call; launches nothing.  `elem_bytes`: 4, or 2 for the calls on
